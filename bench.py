@@ -29,6 +29,8 @@ HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6
 PRE_WARM_SECONDS = 0.25     # the same step, untimed, before the W warm-up steps (see main)
 LOG_FLOP_EQUIV = 20         # flop-equivalents per log
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 0
 
 
 # which arithmetic carries which contract (tests named are in the -m gpu suite)
@@ -71,7 +73,14 @@ def parse_args():
     ap.add_argument("--sampler-long-iterations", type=int, default=100000,
                     help="one more such run at the reference's own settings (data/configuration/mcmc_settings.txt: 100 000 "
                          "iterations, burn-in 5 000, adaptation_period 100, thinning 100): about a minute (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loglik, status, n_accept, n_reject of "
+                         "every chain, all ranks in rank order, and the chain index) as DIR/<name>.npy in float64; "
+                         "above %d MB in all, a fixed seeded sample of the chains" % (DUMP_LIMIT_BYTES >> 20))
+    args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
 
 
 def algorithmic_flops_per_eval(n, accepted_steps, t_obs):
@@ -160,6 +169,21 @@ def cpu_baseline(pb, theta, budget_s):
         "single_thread_value": n1 / dt1,
         "cpu_model": cpu_model(), "nproc": os.cpu_count(), "omp_max_threads": oracle_py.load().oracle_num_threads(),
     }
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: `outputs` maps name -> one value per chain (global chain order).  Written as float64 .npy files next to
+    chain.npy, the global chain index of every row; a larger result is cut to a fixed seeded sample of chains (sorted)."""
+    n = len(next(iter(outputs.values())))
+    chain = np.arange(n)
+    per_chain = 8 * (len(outputs) + 1)
+    budget = DUMP_LIMIT_BYTES - 4096  # the .npy headers
+    if n * per_chain > budget:
+        chain = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, budget // per_chain, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "chain.npy"), chain.astype(np.float64))
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a)[chain].astype(np.float64))
 
 
 def sampler_pipeline(mm, pb, theta, iterations=None, long_iterations=0, step_ms=None):
@@ -441,6 +465,9 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     step_ms = ev0.elapsed_time(ev1) / max(K, 1)
+    # --dump-outputs: what the last timed step returned, copied before the passes below reuse the buffers
+    last_step = ({"loglik": d_ll.clone(), "status": d_status.clone(), "n_accept": d_acc.clone(), "n_reject": d_rej.clone()}
+                 if args.dump_outputs is not None else None)
     # The dominant kernel's own duration: a SECOND pass of the same K steps, outside the timed region, with HIP events
     # on the launch stream around the integrator kernel and the likelihood pass of EVERY launch (the records cost ~15 us of
     # stream time per launch, which is why they are not in the timed pass: the kernel time is what they bracket, not
@@ -514,6 +541,16 @@ def main():
         owners = gathered[:, 2 * P + 1].reshape(world, B)
         allgather_check = bool(torch.equal(owners, torch.arange(world, dtype=torch.float64, device=rec.device)[:, None].expand(world, B))
                                and torch.equal(gathered[rank * B:(rank + 1) * B], rec))
+
+    if last_step is not None:
+        mine = {k: v.cpu().numpy() for k, v in last_step.items()}
+        shards = [mine]
+        if world > 1:
+            shards = [None] * world
+            dist.all_gather_object(shards, mine)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {k: np.concatenate([sh[k] for sh in shards]) for k in mine})
+        del last_step
 
     if rank == 0:
         evals_total = world * B * K

@@ -77,9 +77,10 @@ def build_listings():
     """fresh listings of the two translation units that carry inline-asm DPP instructions"""
     csrc = os.path.join(ROOT, "mathematical-modeling-of-infectious-diseases-v1_amd", "csrc")
     outs = []
+    tmp = tempfile.mkdtemp(prefix="dpp_")  # private to this call: a listing another user or run left behind is never reused
     for src, extra, name in (("sepaihrd_kernels.hip", ["-DSEPAIHRD_ARITH_FMA=1"], "sepaihrd_kernels_fma.s"),
                              ("sepaihrd_kernels_f32.hip", [], "sepaihrd_kernels_f32.s")):
-        out = os.path.join(tempfile.gettempdir(), name)
+        out = os.path.join(tmp, name)
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + os.path.join(ROOT, "include"),
                         "-I" + csrc, "-ffp-contract=fast", *extra, "-S", "--cuda-device-only", os.path.join(csrc, src), "-o", out],
                        check=True, capture_output=True)

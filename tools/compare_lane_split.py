@@ -2,7 +2,7 @@
 """The same chains through both forms of the fp64 integrator (sepaihrd_set_integrator_form), every output array compared bit for bit;
 with tools/libsepaihrd_hip_experiments.so present also through its one-wavefront-per-chain kernel.
 usage: compare_lane_split.py [--solver 0|1] [--chains N]"""
-import argparse, json, os, subprocess, sys
+import argparse, json, os, subprocess, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -92,7 +92,7 @@ if __name__ == "__main__":
     # the one-wavefront-per-chain kernel exists in the experiment build only (csrc/Makefile `experiments`)
     exp_lib = os.path.join(ROOT, "tools", "libsepaihrd_hip_experiments.so")
     if a.arith == "fma" and os.path.exists(exp_lib):
-        out = "/tmp/lane_split_wave_chain.npz"
+        out = os.path.join(tempfile.mkdtemp(prefix="lane_split_"), "wave_chain.npz")  # private to this run
         env = dict(os.environ, SEPAIHRD_HIP_LIB=exp_lib, SEPAIHRD_WAVE_CHAIN="2")
         subprocess.run([sys.executable, __file__, "--solver", str(a.solver), "--chains", str(a.chains), "--out", out, "--problem", a.problem, "--arith", a.arith, "--fuzz", str(a.fuzz), "--fuzz-cases", str(a.fuzz_cases),
                         "--one-step", str(a.one_step)],
