@@ -76,6 +76,8 @@ extern "C" {
 /* solver: the dynamic type of the reference's IOdeSolverStrategy */
 #define SEPAIHRD_SOLVER_DOPRI5 0      /* Dopri5SolverStrategy  */
 #define SEPAIHRD_SOLVER_CASH_KARP54 1 /* CashKarpSolverStrategy */
+#define SEPAIHRD_SOLVER_FEHLBERG78 2  /* FehlbergSolverStrategy: controlled runge_kutta_fehlberg78 (one lane per
+                                         (chain, age class) only: no QUAD form, no F32 precision) */
 
 /* constraint mode: SEPAIHRDParameterManager.hpp ConstraintMode */
 #define SEPAIHRD_CONSTRAINT_CLAMP 0   /* OPTIMIZATION_CLAMP */
@@ -90,7 +92,7 @@ extern "C" {
  * the log-likelihood (terms, log, sums), time and theta stay fp64, and the cumulative compartments the likelihood
  * differences (D, CumH, CumICU; also R) are integrated as per-output-interval fp32 accumulators folded into fp64
  * totals, so that a day's increment keeps full fp32 relative precision.  Accuracy vs F64 per tolerance: DESIGN.md 6.
- * 3 to 16 age classes; no ensemble summaries in F32. */
+ * 3 to 16 age classes; no ensemble summaries in F32; Dopri5 and Cash-Karp only (Fehlberg 7(8): SEPAIHRD_E_UNSUPPORTED). */
 #define SEPAIHRD_PRECISION_F64 0
 #define SEPAIHRD_PRECISION_F32 1
 
@@ -191,7 +193,8 @@ int sepaihrd_set_precision(sepaihrd_ctx *ctx, int precision);
  * 3 or 4 age classes sixteen lanes integrate a chain (a quad of lanes per age class, so that a batch too small to fill
  * the chip spreads over four times as many SIMDs), beyond that one lane per (chain, age class).  Both forms round every
  * operation alike: log-likelihood, status, step counts and trajectories are the same bits, and the parity suite proves it
- * by forcing each form on the same chains.  QUAD on other age counts: SEPAIHRD_E_UNSUPPORTED. */
+ * by forcing each form on the same chains.  QUAD on other age counts or with the Fehlberg 7(8) solver (which AUTO never
+ * runs in the QUAD form): SEPAIHRD_E_UNSUPPORTED. */
 #define SEPAIHRD_FORM_AUTO 0
 #define SEPAIHRD_FORM_LANE_PER_AGE 1
 #define SEPAIHRD_FORM_QUAD 2

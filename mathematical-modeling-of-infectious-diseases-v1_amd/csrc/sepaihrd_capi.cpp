@@ -278,7 +278,8 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
         (pb->n_obs > 0 && (!pb->obs_H || !pb->obs_ICU || !pb->obs_D))) {
         set_err(err, errlen, "a required array pointer is NULL"); return nullptr;
     }
-    if (pb->solver != SEPAIHRD_SOLVER_DOPRI5 && pb->solver != SEPAIHRD_SOLVER_CASH_KARP54) {
+    if (pb->solver != SEPAIHRD_SOLVER_DOPRI5 && pb->solver != SEPAIHRD_SOLVER_CASH_KARP54 &&
+        pb->solver != SEPAIHRD_SOLVER_FEHLBERG78) {
         set_err(err, errlen, "unknown solver"); return nullptr;
     }
     // Simulator::run grid validation (Simulator.cpp:78-88) and ctor checks (:15-44)
@@ -325,6 +326,9 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
     }
     if (pb->precision == SEPAIHRD_PRECISION_F32 && lanes_per_chain(n) < 4) {
         set_err(err, errlen, "the fp32-state arm is built for 3 to 16 age classes"); delete ctx; return nullptr;
+    }
+    if (pb->precision == SEPAIHRD_PRECISION_F32 && pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) {
+        set_err(err, errlen, "the fp32-state arm is built for Dopri5 and Cash-Karp only"); delete ctx; return nullptr;
     }
     ctx->precision = pb->precision;
     ctx->n = n; ctx->T = T; ctx->P = P;
@@ -521,6 +525,10 @@ int sepaihrd_set_precision(sepaihrd_ctx* ctx, int precision) {
         ctx->last_error = "the fp32-state arm is built for 3 to 16 age classes";
         return SEPAIHRD_E_UNSUPPORTED;
     }
+    if (precision == SEPAIHRD_PRECISION_F32 && ctx->solver == SEPAIHRD_SOLVER_FEHLBERG78) {
+        ctx->last_error = "the fp32-state arm is built for Dopri5 and Cash-Karp only";
+        return SEPAIHRD_E_UNSUPPORTED;
+    }
     ctx->precision = precision;
     return SEPAIHRD_OK;
 }
@@ -701,6 +709,10 @@ int sepaihrd_set_integrator_form(sepaihrd_ctx* ctx, int form) {
     if (!ctx || form < SEPAIHRD_FORM_AUTO || form > SEPAIHRD_FORM_QUAD) return SEPAIHRD_E_INVALID_ARG;
     if (form == SEPAIHRD_FORM_QUAD && ctx->dp.lpc != 4) {
         ctx->last_error = "set_integrator_form: the sixteen-lanes-per-chain form exists for problems of 3 or 4 age classes";
+        return SEPAIHRD_E_UNSUPPORTED;
+    }
+    if (form == SEPAIHRD_FORM_QUAD && ctx->solver == SEPAIHRD_SOLVER_FEHLBERG78) {
+        ctx->last_error = "set_integrator_form: the sixteen-lanes-per-chain form is not built for the Fehlberg 7(8) solver";
         return SEPAIHRD_E_UNSUPPORTED;
     }
     ctx->dp.form = form;

@@ -187,6 +187,29 @@ constexpr double b1 = 37.0 / 378, b3 = 250.0 / 621, b4 = 125.0 / 594, b6 = 512.0
 constexpr double db1 = 37.0 / 378 - 2825.0 / 27648, db3 = 250.0 / 621 - 18575.0 / 48384,
                  db4 = 125.0 / 594 - 13525.0 / 55296, db5 = -277.0 / 14336, db6 = 512.0 / 1771 - 1.0 / 4;
 }  // namespace ck
+// runge_kutta_fehlberg78 (Fehlberg 1968): every coefficient one quotient of two integers, rounded once.  Zero entries
+// are left out.  The error weights db_i = b_i - bhat_i are exact (+-41/840 at stages 1, 11, 12, 13; zero elsewhere).
+namespace f78 {
+constexpr double c2 = 2.0 / 27, c3 = 1.0 / 9, c4 = 1.0 / 6, c5 = 5.0 / 12, c6 = 1.0 / 2, c7 = 5.0 / 6, c8 = 1.0 / 6,
+                 c9 = 2.0 / 3, c10 = 1.0 / 3, c11 = 1.0 / 1, c13 = 1.0 / 1;
+constexpr double a2_1 = 2.0 / 27;
+constexpr double a3_1 = 1.0 / 36, a3_2 = 1.0 / 12;
+constexpr double a4_1 = 1.0 / 24, a4_3 = 1.0 / 8;
+constexpr double a5_1 = 5.0 / 12, a5_3 = -25.0 / 16, a5_4 = 25.0 / 16;
+constexpr double a6_1 = 1.0 / 20, a6_4 = 1.0 / 4, a6_5 = 1.0 / 5;
+constexpr double a7_1 = -25.0 / 108, a7_4 = 125.0 / 108, a7_5 = -65.0 / 27, a7_6 = 125.0 / 54;
+constexpr double a8_1 = 31.0 / 300, a8_5 = 61.0 / 225, a8_6 = -2.0 / 9, a8_7 = 13.0 / 900;
+constexpr double a9_1 = 2.0 / 1, a9_4 = -53.0 / 6, a9_5 = 704.0 / 45, a9_6 = -107.0 / 9, a9_7 = 67.0 / 90, a9_8 = 3.0 / 1;
+constexpr double a10_1 = -91.0 / 108, a10_4 = 23.0 / 108, a10_5 = -976.0 / 135, a10_6 = 311.0 / 54, a10_7 = -19.0 / 60,
+                 a10_8 = 17.0 / 6, a10_9 = -1.0 / 12;
+constexpr double a11_1 = 2383.0 / 4100, a11_4 = -341.0 / 164, a11_5 = 4496.0 / 1025, a11_6 = -301.0 / 82, a11_7 = 2133.0 / 4100,
+                 a11_8 = 45.0 / 82, a11_9 = 45.0 / 164, a11_10 = 18.0 / 41;
+constexpr double a12_1 = 3.0 / 205, a12_6 = -6.0 / 41, a12_7 = -3.0 / 205, a12_8 = -3.0 / 41, a12_9 = 3.0 / 41, a12_10 = 6.0 / 41;
+constexpr double a13_1 = -1777.0 / 4100, a13_4 = -341.0 / 164, a13_5 = 4496.0 / 1025, a13_6 = -289.0 / 82, a13_7 = 2193.0 / 4100,
+                 a13_8 = 51.0 / 82, a13_9 = 33.0 / 164, a13_10 = 12.0 / 41, a13_12 = 1.0 / 1;
+constexpr double b6 = 34.0 / 105, b7 = 9.0 / 35, b8 = 9.0 / 35, b9 = 9.0 / 280, b10 = 9.0 / 280, b12 = 41.0 / 840, b13 = 41.0 / 840;
+constexpr double db1 = -41.0 / 840, db11 = -41.0 / 840, db12 = 41.0 / 840, db13 = 41.0 / 840;
+}  // namespace f78
 
 // SEPAIHRDParameterManager.cpp:302-313 / :326-343
 __device__ __forceinline__ double reflect_bound(double value, double minb, double maxb) {

@@ -653,8 +653,10 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
     const double eps_abs = pb.abs_tol, eps_rel = pb.rel_tol;
 #if SEPAIHRD_ARITH_FMA
     // sixteen lanes per chain = one DPP row per chain: the stage coefficients come as row broadcasts (see QUAD_COEF)
-    constexpr bool ROW_COEF = (LPC == 16);
-    const double coefA = ROW_COEF ? QUAD_COEF[SOLVER][0][lane & 15] : 0.0, coefB = ROW_COEF ? QUAD_COEF[SOLVER][1][lane & 15] : 0.0;
+    // (not the Fehlberg 7(8) stepper: its stage sums are written out term by term in every lane count)
+    constexpr bool ROW_COEF = (LPC == 16 && SOLVER != 2);
+    constexpr int QC = SOLVER == 2 ? 0 : SOLVER;
+    const double coefA = ROW_COEF ? QUAD_COEF[QC][0][lane & 15] : 0.0, coefB = ROW_COEF ? QUAD_COEF[QC][1][lane & 15] : 0.0;
 #endif
 
 #ifdef SEPAIHRD_STAMPS
@@ -677,8 +679,15 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
 #endif
 
         // stage times and beta*kappa at those times
-        double tau[7], bks[7];
-        if (SOLVER == 0) {
+        constexpr int NST = SOLVER == 2 ? 13 : 7;
+        double tau[NST], bks[NST];
+        if constexpr (SOLVER == 2) {
+            // generic_rk calculate_stage: t + c_i dt (c_12 = 0)
+            tau[0] = t;
+            tau[1] = t + f78::c2 * cur; tau[2] = t + f78::c3 * cur; tau[3] = t + f78::c4 * cur; tau[4] = t + f78::c5 * cur;
+            tau[5] = t + f78::c6 * cur; tau[6] = t + f78::c7 * cur; tau[7] = t + f78::c8 * cur; tau[8] = t + f78::c9 * cur;
+            tau[9] = t + f78::c10 * cur; tau[10] = t + f78::c11 * cur; tau[11] = t; tau[12] = t + f78::c13 * cur;
+        } else if (SOLVER == 0) {
             tau[0] = t;  // unused (k1 is the FSAL derivative)
             tau[1] = t + cur * dp::a2; tau[2] = t + cur * dp::a3; tau[3] = t + cur * dp::a4;
             tau[4] = t + cur * dp::a5; tau[5] = t + cur; tau[6] = t + cur;
@@ -689,7 +698,7 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
         }
         {
             const double tmin = (SOLVER == 0) ? tau[1] : tau[0];
-            const double tmax = (SOLVER == 0) ? tau[6] : tau[4];
+            const double tmax = (SOLVER == 0) ? tau[6] : (SOLVER == 2) ? tau[12] : tau[4];
             const bool in_seg = (tmin > sch.lo) && (tmax <= sch.hi);
             if (SEP_RARELY(__ballot(active && !in_seg) != 0ull)) {  // rare: the common path falls through
                 // some chain's step leaves its cached segment: look the stages up again (rare)
@@ -700,9 +709,9 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
                     // at most one breakpoint b inside the step: stages <= b take v_lo, later ones v_hi
                     const double bpt = (c_lo < pb.nm) ? sch.me[c_lo] : INFINITY;
                     SEP_UNROLL
-                    for (int s = 0; s < 7; ++s) bks[s] = (tau[s] > bpt) ? v_hi : v_lo;
+                    for (int s = 0; s < NST; ++s) bks[s] = (tau[s] > bpt) ? v_hi : v_lo;
                 } else {
-                    for (int s = 0; s < 7; ++s) {
+                    for (int s = 0; s < NST; ++s) {
                         int ca, cb;
                         segment_index2(sch, pb.nm_pad, tau[s], tau[s], ca, cb);
                         bks[s] = sch.bkv[ca];
@@ -716,7 +725,7 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
                 __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
             } else {
                 SEP_UNROLL
-                for (int s = 0; s < 7; ++s) bks[s] = sch.bk;
+                for (int s = 0; s < NST; ++s) bks[s] = sch.bk;
             }
         }
 
@@ -731,6 +740,79 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
                                                  [&](const double (&xin)[NUM_COMP], double (&kout)[NUM_COMP], double bk) { rhs<LPC>(q, xin, kout, bk); });
         } else
 #endif
+        if constexpr (SOLVER == 2) {
+            // controlled_runge_kutta<runge_kutta_fehlberg78>::try_step: sys(x, dxdt, t) at EVERY attempt, then generic_rk's
+            // 13 stages, each input 1.0 x + (a_i1 dt) k1 + ... left to right with the zero entries left out.  Registers: k2 and
+            // k3 die at stages 3 and 5, k11 goes straight into the error sum (the only place it is read), and the solution is
+            // summed after the last stage, when k4 and k5 are dead (summed while k6..k13 arrive it would hold one vector more
+            // through stages 7-13).
+            double k8[NUM_COMP], k9[NUM_COMP], k10[NUM_COMP], k11[NUM_COMP], k12[NUM_COMP], k13[NUM_COMP];
+            rhs<LPC>(q, x, k1, bks[0]);
+            { const double f1 = f78::a2_1 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c];
+              rhs<LPC>(q, xt, k2, bks[1]); }
+            { const double f1 = f78::a3_1 * cur, f2 = f78::a3_2 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c] + f2 * k2[c];
+              rhs<LPC>(q, xt, k3, bks[2]); }
+            { const double f1 = f78::a4_1 * cur, f3 = f78::a4_3 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c] + f3 * k3[c];
+              rhs<LPC>(q, xt, k4, bks[3]); }
+            { const double f1 = f78::a5_1 * cur, f3 = f78::a5_3 * cur, f4 = f78::a5_4 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c] + f3 * k3[c] + f4 * k4[c];
+              rhs<LPC>(q, xt, k5, bks[4]); }
+            { const double f1 = f78::a6_1 * cur, f4 = f78::a6_4 * cur, f5 = f78::a6_5 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c] + f4 * k4[c] + f5 * k5[c];
+              rhs<LPC>(q, xt, k6, bks[5]); }
+            { const double f1 = f78::a7_1 * cur, f4 = f78::a7_4 * cur, f5 = f78::a7_5 * cur, f6 = f78::a7_6 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c] + f4 * k4[c] + f5 * k5[c] + f6 * k6[c];
+              rhs<LPC>(q, xt, k7, bks[6]); }
+            { const double f1 = f78::a8_1 * cur, f5 = f78::a8_5 * cur, f6 = f78::a8_6 * cur, f7 = f78::a8_7 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xt[c] = x[c] + f1 * k1[c] + f5 * k5[c] + f6 * k6[c] + f7 * k7[c];
+              rhs<LPC>(q, xt, k8, bks[7]); }
+            { const double f1 = f78::a9_1 * cur, f4 = f78::a9_4 * cur, f5 = f78::a9_5 * cur, f6 = f78::a9_6 * cur,
+                           f7 = f78::a9_7 * cur, f8 = f78::a9_8 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c)
+                  xt[c] = x[c] + f1 * k1[c] + f4 * k4[c] + f5 * k5[c] + f6 * k6[c] + f7 * k7[c] + f8 * k8[c];
+              rhs<LPC>(q, xt, k9, bks[8]); }
+            { const double f1 = f78::a10_1 * cur, f4 = f78::a10_4 * cur, f5 = f78::a10_5 * cur, f6 = f78::a10_6 * cur,
+                           f7 = f78::a10_7 * cur, f8 = f78::a10_8 * cur, f9 = f78::a10_9 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c)
+                  xt[c] = x[c] + f1 * k1[c] + f4 * k4[c] + f5 * k5[c] + f6 * k6[c] + f7 * k7[c] + f8 * k8[c] + f9 * k9[c];
+              rhs<LPC>(q, xt, k10, bks[9]); }
+            { const double f1 = f78::a11_1 * cur, f4 = f78::a11_4 * cur, f5 = f78::a11_5 * cur, f6 = f78::a11_6 * cur,
+                           f7 = f78::a11_7 * cur, f8 = f78::a11_8 * cur, f9 = f78::a11_9 * cur, f10 = f78::a11_10 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c)
+                  xt[c] = x[c] + f1 * k1[c] + f4 * k4[c] + f5 * k5[c] + f6 * k6[c] + f7 * k7[c] + f8 * k8[c] + f9 * k9[c]
+                          + f10 * k10[c];
+              rhs<LPC>(q, xt, k11, bks[10]); }
+            // error dt (b - bhat) . k: k1, k11, k12, k13 (the two leading products written out in the tolerance build, so that
+            // the result does not depend on which one the contraction pass fuses)
+            { const double e1 = f78::db1 * cur, e11 = f78::db11 * cur;
+#if SEPAIHRD_ARITH_FMA
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xerr[c] = fma(e11, k11[c], e1 * k1[c]); }
+#else
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xerr[c] = e1 * k1[c] + e11 * k11[c]; }
+#endif
+            { const double f1 = f78::a12_1 * cur, f6 = f78::a12_6 * cur, f7 = f78::a12_7 * cur, f8 = f78::a12_8 * cur,
+                           f9 = f78::a12_9 * cur, f10 = f78::a12_10 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c)
+                  xt[c] = x[c] + f1 * k1[c] + f6 * k6[c] + f7 * k7[c] + f8 * k8[c] + f9 * k9[c] + f10 * k10[c];
+              rhs<LPC>(q, xt, k12, bks[11]); }
+            { const double f1 = f78::a13_1 * cur, f4 = f78::a13_4 * cur, f5 = f78::a13_5 * cur, f6 = f78::a13_6 * cur,
+                           f7 = f78::a13_7 * cur, f8 = f78::a13_8 * cur, f9 = f78::a13_9 * cur, f10 = f78::a13_10 * cur,
+                           f12 = f78::a13_12 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c)
+                  xt[c] = x[c] + f1 * k1[c] + f4 * k4[c] + f5 * k5[c] + f6 * k6[c] + f7 * k7[c] + f8 * k8[c] + f9 * k9[c]
+                          + f10 * k10[c] + f12 * k12[c];
+              rhs<LPC>(q, xt, k13, bks[12]); }
+            { const double e12 = f78::db12 * cur, e13 = f78::db13 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c) xerr[c] = xerr[c] + e12 * k12[c] + e13 * k13[c]; }
+            // the 8th-order solution: b1..b5 = b11 = 0
+            { const double f6 = f78::b6 * cur, f7 = f78::b7 * cur, f8 = f78::b8 * cur, f9 = f78::b9 * cur, f10 = f78::b10 * cur,
+                           f12 = f78::b12 * cur, f13 = f78::b13 * cur;
+              SEP_UNROLL for (int c = 0; c < NUM_COMP; ++c)
+                  xnew[c] = x[c] + f6 * k6[c] + f7 * k7[c] + f8 * k8[c] + f9 * k9[c] + f10 * k10[c] + f12 * k12[c] + f13 * k13[c]; }
+        } else
         if (SOLVER == 0) {
             // runge_kutta_dopri5::do_step_impl -- scale_sumN left to right, factors dt*b
             { const double f1 = cur * dp::b21;
@@ -824,14 +906,19 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
         // (dt = max(dt, grown) cannot change min(dt, gap) otherwise).
         const bool need_dec = active && reject;
         const bool need_inc = active && !reject && (err < 0.5) && grow_relevant;
+        // stepper order 5 / error order 4 for Dopri5 and Cash-Karp; 8 / 7 for Fehlberg 7(8) (its floor 5^-8: the largest
+        // growth is 0.9 * 5 = 4.5 as well, so grow_relevant holds for all three)
+        constexpr double CTL_FLOOR = SOLVER == 2 ? 1.0 / 390625.0 : 1.0 / 3125.0;
+        constexpr double CTL_EXPO_DEC = SOLVER == 2 ? -1.0 / (7 - 1) : -1.0 / (4 - 1);
+        constexpr double CTL_EXPO_INC = SOLVER == 2 ? -1.0 / 8 : -1.0 / 5;
 #if SEPAIHRD_ARITH_FMA
         // Tolerance build: what only a rejection or a step-size change touches lives in the block only those attempts enter (see
         // the 16-lane form, sepaihrd_lane_split.inc: when no chain of the wave rejects or grows, cur_after = cur <= dt, so dt keeps
         // its value, every active chain accepted and nothing can give up).  The strict build keeps the form below.
         const bool acc = active && !reject;
         if (SEP_RARELY(__ballot(need_dec || need_inc) != 0ull)) {
-            const double arg = max_moved_uniform(err, 1.0 / 3125.0);  // 5^-5: the floor of the increase rule; a rejected step has err > 1
-            const double expo = need_dec ? -1.0 / (4 - 1) : -1.0 / 5;
+            const double arg = max_moved_uniform(err, CTL_FLOOR);  // 5^-order: the floor of the increase rule; a rejected step has err > 1
+            const double expo = need_dec ? CTL_EXPO_DEC : CTL_EXPO_INC;
             const double pw = 9.0 / 10.0 * pow_ctl(arg, expo);
             const double f = fmax(pw, 1.0 / 5.0);  // the floor of the decrease rule; an increase has pw > 1 (err < 0.5)
             const double cur_after = (need_dec || need_inc) ? cur * f : cur;
@@ -851,8 +938,8 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
 #else
         double cur_after = cur;
         if (SEP_RARELY(__ballot(need_dec || need_inc) != 0ull)) {
-            const double arg = max_moved_uniform(err, 1.0 / 3125.0);  // 5^-5: the floor of the increase rule; a rejected step has err > 1
-            const double expo = need_dec ? -1.0 / (4 - 1) : -1.0 / 5;
+            const double arg = max_moved_uniform(err, CTL_FLOOR);  // 5^-order: the floor of the increase rule; a rejected step has err > 1
+            const double expo = need_dec ? CTL_EXPO_DEC : CTL_EXPO_INC;
             const double pw = 9.0 / 10.0 * pow_ctl(arg, expo);
             const double f = fmax(pw, 1.0 / 5.0);  // the floor of the decrease rule; an increase has pw > 1 (err < 0.5)
             if (need_dec || need_inc) cur_after = cur * f;
@@ -1278,11 +1365,11 @@ int needs_workspace_one(const DevProblem& pb, int B, int force_split) {
     const int blocks = (B + CPW - 1) / CPW;
     if (blocks <= 0) return 0;
 #if SEPAIHRD_HAVE_WAVE_CHAIN
-    if constexpr (LPC == 4) {
+    if constexpr (LPC == 4 && SOLVER != 2) {
         if (wave_chain_wanted(B)) return 1;  // the one-wave-per-chain form parks its increments
     }
 #endif
-    if constexpr (LPC == 4) {
+    if constexpr (LPC == 4 && SOLVER != 2) {  // (no 16-lane form of the Fehlberg 7(8) stepper)
         // the 16-lane form evaluates the likelihood on consumer waves of the same workgroup: no workspace
         if (lane_split_wanted(pb, B)) return (quad_fused_wanted() && !force_split && quad_fused_lds_bytes(pb) <= QUAD_FUSED_MAX_LDS) ? 0 : 1;
     }
@@ -1295,17 +1382,18 @@ int launch_one(const DevProblem& pb, const double* d_theta, int B, const EvalOut
     const int blocks = (B + CPW - 1) / CPW;
     if (blocks <= 0) return 0;
 #if SEPAIHRD_HAVE_WAVE_CHAIN
-    if constexpr (LPC == 4) {
+    if constexpr (LPC == 4 && SOLVER != 2) {
         if (wave_chain_wanted(B)) return launch_wave_chain<SOLVER>(pb, d_theta, B, out, stream);
     }
 #endif
-    if constexpr (LPC == 4) {
+    if constexpr (LPC == 4 && SOLVER != 2) {
         if (lane_split_wanted(pb, B)) return launch_quad<SOLVER>(pb, d_theta, B, out, stream);
     }
     // 1024 SIMDs: up to one wave per SIMD the chip is not full and the separate likelihood pass wins
     if (split_pays<LPC, SOLVER>((size_t)blocks) || out.force_split)
         return launch_wps<LPC, SOLVER, 1, false>(pb, d_theta, blocks, B, out, stream);
-    if constexpr (SOLVER == 1 || (SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()))) {
+    // (the Fehlberg 7(8) stepper has one-wave forms only: 360-512 registers, never two waves on a SIMD)
+    if constexpr (SOLVER == 1 || (SOLVER == 0 && SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()))) {
         // the two-wave form as soon as some SIMD has to hold two waves (its one-wave sibling cannot: one_wave_per_simd_only)
         if (blocks > 1024) return launch_wps<LPC, SOLVER, 2, true>(pb, d_theta, blocks, B, out, stream);
     }
@@ -1336,12 +1424,12 @@ template <int LPC, int SOLVER>
 int info_one(const DevProblem& pb, int batch, LaunchInfo* info, const char* name) {
     constexpr int CPW = WAVE / LPC;
 #if SEPAIHRD_HAVE_WAVE_CHAIN
-    if constexpr (LPC == 4) {
+    if constexpr (LPC == 4 && SOLVER != 2) {
         if (batch > 0 && wave_chain_wanted(batch))
             return info_of(&sepaihrd_eval_wave_kernel<SOLVER>, pb, WAVE, info, "sepaihrd_eval_wave_kernel[fma]", LL_FORM_SEPARATE_PASS, WAVE, wave_chain_lds_bytes(pb));
     }
 #endif
-    if constexpr (LPC == 4) {
+    if constexpr (LPC == 4 && SOLVER != 2) {
         if (batch > 0 && lane_split_wanted(pb, batch))
             return (quad_fused_wanted() && quad_fused_lds_bytes(pb) <= QUAD_FUSED_MAX_LDS)
                        ? info_of(&sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, true, false>, pb, QUAD_LANES, info, SEP_QUAD_NAME "+ll", LL_FORM_CONSUMER_WAVES, 8 * WAVE, quad_fused_lds_bytes(pb))  // the form an evaluation without trajectories launches
@@ -1351,7 +1439,7 @@ int info_one(const DevProblem& pb, int batch, LaunchInfo* info, const char* name
     const size_t blocks = batch > 0 ? (size_t)((batch + CPW - 1) / CPW) : (size_t)1 << 20;
     if (split_pays<LPC, SOLVER>(blocks))
         return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 1, false>, pb, LPC, info, name, LL_FORM_SEPARATE_PASS);
-    if constexpr (SOLVER == 1 || (SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()))) {
+    if constexpr (SOLVER == 1 || (SOLVER == 0 && SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()))) {
         if (blocks > 1024) return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 2, true>, pb, LPC, info, name, LL_FORM_INLINE);
     }
     return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 1, true>, pb, LPC, info, name, LL_FORM_INLINE);
@@ -1368,14 +1456,14 @@ __global__ __launch_bounds__(WAVE) void log_values_kernel(const double* __restri
 }
 #endif
 
-#define SEP_DISPATCH(FN, ...)                                                                  \
-    switch (pb.lpc) {                                                                          \
-        case 1: return solver == 0 ? FN<1, 0>(__VA_ARGS__) : FN<1, 1>(__VA_ARGS__);            \
-        case 2: return solver == 0 ? FN<2, 0>(__VA_ARGS__) : FN<2, 1>(__VA_ARGS__);            \
-        case 4: return solver == 0 ? FN<4, 0>(__VA_ARGS__) : FN<4, 1>(__VA_ARGS__);            \
-        case 8: return solver == 0 ? FN<8, 0>(__VA_ARGS__) : FN<8, 1>(__VA_ARGS__);            \
-        case 16: return solver == 0 ? FN<16, 0>(__VA_ARGS__) : FN<16, 1>(__VA_ARGS__);         \
-        default: return -4;                                                                    \
+#define SEP_DISPATCH(FN, ...)                                                                                                  \
+    switch (pb.lpc) {                                                                                                          \
+        case 1: return solver == 0 ? FN<1, 0>(__VA_ARGS__) : solver == 1 ? FN<1, 1>(__VA_ARGS__) : FN<1, 2>(__VA_ARGS__);      \
+        case 2: return solver == 0 ? FN<2, 0>(__VA_ARGS__) : solver == 1 ? FN<2, 1>(__VA_ARGS__) : FN<2, 2>(__VA_ARGS__);      \
+        case 4: return solver == 0 ? FN<4, 0>(__VA_ARGS__) : solver == 1 ? FN<4, 1>(__VA_ARGS__) : FN<4, 2>(__VA_ARGS__);      \
+        case 8: return solver == 0 ? FN<8, 0>(__VA_ARGS__) : solver == 1 ? FN<8, 1>(__VA_ARGS__) : FN<8, 2>(__VA_ARGS__);      \
+        case 16: return solver == 0 ? FN<16, 0>(__VA_ARGS__) : solver == 1 ? FN<16, 1>(__VA_ARGS__) : FN<16, 2>(__VA_ARGS__);  \
+        default: return -4;                                                                                                    \
     }
 
 }  // namespace

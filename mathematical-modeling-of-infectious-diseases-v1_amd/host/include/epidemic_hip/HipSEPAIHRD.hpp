@@ -150,7 +150,11 @@ public:
     void calculateBatch(const double* thetas, int B, double* out, int* status = nullptr) const override;
     // the SimulationException a per-chain status >= SEPAIHRD_STATUS_STEP_FAILURE stands for (2 odeint's 500 rejections,
     // 3 step-attempt budget, 4 hand-off between wavefronts timed out); never returns
-    [[noreturn]] static void throwIntegrationFailure(int status);
+    // (solver: the context's SEPAIHRD_SOLVER_*, which names the strategy a step failure is reported from)
+    [[noreturn]] static void throwIntegrationFailure(int status, int solver = 0 /* SEPAIHRD_SOLVER_DOPRI5 */);
+    // the reference's `where` of an odeint step failure under this solver: the strategy's integrate()
+    static const char* integrateWhere(int solver);
+    int solverCode() const { return solver_; }
     // per-chain step counters of the last calculateBatch (diagnostics)
     const std::vector<int32_t>& lastAccepted() const { return n_acc_; }
     const std::vector<int32_t>& lastRejected() const { return n_rej_; }
@@ -169,6 +173,8 @@ protected:
     // resolves the manager argument of the model-taking constructors: `owned` is filled when it is not a Hip manager
     static HipSEPAIHRDParameterManager& resolveManager(const std::shared_ptr<AgeSEPAIHRDModel>& model, IParameterManager& given,
                                                        std::unique_ptr<HipSEPAIHRDParameterManager>& owned);
+    // SEPAIHRD_SOLVER_* of a strategy; InvalidParameterException for a strategy without a kernel
+    static int solverOf(const std::shared_ptr<IOdeSolverStrategy>& solver_strategy);
     static int environmentDevice();
     static bool environmentFma();
     std::unique_ptr<HipSEPAIHRDParameterManager> owned_pm_;  // declared before pm_: it may be what pm_ refers to
@@ -176,6 +182,7 @@ protected:
     HipSEPAIHRDParameterManager& pm_;
     ISimulationCache& cache_;
     sepaihrd_ctx* ctx_ = nullptr;
+    int solver_ = 0;  // SEPAIHRD_SOLVER_* of ctx_ (0: Dopri5)
     mutable int device_mode_ = -1;
     mutable std::vector<int32_t> n_acc_, n_rej_, status_;
 };

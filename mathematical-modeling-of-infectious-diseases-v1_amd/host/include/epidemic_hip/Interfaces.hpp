@@ -140,6 +140,15 @@ public:
                                   "host integration is not built: this strategy selects the HIP Cash-Karp kernel");
     }
 };
+class FehlbergSolverStrategy : public IOdeSolverStrategy {
+public:
+    void integrate(const std::function<void(const state_type&, state_type&, double)>&, state_type&,
+                   const std::vector<double>&, double, std::function<void(const state_type&, double)>, double,
+                   double) const override {
+        throw SimulationException("FehlbergSolverStrategy::integrate",
+                                  "host integration is not built: this strategy selects the HIP Fehlberg 7(8) kernel");
+    }
+};
 
 struct OptimizationResult {
     Eigen::VectorXd bestParameters;

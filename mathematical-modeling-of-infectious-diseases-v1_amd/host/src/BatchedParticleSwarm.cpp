@@ -1,5 +1,6 @@
 // host/src/BatchedParticleSwarm.cpp -- see the header for the reference lines mirrored.
 #include "epidemic_hip/BatchedParticleSwarm.hpp"
+#include "epidemic_hip/HipSEPAIHRD.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -90,12 +91,14 @@ OptimizationResult BatchedParticleSwarmOptimization::optimize(const Eigen::Vecto
     auto* batch = dynamic_cast<IBatchObjectiveFunction*>(&objective);
     std::vector<int> status;
     if (batch) {
-        eval_ = [&, batch](const double* th, int B, double* out) {
+        const auto* hip = dynamic_cast<const HipSEPAIHRDObjectiveFunction*>(&objective);
+        const char* where = HipSEPAIHRDObjectiveFunction::integrateWhere(hip ? hip->solverCode() : 0);  // 0: Dopri5
+        eval_ = [&, batch, where](const double* th, int B, double* out) {
             status.resize(static_cast<size_t>(B));
             batch->calculateBatch(th, B, out, status.data());
             for (int b = 0; b < B; ++b)  // calculate() lets SimulationException escape and the swarm loop does not catch it
                 if (status[static_cast<size_t>(b)] >= 2)
-                    throw SimulationException("Dopri5SolverStrategy::integrate", "Boost.Odeint integration failed: step size adjustment");
+                    throw SimulationException(where, "Boost.Odeint integration failed: step size adjustment");
         };
     } else {
         eval_ = [&](const double* th, int B, double* out) {

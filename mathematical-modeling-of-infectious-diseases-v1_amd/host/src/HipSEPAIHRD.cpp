@@ -316,7 +316,17 @@ HipSEPAIHRDObjectiveFunction::HipSEPAIHRDObjectiveFunction(
     : pm_(parameterManager), cache_(cache) {
     ctx_ = createContext(pm_, data, time_points, initial_state, solver_strategy, abs_error, rel_error, device,
                          fma_arithmetic, nullptr);
+    solver_ = solverOf(solver_strategy);
     device_mode_ = pm_.getConstraintMode() == ConstraintMode::MCMC_REFLECT ? SEPAIHRD_CONSTRAINT_REFLECT : SEPAIHRD_CONSTRAINT_CLAMP;
+}
+
+int HipSEPAIHRDObjectiveFunction::solverOf(const std::shared_ptr<IOdeSolverStrategy>& solver_strategy) {
+    if (!solver_strategy) throw InvalidParameterException("Simulator::Simulator", "Solver strategy pointer cannot be null.");
+    if (dynamic_cast<Dopri5SolverStrategy*>(solver_strategy.get())) return SEPAIHRD_SOLVER_DOPRI5;
+    if (dynamic_cast<CashKarpSolverStrategy*>(solver_strategy.get())) return SEPAIHRD_SOLVER_CASH_KARP54;
+    if (dynamic_cast<FehlbergSolverStrategy*>(solver_strategy.get())) return SEPAIHRD_SOLVER_FEHLBERG78;
+    throw InvalidParameterException("SEPAIHRDObjectiveFunction",
+                                    "solver strategy has no HIP kernel (Dopri5, Cash-Karp and Fehlberg 7(8) are built)");
 }
 
 sepaihrd_ctx* HipSEPAIHRDObjectiveFunction::createContext(
@@ -326,11 +336,7 @@ sepaihrd_ctx* HipSEPAIHRDObjectiveFunction::createContext(
     const char* W = "SEPAIHRDObjectiveFunction";
     const SEPAIHRDParameters& mp = pm_.modelParameters();
     const int n = static_cast<int>(mp.N.size());
-    if (!solver_strategy) throw InvalidParameterException("Simulator::Simulator", "Solver strategy pointer cannot be null.");
-    int solver;
-    if (dynamic_cast<Dopri5SolverStrategy*>(solver_strategy.get())) solver = SEPAIHRD_SOLVER_DOPRI5;
-    else if (dynamic_cast<CashKarpSolverStrategy*>(solver_strategy.get())) solver = SEPAIHRD_SOLVER_CASH_KARP54;
-    else throw InvalidParameterException(W, "solver strategy has no HIP kernel (Dopri5 and Cash-Karp are built)");
+    const int solver = solverOf(solver_strategy);
     if (initial_state.size() != 11 * n)
         throw InvalidParameterException("Simulator::run", "Initial state size does not match model state size.");
     if (time_points.empty()) throw InvalidParameterException("Simulator::run", "Output time points vector cannot be empty.");
@@ -441,6 +447,7 @@ HipSEPAIHRDObjectiveFunction::HipSEPAIHRDObjectiveFunction(
     syncConstraintMode();  // a foreign manager's mode, before the context is built with it
     ctx_ = createContext(pm_, data, time_points, initial_state, solver_strategy, abs_error, rel_error, environmentDevice(),
                          environmentFma(), nullptr);
+    solver_ = solverOf(solver_strategy);
     device_mode_ = pm_.getConstraintMode() == ConstraintMode::MCMC_REFLECT ? SEPAIHRD_CONSTRAINT_REFLECT : SEPAIHRD_CONSTRAINT_CLAMP;
 }
 
@@ -485,17 +492,22 @@ void HipSEPAIHRDObjectiveFunction::calculateBatch(const double* thetas, int B, d
         if (status) status[b] = status_[static_cast<size_t>(b)];
         worst = std::max(worst, static_cast<int>(status_[static_cast<size_t>(b)]));
     }
-    if (worst >= SEPAIHRD_STATUS_STEP_FAILURE && !status) throwIntegrationFailure(worst);
+    if (worst >= SEPAIHRD_STATUS_STEP_FAILURE && !status) throwIntegrationFailure(worst, solver_);
 }
 
 // Per-chain status >= 2: the evaluation produced no value.  The reference lets the solver's exception leave calculate()
 // (no try/catch around Simulator::run, SEPAIHRDObjectiveFunction.cpp:165; Dopri5SolverStrategy.cpp:38-42 rethrows
 // odeint's as SimulationException) and the samplers' safeEvaluate turns it into -1e18; same exception type here, the
 // message says which of the three causes it was.
-void HipSEPAIHRDObjectiveFunction::throwIntegrationFailure(int status) {
+// (The Dopri5 and Cash-Karp contexts both report from Dopri5SolverStrategy::integrate, as they always have.)
+const char* HipSEPAIHRDObjectiveFunction::integrateWhere(int solver) {
+    return solver == SEPAIHRD_SOLVER_FEHLBERG78 ? "FehlbergSolverStrategy::integrate" : "Dopri5SolverStrategy::integrate";
+}
+
+void HipSEPAIHRDObjectiveFunction::throwIntegrationFailure(int status, int solver) {
     switch (status) {
         case SEPAIHRD_STATUS_STEP_FAILURE:
-            throw SimulationException("Dopri5SolverStrategy::integrate", "Boost.Odeint integration failed: step size adjustment");
+            throw SimulationException(integrateWhere(solver), "Boost.Odeint integration failed: step size adjustment");
         case SEPAIHRD_STATUS_STEP_BUDGET:
             throw SimulationException("HipSEPAIHRDObjectiveFunction", "integration stopped: step-attempt budget exhausted (SEPAIHRD_STATUS_STEP_BUDGET)");
         case SEPAIHRD_STATUS_PIPELINE:
@@ -526,7 +538,7 @@ double HipSEPAIHRDObjectiveFunction::calculate(const Eigen::VectorXd& parameters
     int st = 0;
     calculateBatch(parameters.data(), 1, &value, &st);
     if (st >= SEPAIHRD_STATUS_STEP_FAILURE)  // propagates out of calculate(); samplers map it to -1e18
-        throw SimulationException("Dopri5SolverStrategy::integrate", "Boost.Odeint integration failed: step size adjustment");
+        throw SimulationException(integrateWhere(solver_), "Boost.Odeint integration failed: step size adjustment");
     if (fast) fast->storeLikelihood(fast_key, value);
     else cache_.storeLikelihood(key, value);
     return value;
@@ -641,7 +653,7 @@ double HipSEPAIHRDGradientObjectiveFunction::evaluate_with_gradient(const Eigen:
             // -inf, then mapped to lowest() (:148-155); the simulation result is not used
             fp = LOWEST;
         } else {
-            if (status[u] >= SEPAIHRD_STATUS_STEP_FAILURE) throwIntegrationFailure(status[u]);
+            if (status[u] >= SEPAIHRD_STATUS_STEP_FAILURE) throwIntegrationFailure(status[u], solver_);
             fp = f_plus[u];  // status 1 with a valid state: non-finite likelihood, already lowest()
         }
         grad[i] = std::isfinite(fp) ? (fp - f_center) / eps[u] : 0.0;  // :163-167

@@ -120,6 +120,7 @@ void* host_objective_create(const sepaihrd_problem* pb, const char* names, const
         h->data = std::make_unique<CalibrationData>(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), mp.N);
         std::shared_ptr<IOdeSolverStrategy> solver;
         if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
+        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
         else solver = std::make_shared<Dopri5SolverStrategy>();
         h->obj = std::make_unique<HipSEPAIHRDObjectiveFunction>(
             *h->pm, *h->cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
@@ -146,6 +147,7 @@ int host_ensemble(void* hv, const sepaihrd_problem* pb, int device, const double
         const size_t P = h->pm->getParameterCount();
         std::shared_ptr<IOdeSolverStrategy> solver;
         if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
+        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
         else solver = std::make_shared<Dopri5SolverStrategy>();
         const std::vector<double> times(pb->times, pb->times + pb->n_times);
         HipPosteriorEnsemble ens(*h->pm, *h->data, times, vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err,
@@ -466,6 +468,7 @@ int host_gradient(void* hv, const sepaihrd_problem* pb, int device, const double
         const int P = static_cast<int>(h->pm->getParameterCount());
         std::shared_ptr<IOdeSolverStrategy> solver;
         if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
+        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
         else solver = std::make_shared<Dopri5SolverStrategy>();
         SimulationCache cache(16);
         HipSEPAIHRDGradientObjectiveFunction obj(*h->pm, cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
@@ -497,6 +500,7 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
         h->pm->setConstraintMode(constraint_mode == 0 ? ConstraintMode::OPTIMIZATION_CLAMP : ConstraintMode::MCMC_REFLECT);
         std::shared_ptr<IOdeSolverStrategy> solver;
         if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
+        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
         else solver = std::make_shared<Dopri5SolverStrategy>();
         SimulationCache cache(1000);
         HipSEPAIHRDGradientObjectiveFunction obj(*h->pm, cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
@@ -768,6 +772,7 @@ extern "C" int host_reference_constructors(const sepaihrd_problem* pb, const cha
         const CalibrationData data(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), mp.N);
         std::shared_ptr<IOdeSolverStrategy> solver;
         if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
+        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
         else solver = std::make_shared<Dopri5SolverStrategy>();
         const std::vector<double> times(pb->times, pb->times + pb->n_times);
         const Eigen::VectorXd x0 = vec(pb->initial_state, 11 * n);

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 NUM_COMPARTMENTS = 11
-SOLVER_DOPRI5, SOLVER_CASH_KARP54 = 0, 1
+SOLVER_DOPRI5, SOLVER_CASH_KARP54, SOLVER_FEHLBERG78 = 0, 1, 2  # include/sepaihrd_hip.h SEPAIHRD_SOLVER_*
 CONSTRAINT_CLAMP, CONSTRAINT_REFLECT = 0, 1
 ARITH_STRICT, ARITH_FMA = 0, 1
 PRECISION_F64, PRECISION_F32 = 0, 1  # number type of the ODE state (include/sepaihrd_hip.h)
