@@ -1325,6 +1325,50 @@ inline bool split_pays(size_t blocks) {
     return second_wave;
 }
 
+// The forms in which a batch of the fp64 evaluator can be launched.
+enum class EvalForm {
+    WaveChain,       // one wave per chain, separate likelihood pass (experiment builds only)
+    QuadFused,       // 16 lanes per chain, the likelihood on consumer waves of the same workgroup
+    QuadSplit,       // 16 lanes per chain, separate likelihood pass
+    Split,           // LPC lanes per chain, separate likelihood pass
+    InlineTwoWaves,  // LPC lanes per chain, the likelihood inline, two waves per SIMD
+    Inline,          // the same, one wave per SIMD
+};
+// Which forms a lane count / solver has at all: `if constexpr` on these keeps the kernels of the others from being
+// instantiated.  The Fehlberg 7(8) stepper has no 16-lane or one-wave-per-chain form, and one-wave forms only (360-512
+// registers, never two waves on a SIMD).
+template <int LPC, int SOLVER>
+constexpr bool has_quad_form() { return LPC == 4 && SOLVER != 2; }
+template <int LPC, int SOLVER>
+constexpr bool has_two_wave_form() {
+    return SOLVER == 1 || (SOLVER == 0 && SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()));
+}
+
+// The form a batch of B chains is launched in: the ONE place that decides it.  launch_one launches it, the C ABI sizes
+// the workspace from it (needs_workspace_one) and sepaihrd_get_kernel_info_for_batch describes it (info_one).
+// B <= 0 stands for a batch that fills the chip (kernel_info without a batch): the wave-chain and 16-lane tests are
+// skipped.  force_split: the caller reads the parked increments (the ensemble summaries), so the likelihood is a separate pass.
+template <int LPC, int SOLVER>
+EvalForm choose_form(const DevProblem& pb, int B, bool force_split) {
+    constexpr int CPW = WAVE / LPC;
+    const size_t blocks = B > 0 ? (size_t)((B + CPW - 1) / CPW) : (size_t)1 << 20;
+    if constexpr (has_quad_form<LPC, SOLVER>()) {
+#if SEPAIHRD_HAVE_WAVE_CHAIN
+        if (B > 0 && wave_chain_wanted(B)) return EvalForm::WaveChain;
+#endif
+        if (B > 0 && lane_split_wanted(pb, B))
+            return quad_fused_wanted() && !force_split && quad_fused_lds_bytes(pb) <= QUAD_FUSED_MAX_LDS ? EvalForm::QuadFused
+                                                                                                         : EvalForm::QuadSplit;
+    }
+    // 1024 SIMDs: up to one wave per SIMD the chip is not full and the separate likelihood pass wins
+    if (split_pays<LPC, SOLVER>(blocks) || force_split) return EvalForm::Split;
+    // the two-wave form as soon as some SIMD has to hold two waves (its one-wave sibling cannot: one_wave_per_simd_only)
+    if constexpr (has_two_wave_form<LPC, SOLVER>()) {
+        if (blocks > 1024) return EvalForm::InlineTwoWaves;
+    }
+    return EvalForm::Inline;
+}
+
 template <int LPC, int SOLVER, int WPS, bool INLINE_LL>
 int launch_wps(const DevProblem& pb, const double* d_theta, int blocks, int B, const EvalOutputs& out, void* stream) {
     const size_t lds = eval_lds_bytes(pb, INLINE_LL);
@@ -1357,23 +1401,12 @@ int launch_wps(const DevProblem& pb, const double* d_theta, int blocks, int B, c
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// Does a launch of B chains park the daily increments in the ctx-owned workspace (cum / rows / wstatus)?  The ONE
-// place that decides it: launch_one below takes the same branches, and the C ABI sizes the workspace from this.
+// Does a launch of B chains park the daily increments in the ctx-owned workspace (cum / rows / wstatus)?
 template <int LPC, int SOLVER>
 int needs_workspace_one(const DevProblem& pb, int B, int force_split) {
-    constexpr int CPW = WAVE / LPC;
-    const int blocks = (B + CPW - 1) / CPW;
-    if (blocks <= 0) return 0;
-#if SEPAIHRD_HAVE_WAVE_CHAIN
-    if constexpr (LPC == 4 && SOLVER != 2) {
-        if (wave_chain_wanted(B)) return 1;  // the one-wave-per-chain form parks its increments
-    }
-#endif
-    if constexpr (LPC == 4 && SOLVER != 2) {  // (no 16-lane form of the Fehlberg 7(8) stepper)
-        // the 16-lane form evaluates the likelihood on consumer waves of the same workgroup: no workspace
-        if (lane_split_wanted(pb, B)) return (quad_fused_wanted() && !force_split && quad_fused_lds_bytes(pb) <= QUAD_FUSED_MAX_LDS) ? 0 : 1;
-    }
-    return (split_pays<LPC, SOLVER>((size_t)blocks) || force_split) ? 1 : 0;
+    if (B <= 0) return 0;
+    const EvalForm form = choose_form<LPC, SOLVER>(pb, B, force_split != 0);
+    return form == EvalForm::WaveChain || form == EvalForm::QuadSplit || form == EvalForm::Split;
 }
 
 template <int LPC, int SOLVER>
@@ -1381,21 +1414,17 @@ int launch_one(const DevProblem& pb, const double* d_theta, int B, const EvalOut
     constexpr int CPW = WAVE / LPC;
     const int blocks = (B + CPW - 1) / CPW;
     if (blocks <= 0) return 0;
+    const EvalForm form = choose_form<LPC, SOLVER>(pb, B, out.force_split);
+    if constexpr (has_quad_form<LPC, SOLVER>()) {
 #if SEPAIHRD_HAVE_WAVE_CHAIN
-    if constexpr (LPC == 4 && SOLVER != 2) {
-        if (wave_chain_wanted(B)) return launch_wave_chain<SOLVER>(pb, d_theta, B, out, stream);
-    }
+        if (form == EvalForm::WaveChain) return launch_wave_chain<SOLVER>(pb, d_theta, B, out, stream);
 #endif
-    if constexpr (LPC == 4 && SOLVER != 2) {
-        if (lane_split_wanted(pb, B)) return launch_quad<SOLVER>(pb, d_theta, B, out, stream);
+        if (form == EvalForm::QuadFused || form == EvalForm::QuadSplit)
+            return launch_quad<SOLVER>(pb, d_theta, B, out, stream, form == EvalForm::QuadFused);
     }
-    // 1024 SIMDs: up to one wave per SIMD the chip is not full and the separate likelihood pass wins
-    if (split_pays<LPC, SOLVER>((size_t)blocks) || out.force_split)
-        return launch_wps<LPC, SOLVER, 1, false>(pb, d_theta, blocks, B, out, stream);
-    // (the Fehlberg 7(8) stepper has one-wave forms only: 360-512 registers, never two waves on a SIMD)
-    if constexpr (SOLVER == 1 || (SOLVER == 0 && SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()))) {
-        // the two-wave form as soon as some SIMD has to hold two waves (its one-wave sibling cannot: one_wave_per_simd_only)
-        if (blocks > 1024) return launch_wps<LPC, SOLVER, 2, true>(pb, d_theta, blocks, B, out, stream);
+    if (form == EvalForm::Split) return launch_wps<LPC, SOLVER, 1, false>(pb, d_theta, blocks, B, out, stream);
+    if constexpr (has_two_wave_form<LPC, SOLVER>()) {
+        if (form == EvalForm::InlineTwoWaves) return launch_wps<LPC, SOLVER, 2, true>(pb, d_theta, blocks, B, out, stream);
     }
     return launch_wps<LPC, SOLVER, 1, true>(pb, d_theta, blocks, B, out, stream);
 }
@@ -1420,27 +1449,23 @@ int info_of(K kernel, const DevProblem& pb, int lanes, LaunchInfo* info, const c
     return 0;
 }
 
+// batch <= 0: a batch that fills the chip.  force_split is off: the form an evaluation without trajectories launches.
 template <int LPC, int SOLVER>
 int info_one(const DevProblem& pb, int batch, LaunchInfo* info, const char* name) {
-    constexpr int CPW = WAVE / LPC;
+    const EvalForm form = choose_form<LPC, SOLVER>(pb, batch, false);
+    if constexpr (has_quad_form<LPC, SOLVER>()) {
 #if SEPAIHRD_HAVE_WAVE_CHAIN
-    if constexpr (LPC == 4 && SOLVER != 2) {
-        if (batch > 0 && wave_chain_wanted(batch))
+        if (form == EvalForm::WaveChain)
             return info_of(&sepaihrd_eval_wave_kernel<SOLVER>, pb, WAVE, info, "sepaihrd_eval_wave_kernel[fma]", LL_FORM_SEPARATE_PASS, WAVE, wave_chain_lds_bytes(pb));
-    }
 #endif
-    if constexpr (LPC == 4 && SOLVER != 2) {
-        if (batch > 0 && lane_split_wanted(pb, batch))
-            return (quad_fused_wanted() && quad_fused_lds_bytes(pb) <= QUAD_FUSED_MAX_LDS)
-                       ? info_of(&sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, true, false>, pb, QUAD_LANES, info, SEP_QUAD_NAME "+ll", LL_FORM_CONSUMER_WAVES, 8 * WAVE, quad_fused_lds_bytes(pb))  // the form an evaluation without trajectories launches
-                       : info_of(&sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, false>, pb, QUAD_LANES, info, SEP_QUAD_NAME, LL_FORM_SEPARATE_PASS);
+        if (form == EvalForm::QuadFused)
+            return info_of(&sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, true, false>, pb, QUAD_LANES, info, SEP_QUAD_NAME "+ll", LL_FORM_CONSUMER_WAVES, 8 * WAVE, quad_fused_lds_bytes(pb));
+        if (form == EvalForm::QuadSplit)
+            return info_of(&sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, false>, pb, QUAD_LANES, info, SEP_QUAD_NAME, LL_FORM_SEPARATE_PASS);
     }
-    // the same branches as launch_one (batch <= 0: a batch that fills the chip)
-    const size_t blocks = batch > 0 ? (size_t)((batch + CPW - 1) / CPW) : (size_t)1 << 20;
-    if (split_pays<LPC, SOLVER>(blocks))
-        return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 1, false>, pb, LPC, info, name, LL_FORM_SEPARATE_PASS);
-    if constexpr (SOLVER == 1 || (SOLVER == 0 && SEPAIHRD_ARITH_FMA && (SEPAIHRD_DOPRI5_WPS2 || dopri5_two_waves<LPC>()))) {
-        if (blocks > 1024) return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 2, true>, pb, LPC, info, name, LL_FORM_INLINE);
+    if (form == EvalForm::Split) return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 1, false>, pb, LPC, info, name, LL_FORM_SEPARATE_PASS);
+    if constexpr (has_two_wave_form<LPC, SOLVER>()) {
+        if (form == EvalForm::InlineTwoWaves) return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 2, true>, pb, LPC, info, name, LL_FORM_INLINE);
     }
     return info_of(&sepaihrd_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA, 1, true>, pb, LPC, info, name, LL_FORM_INLINE);
 }

@@ -964,10 +964,11 @@ inline bool quad_fused_wanted() {
 #endif
 }
 
+// fused: the likelihood on consumer waves (EvalForm::QuadFused), else as a separate pass (choose_form decides)
 template <int SOLVER>
-int launch_quad(const DevProblem& pb, const double* d_theta, int B, const EvalOutputs& out, void* stream) {
+int launch_quad(const DevProblem& pb, const double* d_theta, int B, const EvalOutputs& out, void* stream, bool fused) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (quad_fused_wanted() && !out.force_split && quad_fused_lds_bytes(pb) <= QUAD_FUSED_MAX_LDS) {
+    if (fused) {
         const int wgs = (B + QUAD_UNITS * QUAD_CPW - 1) / (QUAD_UNITS * QUAD_CPW);
         static const bool lds_limit_raised = [] {  // dynamic LDS beyond the default 64 KiB needs the opt-in
             return hipFuncSetAttribute(reinterpret_cast<const void*>(&sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, true>),

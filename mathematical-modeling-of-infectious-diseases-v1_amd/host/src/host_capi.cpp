@@ -33,6 +33,12 @@ std::vector<std::string> split_lines(const char* s) {
         if (!line.empty()) out.push_back(line);
     return out;
 }
+// the host strategy of a sepaihrd_problem solver code
+std::shared_ptr<IOdeSolverStrategy> strategy_for(int solver) {
+    if (solver == SEPAIHRD_SOLVER_CASH_KARP54) return std::make_shared<CashKarpSolverStrategy>();
+    if (solver == SEPAIHRD_SOLVER_FEHLBERG78) return std::make_shared<FehlbergSolverStrategy>();
+    return std::make_shared<Dopri5SolverStrategy>();
+}
 Eigen::VectorXd vec(const double* p, int n) {
     Eigen::VectorXd v(n);
     for (int i = 0; i < n; ++i) v[i] = p ? p[i] : 0.0;
@@ -118,10 +124,7 @@ void* host_objective_create(const sepaihrd_problem* pb, const char* names, const
             return m;
         };
         h->data = std::make_unique<CalibrationData>(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), mp.N);
-        std::shared_ptr<IOdeSolverStrategy> solver;
-        if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
-        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
-        else solver = std::make_shared<Dopri5SolverStrategy>();
+        const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         h->obj = std::make_unique<HipSEPAIHRDObjectiveFunction>(
             *h->pm, *h->cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
             vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
@@ -145,10 +148,7 @@ int host_ensemble(void* hv, const sepaihrd_problem* pb, int device, const double
     try {
         const int n = pb->n_age;
         const size_t P = h->pm->getParameterCount();
-        std::shared_ptr<IOdeSolverStrategy> solver;
-        if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
-        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
-        else solver = std::make_shared<Dopri5SolverStrategy>();
+        const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         const std::vector<double> times(pb->times, pb->times + pb->n_times);
         HipPosteriorEnsemble ens(*h->pm, *h->data, times, vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err,
                                  device, pb->arith == SEPAIHRD_ARITH_FMA);
@@ -466,10 +466,7 @@ int host_gradient(void* hv, const sepaihrd_problem* pb, int device, const double
     try {
         const int n = pb->n_age;
         const int P = static_cast<int>(h->pm->getParameterCount());
-        std::shared_ptr<IOdeSolverStrategy> solver;
-        if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
-        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
-        else solver = std::make_shared<Dopri5SolverStrategy>();
+        const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         SimulationCache cache(16);
         HipSEPAIHRDGradientObjectiveFunction obj(*h->pm, cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
                                                  vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err, device,
@@ -498,10 +495,7 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
         const int n = pb->n_age;
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(constraint_mode == 0 ? ConstraintMode::OPTIMIZATION_CLAMP : ConstraintMode::MCMC_REFLECT);
-        std::shared_ptr<IOdeSolverStrategy> solver;
-        if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
-        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
-        else solver = std::make_shared<Dopri5SolverStrategy>();
+        const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         SimulationCache cache(1000);
         HipSEPAIHRDGradientObjectiveFunction obj(*h->pm, cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
                                                  vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err, device,
@@ -770,10 +764,7 @@ extern "C" int host_reference_constructors(const sepaihrd_problem* pb, const cha
             return m;
         };
         const CalibrationData data(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), mp.N);
-        std::shared_ptr<IOdeSolverStrategy> solver;
-        if (pb->solver == SEPAIHRD_SOLVER_CASH_KARP54) solver = std::make_shared<CashKarpSolverStrategy>();
-        else if (pb->solver == SEPAIHRD_SOLVER_FEHLBERG78) solver = std::make_shared<FehlbergSolverStrategy>();
-        else solver = std::make_shared<Dopri5SolverStrategy>();
+        const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         const std::vector<double> times(pb->times, pb->times + pb->n_times);
         const Eigen::VectorXd x0 = vec(pb->initial_state, 11 * n);
         const size_t P = nm.size();
