@@ -288,6 +288,34 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx *ctx, const double *theta, int S, c
                                 int n_probs, double *ppc_quantiles, double *sero_quantiles,
                                 double *rt_quantiles, double *metrics, int32_t *status, int32_t *n_valid);
 
+/* sepaihrd_scenario_ensemble: NPI scenario analysis over a posterior ensemble -- every sample theta[s] (S x n_params,
+ * host) under each of K scenarios, in ONE integrator launch of K x S chains.  Scenario k integrates with
+ * kappa_values[i] * kappa_mult[k n_kappa + i] (K x n_kappa, host; n_kappa must equal the problem's kappa count;
+ * finite and >= 0), the multiplier applied on the device AFTER the constraints, as
+ * PostCalibrationAnalyser::performScenarioAnalysis scales the already-constrained parameters
+ * (src/model/PostCalibrationAnalyser.cpp:94-141).  Only the integration sees the scaled kappa: R0, Rt and the
+ * attack-rate accumulation of the metric table read the unscaled kappa, as the reference's metrics, computed through
+ * the template's NPI strategy, do (:163-168).  Per scenario, the outputs of sepaihrd_ensemble_quantiles stacked on a
+ * leading scenario axis, and over the metric table:
+ *   ppc_quantiles   [K][6][n_probs][T_pos][n_age] or NULL
+ *   sero_quantiles  [K][n_probs][n_times] or NULL;  rt_quantiles  [K][n_probs][n_times] or NULL
+ *   metrics         [K][S][12 + 4 n_age] or NULL (NaN rows for failed samples)
+ *   metric_summary  [K][12 + 4 n_age][2 + n_probs] or NULL: mean, population std_dev, then the quantiles of each column
+ *                   over the scenario's valid samples (HipPosteriorEnsemble::aggregateMetrics' rule)
+ *   diff_quantiles  [K][12 + 4 n_age][n_probs] or NULL: quantiles of the paired differences metric[k][s] - metric[0][s]
+ *                   over the samples valid in both scenario k and scenario 0 (e.g. deaths averted = -total_deaths diff)
+ *   status          [K][S] or NULL;  n_valid [K] or NULL
+ * Same quantile rule as sepaihrd_ensemble_quantiles (exact sort in LDS up to 16384 samples, global segmented sort
+ * beyond).  K = 1 with all multipliers 1 reproduces sepaihrd_ensemble_quantiles bit for bit.
+ * SEPAIHRD_E_INVALID_ARG for a bad multiplier table, a pending sepaihrd_eval_batch_begin or K x S beyond one launch:
+ * more chains than a 32-bit count holds, or more device memory than the device has (the K S trajectories,
+ * K S n_times 11 n_age doubles, dominate); SEPAIHRD_E_UNSUPPORTED in F32 or beyond 16 age classes.  A request that fits the
+ * device but not its free memory fails with SEPAIHRD_E_HIP ("device allocation failed"). */
+int sepaihrd_scenario_ensemble(sepaihrd_ctx *ctx, const double *theta, int S, const double *kappa_mult, int K,
+                               int n_kappa, const double *probs, int n_probs, double *ppc_quantiles,
+                               double *sero_quantiles, double *rt_quantiles, double *metrics,
+                               double *metric_summary, double *diff_quantiles, int32_t *status, int32_t *n_valid);
+
 /* ---- Adaptive-Metropolis chains with their state resident on the device ----
  *
  * MetropolisHastingsSampler (src/sir_age_structured/optimizers/MetropolisHastingsSampler.cpp:201-412)

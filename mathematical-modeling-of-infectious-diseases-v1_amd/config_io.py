@@ -604,10 +604,103 @@ def write_metrics_summary(path: str, metrics: np.ndarray, n_age: int) -> None:
                                                         _quantile_sorted(v, 0.025), _quantile_sorted(v, 0.975)))
 
 
+# ---- NPI scenario analysis (PostCalibrationAnalyser.cpp:94-141,378-401) ----
+SCENARIO_NAMES = ("baseline", "stricter_lockdown", "weaker_lockdown")
+
+
+def default_lockdown_scenarios(n_kappa: int, baseline_fixed: bool = True) -> List[Tuple[str, np.ndarray]]:
+    """The reference's scenarios as kappa multiplier rows: baseline, then kappa_values[idx] x 0.9 and x 1.1 with idx = 1,
+    or 0 when the piecewise NPI strategy's baseline is calibratable (:111-130); only the baseline when n_kappa <= idx."""
+    idx = 1 if baseline_fixed else 0
+    rows = [("baseline", np.ones(n_kappa))]
+    if n_kappa > idx:
+        for name, f in (("stricter_lockdown", 0.9), ("weaker_lockdown", 1.1)):
+            m = np.ones(n_kappa)
+            m[idx] = f
+            rows.append((name, m))
+    return rows
+
+
+def scenario_kappa_values(pb, theta_constrained, multipliers) -> np.ndarray:
+    """The scenario's kappa_values for one constrained theta: the problem's kappa_values with the calibrated entries
+    from theta, times the multipliers (SEPAIHRDParameters::kappa_values[idx] *= f after updateModelParameters)."""
+    from .problem import F_KAPPA_VALUE
+    kappa = np.array(pb.kappa_values, dtype=np.float64)
+    codes, idxs = pb.field_map()
+    for p, (c, i) in enumerate(zip(codes, idxs)):
+        if c == F_KAPPA_VALUE:
+            kappa[i] = theta_constrained[p]
+    return kappa * np.asarray(multipliers, dtype=np.float64)
+
+
+def scenario_comparison_rows(names, metrics, status, kappas, n_age: int):
+    """Rows for write_scenario_comparison from one run per scenario: metrics [K][12 + 4 n], status [K], kappas [K][nk].
+    A failed run gets the default EssentialMetrics (zeros, min_Rt 1e6, AnalysisTypes.hpp:14-39) and no kappa values,
+    as MetricsCalculator::calculateEssentialMetrics returns for an invalid result (MetricsCalculator.cpp:23-26)."""
+    rows = []
+    for name, row, st, kappa in zip(names, metrics, status, kappas):
+        if st != 0:
+            row = np.zeros(12 + 4 * n_age)
+            row[9] = 1e6
+            kappa = []
+        rows.append((name, np.asarray(row, dtype=np.float64), list(kappa)))
+    return rows
+
+
+def kappa_column_order(n_kappa: int) -> List[int]:
+    """Indices of kappa_1 .. kappa_nk in the order a std::map<std::string, double> keyed "kappa_<i+1>" iterates them
+    (EssentialMetrics::kappa_values, MetricsCalculator.cpp:166-169): lexicographic, kappa_10 before kappa_2."""
+    return sorted(range(n_kappa), key=lambda i: "kappa_%d" % (i + 1))
+
+
+def write_scenario_comparison(path: str, scenarios) -> None:
+    """scenarios/scenario_comparison.csv (AnalysisWriter::writeScenarioComparison, AnalysisWriter.cpp:439-477), values
+    with the stream defaults.  scenarios: (name, metric row [12 + 4 n] as sepaihrd_ensemble_quantiles returns it,
+    the scenario's own kappa_values [nk]) in row order; the kappa header comes from the first row."""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write("scenario,R0,overall_IFR,overall_attack_rate,peak_hospital,peak_ICU,"
+                 "time_to_peak_hospital,time_to_peak_ICU,total_deaths,seroprevalence_day64")
+        if scenarios and len(scenarios[0][2]) > 0:
+            fh.write("".join(",kappa_%d" % (i + 1) for i in kappa_column_order(len(scenarios[0][2]))))
+        fh.write("\n")
+        for name, row, kappa in scenarios:
+            fh.write(name + "".join("," + _cxx_default(row[c]) for c in (0, 1, 2, 3, 4, 5, 6, 7, 11)))
+            fh.write("".join("," + _cxx_default(kappa[i]) for i in kappa_column_order(len(kappa))))
+            fh.write("\n")
+
+
+ENE_COVID = {"target_day": 64.0, "mean": 0.048, "lower_ci": 0.043, "upper_ci": 0.054}  # PostCalibrationAnalyser.cpp:288-299
+
+
+def write_ene_covid_validation(path: str, sero64: Dict[str, float] | None) -> None:
+    """seroprevalence/ene_covid_validation.csv (ResultAggregator::performENECOVIDValidation :485-518,
+    AnalysisWriter::writeEneCovidValidation :479-510): fixed 5 digits.  sero64: median / q025 / q975 of
+    seroprevalence_day64 from the metric summary, or None (no model row, as when the summary lacks the metric)."""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    day = ENE_COVID["target_day"]
+    with open(path, "w") as fh:
+        fh.write("source,median_seroprevalence,lower_95ci,upper_95ci,target_day\n")
+        if sero64 is not None and "median" in sero64:
+            fh.write("Model,%.5f,%.5f,%.5f,%.5f\n" % (sero64["median"], sero64["q025"], sero64["q975"], day))
+        fh.write("ENE_COVID,%.5f,%.5f,%.5f,%.5f\n" % (ENE_COVID["mean"], ENE_COVID["lower_ci"], ENE_COVID["upper_ci"], day))
+
+
+def sero64_summary(metrics: np.ndarray) -> Dict[str, float] | None:
+    """median / q025 / q975 of seroprevalence_day64 over the valid rows of a metric table, by write_metrics_summary's rule."""
+    m = np.asarray(metrics)
+    v = np.sort(m[np.isfinite(m[:, 0]), 11])
+    if len(v) == 0:
+        return None
+    return {"median": _quantile_sorted(v, 0.5), "q025": _quantile_sorted(v, 0.025), "q975": _quantile_sorted(v, 0.975)}
+
+
 def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: np.ndarray, names: List[str], n_age: int,
-                                observed: Dict[str, np.ndarray] | None = None, burn_in: int = 0, thinning: int = 1) -> None:
-    """Everything PostCalibrationAnalysis.py loads (except the scenario comparison, which is not on this path), under
-    out_base, from one sepaihrd_ensemble_quantiles result (keys ppc, sero, rt, metrics; quantiles at PPC_PROBS)."""
+                                observed: Dict[str, np.ndarray] | None = None, burn_in: int = 0, thinning: int = 1,
+                                scenarios=None, ene_covid: bool = False) -> None:
+    """Everything PostCalibrationAnalysis.py loads under out_base, from one sepaihrd_ensemble_quantiles result (keys
+    ppc, sero, rt, metrics; quantiles at PPC_PROBS).  scenarios (rows as write_scenario_comparison takes them):
+    scenarios/scenario_comparison.csv; ene_covid: seroprevalence/ene_covid_validation.csv from the metric table."""
     times = np.asarray(times, dtype=np.float64)
     write_posterior_predictive(os.path.join(out_base, "posterior_predictive"), times[times >= 0], ensemble["ppc"], observed or {})
     write_parameter_posteriors(os.path.join(out_base, "parameter_posteriors"), samples, names, burn_in, thinning)
@@ -618,3 +711,8 @@ def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: n
     if ensemble.get("metrics") is not None:
         write_batch_metrics(os.path.join(out_base, "mcmc_batches", "batch_0.csv"), ensemble["metrics"], n_age)
         write_metrics_summary(os.path.join(out_base, "mcmc_aggregated", "metrics_summary.csv"), ensemble["metrics"], n_age)
+    if scenarios is not None:
+        write_scenario_comparison(os.path.join(out_base, "scenarios", "scenario_comparison.csv"), scenarios)
+    if ene_covid:
+        sero64 = sero64_summary(ensemble["metrics"]) if ensemble.get("metrics") is not None else None
+        write_ene_covid_validation(os.path.join(out_base, "seroprevalence", "ene_covid_validation.csv"), sero64)

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sepaihrd_device.h"
@@ -34,8 +35,9 @@ struct sepaihrd_ctx {
     std::vector<double> host_N;  // population sizes (ensemble seroprevalence)
     // buffers of sepaihrd_ensemble_quantiles, kept between calls (grow-only): allocating tens of GB per call
     // costs more than the kernels at large ensembles
-    void* ens_buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t ens_cap[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // (slots 0-8; sepaihrd_scenario_ensemble shares them by role and adds 9-12)
+    void* ens_buf[13] = {};
+    size_t ens_cap[13] = {};
     std::string last_error;
     // staging buffers for the host-pointer entry point (grown on demand)
     size_t cap_B = 0;
@@ -852,6 +854,202 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx* ctx, const double* theta, int S, c
     if (n_valid)
         HIP_TRY(hipMemcpy(n_valid, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
     cleanup();
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_scenario_ensemble(sepaihrd_ctx* ctx, const double* theta, int S, const double* kappa_mult, int K, int n_kappa,
+                               const double* probs, int n_probs, double* ppc_quantiles, double* sero_quantiles,
+                               double* rt_quantiles, double* metrics, double* metric_summary, double* diff_quantiles,
+                               int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (S <= 0 || K <= 0 || !theta || !kappa_mult || !probs || n_probs <= 0 || n_probs > 1024) {
+        ctx->last_error = "scenario_ensemble: need S > 0, K > 0, theta, kappa_mult and probs (1..1024)";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) {
+            ctx->last_error = "scenario_ensemble: probabilities must lie in [0, 1]";
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    const DevProblem& dp = ctx->dp;
+    if (n_kappa != dp.nk) {
+        ctx->last_error = "scenario_ensemble: the multiplier table must have one column per kappa value";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    for (size_t i = 0; i < (size_t)K * n_kappa; ++i)
+        if (!(std::isfinite(kappa_mult[i]) && kappa_mult[i] >= 0.0)) {
+            ctx->last_error = "scenario_ensemble: kappa multipliers must be finite and >= 0";
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    if (ctx->pending_B > 0) {
+        ctx->last_error = "scenario_ensemble: a sepaihrd_eval_batch_begin is pending on this context";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (ctx->precision != SEPAIHRD_PRECISION_F64) {
+        ctx->last_error = "scenario_ensemble: the ensemble summaries read the fp64 integrator's parked increments (set precision F64)";
+        return SEPAIHRD_E_UNSUPPORTED;
+    }
+    if (dp.n > 16) {
+        ctx->last_error = "scenario_ensemble: the metric table needs Rt trajectories, built for at most 16 age classes";
+        return SEPAIHRD_E_UNSUPPORTED;
+    }
+    const int Tp = dp.T - dp.runup_offset;
+    if (Tp <= 0) {
+        ctx->last_error = "scenario_ensemble: no output time >= 0";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    // scenario k's samples are chains k S_str .. k S_str + S - 1: S_str = S rounded up to whole waves' worth of chains, so that
+    // every scenario's parked increments start on a wave boundary of the workspace (the ensemble passes then read it in place)
+    const size_t cpw = (size_t)(WAVE / dp.lpc);
+    const size_t S_str = ((size_t)S + cpw - 1) / cpw * cpw;
+    const size_t B = (size_t)(K - 1) * S_str + (size_t)S;  // the last scenario needs no padding chains
+    if (B > (size_t)std::numeric_limits<int32_t>::max() / 2) {
+        ctx->last_error = "scenario_ensemble: K x S chains exceed one launch (the workspace is sized by a 32-bit chain count)";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    int S_pad = WAVE;
+    while (S_pad < S && S_pad < ENSEMBLE_MAX_SAMPLES) S_pad <<= 1;
+    const bool big = S > ENSEMBLE_MAX_SAMPLES;
+    if (big) S_pad = (S + WAVE - 1) / WAVE * WAVE;
+    const size_t chains = (B + cpw - 1) / cpw * cpw;
+
+    const bool want_sero = sero_quantiles != nullptr;
+    const int W = 12 + 4 * dp.n;
+    const size_t P = (size_t)ctx->P;
+    const size_t n_ppc = (size_t)6 * n_probs * Tp * dp.n;  // per scenario
+    const size_t n_sero = want_sero ? (size_t)n_probs * dp.T : 0;
+    const size_t n_rt = (size_t)n_probs * dp.T;
+    const size_t n_q = n_ppc + n_sero + n_rt;
+    const size_t n_vals = ((size_t)6 * Tp * dp.n + (want_sero ? dp.T : 0) + dp.T) * S_pad;
+    const size_t n_svals = (size_t)2 * K * W * S_pad;
+    const size_t n_metrics = (size_t)K * S * W;
+    const size_t n_summary = (size_t)K * W * (2 + n_probs), n_diff = (size_t)K * W * n_probs;
+    const size_t n_scratch =
+        big ? std::max<size_t>((size_t)S_pad, std::min<size_t>(std::max(n_vals, n_svals), (size_t)1 << 28) / S_pad * S_pad) : 0;
+    // K x S within one launch: the device buffers below plus the likelihood workspace must fit the device's memory
+    // (the trajectories dominate: K S T 11 n doubles); larger requests are refused before anything is allocated
+    const size_t need_bytes =
+        sizeof(double) * (chains * P + chains + n_vals + chains * dp.T * NUM_COMP * dp.n + (size_t)K * n_q + n_metrics + n_scratch +
+                          (size_t)K * n_kappa + n_svals + n_summary + n_diff + (size_t)n_probs) +
+        sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) + sizeof(int32_t) * (chains + 3 * (size_t)K);
+    size_t device_bytes = 0;
+    HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
+    if (need_bytes > device_bytes) {
+        ctx->last_error = "scenario_ensemble: K x S = " + std::to_string((size_t)K * S) + " runs need " +
+                          std::to_string(need_bytes >> 20) + " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
+                          " MiB: split the scenarios or the samples over several calls";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    int rc = ensure_workspace(ctx, chains);
+    if (rc != SEPAIHRD_OK) return rc;
+    auto cleanup = [&]() {};  // the buffers stay with the context (grow-only, shared by role with sepaihrd_ensemble_quantiles)
+    auto dalloc = [&](int k, auto** p, size_t elems) {
+        const size_t bytes = std::max<size_t>(elems * sizeof(**p), 8);
+        if (ctx->ens_cap[k] < bytes) {
+            if (ctx->ens_buf[k]) (void)hipFree(ctx->ens_buf[k]);
+            ctx->ens_buf[k] = nullptr;
+            ctx->ens_cap[k] = 0;
+            if (hipMalloc(&ctx->ens_buf[k], bytes) != hipSuccess) return false;
+            ctx->ens_cap[k] = bytes;
+        }
+        *p = static_cast<std::remove_reference_t<decltype(*p)>>(ctx->ens_buf[k]);
+        return true;
+    };
+    double *d_theta = nullptr, *d_ll = nullptr, *d_mult = nullptr, *d_traj = nullptr, *d_vals = nullptr, *d_svals = nullptr,
+           *d_probs = nullptr, *d_q = nullptr, *d_metrics = nullptr, *d_summary = nullptr, *d_scratch = nullptr;
+    int32_t *d_nv = nullptr, *d_counts = nullptr;
+    if (!dalloc(0, &d_theta, chains * P) || !dalloc(1, &d_ll, chains) || !dalloc(2, &d_vals, n_vals) ||
+        !dalloc(3, &d_traj, chains * dp.T * NUM_COMP * dp.n) || !dalloc(4, &d_probs, (size_t)n_probs) ||
+        !dalloc(5, &d_q, (size_t)K * n_q) || !dalloc(6, &d_nv, (size_t)K) || !dalloc(7, &d_metrics, n_metrics) ||
+        !dalloc(8, &d_scratch, n_scratch) || !dalloc(9, &d_mult, (size_t)K * n_kappa) || !dalloc(10, &d_svals, n_svals) ||
+        !dalloc(11, &d_summary, n_summary + n_diff) || !dalloc(12, &d_counts, (size_t)2 * K)) {
+        ctx->last_error = "scenario_ensemble: device allocation failed";
+        return SEPAIHRD_E_HIP;
+    }
+    // every scenario integrates the same samples; the padding chains repeat the scenario's first sample and are never read
+    std::vector<double> h_theta(B * P);
+    for (size_t c = 0; c < B; ++c) {
+        const size_t s = c % S_str;
+        std::memcpy(&h_theta[c * P], theta + (s < (size_t)S ? s : 0) * P, P * sizeof(double));
+    }
+    HIP_TRY(hipMemcpy(d_theta, h_theta.data(), B * P * sizeof(double), hipMemcpyHostToDevice), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
+    HIP_TRY(hipMemcpy(d_mult, kappa_mult, (size_t)K * n_kappa * sizeof(double), hipMemcpyHostToDevice), ctx,
+            { cleanup(); return SEPAIHRD_E_HIP; });
+    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
+    EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, d_traj, ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
+    rc = fence_before(ctx, nullptr);
+    if (rc != SEPAIHRD_OK) { cleanup(); return rc; }
+    // the integrator scales kappa per scenario (scenario build of the kernels); the Rt and metric passes read ctx->dp, unscaled
+    rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_eval_scenario_fma(dp, ctx->solver, d_theta, (int)B, out, nullptr, d_mult, (int)S_str)
+                                          : launch_eval_scenario_strict(dp, ctx->solver, d_theta, (int)B, out, nullptr, d_mult, (int)S_str);
+    if (rc != 0) {
+        cleanup();
+        ctx->last_error = rc == -4 ? "unsupported lanes-per-chain" : "kernel launch failed";
+        return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
+    }
+    double total_pop = 0.0;
+    for (int i = 0; i < dp.n; ++i) total_pop += ctx->host_N[(size_t)i];
+    // series, seroprevalence, Rt, metric table and their quantiles: once per scenario, on the scenario's block of chains
+    for (int k = 0; k < K && rc == 0; ++k) {
+        const size_t c0 = (size_t)k * S_str;
+        EnsembleArgs a{};
+        a.S = S; a.S_pad = S_pad; a.lpc = dp.lpc; a.n = dp.n; a.T = dp.T; a.Tp = Tp; a.runup_offset = dp.runup_offset;
+        a.n_probs = n_probs;
+        a.cum_stride = chains * dp.lpc;
+        a.cum = ctx->ws_cum + cum_index(dp.T, c0 * dp.lpc, 0, 0);  // c0 lpc is a multiple of WAVE
+        a.wstatus = ctx->ws_status + c0;
+        a.traj = d_traj + c0 * dp.T * NUM_COMP * dp.n;
+        a.total_pop = total_pop;
+        a.vals = d_vals; a.probs = d_probs;
+        a.q_out = d_q + (size_t)k * n_q;
+        a.sero_out = want_sero ? a.q_out + n_ppc : nullptr;
+        a.n_valid = d_nv + k;
+        a.rt_out = a.q_out + n_ppc + n_sero;
+        a.rt_segment0 = 6 * Tp * dp.n + (want_sero ? dp.T : 0);
+        a.pb = &ctx->dp;
+        a.theta = d_theta + c0 * P;
+        a.metrics_out = d_metrics + (size_t)k * S * W;
+        a.sort_scratch = big ? d_scratch : nullptr;
+        a.sort_scratch_doubles = n_scratch;
+        rc = launch_ensemble_summaries(a, nullptr);
+    }
+    if (rc == 0) {
+        ScenarioArgs sa{};
+        sa.K = K; sa.S = S; sa.S_pad = S_pad; sa.W = W; sa.n_probs = n_probs; sa.probs = d_probs;
+        sa.metrics = d_metrics; sa.wstatus = ctx->ws_status; sa.status_stride = S_str;
+        sa.vals = d_svals; sa.counts = d_counts;
+        sa.summary_out = d_summary; sa.diff_out = d_summary + n_summary;
+        sa.sort_scratch = big ? d_scratch : nullptr;
+        sa.sort_scratch_doubles = n_scratch;
+        rc = launch_scenario_summaries(sa, nullptr);
+    }
+    if (rc != 0) {
+        cleanup();
+        ctx->last_error = "scenario summary launch failed";
+        return SEPAIHRD_E_HIP;
+    }
+    HIP_TRY(hipDeviceSynchronize(), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
+    bool ok = true;
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        if (ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+    };
+    for (int k = 0; k < K; ++k) {
+        const double* q = d_q + (size_t)k * n_q;
+        fetch(ppc_quantiles ? ppc_quantiles + (size_t)k * n_ppc : nullptr, q, n_ppc * sizeof(double));
+        fetch(want_sero ? sero_quantiles + (size_t)k * n_sero : nullptr, q + n_ppc, n_sero * sizeof(double));
+        fetch(rt_quantiles ? rt_quantiles + (size_t)k * n_rt : nullptr, q + n_ppc + n_sero, n_rt * sizeof(double));
+        fetch(status ? status + (size_t)k * S : nullptr, ctx->ws_status + (size_t)k * S_str, (size_t)S * sizeof(int32_t));
+    }
+    fetch(metrics, d_metrics, n_metrics * sizeof(double));
+    fetch(metric_summary, d_summary, n_summary * sizeof(double));
+    fetch(diff_quantiles, d_summary + n_summary, n_diff * sizeof(double));
+    fetch(n_valid, d_nv, (size_t)K * sizeof(int32_t));
+    cleanup();
+    if (!ok) {
+        ctx->last_error = "scenario_ensemble: copy of the results failed";
+        return SEPAIHRD_E_HIP;
+    }
     return SEPAIHRD_OK;
 }
 

@@ -100,6 +100,14 @@ int launch_eval_strict(const DevProblem& pb, int solver, const double* d_theta, 
                        const EvalOutputs& out, void* stream);
 int launch_eval_fma(const DevProblem& pb, int solver, const double* d_theta, int B,
                     const EvalOutputs& out, void* stream);
+// the same launches from the scenario build of the kernel source (csrc/Makefile kernels_scen_*.o, -DSEPAIHRD_SCENARIO=1):
+// chain c integrates with kappa_values[i] x d_kappa_mult[(c / stride) nk + i] ([K][nk] device), applied after the
+// constraints where the chain forms its beta kappa segment values.  Returns once the launch has completed (the table
+// reaches the kernels through device globals of that build, so launches are serialised).
+int launch_eval_scenario_strict(const DevProblem& pb, int solver, const double* d_theta, int B, const EvalOutputs& out, void* stream,
+                                const double* d_kappa_mult, int stride);
+int launch_eval_scenario_fma(const DevProblem& pb, int solver, const double* d_theta, int B, const EvalOutputs& out, void* stream,
+                             const double* d_kappa_mult, int stride);
 // 1 when a launch of B chains parks its daily increments in the ctx-owned workspace (EvalOutputs::cum / rows /
 // wstatus must then be sized for it), 0 when the likelihood is evaluated inside the integrator, < 0 on error.
 // Decided in the kernel translation unit, next to the launch code that takes the same branches.
@@ -145,6 +153,23 @@ struct EnsembleArgs {
     size_t sort_scratch_doubles;
 };
 int launch_ensemble_summaries(const EnsembleArgs& a, void* stream);
+// scenario analysis over the metric tables of K scenarios (sepaihrd_scenario_ensemble): per (scenario, metric column) mean,
+// population std_dev and quantiles of the valid samples, and quantiles of the paired differences against scenario 0
+struct ScenarioArgs {
+    int K, S, S_pad, W;       // scenarios, samples per scenario, segment stride (as EnsembleArgs::S_pad), metric columns
+    int n_probs;
+    const double* probs;      // [n_probs] device
+    const double* metrics;    // [K][S][W] device
+    const int32_t* wstatus;   // integrator status, sample s of scenario k at k status_stride + s
+    size_t status_stride;
+    double* vals;             // [2 K W][S_pad] scratch: the metric segments, then the paired-difference segments
+    int32_t* counts;          // [2 K] device: valid samples per scenario, then valid in both the scenario and scenario 0
+    double* summary_out;      // [K][W][2 + n_probs] mean, std_dev, quantiles, or null
+    double* diff_out;         // [K][W][n_probs] quantiles of metric[k][s] - metric[0][s], or null
+    double* sort_scratch;     // as EnsembleArgs (S_pad > ENSEMBLE_MAX_SAMPLES)
+    size_t sort_scratch_doubles;
+};
+int launch_scenario_summaries(const ScenarioArgs& a, void* stream);
 
 inline int lanes_per_chain(int n) {
     int l = 1;

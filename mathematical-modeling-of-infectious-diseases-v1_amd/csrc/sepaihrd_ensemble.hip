@@ -348,13 +348,9 @@ __device__ __forceinline__ void write_quantile(const EnsembleArgs& a, int n_seri
     }
 }
 
-// Pass 2: one workgroup per segment; bitonic sort in LDS, then the interpolated quantiles.
-__global__ void ensemble_quantile_kernel(const EnsembleArgs a, const int n_series_segments) {
-    extern __shared__ double seg[];
-    const int Np = a.S_pad;
+// Np (a power of two) doubles of src sorted ascending into seg (LDS) by the whole workgroup
+__device__ __forceinline__ void lds_bitonic_sort(double* seg, const double* src, const int Np) {
     const int tid = threadIdx.x, BS = blockDim.x;
-    const size_t sid = blockIdx.x;
-    const double* src = a.vals + sid * (size_t)Np;
     for (int i = tid; i < Np; i += BS) seg[i] = src[i];
     __syncthreads();
     for (int k = 2; k <= Np; k <<= 1) {
@@ -369,6 +365,16 @@ __global__ void ensemble_quantile_kernel(const EnsembleArgs a, const int n_serie
             __syncthreads();
         }
     }
+}
+
+// Pass 2: one workgroup per segment; bitonic sort in LDS, then the interpolated quantiles.
+__global__ void ensemble_quantile_kernel(const EnsembleArgs a, const int n_series_segments) {
+    extern __shared__ double seg[];
+    const int Np = a.S_pad;
+    const int tid = threadIdx.x, BS = blockDim.x;
+    const size_t sid = blockIdx.x;
+    const double* src = a.vals + sid * (size_t)Np;
+    lds_bitonic_sort(seg, src, Np);
     const int nv = *a.n_valid;
     for (int p = tid; p < a.n_probs; p += BS) write_quantile(a, n_series_segments, sid, p, nv, seg);
 }
@@ -383,7 +389,190 @@ __global__ void ensemble_quantile_sorted_kernel(const EnsembleArgs a, const int 
     write_quantile(a, n_series_segments, (size_t)(first_segment + g), p, *a.n_valid, sorted + (size_t)g * a.S_pad);
 }
 
+// ---- scenario analysis (sepaihrd_scenario_ensemble): metric table [K][S][W] -> per-scenario summaries ----
+// Segment (k, col) of the metric values and of the paired differences metric[k][s] - metric[0][s]; samples that failed
+// (in scenario k, or for a difference in k or in the baseline) are +inf and sort to the end.
+__global__ __launch_bounds__(256) void scenario_gather_kernel(const ScenarioArgs a) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = (int)(idx % a.S_pad);
+    const size_t seg = idx / a.S_pad;  // k W + col
+    if (seg >= (size_t)a.K * a.W) return;
+    const int k = (int)(seg / a.W), col = (int)(seg % a.W);
+    double v = INFINITY, d = INFINITY;
+    if (s < a.S) {
+        const bool ok = a.wstatus[(size_t)k * a.status_stride + s] == 0, ok0 = a.wstatus[s] == 0;
+        const double x = a.metrics[((size_t)k * a.S + s) * a.W + col];
+        if (ok) v = x;
+        if (ok && ok0) d = x - a.metrics[(size_t)s * a.W + col];
+    }
+    a.vals[seg * a.S_pad + s] = v;
+    a.vals[((size_t)a.K * a.W + seg) * a.S_pad + s] = d;
+}
+
+// valid samples per scenario ([0, K)) and valid in both the scenario and the baseline ([K, 2K)): one block each
+__global__ __launch_bounds__(256) void scenario_count_kernel(const ScenarioArgs a) {
+    __shared__ int part[256];
+    const int k = blockIdx.x % a.K;
+    const bool paired = (int)blockIdx.x >= a.K;
+    int c = 0;
+    for (int s = threadIdx.x; s < a.S; s += 256)
+        c += a.wstatus[(size_t)k * a.status_stride + s] == 0 && (!paired || a.wstatus[s] == 0);
+    part[threadIdx.x] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.counts[blockIdx.x] = part[0];
+}
+
+// mean and population standard deviation of every (k, col) over the valid samples in sample order: the operation
+// sequence of HipPosteriorEnsemble::aggregateMetrics (ResultAggregator::aggregateBatchMetrics, lazy variance).  Reads the
+// gathered segment (sample order, contiguous) before it is sorted; the loads of 8 samples are issued ahead of their sums.
+constexpr int MOMENT_BATCH = 8;
+__global__ __launch_bounds__(64) void scenario_moments_kernel(const ScenarioArgs a) {
+    const int seg = blockIdx.x * blockDim.x + threadIdx.x;
+    if (seg >= a.K * a.W) return;
+    const int k = seg / a.W;
+    const int32_t* st = a.wstatus + (size_t)k * a.status_stride;
+    const double* v = a.vals + (size_t)seg * a.S_pad;  // +inf where the sample failed
+    double* out = a.summary_out + (size_t)seg * (2 + a.n_probs);
+    const int nv = a.counts[k];
+    if (nv == 0) { out[0] = NAN; out[1] = NAN; return; }
+    double mean = 0.0;
+    for (int s0 = 0; s0 < a.S; s0 += MOMENT_BATCH) {
+        double x[MOMENT_BATCH];
+        bool ok[MOMENT_BATCH];
+#pragma unroll
+        for (int d = 0; d < MOMENT_BATCH; ++d) {
+            ok[d] = s0 + d < a.S && st[s0 + d] == 0;
+            x[d] = ok[d] ? v[s0 + d] : 0.0;
+        }
+#pragma unroll
+        for (int d = 0; d < MOMENT_BATCH; ++d)
+            if (ok[d]) mean += x[d];
+    }
+    mean /= (double)(size_t)nv;
+    double var = 0.0;
+    for (int s0 = 0; s0 < a.S; s0 += MOMENT_BATCH) {
+        double x[MOMENT_BATCH];
+        bool ok[MOMENT_BATCH];
+#pragma unroll
+        for (int d = 0; d < MOMENT_BATCH; ++d) {
+            ok[d] = s0 + d < a.S && st[s0 + d] == 0;
+            x[d] = ok[d] ? v[s0 + d] : 0.0;
+        }
+#pragma unroll
+        for (int d = 0; d < MOMENT_BATCH; ++d)
+            if (ok[d]) var += (x[d] - mean) * (x[d] - mean);
+    }
+    var /= (double)(size_t)nv;
+    out[0] = mean;
+    out[1] = sqrt(var);
+}
+
+// quantile p of sorted segment `sid` (metric segments first, then the paired differences) into its output slot
+__device__ __forceinline__ void scenario_write_quantile(const ScenarioArgs& a, size_t sid, int p, const double* seg) {
+    const bool paired = sid >= (size_t)a.K * a.W;
+    const size_t cell = paired ? sid - (size_t)a.K * a.W : sid;
+    const int nv = a.counts[(paired ? a.K : 0) + (int)(cell / a.W)];
+    double r = NAN;
+    if (nv > 0) {
+        const double pos = a.probs[p] * (double)(size_t)(nv - 1);
+        const size_t idx = (size_t)pos;
+        const double frac = pos - (double)idx;
+        r = (idx + 1 < (size_t)nv) ? seg[idx] * (1.0 - frac) + seg[idx + 1] * frac : seg[idx];
+    }
+    if (paired) {
+        if (a.diff_out != nullptr) a.diff_out[cell * a.n_probs + p] = r;
+    } else if (a.summary_out != nullptr) {
+        a.summary_out[cell * (2 + a.n_probs) + 2 + p] = r;
+    }
+}
+
+__global__ void scenario_quantile_kernel(const ScenarioArgs a) {
+    extern __shared__ double seg[];
+    const size_t sid = blockIdx.x;
+    lds_bitonic_sort(seg, a.vals + sid * (size_t)a.S_pad, a.S_pad);
+    for (int p = threadIdx.x; p < a.n_probs; p += blockDim.x) scenario_write_quantile(a, sid, p, seg);
+}
+
+__global__ void scenario_quantile_sorted_kernel(const ScenarioArgs a, const double* sorted, const int first_segment, const int n_group) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)n_group * a.n_probs) return;
+    const int g = (int)(idx / a.n_probs), p = (int)(idx % a.n_probs);
+    scenario_write_quantile(a, (size_t)(first_segment + g), p, sorted + (size_t)g * a.S_pad);
+}
+
+// Segments of S_pad doubles (more than the LDS sort holds) sorted in groups by rocPRIM's segmented radix sort into
+// `scratch`; pick(first, n_group) launches the interpolation of each sorted group.  Synchronises the stream.
+template <class Pick>
+int sort_segments_global(const double* vals, int segments, int S_pad, double* scratch, size_t scratch_doubles, hipStream_t st,
+                         Pick pick) {
+    // group size bounded by the scratch buffer
+    int group = (int)(scratch_doubles / (size_t)S_pad);
+    if (group > segments) group = segments;
+    if (group < 1 || (size_t)group * S_pad >= (size_t)1 << 31) return -4;
+    std::vector<unsigned> offs((size_t)group + 1);
+    for (int g = 0; g <= group; ++g) offs[(size_t)g] = (unsigned)((size_t)g * S_pad);
+    unsigned* d_offs = nullptr;
+    if (hipMalloc((void**)&d_offs, offs.size() * sizeof(unsigned)) != hipSuccess) return -3;
+    int rc = 0;
+    if (hipMemcpyAsync(d_offs, offs.data(), offs.size() * sizeof(unsigned), hipMemcpyHostToDevice, st) != hipSuccess) rc = -3;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    for (int first = 0; first < segments && rc == 0; first += group) {
+        const int ng = (segments - first < group) ? segments - first : group;
+        const double* in = vals + (size_t)first * S_pad;
+        const unsigned size = (unsigned)((size_t)ng * S_pad);
+        size_t need = 0;
+        if (rocprim::segmented_radix_sort_keys(nullptr, need, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
+                                               st) != hipSuccess) { rc = -3; break; }
+        if (need > tmp_bytes) {
+            if (tmp) (void)hipFree(tmp);
+            tmp = nullptr;
+            if (hipMalloc(&tmp, need) != hipSuccess) { rc = -3; break; }
+            tmp_bytes = need;
+        }
+        if (rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
+                                               st) != hipSuccess) { rc = -3; break; }
+        pick(first, ng);
+    }
+    (void)hipStreamSynchronize(st);
+    if (tmp) (void)hipFree(tmp);
+    (void)hipFree(d_offs);
+    return (rc == 0 && hipGetLastError() == hipSuccess) ? 0 : -3;
+}
+
 }  // namespace
+
+int launch_scenario_summaries(const ScenarioArgs& a, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool in_lds = a.S_pad <= ENSEMBLE_MAX_SAMPLES;
+    if (a.K <= 0 || a.S <= 0 || a.W <= 0 || a.S_pad < WAVE || a.S > a.S_pad ||
+        (in_lds ? (a.S_pad & (a.S_pad - 1)) != 0 : a.S_pad % WAVE != 0))
+        return -4;
+    const int segments = 2 * a.K * a.W;
+    hipLaunchKernelGGL(scenario_count_kernel, dim3(2 * a.K), dim3(256), 0, st, a);
+    const size_t cells = (size_t)a.K * a.W * a.S_pad;
+    hipLaunchKernelGGL(scenario_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a);
+    if (a.summary_out != nullptr)
+        hipLaunchKernelGGL(scenario_moments_kernel, dim3((unsigned)((a.K * a.W + 63) / 64)), dim3(64), 0, st, a);
+    if (!in_lds)
+        return sort_segments_global(a.vals, segments, a.S_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
+            const size_t work = (size_t)ng * a.n_probs;
+            hipLaunchKernelGGL(scenario_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a,
+                               a.sort_scratch, first, ng);
+        });
+    const int threads = a.S_pad / 2 < 1024 ? a.S_pad / 2 : 1024;
+    const size_t lds = (size_t)a.S_pad * sizeof(double);
+    if (lds > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&scenario_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+        return -3;
+    hipLaunchKernelGGL(scenario_quantile_kernel, dim3(segments), dim3(threads), lds, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -408,40 +597,11 @@ int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
     if (!in_lds) {
         // segments of S_pad doubles sorted in groups by rocPRIM's segmented radix sort (8 passes over the keys)
         // into a scratch buffer, quantiles picked from it; group size bounded by the scratch buffer
-        int group = (int)(a.sort_scratch_doubles / (size_t)a.S_pad);
-        if (group > segments) group = segments;
-        if (group < 1 || (size_t)group * a.S_pad >= (size_t)1 << 31) return -4;
-        std::vector<unsigned> offs((size_t)group + 1);
-        for (int g = 0; g <= group; ++g) offs[(size_t)g] = (unsigned)((size_t)g * a.S_pad);
-        unsigned* d_offs = nullptr;
-        if (hipMalloc((void**)&d_offs, offs.size() * sizeof(unsigned)) != hipSuccess) return -3;
-        int rc = 0;
-        if (hipMemcpyAsync(d_offs, offs.data(), offs.size() * sizeof(unsigned), hipMemcpyHostToDevice, st) != hipSuccess) rc = -3;
-        void* tmp = nullptr;
-        size_t tmp_bytes = 0;
-        for (int first = 0; first < segments && rc == 0; first += group) {
-            const int ng = (segments - first < group) ? segments - first : group;
-            const double* in = a.vals + (size_t)first * a.S_pad;
-            const unsigned size = (unsigned)((size_t)ng * a.S_pad);
-            size_t need = 0;
-            if (rocprim::segmented_radix_sort_keys(nullptr, need, in, a.sort_scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
-                                                   st) != hipSuccess) { rc = -3; break; }
-            if (need > tmp_bytes) {
-                if (tmp) (void)hipFree(tmp);
-                tmp = nullptr;
-                if (hipMalloc(&tmp, need) != hipSuccess) { rc = -3; break; }
-                tmp_bytes = need;
-            }
-            if (rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, a.sort_scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
-                                                   st) != hipSuccess) { rc = -3; break; }
+        return sort_segments_global(a.vals, segments, a.S_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
             const size_t work = (size_t)ng * a.n_probs;
             hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a,
                                n_series_segments, a.sort_scratch, first, ng);
-        }
-        (void)hipStreamSynchronize(st);
-        if (tmp) (void)hipFree(tmp);
-        (void)hipFree(d_offs);
-        return (rc == 0 && hipGetLastError() == hipSuccess) ? 0 : -3;
+        });
     }
     const int threads = a.S_pad / 2 < 1024 ? a.S_pad / 2 : 1024;
     const size_t lds = (size_t)a.S_pad * sizeof(double);

@@ -45,6 +45,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <mutex>
 #include <utility>
 
 #include "sepaihrd_device.h"
@@ -63,6 +64,25 @@ namespace sepaihrd {
 namespace {
 
 #include "sepaihrd_dev_common.inc"  // cross-lane helpers, tableaus, constraints, schedule lookup, log_pos
+
+// kappa value `ik` of `chain` as the integrator sees it.  The scenario build (-DSEPAIHRD_SCENARIO=1, csrc/Makefile
+// kernels_scen_*.o, launch_eval_scenario_*) scales it by the chain's row of the multiplier table, once per chain outside the
+// step loop, after the constraints; the shipped builds compile the identity, so their kernels are those without scenarios.
+#ifndef SEPAIHRD_SCENARIO
+#define SEPAIHRD_SCENARIO 0
+#endif
+#if SEPAIHRD_SCENARIO
+__device__ const double* g_kappa_mult;  // [K][nk]
+__device__ int g_kappa_mult_stride;     // chains per scenario
+#endif
+__device__ __forceinline__ double scenario_kappa(const DevProblem& pb, long long chain, int ik, double kappa) {
+#if SEPAIHRD_SCENARIO
+    return kappa * g_kappa_mult[(int)chain / g_kappa_mult_stride * pb.nk + ik];
+#else
+    (void)pb; (void)chain; (void)ik;
+    return kappa;
+#endif
+}
 
 // ----------------------------------------------------------------------------------
 // per-lane model record
@@ -498,7 +518,7 @@ __global__ __launch_bounds__(WAVE, WPS) void sepaihrd_eval_kernel(const DevProbl
         double* bkv = lds_bk + grp * (pb.nm + 1);  // own region even for shadow groups
         for (int j = age; j <= pb.nm; j += LPC) {
             const double beta = (pb.nb > 0) ? scalar_slot(SS_SCHEDULE0 + pb.seg_ib[j]) : scalar_slot(SS_BETA);
-            const double kappa = scalar_slot(SS_SCHEDULE0 + pb.nb + pb.seg_ik[j]);
+            const double kappa = scenario_kappa(pb, chain, pb.seg_ik[j], scalar_slot(SS_SCHEDULE0 + pb.nb + pb.seg_ik[j]));
             bkv[j] = beta * kappa;
         }
         sch.bkv = bkv;
@@ -1493,6 +1513,27 @@ __global__ __launch_bounds__(WAVE) void log_values_kernel(const double* __restri
 
 }  // namespace
 
+#if SEPAIHRD_SCENARIO
+// scenario build (csrc/Makefile kernels_scen_*.o): the launch entry point only
+#if SEPAIHRD_ARITH_FMA
+#define SEP_LAUNCH launch_eval_scenario_fma
+#else
+#define SEP_LAUNCH launch_eval_scenario_strict
+#endif
+int SEP_LAUNCH(const DevProblem& pb, int solver, const double* d_theta, int B, const EvalOutputs& out, void* stream,
+               const double* d_kappa_mult, int stride) {
+    static std::mutex serial;  // the table lives in device globals: one scenario launch in flight at a time
+    std::lock_guard<std::mutex> lock(serial);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (stride <= 0 || d_kappa_mult == nullptr ||
+        hipMemcpyToSymbolAsync(HIP_SYMBOL(g_kappa_mult), &d_kappa_mult, sizeof(d_kappa_mult), 0, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyToSymbolAsync(HIP_SYMBOL(g_kappa_mult_stride), &stride, sizeof(stride), 0, hipMemcpyHostToDevice, st) != hipSuccess)
+        return -3;
+    const int rc = [&]() -> int { SEP_DISPATCH(launch_one, pb, d_theta, B, out, stream) }();
+    if (hipStreamSynchronize(st) != hipSuccess) return -3;
+    return rc;
+}
+#else
 #if SEPAIHRD_ARITH_FMA
 #define SEP_LAUNCH launch_eval_fma
 #define SEP_NEEDS_WS launch_needs_workspace_fma
@@ -1530,5 +1571,6 @@ int poisson_log_values(const double* d_x, int n, double* d_out, void* stream) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #endif
+#endif  // SEPAIHRD_SCENARIO
 
 }  // namespace sepaihrd

@@ -499,7 +499,7 @@ __global__ __launch_bounds__(FUSED ? 8 * WAVE : WAVE, 2) void sepaihrd_eval_quad
         double* bkv = lds_bk + grp * (pb.nm + 1);
         for (int j = lane % QUAD_LANES; j <= pb.nm; j += QUAD_LANES) {
             const double beta = (pb.nb > 0) ? scalar_slot(SS_SCHEDULE0 + pb.seg_ib[j]) : scalar_slot(SS_BETA);
-            const double kappa = scalar_slot(SS_SCHEDULE0 + pb.nb + pb.seg_ik[j]);
+            const double kappa = scenario_kappa(pb, chain, pb.seg_ik[j], scalar_slot(SS_SCHEDULE0 + pb.nb + pb.seg_ik[j]));
             bkv[j] = beta * kappa;
         }
         sch.bkv = bkv;

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(WAVE, 2) void sepaihrd_eval_wave_kernel(const DevPr
     sch.me = lds_mends;
     for (int j = lane; j <= pb.nm; j += WAVE) {
         const double beta = (pb.nb > 0) ? scalar_slot(SS_SCHEDULE0 + pb.seg_ib[j]) : scalar_slot(SS_BETA);
-        const double kappa = scalar_slot(SS_SCHEDULE0 + pb.nb + pb.seg_ik[j]);
+        const double kappa = scenario_kappa(pb, chain, pb.seg_ik[j], scalar_slot(SS_SCHEDULE0 + pb.nb + pb.seg_ik[j]));
         lds_bk[j] = beta * kappa;
     }
     sch.bkv = lds_bk;

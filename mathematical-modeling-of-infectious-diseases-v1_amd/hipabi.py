@@ -85,7 +85,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_set_constraint_mode", "sepaihrd_set_arith", "sepaihrd_set_precision", "sepaihrd_set_integrator_form", "sepaihrd_eval_batch",
     "sepaihrd_eval_batch_device", "sepaihrd_eval_batch_begin", "sepaihrd_eval_batch_end", "sepaihrd_apply_constraints", "sepaihrd_get_kernel_info", "sepaihrd_get_kernel_info_for_batch", "sepaihrd_reserve",
     "sepaihrd_set_timing", "sepaihrd_get_timing", "sepaihrd_set_initial_state_mode",
-    "sepaihrd_ensemble_quantiles", "sepaihrd_mh_create", "sepaihrd_mh_destroy", "sepaihrd_mh_evaluate_current",
+    "sepaihrd_ensemble_quantiles", "sepaihrd_scenario_ensemble", "sepaihrd_mh_create", "sepaihrd_mh_destroy", "sepaihrd_mh_evaluate_current",
     "sepaihrd_mh_propose", "sepaihrd_mh_fetch", "sepaihrd_mh_stage_normals", "sepaihrd_mh_staging_buffer", "sepaihrd_mh_step", "sepaihrd_mh_read_best", "sepaihrd_mh_busy", "sepaihrd_mh_set_values", "sepaihrd_mh_test_buffer",
     "sepaihrd_mh_step_tested", "sepaihrd_mh_fetch_test", "sepaihrd_mh_commit", "sepaihrd_mh_adapt", "sepaihrd_mh_read_history",
     "sepaihrd_mh_read_covariance", "sepaihrd_mh_read_proposal", "sepaihrd_mh_history_length",
@@ -191,6 +191,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_mh_history_length.argtypes = [vp]
     lib.sepaihrd_set_initial_state_mode.argtypes = [vp, C.c_int]
     lib.sepaihrd_ensemble_quantiles.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_scenario_ensemble.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -359,6 +360,36 @@ class HipObjective:
             out["rt"] = rt
         if want_metrics:
             out["metrics"] = met
+        return out
+
+    def scenario_ensemble(self, theta, kappa_mult, probs, want_sero: bool = False, want_rt: bool = False) -> dict:
+        """NPI scenario analysis (sepaihrd_scenario_ensemble): every sample of theta under every row k of kappa_mult
+        ([K][n_kappa], applied to kappa after the constraints) in one launch.  ppc [K][6][n_probs][T_pos][n],
+        metrics [K][S][12 + 4 n], summary [K][12 + 4 n][2 + n_probs] (mean, std_dev, quantiles), diff [K][12 + 4 n][n_probs]
+        (quantiles of metric[k][s] - metric[0][s]), status [K][S], n_valid [K]; sero / rt [K][n_probs][T] on request."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        km = np.ascontiguousarray(np.atleast_2d(kappa_mult), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        S, K, npb, n = th.shape[0], km.shape[0], pr.size, self.pb.n
+        W = 12 + 4 * n
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        ppc = np.empty((K, 6, npb, Tp, n))
+        sero = np.empty((K, npb, self.pb.n_times)) if want_sero else None
+        rt = np.empty((K, npb, self.pb.n_times)) if want_rt else None
+        met = np.empty((K, S, W))
+        summ = np.empty((K, W, 2 + npb))
+        diff = np.empty((K, W, npb))
+        status = np.empty((K, S), dtype=np.int32)
+        nv = np.empty(K, dtype=np.int32)
+        self._check(self.lib.sepaihrd_scenario_ensemble(
+            self.ctx, th.ctypes.data, S, km.ctypes.data, K, km.shape[1], pr.ctypes.data, npb, ppc.ctypes.data,
+            sero.ctypes.data if want_sero else None, rt.ctypes.data if want_rt else None, met.ctypes.data,
+            summ.ctypes.data, diff.ctypes.data, status.ctypes.data, nv.ctypes.data), "scenario_ensemble")
+        out = {"ppc": ppc, "metrics": met, "summary": summ, "diff": diff, "status": status, "n_valid": nv}
+        if want_sero:
+            out["sero"] = sero
+        if want_rt:
+            out["rt"] = rt
         return out
 
     def reserve(self, max_B: int):

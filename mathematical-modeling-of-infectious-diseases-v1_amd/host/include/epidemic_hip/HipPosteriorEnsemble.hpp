@@ -36,12 +36,28 @@ struct PosteriorPredictiveData {
 
 using AggregatedStats = std::map<std::string, double>;  // "median", "q025", "q975", "q05", "q95" (+ "mean", "std_dev")
 
-// include/model/AnalysisTypes.hpp:14-39 (kappa_values omitted: they are the sample's own parameters)
+// include/model/AnalysisTypes.hpp:14-39
 struct EssentialMetrics {
     double R0 = 0.0, overall_IFR = 0.0, overall_attack_rate = 0.0, peak_hospital_occupancy = 0.0, peak_ICU_occupancy = 0.0,
            time_to_peak_hospital = 0.0, time_to_peak_ICU = 0.0, total_cumulative_deaths = 0.0;
     double max_Rt = 0.0, min_Rt = 1e6, final_Rt = 0.0, seroprevalence_at_target_day = 0.0;
     std::vector<double> age_specific_IFR, age_specific_IHR, age_specific_IICUR, age_specific_attack_rate;
+    // "kappa_<i+1>" -> kappa_values[i] of the run (MetricsCalculator.cpp:166-169); filled by the scenario analysis only
+    std::map<std::string, double> kappa_values;
+};
+
+// an NPI scenario: its name and one multiplier per kappa value, applied after the constraints
+using KappaScenario = std::pair<std::string, std::vector<double>>;
+
+// posterior-wide summaries of one scenario (sepaihrd_scenario_ensemble): per metric (names of aggregateMetrics) mean,
+// std_dev, median, q025, q975 over the scenario's valid samples, and median / q025 / q975 of the paired differences
+// metric(scenario) - metric(first scenario) over the samples valid in both
+struct ScenarioSummary {
+    std::string name;
+    std::vector<double> kappa_multipliers;
+    int n_valid = 0;
+    std::map<std::string, AggregatedStats> metrics;
+    std::map<std::string, AggregatedStats> difference_to_baseline;
 };
 
 class HipPosteriorEnsemble {
@@ -74,7 +90,30 @@ public:
                                                             int thinning);
     static std::map<std::string, AggregatedStats> aggregateMetrics(const std::vector<EssentialMetrics>& rows);
 
+    // NPI scenario analysis (PostCalibrationAnalyser::generateFullReport step 4, PostCalibrationAnalyser.cpp:94-141,378-401):
+    // one run of baseline_theta per scenario, all in one device launch; the scenario's kappa_values = the constrained
+    // baseline's x its multipliers, used by the integration only (the metrics read the unscaled kappa, :163-168).
+    // Rows in scenario order, each with the scenario's own kappa_values; an invalid run gives the default metrics.
+    std::vector<std::pair<std::string, EssentialMetrics>> performScenarioAnalysis(const Eigen::VectorXd& baseline_theta,
+                                                                                  const std::vector<KappaScenario>& scenarios);
+    // every sample burn_in, burn_in + thinning, ... under every scenario: per-scenario summaries and paired differences
+    std::vector<ScenarioSummary> analyseScenarios(const std::vector<Eigen::VectorXd>& param_samples, int burn_in, int thinning,
+                                                  const std::vector<KappaScenario>& scenarios);
+    // baseline, stricter_lockdown (kappa_values[idx] x 0.9), weaker_lockdown (x 1.1): idx = 1, or 0 when the piecewise
+    // strategy's baseline is calibratable (:111-130) -- never on this path, whose baseline kappa is fixed; only the
+    // baseline when there are not more than idx kappa values
+    static std::vector<KappaScenario> defaultLockdownScenarios(const HipSEPAIHRDParameterManager& pm);
+    // the scenario's kappa_values for theta: constrained, then scaled
+    std::vector<double> scenarioKappaValues(const Eigen::VectorXd& theta, const std::vector<double>& multipliers) const;
+
+    // AnalysisWriter::writeScenarioComparison (AnalysisWriter.cpp:439-477), stream defaults
+    static void writeScenarioComparison(const std::string& path, const std::vector<std::pair<std::string, EssentialMetrics>>& rows);
+    // ResultAggregator::performENECOVIDValidation (:485-518) over a metric summary + AnalysisWriter::writeEneCovidValidation
+    // (:479-510): target day 64, ENE-COVID 0.048 [0.043, 0.054], std::fixed with 5 digits
+    static void writeEneCovidValidation(const std::string& path, const std::map<std::string, AggregatedStats>& summary);
+
 private:
+    std::vector<double> scenarioTable(const std::vector<KappaScenario>& scenarios) const;
     void run(const std::vector<double>& thetas, int S, bool want_sero);
     HipSEPAIHRDParameterManager& pm_;
     const CalibrationData& data_;

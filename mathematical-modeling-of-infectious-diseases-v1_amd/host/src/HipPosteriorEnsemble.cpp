@@ -3,6 +3,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <fstream>
+#include <iomanip>
 #include <functional>
 #include <numeric>
 #include <random>
@@ -211,6 +213,170 @@ std::map<std::string, AggregatedStats> HipPosteriorEnsemble::aggregateMetrics(co
         result[col.first] = st;
     }
     return result;
+}
+
+namespace {
+EssentialMetrics metricsRow(const double* r, int n) {
+    EssentialMetrics m;
+    m.R0 = r[0]; m.overall_IFR = r[1]; m.overall_attack_rate = r[2]; m.peak_hospital_occupancy = r[3];
+    m.peak_ICU_occupancy = r[4]; m.time_to_peak_hospital = r[5]; m.time_to_peak_ICU = r[6];
+    m.total_cumulative_deaths = r[7]; m.max_Rt = r[8]; m.min_Rt = r[9]; m.final_Rt = r[10];
+    m.seroprevalence_at_target_day = r[11];
+    for (int a = 0; a < n; ++a) {
+        m.age_specific_IFR.push_back(r[12 + 4 * a + 0]);
+        m.age_specific_IHR.push_back(r[12 + 4 * a + 1]);
+        m.age_specific_IICUR.push_back(r[12 + 4 * a + 2]);
+        m.age_specific_attack_rate.push_back(r[12 + 4 * a + 3]);
+    }
+    return m;
+}
+// metric names in table column order (aggregateMetrics' names)
+std::vector<std::string> metricNames(int n) {
+    std::vector<std::string> names = {"R0", "overall_IFR", "overall_attack_rate", "peak_hospital", "peak_ICU", "time_to_peak_hospital",
+                                      "time_to_peak_ICU", "total_deaths", "max_Rt", "min_Rt", "final_Rt", "seroprevalence_day64"};
+    for (int a = 0; a < n; ++a)
+        for (const char* m : {"IFR", "IHR", "IICUR", "AttackRate"}) names.push_back(std::string(m) + "_age_" + std::to_string(a));
+    return names;
+}
+}  // namespace
+
+std::vector<KappaScenario> HipPosteriorEnsemble::defaultLockdownScenarios(const HipSEPAIHRDParameterManager& pm) {
+    const size_t nk = pm.modelParameters().kappa_values.size();
+    const size_t idx = 1;  // the device path's piecewise strategy always has a fixed baseline kappa
+    std::vector<KappaScenario> out = {{"baseline", std::vector<double>(nk, 1.0)}};
+    if (nk > idx) {
+        std::vector<double> stricter(nk, 1.0), weaker(nk, 1.0);
+        stricter[idx] = 0.9;
+        weaker[idx] = 1.1;
+        out.push_back({"stricter_lockdown", stricter});
+        out.push_back({"weaker_lockdown", weaker});
+    }
+    return out;
+}
+
+std::vector<double> HipPosteriorEnsemble::scenarioKappaValues(const Eigen::VectorXd& theta, const std::vector<double>& multipliers) const {
+    std::vector<double> kappa = pm_.modelParameters().kappa_values;
+    const Eigen::VectorXd c = pm_.applyConstraints(theta);
+    for (size_t p = 0; p < pm_.getParameterCount(); ++p)
+        if (pm_.fieldCodes()[p] == SEPAIHRD_F_KAPPA_VALUE)
+            kappa[static_cast<size_t>(pm_.fieldIndices()[p])] = c[static_cast<Eigen::Index>(p)];
+    for (size_t i = 0; i < kappa.size(); ++i) kappa[i] *= multipliers[i];  // SEPAIHRDParameters::kappa_values[idx] *= f
+    return kappa;
+}
+
+std::vector<double> HipPosteriorEnsemble::scenarioTable(const std::vector<KappaScenario>& scenarios) const {
+    const size_t nk = pm_.modelParameters().kappa_values.size();
+    std::vector<double> table;
+    for (const KappaScenario& sc : scenarios) {
+        if (sc.second.size() != nk) throw InvalidParameterException("HipPosteriorEnsemble", "scenario " + sc.first + ": one multiplier per kappa value");
+        table.insert(table.end(), sc.second.begin(), sc.second.end());
+    }
+    return table;
+}
+
+std::vector<std::pair<std::string, EssentialMetrics>> HipPosteriorEnsemble::performScenarioAnalysis(
+    const Eigen::VectorXd& baseline_theta, const std::vector<KappaScenario>& scenarios) {
+    std::vector<std::pair<std::string, EssentialMetrics>> out;
+    if (scenarios.empty()) return out;
+    const size_t P = pm_.getParameterCount();
+    if (static_cast<size_t>(baseline_theta.size()) != P) throw InvalidParameterException("HipPosteriorEnsemble", "baseline size mismatch");
+    sepaihrd_ctx* ctx = objective_->deviceContext();
+    objective_->syncDeviceConstraintMode();
+    const std::vector<double> table = scenarioTable(scenarios);
+    const int K = static_cast<int>(scenarios.size()), W = 12 + 4 * n_;
+    std::vector<double> theta(baseline_theta.data(), baseline_theta.data() + P), metrics(static_cast<size_t>(K) * W);
+    std::vector<int32_t> status(static_cast<size_t>(K));
+    const int rc = sepaihrd_scenario_ensemble(ctx, theta.data(), 1, table.data(), K, static_cast<int>(table.size() / K), kProbs, 5,
+                                              nullptr, nullptr, nullptr, metrics.data(), nullptr, nullptr, status.data(), nullptr);
+    if (rc != SEPAIHRD_OK)
+        throw ModelException("HipPosteriorEnsemble", std::string("sepaihrd_scenario_ensemble: ") + sepaihrd_last_error(ctx));
+    for (int k = 0; k < K; ++k) {
+        if (status[static_cast<size_t>(k)] != 0) {
+            // an invalid run: default metrics, zero per-age vectors and no kappa values (MetricsCalculator.cpp:23-26)
+            EssentialMetrics m;
+            m.age_specific_IFR.assign(static_cast<size_t>(n_), 0.0);
+            m.age_specific_IHR = m.age_specific_IICUR = m.age_specific_attack_rate = m.age_specific_IFR;
+            out.push_back({scenarios[static_cast<size_t>(k)].first, std::move(m)});
+            continue;
+        }
+        EssentialMetrics m = metricsRow(&metrics[static_cast<size_t>(k) * W], n_);
+        const std::vector<double> kappa = scenarioKappaValues(baseline_theta, scenarios[static_cast<size_t>(k)].second);
+        for (size_t i = 0; i < kappa.size(); ++i) m.kappa_values["kappa_" + std::to_string(i + 1)] = kappa[i];
+        out.push_back({scenarios[static_cast<size_t>(k)].first, std::move(m)});
+    }
+    return out;
+}
+
+std::vector<ScenarioSummary> HipPosteriorEnsemble::analyseScenarios(const std::vector<Eigen::VectorXd>& param_samples, int burn_in,
+                                                                    int thinning, const std::vector<KappaScenario>& scenarios) {
+    std::vector<ScenarioSummary> out;
+    if (scenarios.empty() || param_samples.empty() || burn_in >= static_cast<int>(param_samples.size()) || thinning <= 0) return out;
+    const size_t P = pm_.getParameterCount();
+    std::vector<double> thetas;
+    int S = 0;
+    for (size_t i = static_cast<size_t>(burn_in); i < param_samples.size(); i += static_cast<size_t>(thinning)) {
+        const Eigen::VectorXd& v = param_samples[i];
+        if (static_cast<size_t>(v.size()) != P) throw InvalidParameterException("HipPosteriorEnsemble", "sample size mismatch");
+        for (size_t k = 0; k < P; ++k) thetas.push_back(v[static_cast<Eigen::Index>(k)]);
+        ++S;
+    }
+    sepaihrd_ctx* ctx = objective_->deviceContext();
+    objective_->syncDeviceConstraintMode();
+    const std::vector<double> table = scenarioTable(scenarios);
+    const int K = static_cast<int>(scenarios.size()), W = 12 + 4 * n_;
+    // the summary rule of aggregateMetrics: mean, std_dev, median, q025, q975
+    const double probs[3] = {0.5, 0.025, 0.975};
+    std::vector<double> summary(static_cast<size_t>(K) * W * 5), diff(static_cast<size_t>(K) * W * 3);
+    std::vector<int32_t> nv(static_cast<size_t>(K));
+    const int rc = sepaihrd_scenario_ensemble(ctx, thetas.data(), S, table.data(), K, static_cast<int>(table.size() / K), probs, 3,
+                                              nullptr, nullptr, nullptr, nullptr, summary.data(), diff.data(), nullptr, nv.data());
+    if (rc != SEPAIHRD_OK)
+        throw ModelException("HipPosteriorEnsemble", std::string("sepaihrd_scenario_ensemble: ") + sepaihrd_last_error(ctx));
+    const std::vector<std::string> names = metricNames(n_);
+    for (int k = 0; k < K; ++k) {
+        ScenarioSummary sc;
+        sc.name = scenarios[static_cast<size_t>(k)].first;
+        sc.kappa_multipliers = scenarios[static_cast<size_t>(k)].second;
+        sc.n_valid = nv[static_cast<size_t>(k)];
+        for (int c = 0; c < W; ++c) {
+            const double* s = &summary[(static_cast<size_t>(k) * W + c) * 5];
+            const double* d = &diff[(static_cast<size_t>(k) * W + c) * 3];
+            sc.metrics[names[static_cast<size_t>(c)]] = {{"mean", s[0]}, {"std_dev", s[1]}, {"median", s[2]}, {"q025", s[3]}, {"q975", s[4]}};
+            sc.difference_to_baseline[names[static_cast<size_t>(c)]] = {{"median", d[0]}, {"q025", d[1]}, {"q975", d[2]}};
+        }
+        out.push_back(std::move(sc));
+    }
+    return out;
+}
+
+void HipPosteriorEnsemble::writeScenarioComparison(const std::string& path, const std::vector<std::pair<std::string, EssentialMetrics>>& rows) {
+    std::ofstream file(path);
+    if (!file.is_open()) throw ModelException("HipPosteriorEnsemble", "cannot open " + path);
+    file << "scenario,R0,overall_IFR,overall_attack_rate,peak_hospital,peak_ICU,"
+         << "time_to_peak_hospital,time_to_peak_ICU,total_deaths,seroprevalence_day64";
+    if (!rows.empty())
+        for (const auto& kv : rows[0].second.kappa_values) file << "," << kv.first;
+    file << "\n";
+    for (const auto& [name, m] : rows) {
+        file << name << "," << m.R0 << "," << m.overall_IFR << "," << m.overall_attack_rate << "," << m.peak_hospital_occupancy << ","
+             << m.peak_ICU_occupancy << "," << m.time_to_peak_hospital << "," << m.time_to_peak_ICU << ","
+             << m.total_cumulative_deaths << "," << m.seroprevalence_at_target_day;
+        for (const auto& kv : m.kappa_values) file << "," << kv.second;
+        file << "\n";
+    }
+}
+
+void HipPosteriorEnsemble::writeEneCovidValidation(const std::string& path, const std::map<std::string, AggregatedStats>& summary) {
+    std::ofstream file(path);
+    if (!file.is_open()) throw ModelException("HipPosteriorEnsemble", "cannot open " + path);
+    const double target_day = 64.0;
+    file << "source,median_seroprevalence,lower_95ci,upper_95ci,target_day\n";
+    file << std::fixed << std::setprecision(5);
+    const auto it = summary.find("seroprevalence_day64");
+    if (it != summary.end() && it->second.count("median"))
+        file << "Model," << it->second.at("median") << "," << it->second.at("q025") << "," << it->second.at("q975") << ","
+             << target_day << "\n";
+    file << "ENE_COVID," << 0.048 << "," << 0.043 << "," << 0.054 << "," << target_day << "\n";
 }
 
 }  // namespace epidemic

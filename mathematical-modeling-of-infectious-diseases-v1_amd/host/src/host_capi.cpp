@@ -204,6 +204,75 @@ int host_ensemble(void* hv, const sepaihrd_problem* pb, int device, const double
     }
 }
 
+// PostCalibrationAnalyser::generateFullReport step 4 as the reference runs it (PostCalibrationAnalyser.cpp:94-141,210-219): the
+// baseline is the LAST analysed sample (burn_in, burn_in + thinning, ...) after the constraints -- the parameters the batch loop
+// left in the model template -- and the default lockdown scenarios.  Writes scenario_comparison.csv to path (if not null);
+// metrics [n_rows][12 + 4 n] and kappa [n_rows][n_kappa] (nullable, capacity 3 rows) receive the rows.
+int host_scenario_comparison(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int burn_in,
+                             int thinning, const char* path, double* metrics, double* kappa, int32_t* n_rows) {
+    auto* h = static_cast<HostHandle*>(hv);
+    try {
+        *n_rows = 0;
+        if (n_samples <= 0 || burn_in >= n_samples || thinning <= 0) return 0;
+        const int n = pb->n_age;
+        const size_t P = h->pm->getParameterCount();
+        HipPosteriorEnsemble ens(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
+                                 strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
+        int last = burn_in;
+        while (last + thinning < n_samples) last += thinning;
+        const Eigen::VectorXd baseline = vec(samples + static_cast<size_t>(last) * P, static_cast<int>(P));
+        const auto rows = ens.performScenarioAnalysis(baseline, HipPosteriorEnsemble::defaultLockdownScenarios(*h->pm));
+        if (path) HipPosteriorEnsemble::writeScenarioComparison(path, rows);
+        const size_t W = static_cast<size_t>(12 + 4 * n), nk = h->pm->modelParameters().kappa_values.size();
+        for (size_t r = 0; r < rows.size(); ++r) {
+            const EssentialMetrics& m = rows[r].second;
+            if (metrics) {
+                double* o = metrics + r * W;
+                const double head[12] = {m.R0, m.overall_IFR, m.overall_attack_rate, m.peak_hospital_occupancy, m.peak_ICU_occupancy,
+                                         m.time_to_peak_hospital, m.time_to_peak_ICU, m.total_cumulative_deaths, m.max_Rt, m.min_Rt,
+                                         m.final_Rt, m.seroprevalence_at_target_day};
+                for (int c = 0; c < 12; ++c) o[c] = head[c];
+                for (int a = 0; a < n; ++a) {
+                    o[12 + 4 * a + 0] = m.age_specific_IFR[static_cast<size_t>(a)];
+                    o[12 + 4 * a + 1] = m.age_specific_IHR[static_cast<size_t>(a)];
+                    o[12 + 4 * a + 2] = m.age_specific_IICUR[static_cast<size_t>(a)];
+                    o[12 + 4 * a + 3] = m.age_specific_attack_rate[static_cast<size_t>(a)];
+                }
+            }
+            if (kappa)
+                for (size_t i = 0; i < nk; ++i) {
+                    const auto it = m.kappa_values.find("kappa_" + std::to_string(i + 1));
+                    kappa[r * nk + i] = it == m.kappa_values.end() ? std::numeric_limits<double>::quiet_NaN() : it->second;
+                }
+        }
+        *n_rows = static_cast<int32_t>(rows.size());
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// seroprevalence/ene_covid_validation.csv from the metric summary of samples burn_in, burn_in + thinning, ...
+// (PostCalibrationAnalyser.cpp:288-299)
+int host_ene_covid_validation(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int burn_in,
+                              int thinning, const char* path) {
+    auto* h = static_cast<HostHandle*>(hv);
+    try {
+        const int n = pb->n_age;
+        const size_t P = h->pm->getParameterCount();
+        HipPosteriorEnsemble ens(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
+                                 strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
+        std::vector<Eigen::VectorXd> ps;
+        for (int s = 0; s < n_samples; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+        HipPosteriorEnsemble::writeEneCovidValidation(path, HipPosteriorEnsemble::aggregateMetrics(ens.calculateEssentialMetrics(ps, burn_in, thinning)));
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
 // returns 0 ok, 1 = exception thrown by calculate() (message in host_last_error)
 int host_objective_calculate(void* hv, const double* theta, double* value) {
     auto* h = static_cast<HostHandle*>(hv);

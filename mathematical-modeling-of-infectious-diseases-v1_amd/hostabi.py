@@ -56,6 +56,10 @@ def load_library() -> C.CDLL:
     lib.host_pso_run.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.host_ensemble.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32,
                                   vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.host_scenario_comparison.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                             C.c_char_p, vp, vp, vp]
+    lib.host_ene_covid_validation.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_char_p]
     _lib = lib
     return lib
 
@@ -224,6 +228,31 @@ class HostObjective:
         if rc != 0:
             raise RuntimeError("host_ensemble: " + self.lib.host_last_error().decode())
         return {"ppc": ppc, "selected": sel[:nsel.value].copy(), "samples_used": used.value, "sero": sero, "rt": rt}
+
+    def scenario_comparison(self, samples, burn_in: int = 0, thinning: int = 1, path: str | None = None, device: int = -1) -> dict:
+        """The reference's scenario step (PostCalibrationAnalyser.cpp:94-141): the default lockdown scenarios of the last
+        analysed sample, through HipPosteriorEnsemble::performScenarioAnalysis; writes scenario_comparison.csv to path.
+        names [rows], metrics [rows][12 + 4 n], kappa [rows][n_kappa] (the scenario's own kappa_values)."""
+        ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        met = np.empty((3, 12 + 4 * self.pb.n))
+        kap = np.empty((3, len(self.pb.kappa_values)))
+        rows = C.c_int32(0)
+        rc = self.lib.host_scenario_comparison(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning,
+                                               path.encode() if path else None, met.ctypes.data, kap.ctypes.data, C.byref(rows))
+        if rc != 0:
+            raise RuntimeError("host_scenario_comparison: " + self.lib.host_last_error().decode())
+        names = ["baseline", "stricter_lockdown", "weaker_lockdown"][:rows.value]
+        return {"names": names, "metrics": met[:rows.value].copy(), "kappa": kap[:rows.value].copy()}
+
+    def ene_covid_validation(self, samples, path: str, burn_in: int = 0, thinning: int = 1, device: int = -1) -> None:
+        """seroprevalence/ene_covid_validation.csv from the metric summary of the samples (PostCalibrationAnalyser.cpp:288-299)."""
+        ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        if self.lib.host_ene_covid_validation(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning, path.encode()):
+            raise RuntimeError("host_ene_covid_validation: " + self.lib.host_last_error().decode())
 
     def calculate(self, theta) -> float:
         th = np.ascontiguousarray(theta, dtype=np.float64)

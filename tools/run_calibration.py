@@ -48,6 +48,10 @@ def main():
     ap.add_argument("--thinning", type=int, default=10)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--arith", choices=["fma", "strict"], default="fma")
+    ap.add_argument("--scenarios", action="store_true",
+                    help="also the NPI scenario analysis (scenarios/scenario_comparison.csv, the reference's three rows from the "
+                         "last analysed sample; scenarios/scenario_posterior.json, every pooled sample under every scenario) "
+                         "and seroprevalence/ene_covid_validation.csv")
     args = ap.parse_args()
 
     mm = mmid_amd_loader.load()
@@ -90,11 +94,36 @@ def main():
     pos = times[times >= 0]
     # the reference's post-calibration output tree (file names, headers and number formats of AnalysisWriter.cpp; what
     # scripts/model/PostCalibrationAnalysis.py loads): posterior_predictive/, parameter_posteriors/, rt_trajectories/,
-    # seroprevalence/, mcmc_batches/, mcmc_aggregated/
+    # seroprevalence/, mcmc_batches/, mcmc_aggregated/ (and with --scenarios: scenarios/, seroprevalence/ene_covid_validation.csv)
     observed = {"daily_hospitalizations": pb.obs_H, "daily_icu_admissions": pb.obs_ICU, "daily_deaths": pb.obs_D,
                 "cumulative_hospitalizations": np.cumsum(pb.obs_H, axis=0), "cumulative_icu_admissions": np.cumsum(pb.obs_ICU, axis=0),
                 "cumulative_deaths": np.cumsum(pb.obs_D, axis=0)}
-    mm.config_io.write_post_calibration_tree(args.out, times, ens, pooled, list(pb.param_names), pb.n, observed=observed)
+    scenario_rows = None
+    if args.scenarios:
+        # the reference's baseline: the last analysed sample after the constraints (PostCalibrationAnalyser.cpp:100-109,
+        # 210-219), one run per scenario
+        scen = mm.config_io.default_lockdown_scenarios(len(pb.kappa_values))
+        table = np.array([m for _, m in scen])
+        last = pooled[-1:]
+        three = hip.scenario_ensemble(last, table, PROBS)
+        c = hip.apply_constraints(last, 1)[0]
+        scenario_rows = mm.config_io.scenario_comparison_rows(
+            [name for name, _ in scen], three["metrics"][:, 0], three["status"][:, 0],
+            [mm.config_io.scenario_kappa_values(pb, c, m) for _, m in scen], pb.n)
+        # the posterior-wide form: every pooled sample under every scenario, paired differences against the baseline
+        wide = hip.scenario_ensemble(pooled, table, PROBS)
+        cols = mm.config_io.essential_metric_columns(pb.n)
+        post = {name: {"n_valid": int(wide["n_valid"][k]),
+                       "metrics": {col: dict(zip(["mean", "std_dev"] + [f"q{p}" for p in PROBS], map(float, wide["summary"][k, j])))
+                                   for j, col in enumerate(cols)},
+                       "difference_to_baseline": {col: dict(zip([f"q{p}" for p in PROBS], map(float, wide["diff"][k, j])))
+                                                  for j, col in enumerate(cols)}}
+                for k, (name, _) in enumerate(scen)}
+        os.makedirs(os.path.join(args.out, "scenarios"), exist_ok=True)
+        with open(os.path.join(args.out, "scenarios", "scenario_posterior.json"), "w") as fh:
+            json.dump(post, fh, indent=1)
+    mm.config_io.write_post_calibration_tree(args.out, times, ens, pooled, list(pb.param_names), pb.n, observed=observed,
+                                             scenarios=scenario_rows, ene_covid=args.scenarios)
     assert len(pos) == ens["ppc"].shape[2]
 
     evals = args.chains * args.mcmc_iterations
