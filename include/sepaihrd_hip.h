@@ -490,6 +490,31 @@ int sepaihrd_mh_busy(sepaihrd_mh *mh);
 int sepaihrd_mh_read_proposal(sepaihrd_mh *mh, double *prop);
 int sepaihrd_mh_history_length(const sepaihrd_mh *mh);
 
+/* ---- Convergence diagnostics of C chains x N draws ----
+ *
+ * The reference runs one chain and reports none.  Here, per column (a parameter, or the chains' log-likelihood values):
+ * the rank-normalised split R-hat and the bulk / tail effective sample sizes of Vehtari, Gelman, Simpson, Carpenter,
+ * Buerkner (2021), as the R package `posterior` (1.x) computes them: each chain split into its first and last floor(N/2)
+ * draws (odd N: the middle draw dropped), ranks over all split draws with ties averaged, z = Phi^-1((r - 3/8) / (S + 1/4)),
+ * folded draws |x - median|, Geyer's initial positive and monotone sequences over direct-sum autocovariances.  A row is
+ *   mean, sd (over all C N draws, n - 1), mcse_mean = sd / sqrt(ess_mean), ess_mean (raw split draws), ess_bulk (their z),
+ *   ess_tail = min(ESS of I[x <= q05], ESS of I[x <= q95]) (type-7 quantiles of all C N draws), r_hat = max(R(z), R(z folded))
+ * and is all NaN when a draw is non-finite or max - min < DBL_EPSILON (posterior's should_return_NA; the same rule makes
+ * one series NaN, e.g. a tail indicator that is constant).  ESS is NaN for floor(N/2) < 3.  Every sum runs in a fixed order:
+ * the table has the same bits from call to call and through both entry points.  Ranks come from rocPRIM's segmented radix
+ * sort on the device, autocovariances in blocks of 64 lags up to Geyer's truncation (one 4-byte read-back per block).
+ *   chain_diagnostics   samples [C][N][P] host, values [C][N] host or NULL -> out [P + (values != NULL)][7] host, the values
+ *                       row last; max_lag [P + 1][4] or NULL: Geyer's max_t of the raw, z, I05 and I95 series (-1: NaN ESS)
+ *   mh_diagnostics      the same over the sampler's RESIDENT thinned samples first_sample .. first_sample + count - 1
+ *                       (count <= 0: to the last stored) and, with with_values, the chains' values at them (stored with
+ *                       sepaihrd_mh_keep_scale_on_device); nothing is read back but the table
+ * SEPAIHRD_E_INVALID_ARG (sepaihrd_last_error says which) for C < 1, P < 1 or N < 4, C N >= 2^31, a range beyond the stored
+ * samples, a sampler that stores no samples, with_values without stored values, or a pending sepaihrd_eval_batch_begin. */
+#define SEPAIHRD_DIAG_COLUMNS 7 /* mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail, r_hat */
+int sepaihrd_chain_diagnostics(sepaihrd_ctx *ctx, const double *samples, const double *values, int C, int N, int P,
+                               double *out, int32_t *max_lag);
+int sepaihrd_mh_diagnostics(sepaihrd_mh *mh, int first_sample, int count, int with_values, double *out, int32_t *max_lag);
+
 /* ---- per-chain summary records across devices (the one exchange of the path) ----
  *
  * After sampling, the post-calibration summary needs the records of ALL chains -- [P posterior means | P variances |

@@ -695,12 +695,32 @@ def sero64_summary(metrics: np.ndarray) -> Dict[str, float] | None:
     return {"median": _quantile_sorted(v, 0.5), "q025": _quantile_sorted(v, 0.025), "q975": _quantile_sorted(v, 0.975)}
 
 
+DIAGNOSTIC_COLUMNS = ["mean", "sd", "mcse_mean", "ess_mean", "ess_bulk", "ess_tail", "r_hat"]
+
+
+def write_posterior_diagnostics(path: str, names: List[str], table) -> None:
+    """parameter_posteriors/posterior_diagnostics.csv: one row per parameter name and, when the table has one row more,
+    a final log_likelihood row; numbers as %.8e (HipChainDiagnostics::writeCsv writes the same file)."""
+    t = np.asarray(table, dtype=np.float64)
+    if t.ndim != 2 or t.shape[1] != len(DIAGNOSTIC_COLUMNS) or t.shape[0] not in (len(names), len(names) + 1):
+        raise ValueError("the table needs one row per name (+ the values row) and 7 columns")
+    rows = list(names) + (["log_likelihood"] if t.shape[0] == len(names) + 1 else [])
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write("parameter," + ",".join(DIAGNOSTIC_COLUMNS) + "\n")
+        for name, row in zip(rows, t):
+            fh.write(name + "," + ",".join("%.8e" % v for v in row) + "\n")
+
+
 def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: np.ndarray, names: List[str], n_age: int,
                                 observed: Dict[str, np.ndarray] | None = None, burn_in: int = 0, thinning: int = 1,
-                                scenarios=None, ene_covid: bool = False) -> None:
+                                scenarios=None, ene_covid: bool = False, diagnostics=None) -> None:
     """Everything PostCalibrationAnalysis.py loads under out_base, from one sepaihrd_ensemble_quantiles result (keys
     ppc, sero, rt, metrics; quantiles at PPC_PROBS).  scenarios (rows as write_scenario_comparison takes them):
-    scenarios/scenario_comparison.csv; ene_covid: seroprevalence/ene_covid_validation.csv from the metric table."""
+    scenarios/scenario_comparison.csv; ene_covid: seroprevalence/ene_covid_validation.csv from the metric table;
+    diagnostics (a table as write_posterior_diagnostics takes it): parameter_posteriors/posterior_diagnostics.csv."""
     times = np.asarray(times, dtype=np.float64)
     write_posterior_predictive(os.path.join(out_base, "posterior_predictive"), times[times >= 0], ensemble["ppc"], observed or {})
     write_parameter_posteriors(os.path.join(out_base, "parameter_posteriors"), samples, names, burn_in, thinning)
@@ -716,3 +736,5 @@ def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: n
     if ene_covid:
         sero64 = sero64_summary(ensemble["metrics"]) if ensemble.get("metrics") is not None else None
         write_ene_covid_validation(os.path.join(out_base, "seroprevalence", "ene_covid_validation.csv"), sero64)
+    if diagnostics is not None:
+        write_posterior_diagnostics(os.path.join(out_base, "parameter_posteriors", "posterior_diagnostics.csv"), names, diagnostics)

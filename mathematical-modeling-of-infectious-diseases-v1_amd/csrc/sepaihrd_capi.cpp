@@ -2056,6 +2056,102 @@ int sepaihrd_mh_summary_records(sepaihrd_mh* mh, int first_sample, double* out, 
     return SEPAIHRD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+int diag_check_shape(sepaihrd_ctx* ctx, const char* who, int C, int N, int P) {
+    if (C < 1 || P < 1 || N < 4) {
+        ctx->last_error = std::string(who) + ": need C >= 1 chains, P >= 1 columns and N >= 4 draws per chain";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if ((int64_t)C * N >= ((int64_t)1 << 31)) {
+        ctx->last_error = std::string(who) + ": C N must stay below 2^31 draws per column";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (ctx->pending_B > 0) {
+        ctx->last_error = std::string(who) + ": a sepaihrd_eval_batch_begin is pending on this context";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    return SEPAIHRD_OK;
+}
+
+int diag_run(sepaihrd_ctx* ctx, const char* who, const DiagInput& in, double* out, int32_t* max_lag, hipStream_t st) {
+    const int rc = chain_diagnostics(in, out, max_lag, st);
+    if (rc == -4) { ctx->last_error = std::string(who) + ": invalid shape"; return SEPAIHRD_E_INVALID_ARG; }
+    if (rc != 0) {
+        const hipError_t e = hipGetLastError();
+        ctx->last_error = std::string(who) + ": device failure (" + hipGetErrorString(e) + ")";
+        return SEPAIHRD_E_HIP;
+    }
+    return SEPAIHRD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sepaihrd_chain_diagnostics(sepaihrd_ctx* ctx, const double* samples, const double* values, int C, int N, int P, double* out,
+                               int32_t* max_lag) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (!samples || !out) { ctx->last_error = "chain_diagnostics: samples and out are required"; return SEPAIHRD_E_INVALID_ARG; }
+    int rc = diag_check_shape(ctx, "chain_diagnostics", C, N, P);
+    if (rc != SEPAIHRD_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    if (!ctx->own_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking), ctx, return SEPAIHRD_E_HIP);
+    const size_t CN = (size_t)C * N;
+    double* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, CN * ((size_t)P + (values ? 1 : 0)) * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
+    struct Free { double* p; ~Free() { (void)hipFree(p); } } guard{d};
+    HIP_TRY(hipMemcpyAsync(d, samples, CN * P * sizeof(double), hipMemcpyHostToDevice, ctx->own_stream), ctx, return SEPAIHRD_E_HIP);
+    if (values)
+        HIP_TRY(hipMemcpyAsync(d + CN * P, values, CN * sizeof(double), hipMemcpyHostToDevice, ctx->own_stream), ctx, return SEPAIHRD_E_HIP);
+    DiagInput in{};
+    in.samples = d;
+    in.chain_stride = (size_t)N * P;
+    in.sample_stride = (size_t)P;
+    in.P = P;
+    in.values = values ? d + CN * P : nullptr;
+    in.value_chain_stride = (size_t)N;
+    in.C = C;
+    in.N = N;
+    return diag_run(ctx, "chain_diagnostics", in, out, max_lag, ctx->own_stream);
+}
+
+int sepaihrd_mh_diagnostics(sepaihrd_mh* mh, int first_sample, int count, int with_values, double* out, int32_t* max_lag) {
+    if (!mh) return SEPAIHRD_E_INVALID_ARG;
+    sepaihrd_ctx* ctx = mh->ctx;
+    if (!out) { ctx->last_error = "mh_diagnostics: out is required"; return SEPAIHRD_E_INVALID_ARG; }
+    if (ctx->pending_B > 0) {
+        ctx->last_error = "mh_diagnostics: a sepaihrd_eval_batch_begin is pending on this context";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    const int ns = sepaihrd_mh_sample_count(mh);
+    if (mh->st.n_store <= 0 || !mh->st.store) { ctx->last_error = "mh_diagnostics: the sampler stores no samples"; return SEPAIHRD_E_INVALID_ARG; }
+    if (with_values && !mh->st.lp_store) {
+        ctx->last_error = "mh_diagnostics: no values stored (sepaihrd_mh_keep_scale_on_device)";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (first_sample < 0 || first_sample >= ns || (count > 0 && first_sample + count > ns)) {
+        ctx->last_error = "mh_diagnostics: range beyond the samples stored so far";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    const int N = count > 0 ? count : ns - first_sample;
+    int rc = diag_check_shape(ctx, "mh_diagnostics", mh->st.C, N, mh->st.P);
+    if (rc != SEPAIHRD_OK) return rc;
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);
+    const size_t P = (size_t)mh->st.P, n_store = (size_t)mh->st.n_store;
+    DiagInput in{};
+    in.samples = mh->st.store + (size_t)first_sample * P;
+    in.chain_stride = n_store * P;
+    in.sample_stride = P;
+    in.P = mh->st.P;
+    in.values = with_values ? mh->st.lp_store + first_sample : nullptr;
+    in.value_chain_stride = n_store;
+    in.C = mh->st.C;
+    in.N = N;
+    return diag_run(ctx, "mh_diagnostics", in, out, max_lag, mh->stream);
+}
+
 int sepaihrd_mh_read_moments(sepaihrd_mh* mh, double* mean, double* m2) {
     if (!mh || (!mean && !m2)) return SEPAIHRD_E_INVALID_ARG;
     sepaihrd_ctx* ctx = mh->ctx;

@@ -170,6 +170,20 @@ struct ScenarioArgs {
     size_t sort_scratch_doubles;
 };
 int launch_scenario_summaries(const ScenarioArgs& a, void* stream);
+// convergence diagnostics of C chains x N draws (csrc/sepaihrd_diagnostics.hip): draw (c, n) of parameter p at
+// samples[c chain_stride + n sample_stride + p], of the values column at values[c value_chain_stride + n] (values may be null).
+// out [P + (values != null)][7]: mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail, r_hat; max_lag (nullable) [..][4]: Geyer's
+// max_t of the raw, z, I[x <= q05] and I[x <= q95] series (-1 where that ESS is NaN).  Synchronises the stream.
+// 0, -3 (HIP failure), -4 (C < 1, P < 1, N < 4 or C N >= 2^31)
+struct DiagInput {
+    const double* samples;
+    size_t chain_stride, sample_stride;
+    int P;
+    const double* values;
+    size_t value_chain_stride;
+    int C, N;
+};
+int chain_diagnostics(const DiagInput& in, double* out, int32_t* max_lag, void* stream);
 
 inline int lanes_per_chain(int n) {
     int l = 1;

@@ -80,6 +80,25 @@ def mh_create(lib, ctx, chains: int, iterations: int, x0: np.ndarray, cov0: np.n
     return lib.sepaihrd_mh_create(ctx, C.byref(cfg), x0.ctypes.data, cov0.ctypes.data)
 
 
+DIAG_COLUMNS = ("mean", "sd", "mcse_mean", "ess_mean", "ess_bulk", "ess_tail", "r_hat")  # SEPAIHRD_DIAG_COLUMNS, in order
+
+
+def _diag_result(out: np.ndarray, lag: np.ndarray) -> dict:
+    return {"table": out, "columns": list(DIAG_COLUMNS), "max_lag": lag}
+
+
+def mh_diagnostics(lib, mh, P: int, chains: int, first_sample: int = 0, count: int = 0, with_values: bool = False) -> dict:
+    """sepaihrd_mh_diagnostics over a sampler's resident samples first_sample .. (count <= 0: to the last stored):
+    table [P + with_values][7], max_lag [..][4].  Raises RuntimeError (with the code) when the call is refused."""
+    rows = P + (1 if with_values else 0)
+    out = np.empty((rows, len(DIAG_COLUMNS)))
+    lag = np.empty((rows, 4), dtype=np.int32)
+    rc = lib.sepaihrd_mh_diagnostics(mh, int(first_sample), int(count), int(bool(with_values)), out.ctypes.data, lag.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"sepaihrd_mh_diagnostics failed ({rc})")
+    return _diag_result(out, lag)
+
+
 EXPORTED_SYMBOLS = (
     "sepaihrd_create", "sepaihrd_destroy", "sepaihrd_last_error", "sepaihrd_abi_version",
     "sepaihrd_set_constraint_mode", "sepaihrd_set_arith", "sepaihrd_set_precision", "sepaihrd_set_integrator_form", "sepaihrd_eval_batch",
@@ -94,7 +113,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_mh_seed_streams", "sepaihrd_mh_draw_first", "sepaihrd_mh_keep_scale_on_device", "sepaihrd_mh_read_run_state",
     "sepaihrd_mh_read_sample_values", "sepaihrd_mh_read_accept_trace",
     "sepaihrd_device_libm_check", "sepaihrd_mh_read_failure_counts", "sepaihrd_mh_snapshot_begin", "sepaihrd_mh_snapshot_end",
-    "sepaihrd_device_log_values",
+    "sepaihrd_device_log_values", "sepaihrd_chain_diagnostics", "sepaihrd_mh_diagnostics",
 )
 
 _lib = None
@@ -192,6 +211,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_set_initial_state_mode.argtypes = [vp, C.c_int]
     lib.sepaihrd_ensemble_quantiles.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.sepaihrd_scenario_ensemble.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_chain_diagnostics.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.sepaihrd_mh_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -391,6 +412,22 @@ class HipObjective:
         if want_rt:
             out["rt"] = rt
         return out
+
+    def chain_diagnostics(self, samples, values=None) -> dict:
+        """Convergence diagnostics on the device (sepaihrd_chain_diagnostics): samples [C][N][P], values [C][N] or None ->
+        table [P + (values given)][7] (columns DIAG_COLUMNS; the values row last), max_lag [..][4] (Geyer's max_t of the raw,
+        z, I[x <= q05] and I[x <= q95] series, -1 where that ESS is NaN)."""
+        s = np.ascontiguousarray(samples, dtype=np.float64)
+        if s.ndim != 3:
+            raise ValueError("samples must be [C][N][P]")
+        Cn, N, P = s.shape
+        v = None if values is None else np.ascontiguousarray(np.reshape(values, (Cn, N)), dtype=np.float64)
+        rows = P + (0 if v is None else 1)
+        out = np.empty((rows, len(DIAG_COLUMNS)))
+        lag = np.empty((rows, 4), dtype=np.int32)
+        self._check(self.lib.sepaihrd_chain_diagnostics(self.ctx, s.ctypes.data, None if v is None else v.ctypes.data, Cn, N, P,
+                                                        out.ctypes.data, lag.ctypes.data), "chain_diagnostics")
+        return _diag_result(out, lag)
 
     def reserve(self, max_B: int):
         self._check(self.lib.sepaihrd_reserve(self.ctx, int(max_B)), "sepaihrd_reserve")

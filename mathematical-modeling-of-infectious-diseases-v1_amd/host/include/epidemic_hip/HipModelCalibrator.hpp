@@ -45,6 +45,8 @@ public:
     // objective value of every stored sample of every chain, chain-major (:141-144)
     const std::vector<double>& getMCMCObjectiveValues() const { return mcmc_values_; }
     const std::vector<std::vector<unsigned char>>& acceptTraces() const { return traces_; }
+    // phase 2's convergence diagnostics (MultiChainMetropolisHastings::diagnostics; settings key compute_diagnostics)
+    const ChainDiagnosticsTable& diagnostics() const { return diagnostics_; }
 private:
     HipSEPAIHRDParameterManager& pm_;
     HipSEPAIHRDObjectiveFunction& obj_;
@@ -56,6 +58,7 @@ private:
     Eigen::MatrixXd phase2_cov_;
     std::vector<double> mcmc_values_;
     std::vector<std::vector<unsigned char>> traces_;
+    ChainDiagnosticsTable diagnostics_;
     std::vector<Eigen::VectorXd> empty_;
 };
 

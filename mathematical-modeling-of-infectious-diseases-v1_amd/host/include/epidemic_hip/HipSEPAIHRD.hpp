@@ -224,6 +224,15 @@ private:
     std::vector<int> mult_index_;  // parameter index of E0..D0 multiplier, -1 = not calibrated
 };
 
+// Convergence diagnostics of a set of chains (HipChainDiagnostics, sepaihrd_chain_diagnostics / sepaihrd_mh_diagnostics)
+struct ChainDiagnosticsTable {
+    int rows = 0;                 // parameters, + 1 for the values row (last) when values were given
+    std::vector<double> values;   // [rows][7]: mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail, r_hat
+    std::vector<int32_t> max_lag; // [rows][4]: Geyer's max_t of the raw, z, I[x <= q05], I[x <= q95] series (-1: NaN ESS)
+    bool empty() const { return rows == 0; }
+    double at(int row, int col) const { return values[static_cast<size_t>(row) * 7 + static_cast<size_t>(col)]; }
+};
+
 // MetropolisHastingsSampler for many independent chains.  configure() takes the reference's
 // settings keys (mcmc_iterations, burn_in, adaptation_period, thinning, regularization_epsilon,
 // target_acceptance_rate, adapt_scale, store_samples).  A seed replaces the reference's
@@ -311,6 +320,13 @@ public:
     // wall time of the iteration loop of the last device-resident run (proposal 1 staged .. last accept test), without
     // the set-up before it (history allocation, initial values) and the read-back after it; groups: the slowest group
     double lastLoopSeconds() const { return last_loop_seconds_; }
+    // Convergence diagnostics of the run (settings key compute_diagnostics, default 0): per parameter, then for the chains'
+    // values, the split R-hat and bulk / tail ESS over the stored samples after burn-in -- the samples the summary records
+    // cover.  A device-resident run forms them from the resident samples (sepaihrd_mh_diagnostics) before the sampler goes;
+    // a grouped run from the samples it reads back, on group 0's context.  Empty when off, or with fewer than 4 such samples.
+    void setComputeDiagnostics(bool on) { compute_diagnostics_ = on; }
+    const ChainDiagnosticsTable& diagnostics() const { return diagnostics_; }
+    double lastDiagnosticsSeconds() const { return diagnostics_seconds_; }  // wall time of forming that table
 private:
     struct Chain;
     using BatchEval = std::function<void(const double*, int, double*)>;
@@ -337,6 +353,9 @@ private:
     std::function<void(const std::string&, const std::string&)> progress_sink_;
     bool device_streams_fell_back_ = false;
     std::vector<long> failure_counts_;
+    bool compute_diagnostics_ = false;
+    ChainDiagnosticsTable diagnostics_;
+    double diagnostics_seconds_ = 0.0;
     struct Reporter;
     friend struct Reporter;
 };

@@ -124,6 +124,7 @@ void HipModelCalibrator::calibrate(const std::map<std::string, double>& phase1_s
         for (int i = 0; i < P; ++i) init[static_cast<size_t>(c) * P + i] = best_[i];
     phase2_ = mh.optimizeChainsOnDevice(init, C, obj_, pm_);  // sampler state resident in HBM, same numbers
     traces_ = mh.acceptTraces();
+    diagnostics_ = mh.diagnostics();  // empty unless phase2_settings has compute_diagnostics != 0
     for (const OptimizationResult& r : phase2_)
         if (r.bestObjectiveValue > best_value_) {
             best_value_ = r.bestObjectiveValue;

@@ -7,6 +7,7 @@
 // proposal_cholesky_, running_mean_, log_scale_/global_scale_, recent_accepts_, chain_history_
 // and its own std::mt19937.  Host work per iteration is O(C P^2) and runs under OpenMP.
 #include "epidemic_hip/HipSEPAIHRD.hpp"
+#include "epidemic_hip/HipChainDiagnostics.hpp"
 #include "sepaihrd_hip.h"
 
 #include <sched.h>
@@ -330,6 +331,7 @@ void MultiChainMetropolisHastings::configure(const std::map<std::string, double>
     write_checkpoints_ = get("write_checkpoints", 1.0) != 0.0;
     write_trace_ = get("write_trace", 1.0) != 0.0;
     checkpoint_chains_ = static_cast<int>(get("checkpoint_chains", static_cast<double>(checkpoint_chains_)));
+    compute_diagnostics_ = get("compute_diagnostics", compute_diagnostics_ ? 1.0 : 0.0) != 0.0;
 }
 
 OptimizationResult MultiChainMetropolisHastings::optimize(const Eigen::VectorXd& x0, IObjectiveFunction& objective,
@@ -927,6 +929,7 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
     summary_records_.clear();
     summary_width_ = 2 * P + 2;
     group_rows_.assign(1, C);
+    diagnostics_ = ChainDiagnosticsTable{};
     if (ns > 0 && iterations_ > 1) {
         // per-chain summary over the samples after burn-in (all of them when none is): formed on the device, left in the
         // context's records buffer for a later all-gather, copied here
@@ -936,6 +939,21 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
         if (!d_rec) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_records_buffer: ") + sepaihrd_last_error(ctx));
         summary_records_.resize(static_cast<size_t>(C) * summary_width_);
         check(sepaihrd_mh_summary_records(mh, first, summary_records_.data(), d_rec), "mh_summary_records");
+        if (compute_diagnostics_) {
+            // convergence diagnostics over the same samples, from the resident store (and the values the device kept)
+            if (ns - first >= 4) {
+                ChainDiagnosticsTable t;
+                t.rows = P + (device_streams ? 1 : 0);
+                t.values.resize(static_cast<size_t>(t.rows) * SEPAIHRD_DIAG_COLUMNS);
+                t.max_lag.resize(static_cast<size_t>(t.rows) * 4);
+                const auto d0 = now();
+                check(sepaihrd_mh_diagnostics(mh, first, 0, device_streams ? 1 : 0, t.values.data(), t.max_lag.data()), "mh_diagnostics");
+                diagnostics_seconds_ = secs(d0, now());
+                diagnostics_ = std::move(t);
+            } else {
+                reporter.say("WARNING", "fewer than 4 stored samples after burn-in: no convergence diagnostics");
+            }
+        }
     }
     if (ns > 0) {
         rows.resize(static_cast<size_t>(C) * ns * P);
@@ -1031,6 +1049,7 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainGroup
                 local.seed_ = seed_ + static_cast<uint32_t>(first[static_cast<size_t>(g)]);
                 local.host_threads_ = std::max(1, share / G);
                 if (g > 0) local.checkpoint_chains_ = 0;  // the reports and trace files cover the run's first chains: group 0's
+                local.compute_diagnostics_ = false;  // formed once below, over every group's chains
                 const int c0 = first[static_cast<size_t>(g)], c1 = first[static_cast<size_t>(g) + 1];
                 const std::vector<double> init(initial.begin() + static_cast<size_t>(c0) * P, initial.begin() + static_cast<size_t>(c1) * P);
                 parts[static_cast<size_t>(g)] = local.optimizeChainsOnDevice(init, c1 - c0, *objectives[static_cast<size_t>(g)], pm);
@@ -1060,6 +1079,24 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainGroup
         for (auto& t : part_traces[static_cast<size_t>(g)]) traces_.push_back(std::move(t));
         summary_records_.insert(summary_records_.end(), part_records[static_cast<size_t>(g)].begin(), part_records[static_cast<size_t>(g)].end());
         group_rows_.push_back(first[static_cast<size_t>(g) + 1] - first[static_cast<size_t>(g)]);
+    }
+    diagnostics_ = ChainDiagnosticsTable{};
+    const int ns = results.empty() ? 0 : static_cast<int>(results[0].samples.size());
+    if (compute_diagnostics_ && ns > 0 && iterations_ > 1) {
+        // from the samples read back anyway, after burn-in as the summary records, on group 0's context
+        int s0 = burn_in_ / thinning_ + 1;
+        if (s0 >= ns) s0 = 0;
+        if (ns - s0 >= 4) {
+            std::vector<std::vector<Eigen::VectorXd>> chains;
+            std::vector<std::vector<double>> values;
+            bool have_values = true;
+            for (const OptimizationResult& r : results) {
+                chains.emplace_back(r.samples.begin() + s0, r.samples.end());
+                have_values = have_values && static_cast<int>(r.sampleObjectiveValues.size()) == ns;
+                if (have_values) values.emplace_back(r.sampleObjectiveValues.begin() + s0, r.sampleObjectiveValues.end());
+            }
+            diagnostics_ = HipChainDiagnostics::compute(*objectives[0], chains, have_values ? values : std::vector<std::vector<double>>{});
+        }
     }
     return results;
 }

@@ -6,6 +6,7 @@
 #include <sstream>
 
 #include "epidemic_hip/BatchedHillClimbing.hpp"
+#include "epidemic_hip/HipChainDiagnostics.hpp"
 #include "epidemic_hip/BatchedParticleSwarm.hpp"
 #include "epidemic_hip/HipModelCalibrator.hpp"
 #include "epidemic_hip/HipNUTSSampler.hpp"
@@ -23,6 +24,8 @@ struct HostHandle {
     std::unique_ptr<CalibrationData> data;
     std::unique_ptr<HipSEPAIHRDObjectiveFunction> obj;
     std::string error;
+    bool mh_diagnostics = false;        // host_set_mh_diagnostics: compute_diagnostics for the runs below
+    ChainDiagnosticsTable last_diag;    // of the last host_mh_run / host_calibrate / host_calibrate_pso
 };
 std::vector<std::string> split_lines(const char* s) {
     std::vector<std::string> out;
@@ -46,6 +49,7 @@ Eigen::VectorXd vec(const double* p, int n) {
 }
 thread_local std::string g_error;
 thread_local double g_last_mh_loop_seconds = 0.0;
+thread_local double g_last_diag_seconds = 0.0;
 }  // namespace
 
 namespace epidemic {
@@ -338,7 +342,9 @@ int host_mh_run(void* hv, int C, const double* initial, uint32_t seed, int itera
                       {"regularization_epsilon", reg_eps}, {"target_acceptance_rate", target_acc},
                       {"adapt_scale", double(adapt_scale)}, {"store_samples", 1.0},
                       {"two_pass_covariance", double(two_pass_covariance)}, {"adaptation_window", double(adaptation_window)},
-                      {"device_streams", double(device_streams)}, {"keep_accept_traces", accept_trace ? 1.0 : 0.0}});
+                      {"device_streams", double(device_streams)}, {"keep_accept_traces", accept_trace ? 1.0 : 0.0},
+                      {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}});
+        h->last_diag = ChainDiagnosticsTable{};
         mh.setSeed(seed);
         std::vector<OptimizationResult> res;
         if (use_scalar_interface == 1) {
@@ -354,6 +360,8 @@ int host_mh_run(void* hv, int C, const double* initial, uint32_t seed, int itera
             res = use_scalar_interface == 2 ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm)  // device-resident state
                                             : mh.optimizeChains(init, C, *h->obj, *h->pm);
             g_last_mh_loop_seconds = mh.lastLoopSeconds();
+            h->last_diag = mh.diagnostics();
+            g_last_diag_seconds = mh.lastDiagnosticsSeconds();
             if (accept_trace)
                 for (int c = 0; c < C; ++c)
                     std::copy(mh.acceptTraces()[static_cast<size_t>(c)].begin(), mh.acceptTraces()[static_cast<size_t>(c)].end(),
@@ -483,13 +491,15 @@ int host_calibrate(void* hv, int hc_iterations, int cloud_size_multiplier, int t
     try {
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);  // mode at construction time
+        h->last_diag = ChainDiagnosticsTable{};
         HipModelCalibrator cal(*h->pm, *h->obj);
         cal.calibrate({{"iterations", double(hc_iterations)}, {"cloud_size_multiplier", double(cloud_size_multiplier)},
                        {"threads", double(threads)}, {"seed", double(hc_seed)}},
                       {{"mcmc_iterations", double(mh_iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
                        {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                       {"seed", double(mh_seed)}, {"store_samples", 1.0}},
+                       {"seed", double(mh_seed)}, {"store_samples", 1.0}, {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}},
                       chains);
+        h->last_diag = cal.diagnostics();
         copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace,
                          samples, sample_values, mcmc_objective_values, n_samples);
         return 0;
@@ -511,15 +521,54 @@ int host_calibrate_pso(void* hv, const char* const* keys, const double* values, 
         h->pm->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);
         std::map<std::string, double> phase1;
         for (int i = 0; i < n_settings; ++i) phase1[keys[i]] = values[i];
+        h->last_diag = ChainDiagnosticsTable{};
         HipModelCalibrator cal(*h->pm, *h->obj);
         cal.setPhase1Algorithm(std::make_unique<BatchedParticleSwarmOptimization>());
         cal.calibrate(phase1,
                       {{"mcmc_iterations", double(mh_iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
                        {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                       {"seed", double(mh_seed)}, {"store_samples", 1.0}},
+                       {"seed", double(mh_seed)}, {"store_samples", 1.0}, {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}},
                       chains);
+        h->last_diag = cal.diagnostics();
         copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace,
                          samples, sample_values, mcmc_objective_values, n_samples);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// Convergence diagnostics (HipChainDiagnostics).  set_mh_diagnostics: host_mh_run (device-resident state), host_calibrate
+// and host_calibrate_pso form the table of their chains (settings key compute_diagnostics); mh_diagnostics serves the last
+// one: *rows = its rows (0: none), out [rows][7] when not NULL.  chain_diagnostics: over host draws samples [C][N][P] (+
+// values [C][N] or NULL) on the handle's device, out [P + (values != NULL)][7], max_lag [..][4] or NULL.  0 ok, 1 error.
+// wall time of sepaihrd_mh_diagnostics in this thread's last host_mh_run (seconds)
+double host_last_mh_diagnostics_seconds(void) { return g_last_diag_seconds; }
+
+void host_set_mh_diagnostics(void* hv, int on) { static_cast<HostHandle*>(hv)->mh_diagnostics = on != 0; }
+
+int host_mh_diagnostics(void* hv, double* out, int32_t* rows) {
+    const ChainDiagnosticsTable& t = static_cast<HostHandle*>(hv)->last_diag;
+    if (rows) *rows = t.rows;
+    if (out) std::copy(t.values.begin(), t.values.end(), out);
+    return 0;
+}
+
+int host_chain_diagnostics(void* hv, const double* samples, const double* values, int C, int N, int P, double* out, int32_t* max_lag) {
+    auto* h = static_cast<HostHandle*>(hv);
+    try {
+        if (!h->obj) throw InvalidParameterException("host_chain_diagnostics", "the handle has no objective (device context)");
+        if (C < 1 || N < 1 || P < 1) throw InvalidParameterException("host_chain_diagnostics", "need C, N, P >= 1");
+        std::vector<std::vector<Eigen::VectorXd>> chains(static_cast<size_t>(C));
+        std::vector<std::vector<double>> vals;
+        for (int c = 0; c < C; ++c)
+            for (int n = 0; n < N; ++n) chains[static_cast<size_t>(c)].push_back(vec(samples + (static_cast<size_t>(c) * N + n) * P, P));
+        if (values)
+            for (int c = 0; c < C; ++c) vals.emplace_back(values + static_cast<size_t>(c) * N, values + static_cast<size_t>(c + 1) * N);
+        const ChainDiagnosticsTable t = HipChainDiagnostics::compute(*h->obj, chains, vals);
+        std::copy(t.values.begin(), t.values.end(), out);
+        if (max_lag) std::copy(t.max_lag.begin(), t.max_lag.end(), max_lag);
         return 0;
     } catch (const std::exception& e) {
         g_error = e.what();

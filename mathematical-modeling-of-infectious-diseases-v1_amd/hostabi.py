@@ -30,6 +30,7 @@ def load_library() -> C.CDLL:
     vp = C.c_void_p
     lib.host_last_error.restype = C.c_char_p
     lib.host_last_mh_loop_seconds.restype = C.c_double
+    lib.host_last_mh_diagnostics_seconds.restype = C.c_double
     lib.host_objective_create.restype = vp
     lib.host_objective_create.argtypes = [C.POINTER(hipabi.sepaihrd_problem), C.c_char_p, C.c_char_p, vp, C.c_int,
                                           C.c_int, C.c_int]
@@ -60,6 +61,10 @@ def load_library() -> C.CDLL:
                                              C.c_char_p, vp, vp, vp]
     lib.host_ene_covid_validation.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_int,
                                               C.c_char_p]
+    lib.host_set_mh_diagnostics.argtypes = [vp, C.c_int]
+    lib.host_set_mh_diagnostics.restype = None
+    lib.host_mh_diagnostics.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    lib.host_chain_diagnostics.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -253,6 +258,35 @@ class HostObjective:
         st = hipabi.build_problem_struct(self.pb, keep)
         if self.lib.host_ene_covid_validation(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning, path.encode()):
             raise RuntimeError("host_ene_covid_validation: " + self.lib.host_last_error().decode())
+
+    def set_mh_diagnostics(self, on: bool) -> None:
+        """Convergence diagnostics for the following metropolis_hastings(device_state=True) / calibrate / calibrate_pso runs
+        (MultiChainMetropolisHastings::setComputeDiagnostics)."""
+        self.lib.host_set_mh_diagnostics(self.h, int(bool(on)))
+
+    def mh_diagnostics(self):
+        """The last such run's table [P (+ 1 values row)][7] (columns hipabi.DIAG_COLUMNS), or None when it formed none."""
+        rows = C.c_int32(0)
+        self.lib.host_mh_diagnostics(self.h, None, C.byref(rows))
+        if rows.value == 0:
+            return None
+        out = np.empty((rows.value, len(hipabi.DIAG_COLUMNS)))
+        self.lib.host_mh_diagnostics(self.h, out.ctypes.data, C.byref(rows))
+        return out
+
+    def chain_diagnostics(self, samples, values=None) -> dict:
+        """HipChainDiagnostics::compute over host draws samples [C][N][P] (+ values [C][N]) on this handle's device:
+        table [P (+ 1)][7], max_lag [..][4] (the NUTS trace or any other sample set)."""
+        s = np.ascontiguousarray(samples, dtype=np.float64)
+        Cn, N, P = s.shape
+        v = None if values is None else np.ascontiguousarray(np.reshape(values, (Cn, N)), dtype=np.float64)
+        rows = P + (0 if v is None else 1)
+        out = np.empty((rows, len(hipabi.DIAG_COLUMNS)))
+        lag = np.empty((rows, 4), dtype=np.int32)
+        if self.lib.host_chain_diagnostics(self.h, s.ctypes.data, None if v is None else v.ctypes.data, Cn, N, P,
+                                           out.ctypes.data, lag.ctypes.data):
+            raise RuntimeError("host_chain_diagnostics: " + self.lib.host_last_error().decode())
+        return {"table": out, "columns": list(hipabi.DIAG_COLUMNS), "max_lag": lag}
 
     def calculate(self, theta) -> float:
         th = np.ascontiguousarray(theta, dtype=np.float64)

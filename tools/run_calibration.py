@@ -52,6 +52,10 @@ def main():
                     help="also the NPI scenario analysis (scenarios/scenario_comparison.csv, the reference's three rows from the "
                          "last analysed sample; scenarios/scenario_posterior.json, every pooled sample under every scenario) "
                          "and seroprevalence/ene_covid_validation.csv")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="also the chains' convergence diagnostics on the device (split R-hat, bulk / tail ESS over the post-burn-in "
+                         "samples): parameter_posteriors/posterior_diagnostics.csv, and max_r_hat / min_ess_bulk / min_ess_tail in "
+                         "run_summary.json")
     args = ap.parse_args()
 
     mm = mmid_amd_loader.load()
@@ -60,6 +64,8 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     host = mm.HostObjective(pb)
 
+    if args.diagnostics:
+        host.set_mh_diagnostics(True)
     t0 = time.perf_counter()
     if args.algorithm == "pso":
         cal = host.calibrate_pso(dict(iterations=args.pso_iterations, swarm_size=args.swarm_size, variant=args.pso_variant,
@@ -72,6 +78,9 @@ def main():
                            cloud_size_multiplier=args.cloud_size_multiplier, threads=args.hc_threads,
                            adaptation_period=args.adaptation_period, thinning=args.thinning, chains=args.chains)
     t_cal = time.perf_counter() - t0
+    diag = host.mh_diagnostics() if args.diagnostics else None
+    if args.diagnostics and diag is None:
+        raise SystemExit("--diagnostics: the run formed no diagnostics (fewer than 4 stored samples after burn-in?)")
     for c in range(args.chains):
         mm.config_io.write_posterior_trace_csv(os.path.join(args.out, f"posterior_trace_chain{c}.csv"), cal["samples"][c],
                                                cal["sample_values"][c], list(pb.param_names))
@@ -123,7 +132,7 @@ def main():
         with open(os.path.join(args.out, "scenarios", "scenario_posterior.json"), "w") as fh:
             json.dump(post, fh, indent=1)
     mm.config_io.write_post_calibration_tree(args.out, times, ens, pooled, list(pb.param_names), pb.n, observed=observed,
-                                             scenarios=scenario_rows, ene_covid=args.scenarios)
+                                             scenarios=scenario_rows, ene_covid=args.scenarios, diagnostics=diag)
     assert len(pos) == ens["ppc"].shape[2]
 
     evals = args.chains * args.mcmc_iterations
@@ -132,6 +141,9 @@ def main():
                "acceptance_rate_mean": float(cal["accept_trace"].mean()), "calibration_seconds": t_cal,
                "proposals_per_s": evals / t_cal, "ensemble_samples": int(len(pooled)), "ensemble_valid": int(ens["n_valid"]),
                "ensemble_seconds": t_ens, "median_R0": float(np.nanmedian(ens["metrics"][:, 0])), "out": args.out}
+    if diag is not None:
+        summary.update(max_r_hat=float(np.nanmax(diag[:, 6])), min_ess_bulk=float(np.nanmin(diag[:, 4])),
+                       min_ess_tail=float(np.nanmin(diag[:, 5])))
     with open(os.path.join(args.out, "run_summary.json"), "w") as fh:
         json.dump(summary, fh, indent=1)
     print(json.dumps(summary))
