@@ -11,6 +11,12 @@ torch.distributed.run, one rank per GPU (RCCL).  Chains are independent, so rank
 chains with no data-path collective ("scaling": "weak"); the only collective is the barrier /
 max-reduction of the elapsed time, plus the optional post-run all-gather of per-chain summaries
 (reported separately, outside the timed region).  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, the untimed pre-warm, the W warm-up steps, the K timed
+steps, --dump-outputs when given, and the line.  Everything else the line can carry runs only with --full, after the
+timed region as before: the kernel's own time (roofline), the other arithmetic on the same draws (value_strict), the CPU
+baseline, the other BASELINE workloads and the Adaptive-Metropolis runs.  Without --full, roofline, config.other_arith,
+cpu_baseline, other_workloads and sampler_pipeline are null, and so is value_strict unless the headline itself is strict.
 """
 import argparse
 import json
@@ -63,16 +69,20 @@ def parse_args():
     ap.add_argument("--precision", choices=["f64", "f32"], default="f64",
                     help="number type of the ODE state: f64 = the reference's arithmetic (headline); f32 = the fp32-state arm "
                          "of BASELINE configs[4]'s sweep (fp64 likelihood), 3..16 age classes")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: the kernel's own time "
+                         "(roofline), the other arithmetic (value_strict), the CPU baseline, the other BASELINE workloads and "
+                         "the sampler runs (about a minute and a half); off by default, and those fields are null")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget, with --full (0 = skip)")
     ap.add_argument("--allgather", action="store_true", help="time the RCCL all-gather of chain summaries")
     ap.add_argument("--other-workloads", type=int, default=1,
-                    help="1 (default, with --workload c1 on one GPU): a few steps of every other BASELINE config after the timed region "
-                         "(other_workloads in the line; about 25 s, most of it generating their draws); 0 = skip")
+                    help="1 (default, with --full and --workload c1 on one GPU): a few steps of every other BASELINE config after the "
+                         "timed region (other_workloads in the line; about 25 s, most of it generating their draws); 0 = skip")
     ap.add_argument("--sampler-iterations", type=int, default=400,
-                    help="informational Adaptive-Metropolis run around the kernel after the timed region (0 = skip)")
+                    help="with --full: informational Adaptive-Metropolis run around the kernel after the timed region (0 = skip)")
     ap.add_argument("--sampler-long-iterations", type=int, default=100000,
-                    help="one more such run at the reference's own settings (data/configuration/mcmc_settings.txt: 100 000 "
-                         "iterations, burn-in 5 000, adaptation_period 100, thinning 100): about a minute (0 = skip)")
+                    help="with --full: one more such run at the reference's own MCMC settings (100 000 iterations, "
+                         "burn-in 5 000, adaptation_period 100, thinning 100): about a minute (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (loglik, status, n_accept, n_reject of "
                          "every chain, all ranks in rank order, and the chain index) as DIR/<name>.npy in float64; "
@@ -468,22 +478,23 @@ def main():
     # --dump-outputs: what the last timed step returned, copied before the passes below reuse the buffers
     last_step = ({"loglik": d_ll.clone(), "status": d_status.clone(), "n_accept": d_acc.clone(), "n_reject": d_rej.clone()}
                  if args.dump_outputs is not None else None)
-    # The dominant kernel's own duration: a SECOND pass of the same K steps, outside the timed region, with HIP events
+    # --full: the dominant kernel's own duration: a SECOND pass of the same K steps, outside the timed region, with HIP events
     # on the launch stream around the integrator kernel and the likelihood pass of EVERY launch (the records cost ~15 us of
     # stream time per launch, which is why they are not in the timed pass: the kernel time is what they bracket, not
     # what they cost).  roofline.achieved divides by this; roofline.frac_of_step divides by ms_per_step instead.
-    hip.set_timing(1)
-    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    k0.record(stream)
-    for i in range(K):
-        step(i)
-    k1.record(stream)
-    torch.cuda.synchronize(dev)
-    kernel_pass_step_ms = k0.elapsed_time(k1) / max(K, 1)   # that pass's OWN step: kernel_ms is part of it by construction
-    tm = hip.get_timing()
-    hip.set_timing(False)
-    kernel_ms = tm["integrator_ms"] / max(tm["launches"], 1)      # dominant kernel: sepaihrd_eval_kernel
-    ll_pass_ms = tm["likelihood_ms"] / max(tm["launches"], 1)     # ll_terms + ll_reduce (0 when inline)
+    if args.full:
+        hip.set_timing(1)
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        k0.record(stream)
+        for i in range(K):
+            step(i)
+        k1.record(stream)
+        torch.cuda.synchronize(dev)
+        kernel_pass_step_ms = k0.elapsed_time(k1) / max(K, 1)   # that pass's OWN step: kernel_ms is part of it by construction
+        tm = hip.get_timing()
+        hip.set_timing(False)
+        kernel_ms = tm["integrator_ms"] / max(tm["launches"], 1)      # dominant kernel: sepaihrd_eval_kernel
+        ll_pass_ms = tm["likelihood_ms"] / max(tm["launches"], 1)     # ll_terms + ll_reduce (0 when inline)
 
     el = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
     if world > 1:
@@ -494,28 +505,36 @@ def main():
     acc = d_acc.cpu().numpy().astype(np.float64)
     rej = d_rej.cpu().numpy().astype(np.float64)
 
-    # the other arithmetic mode, same draws, reported next to the headline (not part of `value`)
+    # --full: the other arithmetic mode, same draws, reported next to the headline (not part of `value`)
     other = "strict" if args.arith == "fma" else "fma"
     if args.precision == "f32":  # next to the fp32 arm: the fp64 production arithmetic on the same draws
         other = "fma"
-        hip.set_precision(mm.PRECISION_F64)
-    hip.set_arith(mm.ARITH_STRICT if other == "strict" else mm.ARITH_FMA)
-    for i in range(max(1, W)):
-        step(i)
-    torch.cuda.synchronize(dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t_other = time.perf_counter()
-    e0.record(stream)
-    n_other = max(1, K)  # the SAME number of steps as the headline
-    for i in range(n_other):
-        step(i)
-    e1.record(stream)
-    torch.cuda.synchronize(dev)
-    other_wall_ms = (time.perf_counter() - t_other) * 1e3 / n_other
-    other_ms = e0.elapsed_time(e1) / n_other
-    strict_wall_ms = other_wall_ms if other == "strict" else (elapsed / max(K, 1) * 1e3 if args.arith == "strict" and args.precision == "f64" else None)
-    hip.set_arith(pb.arith)
-    hip.set_precision(pb.precision)
+    other_arith = None
+    strict_wall_ms = elapsed / max(K, 1) * 1e3 if args.arith == "strict" and args.precision == "f64" else None
+    if args.full:
+        if args.precision == "f32":
+            hip.set_precision(mm.PRECISION_F64)
+        hip.set_arith(mm.ARITH_STRICT if other == "strict" else mm.ARITH_FMA)
+        for i in range(max(1, W)):
+            step(i)
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t_other = time.perf_counter()
+        e0.record(stream)
+        n_other = max(1, K)  # the SAME number of steps as the headline
+        for i in range(n_other):
+            step(i)
+        e1.record(stream)
+        torch.cuda.synchronize(dev)
+        other_wall_ms = (time.perf_counter() - t_other) * 1e3 / n_other
+        other_ms = e0.elapsed_time(e1) / n_other
+        if other == "strict":
+            strict_wall_ms = other_wall_ms
+        hip.set_arith(pb.arith)
+        hip.set_precision(pb.precision)
+        other_arith = {"mode": other if args.precision == "f64" else "f64 " + other, "steps": n_other, "ms_per_step": other_wall_ms,
+                       "ms_per_step_on_stream": other_ms,
+                       "evals_per_s_per_gpu": B / (other_wall_ms * 1e-3)}
 
     allgather_ms = None
     allgather_check = None
@@ -556,47 +575,29 @@ def main():
         evals_total = world * B * K
         value = evals_total / elapsed_max
         info = hip.kernel_info(B)
-        bytes_eval = 8 * P + 16 + problem_bytes(pb) / B        # theta in, loglik + counters out
-        split_ll = info.get("likelihood_form", 0) == 1 and args.precision == "f64"  # SEPAIHRD_LL_SEPARATE_PASS: increments parked in HBM
-        ws_bytes_eval = pb.n_times * 3 * pb.n * 8 if split_ll else 0
-        bytes_launch = bytes_eval * B
-        achieved = bytes_launch / (kernel_ms * 1e-3) / 1e9
-        flops_eval = algorithmic_flops_per_eval(pb.n, float(acc.mean()), pb.n_obs)
-        fp64_tflops = flops_eval * B / (kernel_ms * 1e-3) / 1e12
-        traffic = None
-        traffic_src = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(traffic_src):
-            try:
-                with open(traffic_src) as fh:
-                    tj = json.load(fh)
-                key = f"{args.workload}_{solver_name}_{args.arith if args.precision == 'f64' else 'f32'}_B{B}"
-                traffic = tj.get(key, {}).get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-        out = {
-            "metric": "ODE-solve+likelihood evals/sec (SEPAIHRD %d-age, %dd)" % (pb.n, int(pb.times[-1] - pb.times[0])),
-            "value": value, "unit": "evals/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": elapsed_max / max(K, 1) * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64" if args.precision == "f64" else "f32", "data": "synthetic",
-            # the bit-exact-contract arithmetic on the same draws over the same number of steps (config.parity_mode)
-            "value_strict": (world * B / (strict_wall_ms * 1e-3)) if strict_wall_ms else None,
-            "config": {
-                "workload": f"BASELINE {args.workload}: SEPAIHRD {pb.n} age groups, {solver_name}, "
-                            f"{int(pb.times[-1] - pb.times[0])} days (T={pb.n_times}), {B} chains/GPU, fp64",
-                "chains_per_gpu": B, "n_params": P, "abs_err": pb.abs_err, "rel_err": pb.rel_err,
-                "pre_warmup_steps": pre_warm_steps,  # untimed, before the W warm-up steps: PRE_WARM_SECONDS of the same step
-                "arith": args.arith if args.precision == "f64" else "f32 state (fma), fp64 likelihood / time / theta",
-                "other_arith": {"mode": other if args.precision == "f64" else "f64 " + other, "steps": n_other, "ms_per_step": other_wall_ms,
-                                "ms_per_step_on_stream": other_ms,
-                                "evals_per_s_per_gpu": B / (other_wall_ms * 1e-3)},
-                "parity_mode": PARITY_NOTES,
-                "draws": "reflect(base + sigma*N(0,1)), mt19937(1+chain), libstdc++ order",
-                "parallelism": f"chains sharded over {world} GPU(s), no data-path collective",
-            },
+        roofline = None  # --full: needs the kernel pass
+        if args.full:
+            bytes_eval = 8 * P + 16 + problem_bytes(pb) / B        # theta in, loglik + counters out
+            split_ll = info.get("likelihood_form", 0) == 1 and args.precision == "f64"  # SEPAIHRD_LL_SEPARATE_PASS: increments parked in HBM
+            ws_bytes_eval = pb.n_times * 3 * pb.n * 8 if split_ll else 0
+            bytes_launch = bytes_eval * B
+            achieved = bytes_launch / (kernel_ms * 1e-3) / 1e9
+            flops_eval = algorithmic_flops_per_eval(pb.n, float(acc.mean()), pb.n_obs)
+            fp64_tflops = flops_eval * B / (kernel_ms * 1e-3) / 1e12
+            traffic = None
+            traffic_src = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(traffic_src):
+                try:
+                    with open(traffic_src) as fh:
+                        tj = json.load(fh)
+                    key = f"{args.workload}_{solver_name}_{args.arith if args.precision == 'f64' else 'f32'}_B{B}"
+                    traffic = tj.get(key, {}).get("hbm_bytes_per_launch")
+                except Exception:
+                    traffic = None
             # the binding resource first: ~4000 flop per byte puts the path on the FP64 vector ALU, not on
             # HBM and not on MFMA (a 4x4 contact contraction is far below a tile); the HBM figures BASELINE.json asks
             # for follow in "hbm"
-            "roofline": {
+            roofline = {
                 "bound": "fp64_valu" if args.precision == "f64" else "fp32_valu", "achieved": fp64_tflops,
                 "peak": FP64_VALU_PEAK_TFLOPS if args.precision == "f64" else 2 * FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "frac": fp64_tflops / (FP64_VALU_PEAK_TFLOPS if args.precision == "f64" else 2 * FP64_VALU_PEAK_TFLOPS),
@@ -621,7 +622,27 @@ def main():
                         "achieved_incl_workspace": (bytes_eval + ws_bytes_eval) * B / (kernel_ms * 1e-3) / 1e9,
                         "note": "BASELINE.json asks for the HBM fraction: reported, never padded -- the path moves "
                                 "~0.5 KB per 2 MFLOP evaluation and cannot approach the HBM roof"},
+            }
+        out = {
+            "metric": "ODE-solve+likelihood evals/sec (SEPAIHRD %d-age, %dd)" % (pb.n, int(pb.times[-1] - pb.times[0])),
+            "value": value, "unit": "evals/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": elapsed_max / max(K, 1) * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64" if args.precision == "f64" else "f32", "data": "synthetic",
+            # the bit-exact-contract arithmetic on the same draws over the same number of steps (config.parity_mode)
+            "value_strict": (world * B / (strict_wall_ms * 1e-3)) if strict_wall_ms else None,
+            "config": {
+                "workload": f"BASELINE {args.workload}: SEPAIHRD {pb.n} age groups, {solver_name}, "
+                            f"{int(pb.times[-1] - pb.times[0])} days (T={pb.n_times}), {B} chains/GPU, fp64",
+                "chains_per_gpu": B, "n_params": P, "abs_err": pb.abs_err, "rel_err": pb.rel_err,
+                "pre_warmup_steps": pre_warm_steps,  # untimed, before the W warm-up steps: PRE_WARM_SECONDS of the same step
+                "arith": args.arith if args.precision == "f64" else "f32 state (fma), fp64 likelihood / time / theta",
+                "other_arith": other_arith,
+                "full": args.full,  # without it, the fields the module docstring names are null
+                "parity_mode": PARITY_NOTES,
+                "draws": "reflect(base + sigma*N(0,1)), mt19937(1+chain), libstdc++ order",
+                "parallelism": f"chains sharded over {world} GPU(s), no data-path collective",
             },
+            "roofline": roofline,
             "kernel_info": {k: info[k] for k in ("lanes_per_chain", "chains_per_wave", "vgprs", "lds_bytes",
                                                  "scratch_bytes", "max_blocks_per_cu", "num_cus",
                                                  "device_name", "phase_pass_applied")},
@@ -636,12 +657,12 @@ def main():
                                 "blocks_in_rank_order": allgather_check}
         if rehearsal:
             out["rehearsal"] = True  # not a measurement: every rank shares device 0
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(pb, pools_host[0], args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
         out["other_workloads"] = None
-        if world == 1 and args.workload == "c1" and args.other_workloads and args.precision == "f64":
+        if args.full and world == 1 and args.workload == "c1" and args.other_workloads and args.precision == "f64":
             tt = {}
             try:
                 with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as fh:
@@ -657,7 +678,7 @@ def main():
                     out["other_workloads"][key] = {"error": str(e)[:200]}
         out["sampler_pipeline"] = (sampler_pipeline(mm, pb, pools_host[0], args.sampler_iterations,
                                                     args.sampler_long_iterations if args.workload == "c1" else 0, out["ms_per_step"])
-                                   if world == 1 and args.sampler_iterations > 1 else None)
+                                   if args.full and world == 1 and args.sampler_iterations > 1 else None)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

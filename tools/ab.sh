@@ -14,7 +14,7 @@ for W in $WL; do
   for rep in $(seq 1 $REPS); do
     for L in "$@"; do
       if [ "$L" = shipped ]; then unset SEPAIHRD_HIP_LIB; else export SEPAIHRD_HIP_LIB=$PWD/$L; fi
-      python3 bench.py --workload $W --steps $STEPS --warmup 3 --cpu-seconds 0 --sampler-iterations 0 --other-workloads 0 $ARGS 2>/dev/null | python3 -c "
+      python3 bench.py --full --workload $W --steps $STEPS --warmup 3 --cpu-seconds 0 --sampler-iterations 0 --other-workloads 0 $ARGS 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('%-3s %-34s %10.0f evals/s  %8.4f ms/step  other arith %8.4f  kernel %8.4f + ll %6.4f  vgprs %d' % ('$W', '$L', d['value'], d['ms_per_step'], d['config']['other_arith']['ms_per_step'], r['kernel_ms'], r['likelihood_pass_ms'], d['kernel_info']['vgprs']))"

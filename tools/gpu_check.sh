@@ -13,7 +13,7 @@ fi
 RC=$?
 tail -8 $O/${TAG}_tests.log
 [ $RC -ne 0 ] && exit $RC
-python bench.py ${BENCH_ARGS:-} > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -c 800 $O/${TAG}_bench.err; exit 1; }
+python bench.py --full ${BENCH_ARGS:-} > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -c 800 $O/${TAG}_bench.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/${TAG}_bench.json"))

@@ -6,7 +6,7 @@ O=gpurun_out/measure
 mkdir -p $O
 set -o pipefail
 for W in c1 c3 c2 c5; do
-  python3 bench.py --workload $W --steps 10 --warmup 2 --sampler-iterations 0 --cpu-seconds 0 > $O/bench_$W.json 2> $O/bench_$W.err \
+  python3 bench.py --full --workload $W --steps 10 --warmup 2 --sampler-iterations 0 --cpu-seconds 0 > $O/bench_$W.json 2> $O/bench_$W.err \
     && python3 -c "import json,sys; d=json.load(open('$O/bench_$W.json')); print('$W', round(d['value']), 'evals/s', round(d['ms_per_step'],3), 'ms/step; other arithmetic', round(d['config']['other_arith']['evals_per_s_per_gpu']))"
 done
 python3 tools/sweep_batch.py 2>/dev/null | tee $O/sweep_batch.log | grep -c chains

@@ -5,7 +5,7 @@
 #   tools/profile_round.sh r04_c3_fma "--workload c3 --steps 10 --warmup 2"
 TAG=${1:-r04_c1_fma}
 ARGS=${2:-"--steps 20 --warmup 3"}
-COMMON="--cpu-seconds 0 --sampler-iterations 0 --other-workloads 0"
+COMMON="--full --cpu-seconds 0 --sampler-iterations 0 --other-workloads 0"
 R=$PWD
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
