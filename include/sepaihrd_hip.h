@@ -567,6 +567,73 @@ int sepaihrd_get_kernel_info(sepaihrd_ctx *ctx, sepaihrd_kernel_info *info);
  * the two forms.  batch_chains <= 0: the large-batch kernel (what sepaihrd_get_kernel_info reports). */
 int sepaihrd_get_kernel_info_for_batch(sepaihrd_ctx *ctx, int32_t batch_chains, sepaihrd_kernel_info *info);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Age-structured SIR model: a batched PoissonLikelihoodObjective::calculate on the device (csrc/sepaihrd_sir.hip,
+ * csrc/sepaihrd_sir_capi.cpp).  Additive: nothing above changes, SEPAIHRD_ABI_VERSION stays as it is.
+ * Reference behaviour (paths under the reference tree):
+ *   right-hand side          src/sir_age_structured/AgeSIRModel.cpp:106-139
+ *   model validation         src/sir_age_structured/AgeSIRModel.cpp:66-77 (validate_parameters)
+ *   constraints, theta       src/sir_age_structured/parameters/SIRParameterManager.cpp:98-156
+ *   incidence                src/sir_age_structured/SimulationResultProcessor.cpp:144-189
+ *   objective                src/sir_age_structured/objectives/PoissonLikelihoodObjective.cpp:46-144
+ *   grid rules               src/sir_age_structured/Simulator.cpp:60-150
+ * Per chain: theta -> max(1e-12, q) / max(0, scale_C_total) / max(0, gamma_i) (no bounds, no reflect mode in this
+ * manager; fields that are not calibrated keep the problem's values) -> integrate_times from the FIXED initial_state
+ * [S(n), I(n), R(n)] -> at EVERY output time incidence_i = lambda_i(x(t)) S_i(t), sim = max(incidence, 1e-9),
+ * obs = max(observed, 0), loglik = sum_t sum_i (obs log(sim) - sim), added in (t, i) row order.
+ * Failure convention (differs from the SEPAIHRD objective): this objective catches every exception, so a chain that
+ * fails returns -INFINITY (not lowest()) with its status set -- SEPAIHRD_STATUS_INVALID for a non-finite observation,
+ * incidence or total, _STEP_FAILURE, _STEP_BUDGET -- and nothing is raised.  A NaN observation counts as non-finite.
+ * F64 state only, one lane per (chain, age class), 1 <= n_age <= 64; no quad-lane form.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SEPAIHRD_SIR_NUM_COMPARTMENTS 3 /* S, I, R */
+/* param_field codes of sepaihrd_sir_problem */
+#define SEPAIHRD_SIR_F_Q 0             /* "q" */
+#define SEPAIHRD_SIR_F_SCALE_C_TOTAL 1 /* "scale_C_total" */
+#define SEPAIHRD_SIR_F_GAMMA 2         /* "gamma_<i>", i in param_index */
+
+typedef struct sepaihrd_sir_problem {
+    int32_t abi_version; /* SEPAIHRD_ABI_VERSION */
+    int32_t n_age;       /* n */
+    int32_t n_times;     /* T: output times = rows of obs (PoissonLikelihoodObjective.cpp:38-42) */
+    int32_t n_params;    /* P */
+    int32_t solver;      /* SEPAIHRD_SOLVER_* */
+    int32_t arith;       /* SEPAIHRD_ARITH_* */
+    int32_t max_attempts; /* step-attempt budget per chain; <= 0: 1000000 */
+    int32_t reserved;
+    const double *times;         /* [T] strictly increasing */
+    const double *N;             /* [n] population sizes, >= 0 */
+    const double *C;             /* [n*n] ROW-major baseline contact matrix, entries >= 0 */
+    const double *gamma;         /* [n] recovery rates, >= 0 */
+    const double *initial_state; /* [3n] S(n), I(n), R(n) */
+    const double *obs;           /* [T*n] row-major observed incidence */
+    const int32_t *param_field;  /* [P] SEPAIHRD_SIR_F_* */
+    const int32_t *param_index;  /* [P] age class of a SEPAIHRD_SIR_F_GAMMA entry, ignored otherwise */
+    double q;             /* transmissibility, >= 0 */
+    double scale_C_total; /* contact scale factor, >= 0 */
+    double abs_err, rel_err, dt_hint;
+} sepaihrd_sir_problem;
+
+typedef struct sepaihrd_sir_ctx sepaihrd_sir_ctx;
+
+/* Validates the problem (Simulator::run grid rules; AgeSIRModel::validate_parameters: a negative N / gamma / q / scale / C
+ * entry is refused with a message; field codes and gamma indices), uploads it once.  NULL + message on failure; there is no
+ * CPU fallback (no device: the message says so).  Validation comes before the device is touched. */
+sepaihrd_sir_ctx *sepaihrd_sir_create(const sepaihrd_sir_problem *pb, int device, char *err, int errlen);
+void sepaihrd_sir_destroy(sepaihrd_sir_ctx *ctx);
+const char *sepaihrd_sir_last_error(const sepaihrd_sir_ctx *ctx);
+/* theta [B][P] host; loglik [B]; status / n_accept / n_reject [B] or NULL; traj [B][T][3n] or NULL.  Synchronous. */
+int sepaihrd_sir_eval_batch(sepaihrd_sir_ctx *ctx, const double *theta, int B, double *loglik, int32_t *status,
+                            int32_t *n_accept, int32_t *n_reject, double *traj);
+/* The same on device-resident arrays, asynchronous on `stream` (a hipStream_t, NULL: the default stream); allocates nothing. */
+int sepaihrd_sir_eval_batch_device(sepaihrd_sir_ctx *ctx, const double *d_theta, int B, double *d_loglik, int32_t *d_status,
+                                   int32_t *d_n_accept, int32_t *d_n_reject, double *d_traj, void *stream);
+/* Sizes the staging buffers of sepaihrd_sir_eval_batch for max_B chains ahead of time. */
+int sepaihrd_sir_reserve(sepaihrd_sir_ctx *ctx, int max_B);
+/* SIRParameterManager::applyConstraints on B host vectors (no device work). */
+int sepaihrd_sir_apply_constraints(const sepaihrd_sir_ctx *ctx, const double *in, int B, double *out);
+int sepaihrd_sir_set_arith(sepaihrd_sir_ctx *ctx, int arith);
+
 #ifdef __cplusplus
 }
 #endif

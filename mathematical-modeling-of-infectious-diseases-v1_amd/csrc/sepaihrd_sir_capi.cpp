@@ -1,0 +1,276 @@
+// csrc/sepaihrd_sir_capi.cpp -- the age-structured SIR block of the C ABI (include/sepaihrd_hip.h, sepaihrd_sir_*).
+// Host side only: validates the problem, pads the per-age tables to the lanes of a chain, uploads them once and launches
+// the kernels of csrc/sepaihrd_sir.hip.  There is no CPU evaluation path.
+#include "sepaihrd_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sepaihrd_device.h"
+#include "sepaihrd_sir_device.h"
+
+using namespace sepaihrd;
+
+struct sepaihrd_sir_ctx {
+    int device = 0, solver = 0, arith = 0;
+    int n = 0, T = 0, P = 0;
+    SirDevProblem dp{};
+    std::vector<void*> allocs;
+    std::vector<int32_t> field;  // host copy for sepaihrd_sir_apply_constraints
+    std::string last_error;
+    // staging of the host-pointer entry point (grow-only)
+    size_t cap_B = 0, cap_traj = 0;
+    double* d_theta = nullptr;
+    double* d_loglik = nullptr;
+    int32_t* d_ints = nullptr;  // [3][cap_B] status, accepted, rejected
+    double* d_traj = nullptr;
+};
+
+namespace {
+
+void set_err(char* err, int errlen, const std::string& msg) {
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
+}
+
+#define SIR_HIP_TRY(expr, ctx, fail)                                                 \
+    do {                                                                             \
+        hipError_t e_ = (expr);                                                      \
+        if (e_ != hipSuccess) {                                                      \
+            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);   \
+            fail;                                                                    \
+        }                                                                            \
+    } while (0)
+
+template <class T>
+const T* upload(sepaihrd_sir_ctx* ctx, const std::vector<T>& v, bool& ok) {
+    void* p = nullptr;
+    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);  // a valid allocation even when empty
+    if (hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
+    ctx->allocs.push_back(p);
+    if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    return static_cast<const T*>(p);
+}
+
+void free_staging(sepaihrd_sir_ctx* c) {
+    void* ptrs[] = {c->d_theta, c->d_loglik, c->d_ints, c->d_traj};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    c->d_theta = c->d_loglik = c->d_traj = nullptr;
+    c->d_ints = nullptr;
+    c->cap_B = c->cap_traj = 0;
+}
+
+int ensure_staging(sepaihrd_sir_ctx* c, size_t B, size_t traj_elems) {
+    if (B > c->cap_B) {
+        void* ptrs[] = {c->d_theta, c->d_loglik, c->d_ints};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        c->d_theta = c->d_loglik = nullptr;
+        c->d_ints = nullptr;
+        c->cap_B = 0;
+        SIR_HIP_TRY(hipMalloc((void**)&c->d_theta, B * c->P * sizeof(double)), c, return SEPAIHRD_E_HIP);
+        SIR_HIP_TRY(hipMalloc((void**)&c->d_loglik, B * sizeof(double)), c, return SEPAIHRD_E_HIP);
+        SIR_HIP_TRY(hipMalloc((void**)&c->d_ints, 3 * B * sizeof(int32_t)), c, return SEPAIHRD_E_HIP);
+        c->cap_B = B;
+    }
+    if (traj_elems > c->cap_traj) {
+        if (c->d_traj) (void)hipFree(c->d_traj);
+        c->d_traj = nullptr;
+        c->cap_traj = 0;
+        SIR_HIP_TRY(hipMalloc((void**)&c->d_traj, traj_elems * sizeof(double)), c, return SEPAIHRD_E_HIP);
+        c->cap_traj = traj_elems;
+    }
+    return SEPAIHRD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+sepaihrd_sir_ctx* sepaihrd_sir_create(const sepaihrd_sir_problem* pb, int device, char* err, int errlen) {
+    if (!pb) { set_err(err, errlen, "problem is NULL"); return nullptr; }
+    if (pb->abi_version != SEPAIHRD_ABI_VERSION) { set_err(err, errlen, "ABI version mismatch"); return nullptr; }
+    const int n = pb->n_age, T = pb->n_times, P = pb->n_params;
+    if (n < 1 || n > SEPAIHRD_MAX_AGE_CLASSES) { set_err(err, errlen, "n_age out of range [1,64]"); return nullptr; }
+    if (T < 1) { set_err(err, errlen, "n_times must be >= 1"); return nullptr; }
+    if (P < 1) { set_err(err, errlen, "n_params must be >= 1"); return nullptr; }
+    if (!pb->times || !pb->N || !pb->C || !pb->gamma || !pb->initial_state || !pb->obs || !pb->param_field || !pb->param_index) {
+        set_err(err, errlen, "a required array pointer is NULL"); return nullptr;
+    }
+    if (pb->solver != SEPAIHRD_SOLVER_DOPRI5 && pb->solver != SEPAIHRD_SOLVER_CASH_KARP54 && pb->solver != SEPAIHRD_SOLVER_FEHLBERG78) {
+        set_err(err, errlen, "unknown solver"); return nullptr;
+    }
+    if (pb->arith != SEPAIHRD_ARITH_STRICT && pb->arith != SEPAIHRD_ARITH_FMA) { set_err(err, errlen, "unknown arithmetic mode"); return nullptr; }
+    // Simulator::run grid rules (Simulator.cpp:78-88) and its ctor checks
+    for (int i = 1; i < T; ++i)
+        if (!(pb->times[i] > pb->times[i - 1])) { set_err(err, errlen, "time points must be strictly increasing"); return nullptr; }
+    if (pb->abs_err < 0 || pb->rel_err < 0) { set_err(err, errlen, "negative error tolerance"); return nullptr; }
+    if (!(pb->dt_hint > 0)) { set_err(err, errlen, "dt_hint must be positive"); return nullptr; }
+    // AgeSIRModel::validate_parameters (AgeSIRModel.cpp:66-77)
+    for (int i = 0; i < n; ++i) {
+        if (pb->N[i] < 0) { set_err(err, errlen, "Population sizes (N) cannot be negative."); return nullptr; }
+        if (pb->gamma[i] < 0) { set_err(err, errlen, "Recovery rates (gamma) cannot be negative."); return nullptr; }
+    }
+    if (pb->q < 0) { set_err(err, errlen, "Transmissibility (q) cannot be negative."); return nullptr; }
+    if (pb->scale_C_total < 0) { set_err(err, errlen, "Contact scale factor (scale_C_total) cannot be negative."); return nullptr; }
+    for (int i = 0; i < n * n; ++i)
+        if (pb->C[i] < 0) { set_err(err, errlen, "Baseline contact matrix entries cannot be negative."); return nullptr; }
+    for (int p = 0; p < P; ++p) {
+        const int f = pb->param_field[p];
+        if (f != SEPAIHRD_SIR_F_Q && f != SEPAIHRD_SIR_F_SCALE_C_TOTAL && f != SEPAIHRD_SIR_F_GAMMA) {
+            set_err(err, errlen, "param " + std::to_string(p) + ": unknown field code"); return nullptr;
+        }
+        if (f == SEPAIHRD_SIR_F_GAMMA && (pb->param_index[p] < 0 || pb->param_index[p] >= n)) {
+            set_err(err, errlen, "param " + std::to_string(p) + ": age index out of range"); return nullptr;
+        }
+    }
+
+    int ndev = 0;
+    {
+        const hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess || ndev <= 0) {
+            set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): hipGetDeviceCount -> ") +
+                                     hipGetErrorString(e) + ", count " + std::to_string(ndev));
+            return nullptr;
+        }
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return nullptr; }
+    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return nullptr; }
+
+    auto* ctx = new sepaihrd_sir_ctx();
+    ctx->device = device; ctx->solver = pb->solver; ctx->arith = pb->arith;
+    ctx->n = n; ctx->T = T; ctx->P = P;
+    ctx->field.assign(pb->param_field, pb->param_field + P);
+
+    const int lpc = lanes_per_chain(n);
+    std::vector<double> Npad(lpc, 0.0), gpad(lpc, 0.0), Cpad((size_t)lpc * lpc, 0.0), init((size_t)SIR_COMP * lpc, 0.0),
+        obs((size_t)T * lpc, 0.0);
+    for (int i = 0; i < n; ++i) { Npad[i] = pb->N[i]; gpad[i] = pb->gamma[i]; }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) Cpad[(size_t)i * lpc + j] = pb->C[(size_t)i * n + j];
+    for (int c = 0; c < SIR_COMP; ++c)
+        for (int i = 0; i < n; ++i) init[(size_t)c * lpc + i] = pb->initial_state[(size_t)c * n + i];
+    int obs_not_finite = 0;
+    for (int k = 0; k < T; ++k)
+        for (int i = 0; i < n; ++i) {
+            const double o = pb->obs[(size_t)k * n + i];
+            const double y = (o < 0.0) ? 0.0 : o;  // cwiseMax(0.0); +inf and NaN stay as they are
+            if (!std::isfinite(y)) obs_not_finite = 1;
+            obs[(size_t)k * lpc + i] = y;
+        }
+    double max_gap = 0.0;
+    for (int i = 1; i < T; ++i) max_gap = std::max(max_gap, pb->times[i] - pb->times[i - 1]);
+
+    SirDevProblem& d = ctx->dp;
+    d.n = n; d.lpc = lpc; d.T = T; d.P = P;
+    d.max_attempts = pb->max_attempts > 0 ? pb->max_attempts : 1000000;
+    d.obs_not_finite = obs_not_finite;
+    d.abs_tol = pb->abs_err; d.rel_tol = pb->rel_err; d.dt_hint = pb->dt_hint; d.max_gap = max_gap;
+    d.q = pb->q; d.scale = pb->scale_C_total;
+    bool ok = true;
+    d.times = upload(ctx, std::vector<double>(pb->times, pb->times + T), ok);
+    d.N = upload(ctx, Npad, ok);
+    d.C = upload(ctx, Cpad, ok);
+    d.gamma = upload(ctx, gpad, ok);
+    d.init_state = upload(ctx, init, ok);
+    d.obs = upload(ctx, obs, ok);
+    d.param_field = upload(ctx, ctx->field, ok);
+    d.param_index = upload(ctx, std::vector<int32_t>(pb->param_index, pb->param_index + P), ok);
+    if (!ok) {
+        set_err(err, errlen, "device allocation / upload failed");
+        sepaihrd_sir_destroy(ctx);
+        return nullptr;
+    }
+    return ctx;
+}
+
+void sepaihrd_sir_destroy(sepaihrd_sir_ctx* ctx) {
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    free_staging(ctx);
+    for (void* p : ctx->allocs) (void)hipFree(p);
+    delete ctx;
+}
+
+const char* sepaihrd_sir_last_error(const sepaihrd_sir_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "ctx is NULL"; }
+
+int sepaihrd_sir_set_arith(sepaihrd_sir_ctx* ctx, int arith) {
+    if (!ctx || (arith != SEPAIHRD_ARITH_STRICT && arith != SEPAIHRD_ARITH_FMA)) return SEPAIHRD_E_INVALID_ARG;
+    ctx->arith = arith;
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_sir_reserve(sepaihrd_sir_ctx* ctx, int max_B) {
+    if (!ctx || max_B < 0) return SEPAIHRD_E_INVALID_ARG;
+    SIR_HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    return ensure_staging(ctx, (size_t)max_B, 0);
+}
+
+int sepaihrd_sir_eval_batch_device(sepaihrd_sir_ctx* ctx, const double* d_theta, int B, double* d_loglik, int32_t* d_status,
+                                   int32_t* d_n_accept, int32_t* d_n_reject, double* d_traj, void* stream) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (B < 0 || (B > 0 && (!d_theta || !d_loglik))) {
+        ctx->last_error = "sir_eval_batch_device: NULL theta/loglik or negative B";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (B == 0) return SEPAIHRD_OK;
+    const SirOutputs out{d_loglik, d_status, d_n_accept, d_n_reject, d_traj};
+    const int rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_sir_eval_fma(ctx->dp, ctx->solver, d_theta, B, out, stream)
+                                                    : launch_sir_eval_strict(ctx->dp, ctx->solver, d_theta, B, out, stream);
+    if (rc != 0) {
+        ctx->last_error = rc == -4 ? "unsupported lanes-per-chain or solver" : "kernel launch failed";
+        return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
+    }
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_sir_eval_batch(sepaihrd_sir_ctx* ctx, const double* theta, int B, double* loglik, int32_t* status, int32_t* n_accept,
+                            int32_t* n_reject, double* traj) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (B < 0 || (B > 0 && (!theta || !loglik))) {
+        ctx->last_error = "sir_eval_batch: NULL theta/loglik or negative B";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (B == 0) return SEPAIHRD_OK;
+    SIR_HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    const size_t nB = (size_t)B;
+    const size_t traj_elems = traj ? nB * ctx->T * SIR_COMP * ctx->n : 0;
+    {
+        const int rc = ensure_staging(ctx, nB, traj_elems);
+        if (rc != SEPAIHRD_OK) return rc;
+    }
+    int32_t* d_status = ctx->d_ints;
+    int32_t* d_nacc = ctx->d_ints + ctx->cap_B;
+    int32_t* d_nrej = ctx->d_ints + 2 * ctx->cap_B;
+    SIR_HIP_TRY(hipMemcpy(ctx->d_theta, theta, nB * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    const int rc = sepaihrd_sir_eval_batch_device(ctx, ctx->d_theta, B, ctx->d_loglik, d_status, d_nacc, d_nrej,
+                                                  traj ? ctx->d_traj : nullptr, nullptr);
+    if (rc != SEPAIHRD_OK) return rc;
+    SIR_HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    SIR_HIP_TRY(hipMemcpy(loglik, ctx->d_loglik, nB * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (status) SIR_HIP_TRY(hipMemcpy(status, d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (n_accept) SIR_HIP_TRY(hipMemcpy(n_accept, d_nacc, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (n_reject) SIR_HIP_TRY(hipMemcpy(n_reject, d_nrej, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (traj) SIR_HIP_TRY(hipMemcpy(traj, ctx->d_traj, traj_elems * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    return SEPAIHRD_OK;
+}
+
+// SIRParameterManager::applyConstraints (SIRParameterManager.cpp:137-156)
+int sepaihrd_sir_apply_constraints(const sepaihrd_sir_ctx* ctx, const double* in, int B, double* out) {
+    if (!ctx || !in || !out || B < 0) return SEPAIHRD_E_INVALID_ARG;
+    for (int b = 0; b < B; ++b)
+        for (int p = 0; p < ctx->P; ++p) {
+            const double v = in[(size_t)b * ctx->P + p];
+            out[(size_t)b * ctx->P + p] = ctx->field[p] == SEPAIHRD_SIR_F_Q ? std::max(1e-12, v) : std::max(0.0, v);
+        }
+    return SEPAIHRD_OK;
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .problem import SEPAIHRDProblem
+from .problem import SEPAIHRDProblem, SIRProblem
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsepaihrd_hip.so")
@@ -51,6 +51,18 @@ class sepaihrd_kernel_info(C.Structure):
         ("max_blocks_per_cu", C.c_int32), ("num_cus", C.c_int32), ("likelihood_form", C.c_int32),
         ("phase_pass_applied", C.c_int32),
         ("kernel_name", C.c_char * 128), ("device_name", C.c_char * 128),
+    ]
+
+
+class sepaihrd_sir_problem(C.Structure):
+    """include/sepaihrd_hip.h: struct sepaihrd_sir_problem"""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("n_age", C.c_int32), ("n_times", C.c_int32), ("n_params", C.c_int32),
+        ("solver", C.c_int32), ("arith", C.c_int32), ("max_attempts", C.c_int32), ("reserved", C.c_int32),
+        ("times", _dp), ("N", _dp), ("C", _dp), ("gamma", _dp), ("initial_state", _dp), ("obs", _dp),
+        ("param_field", _ip), ("param_index", _ip),
+        ("q", C.c_double), ("scale_C_total", C.c_double),
+        ("abs_err", C.c_double), ("rel_err", C.c_double), ("dt_hint", C.c_double),
     ]
 
 
@@ -114,6 +126,8 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_mh_read_sample_values", "sepaihrd_mh_read_accept_trace",
     "sepaihrd_device_libm_check", "sepaihrd_mh_read_failure_counts", "sepaihrd_mh_snapshot_begin", "sepaihrd_mh_snapshot_end",
     "sepaihrd_device_log_values", "sepaihrd_chain_diagnostics", "sepaihrd_mh_diagnostics",
+    "sepaihrd_sir_create", "sepaihrd_sir_destroy", "sepaihrd_sir_last_error", "sepaihrd_sir_eval_batch", "sepaihrd_sir_eval_batch_device",
+    "sepaihrd_sir_reserve", "sepaihrd_sir_apply_constraints", "sepaihrd_sir_set_arith",
 )
 
 _lib = None
@@ -213,6 +227,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_scenario_ensemble.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sepaihrd_chain_diagnostics.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.sepaihrd_mh_diagnostics.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.sepaihrd_sir_create.restype = vp
+    lib.sepaihrd_sir_create.argtypes = [C.POINTER(sepaihrd_sir_problem), C.c_int, C.c_char_p, C.c_int]
+    lib.sepaihrd_sir_destroy.restype = None
+    lib.sepaihrd_sir_destroy.argtypes = [vp]
+    lib.sepaihrd_sir_last_error.restype = C.c_char_p
+    lib.sepaihrd_sir_last_error.argtypes = [vp]
+    lib.sepaihrd_sir_eval_batch.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.sepaihrd_sir_eval_batch_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_sir_reserve.argtypes = [vp, C.c_int]
+    lib.sepaihrd_sir_apply_constraints.argtypes = [vp, vp, C.c_int, vp]
+    lib.sepaihrd_sir_set_arith.argtypes = [vp, C.c_int]
     if path is None:
         _lib = lib
     return lib
@@ -461,3 +486,104 @@ class HipObjective:
         d["kernel_name"] = info.kernel_name.decode()
         d["device_name"] = info.device_name.decode()
         return d
+
+
+def build_sir_problem_struct(pb: SIRProblem, keep: list) -> sepaihrd_sir_problem:
+    """Fill the C struct of the age-structured SIR objective; ``keep`` receives the arrays that must outlive the call."""
+    s = sepaihrd_sir_problem()
+    s.abi_version = ABI_VERSION
+    s.n_age, s.n_times, s.n_params = pb.n, pb.n_times, pb.n_params
+    s.solver, s.arith, s.max_attempts, s.reserved = pb.solver, pb.arith, int(pb.max_attempts), 0
+
+    def dbl(x):
+        a = np.ascontiguousarray(x, dtype=np.float64)
+        keep.append(a)
+        return _ptr(a, _dp)
+
+    s.times, s.N, s.C, s.gamma = dbl(pb.times), dbl(pb.N), dbl(pb.C), dbl(pb.gamma)  # C row-major
+    s.initial_state, s.obs = dbl(pb.initial_state), dbl(pb.obs)
+    codes, idxs = pb.field_map()
+    keep.extend([codes, idxs])
+    s.param_field, s.param_index = _ptr(codes, _ip), _ptr(idxs, _ip)
+    s.q, s.scale_C_total = float(pb.q), float(pb.scale_C_total)
+    s.abs_err, s.rel_err, s.dt_hint = pb.abs_err, pb.rel_err, pb.dt_hint
+    return s
+
+
+class HipSIRObjective:
+    """Batched PoissonLikelihoodObjective of the age-structured SIR model on one MI355X.  A failed chain is -inf with its
+    status set (1 non-finite, 2 step failure, 3 step budget); nothing raises for a chain."""
+
+    def __init__(self, pb: SIRProblem, device: int = -1):
+        self.lib = load_library()
+        self.pb = pb
+        self._keep: list = []
+        st = build_sir_problem_struct(pb, self._keep)
+        err = C.create_string_buffer(512)
+        self.ctx = self.lib.sepaihrd_sir_create(C.byref(st), device, err, len(err))
+        if not self.ctx:
+            raise RuntimeError("sepaihrd_sir_create failed: " + err.value.decode())
+        self.P, self.n, self.T = pb.n_params, pb.n, pb.n_times
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            self.lib.sepaihrd_sir_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int, what: str):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): " + self.lib.sepaihrd_sir_last_error(self.ctx).decode())
+
+    def getParameterNames(self):
+        return list(self.pb.param_names)
+
+    def set_arith(self, arith: int):
+        self._check(self.lib.sepaihrd_sir_set_arith(self.ctx, int(arith)), "sepaihrd_sir_set_arith")
+
+    def reserve(self, max_B: int):
+        self._check(self.lib.sepaihrd_sir_reserve(self.ctx, int(max_B)), "sepaihrd_sir_reserve")
+
+    def calculate(self, theta) -> float:
+        return float(self.eval_batch(np.asarray(theta, dtype=np.float64)[None, :])["loglik"][0])
+
+    def eval_batch(self, theta, want_traj: bool = False) -> dict:
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError(f"theta must be B x {self.P}")
+        B = th.shape[0]
+        out = {"loglik": np.empty(B), "status": np.empty(B, dtype=np.int32),
+               "n_accept": np.empty(B, dtype=np.int32), "n_reject": np.empty(B, dtype=np.int32)}
+        traj = np.empty((B, self.T, 3 * self.n)) if want_traj else None
+        rc = self.lib.sepaihrd_sir_eval_batch(self.ctx, th.ctypes.data, B, out["loglik"].ctypes.data, out["status"].ctypes.data,
+                                              out["n_accept"].ctypes.data, out["n_reject"].ctypes.data,
+                                              traj.ctypes.data if want_traj else None)
+        self._check(rc, "sepaihrd_sir_eval_batch")
+        if want_traj:
+            out["traj"] = traj
+        return out
+
+    def eval_batch_device(self, d_theta, d_loglik, d_status=None, d_n_accept=None, d_n_reject=None, d_traj=None,
+                          stream: int = 0, B: Optional[int] = None):
+        """Arguments are torch CUDA tensors (or raw device addresses); async on ``stream``."""
+        def addr(t):
+            if t is None:
+                return None
+            return t if isinstance(t, int) else t.data_ptr()
+        if B is None:
+            B = int(d_theta.shape[0])
+        rc = self.lib.sepaihrd_sir_eval_batch_device(self.ctx, addr(d_theta), B, addr(d_loglik), addr(d_status), addr(d_n_accept),
+                                                     addr(d_n_reject), addr(d_traj), stream if stream else None)
+        self._check(rc, "sepaihrd_sir_eval_batch_device")
+
+    def apply_constraints(self, theta) -> np.ndarray:
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        out = np.empty_like(th)
+        self._check(self.lib.sepaihrd_sir_apply_constraints(self.ctx, th.ctypes.data, th.shape[0], out.ctypes.data),
+                    "sepaihrd_sir_apply_constraints")
+        return out.reshape(np.shape(theta))

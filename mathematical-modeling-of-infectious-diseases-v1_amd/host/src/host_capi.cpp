@@ -12,6 +12,7 @@
 #include "epidemic_hip/HipNUTSSampler.hpp"
 #include "epidemic_hip/HipPosteriorEnsemble.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
+#include "epidemic_hip/HipSIR.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_rng.inc"
 
@@ -955,3 +956,183 @@ extern "C" int host_model_holders(const double* ends_after, const double* values
         return 1;
     }
 }
+
+// ---- age-structured SIR: AgeSIRModel, HipSIRParameterManager, HipPoissonLikelihoodObjective (HipSIR.hpp) ----
+namespace {
+struct SirHandle {
+    std::shared_ptr<AgeSIRModel> model;
+    std::unique_ptr<HipSIRParameterManager> pm;
+    std::unique_ptr<SimulationCache> cache;
+    std::unique_ptr<HipPoissonLikelihoodObjective> obj;
+};
+std::shared_ptr<AgeSIRModel> sir_model(int n, const double* N, const double* C, const double* gamma, double q, double scale) {
+    Eigen::MatrixXd Cm(n, n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) Cm(i, j) = C[static_cast<size_t>(i) * n + j];  // row-major in
+    return AgeSIRModel::create(vec(N, n), Cm, vec(gamma, n), q, scale);
+}
+}  // namespace
+
+extern "C" {
+
+// AgeSIRModel::computeDerivatives on the host (no device); C row-major.  0 ok, 1 = exception (host_last_error)
+int host_sir_rhs(int n, const double* N, const double* C, const double* gamma, double q, double scale, const double* state, double* out) {
+    try {
+        auto m = sir_model(n, N, C, gamma, q, scale);
+        std::vector<double> x(state, state + 3 * n), dx(static_cast<size_t>(3 * n));
+        m->computeDerivatives(x, dx, 0.0);
+        std::copy(dx.begin(), dx.end(), out);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// names: '\n'-joined; sigma_names / sigma_values: n_sigmas explicit proposal sigmas (the rest take the defaults).
+// with_objective = 0 builds model and parameter manager only (no device needed).  NULL + host_last_error on failure.
+void* host_sir_create(const sepaihrd_sir_problem* pb, const char* names, const char* sigma_names, const double* sigma_values,
+                      int device, int cache_capacity, int with_objective) {
+    try {
+        const int n = pb->n_age;
+        auto h = std::make_unique<SirHandle>();
+        h->model = sir_model(n, pb->N, pb->C, pb->gamma, pb->q, pb->scale_C_total);
+        std::map<std::string, double> sg;
+        const std::vector<std::string> sn = split_lines(sigma_names);
+        for (size_t i = 0; i < sn.size(); ++i) sg[sn[i]] = sigma_values[i];
+        h->pm = std::make_unique<HipSIRParameterManager>(h->model, split_lines(names), sg);
+        h->cache = std::make_unique<SimulationCache>(static_cast<size_t>(cache_capacity > 0 ? cache_capacity : 1000));
+        if (!with_objective) return h.release();
+        Eigen::MatrixXd obs(pb->n_times, n);
+        for (int r = 0; r < pb->n_times; ++r)
+            for (int c = 0; c < n; ++c) obs(r, c) = pb->obs[static_cast<size_t>(r) * n + c];
+        h->obj = std::make_unique<HipPoissonLikelihoodObjective>(
+            h->model, *h->pm, *h->cache, obs, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 3 * n),
+            strategy_for(pb->solver), pb->dt_hint, pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA, pb->max_attempts);
+        return h.release();
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return nullptr;
+    }
+}
+
+void host_sir_destroy(void* hv) { delete static_cast<SirHandle*>(hv); }
+
+// sigma, lower and upper bound of every parameter; the manager's current parameters; 0 ok
+int host_sir_manager_info(void* hv, double* sigmas, double* lower, double* upper, double* current) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        const int P = static_cast<int>(h->pm->getParameterCount());
+        const Eigen::VectorXd cur = h->pm->getCurrentParameters();
+        for (int i = 0; i < P; ++i) {
+            sigmas[i] = h->pm->getSigmaForParamIndex(i);
+            lower[i] = h->pm->getLowerBoundForParamIndex(i);
+            upper[i] = h->pm->getUpperBoundForParamIndex(i);
+            current[i] = cur[i];
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+int host_sir_index_for_param(void* hv, const char* name) { return static_cast<SirHandle*>(hv)->pm->getIndexForParam(name); }
+
+int host_sir_apply_constraints(void* hv, const double* in, double* out) {
+    auto* h = static_cast<SirHandle*>(hv);
+    const int P = static_cast<int>(h->pm->getParameterCount());
+    const Eigen::VectorXd c = h->pm->applyConstraints(vec(in, P));
+    for (int i = 0; i < P; ++i) out[i] = c[i];
+    return 0;
+}
+
+// updateModelParameters(theta), then the model's q, scale_C_total and gamma[n]; 0 ok, 1 = exception
+int host_sir_update_model(void* hv, const double* theta, double* q, double* scale, double* gamma) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        h->pm->updateModelParameters(vec(theta, static_cast<int>(h->pm->getParameterCount())));
+        *q = h->model->getTransmissibility();
+        *scale = h->model->getContactScaleFactor();
+        for (int i = 0; i < h->model->getNumAgeClasses(); ++i) gamma[i] = h->model->getRecoveryRate()[i];
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+int host_sir_calculate(void* hv, const double* theta, double* value) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        *value = h->obj->calculate(vec(theta, static_cast<int>(h->pm->getParameterCount())));
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+int host_sir_calculate_batch(void* hv, const double* thetas, int B, double* out, int* status) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        h->obj->calculateBatch(thetas, B, out, status);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+void host_sir_cache_stats(void* hv, long* calls, long* hits, long* size) {
+    auto* h = static_cast<SirHandle*>(hv);
+    *calls = static_cast<long>(h->cache->getLikelihoodCalls());
+    *hits = static_cast<long>(h->cache->getLikelihoodHits());
+    *size = static_cast<long>(h->cache->size());
+}
+
+// BatchedHillClimbingOptimizer on the SIR objective, unchanged
+int host_sir_hc_run(void* hv, const double* x0, uint32_t seed, int threads, int iterations, int cloud_size_multiplier, double* best,
+                    double* best_value) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        const int P = static_cast<int>(h->pm->getParameterCount());
+        BatchedHillClimbingOptimizer hc;
+        hc.configure({{"iterations", double(iterations)}, {"cloud_size_multiplier", double(cloud_size_multiplier)},
+                      {"threads", double(threads)}, {"seed", double(seed)}});
+        const OptimizationResult r = hc.optimize(vec(x0, P), *h->obj, *h->pm);
+        for (int i = 0; i < P; ++i) best[i] = r.bestParameters[i];
+        *best_value = r.bestObjectiveValue;
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// MultiChainMetropolisHastings::optimizeChains (the lock-step branch over any IBatchObjectiveFunction), unchanged:
+// per chain best_value[C], best[C*P], accepted[C]
+int host_sir_mh_run(void* hv, int C, const double* initial, uint32_t seed, int iterations, int burn_in, double* best_value, double* best,
+                    int32_t* accepted) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        const int P = static_cast<int>(h->pm->getParameterCount());
+        MultiChainMetropolisHastings mh;
+        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0},
+                      {"burn_in", double(burn_in)}, {"store_samples", 0.0}});
+        mh.setSeed(seed);
+        const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
+        const std::vector<OptimizationResult> res = mh.optimizeChains(init, C, *h->obj, *h->pm);
+        for (int c = 0; c < C; ++c) {
+            best_value[c] = res[static_cast<size_t>(c)].bestObjectiveValue;
+            for (int i = 0; i < P; ++i) best[static_cast<size_t>(c) * P + i] = res[static_cast<size_t>(c)].bestParameters[i];
+            if (accepted) accepted[c] = static_cast<int32_t>(res[static_cast<size_t>(c)].additionalStats.at("accepted_count"));
+        }
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+}  // extern "C"

@@ -65,6 +65,20 @@ def load_library() -> C.CDLL:
     lib.host_set_mh_diagnostics.restype = None
     lib.host_mh_diagnostics.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     lib.host_chain_diagnostics.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.host_sir_rhs.argtypes = [C.c_int, vp, vp, vp, C.c_double, C.c_double, vp, vp]
+    lib.host_sir_create.restype = vp
+    lib.host_sir_create.argtypes = [C.POINTER(hipabi.sepaihrd_sir_problem), C.c_char_p, C.c_char_p, vp, C.c_int, C.c_int, C.c_int]
+    lib.host_sir_destroy.restype = None
+    lib.host_sir_destroy.argtypes = [vp]
+    lib.host_sir_manager_info.argtypes = [vp, vp, vp, vp, vp]
+    lib.host_sir_index_for_param.argtypes = [vp, C.c_char_p]
+    lib.host_sir_apply_constraints.argtypes = [vp, vp, vp]
+    lib.host_sir_update_model.argtypes = [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp]
+    lib.host_sir_calculate.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    lib.host_sir_calculate_batch.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.host_sir_cache_stats.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    lib.host_sir_hc_run.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)]
+    lib.host_sir_mh_run.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -517,3 +531,99 @@ def glibc_exp(x) -> np.ndarray:
     lib.host_glibc_exp.restype = None
     lib.host_glibc_exp(a.ctypes.data, a.size, out.ctypes.data)
     return out
+
+
+def sir_rhs(N, Cm, gamma, q, scale_C, state) -> np.ndarray:
+    """The host AgeSIRModel::computeDerivatives (C++; no device)."""
+    N, Cm, gamma, state = (np.ascontiguousarray(a, dtype=np.float64) for a in (N, Cm, gamma, state))
+    out = np.empty_like(state)
+    lib = load_library()
+    if lib.host_sir_rhs(len(N), N.ctypes.data, Cm.ctypes.data, gamma.ctypes.data, q, scale_C, state.ctypes.data, out.ctypes.data) != 0:
+        raise RuntimeError("host_sir_rhs: " + lib.host_last_error().decode())
+    return out
+
+
+class HostSIRObjective:
+    """AgeSIRModel + HipSIRParameterManager + SimulationCache + HipPoissonLikelihoodObjective (C++ objects).
+    ``param_names`` overrides the problem's (the manager's name errors are the C++ ones); ``with_objective=False`` builds
+    model and manager only and needs no device."""
+
+    def __init__(self, pb, device: int = -1, cache_capacity: int = 1000, with_objective: bool = True, param_names=None,
+                 sigmas: dict | None = None):
+        self.lib = load_library()
+        self.pb = pb
+        names = list(pb.param_names if param_names is None else param_names)
+        keep: list = []
+        st = hipabi.build_sir_problem_struct(pb, keep)
+        sg = dict(sigmas or {})
+        sv = np.array(list(sg.values()) + [0.0])
+        self.h = self.lib.host_sir_create(C.byref(st), "\n".join(names).encode(), "\n".join(sg.keys()).encode(), sv.ctypes.data,
+                                          device, cache_capacity, int(with_objective))
+        if not self.h:
+            raise RuntimeError("host_sir_create failed: " + self.lib.host_last_error().decode())
+        self.P, self.n = len(names), pb.n
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.lib.host_sir_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def manager_info(self) -> dict:
+        out = [np.empty(self.P) for _ in range(4)]
+        if self.lib.host_sir_manager_info(self.h, *[a.ctypes.data for a in out]) != 0:
+            raise RuntimeError("host_sir_manager_info: " + self.lib.host_last_error().decode())
+        return dict(zip(("sigma", "lower", "upper", "current"), out))
+
+    def index_for_param(self, name: str) -> int:
+        return int(self.lib.host_sir_index_for_param(self.h, name.encode()))
+
+    def apply_constraints(self, theta) -> np.ndarray:
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        out = np.empty(self.P)
+        self.lib.host_sir_apply_constraints(self.h, th.ctypes.data, out.ctypes.data)
+        return out
+
+    def update_model(self, theta) -> dict:
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        q, sc, g = C.c_double(0.0), C.c_double(0.0), np.empty(self.n)
+        if self.lib.host_sir_update_model(self.h, th.ctypes.data, C.byref(q), C.byref(sc), g.ctypes.data) != 0:
+            raise RuntimeError("host_sir_update_model: " + self.lib.host_last_error().decode())
+        return {"q": q.value, "scale_C_total": sc.value, "gamma": g}
+
+    def calculate(self, theta) -> float:
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        v = C.c_double(0.0)
+        if self.lib.host_sir_calculate(self.h, th.ctypes.data, C.byref(v)) != 0:
+            raise RuntimeError("host_sir_calculate: " + self.lib.host_last_error().decode())
+        return v.value
+
+    def calculate_batch(self, thetas):
+        th = np.ascontiguousarray(thetas, dtype=np.float64)
+        out, st = np.empty(len(th)), np.empty(len(th), dtype=np.int32)
+        if self.lib.host_sir_calculate_batch(self.h, th.ctypes.data, len(th), out.ctypes.data, st.ctypes.data) != 0:
+            raise RuntimeError("host_sir_calculate_batch: " + self.lib.host_last_error().decode())
+        return out, st
+
+    def cache_stats(self) -> dict:
+        a, b, c = C.c_long(0), C.c_long(0), C.c_long(0)
+        self.lib.host_sir_cache_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return {"calls": a.value, "hits": b.value, "size": c.value}
+
+    def hill_climbing(self, x0, seed: int, iterations: int, cloud_size_multiplier: int = 8, threads: int = 16) -> dict:
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        best, bv = np.empty(self.P), C.c_double(0.0)
+        if self.lib.host_sir_hc_run(self.h, x0.ctypes.data, seed, threads, iterations, cloud_size_multiplier, best.ctypes.data, C.byref(bv)) != 0:
+            raise RuntimeError("host_sir_hc_run: " + self.lib.host_last_error().decode())
+        return {"best": best, "best_value": bv.value}
+
+    def metropolis_hastings(self, initial, seed: int, iterations: int, burn_in: int = 0) -> dict:
+        init = np.ascontiguousarray(initial, dtype=np.float64)
+        chains = init.shape[0]
+        bv, best, acc = np.empty(chains), np.empty((chains, self.P)), np.empty(chains, dtype=np.int32)
+        if self.lib.host_sir_mh_run(self.h, chains, init.ctypes.data, seed, iterations, burn_in, bv.ctypes.data, best.ctypes.data,
+                                    acc.ctypes.data) != 0:
+            raise RuntimeError("host_sir_mh_run: " + self.lib.host_last_error().decode())
+        return {"best_value": bv, "best": best, "accepted": acc}

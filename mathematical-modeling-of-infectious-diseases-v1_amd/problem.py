@@ -312,3 +312,111 @@ def restrict_age_classes(pb: SEPAIHRDProblem, keep: Sequence[int]) -> SEPAIHRDPr
                     d_community=pb.d_community[sel], initial_state=init, obs_H=pb.obs_H[:, sel],
                     obs_ICU=pb.obs_ICU[:, sel], obs_D=pb.obs_D[:, sel], param_names=names, sigmas=sig, bounds=bnd,
                     base_theta=np.array(base) if base else None)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Age-structured SIR model (include/sepaihrd_hip.h: sepaihrd_sir_problem)
+# ---------------------------------------------------------------------------------------------------------------
+SIR_F_Q, SIR_F_SCALE_C_TOTAL, SIR_F_GAMMA = 0, 1, 2
+
+
+def resolve_sir_param_name(name: str, n_age: int) -> Tuple[int, int]:
+    """(field code, age index) of a calibrated parameter name, with the errors of the reference's manager
+    (SIRParameterManager.cpp:26-52): unknown name, unparsable or out-of-range ``gamma_<i>``."""
+    if name == "q":
+        return SIR_F_Q, 0
+    if name == "scale_C_total":
+        return SIR_F_SCALE_C_TOTAL, 0
+    if name.startswith("gamma_"):
+        try:
+            idx = int(name[6:])
+        except ValueError:
+            raise ValueError(f"Could not parse age index from parameter name '{name}': Invalid argument")
+        if idx < 0 or idx >= n_age:
+            raise ValueError(f"Invalid age index in parameter name '{name}'. Max index: {n_age - 1}")
+        return SIR_F_GAMMA, idx
+    raise ValueError(f"Parameter name '{name}' not recognized for AgeSIRModel calibration.")
+
+
+@dataclass
+class SIRProblem:
+    """One PoissonLikelihoodObjective of the age-structured SIR model: the model's values, the fixed initial state
+    [S(n), I(n), R(n)], the output times, the observed incidence [T][n] and the names of the calibrated parameters."""
+    N: np.ndarray
+    C: np.ndarray            # [n][n] baseline contact matrix
+    gamma: np.ndarray
+    q: float
+    scale_C_total: float
+    initial_state: np.ndarray
+    times: np.ndarray
+    obs: np.ndarray          # [T][n]
+    param_names: List[str]
+    solver: int = SOLVER_DOPRI5
+    arith: int = ARITH_STRICT
+    abs_err: float = 1e-6
+    rel_err: float = 1e-6
+    dt_hint: float = 1.0
+    max_attempts: int = 0
+
+    def __post_init__(self):
+        self.N = _arr(self.N)
+        n = len(self.N)
+        self.C = _arr(self.C).reshape(n, n)
+        self.gamma = _arr(self.gamma)
+        self.initial_state = _arr(self.initial_state)
+        self.times = _arr(self.times)
+        self.obs = _arr(self.obs).reshape(len(self.times), n) if np.size(self.obs) == len(self.times) * n else _arr(self.obs)
+        self.param_names = list(self.param_names)
+        if not self.param_names:
+            raise ValueError("Parameter names list cannot be empty.")
+        if self.gamma.shape != (n,) or self.initial_state.shape != (3 * n,):
+            raise ValueError("gamma must have n entries and initial_state 3 n")
+        if self.obs.ndim != 2 or self.obs.shape != (len(self.times), n):
+            raise ValueError(f"Time points size ({len(self.times)}) does not match observed data rows ({self.obs.shape[0] if self.obs.ndim == 2 else self.obs.size})")
+        self.field_map()  # name errors surface at construction, as in the reference's manager
+
+    @property
+    def n(self) -> int:
+        return len(self.N)
+
+    @property
+    def n_times(self) -> int:
+        return len(self.times)
+
+    @property
+    def n_params(self) -> int:
+        return len(self.param_names)
+
+    def field_map(self) -> Tuple[np.ndarray, np.ndarray]:
+        pairs = [resolve_sir_param_name(nm, self.n) for nm in self.param_names]
+        return (np.array([p[0] for p in pairs], dtype=np.int32), np.array([p[1] for p in pairs], dtype=np.int32))
+
+    def current_parameters(self) -> np.ndarray:
+        """SIRParameterManager::getCurrentParameters: the model's value of every calibrated name."""
+        codes, idx = self.field_map()
+        return np.array([self.q if c == SIR_F_Q else self.scale_C_total if c == SIR_F_SCALE_C_TOTAL else self.gamma[i]
+                         for c, i in zip(codes, idx)])
+
+    def apply_constraints(self, theta) -> np.ndarray:
+        """SIRParameterManager::applyConstraints (:137-156)."""
+        th = np.array(theta, dtype=np.float64)
+        codes, _ = self.field_map()
+        floor = np.where(codes == SIR_F_Q, 1e-12, 0.0)
+        return np.where(floor < th, th, floor)  # std::max(floor, x)
+
+    def model_values(self, theta) -> dict:
+        """q, scale_C_total and gamma of the model after updateModelParameters(theta)."""
+        c = self.apply_constraints(theta)
+        codes, idx = self.field_map()
+        q, scale, gamma = float(self.q), float(self.scale_C_total), self.gamma.copy()
+        for v, code, i in zip(c, codes, idx):
+            if code == SIR_F_Q:
+                q = float(v)
+            elif code == SIR_F_SCALE_C_TOTAL:
+                scale = float(v)
+            else:
+                gamma[i] = v
+        return {"q": q, "scale_C_total": scale, "gamma": gamma}
+
+    def with_(self, **kw) -> "SIRProblem":
+        return replace(self, **kw)

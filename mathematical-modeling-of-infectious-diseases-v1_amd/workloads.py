@@ -56,3 +56,38 @@ def build(name: str, golden_dir: str, hip_factory=None) -> SEPAIHRDProblem:
             raise ValueError("workload c5 needs a device to draw its synthetic observations")
         return with_synthetic_observations(wide, hip_factory)
     raise ValueError(f"unknown workload {name}")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Age-structured SIR: BASELINE configs[0]'s problem with synthetic observations
+# ---------------------------------------------------------------------------------------------------------------
+SIR_TRUE_THETA = (0.03, 1.0, 0.2, 0.2, 0.15)  # q, scale_C_total, gamma_0..2
+SIR_ALL_NAMES = ("q", "scale_C_total", "gamma_0", "gamma_1", "gamma_2")
+
+
+def sir_incidence(pb, traj, values=None) -> np.ndarray:
+    """SimulationResultProcessor::getIncidenceData on a trajectory [T][3n]: max(q ((C scale) (I / N)), 0) * S."""
+    v = values or {"q": pb.q, "scale_C_total": pb.scale_C_total}
+    n = pb.n
+    ion = np.where(pb.N > 1e-9, traj[:, n:2 * n] / np.where(pb.N > 1e-9, pb.N, 1.0), 0.0)
+    lam = np.maximum(v["q"] * (ion @ (pb.C * v["scale_C_total"]).T), 0.0)
+    return lam * traj[:, :n]
+
+
+def sir_config0(simulate, param_names=SIR_ALL_NAMES, seed: int = 20240229, **kw):
+    """configs[0]'s three-age SIR problem (N, C, gamma, q = 0.03, I0 = 10 / 20 / 5, days 0..200) with observations drawn
+    once, with a fixed seed, as Poisson counts of the true incidence.  ``simulate(N, C, gamma, q, scale, init, times)``
+    returns {"traj": [T][3n]} of the true parameters (the tests pass the CPU oracle's sir_simulate; tools pass a device
+    evaluation): the package itself holds no integrator."""
+    from .problem import SIRProblem
+    N = np.array([5.0e5, 1.2e6, 3.0e5])
+    Cm = np.array([[8.0, 3.0, 1.0], [3.0, 6.0, 2.0], [1.0, 2.0, 3.0]])
+    gamma = np.array([0.2, 0.2, 0.15])
+    I0 = np.array([10.0, 20.0, 5.0])
+    init = np.concatenate([N - I0, I0, np.zeros(3)])
+    times = np.arange(0.0, 201.0)
+    pb = SIRProblem(N=N, C=Cm, gamma=gamma, q=0.03, scale_C_total=1.0, initial_state=init, times=times,
+                    obs=np.zeros((len(times), 3)), param_names=list(param_names), **kw)
+    traj = np.asarray(simulate(N, Cm, gamma, 0.03, 1.0, init, times)["traj"]).reshape(len(times), 9)
+    rng = np.random.default_rng(seed)
+    return pb.with_(obs=rng.poisson(sir_incidence(pb, traj)).astype(np.float64))

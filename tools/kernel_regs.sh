@@ -1,11 +1,12 @@
 #!/bin/bash
 # Register / spill / scratch figures of the evaluation kernels from a device-only compile (no GPU needed).
 #   tools/kernel_regs.sh fma|strict [extra -D flags...]      prints one line per kernel whose name matches $PATTERN (default: eval)
+#   SRC=sepaihrd_sir.hip tools/kernel_regs.sh strict          another translation unit of csrc/ (default: sepaihrd_kernels.hip)
 A=${1:-fma}; shift
 C=mathematical-modeling-of-infectious-diseases-v1_amd/csrc
 F="-ffp-contract=fast -DSEPAIHRD_ARITH_FMA=1"; [ "$A" = strict ] && F="-ffp-contract=off -DSEPAIHRD_ARITH_FMA=0"
 OUT=${OUT:-/tmp/kernel_regs_$A.s}
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Iinclude -I$C -Wno-unused-function $F "$@" --cuda-device-only -S $C/sepaihrd_kernels.hip -o $OUT || exit 1
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++20 -fPIC -Iinclude -I$C -Wno-unused-function $F "$@" --cuda-device-only -S $C/${SRC:-sepaihrd_kernels.hip} -o $OUT || exit 1
 python3 - "$OUT" "${PATTERN:-eval}" <<'PY'
 import re, sys
 txt = open(sys.argv[1]).read()
