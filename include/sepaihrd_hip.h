@@ -634,6 +634,39 @@ int sepaihrd_sir_reserve(sepaihrd_sir_ctx *ctx, int max_B);
 int sepaihrd_sir_apply_constraints(const sepaihrd_sir_ctx *ctx, const double *in, int B, double *out);
 int sepaihrd_sir_set_arith(sepaihrd_sir_ctx *ctx, int arith);
 
+/* ---- the device-resident Adaptive-Metropolis sampler on the SIR objective ----
+ * sepaihrd_sir_mh_create returns the SAME opaque sepaihrd_mh as sepaihrd_mh_create: every sepaihrd_mh_* entry point above
+ * works on it unchanged (propose / commit / adapt, step, step_tested, seed_streams, keep_scale_on_device, draw_first, the
+ * read_* calls, summary_records, snapshot_begin / _end, read_failure_counts, mh_diagnostics, busy).  The errors of such a
+ * sampler are read with sepaihrd_sir_last_error(ctx).  Proposals go through SIRParameterManager::applyConstraints
+ * (max(1e-12, q), max(0, scale_C_total), max(0, gamma_i)): the kernels' clamp mode with lower = 1e-12 / 0 and upper = +inf
+ * (sepaihrd_sir_constraint_bounds), equal to sepaihrd_sir_apply_constraints bit for bit on finite input.  A failed evaluation (-INFINITY with status 1 / 2 / 3) enters
+ * the accept test by the rule of every sampler here: status >= 2, NaN or +-inf count as -1e18.  The context must outlive the
+ * sampler.  NULL ctx: NULL, no device touched.
+ * sepaihrd_sir_device_libm_check is sepaihrd_device_libm_check for a SIR context (same self-check, same
+ * SEPAIHRD_LIBM_SELFCHECK=fail hook). */
+sepaihrd_mh *sepaihrd_sir_mh_create(sepaihrd_sir_ctx *ctx, const sepaihrd_mh_config *config, const double *x0, const double *cov0);
+int sepaihrd_sir_device_libm_check(sepaihrd_sir_ctx *ctx, int32_t *n_log_diff, int32_t *n_exp_diff);
+/* The table such a sampler clamps its proposals with, for param_field[n_params] (SEPAIHRD_SIR_F_*): lower = 1e-12 for q and
+ * 0 otherwise, upper = +inf; has_bounds (NULL: not wanted) = 1 for q -- clamp(v, lower, upper) -- and 0 otherwise -- the
+ * kernels' unbounded clamp (0 < v) ? v : 0, which is std::max(0.0, v) with the sign of a zero.  Host only, no device and
+ * no context needed. */
+int sepaihrd_sir_constraint_bounds(const int32_t *param_field, int n_params, double *lower, double *upper, int32_t *has_bounds);
+
+/* Which form of the per-iteration sampler kernels (the draws; L z ahead of the test; test + commit + proposal; their unfused
+ * siblings) a sampler launches.  BLOCK_PER_CHAIN gives every chain a workgroup of one or two wavefronts (shaped for P = 62); PACKED
+ * gives a chain a group of pow2(P) adjacent lanes, 64 / pow2(P) chains per wavefront (P <= 64 only: SEPAIHRD_E_UNSUPPORTED
+ * beyond).  The two forms give the same bits: states, proposals, accept flags, scales, stored samples and values.  AUTO is
+ * BLOCK_PER_CHAIN on a sampler made by sepaihrd_mh_create whatever P is; on a sepaihrd_sir_mh_create sampler it is whichever
+ * form was measured faster for its (P, chains).  May be called between any two iterations.
+ * NULL sampler or an unknown code: SEPAIHRD_E_INVALID_ARG, no device touched. */
+#define SEPAIHRD_MH_FORM_AUTO 0
+#define SEPAIHRD_MH_FORM_BLOCK_PER_CHAIN 1
+#define SEPAIHRD_MH_FORM_PACKED 2
+int sepaihrd_mh_set_kernel_form(sepaihrd_mh *mh, int form);
+/* the form in use (AUTO resolved): SEPAIHRD_MH_FORM_BLOCK_PER_CHAIN or _PACKED; NULL: SEPAIHRD_E_INVALID_ARG */
+int sepaihrd_mh_get_kernel_form(const sepaihrd_mh *mh);
+
 #ifdef __cplusplus
 }
 #endif

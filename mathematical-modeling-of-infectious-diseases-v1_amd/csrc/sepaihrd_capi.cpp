@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_mh_backend.h"
 
 using namespace sepaihrd;
 
@@ -1106,7 +1107,12 @@ int sepaihrd_get_kernel_info(sepaihrd_ctx* ctx, sepaihrd_kernel_info* info) {
 
 // ------------------------------------------------------------------ device-resident Adaptive Metropolis
 struct sepaihrd_mh {
-    sepaihrd_ctx* ctx = nullptr;
+    explicit sepaihrd_mh(const MhBackend& b) : be(b) {}
+    // the context this sampler evaluates on, as far as a sampler needs it (csrc/sepaihrd_mh_backend.h)
+    MhBackend be;
+    MhBackend* const ctx = &be;
+    int form_asked = SEPAIHRD_MH_FORM_AUTO;  // sepaihrd_mh_set_kernel_form
+    bool packed = false;                     // ... resolved: the per-iteration kernels run in the packed form
     SamplerState st{};
     int rows = 0;  // history rows written so far
     hipStream_t stream = nullptr;  // own non-blocking stream: several samplers (one per host thread) overlap
@@ -1115,6 +1121,7 @@ struct sepaihrd_mh {
     double* d_loglik = nullptr;
     int32_t* d_status = nullptr;
     uint8_t* d_accept = nullptr;
+    uint8_t* d_draw_todo = nullptr;  // [C] chains the windowed draw of the packed form left to the block-per-chain kernel
     int32_t* d_rows = nullptr;
     double* d_gather = nullptr;
     size_t gather_cap = 0;
@@ -1254,7 +1261,7 @@ int mh_adapt_step(sepaihrd_mh* mh, double gamma, int adapt) {
 
 // log-likelihoods (and statuses) of the last evaluation: one copy into the page-locked mirror, the wait, two memcpy
 int mh_fetch_values(sepaihrd_mh* mh, double* loglik, int32_t* status) {
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     const size_t C = (size_t)mh->st.C;
     const size_t bytes = C * sizeof(double) + (status ? C * sizeof(int32_t) : 0);
     HIP_TRY(hipMemcpyAsync(mh->h_fetch, mh->d_loglik, bytes, hipMemcpyDeviceToHost, mh->stream), ctx, return SEPAIHRD_E_HIP);
@@ -1264,17 +1271,59 @@ int mh_fetch_values(sepaihrd_mh* mh, double* loglik, int32_t* status) {
     return SEPAIHRD_OK;
 }
 
+// the objective of every chain at d_theta, queued on the sampler's stream: values and statuses land in d_loglik / d_status
+int mh_eval_device(sepaihrd_mh* mh, const double* d_theta) {
+    MhBackend* ctx = mh->ctx;
+    if (ctx->sep)
+        return sepaihrd_eval_batch_device(ctx->sep, d_theta, mh->st.C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, nullptr, mh->stream);
+    return sepaihrd_sir_eval_batch_device(ctx->sir, d_theta, mh->st.C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, mh->stream);
+}
 int mh_eval(sepaihrd_mh* mh, const double* d_theta, double* loglik, int32_t* status) {
-    sepaihrd_ctx* ctx = mh->ctx;
-    const int C = mh->st.C;
-    const int rc = sepaihrd_eval_batch_device(ctx, d_theta, C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, nullptr, mh->stream);
+    const int rc = mh_eval_device(mh, d_theta);
     if (rc != SEPAIHRD_OK) return rc;
     return mh_fetch_values(mh, loglik, status);
 }
+
+// The form of the per-iteration kernels.  AUTO on a SEPAIHRD-backed sampler is block-per-chain whatever P is.  On a
+// SIR-backed sampler it is the packed form where that measured faster by more than the alternating runs' own spread
+// (tools/bench_sir_mh.py): P = 5 (groups of 8 lanes) and P = 18 (groups of 32), at 4096 and at
+// 65 536 chains -- 1.2 % to 33 % per iteration against spreads of 0.02 - 0.9 %.  Both chain counts won, so the rule does not
+// look at C; it covers the group widths up to the widest one measured.  A group of 64 lanes (P > 32: one chain per
+// wavefront, the mapping the block-per-chain kernels already have) was not measured and stays block-per-chain.
+bool mh_auto_packed(const MhBackend* ctx, int P, int C) {
+    (void)C;
+    return ctx->sir != nullptr && mh_packed_group(P) <= 32;
+}
+void mh_resolve_form(sepaihrd_mh* mh) {
+    mh->packed = mh->form_asked == SEPAIHRD_MH_FORM_PACKED ||
+                 (mh->form_asked == SEPAIHRD_MH_FORM_AUTO && mh_auto_packed(mh->ctx, mh->st.P, mh->st.C));
+}
+// the four launches that have two forms
+int mh_launch_propose(sepaihrd_mh* mh, const double* d_z, const double* d_scale, hipStream_t st) {
+    return mh->packed ? sampler_propose_packed(mh->st, mh_bounds_of(mh->ctx->dp), d_z, d_scale, st)
+                      : sampler_propose(mh->st, mh->ctx->dp, d_z, d_scale, st);
+}
+int mh_launch_propose_select(sepaihrd_mh* mh, const double* d_z_uniform, const double* d_z_plain, const uint8_t* d_flags,
+                             const double* d_scale, hipStream_t st) {
+    return mh->packed ? sampler_propose_select_packed(mh->st, mh_bounds_of(mh->ctx->dp), d_z_uniform, d_z_plain, d_flags, d_scale, st)
+                      : sampler_propose_select(mh->st, mh->ctx->dp, d_z_uniform, d_z_plain, d_flags, d_scale, st);
+}
+int mh_launch_draw(sepaihrd_mh* mh, const uint8_t* d_flags, int first, double* d_log_u, double* d_z_uniform, double* d_z_plain,
+                   int want_normals, hipStream_t st) {
+    return mh->packed ? sampler_draw_packed(mh->st, d_flags, first, d_log_u, d_z_uniform, d_z_plain, want_normals, mh->d_draw_todo, st)
+                      : sampler_draw(mh->st, d_flags, first, d_log_u, d_z_uniform, d_z_plain, want_normals, st);
+}
+int mh_launch_lz(sepaihrd_mh* mh, const double* d_z_uniform, const double* d_z_plain, double* d_lz_uniform, double* d_lz_plain, hipStream_t st) {
+    return mh->packed ? sampler_lz_packed(mh->st, d_z_uniform, d_z_plain, d_lz_uniform, d_lz_plain, st)
+                      : sampler_lz(mh->st, d_z_uniform, d_z_plain, d_lz_uniform, d_lz_plain, st);
+}
 }  // namespace
 
-sepaihrd_mh* sepaihrd_mh_create(sepaihrd_ctx* ctx, const sepaihrd_mh_config* cfg, const double* x0, const double* cov0) {
-    if (!ctx) return nullptr;
+}  // extern "C"
+
+// sepaihrd_mh_create / sepaihrd_sir_mh_create: the sampler's state on the device of the context `be` names
+sepaihrd_mh* sepaihrd::mh_create_on(const MhBackend& be, const sepaihrd_mh_config* cfg, const double* x0, const double* cov0) {
+    const MhBackend* const ctx = &be;
     const int P = ctx->P;
     if (!cfg || cfg->chains <= 0 || cfg->iterations <= 0 || !x0 || !cov0 || P > 200 ||
         (cfg->covariance_mode != SEPAIHRD_MH_COV_RUNNING && cfg->covariance_mode != SEPAIHRD_MH_COV_TWO_PASS)) {
@@ -1307,8 +1356,7 @@ sepaihrd_mh* sepaihrd_mh_create(sepaihrd_ctx* ctx, const sepaihrd_mh_config* cfg
             return nullptr;
         }
     }
-    auto* mh = new sepaihrd_mh();
-    mh->ctx = ctx;
+    auto* mh = new sepaihrd_mh(be);
     SamplerState& st = mh->st;
     st.C = C; st.P = P; st.window = window; st.thinning = std::max(thinning, 1); st.n_store = n_store;
     st.scaling = scaling_factor; st.reg_eps = reg_eps;
@@ -1342,6 +1390,7 @@ sepaihrd_mh* sepaihrd_mh_create(sepaihrd_ctx* ctx, const sepaihrd_mh_config* cfg
     dalloc((void**)&mh->d_loglik, (size_t)C * (sizeof(double) + sizeof(int32_t)));
     mh->d_status = mh->d_loglik ? reinterpret_cast<int32_t*>(mh->d_loglik + C) : nullptr;
     dalloc((void**)&mh->d_accept, (size_t)C);
+    dalloc((void**)&mh->d_draw_todo, (size_t)C);
     dalloc((void**)&mh->d_z_stage, CP * sizeof(double));
     dalloc((void**)&mh->d_lz, 2 * CP * sizeof(double));
     dalloc((void**)&mh->d_lp, (size_t)C * sizeof(double));
@@ -1363,7 +1412,7 @@ sepaihrd_mh* sepaihrd_mh_create(sepaihrd_ctx* ctx, const sepaihrd_mh_config* cfg
         for (int b = 0; b < 2; ++b)
             if (ok && hipHostMalloc((void**)&mh->h_stage[b], CP * sizeof(double), hipHostMallocDefault) != hipSuccess) { mh->h_stage[b] = nullptr; ok = false; }
     }
-    if (ok && sepaihrd_reserve(ctx, C) != SEPAIHRD_OK) ok = false;
+    if (ok && (ctx->sep ? sepaihrd_reserve(ctx->sep, C) : sepaihrd_sir_reserve(ctx->sir, C)) != SEPAIHRD_OK) ok = false;
     if (ok && hipStreamCreateWithFlags(&mh->stream, hipStreamNonBlocking) != hipSuccess) ok = false;
     if (ok && hipStreamCreateWithFlags(&mh->copy_stream, hipStreamNonBlocking) != hipSuccess) ok = false;
     if (ok && hipEventCreateWithFlags(&mh->ev_staged, hipEventDisableTiming) != hipSuccess) ok = false;
@@ -1402,8 +1451,34 @@ sepaihrd_mh* sepaihrd_mh_create(sepaihrd_ctx* ctx, const sepaihrd_mh_config* cfg
         return nullptr;
     }
     mh->rows = 1;
-    ctx->lazy_stream = mh->stream;
+    mh_resolve_form(mh);
+    if (ctx->sep) ctx->sep->lazy_stream = mh->stream;
     return mh;
+}
+
+extern "C" {
+
+sepaihrd_mh* sepaihrd_mh_create(sepaihrd_ctx* ctx, const sepaihrd_mh_config* cfg, const double* x0, const double* cov0) {
+    if (!ctx) return nullptr;
+    return mh_create_on(MhBackend{ctx->device, ctx->P, ctx->last_error, ctx->dp, ctx->libm_log_diff, ctx->libm_exp_diff, ctx->pending_B, ctx, nullptr},
+                        cfg, x0, cov0);
+}
+
+int sepaihrd_mh_set_kernel_form(sepaihrd_mh* mh, int form) {
+    if (!mh || (form != SEPAIHRD_MH_FORM_AUTO && form != SEPAIHRD_MH_FORM_BLOCK_PER_CHAIN && form != SEPAIHRD_MH_FORM_PACKED))
+        return SEPAIHRD_E_INVALID_ARG;
+    if (form == SEPAIHRD_MH_FORM_PACKED && mh->st.P > MH_PACKED_MAX_P) {
+        mh->ctx->last_error = "mh_set_kernel_form: the packed form holds a chain in one wavefront (at most 64 parameters)";
+        return SEPAIHRD_E_UNSUPPORTED;
+    }
+    mh->form_asked = form;
+    mh_resolve_form(mh);
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_mh_get_kernel_form(const sepaihrd_mh* mh) {
+    if (!mh) return SEPAIHRD_E_INVALID_ARG;
+    return mh->packed ? SEPAIHRD_MH_FORM_PACKED : SEPAIHRD_MH_FORM_BLOCK_PER_CHAIN;
 }
 
 void sepaihrd_mh_destroy(sepaihrd_mh* mh) {
@@ -1412,9 +1487,10 @@ void sepaihrd_mh_destroy(sepaihrd_mh* mh) {
     if (mh->copy_stream) { (void)hipStreamSynchronize(mh->copy_stream); (void)hipStreamDestroy(mh->copy_stream); }
     if (mh->stream) {
         (void)hipStreamSynchronize(mh->stream);
-        sepaihrd_ctx* ctx = mh->ctx;
-        if (ctx->lazy_stream == mh->stream) ctx->lazy_stream = nullptr;
-        if (ctx->busy_stream == mh->stream) { ctx->busy_valid = false; ctx->busy_stream = nullptr; }  // all of it is done
+        if (sepaihrd_ctx* ctx = mh->ctx->sep) {
+            if (ctx->lazy_stream == mh->stream) ctx->lazy_stream = nullptr;
+            if (ctx->busy_stream == mh->stream) { ctx->busy_valid = false; ctx->busy_stream = nullptr; }  // all of it is done
+        }
         (void)hipStreamDestroy(mh->stream);
     }
     if (mh->ev_staged) (void)hipEventDestroy(mh->ev_staged);
@@ -1448,19 +1524,18 @@ int sepaihrd_mh_evaluate_current(sepaihrd_mh* mh, double* loglik, int32_t* statu
 
 int sepaihrd_mh_propose(sepaihrd_mh* mh, const double* z, const double* scale, double* loglik, int32_t* status) {
     if (!mh || !z || !scale) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     const size_t CP = (size_t)mh->st.C * mh->st.P;
     HIP_TRY(hipMemcpyAsync(mh->d_z, z, CP * sizeof(double), hipMemcpyHostToDevice, mh->stream), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpyAsync(mh->d_scale, scale, (size_t)mh->st.C * sizeof(double), hipMemcpyHostToDevice, mh->stream), ctx,
             return SEPAIHRD_E_HIP);
-    if (sampler_propose(mh->st, ctx->dp, mh->d_z, mh->d_scale, mh->stream) != 0) {
+    if (mh_launch_propose(mh, mh->d_z, mh->d_scale, mh->stream) != 0) {
         ctx->last_error = "mh_propose: launch failed";
         return SEPAIHRD_E_HIP;
     }
     if (!loglik)  // launch only: the caller overlaps host work and calls sepaihrd_mh_fetch
-        return sepaihrd_eval_batch_device(ctx, mh->st.prop, mh->st.C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, nullptr,
-                                          mh->stream);
+        return mh_eval_device(mh, mh->st.prop);
     return mh_eval(mh, mh->st.prop, loglik, status);
 }
 
@@ -1469,7 +1544,7 @@ double* sepaihrd_mh_staging_buffer(sepaihrd_mh* mh) { return mh ? mh->h_stage[mh
 int sepaihrd_mh_stage_normals(sepaihrd_mh* mh, const double* z) {
     if (!mh || !z) return SEPAIHRD_E_INVALID_ARG;
     if (z == mh->h_stage[mh->stage_turn]) mh->stage_turn ^= 1;  // page-locked source: a real DMA; the next fill goes to the other buffer
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     const size_t CP = (size_t)mh->st.C * mh->st.P;
     HIP_TRY(hipMemcpyAsync(mh->d_z_stage, z, CP * sizeof(double), hipMemcpyHostToDevice, mh->copy_stream), ctx, return SEPAIHRD_E_HIP);
@@ -1481,7 +1556,7 @@ int sepaihrd_mh_stage_normals(sepaihrd_mh* mh, const double* z) {
 int sepaihrd_mh_step(sepaihrd_mh* mh, const uint8_t* accept, const double* scale, const int32_t* patch_chain, const double* patch_z,
                      int n_patch, double gamma, int adapt) {
     if (!mh || !scale || n_patch < 0 || (n_patch > 0 && (!patch_chain || !patch_z)) || adapt < 0 || adapt > 3) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     const int C = mh->st.C, P = mh->st.P;
     if (!mh->staged) { ctx->last_error = "mh_step: no staged normals (call sepaihrd_mh_stage_normals first)"; return SEPAIHRD_E_INVALID_ARG; }
     if (n_patch > C) { ctx->last_error = "mh_step: more patched rows than chains"; return SEPAIHRD_E_INVALID_ARG; }
@@ -1513,23 +1588,23 @@ int sepaihrd_mh_step(sepaihrd_mh* mh, const uint8_t* accept, const double* scale
     HIP_TRY(hipStreamWaitEvent(st, mh->ev_staged, 0), ctx, return SEPAIHRD_E_HIP);  // the staged normals have landed
     rc = sampler_patch_normals(mh->d_z_stage, reinterpret_cast<const int32_t*>(mh->d_pack + mh->off_chain),
                                reinterpret_cast<const double*>(mh->d_pack + mh->off_rows), n_patch, P, st);
-    if (rc == 0) rc = sampler_propose(mh->st, ctx->dp, mh->d_z_stage, reinterpret_cast<const double*>(mh->d_pack + mh->off_scale), st);
+    if (rc == 0) rc = mh_launch_propose(mh, mh->d_z_stage, reinterpret_cast<const double*>(mh->d_pack + mh->off_scale), st);
     if (rc != 0) { ctx->last_error = "mh_step: launch failed"; return SEPAIHRD_E_HIP; }
     std::swap(mh->d_z, mh->d_z_stage);  // the next staging goes to the other buffer
     mh->staged = false;
-    return sepaihrd_eval_batch_device(ctx, mh->st.prop, C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, nullptr, st);
+    return mh_eval_device(mh, mh->st.prop);
 }
 
 int sepaihrd_mh_fetch(sepaihrd_mh* mh, double* loglik, int32_t* status) {
     if (!mh || !loglik) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     return mh_fetch_values(mh, loglik, status);
 }
 
 int sepaihrd_mh_set_values(sepaihrd_mh* mh, const double* values) {
     if (!mh || !values) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     const size_t bytes = (size_t)mh->st.C * sizeof(double);
     HIP_TRY(hipMemcpy(mh->d_lp, values, bytes, hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
@@ -1547,6 +1622,13 @@ double* sepaihrd_mh_test_buffer(sepaihrd_mh* mh) { return mh ? mh->h_test : null
 // evaluated on fixed arguments and compared, bit for bit, with the std::log / std::exp of THIS process.
 int sepaihrd_device_libm_check(sepaihrd_ctx* ctx, int32_t* n_log_diff, int32_t* n_exp_diff) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    return device_libm_check(ctx->device, ctx->last_error, ctx->libm_log_diff, ctx->libm_exp_diff, n_log_diff, n_exp_diff);
+}
+
+}  // extern "C"
+
+int sepaihrd::device_libm_check(int device, std::string& last_error, int& log_diff, int& exp_diff, int32_t* n_log_diff, int32_t* n_exp_diff) {
+    struct { int device; std::string& last_error; int& libm_log_diff; int& libm_exp_diff; } view{device, last_error, log_diff, exp_diff}, *ctx = &view;
     if (ctx->libm_log_diff < 0) {
         HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
         const int N = sampler_libm_check_count();
@@ -1576,13 +1658,15 @@ int sepaihrd_device_libm_check(sepaihrd_ctx* ctx, int32_t* n_log_diff, int32_t* 
     return SEPAIHRD_OK;
 }
 
+extern "C" {
+
 namespace {
 // does a batch of C chains fill the chip with two integrator waves per SIMD (the same threshold as launch_one's)?
 bool mh_lz_ahead_wanted() {
     const char* e = std::getenv("SEPAIHRD_MH_LZ");
     return !(e && std::string(e) == "fused");
 }
-bool mh_draws_behind_the_evaluation(const sepaihrd_ctx* ctx, int C) {
+bool mh_draws_behind_the_evaluation(const MhBackend* ctx, int C) {
     if (const char* e = std::getenv("SEPAIHRD_MH_DRAW")) {
         if (std::string(e) == "overlap") return false;
         if (std::string(e) == "serial") return true;
@@ -1609,9 +1693,9 @@ int sepaihrd_device_log_values(sepaihrd_ctx* ctx, const double* x, int32_t n, do
 namespace {
 // seed_streams / keep_scale_on_device refuse when the device functions are not this host's libm
 int mh_require_matching_libm(sepaihrd_mh* mh, const char* who) {
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     int32_t dl = 0, de = 0;
-    const int rc = sepaihrd_device_libm_check(ctx, &dl, &de);
+    const int rc = device_libm_check(ctx->device, ctx->last_error, ctx->libm_log_diff, ctx->libm_exp_diff, &dl, &de);
     if (rc != SEPAIHRD_OK) return rc;
     if (dl == 0 && de == 0) return SEPAIHRD_OK;
     char msg[384];
@@ -1626,7 +1710,7 @@ int mh_require_matching_libm(sepaihrd_mh* mh, const char* who) {
 
 int sepaihrd_mh_seed_streams(sepaihrd_mh* mh, uint32_t seed0) {
     if (!mh) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     if (const int rc = mh_require_matching_libm(mh, "mh_seed_streams")) return rc;
     if (sampler_seed_streams(mh->st, seed0, mh->stream) != 0) { ctx->last_error = "mh_seed_streams: launch failed"; return SEPAIHRD_E_HIP; }
@@ -1637,7 +1721,7 @@ int sepaihrd_mh_seed_streams(sepaihrd_mh* mh, uint32_t seed0) {
 
 int sepaihrd_mh_keep_scale_on_device(sepaihrd_mh* mh, int adapt_scale, double target_rate, int keep_trace) {
     if (!mh) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     if (mh->rows > 1) {
         ctx->last_error = "mh_keep_scale_on_device: call it before the first iteration (the accept window and the sample values start with the run)";
@@ -1688,7 +1772,7 @@ int sepaihrd_mh_keep_scale_on_device(sepaihrd_mh* mh, int adapt_scale, double ta
 
 int sepaihrd_mh_read_run_state(sepaihrd_mh* mh, double* values, double* best_values, double* scales, int32_t* accepted, int32_t* emergency) {
     if (!mh) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);
     const size_t C = (size_t)mh->st.C;
@@ -1712,7 +1796,7 @@ int sepaihrd_mh_read_run_state(sepaihrd_mh* mh, double* values, double* best_val
 // report_interval iterations).  Reading them with the synchronous getters would drain the queue.
 int sepaihrd_mh_snapshot_begin(sepaihrd_mh* mh, const int32_t* chains, int n, int first_sample, int count) {
     if (!mh || !chains || n <= 0 || first_sample < 0 || count < 0) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     const int C = mh->st.C, P = mh->st.P;
     if (mh->snap_pending) { ctx->last_error = "mh_snapshot_begin: the previous snapshot has not been collected (sepaihrd_mh_snapshot_end)"; return SEPAIHRD_E_INVALID_ARG; }
     if (!mh->values_set) { ctx->last_error = "mh_snapshot_begin: the chains' values are unknown (sepaihrd_mh_set_values)"; return SEPAIHRD_E_INVALID_ARG; }
@@ -1786,7 +1870,7 @@ int sepaihrd_mh_snapshot_end(sepaihrd_mh* mh, int wait, double* state, double* s
 
 int sepaihrd_mh_read_failure_counts(sepaihrd_mh* mh, int64_t counts[3]) {
     if (!mh || !counts) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);
     uint32_t h[3] = {0, 0, 0};
@@ -1797,7 +1881,7 @@ int sepaihrd_mh_read_failure_counts(sepaihrd_mh* mh, int64_t counts[3]) {
 
 int sepaihrd_mh_read_sample_values(sepaihrd_mh* mh, int first, int count, double* out) {
     if (!mh || !out || first < 0 || count <= 0) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (!mh->st.lp_store || first + count > sepaihrd_mh_sample_count(mh)) {
         ctx->last_error = "mh_read_sample_values: not kept (sepaihrd_mh_keep_scale_on_device) or beyond the samples stored so far";
         return SEPAIHRD_E_INVALID_ARG;
@@ -1811,7 +1895,7 @@ int sepaihrd_mh_read_sample_values(sepaihrd_mh* mh, int first, int count, double
 
 int sepaihrd_mh_read_accept_trace(sepaihrd_mh* mh, uint8_t* out) {
     if (!mh || !out) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (!mh->st.trace) { ctx->last_error = "mh_read_accept_trace: no trace kept"; return SEPAIHRD_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);
@@ -1821,11 +1905,11 @@ int sepaihrd_mh_read_accept_trace(sepaihrd_mh* mh, uint8_t* out) {
 
 int sepaihrd_mh_draw_first(sepaihrd_mh* mh) {
     if (!mh) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (!mh->device_rng) { ctx->last_error = "mh_draw_first: call sepaihrd_mh_seed_streams first"; return SEPAIHRD_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     // proposal 1: the normals from the start of every stream, into the staged-normals buffer
-    if (sampler_draw(mh->st, nullptr, 1, nullptr, mh->d_z_stage, nullptr, 1, mh->copy_stream) != 0) { ctx->last_error = "mh_draw_first: launch failed"; return SEPAIHRD_E_HIP; }
+    if (mh_launch_draw(mh, nullptr, 1, nullptr, mh->d_z_stage, nullptr, 1, mh->copy_stream) != 0) { ctx->last_error = "mh_draw_first: launch failed"; return SEPAIHRD_E_HIP; }
     HIP_TRY(hipEventRecord(mh->ev_staged, mh->copy_stream), ctx, return SEPAIHRD_E_HIP);
     mh->staged = true;
     return SEPAIHRD_OK;
@@ -1833,7 +1917,7 @@ int sepaihrd_mh_draw_first(sepaihrd_mh* mh) {
 
 int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) {
     if (!mh || adapt < 0 || adapt > 3) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     const int C = mh->st.C, P = mh->st.P;
     if (!mh->values_set) { ctx->last_error = "mh_step_tested: call sepaihrd_mh_set_values first"; return SEPAIHRD_E_INVALID_ARG; }
     const bool self_contained = mh->device_rng && mh->st.device_scale != 0;  // nothing of the caller's goes into the test
@@ -1871,7 +1955,7 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
         // one round, 32 768 chains, still gains from the overlap -- 1.95 against 2.00 -- as the draws fill the round's tail;
         // a low-priority copy stream changed nothing).  SEPAIHRD_MH_DRAW=overlap|serial overrides (A/B runs).
         const bool serial_draw = mh_draws_behind_the_evaluation(ctx, C);
-        if (sampler_draw(mh->st, prev_flags, 0, mh->d_test, mh->d_z_stage, mh->d_test + 3 * (size_t)C, last ? 0 : 1, serial_draw ? st : cs) != 0) {
+        if (mh_launch_draw(mh, prev_flags, 0, mh->d_test, mh->d_z_stage, mh->d_test + 3 * (size_t)C, last ? 0 : 1, serial_draw ? st : cs) != 0) {
             ctx->last_error = "mh_step_tested: draw launch failed";
             return SEPAIHRD_E_HIP;
         }
@@ -1879,7 +1963,7 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
         // ... and, when the draws run beside the evaluation and no covariance refresh separates this test from its proposal,
         // L z of both continuations too: the launch between two evaluations then reads no factor (SEPAIHRD_MH_LZ=fused: A/B)
         if (!serial_draw && !last && adapt <= 1 && mh->st.P <= 200 && mh_lz_ahead_wanted()) {
-            if (sampler_lz(mh->st, mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->d_lz, mh->d_lz + CP, cs) != 0) {
+            if (mh_launch_lz(mh, mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->d_lz, mh->d_lz + CP, cs) != 0) {
                 ctx->last_error = "mh_step_tested: L z launch failed";
                 return SEPAIHRD_E_HIP;
             }
@@ -1896,10 +1980,14 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
     if (!last && adapt <= 1) {
         // no covariance refresh between commit and proposal: test, commit and proposal in one launch
         // (the staged normals landed before the test's inputs: same copy stream, staged first -- ev_test_up covers them)
-        if (sampler_test_commit_propose(mh->st, ctx->dp, mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C, mh->d_test + 2 * (size_t)C,
-                                        mh->d_lp, mh->d_best_lp, mh->d_scale_sel, d_flags, d_values, mh->d_z_stage,
-                                        mh->d_test + 3 * (size_t)C, mh->rows, st, mh->lz_ready ? mh->d_lz : nullptr,
-                                        mh->lz_ready ? mh->d_lz + CP : nullptr) != 0) {
+        const double* const lz_u = mh->lz_ready ? mh->d_lz : nullptr;
+        const double* const lz_p = mh->lz_ready ? mh->d_lz + CP : nullptr;
+        if ((mh->packed ? sampler_test_commit_propose_packed(mh->st, mh_bounds_of(ctx->dp), mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C,
+                                                             mh->d_test + 2 * (size_t)C, mh->d_lp, mh->d_best_lp, mh->d_scale_sel, d_flags, d_values,
+                                                             mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->rows, st, lz_u, lz_p)
+                        : sampler_test_commit_propose(mh->st, ctx->dp, mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C,
+                                                      mh->d_test + 2 * (size_t)C, mh->d_lp, mh->d_best_lp, mh->d_scale_sel, d_flags, d_values,
+                                                      mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->rows, st, lz_u, lz_p)) != 0) {
             ctx->last_error = "mh_step_tested: launch failed";
             return SEPAIHRD_E_HIP;
         }
@@ -1917,7 +2005,7 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
         if (adapt == 1) mh_queue_rank1(mh, gamma);  // as mh_adapt_step: the queued update names history row rows - 1
         std::swap(mh->d_z, mh->d_z_stage);
         mh->staged = false;
-        return sepaihrd_eval_batch_device(ctx, mh->st.prop, C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, nullptr, st);
+        return mh_eval_device(mh, mh->st.prop);
     }
     int rc = sampler_accept_test(mh->st, mh->rows, mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C, mh->d_test + 2 * (size_t)C, mh->d_lp,
                                  mh->d_best_lp, mh->d_scale_sel, d_flags, d_values, st);
@@ -1938,19 +2026,19 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
     rc = mh_adapt_step(mh, gamma, adapt);
     if (rc != 0) { ctx->last_error = "mh_step_tested: launch failed"; return SEPAIHRD_E_HIP; }
     HIP_TRY(hipStreamWaitEvent(st, mh->ev_staged, 0), ctx, return SEPAIHRD_E_HIP);  // the staged normals have landed
-    rc = sampler_propose_select(mh->st, ctx->dp, mh->d_z_stage, mh->d_test + 3 * (size_t)C, d_flags, mh->d_scale_sel, st);
+    rc = mh_launch_propose_select(mh, mh->d_z_stage, mh->d_test + 3 * (size_t)C, d_flags, mh->d_scale_sel, st);
     if (rc != 0) { ctx->last_error = "mh_step_tested: launch failed"; return SEPAIHRD_E_HIP; }
     HIP_TRY(hipEventRecord(mh->ev_proposed, st), ctx, return SEPAIHRD_E_HIP);
     mh->ev_last_proposed = mh->ev_proposed;
     mh->proposed_once = true;
     std::swap(mh->d_z, mh->d_z_stage);
     mh->staged = false;
-    return sepaihrd_eval_batch_device(ctx, mh->st.prop, C, mh->d_loglik, mh->d_status, nullptr, nullptr, nullptr, nullptr, st);
+    return mh_eval_device(mh, mh->st.prop);
 }
 
 int sepaihrd_mh_fetch_test(sepaihrd_mh* mh, double* values, uint8_t* flags) {
     if (!mh || !values || !flags) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (!mh->test_pending) { ctx->last_error = "mh_fetch_test: no test pending"; return SEPAIHRD_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipEventSynchronize(mh->ev_fetched), ctx, return SEPAIHRD_E_HIP);
@@ -1963,7 +2051,7 @@ int sepaihrd_mh_fetch_test(sepaihrd_mh* mh, double* values, uint8_t* flags) {
 
 int sepaihrd_mh_commit(sepaihrd_mh* mh, const uint8_t* accept) {
     if (!mh || !accept) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (mh->rows >= mh->iterations) {
         ctx->last_error = "mh_commit: more states than the sampler was created for";
         return SEPAIHRD_E_INVALID_ARG;
@@ -1981,7 +2069,7 @@ int sepaihrd_mh_commit(sepaihrd_mh* mh, const uint8_t* accept) {
 
 int sepaihrd_mh_adapt(sepaihrd_mh* mh, double gamma, int refresh, int recompute_full) {
     if (!mh) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     const int rc = mh_adapt_step(mh, gamma, refresh ? (recompute_full ? 3 : 2) : 1);
     if (rc != 0) {
@@ -1993,7 +2081,7 @@ int sepaihrd_mh_adapt(sepaihrd_mh* mh, double gamma, int refresh, int recompute_
 
 int sepaihrd_mh_read_history(sepaihrd_mh* mh, const int32_t* rows, int n_rows, double* out) {
     if (!mh || !rows || n_rows <= 0 || !out) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     const int C = mh->st.C, P = mh->st.P, W = mh->st.window;
     for (int r = 0; r < n_rows; ++r)
@@ -2019,7 +2107,7 @@ int sepaihrd_mh_sample_count(const sepaihrd_mh* mh) {
 
 int sepaihrd_mh_read_samples(sepaihrd_mh* mh, int first, int count, double* out) {
     if (!mh || !out || first < 0 || count <= 0) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (first + count > sepaihrd_mh_sample_count(mh)) {
         ctx->last_error = "mh_read_samples: beyond the samples stored so far";
         return SEPAIHRD_E_INVALID_ARG;
@@ -2036,7 +2124,7 @@ int sepaihrd_mh_read_samples(sepaihrd_mh* mh, int first, int count, double* out)
 
 int sepaihrd_mh_summary_records(sepaihrd_mh* mh, int first_sample, double* out, double* d_out) {
     if (!mh || (!out && !d_out)) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     const int ns = sepaihrd_mh_sample_count(mh);
     if (first_sample < 0 || first_sample >= ns) {
         ctx->last_error = "mh_summary_records: first_sample beyond the samples stored so far";
@@ -2059,7 +2147,8 @@ int sepaihrd_mh_summary_records(sepaihrd_mh* mh, int first_sample, double* out, 
 }  // extern "C"
 
 namespace {
-int diag_check_shape(sepaihrd_ctx* ctx, const char* who, int C, int N, int P) {
+template <class Ctx>  // sepaihrd_ctx, or the record a sampler keeps of its context
+int diag_check_shape(Ctx* ctx, const char* who, int C, int N, int P) {
     if (C < 1 || P < 1 || N < 4) {
         ctx->last_error = std::string(who) + ": need C >= 1 chains, P >= 1 columns and N >= 4 draws per chain";
         return SEPAIHRD_E_INVALID_ARG;
@@ -2075,7 +2164,8 @@ int diag_check_shape(sepaihrd_ctx* ctx, const char* who, int C, int N, int P) {
     return SEPAIHRD_OK;
 }
 
-int diag_run(sepaihrd_ctx* ctx, const char* who, const DiagInput& in, double* out, int32_t* max_lag, hipStream_t st) {
+template <class Ctx>
+int diag_run(Ctx* ctx, const char* who, const DiagInput& in, double* out, int32_t* max_lag, hipStream_t st) {
     const int rc = chain_diagnostics(in, out, max_lag, st);
     if (rc == -4) { ctx->last_error = std::string(who) + ": invalid shape"; return SEPAIHRD_E_INVALID_ARG; }
     if (rc != 0) {
@@ -2118,7 +2208,7 @@ int sepaihrd_chain_diagnostics(sepaihrd_ctx* ctx, const double* samples, const d
 
 int sepaihrd_mh_diagnostics(sepaihrd_mh* mh, int first_sample, int count, int with_values, double* out, int32_t* max_lag) {
     if (!mh) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (!out) { ctx->last_error = "mh_diagnostics: out is required"; return SEPAIHRD_E_INVALID_ARG; }
     if (ctx->pending_B > 0) {
         ctx->last_error = "mh_diagnostics: a sepaihrd_eval_batch_begin is pending on this context";
@@ -2154,7 +2244,7 @@ int sepaihrd_mh_diagnostics(sepaihrd_mh* mh, int first_sample, int count, int wi
 
 int sepaihrd_mh_read_moments(sepaihrd_mh* mh, double* mean, double* m2) {
     if (!mh || (!mean && !m2)) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     if (mh->covariance_mode != SEPAIHRD_MH_COV_RUNNING) { ctx->last_error = "mh_read_moments: the sampler keeps no running sums (two-pass mode)"; return SEPAIHRD_E_INVALID_ARG; }
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     if (mh_flush_moments(mh, 0) != 0) { ctx->last_error = "mh_read_moments: catch-up failed"; return SEPAIHRD_E_HIP; }
@@ -2167,7 +2257,7 @@ int sepaihrd_mh_read_moments(sepaihrd_mh* mh, double* mean, double* m2) {
 
 int sepaihrd_mh_read_proposal(sepaihrd_mh* mh, double* prop) {
     if (!mh || !prop) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(prop, mh->st.prop, (size_t)mh->st.C * mh->st.P * sizeof(double), hipMemcpyDeviceToHost), ctx,
@@ -2177,7 +2267,7 @@ int sepaihrd_mh_read_proposal(sepaihrd_mh* mh, double* prop) {
 
 int sepaihrd_mh_read_best(sepaihrd_mh* mh, double* best) {
     if (!mh || !best) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(best, mh->st.best, (size_t)mh->st.C * mh->st.P * sizeof(double), hipMemcpyDeviceToHost), ctx,
@@ -2192,7 +2282,7 @@ int sepaihrd_mh_busy(sepaihrd_mh* mh) {
 
 int sepaihrd_mh_read_covariance(sepaihrd_mh* mh, double* cov) {
     if (!mh || !cov) return SEPAIHRD_E_INVALID_ARG;
-    sepaihrd_ctx* ctx = mh->ctx;
+    MhBackend* ctx = mh->ctx;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     if (mh_flush_rank1(mh) != 0) { ctx->last_error = "mh_read_covariance: rank-one catch-up failed"; return SEPAIHRD_E_HIP; }
     HIP_TRY(hipStreamSynchronize(mh->stream), ctx, return SEPAIHRD_E_HIP);

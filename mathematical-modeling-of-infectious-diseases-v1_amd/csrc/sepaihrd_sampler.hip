@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_mh_backend.h"
 #include "sepaihrd_rng.inc"
 
 namespace sepaihrd {
@@ -353,6 +354,123 @@ __global__ __launch_bounds__(WAVE) void mh_lz_kernel(const SamplerState s, const
         lz_uniform[(size_t)c * P + i] = a;
         lz_plain[(size_t)c * P + i] = b;
     }
+}
+
+// ---- the packed small-P form of the per-iteration kernels ----
+// The kernels above give a chain a workgroup of one or two wavefronts: right for the 62 parameters they were shaped on, 59 idle
+// lanes of 64 for the five of an age-structured SIR problem, and one workgroup dispatched per chain either way.  Here a
+// chain is a group of G = pow2(P) ADJACENT lanes (lane i of the group owns element i: row i of L z, x_i, prop_i), 64 / G chains
+// share a wavefront and four wavefronts a workgroup; the workgroup needs no LDS and no barrier, the group's first lane runs the
+// serial part (accept rule, scale adaptation, outcome records) and hands flags and scale to its group with two cross-lane
+// reads.  Every value is formed by the device functions the block-per-chain kernels call (chol_row_dot / chol_row_dot2,
+// constrain, adapt_global_scale, record_outcome) on the same operands in the same order: the same bits.  mh_accept_kernel
+// and mh_commit_kernel are one thread per chain / per element already and serve both forms.  The draws' packed form
+// (mh_draw_window_kernel) is next to the draw kernel below.
+constexpr int PACKED_THREADS = 4 * WAVE;
+template <int G>
+struct PackedLane {
+    int c, i;     // chain and element of this lane
+    bool live;    // a chain of the batch and an element of its state (G - P lanes of a group and the last wave's tail idle)
+    __device__ __forceinline__ PackedLane(const SamplerState& s) {
+        const long long t = (long long)blockIdx.x * PACKED_THREADS + threadIdx.x;
+        c = (int)(t / G);
+        i = (int)(t % G);
+        live = c < s.C && i < s.P;
+    }
+};
+
+template <int G>
+__global__ __launch_bounds__(PACKED_THREADS) void mh_propose_packed_kernel(const SamplerState s, const MhBounds pb, const double* z, const double* scale) {
+    const PackedLane<G> ln(s);
+    if (!ln.live) return;
+    const int c = ln.c, i = ln.i, P = s.P;
+    const double sum = chol_row_dot(s.chol + (size_t)c * P * P, z + (size_t)c * P, i, P);
+    const double raw = s.x[(size_t)c * P + i] + scale[c] * sum;
+    s.prop[(size_t)c * P + i] = constrain(raw, pb.lower[i], pb.upper[i], pb.has_bounds[i], pb.constraint_mode);
+}
+
+template <int G>
+__global__ __launch_bounds__(PACKED_THREADS) void mh_propose_select_packed_kernel(const SamplerState s, const MhBounds pb, const double* z_uniform,
+                                                                                  const double* z_plain, const uint8_t* flags, const double* scale) {
+    const PackedLane<G> ln(s);
+    if (!ln.live) return;
+    const int c = ln.c, i = ln.i, P = s.P;
+    const double* zc = ((flags[c] & 4) ? z_plain : z_uniform) + (size_t)c * P;
+    const double sum = chol_row_dot(s.chol + (size_t)c * P * P, zc, i, P);
+    const double raw = s.x[(size_t)c * P + i] + scale[c] * sum;
+    s.prop[(size_t)c * P + i] = constrain(raw, pb.lower[i], pb.upper[i], pb.has_bounds[i], pb.constraint_mode);
+}
+
+template <int G>
+__global__ __launch_bounds__(PACKED_THREADS) void mh_lz_packed_kernel(const SamplerState s, const double* __restrict__ z_uniform,
+                                                                      const double* __restrict__ z_plain, double* __restrict__ lz_uniform,
+                                                                      double* __restrict__ lz_plain) {
+    const PackedLane<G> ln(s);
+    if (!ln.live) return;
+    const int c = ln.c, i = ln.i, P = s.P;
+    double a, b;
+    chol_row_dot2(s.chol + (size_t)c * P * P, z_uniform + (size_t)c * P, z_plain + (size_t)c * P, i, P, a, b);
+    lz_uniform[(size_t)c * P + i] = a;
+    lz_plain[(size_t)c * P + i] = b;
+}
+
+// mh_test_commit_propose_kernel for G-lane chains.  No lane leaves before the cross-lane reads: a group's first lane holds
+// what its other lanes need.
+template <int G>
+__global__ __launch_bounds__(PACKED_THREADS) void mh_test_commit_propose_packed_kernel(const SamplerState s, const MhBounds pb,
+        const double* __restrict__ loglik, const int32_t* __restrict__ status, const double* __restrict__ log_u,
+        const double* __restrict__ scale_reject, const double* __restrict__ scale_accept, double* lp, double* best_lp, double* scale_sel,
+        uint8_t* flags, double* values, const double* z_uniform, const double* z_plain, const int row,
+        const double* __restrict__ lz_uniform, const double* __restrict__ lz_plain) {
+    const PackedLane<G> ln(s);
+    const int c = ln.c, i = ln.i, P = s.P;
+    const size_t idx = (size_t)c * P + i;
+    double su = 0.0, sp = 0.0, x_cur = 0.0, x_prop = 0.0;
+    if (ln.live) {  // requested before the serial part below, consumed after it
+        x_cur = s.x[idx];
+        x_prop = s.prop[idx];
+        if (lz_uniform != nullptr) {
+            su = lz_uniform[idx];
+            sp = lz_plain[idx];
+        } else {
+            chol_row_dot2(s.chol + (size_t)c * P * P, z_uniform + (size_t)c * P, z_plain + (size_t)c * P, i, P, su, sp);
+        }
+    }
+    int f = 0;
+    double sc = 0.0;
+    if (ln.live && i == 0) {
+        double v = loglik[c];
+        count_failure(s, status[c]);
+        if (status[c] >= 2 || isnan(v) || isinf(v)) v = -1e18;
+        const double log_ratio = v - lp[c];
+        const bool no_uniform = log_ratio >= 0.0;
+        const bool acc = no_uniform || (log_u[c] < log_ratio);
+        f = (acc ? 1 : 0) | (no_uniform ? 4 : 0);
+        if (acc) {
+            lp[c] = v;
+            s.accepted[c] += 1;
+            if (v > best_lp[c]) { best_lp[c] = v; f |= 2; }
+        }
+        sc = s.device_scale ? adapt_global_scale(s, c, acc, row) : (acc ? scale_accept[c] : scale_reject[c]);
+        record_outcome(s, c, row, acc, lp[c]);
+        flags[c] = (uint8_t)f;
+        scale_sel[c] = sc;
+        values[c] = v;
+    }
+    if (G > 1) {  // the group's first lane -> its group
+        f = __shfl(f, 0, G);
+        sc = __shfl(sc, 0, G);
+    }
+    if (!ln.live) return;
+    const double v = (f & 1) ? x_prop : x_cur;
+    if (f & 1) s.x[idx] = v;
+    if (f & 2) s.best[idx] = x_prop;
+    ring_row(s, c, row)[i] = v;
+    double* const kept = store_row(s, c, row);
+    if (kept) kept[i] = v;
+    const double sum = (f & 4) ? sp : su;
+    const double raw = v + sc * sum;
+    s.prop[idx] = constrain(raw, pb.lower[i], pb.upper[i], pb.has_bounds[i], pb.constraint_mode);
 }
 
 // accepted_known: the accept byte comes from mh_accept_kernel, which has counted it already
@@ -699,9 +817,9 @@ __global__ void mh_seed_kernel(const SamplerState s, const uint32_t seed0) {
 // the draw's first one whatever the attempts before it decided; the lanes evaluate 64 attempts at once, a ballot ranks the
 // accepted ones, and the first ceil(P / 2) of them are the distribution's pairs (y mult, x mult) in order -- the values and
 // the number of words consumed are those of the sequential loop.
-__global__ __launch_bounds__(WAVE) void mh_draw_kernel(const SamplerState s, const uint8_t* __restrict__ flags, const int first,
-                                                       double* __restrict__ log_u, double* __restrict__ z_uniform,
-                                                       double* __restrict__ z_plain, const int want_normals) {
+__device__ __forceinline__ void mh_draw_chain(const SamplerState& s, const uint8_t* __restrict__ flags, const int first,
+                                              double* __restrict__ log_u, double* __restrict__ z_uniform,
+                                              double* __restrict__ z_plain, const int want_normals) {
     using namespace sepaihrd_rng;
     __shared__ uint32_t st[2][MT_N];
     __shared__ int last_lane[2];
@@ -795,6 +913,74 @@ __global__ __launch_bounds__(WAVE) void mh_draw_kernel(const SamplerState s, con
         s.mt_used[2 * c + 1] = used_words[1];
     }
 }
+__global__ __launch_bounds__(WAVE) void mh_draw_kernel(const SamplerState s, const uint8_t* __restrict__ flags, const int first,
+                                                       double* __restrict__ log_u, double* __restrict__ z_uniform,
+                                                       double* __restrict__ z_plain, const int want_normals) {
+    mh_draw_chain(s, flags, first, log_u, z_uniform, z_plain, want_normals);
+}
+
+// ---- the draws in the packed form ----
+// A proposal of P <= 64 normals and one uniform touches a short window of the generator's 624 words: 2 + 4 words per
+// polar attempt, ~1.27 attempts per pair -- some 20 words for the five parameters of an age-structured SIR problem -- and
+// the state twists once every few dozen iterations.  mh_draw_window_kernel gives a chain ONE LANE that reads that window
+// straight from the stored state and runs the attempts one after the other: the sequential loop of the distribution, of
+// which the wave-parallel kernel above is the restatement -- same words, same canonicals, same products, same count of
+// words consumed.  It handles a chain only while everything it touches lies inside the stored state: a chain whose stream
+// position or look-ahead reaches word 624 writes nothing but todo[c] = 1 (the normals it may have written are
+// overwritten), and mh_draw_rest_kernel runs the kernel above for those chains alone (its other workgroups leave at once).
+constexpr int DRAW_WINDOW_THREADS = 256;
+__global__ __launch_bounds__(DRAW_WINDOW_THREADS) void mh_draw_window_kernel(const SamplerState s, const uint8_t* __restrict__ flags,
+        const int first, double* __restrict__ log_u, double* __restrict__ z_uniform, double* __restrict__ z_plain, const int want_normals,
+        uint8_t* __restrict__ todo) {
+    using namespace sepaihrd_rng;
+    const int c = blockIdx.x * DRAW_WINDOW_THREADS + threadIdx.x;
+    if (c >= s.C) return;
+    const int P = s.P;
+    const uint32_t* const g = s.mt + (size_t)c * MT_N;
+    const int consumed = first ? 0 : ((flags[c] & 4) ? s.mt_used[2 * c + 1] : s.mt_used[2 * c]);
+    const int idx = s.mt_idx[c] + consumed;  // where the previous test's continuation left the stream
+    bool inside = idx < MT_N;
+    double lu = 0.0;
+    if (inside && !first) {
+        if (idx + 1 < MT_N) lu = glibc_log(mt_canonical(mt_temper(g[idx]), mt_temper(g[idx + 1])));
+        else inside = false;
+    }
+    int used_words[2] = {2, 0};
+    const int npairs = (P + 1) / 2;
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {  // [0] the continuation with the uniform in front, [1] without
+        if (!inside || !want_normals || (v == 0 && first)) continue;
+        double* const zd = (v == 0 ? z_uniform : (first ? z_uniform : z_plain)) + (size_t)c * P;
+        int have = 0, k = 0;
+        for (; have < npairs; ++k) {  // attempt k takes canonicals 2k, 2k + 1 from the draw's first one
+            const int q = idx + (v == 0 ? 2 : 0) + 4 * k;
+            if (q + 3 >= MT_N) { inside = false; break; }
+            const double c0 = mt_canonical(mt_temper(g[q]), mt_temper(g[q + 1]));
+            const double c1 = mt_canonical(mt_temper(g[q + 2]), mt_temper(g[q + 3]));
+            const double x = 2.0 * c0 - 1.0, y = 2.0 * c1 - 1.0;
+            const double r2 = x * x + y * y;
+            if (r2 > 1.0 || r2 == 0.0) continue;
+            const double mult = sqrt(-2 * glibc_log(r2) / r2);
+            zd[2 * have] = (y * mult) * 1.0 + 0.0;
+            if (2 * have + 1 < P) zd[2 * have + 1] = (x * mult) * 1.0 + 0.0;
+            ++have;
+        }
+        used_words[v] = (v == 0 ? 2 : 0) + 4 * k;
+    }
+    todo[c] = inside ? 0 : 1;
+    if (!inside) return;
+    s.mt_idx[c] = idx;
+    if (!first) log_u[c] = lu;
+    s.mt_used[2 * c] = first ? used_words[1] : used_words[0];
+    s.mt_used[2 * c + 1] = used_words[1];
+}
+__global__ __launch_bounds__(WAVE) void mh_draw_rest_kernel(const SamplerState s, const uint8_t* __restrict__ flags, const int first,
+                                                            double* __restrict__ log_u, double* __restrict__ z_uniform,
+                                                            double* __restrict__ z_plain, const int want_normals,
+                                                            const uint8_t* __restrict__ todo) {
+    if (!todo[blockIdx.x]) return;  // the whole workgroup: nothing was synchronised yet
+    mh_draw_chain(s, flags, first, log_u, z_uniform, z_plain, want_normals);
+}
 
 }  // namespace
 
@@ -826,6 +1012,17 @@ int sampler_draw(const SamplerState& s, const uint8_t* d_flags, int first, doubl
                  int want_normals, void* stream) {
     hipLaunchKernelGGL(mh_draw_kernel, dim3(s.C), dim3(WAVE), 0, static_cast<hipStream_t>(stream), s, d_flags, first, d_log_u, d_z_uniform,
                        d_z_plain, want_normals);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int sampler_draw_packed(const SamplerState& s, const uint8_t* d_flags, int first, double* d_log_u, double* d_z_uniform, double* d_z_plain,
+                        int want_normals, uint8_t* d_todo, void* stream) {
+    if (s.P > MH_PACKED_MAX_P) return -4;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(mh_draw_window_kernel, dim3(blocks_for((size_t)s.C, DRAW_WINDOW_THREADS)), dim3(DRAW_WINDOW_THREADS), 0, st, s, d_flags,
+                       first, d_log_u, d_z_uniform, d_z_plain, want_normals, d_todo);
+    hipLaunchKernelGGL(mh_draw_rest_kernel, dim3(s.C), dim3(WAVE), 0, st, s, d_flags, first, d_log_u, d_z_uniform, d_z_plain, want_normals,
+                       d_todo);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -878,6 +1075,45 @@ int sampler_lz(const SamplerState& s, const double* d_z_uniform, const double* d
     hipLaunchKernelGGL(mh_lz_kernel, dim3(s.C), dim3(WAVE), 0, static_cast<hipStream_t>(stream), s, d_z_uniform, d_z_plain, d_lz_uniform, d_lz_plain);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
+
+// ---- launches of the packed form: one instantiation per group width, G = pow2(P) ----
+#define SEPAIHRD_PACKED_DISPATCH(KERNEL, ...)                                                                              \
+    do {                                                                                                                   \
+        if (s.P < 1 || s.P > MH_PACKED_MAX_P) return -4;                                                                   \
+        const int g_ = mh_packed_group(s.P);                                                                               \
+        const dim3 grid_(blocks_for((size_t)s.C * g_, PACKED_THREADS)), block_(PACKED_THREADS);                            \
+        hipStream_t st_ = static_cast<hipStream_t>(stream);                                                                \
+        switch (g_) {                                                                                                      \
+            case 1: hipLaunchKernelGGL(KERNEL<1>, grid_, block_, 0, st_, __VA_ARGS__); break;                              \
+            case 2: hipLaunchKernelGGL(KERNEL<2>, grid_, block_, 0, st_, __VA_ARGS__); break;                              \
+            case 4: hipLaunchKernelGGL(KERNEL<4>, grid_, block_, 0, st_, __VA_ARGS__); break;                              \
+            case 8: hipLaunchKernelGGL(KERNEL<8>, grid_, block_, 0, st_, __VA_ARGS__); break;                              \
+            case 16: hipLaunchKernelGGL(KERNEL<16>, grid_, block_, 0, st_, __VA_ARGS__); break;                            \
+            case 32: hipLaunchKernelGGL(KERNEL<32>, grid_, block_, 0, st_, __VA_ARGS__); break;                            \
+            default: hipLaunchKernelGGL(KERNEL<64>, grid_, block_, 0, st_, __VA_ARGS__); break;                            \
+        }                                                                                                                  \
+        return hipGetLastError() == hipSuccess ? 0 : -3;                                                                   \
+    } while (0)
+
+int sampler_propose_packed(const SamplerState& s, const MhBounds& b, const double* d_z, const double* d_scale, void* stream) {
+    SEPAIHRD_PACKED_DISPATCH(mh_propose_packed_kernel, s, b, d_z, d_scale);
+}
+int sampler_propose_select_packed(const SamplerState& s, const MhBounds& b, const double* d_z_uniform, const double* d_z_plain,
+                                  const uint8_t* d_flags, const double* d_scale, void* stream) {
+    SEPAIHRD_PACKED_DISPATCH(mh_propose_select_packed_kernel, s, b, d_z_uniform, d_z_plain, d_flags, d_scale);
+}
+int sampler_lz_packed(const SamplerState& s, const double* d_z_uniform, const double* d_z_plain, double* d_lz_uniform, double* d_lz_plain,
+                      void* stream) {
+    SEPAIHRD_PACKED_DISPATCH(mh_lz_packed_kernel, s, d_z_uniform, d_z_plain, d_lz_uniform, d_lz_plain);
+}
+int sampler_test_commit_propose_packed(const SamplerState& s, const MhBounds& b, const double* d_loglik, const int32_t* d_status,
+                                       const double* d_log_u, const double* d_scale_reject, const double* d_scale_accept, double* d_lp,
+                                       double* d_best_lp, double* d_scale_sel, uint8_t* d_flags, double* d_values, const double* d_z_uniform,
+                                       const double* d_z_plain, int row, void* stream, const double* d_lz_uniform, const double* d_lz_plain) {
+    SEPAIHRD_PACKED_DISPATCH(mh_test_commit_propose_packed_kernel, s, b, d_loglik, d_status, d_log_u, d_scale_reject, d_scale_accept, d_lp,
+                             d_best_lp, d_scale_sel, d_flags, d_values, d_z_uniform, d_z_plain, row, d_lz_uniform, d_lz_plain);
+}
+#undef SEPAIHRD_PACKED_DISPATCH
 
 // d_accept written by sampler_accept_test (flags) has been counted there; a caller's own accept bytes are counted here
 int sampler_commit(const SamplerState& s, const uint8_t* d_accept, int row, void* stream) {

@@ -9,10 +9,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_mh_backend.h"
 #include "sepaihrd_sir_device.h"
 
 using namespace sepaihrd;
@@ -30,6 +32,13 @@ struct sepaihrd_sir_ctx {
     double* d_loglik = nullptr;
     int32_t* d_ints = nullptr;  // [3][cap_B] status, accepted, rejected
     double* d_traj = nullptr;
+    // what a device-resident sampler on this context reads (sepaihrd_sir_mh_create, csrc/sepaihrd_mh_backend.h):
+    // SIRParameterManager::applyConstraints as the clamp mode of the propose kernels' constrain() (the table of
+    // sepaihrd_sir_constraint_bounds, constraint_mode 0; uploaded by the first sampler) -- and the libm self-check's result
+    DevProblem mh_dp{};
+    bool mh_dp_ready = false;
+    int libm_log_diff = -1, libm_exp_diff = -1;
+    int no_pending = 0;  // this context has no begin / end evaluation a sampler could collide with
 };
 
 namespace {
@@ -271,6 +280,47 @@ int sepaihrd_sir_apply_constraints(const sepaihrd_sir_ctx* ctx, const double* in
             out[(size_t)b * ctx->P + p] = ctx->field[p] == SEPAIHRD_SIR_F_Q ? std::max(1e-12, v) : std::max(0.0, v);
         }
     return SEPAIHRD_OK;
+}
+
+// The constraint table of a sampler's proposals, for constrain() of the propose kernels in clamp mode.  q: bounded, lower =
+// 1e-12, upper = +inf -- m = (v < lo) ? lo : v, then (hi < m) ? hi : m = m, the value std::max(1e-12, v) returns for every
+// finite v.  scale_C_total and gamma_i: NOT marked bounded, because the kernels' unbounded clamp is (0 < v) ? v : 0 --
+// std::max(0.0, v) as libstdc++ writes it, the sign of a zero included (the bounded form would keep a -0.0 that std::max
+// turns into +0.0).  Their lower / upper entries (0, +inf) say what the rule amounts to.
+int sepaihrd_sir_constraint_bounds(const int32_t* param_field, int n_params, double* lower, double* upper, int32_t* has_bounds) {
+    if (!param_field || n_params < 0 || !lower || !upper) return SEPAIHRD_E_INVALID_ARG;
+    for (int p = 0; p < n_params; ++p) {
+        lower[p] = param_field[p] == SEPAIHRD_SIR_F_Q ? 1e-12 : 0.0;
+        upper[p] = std::numeric_limits<double>::infinity();
+        if (has_bounds) has_bounds[p] = param_field[p] == SEPAIHRD_SIR_F_Q ? 1 : 0;
+    }
+    return SEPAIHRD_OK;
+}
+
+sepaihrd_mh* sepaihrd_sir_mh_create(sepaihrd_sir_ctx* ctx, const sepaihrd_mh_config* config, const double* x0, const double* cov0) {
+    if (!ctx) return nullptr;
+    if (!ctx->mh_dp_ready) {
+        if (hipSetDevice(ctx->device) != hipSuccess) { ctx->last_error = "hipSetDevice failed"; return nullptr; }
+        std::vector<double> lower((size_t)ctx->P), upper((size_t)ctx->P);
+        std::vector<int32_t> bounded((size_t)ctx->P);
+        (void)sepaihrd_sir_constraint_bounds(ctx->field.data(), ctx->P, lower.data(), upper.data(), bounded.data());
+        bool ok = true;
+        DevProblem& d = ctx->mh_dp;
+        d.n = ctx->n; d.lpc = ctx->dp.lpc; d.T = ctx->T; d.P = ctx->P;
+        d.constraint_mode = 0;  // clamp: this manager has no reflect mode
+        d.lower = upload(ctx, lower, ok);
+        d.upper = upload(ctx, upper, ok);
+        d.has_bounds = upload(ctx, bounded, ok);
+        if (!ok) { ctx->last_error = "sir_mh_create: upload of the constraint table failed"; return nullptr; }
+        ctx->mh_dp_ready = true;
+    }
+    return mh_create_on(MhBackend{ctx->device, ctx->P, ctx->last_error, ctx->mh_dp, ctx->libm_log_diff, ctx->libm_exp_diff, ctx->no_pending, nullptr, ctx},
+                        config, x0, cov0);
+}
+
+int sepaihrd_sir_device_libm_check(sepaihrd_sir_ctx* ctx, int32_t* n_log_diff, int32_t* n_exp_diff) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    return device_libm_check(ctx->device, ctx->last_error, ctx->libm_log_diff, ctx->libm_exp_diff, n_log_diff, n_exp_diff);
 }
 
 }  // extern "C"

@@ -92,6 +92,37 @@ def mh_create(lib, ctx, chains: int, iterations: int, x0: np.ndarray, cov0: np.n
     return lib.sepaihrd_mh_create(ctx, C.byref(cfg), x0.ctypes.data, cov0.ctypes.data)
 
 
+MH_FORM_AUTO, MH_FORM_BLOCK_PER_CHAIN, MH_FORM_PACKED = 0, 1, 2  # sepaihrd_mh_set_kernel_form
+
+
+def sir_mh_create(lib, sir_ctx, chains: int, iterations: int, x0: np.ndarray, cov0: np.ndarray, reg_eps: float = 1e-6,
+                  scaling_factor: Optional[float] = None, thinning: int = 1, adaptation_window: int = 0,
+                  covariance_mode: int = MH_COV_RUNNING):
+    """sepaihrd_sir_mh_create: mh_create on the context of a HipSIRObjective (``sir_ctx``).  The handle is the same opaque
+    sampler: every sepaihrd_mh_* entry point and mh_diagnostics take it; its errors are read with sepaihrd_sir_last_error."""
+    P = x0.shape[-1]
+    cfg = sepaihrd_mh_config(chains, iterations, thinning, adaptation_window, covariance_mode, 0, reg_eps,
+                             scaling_factor if scaling_factor is not None else 2.38 * 2.38 / P)
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    cov0 = np.ascontiguousarray(cov0, dtype=np.float64)
+    return lib.sepaihrd_sir_mh_create(sir_ctx, C.byref(cfg), x0.ctypes.data, cov0.ctypes.data)
+
+
+def mh_set_kernel_form(lib, mh, form: int) -> int:
+    """sepaihrd_mh_set_kernel_form (MH_FORM_*); returns the code (0 ok, -1 unknown form / no sampler, -4 packed with P > 64)."""
+    return int(lib.sepaihrd_mh_set_kernel_form(mh, int(form)))
+
+
+def sir_constraint_bounds(lib, param_field) -> tuple:
+    """(lower, upper, has_bounds) of the clamp a SIR-backed sampler applies to its proposals, for field codes SEPAIHRD_SIR_F_*."""
+    f = np.ascontiguousarray(param_field, dtype=np.int32)
+    lo, hi, has = np.empty(f.size), np.empty(f.size), np.empty(f.size, dtype=np.int32)
+    rc = lib.sepaihrd_sir_constraint_bounds(f.ctypes.data, f.size, lo.ctypes.data, hi.ctypes.data, has.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"sepaihrd_sir_constraint_bounds failed ({rc})")
+    return lo, hi, has
+
+
 DIAG_COLUMNS = ("mean", "sd", "mcse_mean", "ess_mean", "ess_bulk", "ess_tail", "r_hat")  # SEPAIHRD_DIAG_COLUMNS, in order
 
 
@@ -128,6 +159,8 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_device_log_values", "sepaihrd_chain_diagnostics", "sepaihrd_mh_diagnostics",
     "sepaihrd_sir_create", "sepaihrd_sir_destroy", "sepaihrd_sir_last_error", "sepaihrd_sir_eval_batch", "sepaihrd_sir_eval_batch_device",
     "sepaihrd_sir_reserve", "sepaihrd_sir_apply_constraints", "sepaihrd_sir_set_arith",
+    "sepaihrd_sir_mh_create", "sepaihrd_sir_device_libm_check", "sepaihrd_sir_constraint_bounds",
+    "sepaihrd_mh_set_kernel_form", "sepaihrd_mh_get_kernel_form",
 )
 
 _lib = None
@@ -238,6 +271,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_sir_reserve.argtypes = [vp, C.c_int]
     lib.sepaihrd_sir_apply_constraints.argtypes = [vp, vp, C.c_int, vp]
     lib.sepaihrd_sir_set_arith.argtypes = [vp, C.c_int]
+    lib.sepaihrd_sir_mh_create.restype = vp
+    lib.sepaihrd_sir_mh_create.argtypes = [vp, C.POINTER(sepaihrd_mh_config), vp, vp]
+    lib.sepaihrd_sir_device_libm_check.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.sepaihrd_sir_constraint_bounds.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.sepaihrd_mh_set_kernel_form.argtypes = [vp, C.c_int]
+    lib.sepaihrd_mh_get_kernel_form.argtypes = [vp]
     if path is None:
         _lib = lib
     return lib
@@ -580,6 +619,12 @@ class HipSIRObjective:
         rc = self.lib.sepaihrd_sir_eval_batch_device(self.ctx, addr(d_theta), B, addr(d_loglik), addr(d_status), addr(d_n_accept),
                                                      addr(d_n_reject), addr(d_traj), stream if stream else None)
         self._check(rc, "sepaihrd_sir_eval_batch_device")
+
+    def device_libm_check(self):
+        """(n_log_diff, n_exp_diff) of the libm self-check, as HipObjective.device_libm_check."""
+        a, b = C.c_int32(-1), C.c_int32(-1)
+        self._check(self.lib.sepaihrd_sir_device_libm_check(self.ctx, C.byref(a), C.byref(b)), "sir_device_libm_check")
+        return a.value, b.value
 
     def apply_constraints(self, theta) -> np.ndarray:
         th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)

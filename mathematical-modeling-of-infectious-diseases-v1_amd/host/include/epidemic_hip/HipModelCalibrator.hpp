@@ -9,6 +9,9 @@
 // objective value of every stored sample (:141-144) in one launch.
 // `chains` > 1 runs that many phase-2 chains in lock-step from the phase-1 optimum (chain c draws
 // from mt19937(seed + c); chain 0 is the reference's single chain).
+// The second constructor is the same flow on the age-structured SIR objective (the reference's CalibrationDemo.cpp:
+// Hill-Climbing, then MetropolisHastingsSampler on PoissonLikelihoodObjective): SIRParameterManager has one constraint rule,
+// so no mode is switched between the phases; a sample whose evaluation fails has the value -infinity, nothing is thrown.
 // The eigen-decomposition the reference takes from Eigen::SelfAdjointEigenSolver is a cyclic Jacobi
 // iteration here (eigenpairs ascending, like Eigen returns them).
 #pragma once
@@ -19,6 +22,7 @@
 
 #include "epidemic_hip/BatchedHillClimbing.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
+#include "epidemic_hip/HipSIR.hpp"
 
 namespace epidemic {
 
@@ -29,6 +33,7 @@ class HipModelCalibrator {
 public:
     // evaluates the initial objective value like the reference's constructor (:36-45)
     HipModelCalibrator(HipSEPAIHRDParameterManager& parameterManager, HipSEPAIHRDObjectiveFunction& objective);
+    HipModelCalibrator(HipSIRParameterManager& parameterManager, HipPoissonLikelihoodObjective& objective);
     // Phase-1 algorithm, as the map the reference's constructor takes under PHASE1_NAME (ModelCalibrator.hpp:60):
     // BatchedHillClimbingOptimizer unless set (runHillClimbingMCMC); BatchedParticleSwarmOptimization gives
     // SEPAIHRDModelCalibration::runPSOMCMC (SEPAIHRDModelCalibration.cpp:179-208).
@@ -48,8 +53,14 @@ public:
     // phase 2's convergence diagnostics (MultiChainMetropolisHastings::diagnostics; settings key compute_diagnostics)
     const ChainDiagnosticsTable& diagnostics() const { return diagnostics_; }
 private:
-    HipSEPAIHRDParameterManager& pm_;
-    HipSEPAIHRDObjectiveFunction& obj_;
+    void init();
+    IParameterManager& pm_;
+    IObjectiveFunction& obj_;
+    IBatchObjectiveFunction& batch_;
+    // the model the pair belongs to: exactly one of the two objectives is set
+    HipSEPAIHRDParameterManager* sep_pm_ = nullptr;
+    HipSEPAIHRDObjectiveFunction* sep_obj_ = nullptr;
+    HipPoissonLikelihoodObjective* sir_obj_ = nullptr;
     std::unique_ptr<IOptimizationAlgorithm> phase1_algo_;
     Eigen::VectorXd best_;
     double best_value_ = 0.0, initial_value_ = 0.0;

@@ -26,6 +26,8 @@
 #include "Interfaces.hpp"
 
 struct sepaihrd_ctx;
+struct sepaihrd_mh;
+struct sepaihrd_mh_config;
 
 namespace epidemic {
 
@@ -238,6 +240,7 @@ struct ChainDiagnosticsTable {
 // target_acceptance_rate, adapt_scale, store_samples).  A seed replaces the reference's
 // std::random_device (build-side addition): chain c draws from std::mt19937(seed + c) with the
 // reference's draw order (fresh normal_distribution per proposal, uniform only when log_ratio < 0).
+class HipPoissonLikelihoodObjective;
 class MultiChainMetropolisHastings : public IOptimizationAlgorithm {
 public:
     void configure(const std::map<std::string, double>& settings) override;
@@ -264,6 +267,15 @@ public:
     std::vector<OptimizationResult> optimizeChainsOnDevice(const std::vector<double>& initial, int C,
                                                            HipSEPAIHRDObjectiveFunction& objective,
                                                            IParameterManager& parameterManager);
+    // The same run on the age-structured SIR objective (HipSIR.hpp; sepaihrd_sir_mh_create): the same loop, reports,
+    // checkpoints, libm fall-back and diagnostics.  Proposals go through SIRParameterManager::applyConstraints on the device.
+    std::vector<OptimizationResult> optimizeChainsOnDevice(const std::vector<double>& initial, int C,
+                                                           HipPoissonLikelihoodObjective& objective,
+                                                           IParameterManager& parameterManager);
+    // form of the sampler's per-iteration kernels in a device-resident run (SEPAIHRD_MH_FORM_*: 0 by measurement, 1 a
+    // workgroup per chain, 2 several chains per wavefront, at most 64 parameters); same bits either way.  Settings key
+    // kernel_form.
+    void setSamplerKernelForm(int form) { sampler_kernel_form_ = form; }
     // optimizeChainsOnDevice for G = objectives.size() contiguous groups of chains, one host thread, one
     // device context and one stream per group: while one group waits for its evaluation the others draw,
     // decide and launch, so the device sees several evaluations in flight (a batch of a few thousand chains
@@ -329,6 +341,15 @@ public:
     double lastDiagnosticsSeconds() const { return diagnostics_seconds_; }  // wall time of forming that table
 private:
     struct Chain;
+    // what a device-resident run needs of its objective's device context: the calls that differ between the two contexts
+    struct DeviceSampler {
+        std::function<int(int32_t*, int32_t*)> libm_check;
+        std::function<sepaihrd_mh*(const sepaihrd_mh_config*, const double*, const double*)> create;
+        std::function<const char*()> last_error;
+        std::function<double*(size_t)> records_buffer;  // where the summary records stay on the device; empty: in the sampler
+    };
+    std::vector<OptimizationResult> runOnDevice(const std::vector<double>& initial, int C, IParameterManager& pm, const DeviceSampler& dev);
+    int sampler_kernel_form_ = 0;
     using BatchEval = std::function<void(const double*, int, double*)>;
     std::vector<OptimizationResult> run(const std::vector<double>& initial, int C, const BatchEval& eval,
                                         IParameterManager& pm);

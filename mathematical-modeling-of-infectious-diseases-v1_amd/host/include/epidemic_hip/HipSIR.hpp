@@ -4,6 +4,9 @@
 //   AgeSIRModel                  include/sir_age_structured/AgeSIRModel.hpp, src/sir_age_structured/AgeSIRModel.cpp
 //   SIRParameterManager          src/sir_age_structured/parameters/SIRParameterManager.cpp
 //   PoissonLikelihoodObjective   src/sir_age_structured/objectives/PoissonLikelihoodObjective.cpp
+// The calibration flow on top of them runs on the device too: MultiChainMetropolisHastings::optimizeChainsOnDevice has an
+// overload for HipPoissonLikelihoodObjective (sepaihrd_sir_mh_create: chains, streams, accept test and adaptation resident
+// in HBM) and HipModelCalibrator a constructor for this pair (HipModelCalibrator.hpp); deviceContext() is what they borrow.
 // Mid-run interventions (applyIntervention through an InterventionCallback) are outside the objective and not scheduled
 // on the device; AgeSIRModel::applyIntervention only changes the host object's values.
 #pragma once
@@ -95,6 +98,9 @@ public:
     const std::vector<std::string>& getParameterNames() const override { return names_; }
     // B evaluations in one launch, no cache; out[b] = -infinity and status[b] = 1 / 2 / 3 for a failed chain, nothing thrown
     void calculateBatch(const double* thetas, int B, double* out, int* status = nullptr) const override;
+    // the context behind this objective, for the callers that keep work on the device
+    // (MultiChainMetropolisHastings::optimizeChainsOnDevice)
+    sepaihrd_sir_ctx* deviceContext() const { return ctx_; }
 private:
     IParameterManager& pm_;
     ISimulationCache& cache_;

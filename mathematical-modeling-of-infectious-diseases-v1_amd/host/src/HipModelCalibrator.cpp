@@ -87,7 +87,16 @@ Eigen::MatrixXd conditionPhase1Covariance(const Eigen::MatrixXd& cov_in, const I
 
 HipModelCalibrator::HipModelCalibrator(HipSEPAIHRDParameterManager& parameterManager,
                                        HipSEPAIHRDObjectiveFunction& objective)
-    : pm_(parameterManager), obj_(objective) {
+    : pm_(parameterManager), obj_(objective), batch_(objective), sep_pm_(&parameterManager), sep_obj_(&objective) {
+    init();
+}
+
+HipModelCalibrator::HipModelCalibrator(HipSIRParameterManager& parameterManager, HipPoissonLikelihoodObjective& objective)
+    : pm_(parameterManager), obj_(objective), batch_(objective), sir_obj_(&objective) {
+    init();
+}
+
+void HipModelCalibrator::init() {
     if (pm_.getParameterNames() != obj_.getParameterNames())  // :32-34
         throw InvalidParameterException("ModelCalibrator", "Parameter names mismatch between ParameterManager and ObjectiveFunction.");
     best_ = pm_.getCurrentParameters();
@@ -101,7 +110,7 @@ void HipModelCalibrator::calibrate(const std::map<std::string, double>& phase1_s
     const int P = static_cast<int>(pm_.getParameterCount());
     const int C = std::max(1, chains);
     // phase 1 (:57-77)
-    pm_.setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);
+    if (sep_pm_) sep_pm_->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);
     if (!phase1_algo_) phase1_algo_ = std::make_unique<BatchedHillClimbingOptimizer>();
     phase1_algo_->configure(phase1_settings);
     phase1_ = phase1_algo_->optimize(best_, obj_, pm_);
@@ -110,7 +119,7 @@ void HipModelCalibrator::calibrate(const std::map<std::string, double>& phase1_s
         best_ = phase1_.bestParameters;
     }
     // phase 2 (:80-146)
-    pm_.setConstraintMode(ConstraintMode::MCMC_REFLECT);
+    if (sep_pm_) sep_pm_->setConstraintMode(ConstraintMode::MCMC_REFLECT);
     MultiChainMetropolisHastings mh;
     mh.configure(phase2_settings);
     auto it = phase2_settings.find("seed");
@@ -122,7 +131,8 @@ void HipModelCalibrator::calibrate(const std::map<std::string, double>& phase1_s
     std::vector<double> init(static_cast<size_t>(C) * P);
     for (int c = 0; c < C; ++c)
         for (int i = 0; i < P; ++i) init[static_cast<size_t>(c) * P + i] = best_[i];
-    phase2_ = mh.optimizeChainsOnDevice(init, C, obj_, pm_);  // sampler state resident in HBM, same numbers
+    // sampler state resident in HBM, same numbers
+    phase2_ = sep_obj_ ? mh.optimizeChainsOnDevice(init, C, *sep_obj_, pm_) : mh.optimizeChainsOnDevice(init, C, *sir_obj_, pm_);
     traces_ = mh.acceptTraces();
     diagnostics_ = mh.diagnostics();  // empty unless phase2_settings has compute_diagnostics != 0
     for (const OptimizationResult& r : phase2_)
@@ -137,7 +147,7 @@ void HipModelCalibrator::calibrate(const std::map<std::string, double>& phase1_s
             for (int i = 0; i < P; ++i) thetas.push_back(smp[i]);
     const int B = static_cast<int>(thetas.size() / static_cast<size_t>(P));
     mcmc_values_.assign(static_cast<size_t>(B), 0.0);
-    if (B > 0) obj_.calculateBatch(thetas.data(), B, mcmc_values_.data());  // throws like calculate() on integration failure
+    if (B > 0) batch_.calculateBatch(thetas.data(), B, mcmc_values_.data());  // SEPAIHRD: throws like calculate() on integration failure
     pm_.updateModelParameters(best_);  // :151
 }
 

@@ -8,6 +8,7 @@
 // and its own std::mt19937.  Host work per iteration is O(C P^2) and runs under OpenMP.
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipChainDiagnostics.hpp"
+#include "epidemic_hip/HipSIR.hpp"
 #include "sepaihrd_hip.h"
 
 #include <sched.h>
@@ -332,6 +333,7 @@ void MultiChainMetropolisHastings::configure(const std::map<std::string, double>
     write_trace_ = get("write_trace", 1.0) != 0.0;
     checkpoint_chains_ = static_cast<int>(get("checkpoint_chains", static_cast<double>(checkpoint_chains_)));
     compute_diagnostics_ = get("compute_diagnostics", compute_diagnostics_ ? 1.0 : 0.0) != 0.0;
+    sampler_kernel_form_ = static_cast<int>(get("kernel_form", static_cast<double>(sampler_kernel_form_)));
 }
 
 OptimizationResult MultiChainMetropolisHastings::optimize(const Eigen::VectorXd& x0, IObjectiveFunction& objective,
@@ -584,6 +586,30 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
     const std::vector<double>& initial, int C, HipSEPAIHRDObjectiveFunction& objective, IParameterManager& pm) {
     if (auto* spm = dynamic_cast<HipSEPAIHRDParameterManager*>(&pm)) spm->setConstraintMode(ConstraintMode::MCMC_REFLECT);  // :207-209
     objective.syncDeviceConstraintMode();
+    sepaihrd_ctx* ctx = objective.deviceContext();
+    DeviceSampler dev;
+    dev.libm_check = [ctx](int32_t* n_log, int32_t* n_exp) { return sepaihrd_device_libm_check(ctx, n_log, n_exp); };
+    dev.create = [ctx](const sepaihrd_mh_config* cfg, const double* x0, const double* cov0) { return sepaihrd_mh_create(ctx, cfg, x0, cov0); };
+    dev.last_error = [ctx]() { return sepaihrd_last_error(ctx); };
+    dev.records_buffer = [ctx](size_t doubles) { return sepaihrd_records_buffer(ctx, 0, doubles); };
+    return runOnDevice(initial, C, pm, dev);
+}
+
+// The SIR objective: SIRParameterManager has one constraint rule (no clamp / reflect switch to synchronise), and the
+// per-chain summary records stay in the sampler (no all-gather across devices for this model).
+std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDevice(
+    const std::vector<double>& initial, int C, HipPoissonLikelihoodObjective& objective, IParameterManager& pm) {
+    sepaihrd_sir_ctx* ctx = objective.deviceContext();
+    DeviceSampler dev;
+    dev.libm_check = [ctx](int32_t* n_log, int32_t* n_exp) { return sepaihrd_sir_device_libm_check(ctx, n_log, n_exp); };
+    dev.create = [ctx](const sepaihrd_mh_config* cfg, const double* x0, const double* cov0) { return sepaihrd_sir_mh_create(ctx, cfg, x0, cov0); };
+    dev.last_error = [ctx]() { return sepaihrd_sir_last_error(ctx); };
+    return runOnDevice(initial, C, pm, dev);
+}
+
+// the loop of both: everything below goes through the sepaihrd_mh handle, whichever context made it
+std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const std::vector<double>& initial, int C, IParameterManager& pm,
+                                                                           const DeviceSampler& dev) {
     const int P = static_cast<int>(pm.getParameterCount());
     if (static_cast<int>(initial.size()) != C * P) throw InvalidParameterException("MetropolisHastingsSampler", "initial size != C*P");
     const double scaling_factor = (2.38 * 2.38) / static_cast<double>(P);
@@ -605,15 +631,14 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
     }
     for (int i = 0; i < P; ++i) cov0[static_cast<size_t>(i) * P + i] += regularization_epsilon_;
 
-    sepaihrd_ctx* ctx = objective.deviceContext();
     Reporter reporter(*this, pm, C);
     // the device may draw the streams only if its log / exp ARE this host's libm (sepaihrd_device_libm_check)
     bool device_streams = this->device_streams_;
     device_streams_fell_back_ = false;
     if (device_streams) {
         int32_t n_log = 0, n_exp = 0;
-        if (sepaihrd_device_libm_check(ctx, &n_log, &n_exp) != SEPAIHRD_OK)
-            throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_device_libm_check: ") + sepaihrd_last_error(ctx));
+        if (dev.libm_check(&n_log, &n_exp) != SEPAIHRD_OK)
+            throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_device_libm_check: ") + dev.last_error());
         if (n_log != 0 || n_exp != 0) {
             device_streams = false;
             device_streams_fell_back_ = true;
@@ -631,12 +656,13 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
     mcfg.covariance_mode = two_pass_covariance_ ? SEPAIHRD_MH_COV_TWO_PASS : SEPAIHRD_MH_COV_RUNNING;
     mcfg.reg_eps = regularization_epsilon_;
     mcfg.scaling_factor = scaling_factor;
-    sepaihrd_mh* mh = sepaihrd_mh_create(ctx, &mcfg, initial.data(), cov0.data());
-    if (!mh) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_mh_create: ") + sepaihrd_last_error(ctx));
+    sepaihrd_mh* mh = dev.create(&mcfg, initial.data(), cov0.data());
+    if (!mh) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_mh_create: ") + dev.last_error());
     struct Guard { sepaihrd_mh* p; ~Guard() { sepaihrd_mh_destroy(p); } } guard{mh};
     auto check = [&](int rc, const char* what) {
-        if (rc != SEPAIHRD_OK) throw ModelException("MetropolisHastingsSampler", std::string(what) + ": " + sepaihrd_last_error(ctx));
+        if (rc != SEPAIHRD_OK) throw ModelException("MetropolisHastingsSampler", std::string(what) + ": " + dev.last_error());
     };
+    check(sepaihrd_mh_set_kernel_form(mh, sampler_kernel_form_), "mh_set_kernel_form");
 
     // What the host keeps per chain.  The random stream is consumed in the reference's order: the normals of a
     // proposal, then ONE uniform only if log_ratio < 0 (:327), then the next proposal's normals.  While the device
@@ -935,8 +961,11 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
         // context's records buffer for a later all-gather, copied here
         int first = burn_in_ / thinning_ + 1;
         if (first >= ns) first = 0;
-        double* d_rec = sepaihrd_records_buffer(ctx, 0, static_cast<size_t>(C) * summary_width_);
-        if (!d_rec) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_records_buffer: ") + sepaihrd_last_error(ctx));
+        double* d_rec = nullptr;  // null: the records stay in the sampler's own buffer
+        if (dev.records_buffer) {
+            d_rec = dev.records_buffer(static_cast<size_t>(C) * summary_width_);
+            if (!d_rec) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_records_buffer: ") + dev.last_error());
+        }
         summary_records_.resize(static_cast<size_t>(C) * summary_width_);
         check(sepaihrd_mh_summary_records(mh, first, summary_records_.data(), d_rec), "mh_summary_records");
         if (compute_diagnostics_) {

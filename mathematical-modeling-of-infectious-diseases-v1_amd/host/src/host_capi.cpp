@@ -1135,4 +1135,103 @@ int host_sir_mh_run(void* hv, int C, const double* initial, uint32_t seed, int i
     }
 }
 
+// The SIR sampler through EITHER path -- device_state = 0: the host loop optimizeChains above (every iteration through the
+// host-pointer calculateBatch); 1: optimizeChainsOnDevice (sepaihrd_sir_mh_create) -- with what host_mh_run returns:
+// accepted[C], best_value[C], best[C*P], final_scale[C], accept_trace[C*(iterations-1)] or NULL, n_samples, samples
+// [C*n_samples*P], sample_values[C*n_samples], final_cov[C*P*P].  kernel_form: SEPAIHRD_MH_FORM_* (device_state only).
+// dir != NULL switches the reference's progress reports and trace files on (lines into log_path, files into dir).
+// fell_back: the libm self-check refused the device streams; failures[3]: evaluations the accept tests saw fail;
+// diag_out [P + 1][7] with *diag_rows when compute_diagnostics (0 rows: no table).
+int host_sir_mh_run_ex(void* hv, int C, const double* initial, uint32_t seed, int iterations, int burn_in, int adaptation_period, int thinning,
+                       double reg_eps, double target_acc, int adapt_scale, int device_state, int device_streams, int two_pass_covariance,
+                       int adaptation_window, int kernel_form, int compute_diagnostics, int report_interval, int checkpoint_chains,
+                       const char* dir, const char* log_path, int32_t* accepted, double* best_value, double* best, double* final_scale,
+                       unsigned char* accept_trace, int32_t* n_samples, double* samples, double* sample_values, double* final_cov,
+                       int* fell_back, long* failures, double* diag_out, int32_t* diag_rows) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        const int P = static_cast<int>(h->pm->getParameterCount());
+        const bool reported = dir != nullptr;
+        MultiChainMetropolisHastings mh;
+        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", reported ? double(report_interval) : 0.0},
+                      {"write_checkpoints", reported ? 1.0 : 0.0}, {"write_trace", reported ? 1.0 : 0.0},
+                      {"checkpoint_chains", double(std::max(checkpoint_chains, 1))}, {"burn_in", double(burn_in)},
+                      {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
+                      {"regularization_epsilon", reg_eps}, {"target_acceptance_rate", target_acc}, {"adapt_scale", double(adapt_scale)},
+                      {"store_samples", 1.0}, {"two_pass_covariance", double(two_pass_covariance)},
+                      {"adaptation_window", double(adaptation_window)}, {"device_streams", double(device_streams)},
+                      {"keep_accept_traces", accept_trace ? 1.0 : 0.0}, {"compute_diagnostics", compute_diagnostics ? 1.0 : 0.0},
+                      {"kernel_form", double(kernel_form)}});
+        mh.setSeed(seed);
+        std::ofstream log;
+        if (reported) {
+            mh.setOutputDirectory(dir);
+            if (log_path) {
+                log.open(log_path);
+                mh.setProgressSink([&log](const std::string& level, const std::string& msg) { log << level << " " << msg << std::endl; });
+            }
+        }
+        const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
+        const std::vector<OptimizationResult> res = device_state ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm)
+                                                                 : mh.optimizeChains(init, C, *h->obj, *h->pm);
+        g_last_mh_loop_seconds = mh.lastLoopSeconds();
+        const int ns = static_cast<int>(res[0].samples.size());
+        if (n_samples) *n_samples = ns;
+        for (int c = 0; c < C; ++c) {
+            const OptimizationResult& r = res[static_cast<size_t>(c)];
+            if (accept_trace)
+                std::copy(mh.acceptTraces()[static_cast<size_t>(c)].begin(), mh.acceptTraces()[static_cast<size_t>(c)].end(),
+                          accept_trace + static_cast<size_t>(c) * (iterations - 1));
+            if (accepted) accepted[c] = static_cast<int32_t>(r.additionalStats.at("accepted_count"));
+            if (best_value) best_value[c] = r.bestObjectiveValue;
+            if (final_scale) final_scale[c] = r.additionalStats.at("final_scale");
+            if (best) for (int i = 0; i < P; ++i) best[static_cast<size_t>(c) * P + i] = r.bestParameters[i];
+            for (int s = 0; s < ns; ++s) {
+                if (samples) for (int i = 0; i < P; ++i) samples[(static_cast<size_t>(c) * ns + s) * P + i] = r.samples[static_cast<size_t>(s)][i];
+                if (sample_values) sample_values[static_cast<size_t>(c) * ns + s] = r.sampleObjectiveValues[static_cast<size_t>(s)];
+            }
+            if (final_cov)
+                for (int i = 0; i < P; ++i)
+                    for (int j = 0; j < P; ++j) final_cov[(static_cast<size_t>(c) * P + i) * P + j] = r.finalCovariance(i, j);
+        }
+        if (fell_back) *fell_back = mh.deviceStreamsFellBack() ? 1 : 0;
+        if (failures)
+            for (size_t k = 0; k < 3; ++k) failures[k] = device_state && k < mh.failureCounts().size() ? mh.failureCounts()[k] : 0;
+        const ChainDiagnosticsTable& t = mh.diagnostics();
+        if (diag_rows) *diag_rows = device_state ? t.rows : 0;
+        if (diag_out && device_state) std::copy(t.values.begin(), t.values.end(), diag_out);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// HipModelCalibrator on the SIR objective (CalibrationDemo.cpp's flow): Hill-Climbing, covariance conditioning, `chains`
+// device-resident Metropolis-Hastings chains from the phase-1 optimum, the objective value of every stored sample.
+// Outputs as host_calibrate.
+int host_sir_calibrate(void* hv, int hc_iterations, int cloud_size_multiplier, int threads, uint32_t hc_seed, int mh_iterations, int burn_in,
+                       int adaptation_period, int thinning, uint32_t mh_seed, int chains, int kernel_form, int device_streams, double* best,
+                       double* best_value, double* initial_value, double* phase1_best_value, double* phase2_cov, unsigned char* accept_trace,
+                       double* samples, double* sample_values, double* mcmc_objective_values, int32_t* n_samples) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        const int P = static_cast<int>(h->pm->getParameterCount());
+        HipModelCalibrator cal(*h->pm, *h->obj);
+        cal.calibrate({{"iterations", double(hc_iterations)}, {"cloud_size_multiplier", double(cloud_size_multiplier)},
+                       {"threads", double(threads)}, {"seed", double(hc_seed)}},
+                      {{"mcmc_iterations", double(mh_iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0},
+                       {"burn_in", double(burn_in)}, {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
+                       {"seed", double(mh_seed)}, {"store_samples", 1.0}, {"kernel_form", double(kernel_form)},
+                       {"device_streams", double(device_streams)}},
+                      chains);
+        copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace, samples,
+                         sample_values, mcmc_objective_values, n_samples);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
 }  // extern "C"

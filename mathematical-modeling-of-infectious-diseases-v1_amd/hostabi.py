@@ -79,6 +79,12 @@ def load_library() -> C.CDLL:
     lib.host_sir_cache_stats.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
     lib.host_sir_hc_run.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)]
     lib.host_sir_mh_run.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
+    lib.host_sir_mh_run_ex.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double] + \
+        [C.c_int] * 9 + [C.c_char_p, C.c_char_p] + [vp] * 4 + [vp, C.POINTER(C.c_int32), vp, vp, vp, C.POINTER(C.c_int),
+                                                             C.POINTER(C.c_long), vp, C.POINTER(C.c_int32)]
+    lib.host_sir_calibrate.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                       C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_double), vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     _lib = lib
     return lib
 
@@ -627,3 +633,65 @@ class HostSIRObjective:
                                     acc.ctypes.data) != 0:
             raise RuntimeError("host_sir_mh_run: " + self.lib.host_last_error().decode())
         return {"best_value": bv, "best": best, "accepted": acc}
+
+    def metropolis_hastings_ex(self, initial, seed: int, iterations: int, burn_in: int = 0, adaptation_period: int = 100,
+                               thinning: int = 1, reg_eps: float = 1e-6, target_acc: float = 0.234, adapt_scale: bool = True,
+                               device_state: bool = True, device_streams: bool = True, two_pass_covariance: bool = False,
+                               kernel_form: int = 0, want_trace: bool = True, adaptation_window: int = 0,
+                               compute_diagnostics: bool = False, out_dir: str | None = None, log_path: str | None = None,
+                               report_interval: int = 100, checkpoint_chains: int = 1) -> dict:
+        """MultiChainMetropolisHastings on the SIR objective through either path: the host loop optimizeChains
+        (device_state=False: every iteration through the host-pointer calculateBatch) or the device-resident sampler
+        (sepaihrd_sir_mh_create).  Returns the dictionary HostObjective.metropolis_hastings returns, plus fell_back (the libm
+        self-check refused the device streams), failures [3] and, with compute_diagnostics, diagnostics [P + 1][7].
+        kernel_form: hipabi.MH_FORM_*.  out_dir switches the reference's progress reports and trace files on."""
+        x0 = np.ascontiguousarray(np.atleast_2d(initial), dtype=np.float64)
+        Cn, P = x0.shape
+        accepted = np.zeros(Cn, dtype=np.int32)
+        best_value, final_scale = np.zeros(Cn), np.zeros(Cn)
+        best = np.zeros((Cn, P))
+        trace = np.zeros((Cn, max(iterations - 1, 1)), dtype=np.uint8) if want_trace else None
+        n_s = 1 + (max(iterations, 1) - 1) // max(1, thinning)
+        samples, values, cov = np.zeros((Cn, n_s, P)), np.zeros((Cn, n_s)), np.zeros((Cn, P, P))
+        ns, fb, drows = C.c_int32(), C.c_int(), C.c_int32()
+        failures = (C.c_long * 3)()
+        diag = np.zeros((P + 1, len(hipabi.DIAG_COLUMNS)))
+        rc = self.lib.host_sir_mh_run_ex(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning, reg_eps,
+                                         target_acc, int(adapt_scale), int(device_state), int(device_streams), int(two_pass_covariance),
+                                         int(adaptation_window), int(kernel_form), int(compute_diagnostics), int(report_interval),
+                                         int(checkpoint_chains), out_dir.encode() if out_dir else None,
+                                         log_path.encode() if log_path else None, accepted.ctypes.data, best_value.ctypes.data,
+                                         best.ctypes.data, final_scale.ctypes.data, trace.ctypes.data if want_trace else None,
+                                         C.byref(ns), samples.ctypes.data, values.ctypes.data, cov.ctypes.data, C.byref(fb), failures,
+                                         diag.ctypes.data, C.byref(drows))
+        if rc:
+            raise RuntimeError("host_sir_mh_run_ex: " + self.lib.host_last_error().decode())
+        assert ns.value == n_s
+        return {"accepted": accepted, "best_value": best_value, "best": best, "final_scale": final_scale,
+                "accept_trace": trace[:, :iterations - 1] if want_trace else None, "samples": samples, "sample_values": values,
+                "final_cov": cov, "loop_seconds": float(self.lib.host_last_mh_loop_seconds()), "fell_back": bool(fb.value),
+                "failures": list(failures), "diagnostics": diag[:drows.value] if drows.value else None}
+
+    def calibrate(self, hc_seed: int, mh_seed: int, hc_iterations: int, mh_iterations: int, burn_in: int,
+                  cloud_size_multiplier: int = 8, threads: int = 16, adaptation_period: int = 100, thinning: int = 1,
+                  chains: int = 1, kernel_form: int = 0, device_streams: bool = True) -> dict:
+        """HipModelCalibrator on the SIR objective: Hill-Climbing from the manager's current parameters -> covariance
+        conditioning -> `chains` device-resident MH chains -> the objective value of every stored sample.  The dictionary of
+        HostObjective.calibrate."""
+        cap = 1 + (mh_iterations - 1) // max(1, thinning)
+        out = {"best": np.empty(self.P), "phase2_cov": np.empty((self.P, self.P)),
+               "accept_trace": np.empty((chains, mh_iterations - 1), dtype=np.uint8),
+               "samples": np.empty((chains, cap, self.P)), "sample_values": np.empty((chains, cap)),
+               "mcmc_objective_values": np.empty((chains, cap))}
+        bv, iv, p1 = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        ns = C.c_int32(0)
+        rc = self.lib.host_sir_calibrate(self.h, hc_iterations, cloud_size_multiplier, threads, hc_seed, mh_iterations, burn_in,
+                                         adaptation_period, thinning, mh_seed, chains, int(kernel_form), int(device_streams),
+                                         out["best"].ctypes.data, C.byref(bv), C.byref(iv), C.byref(p1),
+                                         out["phase2_cov"].ctypes.data, out["accept_trace"].ctypes.data, out["samples"].ctypes.data,
+                                         out["sample_values"].ctypes.data, out["mcmc_objective_values"].ctypes.data, C.byref(ns))
+        if rc != 0:
+            raise RuntimeError("host_sir_calibrate: " + self.lib.host_last_error().decode())
+        assert ns.value == cap, (ns.value, cap)
+        out.update(best_value=bv.value, initial_value=iv.value, phase1_best_value=p1.value, n_samples=ns.value)
+        return out
