@@ -667,6 +667,71 @@ int sepaihrd_mh_set_kernel_form(sepaihrd_mh *mh, int form);
 /* the form in use (AUTO resolved): SEPAIHRD_MH_FORM_BLOCK_PER_CHAIN or _PACKED; NULL: SEPAIHRD_E_INVALID_ARG */
 int sepaihrd_mh_get_kernel_form(const sepaihrd_mh *mh);
 
+/* ---- age-structured SIR: posterior ensemble and intervention scenarios (additive; SEPAIHRD_ABI_VERSION stays) --------------
+ * S posterior samples under K intervention scenarios in ONE integrator launch of K x S chains (the ensemble build of
+ * csrc/sepaihrd_sir.hip), then per-scenario quantile bands, a per-sample metric table, metric summaries and paired
+ * differences against scenario 0.  Full trajectories are never materialised.
+ *
+ * A scenario is a list of at most SEPAIHRD_SIR_MAX_EVENTS events sorted by time_index (ties apply in listed order);
+ * time_index is an index of the problem's output grid times[] -- interventions act on grid times only.  Kinds, after
+ * AgeSIRModel::applyIntervention (src/sir_age_structured/AgeSIRModel.cpp:141-173):
+ *   SEPAIHRD_SIR_EV_CONTACT       scale_C_total <- scale_C_total * value, value >= 0
+ *                                 ("contact_reduction" / "social_distancing" / "lockdown")
+ *   SEPAIHRD_SIR_EV_TRANSMISSION  q <- q * (1 - value), 0 <= value <= 1  ("mask_mandate" / "transmission_reduction")
+ * Events compound as repeated applyIntervention calls do; after a contact event C_current is re-formed as C_ij * scale (what a
+ * model constructed with the new scale_C_total holds).  An event at index k > 0: the chain integrates to times[k] with the old
+ * parameters, the row observed there (state and incidence) is formed with the old parameters, then the parameters change
+ * and the integrator restarts as a fresh integrate_times call would (dt = dt_hint, no consecutive failures, Dopri5's FSAL
+ * derivative recomputed); max_attempts and the step counters run over the whole chain.  An event at index 0 is applied before
+ * the first observation (= a plain run with the changed parameters); one at index T - 1 is legal and changes nothing.
+ * Scenario 0 may be empty: the baseline. */
+#define SEPAIHRD_SIR_MAX_EVENTS 8
+#define SEPAIHRD_SIR_EV_CONTACT 0
+#define SEPAIHRD_SIR_EV_TRANSMISSION 1
+typedef struct sepaihrd_sir_event {
+    int32_t time_index, kind;
+    double value;
+} sepaihrd_sir_event;
+/* The check both entry points below run before any device work, host only (no device, no context): events
+ * [K][SEPAIHRD_SIR_MAX_EVENTS], n_events [K], n_times = T.  SEPAIHRD_E_INVALID_ARG with a message naming the offending
+ * scenario and event in err (NULL: not wanted) for: more than 8 events (or a negative count), a time_index outside [0, T),
+ * unsorted events, an unknown kind, a value out of its kind's range or non-finite. */
+int sepaihrd_sir_validate_events(const sepaihrd_sir_event *events, const int32_t *n_events, int K, int n_times, char *err, int errlen);
+/* theta [S][P] (host).  Every output is host memory and may be NULL:
+ *   quantiles      [K][3][n_probs][T][n_age + 1]  series 0 incidence max(q (C_current (I / N))_i, 0) S_i(t) with the
+ *                  parameters in force for that row and none of the likelihood's 1e-9 floor
+ *                  (SimulationResultProcessor.cpp:144-189), 1 prevalence I_i(t), 2 cumulative infections S_i(t0) - S_i(t);
+ *                  column n_age is the age total (ages added in ascending order).  Quantile rule of
+ *                  sepaihrd_ensemble_quantiles: exact sort, linear interpolation at q (n_valid - 1), failed samples of
+ *                  that scenario skipped, NaN when none is valid
+ *   metrics        [K][S][6 + 2 n_age]  0 R0 = spectral radius of K_ij = q scale C_ij N_i / (N_j gamma_j) with the sample's
+ *                  parameters before any event (columns with N_j <= 1e-9 dropped, gamma_j = 0: +inf); 1 peak total
+ *                  prevalence over the output times, 2 its output time (first maximal row); 3 peak total incidence, 4 its
+ *                  output time; 5 overall attack rate sum_i (S_i(t0) - S_i(t_last)) / sum N; then per age: attack rate
+ *                  (S_i(t0) - S_i(t_last)) / N_i (0 where N_i <= 0), peak prevalence.  NaN row for a failed sample
+ *   metric_summary [K][W][2 + n_probs]  mean, population standard deviation, quantiles (W = 6 + 2 n_age)  } the rules of
+ *   diff_quantiles [K][W][n_probs]  quantiles of metric[k][s] - metric[0][s] over samples valid in both     } sepaihrd_scenario_ensemble
+ *   status         [K][S]  0, 1 (non-finite incidence), 2 (step failure), 3 (step budget)
+ *   n_accept, n_reject [K][S]  step counts over the whole chain
+ *   n_valid        [K]
+ * K = 1 with no events gives the trajectories of sepaihrd_sir_eval_batch bit for bit.  A failed sample never fails the call.
+ * SEPAIHRD_E_INVALID_ARG: a bad event table (sepaihrd_sir_validate_events; the device is not touched), probabilities outside
+ * [0, 1], K x S beyond a 32-bit chain count or the device's memory (dominant: K 3 T (n_age + 1) S_pad doubles);
+ * SEPAIHRD_E_HIP ("device allocation failed") when it fits the device but not its free memory.  Scratch stays with the
+ * context and is reused.  Up to 16384 samples a segment is sorted in LDS, beyond by a segmented radix sort. */
+int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx *ctx, const double *theta, int S, const sepaihrd_sir_event *events,
+                                   const int32_t *n_events, int K, const double *probs, int n_probs, double *quantiles,
+                                   double *metrics, double *metric_summary, double *diff_quantiles, int32_t *status,
+                                   int32_t *n_accept, int32_t *n_reject, int32_t *n_valid);
+/* K = 1, no events: quantiles [3][n_probs][T][n_age + 1], metrics [S][W], metric_summary [W][2 + n_probs], status [S],
+ * n_valid [1] */
+int sepaihrd_sir_ensemble_quantiles(sepaihrd_sir_ctx *ctx, const double *theta, int S, const double *probs, int n_probs,
+                                    double *quantiles, double *metrics, double *metric_summary, int32_t *status, int32_t *n_valid);
+/* Calls of the two entry points above that reached the device on this context (calls, NULL: not wanted) and the device time
+ * of the last one in milliseconds (ms[3], NULL: not wanted): integrator; fix-up and metric passes; sorts, quantiles and
+ * scenario summaries. */
+int sepaihrd_sir_ensemble_timing(const sepaihrd_sir_ctx *ctx, int64_t *calls, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_sir_device.h"
 
 namespace sepaihrd {
 namespace {
@@ -544,6 +545,141 @@ int sort_segments_global(const double* vals, int segments, int S_pad, double* sc
     return (rc == 0 && hipGetLastError() == hipSuccess) ? 0 : -3;
 }
 
+// ---- age-structured SIR: posterior ensemble and intervention scenarios (sepaihrd_sir_scenario_ensemble) ----
+// The ensemble build of the SIR integrator (csrc/sepaihrd_sir.hip) has stored the series of every valid chain in
+// vals[((k 3 + series) T + t) (n + 1) + column][S_pad].  Fix-up: the rows of samples that failed (at any point of the run)
+// and of the padding s >= S become +inf, so they sort last.  One thread per (scenario, sample) and block of rows; threads
+// of valid samples leave at once.  The scenario is folded into the grid's x dimension (K is bounded by the chain count, not
+// by 65 535) and the row blocks go round the y dimension.
+constexpr int SIR_FIX_ROWS = 64;
+__global__ __launch_bounds__(256) void sir_ens_fixup_kernel(const SirEnsSummaryArgs a) {
+    const int xblocks = (a.S_pad + 255) / 256;
+    const int k = blockIdx.x / xblocks;
+    const int s = (blockIdx.x % xblocks) * 256 + threadIdx.x;
+    if (s >= a.S_pad) return;
+    if (s < a.S && a.status[(size_t)k * a.S + s] == 0) return;
+    const int rows = SIR_ENS_SERIES * a.T * (a.n + 1);
+    double* col = a.vals + (size_t)k * rows * a.S_pad + s;
+    for (int r0 = blockIdx.y * SIR_FIX_ROWS; r0 < rows; r0 += gridDim.y * SIR_FIX_ROWS) {
+        const int r1 = (r0 + SIR_FIX_ROWS < rows) ? r0 + SIR_FIX_ROWS : rows;
+        for (int r = r0; r < r1; ++r) col[(size_t)r * a.S_pad] = INFINITY;
+    }
+}
+
+// R0 of every sample: spectral radius of K_ij = q scale C_ij N_i / (N_j gamma_j) with the sample's parameters before any event
+// (columns with N_j <= 1e-9 dropped, gamma_j = 0: +inf), by Perron iteration in the max-norm with the stopping rule of
+// ensemble_rt_kernel.  Mapped as the integrator maps a chain: one lane per (sample, age), lpc lanes per sample, 64 / lpc
+// samples per one-wavefront block; the baseline matrix sits in LDS, the iterate goes round through LDS.  A sample's iteration
+// is frozen at the first iteration that meets the rule; the block runs until all of its samples have.
+constexpr int SIR_MAX_AGE = 64;
+__global__ __launch_bounds__(WAVE) void sir_ens_r0_kernel(const SirEnsSummaryArgs a, const SirDevProblem pb, double* r0_out) {
+    extern __shared__ double r0_lds[];  // [lpc][lpc] C, [WAVE] g_j v_j
+    const int lpc = pb.lpc, n = pb.n, lane = threadIdx.x;
+    double* sC = r0_lds;
+    double* su = r0_lds + lpc * lpc;
+    for (int i = lane; i < lpc * lpc; i += WAVE) sC[i] = pb.C[i];
+    const int cpw = WAVE / lpc;
+    const int age = lane % lpc, grp = lane / lpc;
+    const int s_raw = blockIdx.x * cpw + grp;
+    const bool valid = s_raw < a.S;
+    const int s = valid ? s_raw : 0;
+    // SIRParameterManager::applyConstraints + updateModelParameters, as the integrator's prologue
+    double q = pb.q, scale = pb.scale, gamma = pb.gamma[age];
+    const double* th = a.theta + (size_t)s * pb.P;
+    for (int p = 0; p < pb.P; ++p) {
+        const int f = pb.param_field[p];
+        const double x = th[p];
+        if (f == 0) q = (1e-12 < x) ? x : 1e-12;
+        else if (f == 1) scale = (0.0 < x) ? x : 0.0;
+        else if (pb.param_index[p] == age) gamma = (0.0 < x) ? x : 0.0;
+    }
+    const double Ni = pb.N[age];
+    const bool has_pop = age < n && Ni > 1e-9;
+    const double ci = q * scale * Ni;
+    const double gj = has_pop ? 1.0 / (Ni * gamma) : 0.0;
+    su[lane] = (has_pop && gamma == 0.0) ? 1.0 : 0.0;
+    __syncthreads();
+    bool unbounded = false;
+    for (int j = 0; j < lpc; ++j) unbounded |= su[grp * lpc + j] != 0.0;
+    double v = 1.0, r0 = 0.0;
+    bool done = unbounded;
+    for (int it = 0; it < 2000; ++it) {
+        if (__ballot(!done) == 0ull) break;
+        __syncthreads();  // the readers of the previous iterate are done
+        su[lane] = gj * v;
+        __syncthreads();
+        double acc = 0.0;
+        for (int j = 0; j < n; ++j) acc += ci * sC[age * lpc + j] * su[grp * lpc + j];
+        if (age >= n) acc = 0.0;
+        __syncthreads();
+        su[lane] = acc;
+        __syncthreads();
+        double m = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double w = su[grp * lpc + j];
+            m = (w > m) ? w : m;
+        }
+        if (!done) {
+            if (!(m > 0.0)) {
+                r0 = 0.0;
+                done = true;
+            } else {
+                v = acc / m;
+                done = fabs(m - r0) <= 1e-15 * m;
+                r0 = m;
+            }
+        }
+    }
+    if (valid && age == 0) r0_out[s] = unbounded ? (double)INFINITY : r0;
+}
+
+// Per-sample metrics of scenario k from the stored series and R0, one thread per (scenario, sample).  Row layout:
+//   [0] R0  [1] peak total prevalence  [2] its output time  [3] peak total incidence  [4] its output time
+//   [5] overall attack rate sum_i (S_i(t0) - S_i(t_last)) / sum N, then per age: attack rate, peak prevalence
+// R0 is the sample's (sir_ens_r0_kernel), whatever the scenario.  Peaks: the first maximal row counts.  The per-age peaks are
+// one more walk over the output times per age (the same loads, coalesced over the samples), so nothing is indexed at run time
+// and nothing lives in scratch.  The scenario is folded into the grid's x dimension, as in the fix-up.
+__global__ __launch_bounds__(WAVE) void sir_ens_metrics_kernel(const SirEnsSummaryArgs a, const SirDevProblem pb, const double* r0_in) {
+    const int sblocks = (a.S + WAVE - 1) / WAVE;
+    const int k = blockIdx.x / sblocks;
+    const int s = (blockIdx.x % sblocks) * WAVE + threadIdx.x;
+    if (s >= a.S) return;
+    const int n = a.n, T = a.T, width = SIR_ENS_SCALARS + 2 * n;
+    double* out = a.metrics + ((size_t)k * a.S + s) * width;
+    if (a.status[(size_t)k * a.S + s] != 0) {
+        for (int i = 0; i < width; ++i) out[i] = NAN;
+        return;
+    }
+    double total_pop = 0.0;
+    for (int i = 0; i < n; ++i) total_pop += pb.N[i];
+    const size_t row = (size_t)(n + 1) * a.S_pad;  // doubles between output times
+    const double* inc = a.vals + ((size_t)(k * SIR_ENS_SERIES + 0) * T) * row + s;
+    const double* prev = a.vals + ((size_t)(k * SIR_ENS_SERIES + 1) * T) * row + s;
+    const double* cumi = a.vals + ((size_t)(k * SIR_ENS_SERIES + 2) * T) * row + s;
+    double peak_prev = prev[(size_t)n * a.S_pad], peak_inc = inc[(size_t)n * a.S_pad];
+    int k_prev = 0, k_inc = 0;
+    for (int t = 1; t < T; ++t) {
+        const double tp = prev[(size_t)t * row + (size_t)n * a.S_pad], ti = inc[(size_t)t * row + (size_t)n * a.S_pad];
+        if (tp > peak_prev) { peak_prev = tp; k_prev = t; }
+        if (ti > peak_inc) { peak_inc = ti; k_inc = t; }
+    }
+    const double* last = cumi + (size_t)(T - 1) * row;
+    out[0] = r0_in[s];
+    out[1] = peak_prev; out[2] = pb.times[k_prev];
+    out[3] = peak_inc; out[4] = pb.times[k_inc];
+    out[5] = last[(size_t)n * a.S_pad] / total_pop;
+    for (int i = 0; i < n; ++i) {
+        const double* pa = prev + (size_t)i * a.S_pad;
+        double w = pa[0];  // peak prevalence of age i
+        for (int t = 1; t < T; ++t) {
+            const double x = pa[(size_t)t * row];
+            w = (x > w) ? x : w;
+        }
+        out[SIR_ENS_SCALARS + 2 * i] = (pb.N[i] > 0) ? last[(size_t)i * a.S_pad] / pb.N[i] : 0.0;
+        out[SIR_ENS_SCALARS + 2 * i + 1] = w;
+    }
+}
+
 }  // namespace
 
 int launch_scenario_summaries(const ScenarioArgs& a, void* stream) {
@@ -611,6 +747,68 @@ int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
         return -3;
     hipLaunchKernelGGL(ensemble_quantile_kernel, dim3(segments), dim3(threads), lds, st, a, n_series_segments);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace sepaihrd
+
+namespace sepaihrd {
+
+int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool in_lds = a.S_pad <= ENSEMBLE_MAX_SAMPLES;
+    if (a.K <= 0 || a.S <= 0 || a.n < 1 || a.n > SIR_MAX_AGE || a.T < 1 || a.S_pad < WAVE || a.S > a.S_pad ||
+        (in_lds ? (a.S_pad & (a.S_pad - 1)) != 0 : a.S_pad % WAVE != 0))
+        return -4;
+    const int rows = SIR_ENS_SERIES * a.T * (a.n + 1);  // sortable segments per scenario
+    // K x S fits a 32-bit chain count (checked by the caller), so K x (blocks of samples) fits the grid's x dimension
+    const int row_blocks = (rows + SIR_FIX_ROWS - 1) / SIR_FIX_ROWS;
+    hipLaunchKernelGGL(sir_ens_fixup_kernel, dim3((unsigned)((a.S_pad + 255) / 256) * (unsigned)a.K, (unsigned)(row_blocks < 65535 ? row_blocks : 65535)),
+                       dim3(256), 0, st, a);
+    if (a.metrics != nullptr) {
+        const int cpw = WAVE / a.lpc;
+        hipLaunchKernelGGL(sir_ens_r0_kernel, dim3((unsigned)((a.S + cpw - 1) / cpw)), dim3(WAVE), (size_t)(a.lpc * a.lpc + WAVE) * sizeof(double), st,
+                           a, *a.pb, a.r0);
+        hipLaunchKernelGGL(sir_ens_metrics_kernel, dim3((unsigned)((a.S + WAVE - 1) / WAVE) * (unsigned)a.K), dim3(WAVE), 0, st, a, *a.pb, a.r0);
+    }
+    if (a.ev_after_metrics != nullptr && hipEventRecord(static_cast<hipEvent_t>(a.ev_after_metrics), st) != hipSuccess) return -3;
+    // the series' quantiles: the segment sort and the interpolation of sepaihrd_ensemble_quantiles, per scenario (each has
+    // its own count of valid samples), with (T, n + 1) in the place of (Tp, n) and no seroprevalence / Rt block
+    const int threads = a.S_pad / 2 < 1024 ? a.S_pad / 2 : 1024;
+    const size_t lds = (size_t)a.S_pad * sizeof(double);
+    if (in_lds && lds > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+        return -3;
+    for (int k = 0; k < a.K; ++k) {
+        EnsembleArgs e{};
+        e.S = a.S; e.S_pad = a.S_pad; e.lpc = a.lpc; e.n = a.n + 1; e.T = a.T; e.Tp = a.T;
+        e.n_probs = a.n_probs; e.probs = a.probs;
+        e.vals = a.vals + (size_t)k * rows * a.S_pad;
+        e.q_out = a.q_out + (size_t)k * SIR_ENS_SERIES * a.n_probs * a.T * (a.n + 1);
+        e.n_valid = a.n_valid + k;
+        e.rt_segment0 = rows;
+        hipLaunchKernelGGL(ensemble_count_valid_kernel, dim3(1), dim3(256), 0, st, a.status + (size_t)k * a.S, a.S, e.n_valid);
+        if (a.q_out == nullptr) continue;
+        if (!in_lds) {
+            const int rc = sort_segments_global(e.vals, rows, a.S_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
+                const size_t work = (size_t)ng * a.n_probs;
+                hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, e, rows,
+                                   a.sort_scratch, first, ng);
+            });
+            if (rc != 0) return rc;
+        } else {
+            hipLaunchKernelGGL(ensemble_quantile_kernel, dim3(rows), dim3(threads), lds, st, e, rows);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return -3;
+    if (a.metrics == nullptr || (a.summary_out == nullptr && a.diff_out == nullptr)) return 0;
+    ScenarioArgs sa{};
+    sa.K = a.K; sa.S = a.S; sa.S_pad = a.S_pad; sa.W = SIR_ENS_SCALARS + 2 * a.n; sa.n_probs = a.n_probs; sa.probs = a.probs;
+    sa.metrics = a.metrics; sa.wstatus = a.status; sa.status_stride = (size_t)a.S;
+    sa.vals = a.svals; sa.counts = a.counts;
+    sa.summary_out = a.summary_out; sa.diff_out = a.diff_out;
+    sa.sort_scratch = a.sort_scratch; sa.sort_scratch_doubles = a.sort_scratch_doubles;
+    return launch_scenario_summaries(sa, stream);
 }
 
 }  // namespace sepaihrd

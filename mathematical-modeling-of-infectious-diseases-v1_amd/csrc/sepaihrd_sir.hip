@@ -37,6 +37,16 @@
 #ifndef SEPAIHRD_ARITH_FMA
 #error "compile with -DSEPAIHRD_ARITH_FMA=0 or 1"
 #endif
+// The ensemble build (csrc/Makefile sir_ens_*.o, sepaihrd_sir_scenario_ensemble): the same integrator with a per-chain
+// cursor over the intervention events of the chain's scenario, the restart an event asks for, and an observer that stores
+// incidence, prevalence and cumulative infections of every output time instead of forming Poisson terms.  Every addition
+// is under this macro: without it the translation unit is token for token the one the shipped objects were compiled from.
+#ifndef SEPAIHRD_SIR_ENSEMBLE
+#define SEPAIHRD_SIR_ENSEMBLE 0
+#endif
+#if SEPAIHRD_SIR_ENSEMBLE
+#define sepaihrd_sir_eval_kernel sepaihrd_sir_ens_kernel
+#endif
 
 namespace sepaihrd {
 namespace {
@@ -126,7 +136,11 @@ __device__ __forceinline__ void sir_rhs(const SirLane<LPC, RL>& m, const double 
 // ----------------------------------------------------------------------------------
 template <int LPC, int SOLVER, int ARITH_FMA>
 __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevProblem pb, const double* __restrict__ theta,
-                                                                 const int B, const SirOutputs out) {
+                                                                 const int B, const SirOutputs out
+#if SEPAIHRD_SIR_ENSEMBLE
+                                                                 , const SirEnsArgs ens
+#endif
+                                                                 ) {
     constexpr int CPW = WAVE / LPC;
     constexpr bool RL = sir_rows_in_lds(LPC, SOLVER);
     const int lane = threadIdx.x;
@@ -142,8 +156,10 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
     const int age_real = in_vgpr(age < n ? 1 : 0);
 
     extern __shared__ __attribute__((aligned(16))) double sir_lds[];  // LPC > 16: [LPC][WAVE] contact rows, [WAVE] exchange
+#if !SEPAIHRD_SIR_ENSEMBLE
     stage_log_table(lane, WAVE);  // the Poisson term's log reads its table from LDS
     __syncthreads();
+#endif
 
     // ---- 1. applyConstraints + updateModelParameters: later entries overwrite earlier ones, as the loop over names does
     SirLane<LPC, RL> m;
@@ -160,6 +176,28 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
             else if (f == SIR_F_GAMMA && pb.param_index[p] == age) m.gamma = (0.0 < v) ? v : 0.0;
         }
     }
+#if SEPAIHRD_SIR_ENSEMBLE
+    // the chain's scenario and its event cursor.  The table is read per lane: a wavefront can straddle two scenarios.
+    // ev_k is the grid index of the next event (-1: none left), so the step loop compares registers only.
+    const int scen = (int)(chain / ens.S);
+    const int samp = (int)(chain - (long long)scen * ens.S);
+    const SirEvent* ev_cur = ens.events + (size_t)scen * SIR_MAX_EVENTS;
+    int ev_left = ens.n_events[scen];
+    int ev_k = (ev_left > 0) ? ev_cur->time_index : -1;
+    // the events of grid index k in listed order, compounding as repeated AgeSIRModel::applyIntervention calls do
+    // (AgeSIRModel.cpp:141-173): contact kinds scale scale_C_total, transmission kinds scale q by 1 - r
+    auto apply_events = [&](bool on, int k) {
+        while (on && ev_k == k) {
+            const double v = ev_cur->value;
+            if (ev_cur->kind == SIR_EV_CONTACT) scale = scale * v;
+            else m.q = m.q * (1.0 - v);
+            ++ev_cur;
+            --ev_left;
+            ev_k = (ev_left > 0) ? ev_cur->time_index : -1;
+        }
+    };
+    apply_events(true, 0);  // before the first observation: a plain run with the changed parameters
+#endif
     const double Ni = pb.N[age];
     m.has_pop = Ni > 1e-9;
 #if SEPAIHRD_ARITH_FMA
@@ -178,7 +216,24 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
         for (int j = 0; j < LPC; ++j) m.cs[j] = pb.C[age * LPC + j] * scale;  // C_current = scale_C_total * C_baseline
     }
 
+#if SEPAIHRD_SIR_ENSEMBLE
+    // C_current of the chains with `on` set re-formed from the baseline row and the scale now in force (not the stored row
+    // times the event's value: this is what a model constructed with the new scale_C_total holds)
+    auto form_rows = [&](bool on) {
+        if constexpr (RL) {
+            for (int j = 0; j < LPC; ++j)
+                if (on) sir_lds[j * WAVE + lane] = pb.C[age * LPC + j] * scale;
+        } else {
+            if (on) {
+                SEP_UNROLL
+                for (int j = 0; j < LPC; ++j) m.cs[j] = pb.C[age * LPC + j] * scale;
+            }
+        }
+    };
+    int status = 0;  // the observations play no part here
+#else
     int status = pb.obs_not_finite ? 1 : 0;  // y_obs.allFinite() fails whatever the simulation gives
+#endif
 
     // ---- 2. the problem's fixed initial state
     double x[SIR_COMP];
@@ -188,17 +243,63 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
     // Observer at output index k for the chains with do_it set: incidence_i = lambda_i(x(t)) S_i(t), sim = max(incidence, 1e-9),
     // term = obs log(sim) - sim; the terms of the row are added to the chain's sum in ascending age order (row order of the
     // (t, i) matrix).  All lanes execute; terms of chains without do_it and of padded ages are +0.0.
+#if SEPAIHRD_SIR_ENSEMBLE
+    const double* times_v = in_vgpr(pb.times);
+    const int writer = in_vgpr((chain_valid && age == 0) ? 1 : 0);
+    // this lane's column of output time 0, series 0 of the chain's scenario; rows are ens_row doubles apart, series T rows
+    double* ens_dst = in_vgpr(chain_valid ? ens.vals + ((size_t)scen * SIR_ENS_SERIES * T * (n + 1) + age) * (size_t)ens.S_pad + samp : nullptr);
+    const size_t ens_row = in_vgpr((size_t)(n + 1) * (size_t)ens.S_pad);
+    const size_t ens_total = in_vgpr((size_t)(n - age) * (size_t)ens.S_pad);  // from this lane's column to the age total's
+    const double* s0_lane = in_vgpr(pb.init_state + age);
+    const int ens_T = in_vgpr(T);
+#else
     const double* obs_lane = in_vgpr(pb.obs + age);
     const double* times_v = in_vgpr(pb.times);
     const int traj_n = in_vgpr(n);
     double* traj_lane = in_vgpr((out.traj != nullptr && chain_valid) ? out.traj + (size_t)chain * T * ((size_t)SIR_COMP * n) + age : nullptr);
     const int writer = in_vgpr((chain_valid && age == 0) ? 1 : 0);  // a lane mask kept to the end would sit in scalar registers
     double* ll_dst = in_vgpr(out.loglik + chain);
+#endif
     int32_t* status_dst = in_vgpr(out.status ? out.status + chain : nullptr);
     int32_t* nacc_dst = in_vgpr(out.n_accept ? out.n_accept + chain : nullptr);
     int32_t* nrej_dst = in_vgpr(out.n_reject ? out.n_reject + chain : nullptr);
     const int max_attempts = in_vgpr(pb.max_attempts);
     const double max_gap = in_vgpr(pb.max_gap);
+#if SEPAIHRD_SIR_ENSEMBLE
+    // Observer of the ensemble build at output index k for the chains with do_it set: series 0 incidence_i = lambda_i(x(t))
+    // S_i(t) with the parameters in force (no 1e-9 floor), 1 prevalence I_i(t), 2 cumulative infections S_i(t0) - S_i(t),
+    // each with its age total (ages added in ascending order) in column n.  All lanes execute; padded ages add +0.0.
+    bool not_finite = false;
+    auto observe = [&](bool do_it, int k) {
+        const double inc = sir_lambda<LPC, RL>(m, x[1]) * x[0];
+        const bool use = do_it && age_real != 0;
+        not_finite |= use && !isfinite(inc);
+        const double v[SIR_ENS_SERIES] = {use ? inc : 0.0, use ? x[1] : 0.0, use ? s0_lane[0] - x[0] : 0.0};
+        double tot[SIR_ENS_SERIES] = {0.0, 0.0, 0.0};
+        SEP_UNROLL
+        for (int ser = 0; ser < SIR_ENS_SERIES; ++ser) {
+            if constexpr (RL) {
+                publish<LPC, RL>(m, v[ser]);
+                const double* mine = m.xch + (lane & ~(LPC - 1));
+#pragma unroll 4
+                for (int j = 0; j < LPC; ++j) tot[ser] += mine[j];
+            } else {
+                [&]<int... J>(std::integer_sequence<int, J...>) {
+                    ((tot[ser] += group_bcast<LPC, J>(v[ser])), ...);
+                }(std::make_integer_sequence<int, LPC>{});
+            }
+        }
+        if (ens_dst != nullptr && use) {
+            double* d = ens_dst + (size_t)k * ens_row;
+            const size_t ser_stride = (size_t)ens_T * ens_row;
+            SEP_UNROLL
+            for (int ser = 0; ser < SIR_ENS_SERIES; ++ser) {
+                d[ser * ser_stride] = v[ser];
+                if (writer != 0) d[ser * ser_stride + ens_total] = tot[ser];
+            }
+        }
+    };
+#else
     double ll = 0.0;
     bool not_finite = false;
     auto observe = [&](bool do_it, int k) {
@@ -225,6 +326,7 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
             for (int c = 0; c < SIR_COMP; ++c) tdst[c * traj_n] = x[c];
         }
     };
+#endif
 
     // ---- 3. integrate_times(controlled stepper, ..., times, dt_hint, observer)
     int n_acc = 0, n_rej = 0;
@@ -306,6 +408,23 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
         const bool reached = acc && !((t_next - t) > DBL_EPSILON);
         if (__ballot(reached) != 0ull) {
             observe(reached, reached ? k_next : 0);
+#if SEPAIHRD_SIR_ENSEMBLE
+            // An event at this grid index: the row just stored belongs to the interval that ends here (old parameters); now
+            // the parameters change and the integrator restarts as a fresh integrate_times call would -- dt = dt_hint, no
+            // consecutive failures, the FSAL derivative recomputed.  attempts and the step counters run on.
+            const bool restart = reached && k_next == ev_k;
+            if (__ballot(restart) != 0ull) {
+                apply_events(restart, k_next);
+                form_rows(restart);
+                if (restart) { dt = pb.dt_hint; fails = 0; }
+                if constexpr (SOLVER == 0) {
+                    double kr[SIR_COMP];
+                    rhs_call(x, kr);  // every lane calls: the contraction is cross-lane
+                    SEP_UNROLL
+                    for (int c = 0; c < SIR_COMP; ++c) k1[c] = restart ? kr[c] : k1[c];
+                }
+            }
+#endif
             if (reached) {
                 t = t_next;  // integrate_times re-reads the exact grid time
                 ++k_next;
@@ -319,8 +438,12 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
     // ---- 4. the total (PoissonLikelihoodObjective.cpp:84-108, :128-141): every failure is -infinity, nothing throws
     const bool any_not_finite = group_any<LPC>(not_finite, lane);
     if (writer != 0) {
+#if SEPAIHRD_SIR_ENSEMBLE
+        if (status == 0 && any_not_finite) status = 1;
+#else
         if (status == 0 && (any_not_finite || isnan(ll) || isinf(ll))) status = 1;
         *ll_dst = (status != 0) ? -INFINITY : ll;
+#endif
         if (status_dst) *status_dst = status;
         if (nacc_dst) *nacc_dst = n_acc;
         if (nrej_dst) *nrej_dst = n_rej;
@@ -328,13 +451,37 @@ __global__ __launch_bounds__(WAVE) void sepaihrd_sir_eval_kernel(const SirDevPro
 }
 
 template <int LPC, int SOLVER>
+#if SEPAIHRD_SIR_ENSEMBLE
+int launch_lpc(const SirDevProblem& pb, const double* d_theta, int B, const SirOutputs& out, hipStream_t st, const SirEnsArgs& ens) {
+    constexpr int CPW = WAVE / LPC;
+    const unsigned blocks = (unsigned)(((long long)B + CPW - 1) / CPW);
+    hipLaunchKernelGGL((sepaihrd_sir_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA>), dim3(blocks), dim3(WAVE), sir_rows_in_lds(LPC, SOLVER) ? (LPC * WAVE + WAVE) * sizeof(double) : 0, st, pb, d_theta, B, out, ens);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+#else
 int launch_lpc(const SirDevProblem& pb, const double* d_theta, int B, const SirOutputs& out, hipStream_t st) {
     constexpr int CPW = WAVE / LPC;
     const unsigned blocks = (unsigned)(((long long)B + CPW - 1) / CPW);
     hipLaunchKernelGGL((sepaihrd_sir_eval_kernel<LPC, SOLVER, SEPAIHRD_ARITH_FMA>), dim3(blocks), dim3(WAVE), sir_rows_in_lds(LPC, SOLVER) ? (LPC * WAVE + WAVE) * sizeof(double) : 0, st, pb, d_theta, B, out);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
+#endif
 
+#if SEPAIHRD_SIR_ENSEMBLE
+template <int SOLVER>
+int launch_solver(const SirDevProblem& pb, const double* d_theta, int B, const SirOutputs& out, hipStream_t st, const SirEnsArgs& ens) {
+    switch (pb.lpc) {
+        case 1: return launch_lpc<1, SOLVER>(pb, d_theta, B, out, st, ens);
+        case 2: return launch_lpc<2, SOLVER>(pb, d_theta, B, out, st, ens);
+        case 4: return launch_lpc<4, SOLVER>(pb, d_theta, B, out, st, ens);
+        case 8: return launch_lpc<8, SOLVER>(pb, d_theta, B, out, st, ens);
+        case 16: return launch_lpc<16, SOLVER>(pb, d_theta, B, out, st, ens);
+        case 32: return launch_lpc<32, SOLVER>(pb, d_theta, B, out, st, ens);
+        case 64: return launch_lpc<64, SOLVER>(pb, d_theta, B, out, st, ens);
+        default: return -4;
+    }
+}
+#else
 template <int SOLVER>
 int launch_solver(const SirDevProblem& pb, const double* d_theta, int B, const SirOutputs& out, hipStream_t st) {
     switch (pb.lpc) {
@@ -348,9 +495,26 @@ int launch_solver(const SirDevProblem& pb, const double* d_theta, int B, const S
         default: return -4;
     }
 }
+#endif
 
 }  // namespace
 
+#if SEPAIHRD_SIR_ENSEMBLE
+#if SEPAIHRD_ARITH_FMA
+int launch_sir_ens_fma(const SirDevProblem& pb, int solver, const double* d_theta, int B, const SirOutputs& out, const SirEnsArgs& ens, void* stream) {
+#else
+int launch_sir_ens_strict(const SirDevProblem& pb, int solver, const double* d_theta, int B, const SirOutputs& out, const SirEnsArgs& ens, void* stream) {
+#endif
+    if (B <= 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (solver) {
+        case 0: return launch_solver<0>(pb, d_theta, B, out, st, ens);
+        case 1: return launch_solver<1>(pb, d_theta, B, out, st, ens);
+        case 2: return launch_solver<2>(pb, d_theta, B, out, st, ens);
+        default: return -4;
+    }
+}
+#else
 #if SEPAIHRD_ARITH_FMA
 int launch_sir_eval_fma(const SirDevProblem& pb, int solver, const double* d_theta, int B, const SirOutputs& out, void* stream) {
 #else
@@ -365,5 +529,6 @@ int launch_sir_eval_strict(const SirDevProblem& pb, int solver, const double* d_
         default: return -4;
     }
 }
+#endif
 
 }  // namespace sepaihrd

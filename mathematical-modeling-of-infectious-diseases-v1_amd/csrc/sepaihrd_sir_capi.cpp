@@ -39,7 +39,18 @@ struct sepaihrd_sir_ctx {
     bool mh_dp_ready = false;
     int libm_log_diff = -1, libm_exp_diff = -1;
     int no_pending = 0;  // this context has no begin / end evaluation a sampler could collide with
+    // scratch of sepaihrd_sir_scenario_ensemble by role (grow-only, reused across calls), its phase events, the device time
+    // of the last call and the number of calls that reached the device
+    static constexpr int ENS_BUFS = 12;
+    void* ens_buf[ENS_BUFS] = {};
+    size_t ens_cap[ENS_BUFS] = {};
+    hipEvent_t ens_ev[4] = {};
+    double ens_ms[3] = {0.0, 0.0, 0.0};
+    int64_t ens_calls = 0;
 };
+static_assert(sizeof(sepaihrd_sir_event) == sizeof(SirEvent) && SEPAIHRD_SIR_MAX_EVENTS == SIR_MAX_EVENTS &&
+                  SEPAIHRD_SIR_EV_CONTACT == SIR_EV_CONTACT && SEPAIHRD_SIR_EV_TRANSMISSION == SIR_EV_TRANSMISSION,
+              "the kernels read the C ABI's event table in place");
 
 namespace {
 
@@ -204,6 +215,10 @@ void sepaihrd_sir_destroy(sepaihrd_sir_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     free_staging(ctx);
+    for (void* p : ctx->ens_buf)
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : ctx->ens_ev)
+        if (e) (void)hipEventDestroy(e);
     for (void* p : ctx->allocs) (void)hipFree(p);
     delete ctx;
 }
@@ -294,6 +309,211 @@ int sepaihrd_sir_constraint_bounds(const int32_t* param_field, int n_params, dou
         upper[p] = std::numeric_limits<double>::infinity();
         if (has_bounds) has_bounds[p] = param_field[p] == SEPAIHRD_SIR_F_Q ? 1 : 0;
     }
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_sir_validate_events(const sepaihrd_sir_event* events, const int32_t* n_events, int K, int n_times, char* err, int errlen) {
+    if (K <= 0 || n_times < 1 || !n_events) { set_err(err, errlen, "validate_events: need K > 0, n_times >= 1 and n_events"); return SEPAIHRD_E_INVALID_ARG; }
+    for (int k = 0; k < K; ++k) {
+        const std::string sc = "scenario " + std::to_string(k);
+        if (n_events[k] < 0 || n_events[k] > SEPAIHRD_SIR_MAX_EVENTS) {
+            set_err(err, errlen, sc + ": " + std::to_string(n_events[k]) + " events (at most " + std::to_string(SEPAIHRD_SIR_MAX_EVENTS) + ")");
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+        if (n_events[k] > 0 && !events) { set_err(err, errlen, sc + ": events is NULL"); return SEPAIHRD_E_INVALID_ARG; }
+        for (int e = 0; e < n_events[k]; ++e) {
+            const sepaihrd_sir_event& ev = events[(size_t)k * SEPAIHRD_SIR_MAX_EVENTS + e];
+            const std::string who = sc + " event " + std::to_string(e) + ": ";
+            if (ev.time_index < 0 || ev.time_index >= n_times) {
+                set_err(err, errlen, who + "time_index " + std::to_string(ev.time_index) + " outside [0, " + std::to_string(n_times) + ")");
+                return SEPAIHRD_E_INVALID_ARG;
+            }
+            if (e > 0 && ev.time_index < events[(size_t)k * SEPAIHRD_SIR_MAX_EVENTS + e - 1].time_index) {
+                set_err(err, errlen, who + "events are not sorted by time_index");
+                return SEPAIHRD_E_INVALID_ARG;
+            }
+            if (ev.kind != SEPAIHRD_SIR_EV_CONTACT && ev.kind != SEPAIHRD_SIR_EV_TRANSMISSION) {
+                set_err(err, errlen, who + "unknown kind " + std::to_string(ev.kind));
+                return SEPAIHRD_E_INVALID_ARG;
+            }
+            if (!std::isfinite(ev.value)) { set_err(err, errlen, who + "value is not finite"); return SEPAIHRD_E_INVALID_ARG; }
+            if (ev.kind == SEPAIHRD_SIR_EV_CONTACT && ev.value < 0.0) {
+                set_err(err, errlen, who + "contact scale factor must be >= 0");
+                return SEPAIHRD_E_INVALID_ARG;
+            }
+            if (ev.kind == SEPAIHRD_SIR_EV_TRANSMISSION && (ev.value < 0.0 || ev.value > 1.0)) {
+                set_err(err, errlen, who + "transmission reduction must lie in [0, 1]");
+                return SEPAIHRD_E_INVALID_ARG;
+            }
+        }
+    }
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx* ctx, const double* theta, int S, const sepaihrd_sir_event* events,
+                                   const int32_t* n_events, int K, const double* probs, int n_probs, double* quantiles, double* metrics,
+                                   double* metric_summary, double* diff_quantiles, int32_t* status, int32_t* n_accept, int32_t* n_reject,
+                                   int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (S <= 0 || K <= 0 || !theta || !n_events || !probs || n_probs <= 0 || n_probs > 1024) {
+        ctx->last_error = "sir_scenario_ensemble: need S > 0, K > 0, theta, n_events and probs (1..1024)";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) {
+            ctx->last_error = "sir_scenario_ensemble: probabilities must lie in [0, 1]";
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    {
+        char msg[256] = "";
+        if (sepaihrd_sir_validate_events(events, n_events, K, ctx->T, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            ctx->last_error = std::string("sir_scenario_ensemble: ") + msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    const SirDevProblem& dp = ctx->dp;
+    const size_t B = (size_t)K * (size_t)S;
+    if (B > (size_t)std::numeric_limits<int32_t>::max() / 2) {
+        ctx->last_error = "sir_scenario_ensemble: K x S chains exceed one launch (a 32-bit chain count)";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    int S_pad = WAVE;
+    while (S_pad < S && S_pad < ENSEMBLE_MAX_SAMPLES) S_pad <<= 1;
+    const bool big = S > ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
+    if (big) S_pad = (S + WAVE - 1) / WAVE * WAVE;
+    const int n = dp.n, T = dp.T, W = SIR_ENS_SCALARS + 2 * n;
+    const size_t P = (size_t)ctx->P;
+    const size_t n_rows = (size_t)SIR_ENS_SERIES * T * (n + 1);  // sortable segments per scenario
+    const size_t n_vals = (size_t)K * n_rows * S_pad;
+    const size_t n_q = (size_t)K * SIR_ENS_SERIES * n_probs * T * (n + 1);
+    const size_t n_metrics = B * W, n_svals = (size_t)2 * K * W * S_pad;
+    const size_t n_summary = (size_t)K * W * (2 + n_probs), n_diff = (size_t)K * W * n_probs;
+    const size_t n_scratch =
+        big ? std::max<size_t>((size_t)S_pad, std::min<size_t>(std::max(n_rows * S_pad, n_svals), (size_t)1 << 28) / S_pad * S_pad) : 0;
+    const size_t n_evbytes = (size_t)K * SEPAIHRD_SIR_MAX_EVENTS * sizeof(sepaihrd_sir_event);
+    SIR_HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    // K x S within one launch: the buffers below must fit the device's memory (the stored series dominate: K 3 T (n + 1)
+    // S_pad doubles); larger requests are refused before anything is allocated
+    const size_t need_bytes = sizeof(double) * (B * P + n_vals + n_q + n_metrics + (size_t)S + n_svals + n_summary + n_diff + n_scratch + (size_t)n_probs) +
+                              sizeof(int32_t) * (3 * B + 4 * (size_t)K) + n_evbytes;
+    size_t device_bytes = 0;
+    SIR_HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
+    if (need_bytes > device_bytes) {
+        ctx->last_error = "sir_scenario_ensemble: K x S = " + std::to_string(B) + " runs need " + std::to_string(need_bytes >> 20) +
+                          " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
+                          " MiB: split the scenarios or the samples over several calls";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    auto dalloc = [&](int k, auto** p, size_t bytes_wanted) {
+        const size_t bytes = std::max<size_t>(bytes_wanted, 8);
+        if (ctx->ens_cap[k] < bytes) {
+            if (ctx->ens_buf[k]) (void)hipFree(ctx->ens_buf[k]);
+            ctx->ens_buf[k] = nullptr;
+            ctx->ens_cap[k] = 0;
+            if (hipMalloc(&ctx->ens_buf[k], bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+            ctx->ens_cap[k] = bytes;
+        }
+        *p = static_cast<std::remove_reference_t<decltype(*p)>>(ctx->ens_buf[k]);
+        return true;
+    };
+    double *d_theta = nullptr, *d_vals = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_metrics = nullptr, *d_svals = nullptr,
+           *d_summary = nullptr, *d_scratch = nullptr;
+    int32_t *d_ints = nullptr, *d_counts = nullptr, *d_nev = nullptr;
+    SirEvent* d_events = nullptr;
+    if (!dalloc(0, &d_theta, B * P * sizeof(double)) || !dalloc(1, &d_vals, n_vals * sizeof(double)) ||
+        !dalloc(2, &d_probs, (size_t)n_probs * sizeof(double)) || !dalloc(3, &d_q, n_q * sizeof(double)) ||
+        !dalloc(4, &d_metrics, (n_metrics + (size_t)S) * sizeof(double)) || !dalloc(5, &d_svals, n_svals * sizeof(double)) ||
+        !dalloc(6, &d_summary, (n_summary + n_diff) * sizeof(double)) || !dalloc(7, &d_scratch, n_scratch * sizeof(double)) ||
+        !dalloc(8, &d_ints, 3 * B * sizeof(int32_t)) || !dalloc(9, &d_counts, (size_t)3 * K * sizeof(int32_t)) ||
+        !dalloc(10, &d_nev, (size_t)K * sizeof(int32_t)) || !dalloc(11, &d_events, n_evbytes)) {
+        ctx->last_error = "sir_scenario_ensemble: device allocation failed";
+        return SEPAIHRD_E_HIP;
+    }
+    for (hipEvent_t& e : ctx->ens_ev)
+        if (!e) SIR_HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    // every scenario integrates the same samples: theta replicated K times, chain c = scenario c / S, sample c % S
+    SIR_HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    for (int k = 1; k < K; ++k)
+        SIR_HIP_TRY(hipMemcpy(d_theta + (size_t)k * S * P, d_theta, (size_t)S * P * sizeof(double), hipMemcpyDeviceToDevice), ctx,
+                    return SEPAIHRD_E_HIP);
+    {
+        std::vector<sepaihrd_sir_event> tab((size_t)K * SEPAIHRD_SIR_MAX_EVENTS, sepaihrd_sir_event{0, 0, 0.0});
+        for (int k = 0; k < K; ++k)
+            for (int e = 0; e < n_events[k]; ++e) tab[(size_t)k * SEPAIHRD_SIR_MAX_EVENTS + e] = events[(size_t)k * SEPAIHRD_SIR_MAX_EVENTS + e];
+        SIR_HIP_TRY(hipMemcpy(d_events, tab.data(), n_evbytes, hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    }
+    SIR_HIP_TRY(hipMemcpy(d_nev, n_events, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    SIR_HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    ++ctx->ens_calls;
+    int32_t* d_status = d_ints;
+    int32_t* d_nacc = d_ints + B;
+    int32_t* d_nrej = d_ints + 2 * B;
+    SIR_HIP_TRY(hipEventRecord(ctx->ens_ev[0], nullptr), ctx, return SEPAIHRD_E_HIP);
+    const SirOutputs out{nullptr, d_status, d_nacc, d_nrej, nullptr};
+    const SirEnsArgs ens{S, S_pad, d_events, d_nev, d_vals};
+    int rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_sir_ens_fma(dp, ctx->solver, d_theta, (int)B, out, ens, nullptr)
+                                              : launch_sir_ens_strict(dp, ctx->solver, d_theta, (int)B, out, ens, nullptr);
+    if (rc != 0) {
+        ctx->last_error = rc == -4 ? "unsupported lanes-per-chain or solver" : "kernel launch failed";
+        return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
+    }
+    SIR_HIP_TRY(hipEventRecord(ctx->ens_ev[1], nullptr), ctx, return SEPAIHRD_E_HIP);
+    SirEnsSummaryArgs a{};
+    a.K = K; a.S = S; a.S_pad = S_pad; a.n = n; a.lpc = dp.lpc; a.T = T; a.P = ctx->P; a.n_probs = n_probs;
+    a.pb = &ctx->dp; a.theta = d_theta; a.status = d_status; a.vals = d_vals; a.probs = d_probs;
+    a.q_out = quantiles ? d_q : nullptr;
+    a.n_valid = d_counts + 2 * K;
+    const bool want_summaries = metric_summary != nullptr || diff_quantiles != nullptr;
+    a.metrics = (metrics != nullptr || want_summaries) ? d_metrics : nullptr;
+    a.r0 = d_metrics + n_metrics;
+    a.svals = d_svals; a.counts = d_counts;
+    a.summary_out = want_summaries ? d_summary : nullptr;
+    a.diff_out = want_summaries ? d_summary + n_summary : nullptr;
+    a.sort_scratch = big ? d_scratch : nullptr;
+    a.sort_scratch_doubles = n_scratch;
+    a.ev_after_metrics = ctx->ens_ev[2];
+    rc = launch_sir_ensemble_summaries(a, nullptr);
+    if (rc != 0) {
+        ctx->last_error = "sir_scenario_ensemble: summary launch failed";
+        return SEPAIHRD_E_HIP;
+    }
+    SIR_HIP_TRY(hipEventRecord(ctx->ens_ev[3], nullptr), ctx, return SEPAIHRD_E_HIP);
+    SIR_HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.0f;
+        ctx->ens_ms[i] = hipEventElapsedTime(&ms, ctx->ens_ev[i], ctx->ens_ev[i + 1]) == hipSuccess ? (double)ms : -1.0;
+    }
+    bool ok = true;
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        if (ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+    };
+    fetch(quantiles, d_q, n_q * sizeof(double));
+    fetch(metrics, d_metrics, n_metrics * sizeof(double));
+    fetch(metric_summary, d_summary, n_summary * sizeof(double));
+    fetch(diff_quantiles, d_summary + n_summary, n_diff * sizeof(double));
+    fetch(status, d_status, B * sizeof(int32_t));
+    fetch(n_accept, d_nacc, B * sizeof(int32_t));
+    fetch(n_reject, d_nrej, B * sizeof(int32_t));
+    fetch(n_valid, d_counts + 2 * K, (size_t)K * sizeof(int32_t));
+    if (!ok) {
+        ctx->last_error = "sir_scenario_ensemble: copy of the results failed";
+        return SEPAIHRD_E_HIP;
+    }
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_sir_ensemble_quantiles(sepaihrd_sir_ctx* ctx, const double* theta, int S, const double* probs, int n_probs, double* quantiles,
+                                    double* metrics, double* metric_summary, int32_t* status, int32_t* n_valid) {
+    const int32_t none = 0;
+    return sepaihrd_sir_scenario_ensemble(ctx, theta, S, nullptr, &none, 1, probs, n_probs, quantiles, metrics, metric_summary, nullptr, status,
+                                          nullptr, nullptr, n_valid);
+}
+
+int sepaihrd_sir_ensemble_timing(const sepaihrd_sir_ctx* ctx, int64_t* calls, double* ms) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (calls) *calls = ctx->ens_calls;
+    if (ms)
+        for (int i = 0; i < 3; ++i) ms[i] = ctx->ens_ms[i];
     return SEPAIHRD_OK;
 }
 

@@ -123,6 +123,48 @@ def sir_constraint_bounds(lib, param_field) -> tuple:
     return lo, hi, has
 
 
+SIR_MAX_EVENTS = 8        # SEPAIHRD_SIR_MAX_EVENTS
+SIR_EV_CONTACT = 0        # scale_C_total <- scale_C_total * value
+SIR_EV_TRANSMISSION = 1   # q <- q * (1 - value)
+SIR_EVENT_KINDS = {"contact": SIR_EV_CONTACT, "transmission": SIR_EV_TRANSMISSION}
+SIR_SERIES = ("incidence", "prevalence", "cumulative_infections")
+
+
+class sepaihrd_sir_event(C.Structure):
+    """include/sepaihrd_hip.h: struct sepaihrd_sir_event"""
+    _fields_ = [("time_index", C.c_int32), ("kind", C.c_int32), ("value", C.c_double)]
+
+
+def sir_metric_names(n_age: int) -> list:
+    """Columns of the metric table of sepaihrd_sir_scenario_ensemble, in order."""
+    names = ["R0", "peak_prevalence", "time_to_peak_prevalence", "peak_incidence", "time_to_peak_incidence", "overall_attack_rate"]
+    for i in range(n_age):
+        names += [f"attack_rate_age_{i}", f"peak_prevalence_age_{i}"]
+    return names
+
+
+def sir_event_table(scenarios) -> tuple:
+    """Scenarios -- each a list of (time_index, kind, value), kind a SIR_EV_* code or "contact" / "transmission" -- as the
+    [K][8] table and the [K] counts the C ABI takes.  Lists longer than 8 keep their count, for the validator to refuse."""
+    K = len(scenarios)
+    tab = (sepaihrd_sir_event * (max(K, 1) * SIR_MAX_EVENTS))()
+    counts = np.zeros(max(K, 1), dtype=np.int32)
+    for k, sc in enumerate(scenarios):
+        counts[k] = len(sc)
+        for e, (ti, kind, value) in enumerate(list(sc)[:SIR_MAX_EVENTS]):
+            ev = tab[k * SIR_MAX_EVENTS + e]
+            ev.time_index, ev.kind, ev.value = int(ti), int(SIR_EVENT_KINDS.get(kind, kind)), float(value)
+    return tab, counts
+
+
+def sir_validate_events(lib, scenarios, n_times: int) -> tuple:
+    """sepaihrd_sir_validate_events on the host (no device): (code, message)."""
+    tab, counts = sir_event_table(scenarios)
+    err = C.create_string_buffer(256)
+    rc = lib.sepaihrd_sir_validate_events(tab, counts.ctypes.data, len(scenarios), int(n_times), err, len(err))
+    return int(rc), err.value.decode()
+
+
 DIAG_COLUMNS = ("mean", "sd", "mcse_mean", "ess_mean", "ess_bulk", "ess_tail", "r_hat")  # SEPAIHRD_DIAG_COLUMNS, in order
 
 
@@ -161,6 +203,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_sir_reserve", "sepaihrd_sir_apply_constraints", "sepaihrd_sir_set_arith",
     "sepaihrd_sir_mh_create", "sepaihrd_sir_device_libm_check", "sepaihrd_sir_constraint_bounds",
     "sepaihrd_mh_set_kernel_form", "sepaihrd_mh_get_kernel_form",
+    "sepaihrd_sir_validate_events", "sepaihrd_sir_scenario_ensemble", "sepaihrd_sir_ensemble_quantiles", "sepaihrd_sir_ensemble_timing",
 )
 
 _lib = None
@@ -275,6 +318,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_sir_mh_create.argtypes = [vp, C.POINTER(sepaihrd_mh_config), vp, vp]
     lib.sepaihrd_sir_device_libm_check.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.sepaihrd_sir_constraint_bounds.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.sepaihrd_sir_validate_events.argtypes = [vp, vp, C.c_int, C.c_int, C.c_char_p, C.c_int]
+    lib.sepaihrd_sir_scenario_ensemble.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_sir_ensemble_quantiles.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
+    lib.sepaihrd_sir_ensemble_timing.argtypes = [vp, C.POINTER(C.c_int64), vp]
     lib.sepaihrd_mh_set_kernel_form.argtypes = [vp, C.c_int]
     lib.sepaihrd_mh_get_kernel_form.argtypes = [vp]
     if path is None:
@@ -632,3 +679,58 @@ class HipSIRObjective:
         self._check(self.lib.sepaihrd_sir_apply_constraints(self.ctx, th.ctypes.data, th.shape[0], out.ctypes.data),
                     "sepaihrd_sir_apply_constraints")
         return out.reshape(np.shape(theta))
+
+    # ---- posterior ensemble and intervention scenarios ----
+    def scenario_ensemble(self, theta, scenarios, probs, want=("quantiles", "metrics", "metric_summary", "diff_quantiles", "status",
+                                                               "n_accept", "n_reject", "n_valid")) -> dict:
+        """sepaihrd_sir_scenario_ensemble: the S samples ``theta`` under the K ``scenarios`` (lists of (time_index, kind,
+        value), see sir_event_table) in one integrator launch.  Returns the outputs named in ``want``:
+        quantiles [K][3][n_probs][T][n + 1], metrics [K][S][6 + 2 n], metric_summary [K][W][2 + n_probs], diff_quantiles
+        [K][W][n_probs], status / n_accept / n_reject [K][S], n_valid [K].  A failed sample is a NaN metric row with its
+        status set; a refused event table raises ValueError before the device is touched."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError(f"theta must be S x {self.P}")
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        S, K, n_probs, W = th.shape[0], len(scenarios), pr.size, 6 + 2 * self.n
+        tab, counts = sir_event_table(scenarios)
+        shapes = {"quantiles": ((K, 3, n_probs, self.T, self.n + 1), np.float64), "metrics": ((K, S, W), np.float64),
+                  "metric_summary": ((K, W, 2 + n_probs), np.float64), "diff_quantiles": ((K, W, n_probs), np.float64),
+                  "status": ((K, S), np.int32), "n_accept": ((K, S), np.int32), "n_reject": ((K, S), np.int32),
+                  "n_valid": ((K,), np.int32)}
+        unknown = set(want) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        out = {k: np.empty(shapes[k][0], dtype=shapes[k][1]) for k in shapes if k in want}
+        ptr = [out[k].ctypes.data if k in out else None for k in shapes]
+        rc = self.lib.sepaihrd_sir_scenario_ensemble(self.ctx, th.ctypes.data, S, tab, counts.ctypes.data, K, pr.ctypes.data, n_probs, *ptr)
+        if rc == -1:
+            raise ValueError(self.lib.sepaihrd_sir_last_error(self.ctx).decode())
+        self._check(rc, "sepaihrd_sir_scenario_ensemble")
+        return out
+
+    def ensemble_quantiles(self, theta, probs) -> dict:
+        """sepaihrd_sir_ensemble_quantiles: one scenario without events.  quantiles [3][n_probs][T][n + 1], metrics [S][W],
+        metric_summary [W][2 + n_probs], status [S], n_valid."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError(f"theta must be S x {self.P}")
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        S, n_probs, W = th.shape[0], pr.size, 6 + 2 * self.n
+        out = {"quantiles": np.empty((3, n_probs, self.T, self.n + 1)), "metrics": np.empty((S, W)),
+               "metric_summary": np.empty((W, 2 + n_probs)), "status": np.empty(S, dtype=np.int32), "n_valid": np.empty(1, dtype=np.int32)}
+        rc = self.lib.sepaihrd_sir_ensemble_quantiles(self.ctx, th.ctypes.data, S, pr.ctypes.data, n_probs, out["quantiles"].ctypes.data,
+                                                      out["metrics"].ctypes.data, out["metric_summary"].ctypes.data,
+                                                      out["status"].ctypes.data, out["n_valid"].ctypes.data)
+        if rc == -1:
+            raise ValueError(self.lib.sepaihrd_sir_last_error(self.ctx).decode())
+        self._check(rc, "sepaihrd_sir_ensemble_quantiles")
+        out["n_valid"] = int(out["n_valid"][0])
+        return out
+
+    def ensemble_timing(self) -> dict:
+        """Calls of the two entry points above that reached the device, and the last one's device time by phase (ms)."""
+        calls = C.c_int64(0)
+        ms = np.zeros(3)
+        self._check(self.lib.sepaihrd_sir_ensemble_timing(self.ctx, C.byref(calls), ms.ctypes.data), "sepaihrd_sir_ensemble_timing")
+        return {"calls": calls.value, "integrator_ms": ms[0], "metrics_ms": ms[1], "sort_ms": ms[2]}

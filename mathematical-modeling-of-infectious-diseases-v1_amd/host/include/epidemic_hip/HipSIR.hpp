@@ -7,8 +7,8 @@
 // The calibration flow on top of them runs on the device too: MultiChainMetropolisHastings::optimizeChainsOnDevice has an
 // overload for HipPoissonLikelihoodObjective (sepaihrd_sir_mh_create: chains, streams, accept test and adaptation resident
 // in HBM) and HipModelCalibrator a constructor for this pair (HipModelCalibrator.hpp); deviceContext() is what they borrow.
-// Mid-run interventions (applyIntervention through an InterventionCallback) are outside the objective and not scheduled
-// on the device; AgeSIRModel::applyIntervention only changes the host object's values.
+// Mid-run interventions are outside the objective: AgeSIRModel::applyIntervention only changes the host object's values.
+// Schedules of them run on the device for every posterior sample through HipSIRScenarioAnalysis.hpp.
 #pragma once
 #include <memory>
 #include <string>

@@ -13,6 +13,7 @@
 #include "epidemic_hip/HipPosteriorEnsemble.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipSIR.hpp"
+#include "epidemic_hip/HipSIRScenarioAnalysis.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_rng.inc"
 
@@ -964,6 +965,7 @@ struct SirHandle {
     std::unique_ptr<HipSIRParameterManager> pm;
     std::unique_ptr<SimulationCache> cache;
     std::unique_ptr<HipPoissonLikelihoodObjective> obj;
+    std::vector<double> times;  // the objective's output grid (host_sir_scenario_comparison)
 };
 std::shared_ptr<AgeSIRModel> sir_model(int n, const double* N, const double* C, const double* gamma, double q, double scale) {
     Eigen::MatrixXd Cm(n, n);
@@ -1002,6 +1004,7 @@ void* host_sir_create(const sepaihrd_sir_problem* pb, const char* names, const c
         for (size_t i = 0; i < sn.size(); ++i) sg[sn[i]] = sigma_values[i];
         h->pm = std::make_unique<HipSIRParameterManager>(h->model, split_lines(names), sg);
         h->cache = std::make_unique<SimulationCache>(static_cast<size_t>(cache_capacity > 0 ? cache_capacity : 1000));
+        h->times.assign(pb->times, pb->times + pb->n_times);
         if (!with_objective) return h.release();
         Eigen::MatrixXd obs(pb->n_times, n);
         for (int r = 0; r < pb->n_times; ++r)
@@ -1227,6 +1230,106 @@ int host_sir_calibrate(void* hv, int hc_iterations, int cloud_size_multiplier, i
                       chains);
         copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace, samples,
                          sample_values, mcmc_objective_values, n_samples);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// ---- SIR scenario analysis (HipSIRScenarioAnalysis.hpp) ----
+// One scenario built entry by entry through SIRScenario::addIntervention on the grid times[T]: entry e is (ev_times[e], the
+// e-th line of names, n_params[e] values of params in sequence).  0 ok -- the events in schedule order in time_index / kind /
+// value (room for n_entries) and their count in *n_events; 1 InvalidParameterException, 2 any other exception (message in
+// host_last_error).  No device.
+int host_sir_scenario_events(const double* times, int T, int n_entries, const double* ev_times, const char* names, const int* n_params,
+                             const double* params, int32_t* time_index, int32_t* kind, double* value, int* n_events) {
+    try {
+        SIRScenario sc("scenario", std::vector<double>(times, times + T));
+        const std::vector<std::string> nm = split_lines(names);
+        if (static_cast<int>(nm.size()) != n_entries) throw ModelException("host_sir_scenario_events", "one name per entry expected");
+        size_t at = 0;
+        for (int e = 0; e < n_entries; ++e) {
+            sc.addIntervention(ev_times[e], nm[static_cast<size_t>(e)], vec(params + at, n_params[e]));
+            at += static_cast<size_t>(n_params[e]);
+        }
+        const auto& ev = sc.events();
+        for (size_t e = 0; e < ev.size(); ++e) { time_index[e] = ev[e].time_index; kind[e] = ev[e].kind; value[e] = ev[e].value; }
+        *n_events = static_cast<int>(ev.size());
+        return 0;
+    } catch (const InvalidParameterException& e) {
+        g_error = e.what();
+        return 1;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 2;
+    }
+}
+
+namespace {
+std::vector<SIRScenario> sir_scenarios(const std::vector<double>& times, const char* scenario_names, int K, const int* counts, const double* ev_times,
+                                       const char* ev_names, const double* ev_values) {
+    const std::vector<std::string> sn = split_lines(scenario_names), en = split_lines(ev_names);
+    if (static_cast<int>(sn.size()) != K) throw InvalidParameterException("host_sir_scenario_comparison", "one name per scenario expected");
+    std::vector<SIRScenario> out;
+    size_t at = 0;
+    for (int k = 0; k < K; ++k) {
+        out.emplace_back(sn[static_cast<size_t>(k)], times);
+        for (int e = 0; e < counts[k]; ++e, ++at) out.back().addIntervention(ev_times[at], en.at(at), vec(ev_values + at, 1));
+    }
+    return out;
+}
+}  // namespace
+
+// The two writers on a result given as arrays (no device): quantiles [K][3][n_probs][T][n_age + 1], metric_summary
+// [K][W][2 + n_probs], diff_quantiles [K][W][n_probs].  A NULL path skips that file.  0 ok, 1 = exception.
+int host_sir_write_scenario_csvs(const char* comparison_path, const char* bands_path, const char* scenario_names, int K, int n_age, int T,
+                                 const double* times, const double* probs, int n_probs, const double* quantiles, const double* metric_summary,
+                                 const double* diff_quantiles) {
+    try {
+        SIRScenarioResult r;
+        r.scenario_names = split_lines(scenario_names);
+        if (static_cast<int>(r.scenario_names.size()) != K) throw InvalidParameterException("host_sir_write_scenario_csvs", "one name per scenario expected");
+        r.metric_names = HipSIRScenarioAnalysis::metricNames(n_age);
+        r.probs.assign(probs, probs + n_probs);
+        r.times.assign(times, times + T);
+        r.n_age = n_age;
+        const size_t W = r.metric_names.size();
+        if (quantiles) r.quantiles.assign(quantiles, quantiles + static_cast<size_t>(K) * 3 * n_probs * T * (n_age + 1));
+        if (metric_summary) r.metric_summary.assign(metric_summary, metric_summary + static_cast<size_t>(K) * W * (2 + n_probs));
+        if (diff_quantiles) r.diff_quantiles.assign(diff_quantiles, diff_quantiles + static_cast<size_t>(K) * W * n_probs);
+        if (comparison_path) HipSIRScenarioAnalysis::writeScenarioComparison(comparison_path, r);
+        if (bands_path) HipSIRScenarioAnalysis::writePosteriorBands(bands_path, r);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// HipSIRScenarioAnalysis::run on the handle's objective and both files.  Scenario k has counts[k] entries taken in sequence
+// from ev_times / ev_names ('\n'-joined) / ev_values (one parameter each).  The outputs (any may be NULL) have the shapes
+// of sepaihrd_sir_scenario_ensemble with S = the samples left after burn-in and thinning.  0 ok, 1 = exception.
+int host_sir_scenario_comparison(void* hv, const double* samples, int n_samples, int burn_in, int thinning, const char* scenario_names, int K,
+                                 const int* counts, const double* ev_times, const char* ev_names, const double* ev_values, const double* probs,
+                                 int n_probs, const char* comparison_path, const char* bands_path, double* quantiles, double* metrics,
+                                 double* metric_summary, double* diff_quantiles, int32_t* status, int32_t* n_valid) {
+    auto* h = static_cast<SirHandle*>(hv);
+    try {
+        if (!h->obj) throw ModelException("host_sir_scenario_comparison", "the handle has no objective");
+        const std::vector<double>& times = h->times;
+        const HipSIRScenarioAnalysis analysis(*h->obj, times, h->model->getNumAgeClasses());
+        const SIRScenarioResult r = analysis.run(samples, n_samples, burn_in, thinning,
+                                                 sir_scenarios(times, scenario_names, K, counts, ev_times, ev_names, ev_values),
+                                                 std::vector<double>(probs, probs + n_probs));
+        if (comparison_path) HipSIRScenarioAnalysis::writeScenarioComparison(comparison_path, r);
+        if (bands_path) HipSIRScenarioAnalysis::writePosteriorBands(bands_path, r);
+        if (quantiles) std::copy(r.quantiles.begin(), r.quantiles.end(), quantiles);
+        if (metrics) std::copy(r.metrics.begin(), r.metrics.end(), metrics);
+        if (metric_summary) std::copy(r.metric_summary.begin(), r.metric_summary.end(), metric_summary);
+        if (diff_quantiles) std::copy(r.diff_quantiles.begin(), r.diff_quantiles.end(), diff_quantiles);
+        if (status) std::copy(r.status.begin(), r.status.end(), status);
+        if (n_valid) std::copy(r.n_valid.begin(), r.n_valid.end(), n_valid);
         return 0;
     } catch (const std::exception& e) {
         g_error = e.what();

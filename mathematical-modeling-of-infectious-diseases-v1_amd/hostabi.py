@@ -82,6 +82,10 @@ def load_library() -> C.CDLL:
     lib.host_sir_mh_run_ex.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double] + \
         [C.c_int] * 9 + [C.c_char_p, C.c_char_p] + [vp] * 4 + [vp, C.POINTER(C.c_int32), vp, vp, vp, C.POINTER(C.c_int),
                                                              C.POINTER(C.c_long), vp, C.POINTER(C.c_int32)]
+    lib.host_sir_scenario_events.argtypes = [vp, C.c_int, C.c_int, vp, C.c_char_p, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.host_sir_write_scenario_csvs.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    lib.host_sir_scenario_comparison.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, vp, vp, C.c_char_p, vp, vp, C.c_int,
+                                                 C.c_char_p, C.c_char_p, vp, vp, vp, vp, vp, vp]
     lib.host_sir_calibrate.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                        C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
@@ -549,6 +553,41 @@ def sir_rhs(N, Cm, gamma, q, scale_C, state) -> np.ndarray:
     return out
 
 
+def sir_scenario_events(times, entries) -> list:
+    """One scenario through the C++ SIRScenario::addIntervention (no device): ``entries`` are (time, name, params) with the
+    reference's intervention names; returns the events [(time_index, kind, value)] in schedule order.  Raises ValueError for
+    what the C++ side throws as InvalidParameterException and RuntimeError for any other exception."""
+    lib = load_library()
+    t = np.ascontiguousarray(times, dtype=np.float64)
+    ev_t = np.array([float(e[0]) for e in entries] + [0.0])
+    counts = np.array([len(np.atleast_1d(e[2])) for e in entries] + [0], dtype=np.int32)
+    params = np.array([float(v) for e in entries for v in np.atleast_1d(e[2])] + [0.0])
+    m = len(entries)
+    ti, kind, val = np.zeros(m + 1, dtype=np.int32), np.zeros(m + 1, dtype=np.int32), np.zeros(m + 1)
+    n = C.c_int(0)
+    rc = lib.host_sir_scenario_events(t.ctypes.data, t.size, m, ev_t.ctypes.data, "\n".join(e[1] for e in entries).encode(), counts.ctypes.data,
+                                      params.ctypes.data, ti.ctypes.data, kind.ctypes.data, val.ctypes.data, C.byref(n))
+    if rc == 1:
+        raise ValueError(lib.host_last_error().decode())
+    if rc != 0:
+        raise RuntimeError(lib.host_last_error().decode())
+    return [(int(ti[e]), int(kind[e]), float(val[e])) for e in range(n.value)]
+
+
+def write_sir_scenario_csvs(comparison_path, bands_path, scenario_names, times, probs, n_age, quantiles=None, metric_summary=None,
+                            diff_quantiles=None):
+    """HipSIRScenarioAnalysis::writeScenarioComparison / writePosteriorBands on arrays (no device); a None path skips the file."""
+    lib = load_library()
+    t, pr = np.ascontiguousarray(times, dtype=np.float64), np.ascontiguousarray(probs, dtype=np.float64)
+    arr = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (quantiles, metric_summary, diff_quantiles)]
+    rc = lib.host_sir_write_scenario_csvs(None if comparison_path is None else str(comparison_path).encode(),
+                                          None if bands_path is None else str(bands_path).encode(), "\n".join(scenario_names).encode(),
+                                          len(scenario_names), int(n_age), t.size, t.ctypes.data, pr.ctypes.data, pr.size,
+                                          *[None if a is None else a.ctypes.data for a in arr])
+    if rc != 0:
+        raise RuntimeError("host_sir_write_scenario_csvs: " + lib.host_last_error().decode())
+
+
 class HostSIRObjective:
     """AgeSIRModel + HipSIRParameterManager + SimulationCache + HipPoissonLikelihoodObjective (C++ objects).
     ``param_names`` overrides the problem's (the manager's name errors are the C++ ones); ``with_objective=False`` builds
@@ -694,4 +733,32 @@ class HostSIRObjective:
             raise RuntimeError("host_sir_calibrate: " + self.lib.host_last_error().decode())
         assert ns.value == cap, (ns.value, cap)
         out.update(best_value=bv.value, initial_value=iv.value, phase1_best_value=p1.value, n_samples=ns.value)
+        return out
+
+    def scenario_comparison(self, samples, scenarios, probs=(0.025, 0.05, 0.5, 0.95, 0.975), burn_in: int = 0, thinning: int = 1,
+                            comparison_path: str | None = None, bands_path: str | None = None) -> dict:
+        """HipSIRScenarioAnalysis (C++): the posterior ``samples`` [rows][P] after burn-in and thinning under the named
+        ``scenarios`` -- {name: [(time, intervention name, value), ...]} with the reference's intervention names, the first
+        one the baseline of the paired differences -- in one device call; writes sir_scenario_comparison.csv and
+        sir_posterior_bands.csv to the given paths.  Returns the outputs of HipSIRObjective.scenario_ensemble."""
+        ps = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, self.P)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        names = list(scenarios.keys())
+        K, T, n = len(names), self.pb.n_times, self.n
+        S = len(range(max(burn_in, 0), ps.shape[0], max(thinning, 1)))
+        W = 6 + 2 * n
+        counts = np.array([len(scenarios[k]) for k in names] + [0], dtype=np.int32)
+        flat = [e for k in names for e in scenarios[k]]
+        ev_t = np.array([float(e[0]) for e in flat] + [0.0])
+        ev_v = np.array([float(e[2]) for e in flat] + [0.0])
+        out = {"quantiles": np.empty((K, 3, pr.size, T, n + 1)), "metrics": np.empty((K, S, W)), "metric_summary": np.empty((K, W, 2 + pr.size)),
+               "diff_quantiles": np.empty((K, W, pr.size)), "status": np.empty((K, S), dtype=np.int32), "n_valid": np.empty(K, dtype=np.int32)}
+        rc = self.lib.host_sir_scenario_comparison(self.h, ps.ctypes.data, ps.shape[0], burn_in, thinning, "\n".join(names).encode(), K,
+                                                   counts.ctypes.data, ev_t.ctypes.data, "\n".join(e[1] for e in flat).encode(), ev_v.ctypes.data,
+                                                   pr.ctypes.data, pr.size, None if comparison_path is None else str(comparison_path).encode(),
+                                                   None if bands_path is None else str(bands_path).encode(),
+                                                   *[out[k].ctypes.data for k in ("quantiles", "metrics", "metric_summary", "diff_quantiles", "status", "n_valid")])
+        if rc != 0:
+            raise RuntimeError("host_sir_scenario_comparison: " + self.lib.host_last_error().decode())
+        out["scenario_names"], out["metric_names"] = names, hipabi.sir_metric_names(n)
         return out

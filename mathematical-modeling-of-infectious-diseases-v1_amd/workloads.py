@@ -91,3 +91,131 @@ def sir_config0(simulate, param_names=SIR_ALL_NAMES, seed: int = 20240229, **kw)
     traj = np.asarray(simulate(N, Cm, gamma, 0.03, 1.0, init, times)["traj"]).reshape(len(times), 9)
     rng = np.random.default_rng(seed)
     return pb.with_(obs=rng.poisson(sir_incidence(pb, traj)).astype(np.float64))
+
+
+def sir_scenario_reference(simulate, pb, theta, scenarios, probs) -> dict:
+    """The semantics of sepaihrd_sir_scenario_ensemble restated in numpy around a caller-supplied
+    ``simulate(N, C, gamma, q, scale, init, times, abs_err, rel_err)`` -> {"traj": [T'][3n], "n_accept", "n_reject"} that
+    raises when a run fails (the package holds no integrator).  ``scenarios``: lists of (time_index, kind, value), kind 0 /
+    "contact" (scale <- scale * value) or 1 / "transmission" (q <- q * (1 - value)), sorted by time_index.
+
+    An event at grid index k splits the run: the segment before it ends at times[k], whose row (state and incidence)
+    is formed with the old parameters; the next segment is a fresh ``simulate`` call on times[k:] from that state with the
+    new ones, C_current = C * scale_now.  Events at index 0 precede the first observation.  Step counts are summed over
+    the segments; a sample whose summed attempts exceed pb.max_attempts (0: 1 000 000) has status 3, as a chain that is still
+    running after that many attempts has on the device.  Quantiles: np.quantile(method="linear") over the samples valid in that scenario, NaN when there is none;
+    R0 = max |eigvals| of K_ij = q scale C_ij N_i / (N_j gamma_j), columns with N_j <= 1e-9 dropped, gamma_j = 0: +inf.
+    Returns the outputs of HipSIRObjective.scenario_ensemble plus "series" [K][S][3][T][n + 1]."""
+    kinds = {"contact": 0, "transmission": 1}
+    theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    probs = np.asarray(probs, dtype=np.float64)
+    K, S, n, T = len(scenarios), theta.shape[0], pb.n, pb.n_times
+    W = 6 + 2 * n
+    series = np.full((K, S, 3, T, n + 1), np.nan)
+    metrics = np.full((K, S, W), np.nan)
+    status = np.zeros((K, S), dtype=np.int32)
+    n_acc = np.zeros((K, S), dtype=np.int32)
+    n_rej = np.zeros((K, S), dtype=np.int32)
+    S0 = pb.initial_state[:n]
+    has_pop = pb.N > 1e-9
+
+    def incidence(rows, q, scale):
+        ion = np.where(has_pop, rows[:, n:2 * n] / np.where(has_pop, pb.N, 1.0), 0.0)
+        return np.maximum(q * (ion @ (pb.C * scale).T), 0.0) * rows[:, :n]
+
+    def total(a):  # ages added in ascending order
+        tot = np.zeros(a.shape[:-1])
+        for i in range(a.shape[-1]):
+            tot = tot + a[..., i]
+        return tot
+
+    for s in range(S):
+        v = pb.model_values(theta[s])
+        # R0 from the sample's own parameters, before any event
+        if np.any(has_pop & (v["gamma"] == 0.0)):
+            r0 = np.inf
+        else:
+            col = np.where(has_pop, 1.0 / np.where(has_pop, pb.N * v["gamma"], 1.0), 0.0)
+            r0 = float(np.max(np.abs(np.linalg.eigvals(v["q"] * v["scale_C_total"] * pb.C * pb.N[:, None] * col[None, :]))))
+        for k, sc in enumerate(scenarios):
+            events = [(int(ti), int(kinds.get(kind, kind)), float(val)) for ti, kind, val in sc]
+            q, scale = v["q"], v["scale_C_total"]
+
+            def apply(at, q, scale):
+                for ti, kind, val in events:
+                    if ti == at:
+                        if kind == 0:
+                            scale = scale * val
+                        else:
+                            q = q * (1.0 - val)
+                return q, scale
+
+            q, scale = apply(0, q, scale)
+            cuts = sorted({ti for ti, _, _ in events if 0 < ti < T - 1}) + [T - 1]
+            traj = np.empty((T, 3 * n))
+            inc = np.empty((T, n))
+            x, k0 = pb.initial_state, 0
+            try:
+                for k1 in cuts:
+                    r = simulate(pb.N, pb.C, v["gamma"], q, scale, x, pb.times[k0:k1 + 1], pb.abs_err, pb.rel_err)
+                    seg = np.asarray(r["traj"]).reshape(k1 - k0 + 1, 3 * n)
+                    first = 0 if k0 == 0 else 1  # row k0 was formed by the segment that ended there
+                    traj[k0 + first:k1 + 1] = seg[first:]
+                    inc[k0 + first:k1 + 1] = incidence(seg[first:], q, scale)
+                    n_acc[k, s] += r.get("n_accept", 0)
+                    n_rej[k, s] += r.get("n_reject", 0)
+                    x, k0 = seg[-1], k1
+                    q, scale = apply(k1, q, scale)
+                if T == 1:
+                    traj[0] = pb.initial_state
+                    inc[0] = incidence(traj[:1], q, scale)[0]
+            except RuntimeError:
+                status[k, s] = 2
+                continue
+            if int(n_acc[k, s]) + int(n_rej[k, s]) > (pb.max_attempts if pb.max_attempts > 0 else 1000000):
+                status[k, s] = 3
+                continue
+            if not np.all(np.isfinite(inc)):
+                status[k, s] = 1
+                continue
+            for ser, a in enumerate((inc, traj[:, n:2 * n], S0[None, :] - traj[:, :n])):
+                series[k, s, ser, :, :n] = a
+                series[k, s, ser, :, n] = total(a)
+            tp, ti_ = series[k, s, 1, :, n], series[k, s, 0, :, n]
+            m = metrics[k, s]
+            m[0] = r0
+            m[1], m[2] = tp.max(), pb.times[int(np.argmax(tp))]
+            m[3], m[4] = ti_.max(), pb.times[int(np.argmax(ti_))]
+            tot_pop = 0.0
+            for i in range(n):
+                tot_pop = tot_pop + pb.N[i]
+            m[5] = series[k, s, 2, T - 1, n] / tot_pop
+            last = series[k, s, 2, T - 1, :n]
+            m[6::2] = np.where(pb.N > 0, last / np.where(pb.N > 0, pb.N, 1.0), 0.0)
+            m[7::2] = series[k, s, 1, :, :n].max(axis=0)
+
+    def q_of(a):  # a [n_valid][...] -> [n_probs][...]
+        if a.shape[0] == 0:
+            return np.full((len(probs),) + a.shape[1:], np.nan)
+        return np.quantile(a, probs, axis=0, method="linear")
+
+    quantiles = np.empty((K, 3, len(probs), T, n + 1))
+    summary = np.empty((K, W, 2 + len(probs)))
+    diff = np.empty((K, W, len(probs)))
+    n_valid = np.zeros(K, dtype=np.int32)
+    for k in range(K):
+        ok = status[k] == 0
+        n_valid[k] = ok.sum()
+        quantiles[k] = np.moveaxis(q_of(series[k, ok]), 0, 1)  # [n_probs][3][T][n+1] -> [3][n_probs][T][n+1]
+        mv = metrics[k, ok]
+        if mv.shape[0]:  # (an infinite R0 gives an infinite mean and NaN below it, as on the device)
+            mean = mv.sum(axis=0) / mv.shape[0]
+            summary[k, :, 0] = mean
+            summary[k, :, 1] = np.sqrt(((mv - mean) ** 2).sum(axis=0) / mv.shape[0])
+        else:
+            summary[k, :, :2] = np.nan
+        summary[k, :, 2:] = q_of(mv).T
+        both = ok & (status[0] == 0)
+        diff[k] = q_of(metrics[k, both] - metrics[0, both]).T
+    return {"quantiles": quantiles, "metrics": metrics, "metric_summary": summary, "diff_quantiles": diff, "status": status,
+            "n_accept": n_acc, "n_reject": n_rej, "n_valid": n_valid, "series": series}
