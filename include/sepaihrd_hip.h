@@ -217,6 +217,35 @@ int sepaihrd_eval_batch_begin(sepaihrd_ctx *ctx, const double *theta, int B);
 int sepaihrd_eval_batch_end(sepaihrd_ctx *ctx, double *loglik, int32_t *status, int32_t *n_accept, int32_t *n_reject,
                             double *ll_parts);
 
+/* Forward-difference gradients of C parameter vectors in one pass (additive entry; the ABI version is unchanged).
+ * For every row c the result is, bit for bit, what the host's finite-difference objective computes for theta[c] alone:
+ *   value[c]   the objective at theta[c], evaluated by centre_ctx (which applies its own initial-state rule, by default
+ *              SEPAIHRD_INIT_FROM_THETA: run-up / seed);
+ *   grad[c][i] (f_i - value[c]) / eps_i with eps_i = fd_epsilon * max(|theta[c][i]|, fd_epsilon) -- a product rounded on
+ *              its own, in either arithmetic mode, before it is added to theta[c][i] and before it divides (IEEE fp64
+ *              division) -- and f_i the objective at theta[c] + eps_i e_i, evaluated by perturbed_ctx (the caller builds
+ *              that context with SEPAIHRD_INIT_MULTIPLIERS, clamp mode, unbounded multipliers and base multipliers 1.0);
+ *              0 where f_i is not finite; 0 where the perturbed initial state is invalid: for some age class k the sum over
+ *              the compartments E..D of initial_state * multiplier lies outside [0, N_k], the multiplier of compartment j
+ *              read UNCONSTRAINED from the perturbed vector at mult_index[j] (-1: not calibrated, 1.0);
+ *              the whole row 0 where value[c] is not finite (lowest() is finite);
+ *   status[c]  the largest per-evaluation status among the centre's and the row's P perturbed evaluations: the caller
+ *              applies its rule for integration failures (>= SEPAIHRD_STATUS_STEP_FAILURE) to it.
+ * want_grad (NULL = every row): rows with want_grad[c] == 0 get value[c] and the centre's status only; their rows of
+ * `grad` are left untouched and no perturbed evaluation is run for them.
+ * What stays with the caller: the rule for output grids with run-up rows (every quotient then uses lowest() for f_i and no
+ * perturbed evaluation is needed: call with want_grad all zero) and the refusal of grids that start before t = 0.
+ * The G P perturbed evaluations (G = rows wanted) run on perturbed_ctx's own stream and the C centre evaluations on
+ * centre_ctx's, ordered by events; the call waits once, for the results.  Workspace: C P P + 2 C P doubles (perturbed
+ * matrix, steps, perturbed values) plus the staging of inputs and results (2 C P + C doubles, C P + 3 C int32), held by
+ * perturbed_ctx, grown on demand and kept.  All pointers are host pointers; theta [C][P], grad [C][P], mult_index [8].
+ * Limits: C * n_params <= 2^22 (4 194 304 perturbed rows; 2.1 GB of workspace at 62 parameters) -- beyond it
+ * SEPAIHRD_E_UNSUPPORTED, as for a context in SEPAIHRD_PRECISION_F32; both contexts on one device, of one problem, neither
+ * with a sepaihrd_eval_batch_begin pending (SEPAIHRD_E_INVALID_ARG).  Errors are reported through perturbed_ctx. */
+int sepaihrd_fd_gradient_batch(sepaihrd_ctx *centre_ctx, sepaihrd_ctx *perturbed_ctx, const double *theta,
+                               const uint8_t *want_grad, int C, double fd_epsilon, const int32_t *mult_index,
+                               double *value, double *grad, int32_t *status);
+
 /* Device-pointer form: same arguments but every pointer is a DEVICE pointer on ctx's device,
  * and the launches (integrator kernel + two likelihood-pass kernels) are asynchronous on `stream`
  * (a hipStream_t, NULL = default stream).  No synchronisation.  The ctx-owned workspace

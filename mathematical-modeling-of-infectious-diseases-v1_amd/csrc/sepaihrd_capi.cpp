@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_fd_device.h"
 #include "sepaihrd_mh_backend.h"
 
 using namespace sepaihrd;
@@ -84,6 +85,12 @@ struct sepaihrd_ctx {
     // per-chain summary records: the table of the chains this context ran, and the gathered table of all
     double* rec_buf[2] = {nullptr, nullptr};
     size_t rec_cap[2] = {0, 0};
+    // sepaihrd_fd_gradient_batch (held by the context of the perturbed evaluations, grow-only): the perturbed matrix, steps
+    // and perturbed values, then the staging of the call's inputs and results with a page-locked mirror of the results
+    void* fd_dev = nullptr;
+    void* fd_host = nullptr;
+    size_t fd_dev_bytes = 0, fd_host_bytes = 0;
+    hipEvent_t fd_ev_uploaded = nullptr, fd_ev_centre = nullptr;
 };
 
 namespace {
@@ -503,6 +510,10 @@ void sepaihrd_destroy(sepaihrd_ctx* ctx) {
         if (p) (void)hipFree(p);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->busy_event) (void)hipEventDestroy(ctx->busy_event);
+    if (ctx->fd_dev) (void)hipFree(ctx->fd_dev);
+    if (ctx->fd_host) (void)hipHostFree(ctx->fd_host);
+    for (hipEvent_t e : {ctx->fd_ev_uploaded, ctx->fd_ev_centre})
+        if (e) (void)hipEventDestroy(e);
     for (void* p : ctx->allocs) (void)hipFree(p);
     delete ctx;
 }
@@ -700,6 +711,101 @@ int sepaihrd_eval_batch_end(sepaihrd_ctx* ctx, double* loglik, int32_t* status, 
     ctx->pending_B = 0;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     return fetch_results(ctx, ctx->own_stream, B, loglik, status, n_accept, n_reject, ll_parts);
+}
+
+// Forward differences of C centres in one pass (see include/sepaihrd_hip.h): upload, builder kernel and the G P perturbed
+// evaluations on the perturbed context's stream, the C centre evaluations on the centre context's stream, the quotient
+// kernel behind both, one copy home and ONE wait.  The two streams are ordered by events only.
+int sepaihrd_fd_gradient_batch(sepaihrd_ctx* cc, sepaihrd_ctx* pc, const double* theta, const uint8_t* want_grad, int C,
+                               double fd_epsilon, const int32_t* mult_index, double* value, double* grad, int32_t* status) {
+    if (!cc || !pc) return SEPAIHRD_E_INVALID_ARG;
+    auto bad = [&](const char* msg, int rc) { pc->last_error = std::string("fd_gradient_batch: ") + msg; return rc; };
+    if (C < 0 || (C > 0 && (!theta || !value || !grad || !status || !mult_index))) return bad("NULL argument or negative C", SEPAIHRD_E_INVALID_ARG);
+    if (cc->device != pc->device || cc->P != pc->P || cc->n != pc->n)
+        return bad("the two contexts are not of one problem on one device", SEPAIHRD_E_INVALID_ARG);
+    if (cc->precision != SEPAIHRD_PRECISION_F64 || pc->precision != SEPAIHRD_PRECISION_F64)
+        return bad("not built for contexts in SEPAIHRD_PRECISION_F32", SEPAIHRD_E_UNSUPPORTED);
+    if (cc->pending_B > 0 || pc->pending_B > 0) return bad("a sepaihrd_eval_batch_begin is pending on one of the contexts", SEPAIHRD_E_INVALID_ARG);
+    if (C == 0) return SEPAIHRD_OK;
+    const size_t P = (size_t)pc->P, nC = (size_t)C;
+    for (int j = 0; j < 8; ++j)
+        if (mult_index[j] >= (int32_t)P) return bad("mult_index entry beyond the parameter count", SEPAIHRD_E_INVALID_ARG);
+    std::vector<int32_t> rows;
+    rows.reserve(nC);
+    for (int c = 0; c < C; ++c)
+        if (!want_grad || want_grad[c]) rows.push_back(c);
+    const size_t G = rows.size(), GP = G * P;
+    if (nC * P > FD_MAX_PERTURBED_ROWS) return bad("C x n_params above 2^22 rows: split the batch", SEPAIHRD_E_UNSUPPORTED);
+    HIP_TRY(hipSetDevice(pc->device), pc, return SEPAIHRD_E_HIP);
+    for (sepaihrd_ctx* c : {cc, pc})
+        if (!c->own_stream) HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking), pc, return SEPAIHRD_E_HIP);
+    for (hipEvent_t* e : {&pc->fd_ev_uploaded, &pc->fd_ev_centre})
+        if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming), pc, return SEPAIHRD_E_HIP);
+    // sized for G = C, so that the want_grad mask never makes a later call allocate
+    const size_t dbl = nC * P * P + 2 * nC * P /* plus, eps, f_plus */ + nC * P /* theta */ + nC + nC * P /* value, grad */;
+    const size_t i32 = nC /* status */ + nC * P /* plus_status */ + nC /* centre_status */ + nC /* rows */;
+    const size_t need = dbl * sizeof(double) + i32 * sizeof(int32_t);
+    const size_t result_bytes = (nC + GP) * sizeof(double) + nC * sizeof(int32_t);
+    if (need > pc->fd_dev_bytes) {  // not stream-ordered: before anything is queued
+        if (pc->fd_dev) (void)hipFree(pc->fd_dev);
+        pc->fd_dev = nullptr; pc->fd_dev_bytes = 0;
+        HIP_TRY(hipMalloc(&pc->fd_dev, need), pc, return SEPAIHRD_E_HIP);
+        pc->fd_dev_bytes = need;
+    }
+    const size_t host_need = (nC + nC * P) * sizeof(double) + nC * sizeof(int32_t);
+    if (host_need > pc->fd_host_bytes) {
+        if (pc->fd_host) (void)hipHostFree(pc->fd_host);
+        pc->fd_host = nullptr; pc->fd_host_bytes = 0;
+        HIP_TRY(hipHostMalloc(&pc->fd_host, host_need, hipHostMallocDefault), pc, return SEPAIHRD_E_HIP);
+        pc->fd_host_bytes = host_need;
+    }
+    if (sepaihrd_reserve(cc, C) != SEPAIHRD_OK) return bad(cc->last_error.c_str(), SEPAIHRD_E_HIP);
+    if (G > 0 && sepaihrd_reserve(pc, (int)GP) != SEPAIHRD_OK) return SEPAIHRD_E_HIP;
+    // carve; the results [value C][grad G P][status C] are contiguous: one copy home
+    double* d_plus = static_cast<double*>(pc->fd_dev);
+    double* d_eps = d_plus + nC * P * P;
+    double* d_fplus = d_eps + nC * P;
+    double* d_theta = d_fplus + nC * P;
+    double* d_value = d_theta + nC * P;
+    double* d_grad = d_value + nC;
+    int32_t* d_status = reinterpret_cast<int32_t*>(d_grad + GP);
+    int32_t* d_pstatus = reinterpret_cast<int32_t*>(d_grad + nC * P) + nC;
+    int32_t* d_cstatus = d_pstatus + nC * P;
+    int32_t* d_rows = d_cstatus + nC;
+    hipStream_t sp = pc->own_stream, sc = cc->own_stream;
+    HIP_TRY(hipMemcpyAsync(d_theta, theta, nC * P * sizeof(double), hipMemcpyHostToDevice, sp), pc, return SEPAIHRD_E_HIP);
+    if (G > 0) HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), G * sizeof(int32_t), hipMemcpyHostToDevice, sp), pc, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemsetAsync(d_status, 0, nC * sizeof(int32_t), sp), pc, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipEventRecord(pc->fd_ev_uploaded, sp), pc, return SEPAIHRD_E_HIP);
+    if (G > 0) {  // the perturbed evaluations do not depend on the centres': queued first, they run beside them
+        if (launch_fd_build(d_theta, d_rows, (int)G, (int)P, fd_epsilon, d_plus, d_eps, sp) != 0) return bad("builder launch failed", SEPAIHRD_E_HIP);
+        const int rc = sepaihrd_eval_batch_device(pc, d_plus, (int)GP, d_fplus, d_pstatus, nullptr, nullptr, nullptr, nullptr, sp);
+        if (rc != SEPAIHRD_OK) return rc;
+    }
+    if (sc != sp) HIP_TRY(hipStreamWaitEvent(sc, pc->fd_ev_uploaded, 0), pc, return SEPAIHRD_E_HIP);
+    {
+        const int rc = sepaihrd_eval_batch_device(cc, d_theta, C, d_value, d_cstatus, nullptr, nullptr, nullptr, nullptr, sc);
+        if (rc != SEPAIHRD_OK) return bad(cc->last_error.c_str(), rc);
+    }
+    if (sc != sp) {
+        HIP_TRY(hipEventRecord(pc->fd_ev_centre, sc), pc, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipStreamWaitEvent(sp, pc->fd_ev_centre, 0), pc, return SEPAIHRD_E_HIP);
+    }
+    FdQuotientArgs qa{};
+    qa.C = C; qa.G = (int32_t)G; qa.P = (int32_t)P; qa.n = pc->dp.n; qa.lpc = pc->dp.lpc;
+    for (int j = 0; j < 8; ++j) qa.mult_index[j] = mult_index[j];
+    qa.rows = d_rows; qa.plus = d_plus; qa.eps = d_eps; qa.f_plus = d_fplus; qa.plus_status = d_pstatus;
+    qa.value = d_value; qa.centre_status = d_cstatus; qa.init_state = pc->dp.init_state; qa.N = pc->dp.N;
+    qa.grad = d_grad; qa.status = d_status;
+    if (launch_fd_quotient(qa, sp) != 0) return bad("quotient launch failed", SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpyAsync(pc->fd_host, d_value, result_bytes, hipMemcpyDeviceToHost, sp), pc, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipStreamSynchronize(sp), pc, return SEPAIHRD_E_HIP);
+    const char* h = static_cast<const char*>(pc->fd_host);
+    std::memcpy(value, h, nC * sizeof(double));
+    const double* hg = reinterpret_cast<const double*>(h) + nC;
+    for (size_t g = 0; g < G; ++g) std::memcpy(grad + (size_t)rows[g] * P, hg + g * P, P * sizeof(double));
+    std::memcpy(status, h + (nC + GP) * sizeof(double), nC * sizeof(int32_t));
+    return SEPAIHRD_OK;
 }
 
 int sepaihrd_set_initial_state_mode(sepaihrd_ctx* ctx, int mode) {

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .problem import SEPAIHRDProblem, SIRProblem
+from .problem import CONSTRAINT_CLAMP, SEPAIHRDProblem, SIRProblem
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsepaihrd_hip.so")
@@ -188,7 +188,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_create", "sepaihrd_destroy", "sepaihrd_last_error", "sepaihrd_abi_version",
     "sepaihrd_set_constraint_mode", "sepaihrd_set_arith", "sepaihrd_set_precision", "sepaihrd_set_integrator_form", "sepaihrd_eval_batch",
     "sepaihrd_eval_batch_device", "sepaihrd_eval_batch_begin", "sepaihrd_eval_batch_end", "sepaihrd_apply_constraints", "sepaihrd_get_kernel_info", "sepaihrd_get_kernel_info_for_batch", "sepaihrd_reserve",
-    "sepaihrd_set_timing", "sepaihrd_get_timing", "sepaihrd_set_initial_state_mode",
+    "sepaihrd_set_timing", "sepaihrd_get_timing", "sepaihrd_set_initial_state_mode", "sepaihrd_fd_gradient_batch",
     "sepaihrd_ensemble_quantiles", "sepaihrd_scenario_ensemble", "sepaihrd_mh_create", "sepaihrd_mh_destroy", "sepaihrd_mh_evaluate_current",
     "sepaihrd_mh_propose", "sepaihrd_mh_fetch", "sepaihrd_mh_stage_normals", "sepaihrd_mh_staging_buffer", "sepaihrd_mh_step", "sepaihrd_mh_read_best", "sepaihrd_mh_busy", "sepaihrd_mh_set_values", "sepaihrd_mh_test_buffer",
     "sepaihrd_mh_step_tested", "sepaihrd_mh_fetch_test", "sepaihrd_mh_commit", "sepaihrd_mh_adapt", "sepaihrd_mh_read_history",
@@ -266,6 +266,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_abi_version.argtypes = []
     lib.sepaihrd_eval_batch_begin.argtypes = [vp, vp, C.c_int]
     lib.sepaihrd_eval_batch_end.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_fd_gradient_batch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp]
     lib.sepaihrd_mh_stage_normals.argtypes = [vp, vp]
     lib.sepaihrd_mh_staging_buffer.restype = vp
     lib.sepaihrd_mh_staging_buffer.argtypes = [vp]
@@ -384,8 +385,13 @@ class HipObjective:
         if not self.ctx:
             raise RuntimeError("sepaihrd_create failed: " + err.value.decode())
         self.P, self.n, self.T = pb.n_params, pb.n, pb.n_times
+        self._device = device
+        self._fd_perturbed = None
 
     def close(self):
+        if getattr(self, "_fd_perturbed", None) is not None:
+            self._fd_perturbed.close()
+            self._fd_perturbed = None
         if getattr(self, "ctx", None):
             self.lib.sepaihrd_destroy(self.ctx)
             self.ctx = None
@@ -453,6 +459,54 @@ class HipObjective:
                                                  addr(d_n_accept), addr(d_n_reject), addr(d_ll_parts),
                                                  addr(d_traj), stream if stream else None)
         self._check(rc, "sepaihrd_eval_batch_device")
+
+    def fd_perturbed_objective(self) -> "HipObjective":
+        """The second context of the finite-difference objective for this problem (kept with this object): the perturbed
+        runs' rules -- clamp mode, the calibrated initial-state multipliers unbounded, the others 1.0, x(t0) always scaled
+        by the multipliers (SEPAIHRD_INIT_MULTIPLIERS) -- in this context's arithmetic."""
+        if getattr(self, "_fd_perturbed", None) is None:
+            pb = self.pb
+            codes, _ = pb.field_map()
+            bounds = dict(pb.bounds)
+            for nm, c in zip(pb.param_names, codes):
+                if 8 <= c <= 15:
+                    bounds[nm] = (-np.inf, np.inf)
+            other = HipObjective(pb.with_(bounds=bounds, constraint_mode=CONSTRAINT_CLAMP, multipliers=np.ones(8)),
+                                 device=getattr(self, "_device", -1))
+            other.set_initial_state_mode(2)
+            self._fd_perturbed = other
+        return self._fd_perturbed
+
+    def fd_gradient_batch(self, theta, want_grad=None, fd_epsilon: float = 1e-4, grad=None) -> dict:
+        """sepaihrd_fd_gradient_batch: forward-difference gradients of the C rows of theta in one pass, this context
+        evaluating the centres and fd_perturbed_objective() the C x P perturbed vectors.  want_grad [C] (None = all):
+        rows with 0 get their value only and their rows of `grad` (an optional array to fill, NaN otherwise) stay
+        untouched.  Row for row what HostObjective.evaluate_with_gradient returns; status [C] is the largest
+        per-evaluation status of each row."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        if th.ndim != 2 or th.shape[1] != self.P:
+            raise ValueError(f"theta must be C x {self.P}")
+        Cn = th.shape[0]
+        codes, _ = self.pb.field_map()
+        mult = np.full(8, -1, dtype=np.int32)
+        for k, c in enumerate(codes):
+            if 8 <= c <= 15 and mult[c - 8] < 0:
+                mult[c - 8] = k
+        want = None if want_grad is None else np.ascontiguousarray(want_grad, dtype=np.uint8)
+        if want is not None and want.shape != (Cn,):
+            raise ValueError("want_grad must have one entry per row")
+        value, status = np.empty(Cn), np.empty(Cn, dtype=np.int32)
+        if grad is None:
+            grad = np.full((Cn, self.P), np.nan)
+        if grad.shape != (Cn, self.P) or grad.dtype != np.float64 or not grad.flags.c_contiguous:
+            raise ValueError("grad must be a C-contiguous float64 array of theta's shape")
+        other = self.fd_perturbed_objective()
+        rc = self.lib.sepaihrd_fd_gradient_batch(self.ctx, other.ctx, th.ctypes.data, None if want is None else want.ctypes.data, Cn,
+                                                 float(fd_epsilon), mult.ctypes.data, value.ctypes.data, grad.ctypes.data,
+                                                 status.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_fd_gradient_batch failed ({rc}): " + self.lib.sepaihrd_last_error(other.ctx).decode())
+        return {"value": value, "grad": grad, "status": status}
 
     def set_timing(self, enable):
         """True / 1: events around every launch; k > 1: around every k-th launch; False / 0: off."""

@@ -196,7 +196,7 @@ protected:
 // unconstrained from the perturbed vector, 1.0 when not calibrated), invalid when the non-S total is
 // above N or negative (entry 0), likelihood over ALL output rows (a row count different from the
 // observations' makes every entry (lowest() - f) / eps, as in the reference).
-class HipSEPAIHRDGradientObjectiveFunction : public HipSEPAIHRDObjectiveFunction, public IGradientObjectiveFunction {
+class HipSEPAIHRDGradientObjectiveFunction : public HipSEPAIHRDObjectiveFunction, public IGradientObjectiveFunction, public IBatchGradientObjective {
 public:
     // SEPAIHRDGradientObjectiveFunction's constructor (SEPAIHRDModelCalibration.cpp:96-104), as above
     HipSEPAIHRDGradientObjectiveFunction(std::shared_ptr<AgeSEPAIHRDModel> model, IParameterManager& parameterManager,
@@ -214,6 +214,16 @@ public:
     double evaluate_with_gradient(const Eigen::VectorXd& params, Eigen::VectorXd& grad) const override;
     double calculate(const Eigen::VectorXd& parameters) const override { return HipSEPAIHRDObjectiveFunction::calculate(parameters); }
     const std::vector<std::string>& getParameterNames() const override { return HipSEPAIHRDObjectiveFunction::getParameterNames(); }
+    // IBatchGradientObjective: row b is what evaluate_with_gradient(thetas[b]) (want_gradient[b] != 0) or the evaluation
+    // behind calculate(thetas[b]) returns, bit for bit, all rows in ONE sepaihrd_fd_gradient_batch over this object's two
+    // contexts, epsilon_ and multiplier indices.  The simulation cache is not consulted or filled: rows of different chains
+    // must not meet in it (it keys on theta quantised to 1e-8).  Integration failures do not throw here: status[b] is the
+    // largest per-evaluation status of the row (the centre's and, where a gradient was wanted, its P perturbed runs').  The
+    // rule for grids with run-up rows (every quotient from lowest()) and the refusal of grids that start before t = 0 are
+    // applied as in evaluate_with_gradient.  Throws ModelException when the call fails.
+    void evaluateRows(const double* thetas, const uint8_t* want_gradient, int B, int P, double* values, double* gradients,
+                      int32_t* status) override;
+    sepaihrd_ctx* gradientContext() const { return grad_ctx_; }
 private:
     void buildGradientContext(const CalibrationData& data, const std::vector<double>& time_points,
                               const std::shared_ptr<IOdeSolverStrategy>& solver_strategy, double abs_error, double rel_error,

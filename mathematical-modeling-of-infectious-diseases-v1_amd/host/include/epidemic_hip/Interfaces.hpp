@@ -11,6 +11,7 @@
 // Inside the reference tree these declarations are replaced by the reference's own headers (see
 // INTEGRATION.md); nothing here adds or changes a virtual.
 #pragma once
+#include <cstdint>
 #include <functional>
 #include <limits>
 #include <map>
@@ -75,6 +76,16 @@ class IBatchObjectiveFunction {
 public:
     virtual ~IBatchObjectiveFunction() = default;
     virtual void calculateBatch(const double* thetas, int B, double* out, int* status = nullptr) const = 0;
+};
+
+// Build-side addition (MultiChainNUTSSampler): B evaluations, each with or without its gradient, in one call.
+// Rows of theta plus a flag in; values, gradients and statuses out.  Row b of `grad` is written only where
+// want_gradient[b] != 0.  status[b] >= 2: the row produced no value (integration failure).  Throws when the call itself fails.
+class IBatchGradientObjective {
+public:
+    virtual ~IBatchGradientObjective() = default;
+    virtual void evaluateRows(const double* thetas, const uint8_t* want_gradient, int B, int P, double* values, double* gradients,
+                              int32_t* status) = 0;
 };
 
 // include/model/interfaces/IGradientObjectiveFunction.hpp

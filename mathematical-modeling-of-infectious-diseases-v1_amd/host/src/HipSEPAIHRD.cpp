@@ -661,4 +661,41 @@ double HipSEPAIHRDGradientObjectiveFunction::evaluate_with_gradient(const Eigen:
     return f_center;
 }
 
+void HipSEPAIHRDGradientObjectiveFunction::evaluateRows(const double* thetas, const uint8_t* want_gradient, int B, int P,
+                                                        double* values, double* gradients, int32_t* status) {
+    const char* W = "SEPAIHRDGradientObjectiveFunction";
+    if (B <= 0) return;
+    if (static_cast<size_t>(P) != pm_.getParameterCount()) throw InvalidParameterException(W, "evaluateRows: rows of another parameter count");
+    bool any_gradient = false;
+    for (int b = 0; b < B; ++b) any_gradient = any_gradient || !want_gradient || want_gradient[b];
+    const bool rows_match = n_times_ == n_obs_rows_;
+    if (any_gradient && rows_match && first_time_ < 0.0)
+        throw InvalidParameterException(W, "output grids that start before t = 0 with one observation row per output are not built");
+    syncConstraintMode();
+    static_assert(sizeof(int) == sizeof(int32_t), "mult_index_ is handed to the C ABI as int32_t");
+    const int32_t* mult = reinterpret_cast<const int32_t*>(mult_index_.data());
+    // with run-up output rows no perturbed value is used (see below): centre values only
+    const std::vector<uint8_t> none(rows_match ? 0 : static_cast<size_t>(B), 0);
+    if (sepaihrd_fd_gradient_batch(ctx_, grad_ctx_, thetas, rows_match ? want_gradient : none.data(), B, epsilon_, mult, values,
+                                   gradients, status) != SEPAIHRD_OK)
+        throw ModelException(W, std::string("sepaihrd_fd_gradient_batch failed: ") + sepaihrd_last_error(grad_ctx_));
+    if (rows_match || !any_gradient) return;
+    // every perturbed likelihood fails its dimension check: lowest() in place of f_i, validity and step as always
+    const double LOWEST = std::numeric_limits<double>::lowest();
+    std::vector<double> plus(static_cast<size_t>(P));
+    for (int b = 0; b < B; ++b) {
+        if (want_gradient && !want_gradient[b]) continue;
+        const double* th = thetas + static_cast<size_t>(b) * P;
+        double* g = gradients + static_cast<size_t>(b) * P;
+        for (int i = 0; i < P; ++i) {
+            g[i] = 0.0;
+            if (!std::isfinite(values[b])) continue;
+            const double step = epsilon_ * std::max(std::abs(th[i]), epsilon_);
+            std::copy(th, th + P, plus.begin());
+            plus[static_cast<size_t>(i)] += step;
+            if (initialStateValid(plus.data())) g[i] = (LOWEST - values[b]) / step;
+        }
+    }
+}
+
 }  // namespace epidemic

@@ -1,5 +1,7 @@
 // host_capi.cpp -- flat C entry points over the C++ host mirror, for the Python test-suite only.
 // The layout of `sepaihrd_problem` is reused as the carrier of the model / data arrays.
+#include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -10,6 +12,7 @@
 #include "epidemic_hip/BatchedParticleSwarm.hpp"
 #include "epidemic_hip/HipModelCalibrator.hpp"
 #include "epidemic_hip/HipNUTSSampler.hpp"
+#include "epidemic_hip/MultiChainNUTSSampler.hpp"
 #include "epidemic_hip/HipPosteriorEnsemble.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipSIR.hpp"
@@ -52,6 +55,138 @@ Eigen::VectorXd vec(const double* p, int n) {
 thread_local std::string g_error;
 thread_local double g_last_mh_loop_seconds = 0.0;
 thread_local double g_last_diag_seconds = 0.0;
+
+// ---- lock-step No-U-Turn chains (MultiChainNUTSSampler): output plumbing shared by the device run and the analytic hook
+struct NutsChainsOut {
+    int iterations, P;
+    double *samples, *values, *eps_trace;   // [C][iterations][P], [C][iterations] x 2; NaN beyond a chain's n_samples
+    int32_t *depth_trace, *n_samples;       // [C][iterations] (-2 beyond n_samples), [C]
+    double *best, *best_value;              // [C][P], [C]
+    int64_t *gradient_calls, *rows_evaluated;  // [C] x 2
+    int32_t *failure_status, *failure_iteration;  // [C] x 2
+    void put(int c, const NUTSChainResult& r) const {
+        const size_t N = static_cast<size_t>(iterations), Pz = static_cast<size_t>(P), base = static_cast<size_t>(c) * N;
+        const double nan = std::nan("");
+        const size_t ns = std::min(r.samples.size(), N);
+        for (size_t s = 0; s < N; ++s) {
+            for (size_t i = 0; i < Pz; ++i) samples[(base + s) * Pz + i] = s < ns ? r.samples[s][i] : nan;
+            values[base + s] = s < ns ? r.sample_values[s] : nan;
+            eps_trace[base + s] = s < ns ? r.epsilon_trace[s] : nan;
+            depth_trace[base + s] = s < ns ? r.depth_trace[s] : -2;
+        }
+        n_samples[c] = static_cast<int32_t>(ns);
+        for (size_t i = 0; i < Pz; ++i) best[static_cast<size_t>(c) * Pz + i] = r.best_parameters.size() == Pz ? r.best_parameters[i] : nan;
+        best_value[c] = r.best_value;
+        gradient_calls[c] = r.gradient_calls;
+        rows_evaluated[c] = r.rows_evaluated;
+        failure_status[c] = r.failure_status;
+        failure_iteration[c] = r.failure_iteration;
+    }
+};
+std::map<std::string, double> nuts_settings(int iterations, int adaptation_window, double delta_target, int max_tree_depth, uint32_t seed) {
+    return {{"nuts_iterations", double(iterations)}, {"nuts_adaptation_window", double(adaptation_window)},
+            {"nuts_delta_target", delta_target}, {"nuts_max_tree_depth", double(max_tree_depth)}, {"seed", double(seed)}};
+}
+std::vector<std::vector<double>> chain_starts(const double* theta0, int C, int P) {
+    std::vector<std::vector<double>> starts(static_cast<size_t>(C));
+    for (int c = 0; c < C; ++c) starts[static_cast<size_t>(c)].assign(theta0 + static_cast<size_t>(c) * P, theta0 + static_cast<size_t>(c + 1) * P);
+    return starts;
+}
+
+// The device objective behind a stopwatch: wall time inside the batched evaluation and, when asked, the evaluation
+// kernels' time from the two contexts' event timers (collected every tick: the call has just waited for its results).
+class TimedRows : public IBatchGradientObjective {
+public:
+    TimedRows(HipSEPAIHRDGradientObjectiveFunction& obj, bool kernel_timing) : obj_(obj), timing_(kernel_timing) {
+        if (timing_) { sepaihrd_set_timing(obj_.deviceContext(), 1); sepaihrd_set_timing(obj_.gradientContext(), 1); }
+    }
+    ~TimedRows() override {
+        if (timing_) { sepaihrd_set_timing(obj_.deviceContext(), 0); sepaihrd_set_timing(obj_.gradientContext(), 0); }
+    }
+    void evaluateRows(const double* thetas, const uint8_t* want, int B, int P, double* values, double* grads, int32_t* status) override {
+        const auto t0 = std::chrono::steady_clock::now();
+        obj_.evaluateRows(thetas, want, B, P, values, grads, status);
+        call_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (!timing_) return;
+        double a = 0.0, b = 0.0;
+        int n = 0;
+        if (sepaihrd_get_timing(obj_.deviceContext(), &a, &b, &n) == SEPAIHRD_OK) centre_ms += a + b;
+        if (sepaihrd_get_timing(obj_.gradientContext(), &a, &b, &n) == SEPAIHRD_OK) perturbed_ms += a + b;
+    }
+    double call_seconds = 0.0, centre_ms = 0.0, perturbed_ms = 0.0;
+private:
+    HipSEPAIHRDGradientObjectiveFunction& obj_;
+    bool timing_;
+};
+
+// Test objective (no GPU): log-density of a correlated Gaussian, -1/2 (x - mean)' A (x - mean), with its exact gradient;
+// inside the ball |x - fail_centre| < fail_radius (radius > 0) an evaluation reports an integration failure instead.
+class AnalyticGaussian : public IGradientObjectiveFunction, public IBatchGradientObjective {
+public:
+    AnalyticGaussian(int D, const double* mean, const double* precision, const double* fail_centre, double fail_radius)
+        : D_(D), mean_(mean, mean + D), A_(precision, precision + static_cast<size_t>(D) * D),
+          fail_centre_(fail_centre ? std::vector<double>(fail_centre, fail_centre + D) : std::vector<double>()), fail_radius_(fail_radius) {
+        for (int i = 0; i < D; ++i) names_.push_back("x" + std::to_string(i));
+    }
+    bool fails(const double* x) const {
+        if (fail_centre_.empty() || !(fail_radius_ > 0.0)) return false;
+        double sq = 0.0;
+        for (int i = 0; i < D_; ++i) sq += (x[i] - fail_centre_[static_cast<size_t>(i)]) * (x[i] - fail_centre_[static_cast<size_t>(i)]);
+        return sq < fail_radius_ * fail_radius_;
+    }
+    double density(const double* x, double* grad) const {
+        double quad = 0.0;
+        for (int i = 0; i < D_; ++i) {
+            double row = 0.0;
+            for (int j = 0; j < D_; ++j) row += A_[static_cast<size_t>(i) * D_ + j] * (x[j] - mean_[static_cast<size_t>(j)]);
+            if (grad) grad[i] = -row;
+            quad += (x[i] - mean_[static_cast<size_t>(i)]) * row;
+        }
+        return -0.5 * quad;
+    }
+    double calculate(const Eigen::VectorXd& x) const override {
+        if (fails(x.data())) HipSEPAIHRDObjectiveFunction::throwIntegrationFailure(SEPAIHRD_STATUS_STEP_FAILURE);
+        return density(x.data(), nullptr);
+    }
+    double evaluate_with_gradient(const Eigen::VectorXd& x, Eigen::VectorXd& grad) const override {
+        if (fails(x.data())) HipSEPAIHRDObjectiveFunction::throwIntegrationFailure(SEPAIHRD_STATUS_STEP_FAILURE);
+        grad.resize(D_);
+        return density(x.data(), grad.data());
+    }
+    const std::vector<std::string>& getParameterNames() const override { return names_; }
+    void evaluateRows(const double* thetas, const uint8_t* want, int B, int P, double* values, double* grads, int32_t* status) override {
+        for (int b = 0; b < B; ++b) {
+            const double* x = thetas + static_cast<size_t>(b) * P;
+            status[b] = fails(x) ? SEPAIHRD_STATUS_STEP_FAILURE : SEPAIHRD_STATUS_OK;
+            values[b] = density(x, !want || want[b] ? grads + static_cast<size_t>(b) * P : nullptr);
+        }
+    }
+private:
+    int D_;
+    std::vector<double> mean_, A_, fail_centre_;
+    double fail_radius_;
+    std::vector<std::string> names_;
+};
+// the manager of the analytic objective: unconstrained, one sigma for every coordinate
+class FreeManager : public IParameterManager {
+public:
+    FreeManager(int D, double sigma) : D_(D), sigma_(sigma) {
+        for (int i = 0; i < D; ++i) names_.push_back("x" + std::to_string(i));
+    }
+    Eigen::VectorXd getCurrentParameters() const override { return Eigen::VectorXd(D_); }
+    void updateModelParameters(const Eigen::VectorXd&) override {}
+    const std::vector<std::string>& getParameterNames() const override { return names_; }
+    size_t getParameterCount() const override { return static_cast<size_t>(D_); }
+    double getSigmaForParamIndex(int) const override { return sigma_; }
+    Eigen::VectorXd applyConstraints(const Eigen::VectorXd& x) const override { return x; }
+    int getIndexForParam(const std::string&) const override { return -1; }
+    double getLowerBoundForParamIndex(int) const override { return -std::numeric_limits<double>::infinity(); }
+    double getUpperBoundForParamIndex(int) const override { return std::numeric_limits<double>::infinity(); }
+private:
+    int D_;
+    double sigma_;
+    std::vector<std::string> names_;
+};
 }  // namespace
 
 namespace epidemic {
@@ -640,6 +775,97 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
         if (gradient_calls) *gradient_calls = nuts.gradientCalls();
         if (gradient_launches) *gradient_launches = nuts.gradientLaunches();
         return ns;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return -1;
+    }
+}
+
+// MultiChainNUTSSampler over the handle's finite-difference objective: C chains in lock step, chain c from theta0[c] with
+// std::mt19937(seed0 + c); the other arguments as host_nuts_run.  Outputs have a leading chain axis (see NutsChainsOut).
+// stats [6]: ticks, rows evaluated, seconds of the whole run, seconds inside the batched evaluations, milliseconds of the
+// evaluation kernels of the centre and of the perturbed context (0 unless kernel_timing).  Returns 0, or -1 on an
+// exception (message in host_last_error).
+int host_nuts_chains_run(void* hv, const sepaihrd_problem* pb, int device, int iterations, int adaptation_window, double delta_target,
+                         int max_tree_depth, double fd_epsilon, int constraint_mode, int C, const double* theta0, uint32_t seed0,
+                         int kernel_timing, double* samples, double* values, double* eps_trace, int32_t* depth_trace, int32_t* n_samples,
+                         double* best, double* best_value, int64_t* gradient_calls, int64_t* rows_evaluated, int32_t* failure_status,
+                         int32_t* failure_iteration, double* stats) {
+    auto* h = static_cast<HostHandle*>(hv);
+    try {
+        const int n = pb->n_age;
+        const int P = static_cast<int>(h->pm->getParameterCount());
+        h->pm->setConstraintMode(constraint_mode == 0 ? ConstraintMode::OPTIMIZATION_CLAMP : ConstraintMode::MCMC_REFLECT);
+        SimulationCache cache(16);  // the constructor's argument; the lock-step run never consults it
+        HipSEPAIHRDGradientObjectiveFunction obj(*h->pm, cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
+                                                 vec(pb->initial_state, 11 * n), strategy_for(pb->solver), pb->abs_err, pb->rel_err,
+                                                 device, pb->arith == SEPAIHRD_ARITH_FMA);
+        obj.epsilon_ = fd_epsilon;
+        TimedRows rows(obj, kernel_timing != 0);
+        MultiChainNUTSSampler nuts;
+        nuts.configure(nuts_settings(iterations, adaptation_window, delta_target, max_tree_depth, seed0));
+        const auto t0 = std::chrono::steady_clock::now();
+        const MultiChainNUTSResult r = nuts.run(chain_starts(theta0, C, P), rows, *h->pm);
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        const NutsChainsOut out{iterations, P, samples, values, eps_trace, depth_trace, n_samples, best, best_value,
+                                gradient_calls, rows_evaluated, failure_status, failure_iteration};
+        for (int c = 0; c < C; ++c) out.put(c, r.chains[static_cast<size_t>(c)]);
+        const double st[6] = {double(r.ticks), double(r.rows_total), seconds, rows.call_seconds, rows.centre_ms, rows.perturbed_ms};
+        if (stats) std::copy(st, st + 6, stats);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return -1;
+    }
+}
+
+// Test hook (no GPU): the same sampler over AnalyticGaussian (dimension D, mean [D], precision [D][D] row-major, optional
+// failure ball).  lock_step != 0: MultiChainNUTSSampler; 0: chain by chain through HipNUTSSampler with seed0 + c on the
+// same objective -- a chain whose evaluation fails there loses its samples with the exception (failure_status 2,
+// n_samples 0; rows_evaluated = its launches otherwise).  stats [6] as host_nuts_chains_run, the clocks 0.
+int host_nuts_chains_analytic(int D, const double* mean, const double* precision, double sigma, const double* fail_centre,
+                              double fail_radius, int lock_step, int iterations, int adaptation_window, double delta_target,
+                              int max_tree_depth, int C, const double* theta0, uint32_t seed0, double* samples, double* values,
+                              double* eps_trace, int32_t* depth_trace, int32_t* n_samples, double* best, double* best_value,
+                              int64_t* gradient_calls, int64_t* rows_evaluated, int32_t* failure_status, int32_t* failure_iteration,
+                              double* stats) {
+    try {
+        AnalyticGaussian obj(D, mean, precision, fail_centre, fail_radius);
+        FreeManager pm(D, sigma);
+        const NutsChainsOut out{iterations, D, samples, values, eps_trace, depth_trace, n_samples, best, best_value,
+                                gradient_calls, rows_evaluated, failure_status, failure_iteration};
+        double st[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (lock_step) {
+            MultiChainNUTSSampler nuts;
+            nuts.configure(nuts_settings(iterations, adaptation_window, delta_target, max_tree_depth, seed0));
+            const MultiChainNUTSResult r = nuts.run(chain_starts(theta0, C, D), obj, pm);
+            for (int c = 0; c < C; ++c) out.put(c, r.chains[static_cast<size_t>(c)]);
+            st[0] = double(r.ticks);
+            st[1] = double(r.rows_total);
+        } else {
+            for (int c = 0; c < C; ++c) {
+                NUTSChainResult one;
+                HipNUTSSampler solo;
+                solo.configure(nuts_settings(iterations, adaptation_window, delta_target, max_tree_depth, seed0 + static_cast<uint32_t>(c)));
+                try {
+                    const OptimizationResult r = solo.optimize(vec(theta0 + static_cast<size_t>(c) * D, D), obj, pm);
+                    for (const Eigen::VectorXd& x : r.samples) one.samples.emplace_back(x.data(), x.data() + D);
+                    one.sample_values = r.sampleObjectiveValues;
+                    one.epsilon_trace = solo.epsilonTrace();
+                    one.depth_trace = solo.depthTrace();
+                    if (r.bestParameters.size() == D) one.best_parameters.assign(r.bestParameters.data(), r.bestParameters.data() + D);
+                    one.best_value = r.bestObjectiveValue;
+                } catch (const SimulationException&) {
+                    one.failure_status = SEPAIHRD_STATUS_STEP_FAILURE;
+                }
+                one.gradient_calls = solo.gradientCalls();
+                one.rows_evaluated = solo.gradientLaunches();
+                out.put(c, one);
+                st[1] += double(one.rows_evaluated);
+            }
+        }
+        if (stats) std::copy(st, st + 6, stats);
+        return 0;
     } catch (const std::exception& e) {
         g_error = e.what();
         return -1;

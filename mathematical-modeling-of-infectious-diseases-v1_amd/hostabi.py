@@ -54,6 +54,10 @@ def load_library() -> C.CDLL:
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.host_nuts_run.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                   C.c_double, C.c_int, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.host_nuts_chains_run.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                         C.c_double, C.c_int, C.c_int, vp, C.c_uint32, C.c_int] + [vp] * 12
+    lib.host_nuts_chains_analytic.argtypes = [C.c_int, vp, vp, C.c_double, vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double,
+                                              C.c_int, C.c_int, vp, C.c_uint32] + [vp] * 12
     lib.host_pso_run.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.host_ensemble.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32,
                                   vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
@@ -91,6 +95,43 @@ def load_library() -> C.CDLL:
                                        C.POINTER(C.c_double), vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     _lib = lib
     return lib
+
+
+def _nuts_chains_outputs(Cn: int, iterations: int, P: int):
+    """Arrays of a lock-step NUTS run, leading axis = chain, and their pointers in the order of the C entry points."""
+    out = {"samples": np.empty((Cn, iterations, P)), "sample_values": np.empty((Cn, iterations)),
+           "epsilon_trace": np.empty((Cn, iterations)), "depth_trace": np.empty((Cn, iterations), dtype=np.int32),
+           "n_samples": np.empty(Cn, dtype=np.int32), "best": np.empty((Cn, P)), "best_value": np.empty(Cn),
+           "gradient_calls": np.empty(Cn, dtype=np.int64), "rows_evaluated": np.empty(Cn, dtype=np.int64),
+           "failure_status": np.empty(Cn, dtype=np.int32), "failure_iteration": np.empty(Cn, dtype=np.int32)}
+    stats = np.zeros(6)
+    return out, stats, [a.ctypes.data for a in out.values()] + [stats.ctypes.data]
+
+
+def nuts_chains_analytic(mean, precision, theta0, seed0: int, iterations: int, adaptation_window: int, max_tree_depth: int = 10,
+                         delta_target: float = 0.8, sigma: float = 1.0, lock_step: bool = True, fail_centre=None,
+                         fail_radius: float = 0.0) -> dict:
+    """Test hook without a GPU (host_nuts_chains_analytic): the lock-step sampler, or chain by chain HipNUTSSampler
+    (lock_step=False), over the log-density of a Gaussian with the given mean and precision matrix and its exact gradient;
+    inside the ball (fail_centre, fail_radius) the objective reports an integration failure.  Result as
+    HostObjective.nuts_chains."""
+    lib = load_library()
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    prec = np.ascontiguousarray(precision, dtype=np.float64)
+    th = np.ascontiguousarray(np.atleast_2d(theta0), dtype=np.float64)
+    D = mean.shape[0]
+    if prec.shape != (D, D) or th.shape[1] != D:
+        raise ValueError("mean [D], precision [D][D], theta0 [C][D]")
+    fc = None if fail_centre is None else np.ascontiguousarray(fail_centre, dtype=np.float64)
+    out, stats, ptrs = _nuts_chains_outputs(th.shape[0], iterations, D)
+    rc = lib.host_nuts_chains_analytic(D, mean.ctypes.data, prec.ctypes.data, sigma, None if fc is None else fc.ctypes.data,
+                                       fail_radius, int(lock_step), iterations, adaptation_window, delta_target, max_tree_depth,
+                                       th.shape[0], th.ctypes.data, seed0, *ptrs)
+    if rc != 0:
+        raise RuntimeError("host_nuts_chains_analytic: " + lib.host_last_error().decode())
+    out.update(ticks=int(stats[0]), rows_total=int(stats[1]),
+               mean_rows_per_tick=stats[1] / stats[0] if stats[0] > 0 else 0.0)
+    return out
 
 
 class HostObjective:
@@ -188,6 +229,30 @@ class HostObjective:
             raise RuntimeError("host_nuts_run: " + self.lib.host_last_error().decode())
         return {"samples": samples[:ns], "sample_values": values[:ns], "epsilon_trace": eps[:ns], "depth_trace": depth[:ns],
                 "best": best, "best_value": bv.value, "gradient_calls": nc.value, "gradient_launches": nl.value}
+
+    def nuts_chains(self, theta0, seed0: int, iterations: int, adaptation_window: int, max_tree_depth: int = 10,
+                    delta_target: float = 0.8, fd_epsilon: float = 1e-4, constraint_mode: int = 1, device: int = -1,
+                    kernel_timing: bool = False) -> dict:
+        """MultiChainNUTSSampler: C = len(theta0) No-U-Turn chains in lock step over the finite-difference objective,
+        chain c from theta0[c] with std::mt19937(seed0 + c) -- each equal to nuts(theta0[c], seed0 + c, ...) -- every
+        tick's requests in one sepaihrd_fd_gradient_batch.  Arrays have a leading chain axis: samples [C][iterations][P]
+        and sample_values [C][iterations] go straight into chain_diagnostics (rows past n_samples[c] are NaN: a chain
+        that stopped on an integration failure, failure_status[c] >= 2 in iteration failure_iteration[c], or began
+        with non-finite values); gradient_calls counts what nuts() counts, rows_evaluated the rows that ran."""
+        th = np.ascontiguousarray(np.atleast_2d(theta0), dtype=np.float64)
+        if th.shape[1] != self.P:
+            raise ValueError(f"theta0 must be C x {self.P}")
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        out, stats, ptrs = _nuts_chains_outputs(th.shape[0], iterations, self.P)
+        rc = self.lib.host_nuts_chains_run(self.h, C.byref(st), device, iterations, adaptation_window, delta_target,
+                                           max_tree_depth, fd_epsilon, constraint_mode, th.shape[0], th.ctypes.data, seed0,
+                                           int(kernel_timing), *ptrs)
+        if rc != 0:
+            raise RuntimeError("host_nuts_chains_run: " + self.lib.host_last_error().decode())
+        out.update(ticks=int(stats[0]), rows_total=int(stats[1]), mean_rows_per_tick=stats[1] / stats[0] if stats[0] > 0 else 0.0,
+                   seconds=stats[2], evaluation_seconds=stats[3], centre_kernel_ms=stats[4], perturbed_kernel_ms=stats[5])
+        return out
 
     def calibrate(self, hc_seed: int, mh_seed: int, hc_iterations: int, mh_iterations: int, burn_in: int,
                   cloud_size_multiplier: int = 8, threads: int = 16, adaptation_period: int = 100, thinning: int = 1,
