@@ -761,6 +761,61 @@ int sepaihrd_sir_ensemble_quantiles(sepaihrd_sir_ctx *ctx, const double *theta, 
  * scenario summaries. */
 int sepaihrd_sir_ensemble_timing(const sepaihrd_sir_ctx *ctx, int64_t *calls, double *ms);
 
+/* ---- stochastic chain-binomial SIR ensembles (the reference's StochasticSIRModel, src/base/SIR_stochastic.cpp) ----
+ * n_replicates independent replicates of each of n_groups parameter sets, one lane per replicate, the step loop inside the
+ * kernel (csrc/sepaihrd_stoch_sir.hip), then per (group, compartment, step) the mean, median, 5 % and 95 % point across the
+ * replicates.  No context: each call names its device.
+ *
+ * One step of one replicate, as the reference takes it (:152-207): S_int = (int)round(S), I_int = (int)round(I); if either
+ * is <= 0 the next row is a copy of this one (so recoveries stop too once S reaches 0); otherwise
+ * pI = 1 - exp(-(beta I h / N)) with the double I and the group's N, pR = 1 - exp(-gamma h), both clamped to [0, 1],
+ * I_new ~ Binomial(S_int, pI) then R_new ~ Binomial(I_int, pR), S' = max(0, S_int - I_new), I' = max(0, I_int + I_new -
+ * R_new), R' = max(0, R + R_new).  Row 0 is (S0, I0, R0); steps = (int)round((t_end - t_start) / h) + 1.
+ *
+ * The random stream is this build's own (the reference seeds one serial generator from the clock): every variate is a
+ * function of (seed, group, replicate, step, transition, attempt) through Philox-4x32-10, csrc/sepaihrd_stoch.inc says how.
+ * A replicate's path therefore depends on nothing else: not on n_replicates, keep, the launch or max_workspace_bytes. */
+typedef struct sepaihrd_stoch_sir_group {
+    double N, beta, gamma, S0, I0, R0;
+} sepaihrd_stoch_sir_group;
+typedef struct sepaihrd_stoch_sir_config {
+    int32_t abi_version; /* SEPAIHRD_ABI_VERSION */
+    int32_t n_groups, n_replicates;
+    int32_t keep; /* replicates 0 .. keep - 1 of every group have their trajectories returned (0 <= keep <= n_replicates) */
+    double t_start, t_end, h;
+    uint64_t seed;
+    /* Device memory the call may hold for trajectories at one time; the time axis is processed in chunks of whole steps
+     * that fit (at least one step), the replicates' states carried between chunks.  Same results for every value.
+     * 0: SEPAIHRD_STOCH_SIR_DEFAULT_WORKSPACE. */
+    uint64_t max_workspace_bytes;
+} sepaihrd_stoch_sir_config;
+#define SEPAIHRD_STOCH_SIR_DEFAULT_WORKSPACE ((uint64_t)4 << 30) /* 4 GiB */
+#define SEPAIHRD_STOCH_SIR_MAX_REPLICATES (1 << 24)
+/* number of rows, or a negative code when the arguments give none (h <= 0, t_end <= t_start, not finite, beyond 2^31 - 1) */
+int64_t sepaihrd_stoch_sir_num_steps(double t_start, double t_end, double h);
+/* Host only.  SEPAIHRD_E_INVALID_ARG with a message in err (NULL: not wanted) unless, for every group: N > 0; beta, gamma,
+ * S0, I0, R0 >= 0; |S0 + I0 + R0 - N| <= 1e-6 N (the reference's constructor, :29-34) -- and h > 0, t_end > t_start,
+ * n_replicates >= 1.  This build adds, because the compartments are int: everything finite, N <= 2^31 - 1, round(S0) +
+ * round(I0) <= 2^31 - 1, steps <= 2^31 - 1; and n_groups in [1, 2^30], n_replicates <= SEPAIHRD_STOCH_SIR_MAX_REPLICATES,
+ * keep in [0, n_replicates], abi_version. */
+int sepaihrd_stoch_sir_validate(const sepaihrd_stoch_sir_config *config, const sepaihrd_stoch_sir_group *groups, char *err, int errlen);
+/* device: a HIP device index, -1 = the current one.  Outputs are host memory:
+ *   stats        [n_groups][4][3][steps]  mean, median, 5 %, 95 % of S, I, R across the replicates: ascending sort, the mean by
+ *                m += (x_i - m) / (i + 1) over the sorted values, the median the middle value or the mean of the two middle
+ *                ones, quantile f as (1 - d) x[lhs] + d x[lhs + 1] with lhs = (int)(f (R - 1)), d its fraction
+ *   traj         [n_groups][keep][3][steps], or NULL
+ *   final_state  [n_groups][n_replicates][3], or NULL
+ *   phase_ms     [3] device time in ms of the step kernels, of the segment sorts and of the summaries (up to 16384
+ *                replicates sort and summary are one kernel, counted under the sorts), or NULL
+ * Up to 16384 replicates a segment is sorted in LDS, beyond by a segmented radix sort.  Refused arguments
+ * (sepaihrd_stoch_sir_validate, a NULL stats) return SEPAIHRD_E_INVALID_ARG before the device is touched. */
+int sepaihrd_stoch_sir_run(int device, const sepaihrd_stoch_sir_config *config, const sepaihrd_stoch_sir_group *groups, double *stats,
+                           double *traj, double *final_state, double *phase_ms, char *err, int errlen);
+/* Probe of the device's sampler: out[i] ~ Binomial(n[i], p[i]), the variate at (seed, group 0, replicate i, step 0,
+ * infection).  n [count] >= 0, p [count], out [count], host memory. */
+int sepaihrd_stoch_sir_binomial_device(int device, uint64_t seed, const int32_t *n, const double *p, int count, int32_t *out, char *err,
+                                       int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,8 @@
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_sir_device.h"
+#include "sepaihrd_stoch_device.h"
+#include "sepaihrd_stoch.inc"
 
 namespace sepaihrd {
 namespace {
@@ -809,6 +811,71 @@ int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
     sa.summary_out = a.summary_out; sa.diff_out = a.diff_out;
     sa.sort_scratch = a.sort_scratch; sa.sort_scratch_doubles = a.sort_scratch_doubles;
     return launch_scenario_summaries(sa, stream);
+}
+
+}  // namespace sepaihrd
+
+// ---- stochastic SIR ensembles (sepaihrd_stoch_sir_run): mean, median, 5 % and 95 % of every (group, compartment, step)
+// segment across the replicates, with the segment sorts above ----
+namespace sepaihrd {
+namespace {
+
+// statistic `stat` of sorted segment `sid` of the chunk into stats[g][stat][compartment][step0 + local step]
+__device__ __forceinline__ void stoch_write_stat(const StochSummaryArgs& a, size_t sid, int stat, const double* seg) {
+    const int s = (int)(sid % (size_t)a.chunk_steps);
+    const size_t gc = sid / (size_t)a.chunk_steps;  // group 3 + compartment
+    const size_t g = gc / 3, comp = gc % 3;
+    a.stats[((g * 4 + (size_t)stat) * 3 + comp) * (size_t)a.steps + (size_t)(a.step0 + s)] = sepaihrd_stoch::sorted_stat(seg, a.R, stat);
+}
+
+// one workgroup per segment: bitonic sort in LDS, then one thread per statistic (the mean's recurrence is serial)
+__global__ void stoch_sir_summary_kernel(const StochSummaryArgs a) {
+    extern __shared__ double seg[];
+    const size_t sid = blockIdx.x;
+    lds_bitonic_sort(seg, a.vals + sid * (size_t)a.R_pad, a.R_pad);
+    if (threadIdx.x < 4) stoch_write_stat(a, sid, (int)threadIdx.x, seg);
+}
+
+// beyond the LDS sort: one thread per (segment, statistic) of a group of globally sorted segments
+__global__ __launch_bounds__(64) void stoch_sir_summary_sorted_kernel(const StochSummaryArgs a, const double* sorted, const int first_segment,
+                                                                      const int n_group) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)n_group * 4) return;
+    const int g = (int)(idx / 4), stat = (int)(idx % 4);
+    stoch_write_stat(a, (size_t)(first_segment + g), stat, sorted + (size_t)g * a.R_pad);
+}
+
+}  // namespace
+
+int launch_stoch_sir_summaries(const StochSummaryArgs& a, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool in_lds = a.R_pad <= ENSEMBLE_MAX_SAMPLES;
+    const size_t segments = (size_t)a.G * 3 * (size_t)a.chunk_steps;
+    if (a.G <= 0 || a.R <= 0 || a.chunk_steps <= 0 || a.step0 < 0 || a.step0 + a.chunk_steps > a.steps || a.R_pad < WAVE || a.R > a.R_pad ||
+        segments >= ((size_t)1 << 31) || (in_lds ? (a.R_pad & (a.R_pad - 1)) != 0 : a.R_pad % WAVE != 0))
+        return -4;
+    if (!in_lds)
+        return sort_segments_global(a.vals, (int)segments, a.R_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
+            const bool timed = a.summary_ms != nullptr && a.ev[0] != nullptr && a.ev[1] != nullptr;
+            if (timed) (void)hipEventRecord(static_cast<hipEvent_t>(a.ev[0]), st);
+            hipLaunchKernelGGL(stoch_sir_summary_sorted_kernel, dim3((unsigned)(((size_t)ng * 4 + 63) / 64)), dim3(64), 0, st, a,
+                               a.sort_scratch, first, ng);
+            if (timed) {
+                float ms = 0.0f;
+                (void)hipEventRecord(static_cast<hipEvent_t>(a.ev[1]), st);
+                if (hipEventSynchronize(static_cast<hipEvent_t>(a.ev[1])) == hipSuccess &&
+                    hipEventElapsedTime(&ms, static_cast<hipEvent_t>(a.ev[0]), static_cast<hipEvent_t>(a.ev[1])) == hipSuccess)
+                    *a.summary_ms += (double)ms;
+            }
+        });
+    const int threads = a.R_pad / 2 < 1024 ? a.R_pad / 2 : 1024;
+    const size_t lds = (size_t)a.R_pad * sizeof(double);
+    if (lds > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&stoch_sir_summary_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+        return -3;
+    hipLaunchKernelGGL(stoch_sir_summary_kernel, dim3((unsigned)segments), dim3(threads), lds, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace sepaihrd

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-from .problem import CONSTRAINT_CLAMP, SEPAIHRDProblem, SIRProblem
+from .problem import CONSTRAINT_CLAMP, SEPAIHRDProblem, SIRProblem, StochasticSIRProblem
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsepaihrd_hip.so")
@@ -64,6 +64,17 @@ class sepaihrd_sir_problem(C.Structure):
         ("q", C.c_double), ("scale_C_total", C.c_double),
         ("abs_err", C.c_double), ("rel_err", C.c_double), ("dt_hint", C.c_double),
     ]
+
+
+class sepaihrd_stoch_sir_config(C.Structure):
+    """include/sepaihrd_hip.h: struct sepaihrd_stoch_sir_config"""
+    _fields_ = [("abi_version", C.c_int32), ("n_groups", C.c_int32), ("n_replicates", C.c_int32), ("keep", C.c_int32),
+                ("t_start", C.c_double), ("t_end", C.c_double), ("h", C.c_double), ("seed", C.c_uint64),
+                ("max_workspace_bytes", C.c_uint64)]
+
+
+STOCH_SIR_STATS = ("mean", "median", "p05", "p95")  # the second axis of `stats`
+STOCH_SIR_DEFAULT_WORKSPACE = 4 << 30                # SEPAIHRD_STOCH_SIR_DEFAULT_WORKSPACE
 
 
 # every symbol include/sepaihrd_hip.h declares
@@ -204,6 +215,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_sir_mh_create", "sepaihrd_sir_device_libm_check", "sepaihrd_sir_constraint_bounds",
     "sepaihrd_mh_set_kernel_form", "sepaihrd_mh_get_kernel_form",
     "sepaihrd_sir_validate_events", "sepaihrd_sir_scenario_ensemble", "sepaihrd_sir_ensemble_quantiles", "sepaihrd_sir_ensemble_timing",
+    "sepaihrd_stoch_sir_num_steps", "sepaihrd_stoch_sir_validate", "sepaihrd_stoch_sir_run", "sepaihrd_stoch_sir_binomial_device",
 )
 
 _lib = None
@@ -324,6 +336,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_sir_ensemble_quantiles.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.sepaihrd_sir_ensemble_timing.argtypes = [vp, C.POINTER(C.c_int64), vp]
     lib.sepaihrd_mh_set_kernel_form.argtypes = [vp, C.c_int]
+    lib.sepaihrd_stoch_sir_num_steps.restype = C.c_int64
+    lib.sepaihrd_stoch_sir_num_steps.argtypes = [C.c_double, C.c_double, C.c_double]
+    lib.sepaihrd_stoch_sir_validate.argtypes = [C.POINTER(sepaihrd_stoch_sir_config), vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_stoch_sir_run.argtypes = [C.c_int, C.POINTER(sepaihrd_stoch_sir_config), vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_stoch_sir_binomial_device.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_mh_get_kernel_form.argtypes = [vp]
     if path is None:
         _lib = lib
@@ -788,3 +805,75 @@ class HipSIRObjective:
         ms = np.zeros(3)
         self._check(self.lib.sepaihrd_sir_ensemble_timing(self.ctx, C.byref(calls), ms.ctypes.data), "sepaihrd_sir_ensemble_timing")
         return {"calls": calls.value, "integrator_ms": ms[0], "metrics_ms": ms[1], "sort_ms": ms[2]}
+
+
+def stoch_sir_config(pb: StochasticSIRProblem, replicates: int, seed: int, keep: int = 0, max_workspace_bytes: Optional[int] = None,
+                     abi_version: int = ABI_VERSION) -> sepaihrd_stoch_sir_config:
+    return sepaihrd_stoch_sir_config(abi_version, pb.n_groups, int(replicates), int(keep), pb.t_start, pb.t_end, pb.h,
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_workspace_bytes or 0))
+
+
+def stoch_sir_num_steps(t_start: float, t_end: float, h: float) -> int:
+    """sepaihrd_stoch_sir_num_steps: the number of rows, or a negative code"""
+    return int(load_library().sepaihrd_stoch_sir_num_steps(float(t_start), float(t_end), float(h)))
+
+
+def stoch_sir_validate(pb: StochasticSIRProblem, replicates: int, keep: int = 0, abi_version: int = ABI_VERSION) -> tuple:
+    """sepaihrd_stoch_sir_validate on the host (no device): (code, message)."""
+    cfg = stoch_sir_config(pb, replicates, 0, keep, abi_version=abi_version)
+    tab = pb.group_table()
+    err = C.create_string_buffer(256)
+    rc = load_library().sepaihrd_stoch_sir_validate(C.byref(cfg), tab.ctypes.data, err, len(err))
+    return int(rc), err.value.decode()
+
+
+def stoch_sir_outputs(pb: StochasticSIRProblem, steps: int, replicates: int, keep: int, want_final: bool) -> dict:
+    G = pb.n_groups
+    return {"stats": np.empty((G, 4, 3, steps)), "traj": np.empty((G, keep, 3, steps)) if keep > 0 else None,
+            "final_state": np.empty((G, replicates, 3)) if want_final else None,
+            "times": pb.t_start + np.arange(steps) * pb.h}
+
+
+class HipStochasticSIR:
+    """Chain-binomial SIR ensembles of the reference's StochasticSIRModel on one MI355X (sepaihrd_stoch_sir_run)."""
+
+    def __init__(self, pb: StochasticSIRProblem, device: int = -1):
+        self.lib = load_library()
+        self.pb = pb
+        self.device = int(device)
+        self.phase_ms = None
+
+    def run(self, replicates: int, seed: int, keep: int = 0, want_final: bool = False, max_workspace_bytes: Optional[int] = None) -> dict:
+        """stats [G][4][3][steps] (STOCH_SIR_STATS), traj [G][keep][3][steps] or None, final_state [G][R][3] or None, times
+        [steps].  Refused arguments raise ValueError before the device is touched; the device time of the call by phase
+        (step kernels, sorts, summaries; ms) is left in ``phase_ms``."""
+        cfg = stoch_sir_config(self.pb, replicates, seed, keep, max_workspace_bytes)
+        tab = self.pb.group_table()
+        err = C.create_string_buffer(512)
+        if self.lib.sepaihrd_stoch_sir_validate(C.byref(cfg), tab.ctypes.data, err, len(err)) != 0:
+            raise ValueError(err.value.decode())
+        steps = stoch_sir_num_steps(self.pb.t_start, self.pb.t_end, self.pb.h)
+        out = stoch_sir_outputs(self.pb, steps, int(replicates), int(keep), want_final)
+        ms = np.zeros(3)
+        rc = self.lib.sepaihrd_stoch_sir_run(self.device, C.byref(cfg), tab.ctypes.data, out["stats"].ctypes.data,
+                                             None if out["traj"] is None else out["traj"].ctypes.data,
+                                             None if out["final_state"] is None else out["final_state"].ctypes.data,
+                                             ms.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_stoch_sir_run failed ({rc}): " + err.value.decode())
+        self.phase_ms = {"step": ms[0], "sort": ms[1], "summary": ms[2]}
+        return out
+
+    def binomial(self, n, p, seed: int) -> np.ndarray:
+        """sepaihrd_stoch_sir_binomial_device: out[i] ~ Binomial(n[i], p[i]) drawn by the device's sampler."""
+        n = np.ascontiguousarray(n, dtype=np.int32).ravel()
+        p = np.ascontiguousarray(p, dtype=np.float64).ravel()
+        if n.shape != p.shape:
+            raise ValueError("n and p must have one entry per draw")
+        out = np.empty(n.size, dtype=np.int32)
+        err = C.create_string_buffer(512)
+        rc = self.lib.sepaihrd_stoch_sir_binomial_device(self.device, int(seed) & 0xFFFFFFFFFFFFFFFF, n.ctypes.data, p.ctypes.data, n.size,
+                                                         out.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_stoch_sir_binomial_device failed ({rc}): " + err.value.decode())
+        return out

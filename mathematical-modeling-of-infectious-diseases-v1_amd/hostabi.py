@@ -93,6 +93,19 @@ def load_library() -> C.CDLL:
     lib.host_sir_calibrate.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32,
                                        C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+    lib.host_stoch_philox.restype = None
+    lib.host_stoch_philox.argtypes = [vp, vp, vp]
+    lib.host_stoch_uniform.restype = C.c_double
+    lib.host_stoch_uniform.argtypes = [C.c_uint32, C.c_uint32]
+    lib.host_stoch_probabilities.restype = None
+    lib.host_stoch_probabilities.argtypes = [C.c_double] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.host_stoch_binomial_at.restype = C.c_int32
+    lib.host_stoch_binomial_at.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_double]
+    lib.host_stoch_binomial_probe.restype = None
+    lib.host_stoch_binomial_probe.argtypes = [C.c_uint64, vp, vp, C.c_int, vp]
+    lib.host_stoch_sir_run.argtypes = [C.POINTER(hipabi.sepaihrd_stoch_sir_config), vp, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.host_stoch_sir_model.argtypes = [C.c_double] * 9 + [C.c_uint, C.c_uint64, C.c_int, C.c_char_p, vp, vp, C.POINTER(C.c_int),
+                                                            C.c_char_p, C.c_int]
     _lib = lib
     return lib
 
@@ -827,3 +840,89 @@ class HostSIRObjective:
             raise RuntimeError("host_sir_scenario_comparison: " + self.lib.host_last_error().decode())
         out["scenario_names"], out["metric_names"] = names, hipabi.sir_metric_names(n)
         return out
+
+
+# ---- stochastic chain-binomial SIR: the CPU twin of the device path and the pieces of csrc/sepaihrd_stoch.inc ----
+STOCH_INFECTION, STOCH_RECOVERY = 0, 1
+STOCH_HOST_TWIN = -2  # HipStochasticSIRModel::HOST_TWIN
+
+
+def stoch_philox(counter, key) -> np.ndarray:
+    """philox4x32_10(counter[4]; key[2]) -> 4 words"""
+    c = np.ascontiguousarray(counter, dtype=np.uint32)
+    k = np.ascontiguousarray(key, dtype=np.uint32)
+    out = np.empty(4, dtype=np.uint32)
+    load_library().host_stoch_philox(c.ctypes.data, k.ctypes.data, out.ctypes.data)
+    return out
+
+
+def stoch_uniform(lo: int, hi: int) -> float:
+    """the stream's rule from two output words to a double inside (0, 1)"""
+    return float(load_library().host_stoch_uniform(int(lo), int(hi)))
+
+
+def stoch_probabilities(beta: float, I: float, h: float, N: float, gamma: float) -> tuple:
+    """(pI, pR) of one step as the model text forms them"""
+    a, b = C.c_double(), C.c_double()
+    load_library().host_stoch_probabilities(beta, I, h, N, gamma, C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def stoch_binomial_at(seed: int, group: int, replicate: int, step: int, transition: int, n: int, p: float) -> int:
+    """the Binomial(n, p) variate at these coordinates of the stream"""
+    return int(load_library().host_stoch_binomial_at(int(seed) & 0xFFFFFFFFFFFFFFFF, group, replicate, step, transition, int(n), float(p)))
+
+
+def stoch_binomial_probe(n, p, seed: int) -> np.ndarray:
+    """the twin of HipStochasticSIR.binomial"""
+    n = np.ascontiguousarray(n, dtype=np.int32).ravel()
+    p = np.ascontiguousarray(p, dtype=np.float64).ravel()
+    out = np.empty(n.size, dtype=np.int32)
+    load_library().host_stoch_binomial_probe(int(seed) & 0xFFFFFFFFFFFFFFFF, n.ctypes.data, p.ctypes.data, n.size, out.ctypes.data)
+    return out
+
+
+class HostStochasticSIR:
+    """The CPU twin of HipStochasticSIR: the same model text on the host, OpenMP over replicates; same outputs bit for bit."""
+
+    def __init__(self, pb):
+        self.lib = load_library()
+        self.pb = pb
+
+    def run(self, replicates: int, seed: int, keep: int = 0, want_final: bool = False, max_workspace_bytes=None) -> dict:
+        cfg = hipabi.stoch_sir_config(self.pb, replicates, seed, keep, max_workspace_bytes)
+        tab = self.pb.group_table()
+        err = C.create_string_buffer(512)
+        if hipabi.load_library().sepaihrd_stoch_sir_validate(C.byref(cfg), tab.ctypes.data, err, len(err)) != 0:
+            raise ValueError(err.value.decode())
+        steps = hipabi.stoch_sir_num_steps(self.pb.t_start, self.pb.t_end, self.pb.h)
+        out = hipabi.stoch_sir_outputs(self.pb, steps, int(replicates), int(keep), want_final)
+        rc = self.lib.host_stoch_sir_run(C.byref(cfg), tab.ctypes.data, out["stats"].ctypes.data,
+                                         None if out["traj"] is None else out["traj"].ctypes.data,
+                                         None if out["final_state"] is None else out["final_state"].ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"host_stoch_sir_run failed ({rc}): " + err.value.decode())
+        return out
+
+
+def stoch_sir_model(N, beta, gamma, S0, I0, R0, t_start, t_end, h, num_simulations: int, seed: int = 0, device: int = STOCH_HOST_TWIN,
+                    out_dir=None, run: bool = True) -> dict:
+    """HipStochasticSIRModel end to end (constructor, runSimulations, writeCsv(out_dir), getStatistics, getResults).
+    std::invalid_argument becomes ValueError, anything else RuntimeError; run=False stops after the constructor."""
+    lib = load_library()
+    err = C.create_string_buffer(512)
+    steps = C.c_int(0)
+    args = [float(N), float(beta), float(gamma), float(S0), float(I0), float(R0), float(t_start), float(t_end), float(h),
+            int(num_simulations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(device)]
+    rc = lib.host_stoch_sir_model(*args, None, None, None, C.byref(steps), err, len(err))
+    if rc == 0 and run:
+        keep = min(int(num_simulations), 100)
+        stats = np.empty((4, 3, steps.value))
+        results = np.empty((keep, 3, steps.value))
+        rc = lib.host_stoch_sir_model(*args, None if out_dir is None else os.fsencode(out_dir), stats.ctypes.data, results.ctypes.data,
+                                      C.byref(steps), err, len(err))
+    if rc == 1:
+        raise ValueError(err.value.decode())
+    if rc != 0:
+        raise RuntimeError(err.value.decode())
+    return {"steps": steps.value, "stats": stats, "results": results} if run else {"steps": steps.value}

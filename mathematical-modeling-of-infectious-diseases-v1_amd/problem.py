@@ -420,3 +420,38 @@ class SIRProblem:
 
     def with_(self, **kw) -> "SIRProblem":
         return replace(self, **kw)
+
+
+@dataclass
+class StochasticSIRProblem:
+    """The reference's StochasticSIRModel arguments for one or several parameter sets ("groups"): N, beta, gamma, S0, I0,
+    R0 are scalars or equally long arrays; the time grid is t_start + step h, steps = round((t_end - t_start) / h) + 1."""
+    N: np.ndarray
+    beta: np.ndarray
+    gamma: np.ndarray
+    S0: np.ndarray
+    I0: np.ndarray
+    R0: np.ndarray
+    t_start: float = 0.0
+    t_end: float = 1.0
+    h: float = 1.0
+
+    def __post_init__(self):
+        cols = [np.atleast_1d(_arr(getattr(self, k))) for k in ("N", "beta", "gamma", "S0", "I0", "R0")]
+        G = max(len(c) for c in cols)
+        for k, c in zip(("N", "beta", "gamma", "S0", "I0", "R0"), cols):
+            if c.ndim != 1 or len(c) not in (1, G):
+                raise ValueError(f"{k} must be a scalar or an array of {G} groups")
+            setattr(self, k, np.ascontiguousarray(np.broadcast_to(c, (G,))))
+        self.t_start, self.t_end, self.h = float(self.t_start), float(self.t_end), float(self.h)
+
+    @property
+    def n_groups(self) -> int:
+        return len(self.N)
+
+    def group_table(self) -> np.ndarray:
+        """[G][6] doubles in the order of struct sepaihrd_stoch_sir_group"""
+        return np.ascontiguousarray(np.stack([self.N, self.beta, self.gamma, self.S0, self.I0, self.R0], axis=1))
+
+    def with_(self, **kw) -> "StochasticSIRProblem":
+        return replace(self, **kw)

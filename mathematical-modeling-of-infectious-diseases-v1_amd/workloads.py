@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .problem import SEPAIHRDProblem, widen_age_classes, SOLVER_DOPRI5, SOLVER_CASH_KARP54
+from .problem import SEPAIHRDProblem, StochasticSIRProblem, widen_age_classes, SOLVER_DOPRI5, SOLVER_CASH_KARP54
 
 DEFAULT_CHAINS = {"c1": 4096, "c2": 65536, "c3": 32768, "c5": 32768}
 
@@ -219,3 +219,16 @@ def sir_scenario_reference(simulate, pb, theta, scenarios, probs) -> dict:
         diff[k] = q_of(metrics[k, both] - metrics[0, both]).T
     return {"quantiles": quantiles, "metrics": metrics, "metric_summary": summary, "diff_quantiles": diff, "status": status,
             "n_accept": n_acc, "n_reject": n_rej, "n_valid": n_valid, "series": series}
+
+
+def stochastic_sir_reference(golden_dir: str = None, **kw):
+    """The workload of the reference's stochastic SIR driver (tests/golden/stochastic_sir_reference_input.json: its
+    input_parameters.txt with h = 1/24): (problem, fixture dict).  Keyword arguments replace fields of the problem."""
+    import json
+    if golden_dir is None:
+        golden_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    with open(os.path.join(golden_dir, "stochastic_sir_reference_input.json")) as fh:
+        fx = json.load(fh)
+    fields = {k: fx[k] for k in ("N", "beta", "gamma", "S0", "I0", "R0", "t_start", "t_end", "h")}
+    fields.update(kw)
+    return StochasticSIRProblem(**fields), fx
