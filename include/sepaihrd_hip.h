@@ -816,6 +816,43 @@ int sepaihrd_stoch_sir_run(int device, const sepaihrd_stoch_sir_config *config, 
 int sepaihrd_stoch_sir_binomial_device(int device, uint64_t seed, const int32_t *n, const double *p, int count, int32_t *out, char *err,
                                        int errlen);
 
+/* ---- posterior predictive draws with Poisson noise (additive; SEPAIHRD_ABI_VERSION stays) ----------------------------------
+ * sepaihrd_ensemble_quantiles takes quantiles across samples of the model's EXPECTED daily counts, as
+ * ResultAggregator::aggregatePosteriorPredictives does: bands of parameter uncertainty only.  The likelihood treats an
+ * observed count as Poisson around that expectation (calculateSingleLogLikelihood: mean max(0, increment) + 1e-10), so the
+ * replicated-data check needs y_rep ~ Poisson(mean).  The reference has no such output; this one is this build's own.
+ *
+ * sepaihrd_ensemble_predictive: one simulation per posterior sample theta[s] (S x n_params, host) as
+ * sepaihrd_ensemble_quantiles runs it (same preconditions, initial-state mode and failure codes), then R replicates per sample:
+ * for every output time j with t >= 0, age a and daily series k in {0 hospitalisations, 1 ICU admissions, 2 deaths}
+ *   m = max(0, increment),  y = Poisson(m + 1e-10) at stream coordinates (seed, c0 = s, c1 = r, c2 = (k T_pos + j) n_age + a)
+ * through Philox-4x32-10 and the sampler of csrc/sepaihrd_poisson.inc (inversion below 10, Hoermann's PTRS from 10 on); s is
+ * the sample's position in theta.  Series 3..5 are the running sums of y in time order per (s, r, a), exact integers.
+ *   pred_quantiles  [6][n_probs][T_pos][n_age]  quantiles over the n_valid R draws of the valid samples; the rule of
+ *                   sepaihrd_ensemble_quantiles (exact sort, interpolation at q (count - 1)); sorted in LDS up to 16384 draws
+ *                   per segment, by the segmented radix sort beyond
+ *   pit             [3][T_pos][n_age] or NULL: the mid-PIT (#{draws < obs} + 0.5 #{draws == obs}) / (n_valid R) of every cell
+ *                   of the daily series whose observation is usable (finite and >= 0, the likelihood's rule), NaN elsewhere
+ *   means           [S][3][T_pos][n_age] or NULL: m as drawn from; NaN rows for failed samples
+ *   draws           [S][R][3][T_pos][n_age] or NULL: the daily y; NaN for failed samples
+ *   status          [S] or NULL;  n_valid: count of status 0, or NULL
+ * A draw is a function of its coordinates and its mean alone: it does not depend on S, R, the launch, the sort path or on
+ * which other samples failed.  The host twin (host/: hostPosteriorPredictive) reproduces draws, quantiles and PIT bit for bit
+ * from `means` and `status`.
+ * SEPAIHRD_E_INVALID_ARG: R < 1, S R >= 2^31 (or S R rounded up to whole wavefronts), 3 T_pos n_age >= 2^32, a probability
+ * outside [0, 1], a pending sepaihrd_eval_batch_begin, or a segment table (6 T_pos n_age segments of S R doubles, plus the
+ * optional outputs and the likelihood workspace) beyond the device's memory -- the rule of sepaihrd_scenario_ensemble. */
+int sepaihrd_ensemble_predictive(sepaihrd_ctx *ctx, const double *theta, int S, int R, uint64_t seed, const double *probs, int n_probs,
+                                 double *pred_quantiles, double *pit, double *means, double *draws, int32_t *status, int32_t *n_valid);
+/* Host only: the argument rules above that need no context, with a message in err (NULL: not wanted). */
+int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, const double *probs, int n_probs, char *err, int errlen);
+/* Device time of the context's last sepaihrd_ensemble_predictive call in milliseconds, ms[3]: integrator; draws and mid-PIT
+ * counts; segment sorts and quantiles. */
+int sepaihrd_predictive_timing(const sepaihrd_ctx *ctx, double *ms);
+/* Probe of the device's Poisson sampler: out[i] ~ Poisson(lambda[i]), the variate at (seed, c0 = i, c1 = 0, c2 = 0).
+ * lambda [count], out [count], host memory; lambda <= 0 gives 0, NaN and +infinity give NaN. */
+int sepaihrd_poisson_device(int device, uint64_t seed, const double *lambda, int count, double *out, char *err, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

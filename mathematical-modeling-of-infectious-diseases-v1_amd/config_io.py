@@ -529,6 +529,63 @@ def write_posterior_predictive(out_dir: str, times_pos, ppc: np.ndarray, observe
     return written
 
 
+def write_posterior_predictive_draws(out_dir: str, times_pos, pred: np.ndarray, pit, observed: Dict[str, np.ndarray]) -> List[str]:
+    """The replicated-data check beside write_posterior_predictive's files (the reference has no such output: its bands are of
+    expectations), into the same directory:
+      <series>_predictive_{median,lower90,upper90,lower95,upper95}.csv   bands of y_rep ~ Poisson(mean), the format above
+      pit_<daily series>.csv                        ``time,age_0,...``, the mid-PIT of every observation (17 significant digits, nan
+                                                    where the observation is not usable)
+      predictive_coverage.csv                       ``series,age,n_observations,coverage_90,coverage_95``: per daily series with
+                                                    observations and age, the share of usable observations (finite and >= 0) inside
+                                                    [lower90, upper90] and [lower95, upper95], computed here; nan without any
+    pred: [6 series][5 PPC_PROBS][T_pos][n] (HipObjective.ensemble_predictive at PPC_PROBS); pit: [3][T_pos][n] or None;
+    observed: series -> [T_pos][n]."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    pred = np.asarray(pred, dtype=np.float64)
+    if pred.ndim != 4 or pred.shape[0] != 6 or pred.shape[1] != len(PPC_PROBS) or pred.shape[2] != len(times_pos):
+        raise ValueError("pred must be [6][5 PPC_PROBS][T_pos][n]")
+    n = pred.shape[3]
+    header = "time" + "".join(f",age_{a}" for a in range(n)) + "\n"
+
+    def dump(path, mat, fmt):
+        with open(path, "w") as fh:
+            fh.write(header)
+            for ti, t in enumerate(times_pos):
+                fh.write(_cxx_default(t) + "".join("," + fmt % mat[ti, a] for a in range(n)) + "\n")
+        written.append(path)
+
+    for si, name in enumerate(PPC_SERIES):
+        for pi, suffix in enumerate(_PPC_SUFFIX):
+            dump(os.path.join(out_dir, f"{name}_predictive_{suffix}.csv"), pred[si, pi], "%.6f")
+    if pit is not None:
+        pit = np.asarray(pit, dtype=np.float64)
+        for si, name in enumerate(PPC_SERIES[:3]):
+            dump(os.path.join(out_dir, f"pit_{name}.csv"), pit[si], "%.17g")
+    lo95, lo90, hi90, hi95 = (_PPC_SUFFIX.index(k) for k in ("lower95", "lower90", "upper90", "upper95"))
+    path = os.path.join(out_dir, "predictive_coverage.csv")
+    with open(path, "w") as fh:
+        fh.write("series,age,n_observations,coverage_90,coverage_95\n")
+        for si, name in enumerate(PPC_SERIES[:3]):
+            if name not in observed:
+                continue
+            obs = np.full((len(times_pos), n), np.nan)
+            rows = np.asarray(observed[name], dtype=np.float64)[:len(times_pos)]
+            obs[:rows.shape[0]] = rows
+            for a in range(n):
+                o = obs[:, a]
+                usable = np.isfinite(o) & (o >= 0.0)
+                cnt = int(np.sum(usable))
+                if cnt == 0:
+                    fh.write(f"{name},{a},0,nan,nan\n")
+                    continue
+                in90 = np.sum((o >= pred[si, lo90, :, a]) & (o <= pred[si, hi90, :, a]) & usable) / cnt
+                in95 = np.sum((o >= pred[si, lo95, :, a]) & (o <= pred[si, hi95, :, a]) & usable) / cnt
+                fh.write("%s,%d,%d,%.6f,%.6f\n" % (name, a, cnt, in90, in95))
+    written.append(path)
+    return written
+
+
 def write_aggregated_trajectory(path: str, times, quantiles: np.ndarray) -> None:
     """rt_trajectories/Rt_aggregated_with_uncertainty.csv, seroprevalence/seroprevalence_trajectory.csv:
     ``time,median,q025,q975,q05,q95`` fixed 6 digits.  quantiles: [5 PPC_PROBS][T]."""
@@ -716,11 +773,13 @@ def write_posterior_diagnostics(path: str, names: List[str], table) -> None:
 
 def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: np.ndarray, names: List[str], n_age: int,
                                 observed: Dict[str, np.ndarray] | None = None, burn_in: int = 0, thinning: int = 1,
-                                scenarios=None, ene_covid: bool = False, diagnostics=None) -> None:
+                                scenarios=None, ene_covid: bool = False, diagnostics=None, predictive: dict | None = None) -> None:
     """Everything PostCalibrationAnalysis.py loads under out_base, from one sepaihrd_ensemble_quantiles result (keys
     ppc, sero, rt, metrics; quantiles at PPC_PROBS).  scenarios (rows as write_scenario_comparison takes them):
     scenarios/scenario_comparison.csv; ene_covid: seroprevalence/ene_covid_validation.csv from the metric table;
-    diagnostics (a table as write_posterior_diagnostics takes it): parameter_posteriors/posterior_diagnostics.csv."""
+    diagnostics (a table as write_posterior_diagnostics takes it): parameter_posteriors/posterior_diagnostics.csv;
+    predictive (a HipObjective.ensemble_predictive result at PPC_PROBS, keys pred and pit): the files of
+    write_posterior_predictive_draws next to the bands of expectations."""
     times = np.asarray(times, dtype=np.float64)
     write_posterior_predictive(os.path.join(out_base, "posterior_predictive"), times[times >= 0], ensemble["ppc"], observed or {})
     write_parameter_posteriors(os.path.join(out_base, "parameter_posteriors"), samples, names, burn_in, thinning)
@@ -738,3 +797,6 @@ def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: n
         write_ene_covid_validation(os.path.join(out_base, "seroprevalence", "ene_covid_validation.csv"), sero64)
     if diagnostics is not None:
         write_posterior_diagnostics(os.path.join(out_base, "parameter_posteriors", "posterior_diagnostics.csv"), names, diagnostics)
+    if predictive is not None:
+        write_posterior_predictive_draws(os.path.join(out_base, "posterior_predictive"), times[times >= 0], predictive["pred"],
+                                         predictive.get("pit"), observed or {})

@@ -20,6 +20,7 @@
 #include "sepaihrd_device.h"
 #include "sepaihrd_fd_device.h"
 #include "sepaihrd_mh_backend.h"
+#include "sepaihrd_predictive_device.h"
 
 using namespace sepaihrd;
 
@@ -91,6 +92,8 @@ struct sepaihrd_ctx {
     void* fd_host = nullptr;
     size_t fd_dev_bytes = 0, fd_host_bytes = 0;
     hipEvent_t fd_ev_uploaded = nullptr, fd_ev_centre = nullptr;
+    // the last sepaihrd_ensemble_predictive call: integrator, draws and mid-PIT counts, sorts and quantiles (ms)
+    double pred_ms[3] = {0.0, 0.0, 0.0};
 };
 
 namespace {
@@ -961,6 +964,129 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx* ctx, const double* theta, int S, c
     if (n_valid)
         HIP_TRY(hipMemcpy(n_valid, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
     cleanup();
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* probs, int n_probs,
+                                 double* pred_quantiles, double* pit, double* means, double* draws, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    auto refuse = [&](const std::string& msg, int rc) { ctx->last_error = "ensemble_predictive: " + msg; return rc; };
+    if (S <= 0 || !theta || !probs || n_probs <= 0 || n_probs > 1024 || !pred_quantiles)
+        return refuse("need S > 0, theta, probs (1..1024) and pred_quantiles", SEPAIHRD_E_INVALID_ARG);
+    if (ctx->pending_B > 0) return refuse("a sepaihrd_eval_batch_begin is pending on this context", SEPAIHRD_E_INVALID_ARG);
+    if (ctx->precision != SEPAIHRD_PRECISION_F64)
+        return refuse("the ensemble summaries read the fp64 integrator's parked increments (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    const DevProblem& dp = ctx->dp;
+    const int Tp = dp.T - dp.runup_offset;
+    if (Tp <= 0) return refuse("no output time >= 0", SEPAIHRD_E_INVALID_ARG);
+    {
+        char msg[256] = "";
+        if (sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            ctx->last_error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    // a segment holds the S R draws of one (series, time, age): stride and padding as EnsembleArgs::S_pad
+    const size_t N = (size_t)S * (size_t)R;
+    size_t N_pad = WAVE;
+    while (N_pad < N && N_pad < (size_t)ENSEMBLE_MAX_SAMPLES) N_pad <<= 1;
+    const bool big = N > (size_t)ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
+    if (big) N_pad = (N + WAVE - 1) / WAVE * WAVE;
+    if (N_pad >= ((size_t)1 << 31)) return refuse("S x R rounded up to whole wavefronts must stay below 2^31", SEPAIHRD_E_INVALID_ARG);
+    const size_t cpw = (size_t)(WAVE / dp.lpc);
+    const size_t chains = ((size_t)S + cpw - 1) / cpw * cpw;
+    const size_t cells = (size_t)3 * Tp * dp.n;
+    const size_t n_q = (size_t)6 * n_probs * Tp * dp.n;
+    const size_t n_vals = 2 * cells * N_pad;
+    const size_t n_scratch = big ? std::max<size_t>(N_pad, std::min<size_t>(n_vals, (size_t)1 << 28) / N_pad * N_pad) : 0;
+    const size_t n_means = means ? (size_t)S * cells : 0, n_draws = draws ? N * cells : 0;
+    // the rule of sepaihrd_scenario_ensemble: the buffers below plus the likelihood workspace must fit the device's memory
+    // (the segment table dominates: 6 T_pos n_age segments of S R doubles); larger requests are refused before anything is allocated
+    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + (size_t)n_probs) +
+                              sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) +
+                              sizeof(int32_t) * (chains + 2);
+    size_t device_bytes = 0;
+    HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
+    if (need_bytes > device_bytes)
+        return refuse("the segment table of S x R = " + std::to_string(N) + " draws needs " + std::to_string(need_bytes >> 20) +
+                          " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
+                          " MiB: split the samples or the replicates over several calls",
+                      SEPAIHRD_E_INVALID_ARG);
+    int rc = ensure_workspace(ctx, chains);
+    if (rc != SEPAIHRD_OK) return rc;
+    // buffers and events of this call alone: the context's own (sepaihrd_ensemble_quantiles') stay as they are
+    struct Scratch {
+        std::vector<void*> bufs;
+        hipEvent_t ev[4] = {};
+        ~Scratch() {
+            for (void* b : bufs) if (b) (void)hipFree(b);
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        }
+        bool alloc(void** p, size_t bytes) {
+            void* q = nullptr;
+            if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return false; }
+            bufs.push_back(q);
+            *p = q;
+            return true;
+        }
+    } sc;
+    double *d_theta = nullptr, *d_ll = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_pit = nullptr,
+           *d_means = nullptr, *d_draws = nullptr;
+    int32_t* d_counts = nullptr;
+    if (!sc.alloc((void**)&d_theta, (size_t)S * ctx->P * sizeof(double)) || !sc.alloc((void**)&d_ll, (size_t)S * sizeof(double)) ||
+        !sc.alloc((void**)&d_vals, n_vals * sizeof(double)) || !sc.alloc((void**)&d_scratch, n_scratch * sizeof(double)) ||
+        !sc.alloc((void**)&d_probs, (size_t)n_probs * sizeof(double)) || !sc.alloc((void**)&d_q, n_q * sizeof(double)) ||
+        !sc.alloc((void**)&d_pit, cells * sizeof(double)) || !sc.alloc((void**)&d_means, n_means * sizeof(double)) ||
+        !sc.alloc((void**)&d_draws, n_draws * sizeof(double)) || !sc.alloc((void**)&d_counts, 2 * sizeof(int32_t)))
+        return refuse("device allocation failed", SEPAIHRD_E_HIP);
+    for (hipEvent_t& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
+    rc = fence_before(ctx, nullptr);  // an evaluation of this context may still be running on another stream
+    if (rc != SEPAIHRD_OK) return rc;
+    (void)hipEventRecord(sc.ev[0], nullptr);
+    rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_eval_fma(dp, ctx->solver, d_theta, S, out, nullptr)
+                                          : launch_eval_strict(dp, ctx->solver, d_theta, S, out, nullptr);
+    if (rc != 0) return refuse(rc == -4 ? "unsupported lanes-per-chain" : "kernel launch failed", rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[1], nullptr);
+    PredictiveArgs a{};
+    a.S = S; a.R = R; a.N_pad = (int)N_pad;
+    a.lpc = dp.lpc; a.n = dp.n; a.T = dp.T; a.Tp = Tp; a.runup_offset = dp.runup_offset;
+    a.seed = seed;
+    a.cum = ctx->ws_cum; a.wstatus = ctx->ws_status; a.grid = dp.grid;
+    a.vals = d_vals; a.means = means ? d_means : nullptr; a.draws = draws ? d_draws : nullptr;
+    a.n_probs = n_probs; a.probs = d_probs; a.q_out = d_q; a.pit_out = pit ? d_pit : nullptr; a.counts = d_counts;
+    a.sort_scratch = big ? d_scratch : nullptr;
+    a.sort_scratch_doubles = n_scratch;
+    if (launch_predictive_draws(a, nullptr) != 0) return refuse("draw kernel launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[2], nullptr);
+    if (launch_predictive_quantiles(a, nullptr) != 0) return refuse("quantile launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[3], nullptr);
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
+        ctx->pred_ms[i] = ms;
+    }
+    bool ok = true;
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        if (ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+    };
+    fetch(pred_quantiles, d_q, n_q * sizeof(double));
+    fetch(pit, d_pit, cells * sizeof(double));
+    fetch(means, d_means, n_means * sizeof(double));
+    fetch(draws, d_draws, n_draws * sizeof(double));
+    fetch(status, ctx->ws_status, (size_t)S * sizeof(int32_t));
+    fetch(n_valid, d_counts, sizeof(int32_t));
+    if (!ok) return refuse("copy of the results failed", SEPAIHRD_E_HIP);
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_predictive_timing(const sepaihrd_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
+    for (int i = 0; i < 3; ++i) ms[i] = ctx->pred_ms[i];
     return SEPAIHRD_OK;
 }
 

@@ -34,6 +34,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_predictive_device.h"
 #include "sepaihrd_sir_device.h"
 #include "sepaihrd_stoch_device.h"
 #include "sepaihrd_stoch.inc"
@@ -875,6 +876,42 @@ int launch_stoch_sir_summaries(const StochSummaryArgs& a, void* stream) {
                             (int)lds) != hipSuccess)
         return -3;
     hipLaunchKernelGGL(stoch_sir_summary_kernel, dim3((unsigned)segments), dim3(threads), lds, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace sepaihrd
+
+// ---- posterior predictive draws (sepaihrd_ensemble_predictive): the quantiles of the 6 Tp n segments of S R replicated
+// counts, with the segment sorts and the interpolation of sepaihrd_ensemble_quantiles; the count of values per segment is
+// the number of valid samples times R ----
+namespace sepaihrd {
+
+int launch_predictive_quantiles(const PredictiveArgs& a, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool in_lds = a.N_pad <= ENSEMBLE_MAX_SAMPLES;
+    const size_t segments = (size_t)6 * a.Tp * a.n;
+    if (a.S <= 0 || a.R <= 0 || a.N_pad < WAVE || (size_t)a.S * a.R > (size_t)a.N_pad || segments >= ((size_t)1 << 31) ||
+        (in_lds ? (a.N_pad & (a.N_pad - 1)) != 0 : a.N_pad % WAVE != 0))
+        return -4;
+    EnsembleArgs e{};
+    e.S = a.S * a.R; e.S_pad = a.N_pad; e.lpc = a.lpc; e.n = a.n; e.T = a.T; e.Tp = a.Tp;
+    e.n_probs = a.n_probs; e.probs = a.probs;
+    e.vals = a.vals; e.q_out = a.q_out;
+    e.n_valid = a.counts + 1;
+    e.rt_segment0 = (int)segments;
+    if (!in_lds)
+        return sort_segments_global(a.vals, (int)segments, a.N_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
+            const size_t work = (size_t)ng * a.n_probs;
+            hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, e, (int)segments,
+                               a.sort_scratch, first, ng);
+        });
+    const int threads = a.N_pad / 2 < 1024 ? a.N_pad / 2 : 1024;
+    const size_t lds = (size_t)a.N_pad * sizeof(double);
+    if (lds > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+        return -3;
+    hipLaunchKernelGGL(ensemble_quantile_kernel, dim3((unsigned)segments), dim3(threads), lds, st, e, (int)segments);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

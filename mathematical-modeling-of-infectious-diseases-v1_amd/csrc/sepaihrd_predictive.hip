@@ -1,0 +1,178 @@
+// csrc/sepaihrd_predictive.hip -- posterior predictive draws with Poisson noise on gfx950 (sepaihrd_ensemble_predictive;
+// DESIGN.md section 6i): the draw kernel over the integrator's parked increments, the mid-PIT counts and the probe of the
+// Poisson sampler.  The sampler is csrc/sepaihrd_poisson.inc, the text the host twin compiles too; the segment sorts and the
+// quantiles are csrc/sepaihrd_ensemble.hip's.  Compiled with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <cstdio>
+#include <string>
+
+#include "sepaihrd_device.h"
+#include "sepaihrd_hip.h"
+#include "sepaihrd_poisson.inc"
+#include "sepaihrd_predictive_device.h"
+
+namespace sepaihrd {
+namespace {
+
+constexpr int DRAW_BLOCK = 256;
+
+// counts[0] = valid samples, counts[1] = valid samples x R
+__global__ __launch_bounds__(256) void predictive_count_kernel(const int32_t* wstatus, int S, int R, int32_t* counts) {
+    __shared__ int part[256];
+    int c = 0;
+    for (int s = threadIdx.x; s < S; s += 256) c += (wstatus[s] == 0);
+    part[threadIdx.x] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { counts[0] = part[0]; counts[1] = part[0] * R; }
+}
+
+// One lane per (sample s, replicate r), consecutive lanes along s R + r: the loads of a sample's increments are broadcasts,
+// the stores into a segment contiguous.  The lane walks the ages and, per age, the output times >= 0 in time order:
+// m = max(0, increment), y ~ Poisson(m + 1e-10) at stream coordinates (s, r, (series Tp + time) n + age), series 3 .. 5
+// the running sums of y (exact integers in double).
+__global__ __launch_bounds__(DRAW_BLOCK) void predictive_draw_kernel(const PredictiveArgs a) {
+    const size_t idx = (size_t)blockIdx.x * DRAW_BLOCK + threadIdx.x;
+    if (idx >= (size_t)a.N_pad) return;
+    const size_t s = idx / (size_t)a.R;
+    const uint32_t r = (uint32_t)(idx % (size_t)a.R);
+    const bool in_range = s < (size_t)a.S;
+    const bool ok = in_range && a.wstatus[s] == 0;
+    const size_t seg_stride = (size_t)a.N_pad;
+    // series order: daily H, daily ICU, daily D; cum rows are D, CumH, CumICU
+    const int comp_of[3] = {1, 2, 0};
+    for (int age = 0; age < a.n; ++age) {
+        const size_t col = s * (size_t)a.lpc + (size_t)age;
+        double run[3] = {0.0, 0.0, 0.0};
+        for (int t = 0; t < a.Tp; ++t) {
+#pragma unroll
+            for (int ser = 0; ser < 3; ++ser) {
+                const size_t cell = ((size_t)ser * a.Tp + t) * a.n + age;
+                double m = NAN, y = INFINITY, cumulative = INFINITY;
+                if (ok) {
+                    const double inc = a.cum[cum_index(a.T, col, a.runup_offset + t, comp_of[ser])];
+                    m = (0.0 < inc) ? inc : 0.0;  // std::max(0.0, cur - prev)
+                    y = sepaihrd_poisson::poisson(a.seed, (uint32_t)s, r, (uint32_t)cell, m + 1e-10);
+                    run[ser] += y;
+                    cumulative = run[ser];
+                }
+                a.vals[cell * seg_stride + idx] = y;
+                a.vals[(cell + (size_t)3 * a.Tp * a.n) * seg_stride + idx] = cumulative;
+                if (in_range) {
+                    if (a.means != nullptr && r == 0) a.means[((s * 3 + ser) * a.Tp + t) * a.n + age] = m;
+                    if (a.draws != nullptr) a.draws[((idx * 3 + ser) * a.Tp + t) * a.n + age] = ok ? y : (double)NAN;
+                }
+            }
+        }
+    }
+}
+
+// One workgroup per cell of the three daily series: the draws below and at the observation, counted before the sort (the
+// padding is +inf and counts as neither).  Usable observation: finite and >= 0, the likelihood's rule; elsewhere NaN.
+__global__ __launch_bounds__(256) void predictive_pit_kernel(const PredictiveArgs a) {
+    __shared__ int less_part[256], equal_part[256];
+    const size_t cell = blockIdx.x;  // (series Tp + t) n + age
+    const int age = (int)(cell % a.n);
+    const int t = (int)((cell / a.n) % a.Tp);
+    const int ser = (int)(cell / ((size_t)a.n * a.Tp));
+    const double obs = a.grid[((size_t)(a.runup_offset + t) * a.lpc + age) * 4 + ser];
+    if (!(obs >= 0.0 && obs <= 0x1.fffffffffffffp+1023)) {
+        if (threadIdx.x == 0) a.pit_out[cell] = NAN;
+        return;
+    }
+    const double* seg = a.vals + cell * (size_t)a.N_pad;
+    const size_t N = (size_t)a.S * a.R;
+    int less = 0, equal = 0;
+    for (size_t i = threadIdx.x; i < N; i += 256) {
+        const double y = seg[i];
+        less += (y < obs);
+        equal += (y == obs);
+    }
+    less_part[threadIdx.x] = less;
+    equal_part[threadIdx.x] = equal;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            less_part[threadIdx.x] += less_part[threadIdx.x + w];
+            equal_part[threadIdx.x] += equal_part[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.pit_out[cell] = sepaihrd_poisson::mid_pit(less_part[0], equal_part[0], a.counts[1]);
+}
+
+__global__ __launch_bounds__(DRAW_BLOCK) void poisson_probe_kernel(uint64_t seed, const double* lambda, int count, double* out) {
+    const int i = (int)(blockIdx.x * (unsigned)DRAW_BLOCK + threadIdx.x);
+    if (i >= count) return;
+    out[i] = sepaihrd_poisson::poisson(seed, (uint32_t)i, 0u, 0u, lambda[i]);
+}
+
+void set_err(char* err, int errlen, const std::string& msg) {
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
+}
+
+}  // namespace
+
+int launch_predictive_draws(const PredictiveArgs& a, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a.S <= 0 || a.R <= 0 || a.n <= 0 || a.Tp <= 0 || (size_t)a.S * a.R > (size_t)a.N_pad || a.N_pad % WAVE != 0 ||
+        (uint64_t)3 * a.Tp * a.n >= ((uint64_t)1 << 32))
+        return -4;
+    hipLaunchKernelGGL(predictive_count_kernel, dim3(1), dim3(256), 0, st, a.wstatus, a.S, a.R, a.counts);
+    hipLaunchKernelGGL(predictive_draw_kernel, dim3((unsigned)((a.N_pad + DRAW_BLOCK - 1) / DRAW_BLOCK)), dim3(DRAW_BLOCK), 0, st, a);
+    if (a.pit_out != nullptr)
+        hipLaunchKernelGGL(predictive_pit_kernel, dim3((unsigned)((size_t)3 * a.Tp * a.n)), dim3(256), 0, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace sepaihrd
+
+using namespace sepaihrd;
+
+extern "C" int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, const double* probs, int n_probs, char* err, int errlen) {
+    auto refuse = [&](const std::string& msg) { set_err(err, errlen, "ensemble_predictive: " + msg); return SEPAIHRD_E_INVALID_ARG; };
+    if (S < 1) return refuse("S must be >= 1 (samples)");
+    if (R < 1) return refuse("R must be >= 1 (replicates per sample)");
+    if ((uint64_t)S * (uint64_t)R >= ((uint64_t)1 << 31)) return refuse("S x R must stay below 2^31 (draws per segment)");
+    if (T_pos < 1 || n_age < 1) return refuse("T_pos and n_age must be >= 1");
+    if ((uint64_t)3 * (uint64_t)T_pos * (uint64_t)n_age >= ((uint64_t)1 << 32))
+        return refuse("3 x T_pos x n_age must stay below 2^32 (the third stream coordinate)");
+    if (!probs || n_probs < 1 || n_probs > 1024) return refuse("need probs (1..1024)");
+    for (int p = 0; p < n_probs; ++p)
+        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return refuse("probabilities must lie in [0, 1]");
+    return SEPAIHRD_OK;
+}
+
+extern "C" int sepaihrd_poisson_device(int device, uint64_t seed, const double* lambda, int count, double* out, char* err, int errlen) {
+    if (!lambda || !out || count < 1) { set_err(err, errlen, "poisson_device: need lambda, out and count >= 1"); return SEPAIHRD_E_INVALID_ARG; }
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): hipGetDeviceCount -> ") +
+                                 hipGetErrorString(e) + ", count " + std::to_string(ndev));
+        return SEPAIHRD_E_NO_DEVICE;
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return SEPAIHRD_E_HIP; }
+    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return SEPAIHRD_E_INVALID_ARG; }
+    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return SEPAIHRD_E_HIP; }
+    double *d_lambda = nullptr, *d_out = nullptr;
+    bool ok = hipMalloc((void**)&d_lambda, (size_t)count * sizeof(double)) == hipSuccess &&
+              hipMalloc((void**)&d_out, (size_t)count * sizeof(double)) == hipSuccess &&
+              hipMemcpy(d_lambda, lambda, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(poisson_probe_kernel, dim3((unsigned)((count + DRAW_BLOCK - 1) / DRAW_BLOCK)), dim3(DRAW_BLOCK), 0, nullptr, seed,
+                           d_lambda, count, d_out);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) set_err(err, errlen, std::string("poisson_device: ") + hipGetErrorString(hipGetLastError()));
+    if (d_lambda) (void)hipFree(d_lambda);
+    if (d_out) (void)hipFree(d_out);
+    return ok ? SEPAIHRD_OK : SEPAIHRD_E_HIP;
+}

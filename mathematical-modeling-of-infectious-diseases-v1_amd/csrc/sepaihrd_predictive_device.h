@@ -1,0 +1,35 @@
+// csrc/sepaihrd_predictive_device.h -- what csrc/sepaihrd_capi.cpp (sepaihrd_ensemble_predictive), csrc/sepaihrd_predictive.hip
+// (the draw kernel, the mid-PIT counts) and csrc/sepaihrd_ensemble.hip (the segment sorts and the quantiles) share.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace sepaihrd {
+
+// Replicated data of a posterior ensemble: draw (s, r) sits in slot s R + r of every (series, time, age) segment of
+// vals[6 Tp n][N_pad]; slots of samples whose integration failed and slots S R .. N_pad - 1 hold +inf and sort last.
+// N_pad: as EnsembleArgs::S_pad for a segment of S R values.
+struct PredictiveArgs {
+    int S, R, N_pad;
+    int lpc, n, T, Tp, runup_offset;  // lanes per chain, ages, output times, output times >= 0, index of the first of them
+    uint64_t seed;
+    const double* cum;         // the integrator's parked daily increments: cum_index()
+    const int32_t* wstatus;    // [S] integrator status
+    const double* grid;        // DevProblem::grid: the observations of output time k and age i at grid[(k lpc + i) 4 + series]
+    double* vals;              // [6 Tp n][N_pad]
+    double* means;             // [S][3][Tp][n] device or null
+    double* draws;             // [S][R][3][Tp][n] device or null
+    int n_probs;
+    const double* probs;       // [n_probs] device
+    double* q_out;             // [6][n_probs][Tp][n] device
+    double* pit_out;           // [3][Tp][n] device or null
+    int32_t* counts;           // [2] device: valid samples, valid samples x R (the draws of a segment)
+    double* sort_scratch;      // as EnsembleArgs (N_pad > ENSEMBLE_MAX_SAMPLES)
+    size_t sort_scratch_doubles;
+};
+// counts, the draws into vals / means / draws, and the mid-PIT of every usable observation (csrc/sepaihrd_predictive.hip)
+int launch_predictive_draws(const PredictiveArgs& a, void* stream);
+// the quantiles of every segment with the ensemble's sorts and interpolation (csrc/sepaihrd_ensemble.hip)
+int launch_predictive_quantiles(const PredictiveArgs& a, void* stream);
+
+}  // namespace sepaihrd

@@ -216,6 +216,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_mh_set_kernel_form", "sepaihrd_mh_get_kernel_form",
     "sepaihrd_sir_validate_events", "sepaihrd_sir_scenario_ensemble", "sepaihrd_sir_ensemble_quantiles", "sepaihrd_sir_ensemble_timing",
     "sepaihrd_stoch_sir_num_steps", "sepaihrd_stoch_sir_validate", "sepaihrd_stoch_sir_run", "sepaihrd_stoch_sir_binomial_device",
+    "sepaihrd_ensemble_predictive", "sepaihrd_predictive_validate", "sepaihrd_predictive_timing", "sepaihrd_poisson_device",
 )
 
 _lib = None
@@ -342,6 +343,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_stoch_sir_run.argtypes = [C.c_int, C.POINTER(sepaihrd_stoch_sir_config), vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_stoch_sir_binomial_device.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_mh_get_kernel_form.argtypes = [vp]
+    lib.sepaihrd_ensemble_predictive.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_predictive_validate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_char_p, C.c_int]
+    lib.sepaihrd_predictive_timing.argtypes = [vp, vp]
+    lib.sepaihrd_poisson_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
     if path is None:
         _lib = lib
     return lib
@@ -563,6 +568,48 @@ class HipObjective:
             out["rt"] = rt
         if want_metrics:
             out["metrics"] = met
+        return out
+
+    def ensemble_predictive(self, theta, R: int, seed: int, probs, want_pit: bool = True, want_means: bool = False,
+                            want_draws: bool = False) -> dict:
+        """Posterior predictive draws with Poisson noise (sepaihrd_ensemble_predictive): R replicates y ~ Poisson(mean) per
+        sample.  pred [6][n_probs][T_pos][n] (quantiles over the draws of the valid samples), pit [3][T_pos][n] (mid-PIT of
+        the usable observations, NaN elsewhere), means [S][3][T_pos][n], draws [S][R][3][T_pos][n], status [S], n_valid,
+        phase_ms (integrator; draws and PIT counts; sorts and quantiles)."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        S, npb, n, R = th.shape[0], pr.size, self.pb.n, int(R)
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        pred = np.empty((6, npb, Tp, n))
+        pit = np.empty((3, Tp, n)) if want_pit else None
+        means = np.empty((S, 3, Tp, n)) if want_means else None
+        draws = np.empty((S, max(R, 0), 3, Tp, n)) if want_draws else None
+        status = np.empty(S, dtype=np.int32)
+        nv = C.c_int32(0)
+        self._check(self.lib.sepaihrd_ensemble_predictive(
+            self.ctx, th.ctypes.data, S, R, int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, npb, pred.ctypes.data,
+            pit.ctypes.data if want_pit else None, means.ctypes.data if want_means else None,
+            draws.ctypes.data if want_draws else None, status.ctypes.data, C.byref(nv)), "ensemble_predictive")
+        ms = np.zeros(3)
+        self._check(self.lib.sepaihrd_predictive_timing(self.ctx, ms.ctypes.data), "predictive_timing")
+        out = {"pred": pred, "status": status, "n_valid": nv.value, "phase_ms": ms}
+        if want_pit:
+            out["pit"] = pit
+        if want_means:
+            out["means"] = means
+        if want_draws:
+            out["draws"] = draws
+        return out
+
+    def poisson(self, lam, seed: int) -> np.ndarray:
+        """Probe of the device's Poisson sampler (sepaihrd_poisson_device): out[i] at (seed, c0 = i, c1 = c2 = 0)."""
+        lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+        out = np.empty(lam.size)
+        err = C.create_string_buffer(512)
+        rc = self.lib.sepaihrd_poisson_device(getattr(self, "_device", -1), int(seed) & 0xFFFFFFFFFFFFFFFF, lam.ctypes.data, lam.size,
+                                              out.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_poisson_device failed ({rc}): " + err.value.decode())
         return out
 
     def scenario_ensemble(self, theta, kappa_mult, probs, want_sero: bool = False, want_rt: bool = False) -> dict:

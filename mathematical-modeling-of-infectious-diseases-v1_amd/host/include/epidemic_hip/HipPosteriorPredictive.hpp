@@ -1,0 +1,68 @@
+// host/include/epidemic_hip/HipPosteriorPredictive.hpp
+//
+// Posterior predictive draws with Poisson noise above sepaihrd_ensemble_predictive.  The reference has no such output: the
+// bands of ResultAggregator::aggregatePosteriorPredictives (HipPosteriorEnsemble) are quantiles of the model's EXPECTED daily
+// counts, parameter uncertainty only, while the likelihood it calibrates with treats an observed count as Poisson around that
+// expectation.  Here every selected sample is simulated once and replicated R times, y ~ Poisson(max(0, increment) + 1e-10)
+// from a stateless stream (csrc/sepaihrd_poisson.inc); bands of y and the mid-PIT of every usable observation follow.
+// The CPU twin of the device's draw, sort and count passes (the same sampler text, OpenMP) is hostPosteriorPredictive.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "epidemic_hip/HipPosteriorEnsemble.hpp"
+
+namespace epidemic {
+
+// From means [S][3][T_pos][n_age] and status [S] as sepaihrd_ensemble_predictive returns them: the same draws
+// [S][R][3][T_pos][n_age] (nullable; NaN for failed samples), pred_quantiles [6][n_probs][T_pos][n_age] and pit
+// [3][T_pos][n_age] (nullable), bit for bit.  observed [3][T_pos][n_age] (hospitalisations, ICU admissions, deaths; NaN where
+// there is none; NULL: no pit).  Returns SEPAIHRD_OK or SEPAIHRD_E_INVALID_ARG with sepaihrd_predictive_validate's message.
+int hostPosteriorPredictive(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
+                            std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                            std::string* error = nullptr);
+
+// the sampler on the host: the variate at (seed, c0, c1, c2), and the twin of sepaihrd_poisson_device (c0 = i, c1 = c2 = 0)
+double hostPoisson(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double lambda);
+void hostPoissonProbe(std::uint64_t seed, const double* lambda, int count, double* out);
+
+struct PosteriorPredictiveDraws {
+    std::vector<double> time_points;  // the output times >= 0
+    int n_age = 0, replicates = 0;
+    int samples_used = 0;             // valid simulations; every segment holds samples_used x replicates draws
+    std::vector<int> selected;        // indices of the simulated samples (HipPosteriorEnsemble::selectSamples)
+    std::vector<double> probs;
+    std::vector<double> pred_quantiles;  // [6][n_probs][T_pos][n_age]
+    std::vector<double> pit;             // [3][T_pos][n_age]
+    std::vector<double> means, draws;    // [S][3][T_pos][n_age], [S][R][3][T_pos][n_age]; empty unless asked for
+    std::vector<int32_t> status;         // [S]
+};
+
+class HipPosteriorPredictive {
+public:
+    HipPosteriorPredictive(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
+                           const std::vector<double>& time_points, const Eigen::VectorXd& initial_state,
+                           std::shared_ptr<IOdeSolverStrategy> solver_strategy, double abs_error = 1.0e-6, double rel_error = 1.0e-6,
+                           int device = -1, bool fma_arithmetic = false);
+
+    // The device call over stored samples, selected by the PPC rule of HipPosteriorEnsemble::selectSamples
+    // (num_samples_for_ppc draws with replacement from mt19937(random_seed) when 0 < num < size, else every sample in order).
+    PosteriorPredictiveDraws draw(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc, unsigned int random_seed,
+                                  int replicates, std::uint64_t seed, const std::vector<double>& probs, bool want_means = false,
+                                  bool want_draws = false);
+
+    // the observations as the device places them: [3][T_pos][n_age], row j of the data at output time j >= 0, NaN beyond the data
+    std::vector<double> observed() const;
+
+private:
+    HipSEPAIHRDParameterManager& pm_;
+    const CalibrationData& data_;
+    std::vector<double> time_points_;
+    SimulationCache cache_;
+    std::unique_ptr<HipSEPAIHRDObjectiveFunction> objective_;
+    int n_ = 0, t_pos_ = 0;
+};
+
+}  // namespace epidemic

@@ -1,0 +1,151 @@
+// host/src/HipPosteriorPredictive.cpp -- HipPosteriorPredictive, the CPU twin of sepaihrd_ensemble_predictive's draw, sort and
+// count passes.  The sampler is csrc/sepaihrd_poisson.inc, the text the kernel compiles; this library is built with -ffp-contract=off like the kernel.
+#include "epidemic_hip/HipPosteriorPredictive.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+
+#include "sepaihrd_hip.h"
+#include "sepaihrd_poisson.inc"
+
+namespace epidemic {
+
+int hostPosteriorPredictive(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
+                            std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                            std::string* error) {
+    char msg[256] = "";
+    int vrc = sepaihrd_predictive_validate(S, R, T_pos, n_age, probs, n_probs, msg, (int)sizeof(msg));
+    if (vrc == SEPAIHRD_OK && (!means || !status || !pred_quantiles)) {
+        std::snprintf(msg, sizeof(msg), "ensemble_predictive: means, status and pred_quantiles must not be NULL");
+        vrc = SEPAIHRD_E_INVALID_ARG;
+    }
+    if (vrc != SEPAIHRD_OK) {
+        if (error) *error = msg;
+        return vrc;
+    }
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    const size_t Tp = (size_t)T_pos, n = (size_t)n_age;
+    std::vector<int> valid;  // positions in theta of the valid samples
+    for (int s = 0; s < S; ++s)
+        if (status[s] == 0) valid.push_back(s);
+    const size_t nd = valid.size() * (size_t)R;  // draws per segment
+    if (draws)
+        for (int s = 0; s < S; ++s)
+            if (status[s] != 0) std::fill(draws + (size_t)s * R * 3 * Tp * n, draws + (size_t)(s + 1) * R * 3 * Tp * n, qnan);
+    // one age class at a time: its 6 T_pos segments of nd draws
+    std::vector<double> seg((size_t)6 * Tp * nd);
+    for (size_t a = 0; a < n; ++a) {
+#pragma omp parallel for schedule(static)
+        for (long long d = 0; d < (long long)nd; ++d) {
+            const size_t s = (size_t)valid[(size_t)d / (size_t)R], r = (size_t)d % (size_t)R;
+            double run[3] = {0.0, 0.0, 0.0};
+            for (size_t t = 0; t < Tp; ++t)
+                for (size_t k = 0; k < 3; ++k) {
+                    const size_t cell = (k * Tp + t) * n + a;
+                    const double m = means[((s * 3 + k) * Tp + t) * n + a];
+                    const double y = sepaihrd_poisson::poisson(seed, (uint32_t)s, (uint32_t)r, (uint32_t)cell, m + 1e-10);
+                    run[k] += y;
+                    seg[(k * Tp + t) * nd + (size_t)d] = y;
+                    seg[((k + 3) * Tp + t) * nd + (size_t)d] = run[k];
+                    if (draws) draws[(((s * (size_t)R + r) * 3 + k) * Tp + t) * n + a] = y;
+                }
+        }
+#pragma omp parallel for schedule(dynamic, 4)
+        for (long long sg = 0; sg < (long long)(6 * Tp); ++sg) {
+            const size_t ser = (size_t)sg / Tp, t = (size_t)sg % Tp;
+            double* x = seg.data() + (size_t)sg * nd;
+            if (pit && ser < 3) {
+                const size_t cell = (ser * Tp + t) * n + a;
+                const double obs = observed ? observed[cell] : qnan;
+                double v = qnan;
+                if (obs >= 0.0 && obs <= std::numeric_limits<double>::max()) {
+                    int64_t less = 0, equal = 0;
+                    for (size_t i = 0; i < nd; ++i) {
+                        less += x[i] < obs;
+                        equal += x[i] == obs;
+                    }
+                    v = sepaihrd_poisson::mid_pit(less, equal, (int64_t)nd);
+                }
+                pit[cell] = v;
+            }
+            std::sort(x, x + nd);
+            for (int p = 0; p < n_probs; ++p)
+                pred_quantiles[((ser * (size_t)n_probs + (size_t)p) * Tp + t) * n + a] = nd > 0 ? sepaihrd_poisson::sorted_quantile(x, nd, probs[p]) : qnan;
+        }
+    }
+    return SEPAIHRD_OK;
+}
+
+double hostPoisson(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double lambda) {
+    return sepaihrd_poisson::poisson(seed, c0, c1, c2, lambda);
+}
+
+void hostPoissonProbe(std::uint64_t seed, const double* lambda, int count, double* out) {
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < count; ++i) out[i] = sepaihrd_poisson::poisson(seed, (uint32_t)i, 0u, 0u, lambda[i]);
+}
+
+HipPosteriorPredictive::HipPosteriorPredictive(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
+                                               const std::vector<double>& time_points, const Eigen::VectorXd& initial_state,
+                                               std::shared_ptr<IOdeSolverStrategy> solver_strategy, double abs_error, double rel_error,
+                                               int device, bool fma_arithmetic)
+    : pm_(parameterManager), data_(observed_data), time_points_(time_points), cache_(1) {
+    objective_ = std::make_unique<HipSEPAIHRDObjectiveFunction>(pm_, cache_, data_, time_points_, initial_state, std::move(solver_strategy),
+                                                                abs_error, rel_error, device, fma_arithmetic);
+    if (sepaihrd_set_initial_state_mode(objective_->deviceContext(), SEPAIHRD_INIT_FIXED) != SEPAIHRD_OK)
+        throw ModelException("HipPosteriorPredictive", "sepaihrd_set_initial_state_mode failed");
+    n_ = static_cast<int>(pm_.modelParameters().N.size());
+    for (double t : time_points_) t_pos_ += (t >= 0.0);
+}
+
+std::vector<double> HipPosteriorPredictive::observed() const {
+    const size_t Tp = static_cast<size_t>(t_pos_), n = static_cast<size_t>(n_);
+    std::vector<double> out(3 * Tp * n, std::numeric_limits<double>::quiet_NaN());
+    const Eigen::MatrixXd* src[3] = {&data_.getNewHospitalizations(), &data_.getNewICU(), &data_.getNewDeaths()};
+    for (size_t k = 0; k < 3; ++k)
+        for (size_t t = 0; t < Tp && t < static_cast<size_t>(src[k]->rows()); ++t)
+            for (size_t a = 0; a < n && a < static_cast<size_t>(src[k]->cols()); ++a)
+                out[(k * Tp + t) * n + a] = (*src[k])(static_cast<Eigen::Index>(t), static_cast<Eigen::Index>(a));
+    return out;
+}
+
+PosteriorPredictiveDraws HipPosteriorPredictive::draw(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc,
+                                                      unsigned int random_seed, int replicates, std::uint64_t seed,
+                                                      const std::vector<double>& probs, bool want_means, bool want_draws) {
+    PosteriorPredictiveDraws out;
+    for (double t : time_points_)
+        if (t >= 0.0) out.time_points.push_back(t);
+    out.n_age = n_;
+    out.replicates = replicates;
+    out.probs = probs;
+    if (out.time_points.empty() || param_samples.empty()) return out;
+    out.selected = HipPosteriorEnsemble::selectSamples(param_samples.size(), num_samples_for_ppc, random_seed);
+    const size_t P = pm_.getParameterCount(), S = out.selected.size();
+    std::vector<double> thetas(S * P);
+    for (size_t s = 0; s < S; ++s) {
+        const Eigen::VectorXd& v = param_samples[static_cast<size_t>(out.selected[s])];
+        if (static_cast<size_t>(v.size()) != P) throw InvalidParameterException("HipPosteriorPredictive", "sample size mismatch");
+        for (size_t i = 0; i < P; ++i) thetas[s * P + i] = v[static_cast<Eigen::Index>(i)];
+    }
+    sepaihrd_ctx* ctx = objective_->deviceContext();
+    objective_->syncDeviceConstraintMode();
+    const size_t cells = static_cast<size_t>(3) * t_pos_ * n_;
+    out.pred_quantiles.assign(2 * cells * probs.size(), 0.0);
+    out.pit.assign(cells, 0.0);
+    if (want_means) out.means.assign(S * cells, 0.0);
+    if (want_draws && replicates > 0) out.draws.assign(S * static_cast<size_t>(replicates) * cells, 0.0);
+    out.status.assign(S, 0);
+    int32_t nv = 0;
+    const int rc = sepaihrd_ensemble_predictive(ctx, thetas.data(), static_cast<int>(S), replicates, seed, probs.data(),
+                                                static_cast<int>(probs.size()), out.pred_quantiles.data(), out.pit.data(),
+                                                want_means ? out.means.data() : nullptr, out.draws.empty() ? nullptr : out.draws.data(),
+                                                out.status.data(), &nv);
+    if (rc != SEPAIHRD_OK)
+        throw ModelException("HipPosteriorPredictive", std::string("sepaihrd_ensemble_predictive: ") + sepaihrd_last_error(ctx));
+    out.samples_used = nv;
+    return out;
+}
+
+}  // namespace epidemic

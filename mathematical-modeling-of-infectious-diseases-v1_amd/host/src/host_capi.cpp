@@ -14,6 +14,7 @@
 #include "epidemic_hip/HipNUTSSampler.hpp"
 #include "epidemic_hip/MultiChainNUTSSampler.hpp"
 #include "epidemic_hip/HipPosteriorEnsemble.hpp"
+#include "epidemic_hip/HipPosteriorPredictive.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipSIR.hpp"
 #include "epidemic_hip/HipSIRScenarioAnalysis.hpp"
@@ -1556,6 +1557,56 @@ int host_sir_scenario_comparison(void* hv, const double* samples, int n_samples,
         if (diff_quantiles) std::copy(r.diff_quantiles.begin(), r.diff_quantiles.end(), diff_quantiles);
         if (status) std::copy(r.status.begin(), r.status.end(), status);
         if (n_valid) std::copy(r.n_valid.begin(), r.n_valid.end(), n_valid);
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// ---- posterior predictive draws (HipPosteriorPredictive) ----
+// the twin of sepaihrd_poisson_device and one variate of the sampler (no device)
+void host_poisson_probe(uint64_t seed, const double* lambda, int count, double* out) { hostPoissonProbe(seed, lambda, count, out); }
+double host_poisson_at(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, double lambda) { return hostPoisson(seed, c0, c1, c2, lambda); }
+
+// hostPosteriorPredictive (no device): shapes as sepaihrd_ensemble_predictive, observed [3][T_pos][n_age] or NULL
+int host_predictive_from_means(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
+                               uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws, char* err,
+                               int errlen) {
+    std::string error;
+    const int rc = hostPosteriorPredictive(means, status, observed, S, R, T_pos, n_age, seed, probs, n_probs, pred_quantiles, pit, draws, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
+// HipPosteriorPredictive::draw over the handle's parameter manager / data.  samples: n_samples x P, selected by the PPC rule
+// (num_for_ppc, ppc_seed).  pred [6][n_probs][T_pos][n], pit [3][T_pos][n], observed [3][T_pos][n]; means / draws (nullable)
+// [n_selected][3][T_pos][n] / [n_selected][R][3][T_pos][n]; selected and status: capacity max(n_samples, num_for_ppc).
+int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int num_for_ppc, uint32_t ppc_seed,
+                    int R, uint64_t seed, const double* probs, int n_probs, double* pred, double* pit, double* observed, double* means,
+                    double* draws, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
+    auto* h = static_cast<HostHandle*>(hv);
+    try {
+        const int n = pb->n_age;
+        const size_t P = h->pm->getParameterCount();
+        HipPosteriorPredictive pp(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
+                                  strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
+        std::vector<Eigen::VectorXd> ps;
+        for (int s = 0; s < n_samples; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+        const PosteriorPredictiveDraws d = pp.draw(ps, num_for_ppc, ppc_seed, R, seed, std::vector<double>(probs, probs + n_probs), means != nullptr,
+                                                   draws != nullptr);
+        std::copy(d.pred_quantiles.begin(), d.pred_quantiles.end(), pred);
+        if (pit) std::copy(d.pit.begin(), d.pit.end(), pit);
+        if (observed) {
+            const std::vector<double> obs = pp.observed();
+            std::copy(obs.begin(), obs.end(), observed);
+        }
+        if (means) std::copy(d.means.begin(), d.means.end(), means);
+        if (draws) std::copy(d.draws.begin(), d.draws.end(), draws);
+        for (size_t i = 0; i < d.selected.size(); ++i) selected[i] = d.selected[i];
+        *n_selected = static_cast<int32_t>(d.selected.size());
+        if (status) std::copy(d.status.begin(), d.status.end(), status);
+        *samples_used = d.samples_used;
         return 0;
     } catch (const std::exception& e) {
         g_error = e.what();

@@ -106,6 +106,14 @@ def load_library() -> C.CDLL:
     lib.host_stoch_sir_run.argtypes = [C.POINTER(hipabi.sepaihrd_stoch_sir_config), vp, vp, vp, vp, C.c_char_p, C.c_int]
     lib.host_stoch_sir_model.argtypes = [C.c_double] * 9 + [C.c_uint, C.c_uint64, C.c_int, C.c_char_p, vp, vp, C.POINTER(C.c_int),
                                                             C.c_char_p, C.c_int]
+    lib.host_poisson_probe.restype = None
+    lib.host_poisson_probe.argtypes = [C.c_uint64, vp, C.c_int, vp]
+    lib.host_poisson_at.restype = C.c_double
+    lib.host_poisson_at.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
+    lib.host_predictive_from_means.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, vp, vp,
+                                               C.c_char_p, C.c_int]
+    lib.host_predictive.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint64,
+                                    vp, C.c_int] + [vp] * 9
     _lib = lib
     return lib
 
@@ -335,6 +343,40 @@ class HostObjective:
         if rc != 0:
             raise RuntimeError("host_ensemble: " + self.lib.host_last_error().decode())
         return {"ppc": ppc, "selected": sel[:nsel.value].copy(), "samples_used": used.value, "sero": sero, "rt": rt}
+
+    def posterior_predictive(self, samples, num_for_ppc: int, ppc_seed: int, R: int, seed: int,
+                             probs=(0.025, 0.05, 0.5, 0.95, 0.975), want_means: bool = False, want_draws: bool = False,
+                             device: int = -1) -> dict:
+        """HipPosteriorPredictive::draw over this handle's parameter manager and data: the samples picked by the PPC rule of
+        posterior_ensemble, R Poisson replicates each.  pred [6][n_probs][T_pos][n], pit and observed [3][T_pos][n], selected,
+        status, samples_used; means [S][3][T_pos][n] and draws [S][R][3][T_pos][n] on request."""
+        ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        n = self.pb.n
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        cap = max(ps.shape[0], num_for_ppc, 1)
+        S = num_for_ppc if 0 < num_for_ppc < ps.shape[0] else ps.shape[0]
+        pred, pit, obs = np.empty((6, pr.size, Tp, n)), np.empty((3, Tp, n)), np.empty((3, Tp, n))
+        means = np.empty((S, 3, Tp, n)) if want_means else None
+        draws = np.empty((S, max(int(R), 0), 3, Tp, n)) if want_draws else None
+        sel, status = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        nsel, used = C.c_int32(0), C.c_int32(0)
+        rc = self.lib.host_predictive(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data, pit.ctypes.data,
+                                      obs.ctypes.data, means.ctypes.data if want_means else None,
+                                      draws.ctypes.data if want_draws else None, sel.ctypes.data, C.byref(nsel), status.ctypes.data,
+                                      C.byref(used))
+        if rc != 0:
+            raise RuntimeError("host_predictive: " + self.lib.host_last_error().decode())
+        out = {"pred": pred, "pit": pit, "observed": obs, "selected": sel[:nsel.value].copy(), "status": status[:nsel.value].copy(),
+               "samples_used": used.value}
+        if want_means:
+            out["means"] = means
+        if want_draws:
+            out["draws"] = draws
+        return out
 
     def scenario_comparison(self, samples, burn_in: int = 0, thinning: int = 1, path: str | None = None, device: int = -1) -> dict:
         """The reference's scenario step (PostCalibrationAnalyser.cpp:94-141): the default lockdown scenarios of the last
@@ -926,3 +968,70 @@ def stoch_sir_model(N, beta, gamma, S0, I0, R0, t_start, t_end, h, num_simulatio
     if rc != 0:
         raise RuntimeError(err.value.decode())
     return {"steps": steps.value, "stats": stats, "results": results} if run else {"steps": steps.value}
+
+
+# ---- posterior predictive draws with Poisson noise: the CPU twin of sepaihrd_ensemble_predictive and its sampler ----
+def poisson_probe(lam, seed: int) -> np.ndarray:
+    """the twin of HipObjective.poisson: out[i] ~ Poisson(lam[i]) at (seed, c0 = i, c1 = c2 = 0)"""
+    lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+    out = np.empty(lam.size)
+    load_library().host_poisson_probe(int(seed) & 0xFFFFFFFFFFFFFFFF, lam.ctypes.data, lam.size, out.ctypes.data)
+    return out
+
+
+def poisson_at(seed: int, c0: int, c1: int, c2: int, lam: float) -> float:
+    """the Poisson(lam) variate at these coordinates of the stream"""
+    return float(load_library().host_poisson_at(int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), int(c1), int(c2), float(lam)))
+
+
+def predictive_validate(S: int, R: int, T_pos: int, n_age: int, probs) -> None:
+    """sepaihrd_predictive_validate (host only): ValueError with its message for arguments the predictive call refuses"""
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    err = C.create_string_buffer(512)
+    if hipabi.load_library().sepaihrd_predictive_validate(int(S), int(R), int(T_pos), int(n_age), pr.ctypes.data, pr.size, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def observed_table(pb) -> np.ndarray:
+    """the problem's observations as the predictive call places them: [3: H, ICU, D][T_pos][n], NaN beyond the data's rows"""
+    Tp = int(np.sum(np.asarray(pb.times) >= 0.0))
+    out = np.full((3, Tp, pb.n), np.nan)
+    for k, name in enumerate(("obs_H", "obs_ICU", "obs_D")):
+        rows = np.asarray(getattr(pb, name), dtype=np.float64).reshape(-1, pb.n)[:Tp]
+        out[k, :rows.shape[0]] = rows
+    return out
+
+
+def predictive_from_means(means, status, observed, R: int, seed: int, probs, want_pit: bool = True, want_draws: bool = True) -> dict:
+    """The twin of HipObjective.ensemble_predictive after the integration: from means [S][3][T_pos][n] and status [S] (and
+    observed [3][T_pos][n], NaN where there is none) the same pred [6][n_probs][T_pos][n], pit [3][T_pos][n] and draws
+    [S][R][3][T_pos][n], bit for bit."""
+    m = np.ascontiguousarray(means, dtype=np.float64)
+    if m.ndim != 4 or m.shape[1] != 3:
+        raise ValueError("means must be [S][3][T_pos][n]")
+    S, _, Tp, n = m.shape
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    if st.shape != (S,):
+        raise ValueError("status must have one entry per sample")
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    predictive_validate(S, R, Tp, n, pr)
+    R = int(R)
+    ob = None if observed is None else np.ascontiguousarray(observed, dtype=np.float64)
+    if ob is not None and ob.shape != (3, Tp, n):
+        raise ValueError("observed must be [3][T_pos][n]")
+    pred = np.empty((6, pr.size, Tp, n))
+    pit = np.empty((3, Tp, n)) if want_pit and ob is not None else None
+    draws = np.empty((S, R, 3, Tp, n)) if want_draws else None
+    err = C.create_string_buffer(512)
+    rc = load_library().host_predictive_from_means(m.ctypes.data, st.ctypes.data, None if ob is None else ob.ctypes.data, S, R, Tp, n,
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data,
+                                                   None if pit is None else pit.ctypes.data, None if draws is None else draws.ctypes.data,
+                                                   err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    out = {"pred": pred, "n_valid": int(np.sum(st == 0))}
+    if pit is not None:
+        out["pit"] = pit
+    if draws is not None:
+        out["draws"] = draws
+    return out
