@@ -853,6 +853,57 @@ int sepaihrd_predictive_timing(const sepaihrd_ctx *ctx, double *ms);
  * lambda [count], out [count], host memory; lambda <= 0 gives 0, NaN and +infinity give NaN. */
 int sepaihrd_poisson_device(int device, uint64_t seed, const double *lambda, int count, double *out, char *err, int errlen);
 
+/* ---- stochastic chain-binomial SEPAIHRD ensembles over posterior samples (additive; SEPAIHRD_ABI_VERSION stays) -------------
+ * Process noise for the age-structured model: the ensemble calls above give parameter uncertainty and observation noise, this
+ * one simulates the epidemic itself as a chain-binomial process, R replicates per posterior sample.  The reference has no such
+ * model; this one is this build's own.  csrc/sepaihrd_stoch_sepaihrd.inc states it (one text for the kernel and the host twin):
+ *   - state: per age class the 11 compartments as int32; row 0 is the sample's deterministic initial state, built by the
+ *     context's initial-state mode (S by subtraction included), every entry rounded with round();
+ *   - a sample is SEPAIHRD_STATUS_INVALID when the deterministic rule rejects it or a rounded entry lies outside [0, 2^31 - 1];
+ *     the counts of an age class whose total exceeds 2^31 - 1 wrap (no check: populations of that size are out of scope);
+ *   - output interval k is cut into steps_per_interval = m steps h_k = (times[k+1] - times[k]) / m; step j has the global index
+ *     k m + j and takes beta and kappa at its midpoint times[k] + (j + 0.5) h_k (the schedule lookup of the integrators);
+ *   - lambda_i = max(0, (sum_j M(i,j) (P_j + A_j + theta I_j) h_infec_j / N_j) ((beta kappa) a_i)), from the state at the start
+ *     of the step; 13 binomial draws per age class and step, all from that state (the table in the .inc file);
+ *   - every variate is the binomial of csrc/sepaihrd_stoch.inc at Philox key = seed, counter = (s, r, (step 64 + age) 16 +
+ *     transition, attempt), s the sample's position in theta, r the replicate.
+ * A replicate's path is a function of (seed, s, r) and the sample's model values alone: it does not depend on S, R, keep, the
+ * launch, the sort path or on which other samples are invalid.  The arithmetic mode of the context does not change the result.
+ *   quantiles     [6][n_probs][T_pos][n_age] over the n_valid R replicates, output times t >= 0: series 0..2 the daily
+ *                 increments of CumH, CumICU and D (hospitalisations, ICU admissions, deaths; the first row of the run has
+ *                 increment 0), 3..5 their running sums over the output times >= 0; the quantile rule and the sorts of
+ *                 sepaihrd_ensemble_predictive
+ *   extinct       [S] or NULL: share of the sample's replicates with E + P + A + I = 0 in every age class at the last time;
+ *                 NaN for an invalid sample
+ *   model_values  [S][W] or NULL, W = sepaihrd_stochastic_values_width(n_age, n_beta, n_kappa): what the replicates ran with,
+ *                 after the constraints of the context's constraint mode.  Row layout:
+ *                   [0..7]  theta, sigma, gamma_p, gamma_A, gamma_I, gamma_H, gamma_ICU, beta
+ *                   beta_values[n_beta], kappa_values[n_kappa]
+ *                   [8][n_age]   a, h_infec, p, h, icu, d_H, d_ICU, d_community
+ *                   [11][n_age]  the rounded initial counts S, E, P, A, I, H, ICU, R, D, CumH, CumICU (written for invalid
+ *                                samples too, as rounded)
+ *   traj          [S][keep][n_times][11][n_age] or NULL: every row of replicates 0 .. keep - 1; NaN for an invalid sample
+ *   final_state   [S][R][11][n_age] or NULL: the last row of every replicate; NaN for an invalid sample
+ *   status [S] or NULL; n_valid: count of status 0, or NULL
+ * The host twin (host/: hostStochasticSEPAIHRD) reproduces quantiles, extinct, traj and final_state bit for bit from
+ * model_values, status and the problem's fixed data.
+ * SEPAIHRD_E_INVALID_ARG, before the device is touched: R < 1, steps_per_interval < 1, keep outside [0, R], keep > 0 without
+ * traj, S R >= 2^31 (rounded up to whole wavefronts), n_times steps_per_interval >= 2^22, a probability outside [0, 1], a
+ * pending sepaihrd_eval_batch_begin, or buffers (6 T_pos n_age segments of S R doubles plus the outputs asked for) beyond the
+ * device's memory -- the rule of sepaihrd_ensemble_predictive.  SEPAIHRD_E_UNSUPPORTED in F32 precision or beyond 16 age
+ * classes. */
+int sepaihrd_ensemble_stochastic(sepaihrd_ctx *ctx, const double *theta, int S, int R, int steps_per_interval, uint64_t seed,
+                                 const double *probs, int n_probs, int keep, double *quantiles, double *extinct, double *model_values,
+                                 double *traj, double *final_state, int32_t *status, int32_t *n_valid);
+/* Host only: the argument rules above that need no context, with a message in err (NULL: not wanted). */
+int sepaihrd_stochastic_validate(int S, int R, int steps_per_interval, int keep, int n_times, int T_pos, int n_age, const double *probs,
+                                 int n_probs, char *err, int errlen);
+/* Host only: W, the width of a model_values row; SEPAIHRD_E_INVALID_ARG for n_age < 1 or a negative count. */
+int sepaihrd_stochastic_values_width(int n_age, int n_beta, int n_kappa);
+/* Device time of the context's last sepaihrd_ensemble_stochastic call in milliseconds, ms[2]: step kernel; segment sorts and
+ * quantiles. */
+int sepaihrd_stochastic_timing(const sepaihrd_ctx *ctx, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 #include "sepaihrd_fd_device.h"
 #include "sepaihrd_mh_backend.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_stoch_sepaihrd_device.h"
 
 using namespace sepaihrd;
 
@@ -94,6 +95,8 @@ struct sepaihrd_ctx {
     hipEvent_t fd_ev_uploaded = nullptr, fd_ev_centre = nullptr;
     // the last sepaihrd_ensemble_predictive call: integrator, draws and mid-PIT counts, sorts and quantiles (ms)
     double pred_ms[3] = {0.0, 0.0, 0.0};
+    // the last sepaihrd_ensemble_stochastic call: step kernel, sorts and quantiles (ms)
+    double stoch_ms[2] = {0.0, 0.0};
 };
 
 namespace {
@@ -1087,6 +1090,135 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
 int sepaihrd_predictive_timing(const sepaihrd_ctx* ctx, double* ms) {
     if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
     for (int i = 0; i < 3; ++i) ms[i] = ctx->pred_ms[i];
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, int R, int steps_per_interval, uint64_t seed,
+                                 const double* probs, int n_probs, int keep, double* quantiles, double* extinct, double* model_values,
+                                 double* traj, double* final_state, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    auto refuse = [&](const std::string& msg, int rc) { ctx->last_error = "ensemble_stochastic: " + msg; return rc; };
+    if (S <= 0 || !theta || !probs || n_probs <= 0 || n_probs > 1024 || !quantiles)
+        return refuse("need S > 0, theta, probs (1..1024) and quantiles", SEPAIHRD_E_INVALID_ARG);
+    if (ctx->pending_B > 0) return refuse("a sepaihrd_eval_batch_begin is pending on this context", SEPAIHRD_E_INVALID_ARG);
+    const DevProblem& dp = ctx->dp;
+    const int Tp = dp.T - dp.runup_offset;
+    {
+        char msg[256] = "";
+        if (sepaihrd_stochastic_validate(S, R, steps_per_interval, keep, dp.T, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            ctx->last_error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    if (keep > 0 && !traj) return refuse("keep > 0 needs traj", SEPAIHRD_E_INVALID_ARG);
+    if (ctx->precision != SEPAIHRD_PRECISION_F64) return refuse("the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    if (dp.n > 16 || dp.lpc > 16) return refuse("built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    // a segment holds the S R replicates of one (series, time, age): stride and padding as EnsembleArgs::S_pad
+    const size_t N = (size_t)S * (size_t)R;
+    size_t N_pad = WAVE;
+    while (N_pad < N && N_pad < (size_t)ENSEMBLE_MAX_SAMPLES) N_pad <<= 1;
+    const bool big = N > (size_t)ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
+    if (big) N_pad = (N + WAVE - 1) / WAVE * WAVE;
+    const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
+    const size_t cells = (size_t)3 * Tp * dp.n;
+    const size_t n_q = (size_t)6 * n_probs * Tp * dp.n;
+    const size_t n_vals = 2 * cells * N_pad;
+    const size_t n_scratch = big ? std::max<size_t>(N_pad, std::min<size_t>(n_vals, (size_t)1 << 28) / N_pad * N_pad) : 0;
+    const size_t n_values = (size_t)S * W;
+    const size_t n_traj = (traj && keep > 0) ? (size_t)S * keep * dp.T * NUM_COMP * dp.n : 0;
+    const size_t n_final = final_state ? N * NUM_COMP * dp.n : 0;
+    // the rule of sepaihrd_ensemble_predictive: what is allocated below must fit the device's memory (the segment table
+    // dominates); larger requests are refused before anything is allocated
+    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + n_vals + n_scratch + n_q + n_values + n_traj + n_final + (size_t)n_probs) +
+                              sizeof(int32_t) * (2 * (size_t)S + 2);
+    size_t device_bytes = 0;
+    HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
+    if (need_bytes > device_bytes)
+        return refuse("the segment table of S x R = " + std::to_string(N) + " replicates and the outputs asked for need " +
+                          std::to_string(need_bytes >> 20) + " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
+                          " MiB: split the samples or the replicates over several calls",
+                      SEPAIHRD_E_INVALID_ARG);
+    struct Scratch {
+        std::vector<void*> bufs;
+        hipEvent_t ev[3] = {};
+        ~Scratch() {
+            for (void* b : bufs) if (b) (void)hipFree(b);
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        }
+        bool alloc(void** p, size_t bytes) {
+            void* q = nullptr;
+            if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return false; }
+            bufs.push_back(q);
+            *p = q;
+            return true;
+        }
+    } sc;
+    double *d_theta = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_values = nullptr, *d_traj = nullptr,
+           *d_final = nullptr;
+    int32_t *d_counts = nullptr, *d_status = nullptr, *d_extinct = nullptr;
+    if (!sc.alloc((void**)&d_theta, (size_t)S * ctx->P * sizeof(double)) || !sc.alloc((void**)&d_vals, n_vals * sizeof(double)) ||
+        !sc.alloc((void**)&d_scratch, n_scratch * sizeof(double)) || !sc.alloc((void**)&d_probs, (size_t)n_probs * sizeof(double)) ||
+        !sc.alloc((void**)&d_q, n_q * sizeof(double)) || !sc.alloc((void**)&d_values, n_values * sizeof(double)) ||
+        !sc.alloc((void**)&d_traj, n_traj * sizeof(double)) || !sc.alloc((void**)&d_final, n_final * sizeof(double)) ||
+        !sc.alloc((void**)&d_counts, 2 * sizeof(int32_t)) || !sc.alloc((void**)&d_status, (size_t)S * sizeof(int32_t)) ||
+        !sc.alloc((void**)&d_extinct, (size_t)S * sizeof(int32_t)))
+        return refuse("device allocation failed", SEPAIHRD_E_HIP);
+    for (hipEvent_t& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    StochEpiArgs a{};
+    a.S = S; a.R = R; a.N_pad = (int)N_pad;
+    a.m = steps_per_interval; a.keep = n_traj ? keep : 0; a.W = W;
+    a.seed = seed;
+    a.theta = d_theta; a.values = d_values; a.status = d_status; a.counts = d_counts; a.extinct_count = d_extinct;
+    a.vals = d_vals; a.traj = n_traj ? d_traj : nullptr; a.final_state = final_state ? d_final : nullptr;
+    int rc = launch_stoch_epi_decode(dp, a, nullptr);
+    if (rc != 0) return refuse("decode kernel launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[0], nullptr);
+    rc = launch_stoch_epi_steps(dp, a, nullptr);
+    if (rc != 0) return refuse("step kernel launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[1], nullptr);
+    PredictiveArgs pa{};
+    pa.S = S; pa.R = R; pa.N_pad = (int)N_pad;
+    pa.lpc = dp.lpc; pa.n = dp.n; pa.T = dp.T; pa.Tp = Tp; pa.runup_offset = dp.runup_offset;
+    pa.seed = seed;
+    pa.wstatus = d_status;
+    pa.vals = d_vals;
+    pa.n_probs = n_probs; pa.probs = d_probs; pa.q_out = d_q; pa.counts = d_counts;
+    pa.sort_scratch = big ? d_scratch : nullptr;
+    pa.sort_scratch_doubles = n_scratch;
+    if (launch_predictive_quantiles(pa, nullptr) != 0) return refuse("quantile launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[2], nullptr);
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    for (int i = 0; i < 2; ++i) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
+        ctx->stoch_ms[i] = ms;
+    }
+    bool ok = true;
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        if (ok && dst && bytes && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
+    };
+    std::vector<int32_t> h_status((size_t)S), h_extinct((size_t)S);
+    fetch(quantiles, d_q, n_q * sizeof(double));
+    fetch(model_values, d_values, n_values * sizeof(double));
+    fetch(traj, d_traj, n_traj * sizeof(double));
+    fetch(final_state, d_final, n_final * sizeof(double));
+    fetch(h_status.data(), d_status, (size_t)S * sizeof(int32_t));
+    fetch(h_extinct.data(), d_extinct, (size_t)S * sizeof(int32_t));
+    fetch(n_valid, d_counts, sizeof(int32_t));
+    if (!ok) return refuse("copy of the results failed", SEPAIHRD_E_HIP);
+    if (status) std::copy(h_status.begin(), h_status.end(), status);
+    if (extinct)
+        for (int s = 0; s < S; ++s)
+            extinct[s] = h_status[(size_t)s] == 0 ? (double)h_extinct[(size_t)s] / (double)R : std::numeric_limits<double>::quiet_NaN();
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_stochastic_timing(const sepaihrd_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
+    for (int i = 0; i < 2; ++i) ms[i] = ctx->stoch_ms[i];
     return SEPAIHRD_OK;
 }
 

@@ -217,6 +217,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_sir_validate_events", "sepaihrd_sir_scenario_ensemble", "sepaihrd_sir_ensemble_quantiles", "sepaihrd_sir_ensemble_timing",
     "sepaihrd_stoch_sir_num_steps", "sepaihrd_stoch_sir_validate", "sepaihrd_stoch_sir_run", "sepaihrd_stoch_sir_binomial_device",
     "sepaihrd_ensemble_predictive", "sepaihrd_predictive_validate", "sepaihrd_predictive_timing", "sepaihrd_poisson_device",
+    "sepaihrd_ensemble_stochastic", "sepaihrd_stochastic_validate", "sepaihrd_stochastic_values_width", "sepaihrd_stochastic_timing",
 )
 
 _lib = None
@@ -346,6 +347,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_ensemble_predictive.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.sepaihrd_predictive_validate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_char_p, C.c_int]
     lib.sepaihrd_predictive_timing.argtypes = [vp, vp]
+    lib.sepaihrd_ensemble_stochastic.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, C.c_int] + [vp] * 7
+    lib.sepaihrd_stochastic_validate.argtypes = [C.c_int] * 7 + [vp, C.c_int, C.c_char_p, C.c_int]
+    lib.sepaihrd_stochastic_values_width.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.sepaihrd_stochastic_timing.argtypes = [vp, vp]
     lib.sepaihrd_poisson_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
     if path is None:
         _lib = lib
@@ -599,6 +604,37 @@ class HipObjective:
             out["means"] = means
         if want_draws:
             out["draws"] = draws
+        return out
+
+    def ensemble_stochastic(self, theta, R: int, steps_per_interval: int, seed: int, probs, keep: int = 0, want_extinct: bool = True,
+                            want_values: bool = False, want_final: bool = False) -> dict:
+        """Stochastic chain-binomial SEPAIHRD replicates of every sample (sepaihrd_ensemble_stochastic): R replicates per row
+        of theta, steps_per_interval binomial steps per output interval.  quantiles [6][n_probs][T_pos][n] (daily
+        hospitalisations, ICU admissions, deaths and their running sums over the replicates of the valid samples), extinct [S],
+        model_values [S][W], traj [S][keep][T][11][n], final_state [S][R][11][n], status [S], n_valid, phase_ms (step kernel;
+        sorts and quantiles)."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        S, npb, n, R, keep = th.shape[0], pr.size, self.pb.n, int(R), int(keep)
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        W = self.lib.sepaihrd_stochastic_values_width(n, len(self.pb.beta_end_times), len(self.pb.kappa_end_times))
+        q = np.empty((6, npb, Tp, n))
+        extinct = np.empty(S) if want_extinct else None
+        values = np.empty((S, W)) if want_values else None
+        traj = np.empty((S, keep, self.pb.n_times, 11, n)) if 0 < keep <= max(R, 0) else None
+        final = np.empty((S, max(R, 0), 11, n)) if want_final else None
+        status = np.empty(S, dtype=np.int32)
+        nv = C.c_int32(0)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.sepaihrd_ensemble_stochastic(
+            self.ctx, th.ctypes.data, S, R, int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, npb, keep, q.ctypes.data,
+            ptr(extinct), ptr(values), ptr(traj), ptr(final), status.ctypes.data, C.byref(nv)), "ensemble_stochastic")
+        ms = np.zeros(2)
+        self._check(self.lib.sepaihrd_stochastic_timing(self.ctx, ms.ctypes.data), "stochastic_timing")
+        out = {"quantiles": q, "status": status, "n_valid": nv.value, "phase_ms": ms}
+        for key, arr in (("extinct", extinct), ("model_values", values), ("traj", traj), ("final_state", final)):
+            if arr is not None:
+                out[key] = arr
         return out
 
     def poisson(self, lam, seed: int) -> np.ndarray:

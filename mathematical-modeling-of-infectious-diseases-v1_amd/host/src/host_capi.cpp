@@ -15,6 +15,7 @@
 #include "epidemic_hip/MultiChainNUTSSampler.hpp"
 #include "epidemic_hip/HipPosteriorEnsemble.hpp"
 #include "epidemic_hip/HipPosteriorPredictive.hpp"
+#include "epidemic_hip/HipStochasticSEPAIHRD.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipSIR.hpp"
 #include "epidemic_hip/HipSIRScenarioAnalysis.hpp"
@@ -1609,6 +1610,73 @@ int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const doub
         *samples_used = d.samples_used;
         return 0;
     } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// ---- stochastic chain-binomial SEPAIHRD ensembles (HipStochasticSEPAIHRD) ----
+// hostStochasticSEPAIHRD (no device): shapes as sepaihrd_ensemble_stochastic; M row-major, M[i n_age + j] = M(i, j)
+int host_stochastic_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                                const double* beta_end_times, const double* kappa_end_times, const double* model_values, const int32_t* status,
+                                int S, int R, int steps_per_interval, uint64_t seed, const double* probs, int n_probs, int keep, double* quantiles,
+                                double* extinct, double* traj, double* final_state, char* err, int errlen) {
+    StochasticSEPAIHRDFixedData fd;
+    fd.n_age = n_age; fd.n_times = n_times; fd.n_beta = n_beta; fd.n_kappa = n_kappa;
+    fd.times = times; fd.N = N; fd.M = M; fd.beta_end_times = beta_end_times; fd.kappa_end_times = kappa_end_times;
+    std::string error;
+    const int rc = hostStochasticSEPAIHRD(fd, model_values, status, S, R, steps_per_interval, seed, probs, n_probs, keep, quantiles, extinct, traj,
+                                          final_state, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
+// HipStochasticSEPAIHRD::run over the handle's parameter manager / data.  samples: n_samples x P, selected by the PPC rule
+// (num_samples, select_seed).  quantiles [6][n_probs][T_pos][n]; extinct, selected and status: capacity max(n_samples, num_samples).
+int host_stochastic(void* hv, const sepaihrd_problem* pb, int device, int initial_state_mode, const double* samples, int n_samples, int num_samples,
+                    uint32_t select_seed, int R, int steps_per_interval, uint64_t seed, const double* probs, int n_probs, double* quantiles,
+                    double* extinct, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
+    auto* h = static_cast<HostHandle*>(hv);
+    try {
+        const int n = pb->n_age;
+        const size_t P = h->pm->getParameterCount();
+        HipStochasticSEPAIHRD model(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
+                                    strategy_for(pb->solver), device, initial_state_mode);
+        std::vector<Eigen::VectorXd> ps;
+        for (int s = 0; s < n_samples; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+        const StochasticSEPAIHRDResult d = model.run(ps, num_samples, select_seed, R, steps_per_interval, seed, std::vector<double>(probs, probs + n_probs));
+        std::copy(d.quantiles.begin(), d.quantiles.end(), quantiles);
+        if (extinct) std::copy(d.extinct.begin(), d.extinct.end(), extinct);
+        for (size_t i = 0; i < d.selected.size(); ++i) selected[i] = d.selected[i];
+        *n_selected = static_cast<int32_t>(d.selected.size());
+        if (status) std::copy(d.status.begin(), d.status.end(), status);
+        *samples_used = d.samples_used;
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// The parameter part of a model_values row (everything before the initial counts) as the handle's parameter manager writes it:
+// updateModelParameters(theta) in the given constraint mode, then the model parameters in the row's order.  0 ok, 1 = exception.
+int host_stochastic_manager_values(void* hv, int mode, const double* theta, double* out) {
+    auto* h = static_cast<HostHandle*>(hv);
+    const ConstraintMode keep = h->pm->getConstraintMode();
+    try {
+        h->pm->setConstraintMode(mode == 1 ? ConstraintMode::MCMC_REFLECT : ConstraintMode::OPTIMIZATION_CLAMP);
+        h->pm->updateModelParameters(vec(theta, static_cast<int>(h->pm->getParameterCount())));
+        h->pm->setConstraintMode(keep);
+        const SEPAIHRDParameters& mp = h->pm->modelParameters();
+        size_t at = 0;
+        for (double v : {mp.theta, mp.sigma, mp.gamma_p, mp.gamma_A, mp.gamma_I, mp.gamma_H, mp.gamma_ICU, mp.beta}) out[at++] = v;
+        for (double v : mp.beta_values) out[at++] = v;
+        for (double v : mp.kappa_values) out[at++] = v;
+        for (const Eigen::VectorXd* f : {&mp.a, &mp.h_infec, &mp.p, &mp.h, &mp.icu, &mp.d_H, &mp.d_ICU, &mp.d_community})
+            for (Eigen::Index i = 0; i < f->size(); ++i) out[at++] = (*f)[i];
+        return 0;
+    } catch (const std::exception& e) {
+        h->pm->setConstraintMode(keep);
         g_error = e.what();
         return 1;
     }

@@ -114,6 +114,11 @@ def load_library() -> C.CDLL:
                                                C.c_char_p, C.c_int]
     lib.host_predictive.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint64,
                                     vp, C.c_int] + [vp] * 9
+    lib.host_stochastic_from_values.argtypes = [C.c_int] * 4 + [vp] * 7 + [C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, C.c_int] + \
+        [vp] * 4 + [C.c_char_p, C.c_int]
+    lib.host_stochastic_manager_values.argtypes = [vp, C.c_int, vp, vp]
+    lib.host_stochastic.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
+                                    C.c_uint64, vp, C.c_int] + [vp] * 6
     _lib = lib
     return lib
 
@@ -376,6 +381,39 @@ class HostObjective:
             out["means"] = means
         if want_draws:
             out["draws"] = draws
+        return out
+
+    def posterior_stochastic(self, samples, num_samples: int, select_seed: int, R: int, steps_per_interval: int, seed: int,
+                             probs=(0.025, 0.05, 0.5, 0.95, 0.975), initial_state_mode: int = 1, device: int = -1) -> dict:
+        """HipStochasticSEPAIHRD::run over this handle's parameter manager and data: the samples picked by the PPC rule of
+        posterior_ensemble, R chain-binomial replicates each.  quantiles [6][n_probs][T_pos][n], extinct, selected, status,
+        samples_used."""
+        ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        cap = max(ps.shape[0], num_samples, 1)
+        q = np.empty((6, pr.size, Tp, self.pb.n))
+        extinct, sel, status = np.empty(cap), np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        nsel, used = C.c_int32(0), C.c_int32(0)
+        rc = self.lib.host_stochastic(self.h, C.byref(st), device, int(initial_state_mode), ps.ctypes.data, ps.shape[0], num_samples,
+                                      select_seed, int(R), int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size,
+                                      q.ctypes.data, extinct.ctypes.data, sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used))
+        if rc != 0:
+            raise RuntimeError("host_stochastic: " + self.lib.host_last_error().decode())
+        k = nsel.value
+        return {"quantiles": q, "extinct": extinct[:k].copy(), "selected": sel[:k].copy(), "status": status[:k].copy(),
+                "samples_used": used.value}
+
+    def stochastic_manager_values(self, theta, mode: int) -> np.ndarray:
+        """The parameter part of a model_values row of sepaihrd_ensemble_stochastic (all but the 11 n initial counts) as this
+        handle's parameter manager writes it: updateModelParameters(theta) in the given constraint mode."""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        W = stochastic_values_width(self.pb.n, len(self.pb.beta_end_times), len(self.pb.kappa_end_times)) - 11 * self.pb.n
+        out = np.empty(W)
+        if self.lib.host_stochastic_manager_values(self.h, int(mode), th.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError("host_stochastic_manager_values: " + self.lib.host_last_error().decode())
         return out
 
     def scenario_comparison(self, samples, burn_in: int = 0, thinning: int = 1, path: str | None = None, device: int = -1) -> dict:
@@ -1034,4 +1072,79 @@ def predictive_from_means(means, status, observed, R: int, seed: int, probs, wan
         out["pit"] = pit
     if draws is not None:
         out["draws"] = draws
+    return out
+
+
+# ---- stochastic chain-binomial SEPAIHRD ensembles: the CPU twin of sepaihrd_ensemble_stochastic ----
+STOCH_COMPARTMENTS = ("S", "E", "P", "A", "I", "H", "ICU", "R", "D", "CumH", "CumICU")
+STOCH_SCALARS = ("theta", "sigma", "gamma_p", "gamma_A", "gamma_I", "gamma_H", "gamma_ICU", "beta")
+STOCH_VECTORS = ("a", "h_infec", "p", "h", "icu", "d_H", "d_ICU", "d_community")
+
+
+def stochastic_values_width(n_age: int, n_beta: int, n_kappa: int) -> int:
+    """sepaihrd_stochastic_values_width: the width W of a model_values row"""
+    return int(hipabi.load_library().sepaihrd_stochastic_values_width(int(n_age), int(n_beta), int(n_kappa)))
+
+
+def stochastic_pack_values(n_age: int, initial, beta_values=(), kappa_values=(1.0,), **fields) -> np.ndarray:
+    """One model_values row in the layout include/sepaihrd_hip.h documents: the scalars of STOCH_SCALARS and the per-age vectors of
+    STOCH_VECTORS by keyword (default 0), the schedule values, and initial [11][n_age] counts."""
+    n = int(n_age)
+    unknown = set(fields) - set(STOCH_SCALARS) - set(STOCH_VECTORS)
+    if unknown:
+        raise ValueError(f"unknown fields {sorted(unknown)}")
+    row = [float(fields.get(k, 0.0)) for k in STOCH_SCALARS]
+    row += [float(v) for v in beta_values] + [float(v) for v in kappa_values]
+    for k in STOCH_VECTORS:
+        row += list(np.broadcast_to(np.asarray(fields.get(k, 0.0), dtype=np.float64), (n,)))
+    row += list(np.asarray(initial, dtype=np.float64).reshape(11, n).ravel())
+    out = np.asarray(row, dtype=np.float64)
+    assert out.size == stochastic_values_width(n, len(beta_values), len(kappa_values))
+    return out
+
+
+def stochastic_validate(S: int, R: int, steps_per_interval: int, keep: int, n_times: int, T_pos: int, n_age: int, probs) -> None:
+    """sepaihrd_stochastic_validate (host only): ValueError with its message for arguments the stochastic call refuses"""
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    err = C.create_string_buffer(512)
+    if hipabi.load_library().sepaihrd_stochastic_validate(int(S), int(R), int(steps_per_interval), int(keep), int(n_times), int(T_pos),
+                                                          int(n_age), pr.ctypes.data, pr.size, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def stochastic_from_values(model_values, status, times, N, M, kappa_end_times, R: int, steps_per_interval: int, seed: int, probs,
+                           beta_end_times=(), keep: int = 0, want_final: bool = True) -> dict:
+    """The twin of HipObjective.ensemble_stochastic after the decoding: from model_values [S][W] and status [S] and the problem's
+    fixed data (times, N [n], M [n][n] with M[i, j] = M(i, j), the schedule end times) the same quantiles [6][n_probs][T_pos][n],
+    extinct [S], traj [S][keep][T][11][n] and final_state [S][R][11][n], bit for bit."""
+    mv = np.ascontiguousarray(np.atleast_2d(model_values), dtype=np.float64)
+    st = np.ascontiguousarray(status, dtype=np.int32).ravel()
+    tm = np.ascontiguousarray(times, dtype=np.float64).ravel()
+    Nv = np.ascontiguousarray(N, dtype=np.float64).ravel()
+    n = Nv.size
+    Mm = np.ascontiguousarray(M, dtype=np.float64)
+    be = np.ascontiguousarray(beta_end_times, dtype=np.float64).ravel()
+    ke = np.ascontiguousarray(kappa_end_times, dtype=np.float64).ravel()
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    S, T, R, keep = mv.shape[0], tm.size, int(R), int(keep)
+    Tp = int(np.sum(tm >= 0.0))
+    if Mm.shape != (n, n) or st.shape != (S,) or mv.shape[1] != stochastic_values_width(n, be.size, ke.size):
+        raise ValueError("model_values [S][W], status [S], N [n], M [n][n]")
+    stochastic_validate(S, R, steps_per_interval, keep, T, Tp, n, pr)
+    q, extinct = np.empty((6, pr.size, Tp, n)), np.empty(S)
+    traj = np.empty((S, keep, T, 11, n)) if keep > 0 else None
+    final = np.empty((S, R, 11, n)) if want_final else None
+    err = C.create_string_buffer(512)
+    rc = load_library().host_stochastic_from_values(n, T, be.size, ke.size, tm.ctypes.data, Nv.ctypes.data, Mm.ctypes.data,
+                                                    be.ctypes.data if be.size else None, ke.ctypes.data, mv.ctypes.data, st.ctypes.data, S, R,
+                                                    int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, keep,
+                                                    q.ctypes.data, extinct.ctypes.data, None if traj is None else traj.ctypes.data,
+                                                    None if final is None else final.ctypes.data, err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    out = {"quantiles": q, "extinct": extinct, "n_valid": int(np.sum(st == 0))}
+    if traj is not None:
+        out["traj"] = traj
+    if final is not None:
+        out["final_state"] = final
     return out
