@@ -14,16 +14,24 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_fd_device.h"
+#include "sepaihrd_host_util.h"
 #include "sepaihrd_mh_backend.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_segments.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
 using namespace sepaihrd;
+
+// The roles of the buffers the ensemble entry points keep with their context.  sepaihrd_ensemble_quantiles uses the first
+// nine; sepaihrd_scenario_ensemble uses the same nine for the same things, sized for K scenarios, and four of its own.
+enum EnsSlot {
+    SLOT_THETA, SLOT_LOGLIK, SLOT_VALS, SLOT_TRAJ, SLOT_PROBS, SLOT_QUANTILES, SLOT_N_VALID, SLOT_METRICS, SLOT_SORT_SCRATCH,
+    SLOT_KAPPA_MULT, SLOT_SCEN_VALS, SLOT_SCEN_SUMMARY, SLOT_SCEN_COUNTS, SLOT_COUNT
+};
 
 struct sepaihrd_ctx {
     int device = 0;
@@ -37,11 +45,8 @@ struct sepaihrd_ctx {
     std::vector<uint8_t> has_bounds;
     int n = 0, T = 0, P = 0;
     std::vector<double> host_N;  // population sizes (ensemble seroprevalence)
-    // buffers of sepaihrd_ensemble_quantiles, kept between calls (grow-only): allocating tens of GB per call
-    // costs more than the kernels at large ensembles
-    // (slots 0-8; sepaihrd_scenario_ensemble shares them by role and adds 9-12)
-    void* ens_buf[13] = {};
-    size_t ens_cap[13] = {};
+    // buffers of sepaihrd_ensemble_quantiles and sepaihrd_scenario_ensemble, kept between calls
+    GrowSlots<SLOT_COUNT> ens;
     std::string last_error;
     // staging buffers for the host-pointer entry point (grown on demand)
     size_t cap_B = 0;
@@ -100,19 +105,6 @@ struct sepaihrd_ctx {
 };
 
 namespace {
-
-void set_err(char* err, int errlen, const std::string& msg) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
-}
-
-#define HIP_TRY(expr, ctx, fail)                                                             \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);           \
-            fail;                                                                            \
-        }                                                                                    \
-    } while (0)
 
 template <class T>
 const T* upload(sepaihrd_ctx* ctx, const std::vector<T>& v, bool& ok) {
@@ -266,6 +258,50 @@ int fetch_results(sepaihrd_ctx* ctx, hipStream_t st, int B, double* loglik, int3
     if (n_accept) std::memcpy(n_accept, h + off_nacc, n * sizeof(int32_t));
     if (n_reject) std::memcpy(n_reject, h + off_nrej, n * sizeof(int32_t));
     return SEPAIHRD_OK;
+}
+
+int refuse(sepaihrd_ctx* ctx, const char* who, const std::string& msg, int rc) {
+    ctx->last_error = std::string(who) + ": " + msg;
+    return rc;
+}
+
+// The opening checks the ensemble entry points share.  Always: the arguments every call needs (have_args, with the text
+// `need` that names them) and n_probs in 1..1024.  Then those of `checks`, in this order; an entry point that has checks of
+// its own in between asks in several steps (need == nullptr: the arguments were checked before).
+enum : unsigned { CHECK_PROBS = 1, CHECK_PENDING = 2, CHECK_F64 = 4, CHECK_TP = 8 };
+int ensemble_preflight(sepaihrd_ctx* ctx, const char* who, bool have_args, const char* need, unsigned checks, const double* probs = nullptr,
+                       int n_probs = 0) {
+    if (need != nullptr && (!have_args || n_probs <= 0 || n_probs > 1024)) return refuse(ctx, who, need, SEPAIHRD_E_INVALID_ARG);
+    if ((checks & CHECK_PROBS) && !probabilities_valid(probs, n_probs))
+        return refuse(ctx, who, "probabilities must lie in [0, 1]", SEPAIHRD_E_INVALID_ARG);
+    if ((checks & CHECK_PENDING) && ctx->pending_B > 0)
+        return refuse(ctx, who, "a sepaihrd_eval_batch_begin is pending on this context", SEPAIHRD_E_INVALID_ARG);
+    if ((checks & CHECK_F64) && ctx->precision != SEPAIHRD_PRECISION_F64)
+        return refuse(ctx, who, "the ensemble summaries read the fp64 integrator's parked increments (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    if ((checks & CHECK_TP) && ctx->dp.T - ctx->dp.runup_offset <= 0) return refuse(ctx, who, "no output time >= 0", SEPAIHRD_E_INVALID_ARG);
+    return SEPAIHRD_OK;
+}
+
+// The integrator on B chains in the context's arithmetic, on the null stream; d_kappa_mult: the scenario build's launch, chain
+// c with row c / stride of the table.  A failure becomes the context's last error (after `prefix`) and the C ABI's code.
+int launch_eval_for(sepaihrd_ctx* ctx, const char* prefix, const double* d_theta, int B, const EvalOutputs& out,
+                    const double* d_kappa_mult = nullptr, int stride = 0) {
+    const bool fma = ctx->arith == SEPAIHRD_ARITH_FMA;
+    int rc;
+    if (d_kappa_mult != nullptr)
+        rc = fma ? launch_eval_scenario_fma(ctx->dp, ctx->solver, d_theta, B, out, nullptr, d_kappa_mult, stride)
+                 : launch_eval_scenario_strict(ctx->dp, ctx->solver, d_theta, B, out, nullptr, d_kappa_mult, stride);
+    else
+        rc = fma ? launch_eval_fma(ctx->dp, ctx->solver, d_theta, B, out, nullptr) : launch_eval_strict(ctx->dp, ctx->solver, d_theta, B, out, nullptr);
+    if (rc == 0) return SEPAIHRD_OK;
+    ctx->last_error = std::string(prefix) + (rc == -4 ? "unsupported lanes-per-chain" : "kernel launch failed");
+    return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
+}
+
+double total_population(const sepaihrd_ctx* ctx) {
+    double total_pop = 0.0;
+    for (int i = 0; i < ctx->dp.n; ++i) total_pop += ctx->host_N[(size_t)i];
+    return total_pop;
 }
 
 }  // namespace
@@ -512,8 +548,7 @@ void sepaihrd_destroy(sepaihrd_ctx* ctx) {
     if (ctx->own_stream) { (void)hipStreamSynchronize(ctx->own_stream); (void)hipStreamDestroy(ctx->own_stream); }
     free_staging(ctx);
     free_workspace(ctx);
-    for (void* p : ctx->ens_buf)
-        if (p) (void)hipFree(p);
+    ctx->ens.release();
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->busy_event) (void)hipEventDestroy(ctx->busy_event);
     if (ctx->fd_dev) (void)hipFree(ctx->fd_dev);
@@ -838,150 +873,94 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx* ctx, const double* theta, int S, c
                                 double* ppc_quantiles, double* sero_quantiles, double* rt_quantiles, double* metrics,
                                 int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    if (S <= 0 || !theta || !probs || n_probs <= 0 || n_probs > 1024 || !ppc_quantiles) {
-        ctx->last_error = "ensemble_quantiles: need S > 0, theta, probs (1..1024) and ppc_quantiles";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    for (int p = 0; p < n_probs; ++p)
-        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) {
-            ctx->last_error = "ensemble_quantiles: probabilities must lie in [0, 1]";
-            return SEPAIHRD_E_INVALID_ARG;
-        }
-    if (ctx->pending_B > 0) {
-        ctx->last_error = "ensemble_quantiles: a sepaihrd_eval_batch_begin is pending on this context";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    if (ctx->precision != SEPAIHRD_PRECISION_F64) {
-        ctx->last_error = "ensemble_quantiles: the ensemble summaries read the fp64 integrator's parked increments (set precision F64)";
-        return SEPAIHRD_E_UNSUPPORTED;
-    }
+    const char* const who = "ensemble_quantiles";
+    int rc = ensemble_preflight(ctx, who, S > 0 && theta && probs && ppc_quantiles, "need S > 0, theta, probs (1..1024) and ppc_quantiles",
+                                CHECK_PROBS | CHECK_PENDING | CHECK_F64 | CHECK_TP, probs, n_probs);
+    if (rc != SEPAIHRD_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    // sizes
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
-    if (Tp <= 0) {
-        ctx->last_error = "ensemble_quantiles: no output time >= 0";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    int S_pad = WAVE;
-    while (S_pad < S && S_pad < ENSEMBLE_MAX_SAMPLES) S_pad <<= 1;
-    const bool big = S > ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
-    if (big) S_pad = (S + WAVE - 1) / WAVE * WAVE;
+    const SegmentPlan plan = plan_segments((size_t)S);  // a segment: the S samples of one (series, time, age)
+    const int S_pad = (int)plan.pad;
     const size_t cpw = (size_t)(WAVE / dp.lpc);
     const size_t chains = ((size_t)S + cpw - 1) / cpw * cpw;
-    int rc = ensure_workspace(ctx, chains);
-    if (rc != SEPAIHRD_OK) return rc;
-
     const bool want_sero = sero_quantiles != nullptr, want_metrics = metrics != nullptr;
     const bool want_rt = rt_quantiles != nullptr || want_metrics;  // the metric table reads the Rt values
     const bool want_traj = want_sero || want_rt;
-    if (want_rt && dp.n > 16) {
-        ctx->last_error = "ensemble_quantiles: Rt trajectories are built for at most 16 age classes";
-        return SEPAIHRD_E_UNSUPPORTED;
-    }
     const size_t n_ppc = (size_t)6 * n_probs * Tp * dp.n;
     const size_t n_sero = want_sero ? (size_t)n_probs * dp.T : 0;
     const size_t n_rt = want_rt ? (size_t)n_probs * dp.T : 0;
     const size_t n_vals = ((size_t)6 * Tp * dp.n + (want_sero ? dp.T : 0) + (want_rt ? dp.T : 0)) * S_pad;
     const size_t n_traj = want_traj ? (size_t)S * dp.T * NUM_COMP * dp.n : 0;
+    const size_t n_scratch = sort_scratch_doubles(plan, n_vals);
+    const size_t n_metrics = want_metrics ? (size_t)S * (12 + 4 * dp.n) : 0;
+    // buffers: they stay with the context
+    rc = ensure_workspace(ctx, chains);
+    if (rc != SEPAIHRD_OK) return rc;
+    if (want_rt && dp.n > 16) return refuse(ctx, who, "Rt trajectories are built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
     double *d_theta = nullptr, *d_ll = nullptr, *d_vals = nullptr, *d_traj = nullptr, *d_probs = nullptr, *d_q = nullptr,
            *d_metrics = nullptr, *d_scratch = nullptr;
-    // scratch of the global sort: up to 2 GiB, at least one segment
-    const size_t n_scratch = big ? std::max<size_t>((size_t)S_pad, std::min<size_t>(n_vals, (size_t)1 << 28) / S_pad * S_pad) : 0;
-    const size_t n_metrics = want_metrics ? (size_t)S * (12 + 4 * dp.n) : 0;
     int32_t* d_nv = nullptr;
-    auto cleanup = [&]() {};  // the buffers stay with the context
-    int slot = 0;
-    auto dalloc = [&](void** p, size_t bytes) {
-        const int k = slot++;
-        if (bytes == 0) bytes = 8;
-        if (ctx->ens_cap[k] < bytes) {
-            if (ctx->ens_buf[k]) (void)hipFree(ctx->ens_buf[k]);
-            ctx->ens_buf[k] = nullptr;
-            ctx->ens_cap[k] = 0;
-            if (hipMalloc(&ctx->ens_buf[k], bytes) != hipSuccess) return false;
-            ctx->ens_cap[k] = bytes;
-        }
-        *p = ctx->ens_buf[k];
-        return true;
-    };
-    if (!dalloc((void**)&d_theta, (size_t)S * ctx->P * sizeof(double)) || !dalloc((void**)&d_ll, (size_t)S * sizeof(double)) ||
-        !dalloc((void**)&d_vals, n_vals * sizeof(double)) || !dalloc((void**)&d_traj, n_traj * sizeof(double)) ||
-        !dalloc((void**)&d_probs, (size_t)n_probs * sizeof(double)) || !dalloc((void**)&d_q, (n_ppc + n_sero + n_rt) * sizeof(double)) ||
-        !dalloc((void**)&d_nv, sizeof(int32_t)) || !dalloc((void**)&d_metrics, n_metrics * sizeof(double)) ||
-        !dalloc((void**)&d_scratch, n_scratch * sizeof(double))) {
-        cleanup();
-        ctx->last_error = "ensemble_quantiles: device allocation failed";
-        return SEPAIHRD_E_HIP;
-    }
-    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx,
-            { cleanup(); return SEPAIHRD_E_HIP; });
-    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx,
-            { cleanup(); return SEPAIHRD_E_HIP; });
+    auto& slots = ctx->ens;
+    if (!slots.get(SLOT_THETA, &d_theta, (size_t)S * ctx->P) || !slots.get(SLOT_LOGLIK, &d_ll, (size_t)S) ||
+        !slots.get(SLOT_VALS, &d_vals, n_vals) || !slots.get(SLOT_TRAJ, &d_traj, n_traj) ||
+        !slots.get(SLOT_PROBS, &d_probs, (size_t)n_probs) || !slots.get(SLOT_QUANTILES, &d_q, n_ppc + n_sero + n_rt) ||
+        !slots.get(SLOT_N_VALID, &d_nv, 1) || !slots.get(SLOT_METRICS, &d_metrics, n_metrics) ||
+        !slots.get(SLOT_SORT_SCRATCH, &d_scratch, n_scratch))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
+    // uploads
+    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
     EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, want_traj ? d_traj : nullptr,
                     ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
     rc = fence_before(ctx, nullptr);  // an evaluation of this context may still be running on another stream
     if (rc != SEPAIHRD_OK) return rc;
-    rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_eval_fma(dp, ctx->solver, d_theta, S, out, nullptr)
-                                          : launch_eval_strict(dp, ctx->solver, d_theta, S, out, nullptr);
-    if (rc != 0) {
-        cleanup();
-        ctx->last_error = rc == -4 ? "unsupported lanes-per-chain" : "kernel launch failed";
-        return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
-    }
-    double total_pop = 0.0;
-    for (int i = 0; i < dp.n; ++i) total_pop += ctx->host_N[(size_t)i];
+    rc = launch_eval_for(ctx, "", d_theta, S, out);
+    if (rc != SEPAIHRD_OK) return rc;
     EnsembleArgs a{};
     a.S = S; a.S_pad = S_pad; a.lpc = dp.lpc; a.n = dp.n; a.T = dp.T; a.Tp = Tp; a.runup_offset = dp.runup_offset;
     a.n_probs = n_probs;
     a.cum_stride = chains * dp.lpc;
     a.cum = ctx->ws_cum; a.wstatus = ctx->ws_status; a.traj = want_traj ? d_traj : nullptr;
-    a.total_pop = total_pop;
+    a.total_pop = total_population(ctx);
     a.vals = d_vals; a.probs = d_probs; a.q_out = d_q; a.sero_out = want_sero ? d_q + n_ppc : nullptr; a.n_valid = d_nv;
     a.rt_out = want_rt ? d_q + n_ppc + n_sero : nullptr;
     a.rt_segment0 = 6 * Tp * dp.n + (want_sero ? dp.T : 0);
     a.pb = &ctx->dp;
     a.theta = d_theta;
     a.metrics_out = want_metrics ? d_metrics : nullptr;
-    a.sort_scratch = big ? d_scratch : nullptr;
+    a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
-    rc = launch_ensemble_summaries(a, nullptr);
-    if (rc != 0) {
-        cleanup();
+    if (launch_ensemble_summaries(a, nullptr) != 0) {
         ctx->last_error = "ensemble summary launch failed";
         return SEPAIHRD_E_HIP;
     }
-    HIP_TRY(hipDeviceSynchronize(), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
-    HIP_TRY(hipMemcpy(ppc_quantiles, d_q, n_ppc * sizeof(double), hipMemcpyDeviceToHost), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    // fetches
+    HIP_TRY(hipMemcpy(ppc_quantiles, d_q, n_ppc * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     if (want_sero)
-        HIP_TRY(hipMemcpy(sero_quantiles, d_q + n_ppc, n_sero * sizeof(double), hipMemcpyDeviceToHost), ctx,
-                { cleanup(); return SEPAIHRD_E_HIP; });
+        HIP_TRY(hipMemcpy(sero_quantiles, d_q + n_ppc, n_sero * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     if (rt_quantiles)
-        HIP_TRY(hipMemcpy(rt_quantiles, d_q + n_ppc + n_sero, n_rt * sizeof(double), hipMemcpyDeviceToHost), ctx,
-                { cleanup(); return SEPAIHRD_E_HIP; });
+        HIP_TRY(hipMemcpy(rt_quantiles, d_q + n_ppc + n_sero, n_rt * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     if (want_metrics)
-        HIP_TRY(hipMemcpy(metrics, d_metrics, n_metrics * sizeof(double), hipMemcpyDeviceToHost), ctx,
-                { cleanup(); return SEPAIHRD_E_HIP; });
+        HIP_TRY(hipMemcpy(metrics, d_metrics, n_metrics * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     if (status)
-        HIP_TRY(hipMemcpy(status, ctx->ws_status, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost), ctx,
-                { cleanup(); return SEPAIHRD_E_HIP; });
-    if (n_valid)
-        HIP_TRY(hipMemcpy(n_valid, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
-    cleanup();
+        HIP_TRY(hipMemcpy(status, ctx->ws_status, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (n_valid) HIP_TRY(hipMemcpy(n_valid, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 
 int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* probs, int n_probs,
                                  double* pred_quantiles, double* pit, double* means, double* draws, int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    auto refuse = [&](const std::string& msg, int rc) { ctx->last_error = "ensemble_predictive: " + msg; return rc; };
-    if (S <= 0 || !theta || !probs || n_probs <= 0 || n_probs > 1024 || !pred_quantiles)
-        return refuse("need S > 0, theta, probs (1..1024) and pred_quantiles", SEPAIHRD_E_INVALID_ARG);
-    if (ctx->pending_B > 0) return refuse("a sepaihrd_eval_batch_begin is pending on this context", SEPAIHRD_E_INVALID_ARG);
-    if (ctx->precision != SEPAIHRD_PRECISION_F64)
-        return refuse("the ensemble summaries read the fp64 integrator's parked increments (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    const char* const who = "ensemble_predictive";
+    int rc = ensemble_preflight(ctx, who, S > 0 && theta && probs && pred_quantiles, "need S > 0, theta, probs (1..1024) and pred_quantiles",
+                                CHECK_PENDING | CHECK_F64 | CHECK_TP, probs, n_probs);
+    if (rc != SEPAIHRD_OK) return rc;
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
-    if (Tp <= 0) return refuse("no output time >= 0", SEPAIHRD_E_INVALID_ARG);
     {
         char msg[256] = "";
         if (sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
@@ -990,69 +969,48 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
         }
     }
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
-    // a segment holds the S R draws of one (series, time, age): stride and padding as EnsembleArgs::S_pad
+    // sizes
     const size_t N = (size_t)S * (size_t)R;
-    size_t N_pad = WAVE;
-    while (N_pad < N && N_pad < (size_t)ENSEMBLE_MAX_SAMPLES) N_pad <<= 1;
-    const bool big = N > (size_t)ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
-    if (big) N_pad = (N + WAVE - 1) / WAVE * WAVE;
-    if (N_pad >= ((size_t)1 << 31)) return refuse("S x R rounded up to whole wavefronts must stay below 2^31", SEPAIHRD_E_INVALID_ARG);
+    const SegmentPlan plan = plan_segments(N);  // a segment: the S R draws of one (series, time, age)
+    const size_t N_pad = plan.pad;
+    if (N_pad >= ((size_t)1 << 31)) return refuse(ctx, who, "S x R rounded up to whole wavefronts must stay below 2^31", SEPAIHRD_E_INVALID_ARG);
     const size_t cpw = (size_t)(WAVE / dp.lpc);
     const size_t chains = ((size_t)S + cpw - 1) / cpw * cpw;
     const size_t cells = (size_t)3 * Tp * dp.n;
     const size_t n_q = (size_t)6 * n_probs * Tp * dp.n;
     const size_t n_vals = 2 * cells * N_pad;
-    const size_t n_scratch = big ? std::max<size_t>(N_pad, std::min<size_t>(n_vals, (size_t)1 << 28) / N_pad * N_pad) : 0;
+    const size_t n_scratch = sort_scratch_doubles(plan, n_vals);
     const size_t n_means = means ? (size_t)S * cells : 0, n_draws = draws ? N * cells : 0;
     // the rule of sepaihrd_scenario_ensemble: the buffers below plus the likelihood workspace must fit the device's memory
-    // (the segment table dominates: 6 T_pos n_age segments of S R doubles); larger requests are refused before anything is allocated
+    // (the segment table dominates: 6 T_pos n_age segments of S R doubles)
     const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + (size_t)n_probs) +
                               sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) +
                               sizeof(int32_t) * (chains + 2);
-    size_t device_bytes = 0;
-    HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
-    if (need_bytes > device_bytes)
-        return refuse("the segment table of S x R = " + std::to_string(N) + " draws needs " + std::to_string(need_bytes >> 20) +
-                          " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
-                          " MiB: split the samples or the replicates over several calls",
-                      SEPAIHRD_E_INVALID_ARG);
-    int rc = ensure_workspace(ctx, chains);
+    rc = require_device_memory(ctx, need_bytes, "ensemble_predictive: the segment table of S x R = " + std::to_string(N) + " draws needs",
+                               "split the samples or the replicates over several calls");
     if (rc != SEPAIHRD_OK) return rc;
     // buffers and events of this call alone: the context's own (sepaihrd_ensemble_quantiles') stay as they are
-    struct Scratch {
-        std::vector<void*> bufs;
-        hipEvent_t ev[4] = {};
-        ~Scratch() {
-            for (void* b : bufs) if (b) (void)hipFree(b);
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        }
-        bool alloc(void** p, size_t bytes) {
-            void* q = nullptr;
-            if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return false; }
-            bufs.push_back(q);
-            *p = q;
-            return true;
-        }
-    } sc;
+    rc = ensure_workspace(ctx, chains);
+    if (rc != SEPAIHRD_OK) return rc;
+    CallScratch sc(4);
     double *d_theta = nullptr, *d_ll = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_pit = nullptr,
            *d_means = nullptr, *d_draws = nullptr;
     int32_t* d_counts = nullptr;
-    if (!sc.alloc((void**)&d_theta, (size_t)S * ctx->P * sizeof(double)) || !sc.alloc((void**)&d_ll, (size_t)S * sizeof(double)) ||
-        !sc.alloc((void**)&d_vals, n_vals * sizeof(double)) || !sc.alloc((void**)&d_scratch, n_scratch * sizeof(double)) ||
-        !sc.alloc((void**)&d_probs, (size_t)n_probs * sizeof(double)) || !sc.alloc((void**)&d_q, n_q * sizeof(double)) ||
-        !sc.alloc((void**)&d_pit, cells * sizeof(double)) || !sc.alloc((void**)&d_means, n_means * sizeof(double)) ||
-        !sc.alloc((void**)&d_draws, n_draws * sizeof(double)) || !sc.alloc((void**)&d_counts, 2 * sizeof(int32_t)))
-        return refuse("device allocation failed", SEPAIHRD_E_HIP);
+    if (!sc.alloc(&d_theta, (size_t)S * ctx->P) || !sc.alloc(&d_ll, (size_t)S) || !sc.alloc(&d_vals, n_vals) ||
+        !sc.alloc(&d_scratch, n_scratch) || !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_pit, cells) ||
+        !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (hipEvent_t& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    // uploads
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
     EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
     rc = fence_before(ctx, nullptr);  // an evaluation of this context may still be running on another stream
     if (rc != SEPAIHRD_OK) return rc;
     (void)hipEventRecord(sc.ev[0], nullptr);
-    rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_eval_fma(dp, ctx->solver, d_theta, S, out, nullptr)
-                                          : launch_eval_strict(dp, ctx->solver, d_theta, S, out, nullptr);
-    if (rc != 0) return refuse(rc == -4 ? "unsupported lanes-per-chain" : "kernel launch failed", rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP);
+    rc = launch_eval_for(ctx, "ensemble_predictive: ", d_theta, S, out);
+    if (rc != SEPAIHRD_OK) return rc;
     (void)hipEventRecord(sc.ev[1], nullptr);
     PredictiveArgs a{};
     a.S = S; a.R = R; a.N_pad = (int)N_pad;
@@ -1061,11 +1019,11 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     a.cum = ctx->ws_cum; a.wstatus = ctx->ws_status; a.grid = dp.grid;
     a.vals = d_vals; a.means = means ? d_means : nullptr; a.draws = draws ? d_draws : nullptr;
     a.n_probs = n_probs; a.probs = d_probs; a.q_out = d_q; a.pit_out = pit ? d_pit : nullptr; a.counts = d_counts;
-    a.sort_scratch = big ? d_scratch : nullptr;
+    a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
-    if (launch_predictive_draws(a, nullptr) != 0) return refuse("draw kernel launch failed", SEPAIHRD_E_HIP);
+    if (launch_predictive_draws(a, nullptr) != 0) return refuse(ctx, who, "draw kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
-    if (launch_predictive_quantiles(a, nullptr) != 0) return refuse("quantile launch failed", SEPAIHRD_E_HIP);
+    if (launch_predictive_quantiles(a, nullptr) != 0) return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[3], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
     for (int i = 0; i < 3; ++i) {
@@ -1073,17 +1031,15 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
         (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
         ctx->pred_ms[i] = ms;
     }
-    bool ok = true;
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        if (ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-    };
-    fetch(pred_quantiles, d_q, n_q * sizeof(double));
-    fetch(pit, d_pit, cells * sizeof(double));
-    fetch(means, d_means, n_means * sizeof(double));
-    fetch(draws, d_draws, n_draws * sizeof(double));
-    fetch(status, ctx->ws_status, (size_t)S * sizeof(int32_t));
-    fetch(n_valid, d_counts, sizeof(int32_t));
-    if (!ok) return refuse("copy of the results failed", SEPAIHRD_E_HIP);
+    // fetches
+    ResultFetch res;
+    res.fetch(pred_quantiles, d_q, n_q * sizeof(double));
+    res.fetch(pit, d_pit, cells * sizeof(double));
+    res.fetch(means, d_means, n_means * sizeof(double));
+    res.fetch(draws, d_draws, n_draws * sizeof(double));
+    res.fetch(status, ctx->ws_status, (size_t)S * sizeof(int32_t));
+    res.fetch(n_valid, d_counts, sizeof(int32_t));
+    if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 
@@ -1097,10 +1053,10 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
                                  const double* probs, int n_probs, int keep, double* quantiles, double* extinct, double* model_values,
                                  double* traj, double* final_state, int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    auto refuse = [&](const std::string& msg, int rc) { ctx->last_error = "ensemble_stochastic: " + msg; return rc; };
-    if (S <= 0 || !theta || !probs || n_probs <= 0 || n_probs > 1024 || !quantiles)
-        return refuse("need S > 0, theta, probs (1..1024) and quantiles", SEPAIHRD_E_INVALID_ARG);
-    if (ctx->pending_B > 0) return refuse("a sepaihrd_eval_batch_begin is pending on this context", SEPAIHRD_E_INVALID_ARG);
+    const char* const who = "ensemble_stochastic";
+    int rc = ensemble_preflight(ctx, who, S > 0 && theta && probs && quantiles, "need S > 0, theta, probs (1..1024) and quantiles",
+                                CHECK_PENDING, probs, n_probs);
+    if (rc != SEPAIHRD_OK) return rc;
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
     {
@@ -1110,74 +1066,54 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
             return SEPAIHRD_E_INVALID_ARG;
         }
     }
-    if (keep > 0 && !traj) return refuse("keep > 0 needs traj", SEPAIHRD_E_INVALID_ARG);
-    if (ctx->precision != SEPAIHRD_PRECISION_F64) return refuse("the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
-    if (dp.n > 16 || dp.lpc > 16) return refuse("built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
+    if (keep > 0 && !traj) return refuse(ctx, who, "keep > 0 needs traj", SEPAIHRD_E_INVALID_ARG);
+    if (ctx->precision != SEPAIHRD_PRECISION_F64)
+        return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    if (dp.n > 16 || dp.lpc > 16) return refuse(ctx, who, "built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
-    // a segment holds the S R replicates of one (series, time, age): stride and padding as EnsembleArgs::S_pad
+    // sizes
     const size_t N = (size_t)S * (size_t)R;
-    size_t N_pad = WAVE;
-    while (N_pad < N && N_pad < (size_t)ENSEMBLE_MAX_SAMPLES) N_pad <<= 1;
-    const bool big = N > (size_t)ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
-    if (big) N_pad = (N + WAVE - 1) / WAVE * WAVE;
+    const SegmentPlan plan = plan_segments(N);  // a segment: the S R replicates of one (series, time, age)
+    const size_t N_pad = plan.pad;
     const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
     const size_t cells = (size_t)3 * Tp * dp.n;
     const size_t n_q = (size_t)6 * n_probs * Tp * dp.n;
     const size_t n_vals = 2 * cells * N_pad;
-    const size_t n_scratch = big ? std::max<size_t>(N_pad, std::min<size_t>(n_vals, (size_t)1 << 28) / N_pad * N_pad) : 0;
+    const size_t n_scratch = sort_scratch_doubles(plan, n_vals);
     const size_t n_values = (size_t)S * W;
     const size_t n_traj = (traj && keep > 0) ? (size_t)S * keep * dp.T * NUM_COMP * dp.n : 0;
     const size_t n_final = final_state ? N * NUM_COMP * dp.n : 0;
     // the rule of sepaihrd_ensemble_predictive: what is allocated below must fit the device's memory (the segment table
-    // dominates); larger requests are refused before anything is allocated
+    // dominates)
     const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + n_vals + n_scratch + n_q + n_values + n_traj + n_final + (size_t)n_probs) +
                               sizeof(int32_t) * (2 * (size_t)S + 2);
-    size_t device_bytes = 0;
-    HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
-    if (need_bytes > device_bytes)
-        return refuse("the segment table of S x R = " + std::to_string(N) + " replicates and the outputs asked for need " +
-                          std::to_string(need_bytes >> 20) + " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
-                          " MiB: split the samples or the replicates over several calls",
-                      SEPAIHRD_E_INVALID_ARG);
-    struct Scratch {
-        std::vector<void*> bufs;
-        hipEvent_t ev[3] = {};
-        ~Scratch() {
-            for (void* b : bufs) if (b) (void)hipFree(b);
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        }
-        bool alloc(void** p, size_t bytes) {
-            void* q = nullptr;
-            if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); return false; }
-            bufs.push_back(q);
-            *p = q;
-            return true;
-        }
-    } sc;
+    rc = require_device_memory(ctx, need_bytes,
+                               "ensemble_stochastic: the segment table of S x R = " + std::to_string(N) + " replicates and the outputs asked for need",
+                               "split the samples or the replicates over several calls");
+    if (rc != SEPAIHRD_OK) return rc;
+    // buffers and events of this call alone
+    CallScratch sc(3);
     double *d_theta = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_values = nullptr, *d_traj = nullptr,
            *d_final = nullptr;
     int32_t *d_counts = nullptr, *d_status = nullptr, *d_extinct = nullptr;
-    if (!sc.alloc((void**)&d_theta, (size_t)S * ctx->P * sizeof(double)) || !sc.alloc((void**)&d_vals, n_vals * sizeof(double)) ||
-        !sc.alloc((void**)&d_scratch, n_scratch * sizeof(double)) || !sc.alloc((void**)&d_probs, (size_t)n_probs * sizeof(double)) ||
-        !sc.alloc((void**)&d_q, n_q * sizeof(double)) || !sc.alloc((void**)&d_values, n_values * sizeof(double)) ||
-        !sc.alloc((void**)&d_traj, n_traj * sizeof(double)) || !sc.alloc((void**)&d_final, n_final * sizeof(double)) ||
-        !sc.alloc((void**)&d_counts, 2 * sizeof(int32_t)) || !sc.alloc((void**)&d_status, (size_t)S * sizeof(int32_t)) ||
-        !sc.alloc((void**)&d_extinct, (size_t)S * sizeof(int32_t)))
-        return refuse("device allocation failed", SEPAIHRD_E_HIP);
+    if (!sc.alloc(&d_theta, (size_t)S * ctx->P) || !sc.alloc(&d_vals, n_vals) || !sc.alloc(&d_scratch, n_scratch) ||
+        !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_traj, n_traj) ||
+        !sc.alloc(&d_final, n_final) || !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)S) || !sc.alloc(&d_extinct, (size_t)S))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (hipEvent_t& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    // uploads
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
     StochEpiArgs a{};
     a.S = S; a.R = R; a.N_pad = (int)N_pad;
     a.m = steps_per_interval; a.keep = n_traj ? keep : 0; a.W = W;
     a.seed = seed;
     a.theta = d_theta; a.values = d_values; a.status = d_status; a.counts = d_counts; a.extinct_count = d_extinct;
     a.vals = d_vals; a.traj = n_traj ? d_traj : nullptr; a.final_state = final_state ? d_final : nullptr;
-    int rc = launch_stoch_epi_decode(dp, a, nullptr);
-    if (rc != 0) return refuse("decode kernel launch failed", SEPAIHRD_E_HIP);
+    if (launch_stoch_epi_decode(dp, a, nullptr) != 0) return refuse(ctx, who, "decode kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[0], nullptr);
-    rc = launch_stoch_epi_steps(dp, a, nullptr);
-    if (rc != 0) return refuse("step kernel launch failed", SEPAIHRD_E_HIP);
+    if (launch_stoch_epi_steps(dp, a, nullptr) != 0) return refuse(ctx, who, "step kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[1], nullptr);
     PredictiveArgs pa{};
     pa.S = S; pa.R = R; pa.N_pad = (int)N_pad;
@@ -1186,9 +1122,9 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
     pa.wstatus = d_status;
     pa.vals = d_vals;
     pa.n_probs = n_probs; pa.probs = d_probs; pa.q_out = d_q; pa.counts = d_counts;
-    pa.sort_scratch = big ? d_scratch : nullptr;
+    pa.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     pa.sort_scratch_doubles = n_scratch;
-    if (launch_predictive_quantiles(pa, nullptr) != 0) return refuse("quantile launch failed", SEPAIHRD_E_HIP);
+    if (launch_predictive_quantiles(pa, nullptr) != 0) return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
     for (int i = 0; i < 2; ++i) {
@@ -1196,19 +1132,17 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
         (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
         ctx->stoch_ms[i] = ms;
     }
-    bool ok = true;
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        if (ok && dst && bytes && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-    };
+    // fetches
+    ResultFetch res;
     std::vector<int32_t> h_status((size_t)S), h_extinct((size_t)S);
-    fetch(quantiles, d_q, n_q * sizeof(double));
-    fetch(model_values, d_values, n_values * sizeof(double));
-    fetch(traj, d_traj, n_traj * sizeof(double));
-    fetch(final_state, d_final, n_final * sizeof(double));
-    fetch(h_status.data(), d_status, (size_t)S * sizeof(int32_t));
-    fetch(h_extinct.data(), d_extinct, (size_t)S * sizeof(int32_t));
-    fetch(n_valid, d_counts, sizeof(int32_t));
-    if (!ok) return refuse("copy of the results failed", SEPAIHRD_E_HIP);
+    res.fetch(quantiles, d_q, n_q * sizeof(double));
+    res.fetch(model_values, d_values, n_values * sizeof(double));
+    res.fetch(traj, d_traj, n_traj * sizeof(double));
+    res.fetch(final_state, d_final, n_final * sizeof(double));
+    res.fetch(h_status.data(), d_status, (size_t)S * sizeof(int32_t));
+    res.fetch(h_extinct.data(), d_extinct, (size_t)S * sizeof(int32_t));
+    res.fetch(n_valid, d_counts, sizeof(int32_t));
+    if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     if (status) std::copy(h_status.begin(), h_status.end(), status);
     if (extinct)
         for (int s = 0; s < S; ++s)
@@ -1227,58 +1161,33 @@ int sepaihrd_scenario_ensemble(sepaihrd_ctx* ctx, const double* theta, int S, co
                                double* rt_quantiles, double* metrics, double* metric_summary, double* diff_quantiles,
                                int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    if (S <= 0 || K <= 0 || !theta || !kappa_mult || !probs || n_probs <= 0 || n_probs > 1024) {
-        ctx->last_error = "scenario_ensemble: need S > 0, K > 0, theta, kappa_mult and probs (1..1024)";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    for (int p = 0; p < n_probs; ++p)
-        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) {
-            ctx->last_error = "scenario_ensemble: probabilities must lie in [0, 1]";
-            return SEPAIHRD_E_INVALID_ARG;
-        }
+    const char* const who = "scenario_ensemble";
+    int rc = ensemble_preflight(ctx, who, S > 0 && K > 0 && theta && kappa_mult && probs, "need S > 0, K > 0, theta, kappa_mult and probs (1..1024)",
+                                CHECK_PROBS, probs, n_probs);
+    if (rc != SEPAIHRD_OK) return rc;
     const DevProblem& dp = ctx->dp;
-    if (n_kappa != dp.nk) {
-        ctx->last_error = "scenario_ensemble: the multiplier table must have one column per kappa value";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
+    if (n_kappa != dp.nk) return refuse(ctx, who, "the multiplier table must have one column per kappa value", SEPAIHRD_E_INVALID_ARG);
     for (size_t i = 0; i < (size_t)K * n_kappa; ++i)
-        if (!(std::isfinite(kappa_mult[i]) && kappa_mult[i] >= 0.0)) {
-            ctx->last_error = "scenario_ensemble: kappa multipliers must be finite and >= 0";
-            return SEPAIHRD_E_INVALID_ARG;
-        }
-    if (ctx->pending_B > 0) {
-        ctx->last_error = "scenario_ensemble: a sepaihrd_eval_batch_begin is pending on this context";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    if (ctx->precision != SEPAIHRD_PRECISION_F64) {
-        ctx->last_error = "scenario_ensemble: the ensemble summaries read the fp64 integrator's parked increments (set precision F64)";
-        return SEPAIHRD_E_UNSUPPORTED;
-    }
-    if (dp.n > 16) {
-        ctx->last_error = "scenario_ensemble: the metric table needs Rt trajectories, built for at most 16 age classes";
-        return SEPAIHRD_E_UNSUPPORTED;
-    }
+        if (!(std::isfinite(kappa_mult[i]) && kappa_mult[i] >= 0.0))
+            return refuse(ctx, who, "kappa multipliers must be finite and >= 0", SEPAIHRD_E_INVALID_ARG);
+    rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING | CHECK_F64);
+    if (rc != SEPAIHRD_OK) return rc;
+    if (dp.n > 16) return refuse(ctx, who, "the metric table needs Rt trajectories, built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
+    rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_TP);
+    if (rc != SEPAIHRD_OK) return rc;
     const int Tp = dp.T - dp.runup_offset;
-    if (Tp <= 0) {
-        ctx->last_error = "scenario_ensemble: no output time >= 0";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
     // scenario k's samples are chains k S_str .. k S_str + S - 1: S_str = S rounded up to whole waves' worth of chains, so that
     // every scenario's parked increments start on a wave boundary of the workspace (the ensemble passes then read it in place)
     const size_t cpw = (size_t)(WAVE / dp.lpc);
     const size_t S_str = ((size_t)S + cpw - 1) / cpw * cpw;
     const size_t B = (size_t)(K - 1) * S_str + (size_t)S;  // the last scenario needs no padding chains
-    if (B > (size_t)std::numeric_limits<int32_t>::max() / 2) {
-        ctx->last_error = "scenario_ensemble: K x S chains exceed one launch (the workspace is sized by a 32-bit chain count)";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
+    if (B > (size_t)std::numeric_limits<int32_t>::max() / 2)
+        return refuse(ctx, who, "K x S chains exceed one launch (the workspace is sized by a 32-bit chain count)", SEPAIHRD_E_INVALID_ARG);
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
-    int S_pad = WAVE;
-    while (S_pad < S && S_pad < ENSEMBLE_MAX_SAMPLES) S_pad <<= 1;
-    const bool big = S > ENSEMBLE_MAX_SAMPLES;
-    if (big) S_pad = (S + WAVE - 1) / WAVE * WAVE;
+    // sizes
+    const SegmentPlan plan = plan_segments((size_t)S);  // a segment: the S samples of one cell of one scenario
+    const int S_pad = (int)plan.pad;
     const size_t chains = (B + cpw - 1) / cpw * cpw;
-
     const bool want_sero = sero_quantiles != nullptr;
     const int W = 12 + 4 * dp.n;
     const size_t P = (size_t)ctx->P;
@@ -1290,71 +1199,47 @@ int sepaihrd_scenario_ensemble(sepaihrd_ctx* ctx, const double* theta, int S, co
     const size_t n_svals = (size_t)2 * K * W * S_pad;
     const size_t n_metrics = (size_t)K * S * W;
     const size_t n_summary = (size_t)K * W * (2 + n_probs), n_diff = (size_t)K * W * n_probs;
-    const size_t n_scratch =
-        big ? std::max<size_t>((size_t)S_pad, std::min<size_t>(std::max(n_vals, n_svals), (size_t)1 << 28) / S_pad * S_pad) : 0;
+    const size_t n_scratch = sort_scratch_doubles(plan, std::max(n_vals, n_svals));
     // K x S within one launch: the device buffers below plus the likelihood workspace must fit the device's memory
-    // (the trajectories dominate: K S T 11 n doubles); larger requests are refused before anything is allocated
+    // (the trajectories dominate: K S T 11 n doubles)
     const size_t need_bytes =
         sizeof(double) * (chains * P + chains + n_vals + chains * dp.T * NUM_COMP * dp.n + (size_t)K * n_q + n_metrics + n_scratch +
                           (size_t)K * n_kappa + n_svals + n_summary + n_diff + (size_t)n_probs) +
         sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) + sizeof(int32_t) * (chains + 3 * (size_t)K);
-    size_t device_bytes = 0;
-    HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
-    if (need_bytes > device_bytes) {
-        ctx->last_error = "scenario_ensemble: K x S = " + std::to_string((size_t)K * S) + " runs need " +
-                          std::to_string(need_bytes >> 20) + " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
-                          " MiB: split the scenarios or the samples over several calls";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    int rc = ensure_workspace(ctx, chains);
+    rc = require_device_memory(ctx, need_bytes, "scenario_ensemble: K x S = " + std::to_string((size_t)K * S) + " runs need",
+                               "split the scenarios or the samples over several calls");
     if (rc != SEPAIHRD_OK) return rc;
-    auto cleanup = [&]() {};  // the buffers stay with the context (grow-only, shared by role with sepaihrd_ensemble_quantiles)
-    auto dalloc = [&](int k, auto** p, size_t elems) {
-        const size_t bytes = std::max<size_t>(elems * sizeof(**p), 8);
-        if (ctx->ens_cap[k] < bytes) {
-            if (ctx->ens_buf[k]) (void)hipFree(ctx->ens_buf[k]);
-            ctx->ens_buf[k] = nullptr;
-            ctx->ens_cap[k] = 0;
-            if (hipMalloc(&ctx->ens_buf[k], bytes) != hipSuccess) return false;
-            ctx->ens_cap[k] = bytes;
-        }
-        *p = static_cast<std::remove_reference_t<decltype(*p)>>(ctx->ens_buf[k]);
-        return true;
-    };
+    // buffers: they stay with the context, the ones sepaihrd_ensemble_quantiles uses in the same roles
+    rc = ensure_workspace(ctx, chains);
+    if (rc != SEPAIHRD_OK) return rc;
     double *d_theta = nullptr, *d_ll = nullptr, *d_mult = nullptr, *d_traj = nullptr, *d_vals = nullptr, *d_svals = nullptr,
            *d_probs = nullptr, *d_q = nullptr, *d_metrics = nullptr, *d_summary = nullptr, *d_scratch = nullptr;
     int32_t *d_nv = nullptr, *d_counts = nullptr;
-    if (!dalloc(0, &d_theta, chains * P) || !dalloc(1, &d_ll, chains) || !dalloc(2, &d_vals, n_vals) ||
-        !dalloc(3, &d_traj, chains * dp.T * NUM_COMP * dp.n) || !dalloc(4, &d_probs, (size_t)n_probs) ||
-        !dalloc(5, &d_q, (size_t)K * n_q) || !dalloc(6, &d_nv, (size_t)K) || !dalloc(7, &d_metrics, n_metrics) ||
-        !dalloc(8, &d_scratch, n_scratch) || !dalloc(9, &d_mult, (size_t)K * n_kappa) || !dalloc(10, &d_svals, n_svals) ||
-        !dalloc(11, &d_summary, n_summary + n_diff) || !dalloc(12, &d_counts, (size_t)2 * K)) {
-        ctx->last_error = "scenario_ensemble: device allocation failed";
-        return SEPAIHRD_E_HIP;
-    }
-    // every scenario integrates the same samples; the padding chains repeat the scenario's first sample and are never read
+    auto& slots = ctx->ens;
+    if (!slots.get(SLOT_THETA, &d_theta, chains * P) || !slots.get(SLOT_LOGLIK, &d_ll, chains) || !slots.get(SLOT_VALS, &d_vals, n_vals) ||
+        !slots.get(SLOT_TRAJ, &d_traj, chains * dp.T * NUM_COMP * dp.n) || !slots.get(SLOT_PROBS, &d_probs, (size_t)n_probs) ||
+        !slots.get(SLOT_QUANTILES, &d_q, (size_t)K * n_q) || !slots.get(SLOT_N_VALID, &d_nv, (size_t)K) ||
+        !slots.get(SLOT_METRICS, &d_metrics, n_metrics) || !slots.get(SLOT_SORT_SCRATCH, &d_scratch, n_scratch) ||
+        !slots.get(SLOT_KAPPA_MULT, &d_mult, (size_t)K * n_kappa) || !slots.get(SLOT_SCEN_VALS, &d_svals, n_svals) ||
+        !slots.get(SLOT_SCEN_SUMMARY, &d_summary, n_summary + n_diff) || !slots.get(SLOT_SCEN_COUNTS, &d_counts, (size_t)2 * K))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
+    // uploads.  Every scenario integrates the same samples; the padding chains repeat the scenario's first sample and are never read
     std::vector<double> h_theta(B * P);
     for (size_t c = 0; c < B; ++c) {
         const size_t s = c % S_str;
         std::memcpy(&h_theta[c * P], theta + (s < (size_t)S ? s : 0) * P, P * sizeof(double));
     }
-    HIP_TRY(hipMemcpy(d_theta, h_theta.data(), B * P * sizeof(double), hipMemcpyHostToDevice), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
-    HIP_TRY(hipMemcpy(d_mult, kappa_mult, (size_t)K * n_kappa * sizeof(double), hipMemcpyHostToDevice), ctx,
-            { cleanup(); return SEPAIHRD_E_HIP; });
-    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
+    HIP_TRY(hipMemcpy(d_theta, h_theta.data(), B * P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_mult, kappa_mult, (size_t)K * n_kappa * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
     EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, d_traj, ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
     rc = fence_before(ctx, nullptr);
-    if (rc != SEPAIHRD_OK) { cleanup(); return rc; }
+    if (rc != SEPAIHRD_OK) return rc;
     // the integrator scales kappa per scenario (scenario build of the kernels); the Rt and metric passes read ctx->dp, unscaled
-    rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_eval_scenario_fma(dp, ctx->solver, d_theta, (int)B, out, nullptr, d_mult, (int)S_str)
-                                          : launch_eval_scenario_strict(dp, ctx->solver, d_theta, (int)B, out, nullptr, d_mult, (int)S_str);
-    if (rc != 0) {
-        cleanup();
-        ctx->last_error = rc == -4 ? "unsupported lanes-per-chain" : "kernel launch failed";
-        return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
-    }
-    double total_pop = 0.0;
-    for (int i = 0; i < dp.n; ++i) total_pop += ctx->host_N[(size_t)i];
+    rc = launch_eval_for(ctx, "", d_theta, (int)B, out, d_mult, (int)S_str);
+    if (rc != SEPAIHRD_OK) return rc;
+    const double total_pop = total_population(ctx);
     // series, seroprevalence, Rt, metric table and their quantiles: once per scenario, on the scenario's block of chains
     for (int k = 0; k < K && rc == 0; ++k) {
         const size_t c0 = (size_t)k * S_str;
@@ -1375,7 +1260,7 @@ int sepaihrd_scenario_ensemble(sepaihrd_ctx* ctx, const double* theta, int S, co
         a.pb = &ctx->dp;
         a.theta = d_theta + c0 * P;
         a.metrics_out = d_metrics + (size_t)k * S * W;
-        a.sort_scratch = big ? d_scratch : nullptr;
+        a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
         a.sort_scratch_doubles = n_scratch;
         rc = launch_ensemble_summaries(a, nullptr);
     }
@@ -1385,36 +1270,29 @@ int sepaihrd_scenario_ensemble(sepaihrd_ctx* ctx, const double* theta, int S, co
         sa.metrics = d_metrics; sa.wstatus = ctx->ws_status; sa.status_stride = S_str;
         sa.vals = d_svals; sa.counts = d_counts;
         sa.summary_out = d_summary; sa.diff_out = d_summary + n_summary;
-        sa.sort_scratch = big ? d_scratch : nullptr;
+        sa.sort_scratch = plan.in_lds ? nullptr : d_scratch;
         sa.sort_scratch_doubles = n_scratch;
         rc = launch_scenario_summaries(sa, nullptr);
     }
     if (rc != 0) {
-        cleanup();
         ctx->last_error = "scenario summary launch failed";
         return SEPAIHRD_E_HIP;
     }
-    HIP_TRY(hipDeviceSynchronize(), ctx, { cleanup(); return SEPAIHRD_E_HIP; });
-    bool ok = true;
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        if (ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-    };
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    // fetches
+    ResultFetch res;
     for (int k = 0; k < K; ++k) {
         const double* q = d_q + (size_t)k * n_q;
-        fetch(ppc_quantiles ? ppc_quantiles + (size_t)k * n_ppc : nullptr, q, n_ppc * sizeof(double));
-        fetch(want_sero ? sero_quantiles + (size_t)k * n_sero : nullptr, q + n_ppc, n_sero * sizeof(double));
-        fetch(rt_quantiles ? rt_quantiles + (size_t)k * n_rt : nullptr, q + n_ppc + n_sero, n_rt * sizeof(double));
-        fetch(status ? status + (size_t)k * S : nullptr, ctx->ws_status + (size_t)k * S_str, (size_t)S * sizeof(int32_t));
+        res.fetch(ppc_quantiles ? ppc_quantiles + (size_t)k * n_ppc : nullptr, q, n_ppc * sizeof(double));
+        res.fetch(want_sero ? sero_quantiles + (size_t)k * n_sero : nullptr, q + n_ppc, n_sero * sizeof(double));
+        res.fetch(rt_quantiles ? rt_quantiles + (size_t)k * n_rt : nullptr, q + n_ppc + n_sero, n_rt * sizeof(double));
+        res.fetch(status ? status + (size_t)k * S : nullptr, ctx->ws_status + (size_t)k * S_str, (size_t)S * sizeof(int32_t));
     }
-    fetch(metrics, d_metrics, n_metrics * sizeof(double));
-    fetch(metric_summary, d_summary, n_summary * sizeof(double));
-    fetch(diff_quantiles, d_summary + n_summary, n_diff * sizeof(double));
-    fetch(n_valid, d_nv, (size_t)K * sizeof(int32_t));
-    cleanup();
-    if (!ok) {
-        ctx->last_error = "scenario_ensemble: copy of the results failed";
-        return SEPAIHRD_E_HIP;
-    }
+    res.fetch(metrics, d_metrics, n_metrics * sizeof(double));
+    res.fetch(metric_summary, d_summary, n_summary * sizeof(double));
+    res.fetch(diff_quantiles, d_summary + n_summary, n_diff * sizeof(double));
+    res.fetch(n_valid, d_nv, (size_t)K * sizeof(int32_t));
+    if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 

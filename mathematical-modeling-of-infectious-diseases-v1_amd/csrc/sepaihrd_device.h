@@ -126,9 +126,9 @@ int phase_pass_applied_fma();
 int poisson_log_values(const double* d_x, int n, double* d_out, void* stream);
 
 // ---- posterior ensemble summaries (csrc/sepaihrd_ensemble.hip) ----
-constexpr int ENSEMBLE_MAX_SAMPLES = 16384;  // one sorted segment lives in LDS (128 KiB of 160 KiB)
+constexpr int ENSEMBLE_MAX_SAMPLES = 16384;  // one sorted segment lives in LDS (128 KiB of 160 KiB); read by csrc/sepaihrd_segments.h
 struct EnsembleArgs {
-    int S, S_pad;             // samples; stride of a segment: a power of two >= 64 (LDS sort) or a multiple of 64
+    int S, S_pad;             // samples; stride of a segment: plan_segments(S).pad (csrc/sepaihrd_segments.h)
     int lpc, n, T, Tp;        // lanes per chain, ages, output times, output times with t >= 0
     int runup_offset;         // index of the first output time >= 0
     int n_probs;
@@ -148,7 +148,7 @@ struct EnsembleArgs {
     const DevProblem* pb;     // host pointer to the ctx's problem (kernel argument by value)
     const double* theta;      // [S][P] device, the samples
     double* metrics_out;      // [S][12 + 4 n] per-sample summary metrics, device or null (needs rt_out)
-    // ensembles beyond the LDS sort (S_pad > ENSEMBLE_MAX_SAMPLES): scratch for groups of globally sorted segments
+    // ensembles beyond the LDS sort (the plan of S_pad is not in_lds): scratch for groups of globally sorted segments
     double* sort_scratch;
     size_t sort_scratch_doubles;
 };
@@ -166,7 +166,7 @@ struct ScenarioArgs {
     int32_t* counts;          // [2 K] device: valid samples per scenario, then valid in both the scenario and scenario 0
     double* summary_out;      // [K][W][2 + n_probs] mean, std_dev, quantiles, or null
     double* diff_out;         // [K][W][n_probs] quantiles of metric[k][s] - metric[0][s], or null
-    double* sort_scratch;     // as EnsembleArgs (S_pad > ENSEMBLE_MAX_SAMPLES)
+    double* sort_scratch;     // as EnsembleArgs
     size_t sort_scratch_doubles;
 };
 int launch_scenario_summaries(const ScenarioArgs& a, void* stream);

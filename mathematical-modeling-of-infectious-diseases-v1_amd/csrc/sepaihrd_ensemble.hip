@@ -19,9 +19,10 @@
 // Layout: the integrator leaves the increments in cum[T][3][S*lpc] (sample-major columns).  Pass 1
 // (one lane per (sample, age)) walks the days and writes every series value into
 // vals[segment][S_pad] with the SAMPLE index contiguous, so that pass 2 (one workgroup per segment)
-// loads its segment coalesced, sorts it in LDS (bitonic, S_pad <= 16384 doubles = 128 KiB) and
+// loads its segment coalesced, sorts it in LDS (bitonic, up to 16384 doubles = 128 KiB) and
 // interpolates the quantiles.  Samples whose integration failed are +inf and sort to the end; the
-// quantile positions use the count of valid samples.
+// quantile positions use the count of valid samples.  How a segment is padded and when it is sorted
+// in global memory instead: csrc/sepaihrd_segments.h; the one dispatch: sort_segments_and_pick below.
 // Compiled with -ffp-contract=off: the interpolation is the CPU build's operation sequence.
 // =============================================================================
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_segments.h"
 #include "sepaihrd_sir_device.h"
 #include "sepaihrd_stoch_device.h"
 #include "sepaihrd_stoch.inc"
@@ -548,6 +550,44 @@ int sort_segments_global(const double* vals, int segments, int S_pad, double* sc
     return (rc == 0 && hipGetLastError() == hipSuccess) ? 0 : -3;
 }
 
+// what every launcher asks of the segments it is handed: `count` values each, in a pad the plan gives (sepaihrd_segments.h)
+bool pad_legal(size_t count, int pad) { return pad > 0 && segment_pad_valid(count, (size_t)pad); }
+
+// the LDS sort of plan.pad doubles needs the kernel's dynamic-LDS limit raised above 48 KiB; 0 or -3
+int raise_lds_limit(const SegmentPlan& plan, const void* lds_kernel) {
+    const size_t lds = plan.pad * sizeof(double);
+    if (!plan.in_lds || lds <= 48 * 1024) return 0;
+    return hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -3;
+}
+
+// Sort every segment, then pick from it, by the plan's route.  In LDS: launch_lds(threads, lds_bytes) launches `lds_kernel`
+// with one workgroup per segment (null: the caller has raised its LDS limit already).  In global memory:
+// sort_segments_global with pick(first, n_group).  0, -3 (HIP failure) or -4 (no segment fits the scratch).
+template <class LaunchLds, class Pick>
+int sort_segments_and_pick(const SegmentPlan& plan, int segments, const double* vals, double* scratch, size_t scratch_doubles,
+                           hipStream_t st, const void* lds_kernel, LaunchLds launch_lds, Pick pick) {
+    if (!plan.in_lds) return sort_segments_global(vals, segments, (int)plan.pad, scratch, scratch_doubles, st, pick);
+    if (lds_kernel != nullptr && raise_lds_limit(plan, lds_kernel) != 0) return -3;
+    launch_lds(plan.pad / 2 < 1024 ? (int)(plan.pad / 2) : 1024, plan.pad * sizeof(double));
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// the interpolated quantiles of `segments` segments of e.vals (e.S_pad apart, e.n_valid values each) into e's outputs
+int launch_segment_quantiles(const EnsembleArgs& e, int n_series_segments, int segments, double* scratch, size_t scratch_doubles,
+                             hipStream_t st, bool lds_limit_raised = false) {
+    return sort_segments_and_pick(
+        plan_of_pad((size_t)e.S_pad), segments, e.vals, scratch, scratch_doubles, st,
+        lds_limit_raised ? nullptr : reinterpret_cast<const void*>(&ensemble_quantile_kernel),
+        [&](int threads, size_t lds) {
+            hipLaunchKernelGGL(ensemble_quantile_kernel, dim3((unsigned)segments), dim3(threads), lds, st, e, n_series_segments);
+        },
+        [&](int first, int ng) {
+            const size_t work = (size_t)ng * e.n_probs;
+            hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, e,
+                               n_series_segments, scratch, first, ng);
+        });
+}
+
 // ---- age-structured SIR: posterior ensemble and intervention scenarios (sepaihrd_sir_scenario_ensemble) ----
 // The ensemble build of the SIR integrator (csrc/sepaihrd_sir.hip) has stored the series of every valid chain in
 // vals[((k 3 + series) T + t) (n + 1) + column][S_pad].  Fix-up: the rows of samples that failed (at any point of the run)
@@ -687,36 +727,27 @@ __global__ __launch_bounds__(WAVE) void sir_ens_metrics_kernel(const SirEnsSumma
 
 int launch_scenario_summaries(const ScenarioArgs& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool in_lds = a.S_pad <= ENSEMBLE_MAX_SAMPLES;
-    if (a.K <= 0 || a.S <= 0 || a.W <= 0 || a.S_pad < WAVE || a.S > a.S_pad ||
-        (in_lds ? (a.S_pad & (a.S_pad - 1)) != 0 : a.S_pad % WAVE != 0))
-        return -4;
+    if (a.K <= 0 || a.S <= 0 || a.W <= 0 || !pad_legal((size_t)a.S, a.S_pad)) return -4;
     const int segments = 2 * a.K * a.W;
     hipLaunchKernelGGL(scenario_count_kernel, dim3(2 * a.K), dim3(256), 0, st, a);
     const size_t cells = (size_t)a.K * a.W * a.S_pad;
     hipLaunchKernelGGL(scenario_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a);
     if (a.summary_out != nullptr)
         hipLaunchKernelGGL(scenario_moments_kernel, dim3((unsigned)((a.K * a.W + 63) / 64)), dim3(64), 0, st, a);
-    if (!in_lds)
-        return sort_segments_global(a.vals, segments, a.S_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
+    return sort_segments_and_pick(
+        plan_of_pad((size_t)a.S_pad), segments, a.vals, a.sort_scratch, a.sort_scratch_doubles, st,
+        reinterpret_cast<const void*>(&scenario_quantile_kernel),
+        [&](int threads, size_t lds) { hipLaunchKernelGGL(scenario_quantile_kernel, dim3(segments), dim3(threads), lds, st, a); },
+        [&](int first, int ng) {
             const size_t work = (size_t)ng * a.n_probs;
             hipLaunchKernelGGL(scenario_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a,
                                a.sort_scratch, first, ng);
         });
-    const int threads = a.S_pad / 2 < 1024 ? a.S_pad / 2 : 1024;
-    const size_t lds = (size_t)a.S_pad * sizeof(double);
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&scenario_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return -3;
-    hipLaunchKernelGGL(scenario_quantile_kernel, dim3(segments), dim3(threads), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool in_lds = a.S_pad <= ENSEMBLE_MAX_SAMPLES;
-    if (a.S <= 0 || a.S_pad < WAVE || a.S > a.S_pad || (in_lds ? (a.S_pad & (a.S_pad - 1)) != 0 : a.S_pad % WAVE != 0)) return -4;
+    if (a.S <= 0 || !pad_legal((size_t)a.S, a.S_pad)) return -4;
     hipLaunchKernelGGL(ensemble_count_valid_kernel, dim3(1), dim3(256), 0, st, a.wstatus, a.S, a.n_valid);
     const size_t cols = (size_t)a.S_pad * a.lpc;
     hipLaunchKernelGGL(ensemble_series_kernel, dim3((unsigned)((cols + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, a);
@@ -733,23 +764,7 @@ int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
         hipLaunchKernelGGL(ensemble_metrics_kernel, dim3((unsigned)((a.S + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, a, *a.pb, a.theta);
     }
     const int segments = n_series_segments + (sero ? a.T : 0) + (rt ? a.T : 0);
-    if (!in_lds) {
-        // segments of S_pad doubles sorted in groups by rocPRIM's segmented radix sort (8 passes over the keys)
-        // into a scratch buffer, quantiles picked from it; group size bounded by the scratch buffer
-        return sort_segments_global(a.vals, segments, a.S_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
-            const size_t work = (size_t)ng * a.n_probs;
-            hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a,
-                               n_series_segments, a.sort_scratch, first, ng);
-        });
-    }
-    const int threads = a.S_pad / 2 < 1024 ? a.S_pad / 2 : 1024;
-    const size_t lds = (size_t)a.S_pad * sizeof(double);
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return -3;
-    hipLaunchKernelGGL(ensemble_quantile_kernel, dim3(segments), dim3(threads), lds, st, a, n_series_segments);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_segment_quantiles(a, n_series_segments, segments, a.sort_scratch, a.sort_scratch_doubles, st);
 }
 
 }  // namespace sepaihrd
@@ -758,10 +773,7 @@ namespace sepaihrd {
 
 int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool in_lds = a.S_pad <= ENSEMBLE_MAX_SAMPLES;
-    if (a.K <= 0 || a.S <= 0 || a.n < 1 || a.n > SIR_MAX_AGE || a.T < 1 || a.S_pad < WAVE || a.S > a.S_pad ||
-        (in_lds ? (a.S_pad & (a.S_pad - 1)) != 0 : a.S_pad % WAVE != 0))
-        return -4;
+    if (a.K <= 0 || a.S <= 0 || a.n < 1 || a.n > SIR_MAX_AGE || a.T < 1 || !pad_legal((size_t)a.S, a.S_pad)) return -4;
     const int rows = SIR_ENS_SERIES * a.T * (a.n + 1);  // sortable segments per scenario
     // K x S fits a 32-bit chain count (checked by the caller), so K x (blocks of samples) fits the grid's x dimension
     const int row_blocks = (rows + SIR_FIX_ROWS - 1) / SIR_FIX_ROWS;
@@ -775,13 +787,9 @@ int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
     }
     if (a.ev_after_metrics != nullptr && hipEventRecord(static_cast<hipEvent_t>(a.ev_after_metrics), st) != hipSuccess) return -3;
     // the series' quantiles: the segment sort and the interpolation of sepaihrd_ensemble_quantiles, per scenario (each has
-    // its own count of valid samples), with (T, n + 1) in the place of (Tp, n) and no seroprevalence / Rt block
-    const int threads = a.S_pad / 2 < 1024 ? a.S_pad / 2 : 1024;
-    const size_t lds = (size_t)a.S_pad * sizeof(double);
-    if (in_lds && lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return -3;
+    // its own count of valid samples), with (T, n + 1) in the place of (Tp, n) and no seroprevalence / Rt block; the LDS
+    // limit is raised once for all scenarios
+    if (raise_lds_limit(plan_of_pad((size_t)a.S_pad), reinterpret_cast<const void*>(&ensemble_quantile_kernel)) != 0) return -3;
     for (int k = 0; k < a.K; ++k) {
         EnsembleArgs e{};
         e.S = a.S; e.S_pad = a.S_pad; e.lpc = a.lpc; e.n = a.n + 1; e.T = a.T; e.Tp = a.T;
@@ -792,16 +800,8 @@ int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
         e.rt_segment0 = rows;
         hipLaunchKernelGGL(ensemble_count_valid_kernel, dim3(1), dim3(256), 0, st, a.status + (size_t)k * a.S, a.S, e.n_valid);
         if (a.q_out == nullptr) continue;
-        if (!in_lds) {
-            const int rc = sort_segments_global(e.vals, rows, a.S_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
-                const size_t work = (size_t)ng * a.n_probs;
-                hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, e, rows,
-                                   a.sort_scratch, first, ng);
-            });
-            if (rc != 0) return rc;
-        } else {
-            hipLaunchKernelGGL(ensemble_quantile_kernel, dim3(rows), dim3(threads), lds, st, e, rows);
-        }
+        const int rc = launch_segment_quantiles(e, rows, rows, a.sort_scratch, a.sort_scratch_doubles, st, /*lds_limit_raised=*/true);
+        if (rc != 0) return rc;  // a failed sort of scenario k ends the call at once
     }
     if (hipGetLastError() != hipSuccess) return -3;
     if (a.metrics == nullptr || (a.summary_out == nullptr && a.diff_out == nullptr)) return 0;
@@ -850,13 +850,15 @@ __global__ __launch_bounds__(64) void stoch_sir_summary_sorted_kernel(const Stoc
 
 int launch_stoch_sir_summaries(const StochSummaryArgs& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool in_lds = a.R_pad <= ENSEMBLE_MAX_SAMPLES;
     const size_t segments = (size_t)a.G * 3 * (size_t)a.chunk_steps;
-    if (a.G <= 0 || a.R <= 0 || a.chunk_steps <= 0 || a.step0 < 0 || a.step0 + a.chunk_steps > a.steps || a.R_pad < WAVE || a.R > a.R_pad ||
-        segments >= ((size_t)1 << 31) || (in_lds ? (a.R_pad & (a.R_pad - 1)) != 0 : a.R_pad % WAVE != 0))
+    if (a.G <= 0 || a.R <= 0 || a.chunk_steps <= 0 || a.step0 < 0 || a.step0 + a.chunk_steps > a.steps || segments >= ((size_t)1 << 31) ||
+        !pad_legal((size_t)a.R, a.R_pad))
         return -4;
-    if (!in_lds)
-        return sort_segments_global(a.vals, (int)segments, a.R_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
+    return sort_segments_and_pick(
+        plan_of_pad((size_t)a.R_pad), (int)segments, a.vals, a.sort_scratch, a.sort_scratch_doubles, st,
+        reinterpret_cast<const void*>(&stoch_sir_summary_kernel),
+        [&](int threads, size_t lds) { hipLaunchKernelGGL(stoch_sir_summary_kernel, dim3((unsigned)segments), dim3(threads), lds, st, a); },
+        [&](int first, int ng) {
             const bool timed = a.summary_ms != nullptr && a.ev[0] != nullptr && a.ev[1] != nullptr;
             if (timed) (void)hipEventRecord(static_cast<hipEvent_t>(a.ev[0]), st);
             hipLaunchKernelGGL(stoch_sir_summary_sorted_kernel, dim3((unsigned)(((size_t)ng * 4 + 63) / 64)), dim3(64), 0, st, a,
@@ -869,14 +871,6 @@ int launch_stoch_sir_summaries(const StochSummaryArgs& a, void* stream) {
                     *a.summary_ms += (double)ms;
             }
         });
-    const int threads = a.R_pad / 2 < 1024 ? a.R_pad / 2 : 1024;
-    const size_t lds = (size_t)a.R_pad * sizeof(double);
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&stoch_sir_summary_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return -3;
-    hipLaunchKernelGGL(stoch_sir_summary_kernel, dim3((unsigned)segments), dim3(threads), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace sepaihrd
@@ -888,31 +882,15 @@ namespace sepaihrd {
 
 int launch_predictive_quantiles(const PredictiveArgs& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool in_lds = a.N_pad <= ENSEMBLE_MAX_SAMPLES;
     const size_t segments = (size_t)6 * a.Tp * a.n;
-    if (a.S <= 0 || a.R <= 0 || a.N_pad < WAVE || (size_t)a.S * a.R > (size_t)a.N_pad || segments >= ((size_t)1 << 31) ||
-        (in_lds ? (a.N_pad & (a.N_pad - 1)) != 0 : a.N_pad % WAVE != 0))
-        return -4;
+    if (a.S <= 0 || a.R <= 0 || segments >= ((size_t)1 << 31) || !pad_legal((size_t)a.S * a.R, a.N_pad)) return -4;
     EnsembleArgs e{};
     e.S = a.S * a.R; e.S_pad = a.N_pad; e.lpc = a.lpc; e.n = a.n; e.T = a.T; e.Tp = a.Tp;
     e.n_probs = a.n_probs; e.probs = a.probs;
     e.vals = a.vals; e.q_out = a.q_out;
     e.n_valid = a.counts + 1;
     e.rt_segment0 = (int)segments;
-    if (!in_lds)
-        return sort_segments_global(a.vals, (int)segments, a.N_pad, a.sort_scratch, a.sort_scratch_doubles, st, [&](int first, int ng) {
-            const size_t work = (size_t)ng * a.n_probs;
-            hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, e, (int)segments,
-                               a.sort_scratch, first, ng);
-        });
-    const int threads = a.N_pad / 2 < 1024 ? a.N_pad / 2 : 1024;
-    const size_t lds = (size_t)a.N_pad * sizeof(double);
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return -3;
-    hipLaunchKernelGGL(ensemble_quantile_kernel, dim3((unsigned)segments), dim3(threads), lds, st, e, (int)segments);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_segment_quantiles(e, (int)segments, (int)segments, a.sort_scratch, a.sort_scratch_doubles, st);
 }
 
 }  // namespace sepaihrd

@@ -24,7 +24,7 @@ struct PredictiveArgs {
     double* q_out;             // [6][n_probs][Tp][n] device
     double* pit_out;           // [3][Tp][n] device or null
     int32_t* counts;           // [2] device: valid samples, valid samples x R (the draws of a segment)
-    double* sort_scratch;      // as EnsembleArgs (N_pad > ENSEMBLE_MAX_SAMPLES)
+    double* sort_scratch;      // as EnsembleArgs
     size_t sort_scratch_doubles;
 };
 // counts, the draws into vals / means / draws, and the mid-PIT of every usable observation (csrc/sepaihrd_predictive.hip)

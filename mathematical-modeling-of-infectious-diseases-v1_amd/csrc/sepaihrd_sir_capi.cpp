@@ -7,17 +7,24 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_host_util.h"
 #include "sepaihrd_mh_backend.h"
+#include "sepaihrd_segments.h"
 #include "sepaihrd_sir_device.h"
 
 using namespace sepaihrd;
+
+// the roles of the buffers sepaihrd_sir_scenario_ensemble keeps with its context
+enum EnsSlot {
+    SLOT_THETA, SLOT_VALS, SLOT_PROBS, SLOT_QUANTILES, SLOT_METRICS, SLOT_SCEN_VALS, SLOT_SCEN_SUMMARY, SLOT_SORT_SCRATCH, SLOT_INTS,
+    SLOT_COUNTS, SLOT_N_EVENTS, SLOT_EVENTS, SLOT_COUNT
+};
 
 struct sepaihrd_sir_ctx {
     int device = 0, solver = 0, arith = 0;
@@ -41,9 +48,7 @@ struct sepaihrd_sir_ctx {
     int no_pending = 0;  // this context has no begin / end evaluation a sampler could collide with
     // scratch of sepaihrd_sir_scenario_ensemble by role (grow-only, reused across calls), its phase events, the device time
     // of the last call and the number of calls that reached the device
-    static constexpr int ENS_BUFS = 12;
-    void* ens_buf[ENS_BUFS] = {};
-    size_t ens_cap[ENS_BUFS] = {};
+    GrowSlots<SLOT_COUNT> slots;
     hipEvent_t ens_ev[4] = {};
     double ens_ms[3] = {0.0, 0.0, 0.0};
     int64_t ens_calls = 0;
@@ -53,19 +58,6 @@ static_assert(sizeof(sepaihrd_sir_event) == sizeof(SirEvent) && SEPAIHRD_SIR_MAX
               "the kernels read the C ABI's event table in place");
 
 namespace {
-
-void set_err(char* err, int errlen, const std::string& msg) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
-}
-
-#define SIR_HIP_TRY(expr, ctx, fail)                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);   \
-            fail;                                                                    \
-        }                                                                            \
-    } while (0)
 
 template <class T>
 const T* upload(sepaihrd_sir_ctx* ctx, const std::vector<T>& v, bool& ok) {
@@ -94,16 +86,16 @@ int ensure_staging(sepaihrd_sir_ctx* c, size_t B, size_t traj_elems) {
         c->d_theta = c->d_loglik = nullptr;
         c->d_ints = nullptr;
         c->cap_B = 0;
-        SIR_HIP_TRY(hipMalloc((void**)&c->d_theta, B * c->P * sizeof(double)), c, return SEPAIHRD_E_HIP);
-        SIR_HIP_TRY(hipMalloc((void**)&c->d_loglik, B * sizeof(double)), c, return SEPAIHRD_E_HIP);
-        SIR_HIP_TRY(hipMalloc((void**)&c->d_ints, 3 * B * sizeof(int32_t)), c, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipMalloc((void**)&c->d_theta, B * c->P * sizeof(double)), c, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipMalloc((void**)&c->d_loglik, B * sizeof(double)), c, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipMalloc((void**)&c->d_ints, 3 * B * sizeof(int32_t)), c, return SEPAIHRD_E_HIP);
         c->cap_B = B;
     }
     if (traj_elems > c->cap_traj) {
         if (c->d_traj) (void)hipFree(c->d_traj);
         c->d_traj = nullptr;
         c->cap_traj = 0;
-        SIR_HIP_TRY(hipMalloc((void**)&c->d_traj, traj_elems * sizeof(double)), c, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipMalloc((void**)&c->d_traj, traj_elems * sizeof(double)), c, return SEPAIHRD_E_HIP);
         c->cap_traj = traj_elems;
     }
     return SEPAIHRD_OK;
@@ -215,8 +207,7 @@ void sepaihrd_sir_destroy(sepaihrd_sir_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     free_staging(ctx);
-    for (void* p : ctx->ens_buf)
-        if (p) (void)hipFree(p);
+    ctx->slots.release();
     for (hipEvent_t e : ctx->ens_ev)
         if (e) (void)hipEventDestroy(e);
     for (void* p : ctx->allocs) (void)hipFree(p);
@@ -233,7 +224,7 @@ int sepaihrd_sir_set_arith(sepaihrd_sir_ctx* ctx, int arith) {
 
 int sepaihrd_sir_reserve(sepaihrd_sir_ctx* ctx, int max_B) {
     if (!ctx || max_B < 0) return SEPAIHRD_E_INVALID_ARG;
-    SIR_HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     return ensure_staging(ctx, (size_t)max_B, 0);
 }
 
@@ -263,7 +254,7 @@ int sepaihrd_sir_eval_batch(sepaihrd_sir_ctx* ctx, const double* theta, int B, d
         return SEPAIHRD_E_INVALID_ARG;
     }
     if (B == 0) return SEPAIHRD_OK;
-    SIR_HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     const size_t nB = (size_t)B;
     const size_t traj_elems = traj ? nB * ctx->T * SIR_COMP * ctx->n : 0;
     {
@@ -273,16 +264,16 @@ int sepaihrd_sir_eval_batch(sepaihrd_sir_ctx* ctx, const double* theta, int B, d
     int32_t* d_status = ctx->d_ints;
     int32_t* d_nacc = ctx->d_ints + ctx->cap_B;
     int32_t* d_nrej = ctx->d_ints + 2 * ctx->cap_B;
-    SIR_HIP_TRY(hipMemcpy(ctx->d_theta, theta, nB * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(ctx->d_theta, theta, nB * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     const int rc = sepaihrd_sir_eval_batch_device(ctx, ctx->d_theta, B, ctx->d_loglik, d_status, d_nacc, d_nrej,
                                                   traj ? ctx->d_traj : nullptr, nullptr);
     if (rc != SEPAIHRD_OK) return rc;
-    SIR_HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
-    SIR_HIP_TRY(hipMemcpy(loglik, ctx->d_loglik, nB * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
-    if (status) SIR_HIP_TRY(hipMemcpy(status, d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
-    if (n_accept) SIR_HIP_TRY(hipMemcpy(n_accept, d_nacc, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
-    if (n_reject) SIR_HIP_TRY(hipMemcpy(n_reject, d_nrej, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
-    if (traj) SIR_HIP_TRY(hipMemcpy(traj, ctx->d_traj, traj_elems * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(loglik, ctx->d_loglik, nB * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (status) HIP_TRY(hipMemcpy(status, d_status, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (n_accept) HIP_TRY(hipMemcpy(n_accept, d_nacc, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (n_reject) HIP_TRY(hipMemcpy(n_reject, d_nrej, nB * sizeof(int32_t), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    if (traj) HIP_TRY(hipMemcpy(traj, ctx->d_traj, traj_elems * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 
@@ -355,32 +346,22 @@ int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx* ctx, const double* theta, i
                                    double* metric_summary, double* diff_quantiles, int32_t* status, int32_t* n_accept, int32_t* n_reject,
                                    int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    if (S <= 0 || K <= 0 || !theta || !n_events || !probs || n_probs <= 0 || n_probs > 1024) {
-        ctx->last_error = "sir_scenario_ensemble: need S > 0, K > 0, theta, n_events and probs (1..1024)";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    for (int p = 0; p < n_probs; ++p)
-        if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) {
-            ctx->last_error = "sir_scenario_ensemble: probabilities must lie in [0, 1]";
-            return SEPAIHRD_E_INVALID_ARG;
-        }
+    auto refuse = [&](const std::string& msg, int rc) { ctx->last_error = "sir_scenario_ensemble: " + msg; return rc; };
+    if (S <= 0 || K <= 0 || !theta || !n_events || !probs || n_probs <= 0 || n_probs > 1024)
+        return refuse("need S > 0, K > 0, theta, n_events and probs (1..1024)", SEPAIHRD_E_INVALID_ARG);
+    if (!probabilities_valid(probs, n_probs)) return refuse("probabilities must lie in [0, 1]", SEPAIHRD_E_INVALID_ARG);
     {
         char msg[256] = "";
-        if (sepaihrd_sir_validate_events(events, n_events, K, ctx->T, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-            ctx->last_error = std::string("sir_scenario_ensemble: ") + msg;
-            return SEPAIHRD_E_INVALID_ARG;
-        }
+        if (sepaihrd_sir_validate_events(events, n_events, K, ctx->T, msg, (int)sizeof(msg)) != SEPAIHRD_OK)
+            return refuse(msg, SEPAIHRD_E_INVALID_ARG);
     }
     const SirDevProblem& dp = ctx->dp;
     const size_t B = (size_t)K * (size_t)S;
-    if (B > (size_t)std::numeric_limits<int32_t>::max() / 2) {
-        ctx->last_error = "sir_scenario_ensemble: K x S chains exceed one launch (a 32-bit chain count)";
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    int S_pad = WAVE;
-    while (S_pad < S && S_pad < ENSEMBLE_MAX_SAMPLES) S_pad <<= 1;
-    const bool big = S > ENSEMBLE_MAX_SAMPLES;  // segments sorted in global memory instead of LDS
-    if (big) S_pad = (S + WAVE - 1) / WAVE * WAVE;
+    if (B > (size_t)std::numeric_limits<int32_t>::max() / 2)
+        return refuse("K x S chains exceed one launch (a 32-bit chain count)", SEPAIHRD_E_INVALID_ARG);
+    // sizes
+    const SegmentPlan plan = plan_segments((size_t)S);  // a segment: the S samples of one (scenario, series, time, column)
+    const int S_pad = (int)plan.pad;
     const int n = dp.n, T = dp.T, W = SIR_ENS_SCALARS + 2 * n;
     const size_t P = (size_t)ctx->P;
     const size_t n_rows = (size_t)SIR_ENS_SERIES * T * (n + 1);  // sortable segments per scenario
@@ -388,67 +369,52 @@ int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx* ctx, const double* theta, i
     const size_t n_q = (size_t)K * SIR_ENS_SERIES * n_probs * T * (n + 1);
     const size_t n_metrics = B * W, n_svals = (size_t)2 * K * W * S_pad;
     const size_t n_summary = (size_t)K * W * (2 + n_probs), n_diff = (size_t)K * W * n_probs;
-    const size_t n_scratch =
-        big ? std::max<size_t>((size_t)S_pad, std::min<size_t>(std::max(n_rows * S_pad, n_svals), (size_t)1 << 28) / S_pad * S_pad) : 0;
+    const size_t n_scratch = sort_scratch_doubles(plan, std::max(n_rows * S_pad, n_svals));
     const size_t n_evbytes = (size_t)K * SEPAIHRD_SIR_MAX_EVENTS * sizeof(sepaihrd_sir_event);
-    SIR_HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     // K x S within one launch: the buffers below must fit the device's memory (the stored series dominate: K 3 T (n + 1)
     // S_pad doubles); larger requests are refused before anything is allocated
     const size_t need_bytes = sizeof(double) * (B * P + n_vals + n_q + n_metrics + (size_t)S + n_svals + n_summary + n_diff + n_scratch + (size_t)n_probs) +
                               sizeof(int32_t) * (3 * B + 4 * (size_t)K) + n_evbytes;
-    size_t device_bytes = 0;
-    SIR_HIP_TRY(hipDeviceTotalMem(&device_bytes, ctx->device), ctx, return SEPAIHRD_E_HIP);
-    if (need_bytes > device_bytes) {
-        ctx->last_error = "sir_scenario_ensemble: K x S = " + std::to_string(B) + " runs need " + std::to_string(need_bytes >> 20) +
-                          " MiB of device memory, the device has " + std::to_string(device_bytes >> 20) +
-                          " MiB: split the scenarios or the samples over several calls";
-        return SEPAIHRD_E_INVALID_ARG;
+    {
+        const int rc = require_device_memory(ctx, need_bytes, "sir_scenario_ensemble: K x S = " + std::to_string(B) + " runs need",
+                                             "split the scenarios or the samples over several calls");
+        if (rc != SEPAIHRD_OK) return rc;
     }
-    auto dalloc = [&](int k, auto** p, size_t bytes_wanted) {
-        const size_t bytes = std::max<size_t>(bytes_wanted, 8);
-        if (ctx->ens_cap[k] < bytes) {
-            if (ctx->ens_buf[k]) (void)hipFree(ctx->ens_buf[k]);
-            ctx->ens_buf[k] = nullptr;
-            ctx->ens_cap[k] = 0;
-            if (hipMalloc(&ctx->ens_buf[k], bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-            ctx->ens_cap[k] = bytes;
-        }
-        *p = static_cast<std::remove_reference_t<decltype(*p)>>(ctx->ens_buf[k]);
-        return true;
-    };
+    // buffers
+    auto& slots = ctx->slots;
     double *d_theta = nullptr, *d_vals = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_metrics = nullptr, *d_svals = nullptr,
            *d_summary = nullptr, *d_scratch = nullptr;
     int32_t *d_ints = nullptr, *d_counts = nullptr, *d_nev = nullptr;
     SirEvent* d_events = nullptr;
-    if (!dalloc(0, &d_theta, B * P * sizeof(double)) || !dalloc(1, &d_vals, n_vals * sizeof(double)) ||
-        !dalloc(2, &d_probs, (size_t)n_probs * sizeof(double)) || !dalloc(3, &d_q, n_q * sizeof(double)) ||
-        !dalloc(4, &d_metrics, (n_metrics + (size_t)S) * sizeof(double)) || !dalloc(5, &d_svals, n_svals * sizeof(double)) ||
-        !dalloc(6, &d_summary, (n_summary + n_diff) * sizeof(double)) || !dalloc(7, &d_scratch, n_scratch * sizeof(double)) ||
-        !dalloc(8, &d_ints, 3 * B * sizeof(int32_t)) || !dalloc(9, &d_counts, (size_t)3 * K * sizeof(int32_t)) ||
-        !dalloc(10, &d_nev, (size_t)K * sizeof(int32_t)) || !dalloc(11, &d_events, n_evbytes)) {
-        ctx->last_error = "sir_scenario_ensemble: device allocation failed";
-        return SEPAIHRD_E_HIP;
-    }
+    if (!slots.get(SLOT_THETA, &d_theta, B * P) || !slots.get(SLOT_VALS, &d_vals, n_vals) ||
+        !slots.get(SLOT_PROBS, &d_probs, (size_t)n_probs) || !slots.get(SLOT_QUANTILES, &d_q, n_q) ||
+        !slots.get(SLOT_METRICS, &d_metrics, n_metrics + (size_t)S) || !slots.get(SLOT_SCEN_VALS, &d_svals, n_svals) ||
+        !slots.get(SLOT_SCEN_SUMMARY, &d_summary, n_summary + n_diff) || !slots.get(SLOT_SORT_SCRATCH, &d_scratch, n_scratch) ||
+        !slots.get(SLOT_INTS, &d_ints, 3 * B) || !slots.get(SLOT_COUNTS, &d_counts, (size_t)3 * K) ||
+        !slots.get(SLOT_N_EVENTS, &d_nev, (size_t)K) || !slots.get(SLOT_EVENTS, &d_events, (size_t)K * SEPAIHRD_SIR_MAX_EVENTS))
+        return refuse("device allocation failed", SEPAIHRD_E_HIP);
     for (hipEvent_t& e : ctx->ens_ev)
-        if (!e) SIR_HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
-    // every scenario integrates the same samples: theta replicated K times, chain c = scenario c / S, sample c % S
-    SIR_HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+        if (!e) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    // uploads.  Every scenario integrates the same samples: theta replicated K times, chain c = scenario c / S, sample c % S
+    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     for (int k = 1; k < K; ++k)
-        SIR_HIP_TRY(hipMemcpy(d_theta + (size_t)k * S * P, d_theta, (size_t)S * P * sizeof(double), hipMemcpyDeviceToDevice), ctx,
+        HIP_TRY(hipMemcpy(d_theta + (size_t)k * S * P, d_theta, (size_t)S * P * sizeof(double), hipMemcpyDeviceToDevice), ctx,
                     return SEPAIHRD_E_HIP);
     {
         std::vector<sepaihrd_sir_event> tab((size_t)K * SEPAIHRD_SIR_MAX_EVENTS, sepaihrd_sir_event{0, 0, 0.0});
         for (int k = 0; k < K; ++k)
             for (int e = 0; e < n_events[k]; ++e) tab[(size_t)k * SEPAIHRD_SIR_MAX_EVENTS + e] = events[(size_t)k * SEPAIHRD_SIR_MAX_EVENTS + e];
-        SIR_HIP_TRY(hipMemcpy(d_events, tab.data(), n_evbytes, hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipMemcpy(d_events, tab.data(), n_evbytes, hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     }
-    SIR_HIP_TRY(hipMemcpy(d_nev, n_events, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
-    SIR_HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_nev, n_events, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
     ++ctx->ens_calls;
     int32_t* d_status = d_ints;
     int32_t* d_nacc = d_ints + B;
     int32_t* d_nrej = d_ints + 2 * B;
-    SIR_HIP_TRY(hipEventRecord(ctx->ens_ev[0], nullptr), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipEventRecord(ctx->ens_ev[0], nullptr), ctx, return SEPAIHRD_E_HIP);
     const SirOutputs out{nullptr, d_status, d_nacc, d_nrej, nullptr};
     const SirEnsArgs ens{S, S_pad, d_events, d_nev, d_vals};
     int rc = ctx->arith == SEPAIHRD_ARITH_FMA ? launch_sir_ens_fma(dp, ctx->solver, d_theta, (int)B, out, ens, nullptr)
@@ -457,7 +423,7 @@ int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx* ctx, const double* theta, i
         ctx->last_error = rc == -4 ? "unsupported lanes-per-chain or solver" : "kernel launch failed";
         return rc == -4 ? SEPAIHRD_E_UNSUPPORTED : SEPAIHRD_E_HIP;
     }
-    SIR_HIP_TRY(hipEventRecord(ctx->ens_ev[1], nullptr), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipEventRecord(ctx->ens_ev[1], nullptr), ctx, return SEPAIHRD_E_HIP);
     SirEnsSummaryArgs a{};
     a.K = K; a.S = S; a.S_pad = S_pad; a.n = n; a.lpc = dp.lpc; a.T = T; a.P = ctx->P; a.n_probs = n_probs;
     a.pb = &ctx->dp; a.theta = d_theta; a.status = d_status; a.vals = d_vals; a.probs = d_probs;
@@ -469,36 +435,28 @@ int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx* ctx, const double* theta, i
     a.svals = d_svals; a.counts = d_counts;
     a.summary_out = want_summaries ? d_summary : nullptr;
     a.diff_out = want_summaries ? d_summary + n_summary : nullptr;
-    a.sort_scratch = big ? d_scratch : nullptr;
+    a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
     a.ev_after_metrics = ctx->ens_ev[2];
     rc = launch_sir_ensemble_summaries(a, nullptr);
-    if (rc != 0) {
-        ctx->last_error = "sir_scenario_ensemble: summary launch failed";
-        return SEPAIHRD_E_HIP;
-    }
-    SIR_HIP_TRY(hipEventRecord(ctx->ens_ev[3], nullptr), ctx, return SEPAIHRD_E_HIP);
-    SIR_HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    if (rc != 0) return refuse("summary launch failed", SEPAIHRD_E_HIP);
+    HIP_TRY(hipEventRecord(ctx->ens_ev[3], nullptr), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
     for (int i = 0; i < 3; ++i) {
         float ms = 0.0f;
         ctx->ens_ms[i] = hipEventElapsedTime(&ms, ctx->ens_ev[i], ctx->ens_ev[i + 1]) == hipSuccess ? (double)ms : -1.0;
     }
-    bool ok = true;
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        if (ok && dst && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) ok = false;
-    };
-    fetch(quantiles, d_q, n_q * sizeof(double));
-    fetch(metrics, d_metrics, n_metrics * sizeof(double));
-    fetch(metric_summary, d_summary, n_summary * sizeof(double));
-    fetch(diff_quantiles, d_summary + n_summary, n_diff * sizeof(double));
-    fetch(status, d_status, B * sizeof(int32_t));
-    fetch(n_accept, d_nacc, B * sizeof(int32_t));
-    fetch(n_reject, d_nrej, B * sizeof(int32_t));
-    fetch(n_valid, d_counts + 2 * K, (size_t)K * sizeof(int32_t));
-    if (!ok) {
-        ctx->last_error = "sir_scenario_ensemble: copy of the results failed";
-        return SEPAIHRD_E_HIP;
-    }
+    // fetches
+    ResultFetch res;
+    res.fetch(quantiles, d_q, n_q * sizeof(double));
+    res.fetch(metrics, d_metrics, n_metrics * sizeof(double));
+    res.fetch(metric_summary, d_summary, n_summary * sizeof(double));
+    res.fetch(diff_quantiles, d_summary + n_summary, n_diff * sizeof(double));
+    res.fetch(status, d_status, B * sizeof(int32_t));
+    res.fetch(n_accept, d_nacc, B * sizeof(int32_t));
+    res.fetch(n_reject, d_nrej, B * sizeof(int32_t));
+    res.fetch(n_valid, d_counts + 2 * K, (size_t)K * sizeof(int32_t));
+    if (!res.ok()) return refuse("copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 

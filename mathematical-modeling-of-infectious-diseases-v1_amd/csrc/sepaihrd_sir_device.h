@@ -86,7 +86,7 @@ struct SirEnsSummaryArgs {
     int32_t* counts;           // [2 K]
     double* summary_out;       // [K][W][2 + n_probs]
     double* diff_out;          // [K][W][n_probs]
-    double* sort_scratch;      // S_pad > ENSEMBLE_MAX_SAMPLES
+    double* sort_scratch;      // as EnsembleArgs
     size_t sort_scratch_doubles;
     void* ev_after_metrics;    // optional hipEvent_t recorded between the fix-up / metric passes and the sorts
 };

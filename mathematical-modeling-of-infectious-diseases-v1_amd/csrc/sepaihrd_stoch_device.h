@@ -7,8 +7,8 @@
 namespace sepaihrd {
 
 // One chunk of the time axis: vals [segments][R_pad], segment = (group 3 + compartment) chunk_steps + local step, the
-// replicates first and +inf after them.  R_pad: a power of two >= 64 up to ENSEMBLE_MAX_SAMPLES (sorted in LDS), a multiple
-// of 64 beyond (sorted into sort_scratch by the segmented radix sort).
+// replicates first and +inf after them.  R_pad: plan_segments(R).pad (csrc/sepaihrd_segments.h); beyond the LDS sort the
+// segments are sorted into sort_scratch by the segmented radix sort.
 struct StochSummaryArgs {
     int G, R, R_pad;
     int chunk_steps, step0, steps;  // this chunk's rows are step0 .. step0 + chunk_steps - 1 of `steps`

@@ -6,12 +6,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_hip.h"
+#include "sepaihrd_host_util.h"
+#include "sepaihrd_segments.h"
 #include "sepaihrd_stoch.inc"
 #include "sepaihrd_stoch_device.h"
 
@@ -85,10 +86,6 @@ __global__ __launch_bounds__(STEP_BLOCK) void stoch_binomial_probe_kernel(uint64
     out[i] = sepaihrd_stoch::binomial(c, n[i], p[i]);
 }
 
-void set_err(char* err, int errlen, const std::string& msg) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
-}
-
 int select_device(int device, char* err, int errlen) {
     int ndev = 0;
     const hipError_t e = hipGetDeviceCount(&ndev);
@@ -101,33 +98,6 @@ int select_device(int device, char* err, int errlen) {
     if (device >= ndev) { set_err(err, errlen, "device index out of range"); return SEPAIHRD_E_INVALID_ARG; }
     if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return SEPAIHRD_E_HIP; }
     return SEPAIHRD_OK;
-}
-
-// device buffers and events of one call, released however it ends
-struct Scratch {
-    std::vector<void*> bufs;
-    hipEvent_t ev[5] = {};
-    hipStream_t stream = nullptr;
-    ~Scratch() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        for (void* b : bufs) if (b) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-    template <class T>
-    bool alloc(T** p, size_t count) {
-        void* q = nullptr;
-        if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        bufs.push_back(q);
-        *p = static_cast<T*>(q);
-        return true;
-    }
-};
-
-int pad_replicates(int R) {
-    if (R > ENSEMBLE_MAX_SAMPLES) return (R + WAVE - 1) / WAVE * WAVE;
-    int p = WAVE;
-    while (p < R) p <<= 1;
-    return p;
 }
 
 }  // namespace
@@ -179,8 +149,9 @@ int sepaihrd_stoch_sir_run(int device, const sepaihrd_stoch_sir_config* cfg, con
     if (cfg->keep > 0 && !traj) { set_err(err, errlen, "stoch_sir: keep > 0 needs traj"); return SEPAIHRD_E_INVALID_ARG; }
     const int G = cfg->n_groups, R = cfg->n_replicates, keep = traj ? cfg->keep : 0;
     const int steps = (int)sepaihrd_stoch_sir_num_steps(cfg->t_start, cfg->t_end, cfg->h);
-    const int R_pad = pad_replicates(R);
-    const bool in_lds = R_pad <= ENSEMBLE_MAX_SAMPLES;
+    const SegmentPlan plan = plan_segments((size_t)R);  // a segment: the R replicates of one (group, compartment, step)
+    const int R_pad = (int)plan.pad;
+    const bool in_lds = plan.in_lds;
     // a step of the chunk: G x 3 rows of R_pad doubles, and as much again of sort scratch beyond the LDS sort
     const uint64_t budget = cfg->max_workspace_bytes ? cfg->max_workspace_bytes : SEPAIHRD_STOCH_SIR_DEFAULT_WORKSPACE;
     const uint64_t step_bytes = (uint64_t)G * 3 * (uint64_t)R_pad * sizeof(double) * (in_lds ? 1 : 2);
@@ -194,7 +165,7 @@ int sepaihrd_stoch_sir_run(int device, const sepaihrd_stoch_sir_config* cfg, con
 
     const int drc = select_device(device, err, errlen);
     if (drc != SEPAIHRD_OK) return drc;
-    Scratch sc;
+    CallScratch sc(5);
     auto hip_fail = [&](const char* what) {
         set_err(err, errlen, std::string("stoch_sir: ") + what + ": " + hipGetErrorString(hipGetLastError()));
         return SEPAIHRD_E_HIP;
@@ -285,7 +256,7 @@ int sepaihrd_stoch_sir_binomial_device(int device, uint64_t seed, const int32_t*
         if (n[i] < 0 || std::isnan(p[i])) { set_err(err, errlen, "stoch_sir_binomial_device: n must be >= 0 and p a number"); return SEPAIHRD_E_INVALID_ARG; }
     const int drc = select_device(device, err, errlen);
     if (drc != SEPAIHRD_OK) return drc;
-    Scratch sc;
+    CallScratch sc;
     int32_t *d_n = nullptr, *d_out = nullptr;
     double* d_p = nullptr;
     if (!sc.alloc(&d_n, (size_t)count) || !sc.alloc(&d_out, (size_t)count) || !sc.alloc(&d_p, (size_t)count)) {
