@@ -54,9 +54,91 @@ Eigen::VectorXd vec(const double* p, int n) {
     for (int i = 0; i < n; ++i) v[i] = p ? p[i] : 0.0;
     return v;
 }
+// the model parameters and the observation tables a sepaihrd_problem carries
+SEPAIHRDParameters model_parameters(const sepaihrd_problem* pb) {
+    const int n = pb->n_age;
+    SEPAIHRDParameters mp;
+    mp.N = vec(pb->N, n);
+    mp.M_baseline = Eigen::MatrixXd(n, n);
+    std::memcpy(mp.M_baseline.data(), pb->M, sizeof(double) * n * n);
+    mp.a = vec(pb->a, n); mp.h_infec = vec(pb->h_infec, n); mp.p = vec(pb->p, n); mp.h = vec(pb->h, n);
+    mp.icu = vec(pb->icu, n); mp.d_H = vec(pb->d_H, n); mp.d_ICU = vec(pb->d_ICU, n);
+    mp.d_community = vec(pb->d_community, n);
+    mp.beta = pb->beta; mp.theta = pb->theta; mp.sigma = pb->sigma; mp.gamma_p = pb->gamma_p;
+    mp.gamma_A = pb->gamma_A; mp.gamma_I = pb->gamma_I; mp.gamma_H = pb->gamma_H; mp.gamma_ICU = pb->gamma_ICU;
+    mp.beta_end_times.assign(pb->beta_end_times, pb->beta_end_times + pb->n_beta);
+    mp.beta_values.assign(pb->beta_values, pb->beta_values + pb->n_beta);
+    mp.kappa_end_times.assign(pb->kappa_end_times, pb->kappa_end_times + pb->n_kappa);
+    mp.kappa_values.assign(pb->kappa_values, pb->kappa_values + pb->n_kappa);
+    mp.E0_multiplier = pb->multipliers[0]; mp.P0_multiplier = pb->multipliers[1];
+    mp.A0_multiplier = pb->multipliers[2]; mp.I0_multiplier = pb->multipliers[3];
+    mp.H0_multiplier = pb->multipliers[4]; mp.ICU0_multiplier = pb->multipliers[5];
+    mp.R0_multiplier = pb->multipliers[6]; mp.D0_multiplier = pb->multipliers[7];
+    mp.runup_days = pb->runup_days; mp.seed_exposed = pb->seed_exposed;
+    return mp;
+}
+CalibrationData calibration_data(const sepaihrd_problem* pb, const Eigen::VectorXd& N) {
+    const int n = pb->n_age;
+    auto mat = [&](const double* src) {
+        Eigen::MatrixXd m(pb->n_obs, n);
+        for (int r = 0; r < pb->n_obs; ++r)
+            for (int c = 0; c < n; ++c) m(r, c) = src[static_cast<size_t>(r) * n + c];
+        return m;
+    };
+    return CalibrationData(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), N);
+}
 thread_local std::string g_error;
 thread_local double g_last_mh_loop_seconds = 0.0;
 thread_local double g_last_diag_seconds = 0.0;
+
+// The error guard of the entry points: 0 after body(); a std::exception leaves its message for host_last_error and gives 1.
+template <class Body>
+int guarded(Body&& body) {
+    try {
+        body();
+        return 0;
+    } catch (const std::exception& e) {
+        g_error = e.what();
+        return 1;
+    }
+}
+
+// samples [n][P] as the vectors the posterior classes take
+std::vector<Eigen::VectorXd> sample_vectors(const double* samples, int n, size_t P) {
+    std::vector<Eigen::VectorXd> ps;
+    for (int s = 0; s < n; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+    return ps;
+}
+// HipPosteriorEnsemble / HipPosteriorPredictive over the handle's parameter manager and data, on the problem's grid, solver and arithmetic
+template <class Posterior>
+Posterior posterior_over(const HostHandle& h, const sepaihrd_problem* pb, int device) {
+    return Posterior(*h.pm, *h.data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * pb->n_age),
+                     strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
+}
+// an aggregate {time -> {quantile name -> value}} as out [5: q025, q05, median, q95, q975][T]; NaN where a time is missing
+void put_quantile_rows(const std::map<double, AggregatedStats>& agg, const std::vector<double>& times, double* out) {
+    const char* keys[5] = {"q025", "q05", "median", "q95", "q975"};
+    size_t k = 0;
+    for (double t : times) {
+        const auto it = agg.find(t);
+        for (int q = 0; q < 5; ++q)
+            out[static_cast<size_t>(q) * times.size() + k] = it == agg.end() ? std::numeric_limits<double>::quiet_NaN() : it->second.at(keys[q]);
+        ++k;
+    }
+}
+// the parameter manager in another constraint mode (1: MCMC_REFLECT, else OPTIMIZATION_CLAMP) until the end of the scope
+class ConstraintModeScope {
+public:
+    ConstraintModeScope(HipSEPAIHRDParameterManager& pm, int mode) : pm_(pm), keep_(pm.getConstraintMode()) {
+        pm_.setConstraintMode(mode == 1 ? ConstraintMode::MCMC_REFLECT : ConstraintMode::OPTIMIZATION_CLAMP);
+    }
+    ~ConstraintModeScope() { pm_.setConstraintMode(keep_); }
+    ConstraintModeScope(const ConstraintModeScope&) = delete;
+    ConstraintModeScope& operator=(const ConstraintModeScope&) = delete;
+private:
+    HipSEPAIHRDParameterManager& pm_;
+    ConstraintMode keep_;
+};
 
 // ---- lock-step No-U-Turn chains (MultiChainNUTSSampler): output plumbing shared by the device run and the analytic hook
 struct NutsChainsOut {
@@ -93,6 +175,82 @@ std::vector<std::vector<double>> chain_starts(const double* theta0, int C, int P
     std::vector<std::vector<double>> starts(static_cast<size_t>(C));
     for (int c = 0; c < C; ++c) starts[static_cast<size_t>(c)].assign(theta0 + static_cast<size_t>(c) * P, theta0 + static_cast<size_t>(c + 1) * P);
     return starts;
+}
+
+// ---- Metropolis-Hastings chains (MultiChainMetropolisHastings): what every entry point that runs them shares
+// The settings every run starts from; `own` adds the entry point's keys.  Reporting is the reference's three keys, on
+// (progress lines every report_interval iterations, checkpoint and trace files) or off.  A key left out keeps the
+// default of a freshly constructed sampler.
+using MhSettings = std::map<std::string, double>;
+MhSettings mh_settings(int iterations, int burn_in, bool reported, int report_interval, std::initializer_list<MhSettings::value_type> own) {
+    MhSettings s{{"mcmc_iterations", double(iterations)}, {"burn_in", double(burn_in)}, {"report_interval", reported ? double(report_interval) : 0.0},
+                 {"write_checkpoints", reported ? 1.0 : 0.0}, {"write_trace", reported ? 1.0 : 0.0}};
+    s.insert(own);
+    return s;
+}
+// Per-chain outputs, chain-major; a NULL destination is skipped.  n_samples is the same for every chain.
+struct MhChainsOut {
+    int iterations, P;
+    int32_t* accepted;                  // [C]
+    double *best_value, *best, *final_scale;  // [C], [C][P], [C]
+    unsigned char* accept_trace;        // [C][iterations - 1]
+    int32_t* n_samples;                 // one count
+    double *samples, *sample_values, *final_cov;  // [C][n_samples][P], [C][n_samples], [C][P][P]
+    void put(int c, const OptimizationResult& r, const std::vector<unsigned char>* trace) const {
+        const size_t Pz = static_cast<size_t>(P), cz = static_cast<size_t>(c), ns = r.samples.size();
+        if (accepted) accepted[c] = static_cast<int32_t>(r.additionalStats.at("accepted_count"));
+        if (best_value) best_value[c] = r.bestObjectiveValue;
+        if (final_scale) final_scale[c] = r.additionalStats.at("final_scale");
+        if (best) for (size_t i = 0; i < Pz; ++i) best[cz * Pz + i] = r.bestParameters[static_cast<Eigen::Index>(i)];
+        if (accept_trace && trace) std::copy(trace->begin(), trace->end(), accept_trace + cz * static_cast<size_t>(iterations - 1));
+        if (n_samples) *n_samples = static_cast<int32_t>(ns);
+        for (size_t s = 0; s < ns; ++s) {
+            if (samples) for (size_t i = 0; i < Pz; ++i) samples[(cz * ns + s) * Pz + i] = r.samples[s][static_cast<Eigen::Index>(i)];
+            if (sample_values) sample_values[cz * ns + s] = r.sampleObjectiveValues[s];
+        }
+        if (final_cov)
+            for (size_t i = 0; i < Pz; ++i)
+                for (size_t j = 0; j < Pz; ++j)
+                    final_cov[(cz * Pz + i) * Pz + j] = r.finalCovariance(static_cast<Eigen::Index>(i), static_cast<Eigen::Index>(j));
+    }
+    // every chain of a lock-step run with the sampler's accept traces (looked at only when a trace is wanted: a run
+    // without keep_accept_traces has none)
+    void put(const std::vector<OptimizationResult>& res, const std::vector<std::vector<unsigned char>>& traces) const {
+        for (size_t c = 0; c < res.size(); ++c) put(static_cast<int>(c), res[c], accept_trace ? &traces[c] : nullptr);
+    }
+};
+// the scalar path: chain c alone through optimize() with seed + c
+void mh_scalar_chains(MultiChainMetropolisHastings& mh, int C, const double* initial, uint32_t seed, IObjectiveFunction& objective,
+                      IParameterManager& pm, const MhChainsOut& out) {
+    for (int c = 0; c < C; ++c) {
+        mh.setSeed(seed + static_cast<uint32_t>(c));
+        const OptimizationResult r = mh.optimize(vec(initial + static_cast<size_t>(c) * out.P, out.P), objective, pm);
+        out.put(c, r, out.accept_trace ? &mh.acceptTraces()[0] : nullptr);
+    }
+}
+// the progress lines of a reported run, one per line, into a file of their own (a NULL path leaves the sampler's sink alone)
+class ProgressLog {
+public:
+    ProgressLog(MultiChainMetropolisHastings& mh, const char* path) {
+        if (!path) return;
+        file_.open(path);
+        mh.setProgressSink([this](const std::string& level, const std::string& msg) { file_ << level << " " << msg << std::endl; });
+    }
+    ProgressLog(const ProgressLog&) = delete;
+    ProgressLog& operator=(const ProgressLog&) = delete;
+private:
+    std::ofstream file_;
+};
+// failures [3] of a device-resident run; a host-loop run counts none
+void put_failures(const std::vector<long>& counts, long* failures) {
+    if (failures)
+        for (size_t k = 0; k < 3; ++k) failures[k] = k < counts.size() ? counts[k] : 0;
+}
+// the objectives behind G handles, one device context each
+std::vector<HipSEPAIHRDObjectiveFunction*> group_objectives(void** handles, int G) {
+    std::vector<HipSEPAIHRDObjectiveFunction*> objs;
+    for (int g = 0; g < G; ++g) objs.push_back(static_cast<HostHandle*>(handles[g])->obj.get());
+    return objs;
 }
 
 // The device objective behind a stopwatch: wall time inside the batched evaluation and, when asked, the evaluation
@@ -228,25 +386,7 @@ void* host_objective_create(const sepaihrd_problem* pb, const char* names, const
                             const double* sigmas, int device, int cache_capacity, int with_objective) {
     try {
         const int n = pb->n_age;
-        SEPAIHRDParameters mp;
-        mp.N = vec(pb->N, n);
-        mp.M_baseline = Eigen::MatrixXd(n, n);
-        std::memcpy(mp.M_baseline.data(), pb->M, sizeof(double) * n * n);
-        mp.a = vec(pb->a, n); mp.h_infec = vec(pb->h_infec, n); mp.p = vec(pb->p, n); mp.h = vec(pb->h, n);
-        mp.icu = vec(pb->icu, n); mp.d_H = vec(pb->d_H, n); mp.d_ICU = vec(pb->d_ICU, n);
-        mp.d_community = vec(pb->d_community, n);
-        mp.beta = pb->beta; mp.theta = pb->theta; mp.sigma = pb->sigma; mp.gamma_p = pb->gamma_p;
-        mp.gamma_A = pb->gamma_A; mp.gamma_I = pb->gamma_I; mp.gamma_H = pb->gamma_H; mp.gamma_ICU = pb->gamma_ICU;
-        mp.beta_end_times.assign(pb->beta_end_times, pb->beta_end_times + pb->n_beta);
-        mp.beta_values.assign(pb->beta_values, pb->beta_values + pb->n_beta);
-        mp.kappa_end_times.assign(pb->kappa_end_times, pb->kappa_end_times + pb->n_kappa);
-        mp.kappa_values.assign(pb->kappa_values, pb->kappa_values + pb->n_kappa);
-        mp.E0_multiplier = pb->multipliers[0]; mp.P0_multiplier = pb->multipliers[1];
-        mp.A0_multiplier = pb->multipliers[2]; mp.I0_multiplier = pb->multipliers[3];
-        mp.H0_multiplier = pb->multipliers[4]; mp.ICU0_multiplier = pb->multipliers[5];
-        mp.R0_multiplier = pb->multipliers[6]; mp.D0_multiplier = pb->multipliers[7];
-        mp.runup_days = pb->runup_days; mp.seed_exposed = pb->seed_exposed;
-
+        const SEPAIHRDParameters mp = model_parameters(pb);
         const std::vector<std::string> nm = split_lines(names);
         std::map<std::string, double> sg;
         std::map<std::string, std::pair<double, double>> bd;
@@ -260,13 +400,7 @@ void* host_objective_create(const sepaihrd_problem* pb, const char* names, const
                                                                                    : ConstraintMode::OPTIMIZATION_CLAMP);
         h->cache = std::make_unique<SimulationCache>(static_cast<size_t>(cache_capacity > 0 ? cache_capacity : 1000));
         if (!with_objective) return h.release();
-        auto mat = [&](const double* src) {
-            Eigen::MatrixXd m(pb->n_obs, n);
-            for (int r = 0; r < pb->n_obs; ++r)
-                for (int c = 0; c < n; ++c) m(r, c) = src[static_cast<size_t>(r) * n + c];
-            return m;
-        };
-        h->data = std::make_unique<CalibrationData>(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), mp.N);
+        h->data = std::make_unique<CalibrationData>(calibration_data(pb, mp.N));
         const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         h->obj = std::make_unique<HipSEPAIHRDObjectiveFunction>(
             *h->pm, *h->cache, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times),
@@ -288,16 +422,11 @@ int host_ensemble(void* hv, const sepaihrd_problem* pb, int device, const double
                   int num_for_ppc, uint32_t seed, double* ppc, int32_t* selected, int32_t* n_selected,
                   int32_t* samples_used, int burn_in, int thinning, double* sero, double* rt) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int n = pb->n_age;
-        const size_t P = h->pm->getParameterCount();
-        const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         const std::vector<double> times(pb->times, pb->times + pb->n_times);
-        HipPosteriorEnsemble ens(*h->pm, *h->data, times, vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err,
-                                 device, pb->arith == SEPAIHRD_ARITH_FMA);
-        std::vector<Eigen::VectorXd> ps(static_cast<size_t>(n_samples), Eigen::VectorXd(static_cast<Eigen::Index>(P)));
-        for (int s = 0; s < n_samples; ++s)
-            for (size_t i = 0; i < P; ++i) ps[static_cast<size_t>(s)][static_cast<Eigen::Index>(i)] = samples[static_cast<size_t>(s) * P + i];
+        HipPosteriorEnsemble ens = posterior_over<HipPosteriorEnsemble>(*h, pb, device);
+        const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
         const std::vector<int> sel = HipPosteriorEnsemble::selectSamples(ps.size(), num_for_ppc, seed);
         for (size_t i = 0; i < sel.size(); ++i) selected[i] = sel[i];
         *n_selected = static_cast<int32_t>(sel.size());
@@ -316,35 +445,9 @@ int host_ensemble(void* hv, const sepaihrd_problem* pb, int device, const double
                         ppc[((static_cast<size_t>(ser) * 5 + q) * Tp + t) * n + a] =
                             (*m[q])(static_cast<Eigen::Index>(t), a);
         }
-        if (sero) {
-            const auto agg = ens.aggregateSeroprevalence(ps, burn_in, thinning);
-            const char* keys[5] = {"q025", "q05", "median", "q95", "q975"};
-            size_t k = 0;
-            for (double t : times) {
-                const auto it = agg.find(t);
-                for (int q = 0; q < 5; ++q)
-                    sero[static_cast<size_t>(q) * times.size() + k] =
-                        it == agg.end() ? std::numeric_limits<double>::quiet_NaN() : it->second.at(keys[q]);
-                ++k;
-            }
-        }
-        if (rt) {
-            const auto agg = ens.aggregateRt(ps, burn_in, thinning);
-            const char* keys[5] = {"q025", "q05", "median", "q95", "q975"};
-            size_t k = 0;
-            for (double t : times) {
-                const auto it = agg.find(t);
-                for (int q = 0; q < 5; ++q)
-                    rt[static_cast<size_t>(q) * times.size() + k] =
-                        it == agg.end() ? std::numeric_limits<double>::quiet_NaN() : it->second.at(keys[q]);
-                ++k;
-            }
-        }
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+        if (sero) put_quantile_rows(ens.aggregateSeroprevalence(ps, burn_in, thinning), times, sero);
+        if (rt) put_quantile_rows(ens.aggregateRt(ps, burn_in, thinning), times, rt);
+    });
 }
 
 // PostCalibrationAnalyser::generateFullReport step 4 as the reference runs it (PostCalibrationAnalyser.cpp:94-141,210-219): the
@@ -354,13 +457,12 @@ int host_ensemble(void* hv, const sepaihrd_problem* pb, int device, const double
 int host_scenario_comparison(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int burn_in,
                              int thinning, const char* path, double* metrics, double* kappa, int32_t* n_rows) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         *n_rows = 0;
-        if (n_samples <= 0 || burn_in >= n_samples || thinning <= 0) return 0;
+        if (n_samples <= 0 || burn_in >= n_samples || thinning <= 0) return;  // nothing selected: no rows, no file, no error
         const int n = pb->n_age;
         const size_t P = h->pm->getParameterCount();
-        HipPosteriorEnsemble ens(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
-                                 strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
+        HipPosteriorEnsemble ens = posterior_over<HipPosteriorEnsemble>(*h, pb, device);
         int last = burn_in;
         while (last + thinning < n_samples) last += thinning;
         const Eigen::VectorXd baseline = vec(samples + static_cast<size_t>(last) * P, static_cast<int>(P));
@@ -389,11 +491,7 @@ int host_scenario_comparison(void* hv, const sepaihrd_problem* pb, int device, c
                 }
         }
         *n_rows = static_cast<int32_t>(rows.size());
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // seroprevalence/ene_covid_validation.csv from the metric summary of samples burn_in, burn_in + thinning, ...
@@ -401,42 +499,26 @@ int host_scenario_comparison(void* hv, const sepaihrd_problem* pb, int device, c
 int host_ene_covid_validation(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int burn_in,
                               int thinning, const char* path) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
-        const int n = pb->n_age;
-        const size_t P = h->pm->getParameterCount();
-        HipPosteriorEnsemble ens(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
-                                 strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
-        std::vector<Eigen::VectorXd> ps;
-        for (int s = 0; s < n_samples; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+    return guarded([&] {
+        HipPosteriorEnsemble ens = posterior_over<HipPosteriorEnsemble>(*h, pb, device);
+        const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
         HipPosteriorEnsemble::writeEneCovidValidation(path, HipPosteriorEnsemble::aggregateMetrics(ens.calculateEssentialMetrics(ps, burn_in, thinning)));
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // returns 0 ok, 1 = exception thrown by calculate() (message in host_last_error)
 int host_objective_calculate(void* hv, const double* theta, double* value) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         *value = h->obj->calculate(vec(theta, static_cast<int>(h->pm->getParameterCount())));
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 int host_objective_calculate_batch(void* hv, const double* thetas, int B, double* out, int* status) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         h->obj->calculateBatch(thetas, B, out, status);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 void host_cache_stats(void* hv, long* calls, long* hits, long* size) {
@@ -448,12 +530,10 @@ void host_cache_stats(void* hv, long* calls, long* hits, long* size) {
 
 int host_apply_constraints(void* hv, int mode, const double* in, double* out) {
     auto* h = static_cast<HostHandle*>(hv);
-    const ConstraintMode keep = h->pm->getConstraintMode();
-    h->pm->setConstraintMode(mode == 1 ? ConstraintMode::MCMC_REFLECT : ConstraintMode::OPTIMIZATION_CLAMP);
+    const ConstraintModeScope in_mode(*h->pm, mode);
     const int P = static_cast<int>(h->pm->getParameterCount());
     const Eigen::VectorXd c = h->pm->applyConstraints(vec(in, P));
     for (int i = 0; i < P; ++i) out[i] = c[i];
-    h->pm->setConstraintMode(keep);
     return 0;
 }
 
@@ -473,62 +553,31 @@ int host_mh_run(void* hv, int C, const double* initial, uint32_t seed, int itera
                 unsigned char* accept_trace, int32_t* n_samples, double* samples, double* sample_values,
                 int two_pass_covariance, double* final_cov, int adaptation_window, int device_streams) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         MultiChainMetropolisHastings mh;
-        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
-                      {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                      {"regularization_epsilon", reg_eps}, {"target_acceptance_rate", target_acc},
-                      {"adapt_scale", double(adapt_scale)}, {"store_samples", 1.0},
-                      {"two_pass_covariance", double(two_pass_covariance)}, {"adaptation_window", double(adaptation_window)},
-                      {"device_streams", double(device_streams)}, {"keep_accept_traces", accept_trace ? 1.0 : 0.0},
-                      {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}});
+        mh.configure(mh_settings(iterations, burn_in, false, 0,
+                                 {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
+                                  {"regularization_epsilon", reg_eps}, {"target_acceptance_rate", target_acc},
+                                  {"adapt_scale", double(adapt_scale)}, {"store_samples", 1.0},
+                                  {"two_pass_covariance", double(two_pass_covariance)}, {"adaptation_window", double(adaptation_window)},
+                                  {"device_streams", double(device_streams)}, {"keep_accept_traces", accept_trace ? 1.0 : 0.0},
+                                  {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}}));
         h->last_diag = ChainDiagnosticsTable{};
+        const MhChainsOut out{iterations, P, accepted, best_value, best, final_scale, accept_trace, n_samples, samples, sample_values, final_cov};
+        if (use_scalar_interface == 1) {  // one chain at a time: no lock-step loop to time, no table of the chains
+            mh_scalar_chains(mh, C, initial, seed, *h->obj, *h->pm, out);
+            return;
+        }
         mh.setSeed(seed);
-        std::vector<OptimizationResult> res;
-        if (use_scalar_interface == 1) {
-            for (int c = 0; c < C; ++c) {
-                mh.setSeed(seed + static_cast<uint32_t>(c));
-                res.push_back(mh.optimize(vec(initial + static_cast<size_t>(c) * P, P), *h->obj, *h->pm));
-                if (accept_trace)
-                    std::copy(mh.acceptTraces()[0].begin(), mh.acceptTraces()[0].end(),
-                              accept_trace + static_cast<size_t>(c) * (iterations - 1));
-            }
-        } else {
-            const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
-            res = use_scalar_interface == 2 ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm)  // device-resident state
-                                            : mh.optimizeChains(init, C, *h->obj, *h->pm);
-            g_last_mh_loop_seconds = mh.lastLoopSeconds();
-            h->last_diag = mh.diagnostics();
-            g_last_diag_seconds = mh.lastDiagnosticsSeconds();
-            if (accept_trace)
-                for (int c = 0; c < C; ++c)
-                    std::copy(mh.acceptTraces()[static_cast<size_t>(c)].begin(), mh.acceptTraces()[static_cast<size_t>(c)].end(),
-                              accept_trace + static_cast<size_t>(c) * (iterations - 1));
-        }
-        const int ns = static_cast<int>(res[0].samples.size());
-        if (n_samples) *n_samples = ns;
-        for (int c = 0; c < C; ++c) {
-            const OptimizationResult& r = res[static_cast<size_t>(c)];
-            if (accepted) accepted[c] = static_cast<int32_t>(r.additionalStats.at("accepted_count"));
-            if (best_value) best_value[c] = r.bestObjectiveValue;
-            if (final_scale) final_scale[c] = r.additionalStats.at("final_scale");
-            if (best) for (int i = 0; i < P; ++i) best[static_cast<size_t>(c) * P + i] = r.bestParameters[i];
-            if (samples)
-                for (int s = 0; s < ns; ++s)
-                    for (int i = 0; i < P; ++i)
-                        samples[(static_cast<size_t>(c) * ns + s) * P + i] = r.samples[static_cast<size_t>(s)][i];
-            if (sample_values)
-                for (int s = 0; s < ns; ++s) sample_values[static_cast<size_t>(c) * ns + s] = r.sampleObjectiveValues[static_cast<size_t>(s)];
-            if (final_cov)
-                for (int i = 0; i < P; ++i)
-                    for (int j = 0; j < P; ++j) final_cov[(static_cast<size_t>(c) * P + i) * P + j] = r.finalCovariance(i, j);
-        }
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+        const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
+        out.put(use_scalar_interface == 2 ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm)  // device-resident state
+                                          : mh.optimizeChains(init, C, *h->obj, *h->pm),
+                mh.acceptTraces());
+        g_last_mh_loop_seconds = mh.lastLoopSeconds();
+        h->last_diag = mh.diagnostics();
+        g_last_diag_seconds = mh.lastDiagnosticsSeconds();
+    });
 }
 
 // BatchedHillClimbingOptimizer in the clamp mode ModelCalibrator sets for phase 1
@@ -538,7 +587,7 @@ int host_hc_run(void* hv, const double* x0, uint32_t seed, int threads, int iter
                 int use_scalar_interface, double* best, double* best_value, double* final_cov, double* trace,
                 long* evaluations, long* launches) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);
         BatchedHillClimbingOptimizer hc;
@@ -559,18 +608,14 @@ int host_hc_run(void* hv, const double* x0, uint32_t seed, int threads, int iter
         if (trace) std::copy(hc.currentTrace().begin(), hc.currentTrace().end(), trace);
         if (evaluations) *evaluations = hc.evaluations();
         if (launches) *launches = hc.launches();
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // BatchedParticleSwarmOptimization.  settings: n_settings (key, value) pairs, keys as in pso_settings.txt plus `seed`.
 int host_pso_run(void* hv, const double* x0, const char* const* keys, const double* values, int n_settings,
                  double* best, double* best_value, double* final_cov, double* trace, long* evaluations, long* launches) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);
         std::map<std::string, double> settings;
@@ -586,11 +631,7 @@ int host_pso_run(void* hv, const double* x0, const char* const* keys, const doub
         if (trace) std::copy(pso.bestTrace().begin(), pso.bestTrace().end(), trace);
         if (evaluations) *evaluations = pso.evaluations();
         if (launches) *launches = pso.launches();
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 namespace {
@@ -604,18 +645,8 @@ void copy_calibration(const HipModelCalibrator& cal, int P, int mh_iterations, d
     if (phase2_cov)
         for (int a = 0; a < P; ++a)
             for (int b = 0; b < P; ++b) phase2_cov[static_cast<size_t>(a) * P + b] = cal.getPhase2Covariance()(a, b);
-    const auto& res = cal.getPhase2Results();
-    const int ns = static_cast<int>(res[0].samples.size());
-    if (n_samples) *n_samples = ns;
-    for (size_t c = 0; c < res.size(); ++c) {
-        if (accept_trace)
-            std::copy(cal.acceptTraces()[c].begin(), cal.acceptTraces()[c].end(), accept_trace + c * static_cast<size_t>(mh_iterations - 1));
-        for (int s = 0; s < ns; ++s) {
-            if (samples)
-                for (int i = 0; i < P; ++i) samples[(c * ns + s) * P + i] = res[c].samples[static_cast<size_t>(s)][i];
-            if (sample_values) sample_values[c * ns + s] = res[c].sampleObjectiveValues[static_cast<size_t>(s)];
-        }
-    }
+    const MhChainsOut chains{mh_iterations, P, nullptr, nullptr, nullptr, nullptr, accept_trace, n_samples, samples, sample_values, nullptr};
+    chains.put(cal.getPhase2Results(), cal.acceptTraces());
     if (mcmc_objective_values) std::copy(cal.getMCMCObjectiveValues().begin(), cal.getMCMCObjectiveValues().end(), mcmc_objective_values);
 }
 }  // namespace
@@ -627,25 +658,21 @@ int host_calibrate(void* hv, int hc_iterations, int cloud_size_multiplier, int t
                    double* phase2_cov, unsigned char* accept_trace, double* samples, double* sample_values,
                    double* mcmc_objective_values, int32_t* n_samples) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);  // mode at construction time
         h->last_diag = ChainDiagnosticsTable{};
         HipModelCalibrator cal(*h->pm, *h->obj);
         cal.calibrate({{"iterations", double(hc_iterations)}, {"cloud_size_multiplier", double(cloud_size_multiplier)},
                        {"threads", double(threads)}, {"seed", double(hc_seed)}},
-                      {{"mcmc_iterations", double(mh_iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
-                       {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                       {"seed", double(mh_seed)}, {"store_samples", 1.0}, {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}},
+                      mh_settings(mh_iterations, burn_in, false, 0,
+                                  {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)}, {"seed", double(mh_seed)},
+                                   {"store_samples", 1.0}, {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}}),
                       chains);
         h->last_diag = cal.diagnostics();
         copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace,
                          samples, sample_values, mcmc_objective_values, n_samples);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // SEPAIHRDModelCalibration::runPSOMCMC (SEPAIHRDModelCalibration.cpp:179-208): phase 1 = particle swarm.
@@ -655,7 +682,7 @@ int host_calibrate_pso(void* hv, const char* const* keys, const double* values, 
                        unsigned char* accept_trace, double* samples, double* sample_values,
                        double* mcmc_objective_values, int32_t* n_samples) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(ConstraintMode::OPTIMIZATION_CLAMP);
         std::map<std::string, double> phase1;
@@ -664,18 +691,14 @@ int host_calibrate_pso(void* hv, const char* const* keys, const double* values, 
         HipModelCalibrator cal(*h->pm, *h->obj);
         cal.setPhase1Algorithm(std::make_unique<BatchedParticleSwarmOptimization>());
         cal.calibrate(phase1,
-                      {{"mcmc_iterations", double(mh_iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
-                       {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                       {"seed", double(mh_seed)}, {"store_samples", 1.0}, {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}},
+                      mh_settings(mh_iterations, burn_in, false, 0,
+                                  {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)}, {"seed", double(mh_seed)},
+                                   {"store_samples", 1.0}, {"compute_diagnostics", h->mh_diagnostics ? 1.0 : 0.0}}),
                       chains);
         h->last_diag = cal.diagnostics();
         copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace,
                          samples, sample_values, mcmc_objective_values, n_samples);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // Convergence diagnostics (HipChainDiagnostics).  set_mh_diagnostics: host_mh_run (device-resident state), host_calibrate
@@ -696,7 +719,7 @@ int host_mh_diagnostics(void* hv, double* out, int32_t* rows) {
 
 int host_chain_diagnostics(void* hv, const double* samples, const double* values, int C, int N, int P, double* out, int32_t* max_lag) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         if (!h->obj) throw InvalidParameterException("host_chain_diagnostics", "the handle has no objective (device context)");
         if (C < 1 || N < 1 || P < 1) throw InvalidParameterException("host_chain_diagnostics", "need C, N, P >= 1");
         std::vector<std::vector<Eigen::VectorXd>> chains(static_cast<size_t>(C));
@@ -708,11 +731,7 @@ int host_chain_diagnostics(void* hv, const double* samples, const double* values
         const ChainDiagnosticsTable t = HipChainDiagnostics::compute(*h->obj, chains, vals);
         std::copy(t.values.begin(), t.values.end(), out);
         if (max_lag) std::copy(t.max_lag.begin(), t.max_lag.end(), max_lag);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // HipSEPAIHRDGradientObjectiveFunction::evaluate_with_gradient over the handle's parameter manager / data.
@@ -720,7 +739,7 @@ int host_chain_diagnostics(void* hv, const double* samples, const double* values
 int host_gradient(void* hv, const sepaihrd_problem* pb, int device, const double* theta, double epsilon, double* value,
                   double* grad) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int n = pb->n_age;
         const int P = static_cast<int>(h->pm->getParameterCount());
         const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
@@ -733,11 +752,7 @@ int host_gradient(void* hv, const sepaihrd_problem* pb, int device, const double
         IGradientObjectiveFunction& iface = obj;  // through the interface NUTS uses (NUTSSampler.cpp:80)
         *value = iface.evaluate_with_gradient(vec(theta, P), g);
         for (int i = 0; i < P; ++i) grad[i] = g[i];
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // HipNUTSSampler over a HipSEPAIHRDGradientObjectiveFunction built on the handle's parameter manager / data
@@ -748,7 +763,8 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
                   double* samples, double* values, double* eps_trace, int32_t* depth_trace, double* best, double* best_value,
                   long* gradient_calls, long* gradient_launches) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    int ns = 0;
+    return guarded([&] {
         const int n = pb->n_age;
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(constraint_mode == 0 ? ConstraintMode::OPTIMIZATION_CLAMP : ConstraintMode::MCMC_REFLECT);
@@ -764,7 +780,7 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
                         {"seed", double(seed)}});
         IObjectiveFunction& iface = static_cast<HipSEPAIHRDObjectiveFunction&>(obj);
         const OptimizationResult r = nuts.optimize(vec(theta0, P), iface, *h->pm);
-        const int ns = static_cast<int>(r.samples.size());
+        ns = static_cast<int>(r.samples.size());
         for (int s = 0; s < ns; ++s) {
             for (int i = 0; i < P; ++i) samples[static_cast<size_t>(s) * P + i] = r.samples[static_cast<size_t>(s)][i];
             values[s] = r.sampleObjectiveValues[static_cast<size_t>(s)];
@@ -776,11 +792,7 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
         *best_value = r.bestObjectiveValue;
         if (gradient_calls) *gradient_calls = nuts.gradientCalls();
         if (gradient_launches) *gradient_launches = nuts.gradientLaunches();
-        return ns;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return -1;
-    }
+    }) ? -1 : ns;
 }
 
 // MultiChainNUTSSampler over the handle's finite-difference objective: C chains in lock step, chain c from theta0[c] with
@@ -794,7 +806,7 @@ int host_nuts_chains_run(void* hv, const sepaihrd_problem* pb, int device, int i
                          double* best, double* best_value, int64_t* gradient_calls, int64_t* rows_evaluated, int32_t* failure_status,
                          int32_t* failure_iteration, double* stats) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int n = pb->n_age;
         const int P = static_cast<int>(h->pm->getParameterCount());
         h->pm->setConstraintMode(constraint_mode == 0 ? ConstraintMode::OPTIMIZATION_CLAMP : ConstraintMode::MCMC_REFLECT);
@@ -814,11 +826,7 @@ int host_nuts_chains_run(void* hv, const sepaihrd_problem* pb, int device, int i
         for (int c = 0; c < C; ++c) out.put(c, r.chains[static_cast<size_t>(c)]);
         const double st[6] = {double(r.ticks), double(r.rows_total), seconds, rows.call_seconds, rows.centre_ms, rows.perturbed_ms};
         if (stats) std::copy(st, st + 6, stats);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return -1;
-    }
+    }) ? -1 : 0;
 }
 
 // Test hook (no GPU): the same sampler over AnalyticGaussian (dimension D, mean [D], precision [D][D] row-major, optional
@@ -831,7 +839,7 @@ int host_nuts_chains_analytic(int D, const double* mean, const double* precision
                               double* eps_trace, int32_t* depth_trace, int32_t* n_samples, double* best, double* best_value,
                               int64_t* gradient_calls, int64_t* rows_evaluated, int32_t* failure_status, int32_t* failure_iteration,
                               double* stats) {
-    try {
+    return guarded([&] {
         AnalyticGaussian obj(D, mean, precision, fail_centre, fail_radius);
         FreeManager pm(D, sigma);
         const NutsChainsOut out{iterations, D, samples, values, eps_trace, depth_trace, n_samples, best, best_value,
@@ -867,11 +875,7 @@ int host_nuts_chains_analytic(int D, const double* mean, const double* precision
             }
         }
         if (stats) std::copy(st, st + 6, stats);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return -1;
-    }
+    }) ? -1 : 0;
 }
 
 // Test hook (no GPU): the device's restatement of glibc's log (csrc/sepaihrd_rng.inc), compiled for the host
@@ -893,39 +897,22 @@ int host_mh_run_reported(void* hv, int C, const double* initial, uint32_t seed, 
                          const char* dir, const char* log_path, double* samples, double* sample_values, int32_t* n_samples,
                          int* fell_back, long* failures) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         MultiChainMetropolisHastings mh;
-        mh.configure({{"mcmc_iterations", double(iterations)}, {"burn_in", double(burn_in)}, {"adaptation_period", double(adaptation_period)},
-                      {"thinning", double(thinning)}, {"report_interval", double(report_interval)}, {"write_checkpoints", 1.0},
-                      {"write_trace", 1.0}, {"checkpoint_chains", double(checkpoint_chains)}, {"device_streams", double(device_streams)},
-                      {"keep_accept_traces", 0.0}});
+        mh.configure(mh_settings(iterations, burn_in, true, report_interval,
+                                 {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
+                                  {"checkpoint_chains", double(checkpoint_chains)},  // as given: with 0 no chain reports or writes
+                                  {"device_streams", double(device_streams)}, {"keep_accept_traces", 0.0}}));
         mh.setSeed(seed);
         mh.setOutputDirectory(dir ? dir : "");
-        std::ofstream log;
-        if (log_path) {
-            log.open(log_path);
-            mh.setProgressSink([&log](const std::string& level, const std::string& msg) { log << level << " " << msg << std::endl; });
-        }
+        const ProgressLog log(mh, log_path);
         const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
-        const std::vector<OptimizationResult> res = device_state ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm)
-                                                                 : mh.optimizeChains(init, C, *h->obj, *h->pm);
-        const int ns = static_cast<int>(res[0].samples.size());
-        if (n_samples) *n_samples = ns;
-        for (int c = 0; c < C; ++c)
-            for (int s = 0; s < ns; ++s) {
-                if (samples)
-                    for (int i = 0; i < P; ++i) samples[(static_cast<size_t>(c) * ns + s) * P + i] = res[static_cast<size_t>(c)].samples[static_cast<size_t>(s)][i];
-                if (sample_values) sample_values[static_cast<size_t>(c) * ns + s] = res[static_cast<size_t>(c)].sampleObjectiveValues[static_cast<size_t>(s)];
-            }
+        const MhChainsOut out{iterations, P, nullptr, nullptr, nullptr, nullptr, nullptr, n_samples, samples, sample_values, nullptr};
+        out.put(device_state ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm) : mh.optimizeChains(init, C, *h->obj, *h->pm), mh.acceptTraces());
         if (fell_back) *fell_back = mh.deviceStreamsFellBack() ? 1 : 0;
-        if (failures)
-            for (size_t k = 0; k < 3; ++k) failures[k] = k < mh.failureCounts().size() ? mh.failureCounts()[k] : 0;
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+        put_failures(mh.failureCounts(), failures);  // not gated on device_state: what the sampler holds after either path
+    });
 }
 
 // The host twin of sepaihrd_device_libm_check (no GPU): csrc/sepaihrd_rng.inc's log / exp compiled for the host, on the SAME
@@ -956,15 +943,11 @@ int host_default_arith() { return HipSEPAIHRDObjectiveFunction::defaultArithmeti
 
 // Pure host (no GPU): exact-sort quantiles across chains of every column of a summary table, out [n_probs][width].
 int host_summary_quantiles(const double* table, int rows, int width, const double* probs, int n_probs, double* out) {
-    try {
+    return guarded([&] {
         const std::vector<double> q = MultiChainMetropolisHastings::summaryQuantiles(
             std::vector<double>(table, table + static_cast<size_t>(rows) * width), width, std::vector<double>(probs, probs + n_probs));
         std::copy(q.begin(), q.end(), out);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // optimizeChainGroupsOnDevice with stored samples, then the all-gather of the per-chain summary records over the
@@ -973,14 +956,13 @@ int host_summary_quantiles(const double* table, int rows, int width, const doubl
 int host_mh_groups_summaries(void** handles, int G, int C, const double* initial, uint32_t seed, int iterations, int burn_in,
                              int adaptation_period, int thinning, int backend, double* records, double* gathered, double* samples,
                              double* best_value, int32_t* accepted, int32_t* backend_used) {
-    try {
+    return guarded([&] {
         auto* h0 = static_cast<HostHandle*>(handles[0]);
         const int P = static_cast<int>(h0->pm->getParameterCount());
-        std::vector<HipSEPAIHRDObjectiveFunction*> objs;
-        for (int g = 0; g < G; ++g) objs.push_back(static_cast<HostHandle*>(handles[g])->obj.get());
+        const std::vector<HipSEPAIHRDObjectiveFunction*> objs = group_objectives(handles, G);
         MultiChainMetropolisHastings mh;
-        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
-                      {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)}, {"store_samples", 1.0}});
+        mh.configure(mh_settings(iterations, burn_in, false, 0,
+                                 {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)}, {"store_samples", 1.0}}));
         mh.setSeed(seed);
         const std::vector<OptimizationResult> res =
             mh.optimizeChainGroupsOnDevice(std::vector<double>(initial, initial + static_cast<size_t>(C) * P), C, objs, *h0->pm);
@@ -993,20 +975,10 @@ int host_mh_groups_summaries(void** handles, int G, int C, const double* initial
                 const std::vector<double> t = mh.gatheredSummaries(*objs[static_cast<size_t>(g)]);
                 std::copy(t.begin(), t.end(), gathered + static_cast<size_t>(g) * rec.size());
             }
-        const size_t ns = res[0].samples.size();
-        for (int c = 0; c < C; ++c) {
-            const OptimizationResult& r = res[static_cast<size_t>(c)];
-            if (best_value) best_value[c] = r.bestObjectiveValue;
-            if (accepted) accepted[c] = static_cast<int32_t>(r.additionalStats.at("accepted_count"));
-            if (samples)
-                for (size_t k = 0; k < ns; ++k)
-                    for (int i = 0; i < P; ++i) samples[(static_cast<size_t>(c) * ns + k) * P + i] = r.samples[k][i];
-        }
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+        // the traces are kept (the sampler's default) but no entry of this signature takes them
+        const MhChainsOut out{iterations, P, accepted, best_value, nullptr, nullptr, nullptr, nullptr, samples, nullptr, nullptr};
+        out.put(res, mh.acceptTraces());
+    });
 }
 
 // optimizeChainGroupsOnDevice over G handles (one device context each; parameter manager of the first).
@@ -1014,33 +986,38 @@ int host_mh_groups_summaries(void** handles, int G, int C, const double* initial
 int host_mh_run_groups(void** handles, int G, int C, const double* initial, uint32_t seed, int iterations, int burn_in,
                        int adaptation_period, int thinning, int32_t* accepted, double* best_value, double* best,
                        unsigned char* accept_trace) {
-    try {
+    return guarded([&] {
         auto* h0 = static_cast<HostHandle*>(handles[0]);
         const int P = static_cast<int>(h0->pm->getParameterCount());
-        std::vector<HipSEPAIHRDObjectiveFunction*> objs;
-        for (int g = 0; g < G; ++g) objs.push_back(static_cast<HostHandle*>(handles[g])->obj.get());
         MultiChainMetropolisHastings mh;
-        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0}, {"burn_in", double(burn_in)},
-                      {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                      {"store_samples", 0.0}});
+        // keep_accept_traces stays at the sampler's default (on), with or without a destination for them
+        mh.configure(mh_settings(iterations, burn_in, false, 0,
+                                 {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)}, {"store_samples", 0.0}}));
         mh.setSeed(seed);
-        const std::vector<OptimizationResult> res =
-            mh.optimizeChainGroupsOnDevice(std::vector<double>(initial, initial + static_cast<size_t>(C) * P), C, objs, *h0->pm);
+        const MhChainsOut out{iterations, P, accepted, best_value, best, nullptr, accept_trace, nullptr, nullptr, nullptr, nullptr};
+        out.put(mh.optimizeChainGroupsOnDevice(std::vector<double>(initial, initial + static_cast<size_t>(C) * P), C, group_objectives(handles, G), *h0->pm),
+                mh.acceptTraces());
         g_last_mh_loop_seconds = mh.lastLoopSeconds();
-        for (int c = 0; c < C; ++c) {
-            const OptimizationResult& r = res[static_cast<size_t>(c)];
-            if (accepted) accepted[c] = static_cast<int32_t>(r.additionalStats.at("accepted_count"));
-            if (best_value) best_value[c] = r.bestObjectiveValue;
-            if (best) for (int i = 0; i < P; ++i) best[static_cast<size_t>(c) * P + i] = r.bestParameters[i];
-            if (accept_trace)
-                std::copy(mh.acceptTraces()[static_cast<size_t>(c)].begin(), mh.acceptTraces()[static_cast<size_t>(c)].end(),
-                          accept_trace + static_cast<size_t>(c) * (iterations - 1));
-        }
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
+}
+
+// Test hook (no GPU): the scalar path of host_mh_run over AnalyticGaussian (dimension D, mean [D], precision [D][D] row-major)
+// with FreeManager(sigma) -- chain c from initial[c] through optimize() with seed + c, through the settings builder and the
+// output record of the entry points above.  Outputs as host_mh_run.
+int host_mh_run_analytic(int D, const double* mean, const double* precision, double sigma, int C, const double* initial, uint32_t seed,
+                         int iterations, int burn_in, int adaptation_period, int thinning, int32_t* accepted, double* best_value, double* best,
+                         double* final_scale, unsigned char* accept_trace, int32_t* n_samples, double* samples, double* sample_values,
+                         double* final_cov) {
+    return guarded([&] {
+        AnalyticGaussian obj(D, mean, precision, nullptr, 0.0);
+        FreeManager pm(D, sigma);
+        MultiChainMetropolisHastings mh;
+        mh.configure(mh_settings(iterations, burn_in, false, 0,
+                                 {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
+                                  {"keep_accept_traces", accept_trace ? 1.0 : 0.0}}));
+        const MhChainsOut out{iterations, D, accepted, best_value, best, final_scale, accept_trace, n_samples, samples, sample_values, final_cov};
+        mh_scalar_chains(mh, C, initial, seed, obj, pm, out);
+    });
 }
 
 }  // extern "C"
@@ -1073,24 +1050,11 @@ private:
 extern "C" int host_reference_constructors(const sepaihrd_problem* pb, const char* names, const char* npi_names,
                                            const double* sigmas, const double* thetas, int B, double* values,
                                            double* model_back) {
-    try {
+    return guarded([&] {
         const int n = pb->n_age;
-        SEPAIHRDParameters mp;
-        mp.N = vec(pb->N, n);
-        mp.M_baseline = Eigen::MatrixXd(n, n);
-        std::memcpy(mp.M_baseline.data(), pb->M, sizeof(double) * n * n);
-        mp.a = vec(pb->a, n); mp.h_infec = vec(pb->h_infec, n); mp.p = vec(pb->p, n); mp.h = vec(pb->h, n);
-        mp.icu = vec(pb->icu, n); mp.d_H = vec(pb->d_H, n); mp.d_ICU = vec(pb->d_ICU, n);
-        mp.d_community = vec(pb->d_community, n);
-        mp.beta = pb->beta; mp.theta = pb->theta; mp.sigma = pb->sigma; mp.gamma_p = pb->gamma_p;
-        mp.gamma_A = pb->gamma_A; mp.gamma_I = pb->gamma_I; mp.gamma_H = pb->gamma_H; mp.gamma_ICU = pb->gamma_ICU;
-        mp.beta_end_times.assign(pb->beta_end_times, pb->beta_end_times + pb->n_beta);
-        mp.beta_values.assign(pb->beta_values, pb->beta_values + pb->n_beta);
-        mp.E0_multiplier = pb->multipliers[0]; mp.P0_multiplier = pb->multipliers[1];
-        mp.A0_multiplier = pb->multipliers[2]; mp.I0_multiplier = pb->multipliers[3];
-        mp.H0_multiplier = pb->multipliers[4]; mp.ICU0_multiplier = pb->multipliers[5];
-        mp.R0_multiplier = pb->multipliers[6]; mp.D0_multiplier = pb->multipliers[7];
-        mp.runup_days = pb->runup_days; mp.seed_exposed = pb->seed_exposed;
+        SEPAIHRDParameters mp = model_parameters(pb);
+        mp.kappa_end_times.clear();  // main.cpp:222-242: the schedule reaches the model through the NPI strategy
+        mp.kappa_values.clear();
         const std::vector<std::string> nm = split_lines(names);
         std::map<std::string, double> sg;
         std::map<std::string, std::pair<double, double>> bd;
@@ -1098,20 +1062,14 @@ extern "C" int host_reference_constructors(const sepaihrd_problem* pb, const cha
             sg[nm[i]] = sigmas[i];
             bd[nm[i]] = {pb->lower[i], pb->upper[i]};
         }
-        // main.cpp:222-242: the strategy takes the schedule after the baseline period
+        // the strategy takes the schedule after the baseline period
         auto npi = std::make_shared<PiecewiseConstantNpiStrategy>(
             std::vector<double>(pb->kappa_end_times + 1, pb->kappa_end_times + pb->n_kappa),
             std::vector<double>(pb->kappa_values + 1, pb->kappa_values + pb->n_kappa),
             std::map<std::string, std::pair<double, double>>{}, pb->kappa_values[0], pb->kappa_end_times[0], true,
             split_lines(npi_names));
         auto model = std::make_shared<AgeSEPAIHRDModel>(mp, npi);
-        auto mat = [&](const double* src) {
-            Eigen::MatrixXd m(pb->n_obs, n);
-            for (int r = 0; r < pb->n_obs; ++r)
-                for (int c = 0; c < n; ++c) m(r, c) = src[static_cast<size_t>(r) * n + c];
-            return m;
-        };
-        const CalibrationData data(mat(pb->obs_H), mat(pb->obs_ICU), mat(pb->obs_D), mp.N);
+        const CalibrationData data = calibration_data(pb, mp.N);
         const std::shared_ptr<IOdeSolverStrategy> solver = strategy_for(pb->solver);
         const std::vector<double> times(pb->times, pb->times + pb->n_times);
         const Eigen::VectorXd x0 = vec(pb->initial_state, 11 * n);
@@ -1144,11 +1102,7 @@ extern "C" int host_reference_constructors(const sepaihrd_problem* pb, const cha
         HipSEPAIHRDParameterManager readback(model, nm, sg, bd);  // reads the model the first manager wrote into
         const Eigen::VectorXd cur = readback.getCurrentParameters();
         for (size_t i = 0; i < P; ++i) model_back[i] = cur[static_cast<Eigen::Index>(i)];
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // Model-side holders without a device: kappa(t) of PiecewiseConstantNpiStrategy at nt times; the model's
@@ -1207,16 +1161,12 @@ extern "C" {
 
 // AgeSIRModel::computeDerivatives on the host (no device); C row-major.  0 ok, 1 = exception (host_last_error)
 int host_sir_rhs(int n, const double* N, const double* C, const double* gamma, double q, double scale, const double* state, double* out) {
-    try {
+    return guarded([&] {
         auto m = sir_model(n, N, C, gamma, q, scale);
         std::vector<double> x(state, state + 3 * n), dx(static_cast<size_t>(3 * n));
         m->computeDerivatives(x, dx, 0.0);
         std::copy(dx.begin(), dx.end(), out);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // names: '\n'-joined; sigma_names / sigma_values: n_sigmas explicit proposal sigmas (the rest take the defaults).
@@ -1252,7 +1202,7 @@ void host_sir_destroy(void* hv) { delete static_cast<SirHandle*>(hv); }
 // sigma, lower and upper bound of every parameter; the manager's current parameters; 0 ok
 int host_sir_manager_info(void* hv, double* sigmas, double* lower, double* upper, double* current) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         const Eigen::VectorXd cur = h->pm->getCurrentParameters();
         for (int i = 0; i < P; ++i) {
@@ -1261,11 +1211,7 @@ int host_sir_manager_info(void* hv, double* sigmas, double* lower, double* upper
             upper[i] = h->pm->getUpperBoundForParamIndex(i);
             current[i] = cur[i];
         }
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 int host_sir_index_for_param(void* hv, const char* name) { return static_cast<SirHandle*>(hv)->pm->getIndexForParam(name); }
@@ -1281,38 +1227,26 @@ int host_sir_apply_constraints(void* hv, const double* in, double* out) {
 // updateModelParameters(theta), then the model's q, scale_C_total and gamma[n]; 0 ok, 1 = exception
 int host_sir_update_model(void* hv, const double* theta, double* q, double* scale, double* gamma) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         h->pm->updateModelParameters(vec(theta, static_cast<int>(h->pm->getParameterCount())));
         *q = h->model->getTransmissibility();
         *scale = h->model->getContactScaleFactor();
         for (int i = 0; i < h->model->getNumAgeClasses(); ++i) gamma[i] = h->model->getRecoveryRate()[i];
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 int host_sir_calculate(void* hv, const double* theta, double* value) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         *value = h->obj->calculate(vec(theta, static_cast<int>(h->pm->getParameterCount())));
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 int host_sir_calculate_batch(void* hv, const double* thetas, int B, double* out, int* status) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         h->obj->calculateBatch(thetas, B, out, status);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 void host_sir_cache_stats(void* hv, long* calls, long* hits, long* size) {
@@ -1326,7 +1260,7 @@ void host_sir_cache_stats(void* hv, long* calls, long* hits, long* size) {
 int host_sir_hc_run(void* hv, const double* x0, uint32_t seed, int threads, int iterations, int cloud_size_multiplier, double* best,
                     double* best_value) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         BatchedHillClimbingOptimizer hc;
         hc.configure({{"iterations", double(iterations)}, {"cloud_size_multiplier", double(cloud_size_multiplier)},
@@ -1334,11 +1268,7 @@ int host_sir_hc_run(void* hv, const double* x0, uint32_t seed, int threads, int 
         const OptimizationResult r = hc.optimize(vec(x0, P), *h->obj, *h->pm);
         for (int i = 0; i < P; ++i) best[i] = r.bestParameters[i];
         *best_value = r.bestObjectiveValue;
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // MultiChainMetropolisHastings::optimizeChains (the lock-step branch over any IBatchObjectiveFunction), unchanged:
@@ -1346,24 +1276,14 @@ int host_sir_hc_run(void* hv, const double* x0, uint32_t seed, int threads, int 
 int host_sir_mh_run(void* hv, int C, const double* initial, uint32_t seed, int iterations, int burn_in, double* best_value, double* best,
                     int32_t* accepted) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         MultiChainMetropolisHastings mh;
-        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0},
-                      {"burn_in", double(burn_in)}, {"store_samples", 0.0}});
+        mh.configure(mh_settings(iterations, burn_in, false, 0, {{"store_samples", 0.0}}));  // adaptation and thinning: the sampler's defaults
         mh.setSeed(seed);
-        const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
-        const std::vector<OptimizationResult> res = mh.optimizeChains(init, C, *h->obj, *h->pm);
-        for (int c = 0; c < C; ++c) {
-            best_value[c] = res[static_cast<size_t>(c)].bestObjectiveValue;
-            for (int i = 0; i < P; ++i) best[static_cast<size_t>(c) * P + i] = res[static_cast<size_t>(c)].bestParameters[i];
-            if (accepted) accepted[c] = static_cast<int32_t>(res[static_cast<size_t>(c)].additionalStats.at("accepted_count"));
-        }
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+        const MhChainsOut out{iterations, P, accepted, best_value, best, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        out.put(mh.optimizeChains(std::vector<double>(initial, initial + static_cast<size_t>(C) * P), C, *h->obj, *h->pm), mh.acceptTraces());
+    });
 }
 
 // The SIR sampler through EITHER path -- device_state = 0: the host loop optimizeChains above (every iteration through the
@@ -1380,62 +1300,31 @@ int host_sir_mh_run_ex(void* hv, int C, const double* initial, uint32_t seed, in
                        unsigned char* accept_trace, int32_t* n_samples, double* samples, double* sample_values, double* final_cov,
                        int* fell_back, long* failures, double* diag_out, int32_t* diag_rows) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         const bool reported = dir != nullptr;
         MultiChainMetropolisHastings mh;
-        mh.configure({{"mcmc_iterations", double(iterations)}, {"report_interval", reported ? double(report_interval) : 0.0},
-                      {"write_checkpoints", reported ? 1.0 : 0.0}, {"write_trace", reported ? 1.0 : 0.0},
-                      {"checkpoint_chains", double(std::max(checkpoint_chains, 1))}, {"burn_in", double(burn_in)},
-                      {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                      {"regularization_epsilon", reg_eps}, {"target_acceptance_rate", target_acc}, {"adapt_scale", double(adapt_scale)},
-                      {"store_samples", 1.0}, {"two_pass_covariance", double(two_pass_covariance)},
-                      {"adaptation_window", double(adaptation_window)}, {"device_streams", double(device_streams)},
-                      {"keep_accept_traces", accept_trace ? 1.0 : 0.0}, {"compute_diagnostics", compute_diagnostics ? 1.0 : 0.0},
-                      {"kernel_form", double(kernel_form)}});
+        mh.configure(mh_settings(iterations, burn_in, reported, report_interval,
+                                 {{"checkpoint_chains", double(std::max(checkpoint_chains, 1))},  // at least chain 0
+                                  {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
+                                  {"regularization_epsilon", reg_eps}, {"target_acceptance_rate", target_acc}, {"adapt_scale", double(adapt_scale)},
+                                  {"store_samples", 1.0}, {"two_pass_covariance", double(two_pass_covariance)},
+                                  {"adaptation_window", double(adaptation_window)}, {"device_streams", double(device_streams)},
+                                  {"keep_accept_traces", accept_trace ? 1.0 : 0.0}, {"compute_diagnostics", compute_diagnostics ? 1.0 : 0.0},
+                                  {"kernel_form", double(kernel_form)}}));
         mh.setSeed(seed);
-        std::ofstream log;
-        if (reported) {
-            mh.setOutputDirectory(dir);
-            if (log_path) {
-                log.open(log_path);
-                mh.setProgressSink([&log](const std::string& level, const std::string& msg) { log << level << " " << msg << std::endl; });
-            }
-        }
+        if (reported) mh.setOutputDirectory(dir);
+        const ProgressLog log(mh, reported ? log_path : nullptr);
         const std::vector<double> init(initial, initial + static_cast<size_t>(C) * P);
-        const std::vector<OptimizationResult> res = device_state ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm)
-                                                                 : mh.optimizeChains(init, C, *h->obj, *h->pm);
+        const MhChainsOut out{iterations, P, accepted, best_value, best, final_scale, accept_trace, n_samples, samples, sample_values, final_cov};
+        out.put(device_state ? mh.optimizeChainsOnDevice(init, C, *h->obj, *h->pm) : mh.optimizeChains(init, C, *h->obj, *h->pm), mh.acceptTraces());
         g_last_mh_loop_seconds = mh.lastLoopSeconds();
-        const int ns = static_cast<int>(res[0].samples.size());
-        if (n_samples) *n_samples = ns;
-        for (int c = 0; c < C; ++c) {
-            const OptimizationResult& r = res[static_cast<size_t>(c)];
-            if (accept_trace)
-                std::copy(mh.acceptTraces()[static_cast<size_t>(c)].begin(), mh.acceptTraces()[static_cast<size_t>(c)].end(),
-                          accept_trace + static_cast<size_t>(c) * (iterations - 1));
-            if (accepted) accepted[c] = static_cast<int32_t>(r.additionalStats.at("accepted_count"));
-            if (best_value) best_value[c] = r.bestObjectiveValue;
-            if (final_scale) final_scale[c] = r.additionalStats.at("final_scale");
-            if (best) for (int i = 0; i < P; ++i) best[static_cast<size_t>(c) * P + i] = r.bestParameters[i];
-            for (int s = 0; s < ns; ++s) {
-                if (samples) for (int i = 0; i < P; ++i) samples[(static_cast<size_t>(c) * ns + s) * P + i] = r.samples[static_cast<size_t>(s)][i];
-                if (sample_values) sample_values[static_cast<size_t>(c) * ns + s] = r.sampleObjectiveValues[static_cast<size_t>(s)];
-            }
-            if (final_cov)
-                for (int i = 0; i < P; ++i)
-                    for (int j = 0; j < P; ++j) final_cov[(static_cast<size_t>(c) * P + i) * P + j] = r.finalCovariance(i, j);
-        }
         if (fell_back) *fell_back = mh.deviceStreamsFellBack() ? 1 : 0;
-        if (failures)
-            for (size_t k = 0; k < 3; ++k) failures[k] = device_state && k < mh.failureCounts().size() ? mh.failureCounts()[k] : 0;
-        const ChainDiagnosticsTable& t = mh.diagnostics();
-        if (diag_rows) *diag_rows = device_state ? t.rows : 0;
-        if (diag_out && device_state) std::copy(t.values.begin(), t.values.end(), diag_out);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+        // failure counts and the diagnostics table are the device-resident run's: the host loop reports none of either
+        put_failures(device_state ? mh.failureCounts() : std::vector<long>(), failures);
+        if (diag_rows) *diag_rows = device_state ? mh.diagnostics().rows : 0;
+        if (diag_out && device_state) std::copy(mh.diagnostics().values.begin(), mh.diagnostics().values.end(), diag_out);
+    });
 }
 
 // HipModelCalibrator on the SIR objective (CalibrationDemo.cpp's flow): Hill-Climbing, covariance conditioning, `chains`
@@ -1446,23 +1335,18 @@ int host_sir_calibrate(void* hv, int hc_iterations, int cloud_size_multiplier, i
                        double* best_value, double* initial_value, double* phase1_best_value, double* phase2_cov, unsigned char* accept_trace,
                        double* samples, double* sample_values, double* mcmc_objective_values, int32_t* n_samples) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         const int P = static_cast<int>(h->pm->getParameterCount());
         HipModelCalibrator cal(*h->pm, *h->obj);
         cal.calibrate({{"iterations", double(hc_iterations)}, {"cloud_size_multiplier", double(cloud_size_multiplier)},
                        {"threads", double(threads)}, {"seed", double(hc_seed)}},
-                      {{"mcmc_iterations", double(mh_iterations)}, {"report_interval", 0.0}, {"write_checkpoints", 0.0}, {"write_trace", 0.0},
-                       {"burn_in", double(burn_in)}, {"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)},
-                       {"seed", double(mh_seed)}, {"store_samples", 1.0}, {"kernel_form", double(kernel_form)},
-                       {"device_streams", double(device_streams)}},
+                      mh_settings(mh_iterations, burn_in, false, 0,
+                                  {{"adaptation_period", double(adaptation_period)}, {"thinning", double(thinning)}, {"seed", double(mh_seed)},
+                                   {"store_samples", 1.0}, {"kernel_form", double(kernel_form)}, {"device_streams", double(device_streams)}}),
                       chains);
         copy_calibration(cal, P, mh_iterations, best, best_value, initial_value, phase1_best_value, phase2_cov, accept_trace, samples,
                          sample_values, mcmc_objective_values, n_samples);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // ---- SIR scenario analysis (HipSIRScenarioAnalysis.hpp) ----
@@ -1514,7 +1398,7 @@ std::vector<SIRScenario> sir_scenarios(const std::vector<double>& times, const c
 int host_sir_write_scenario_csvs(const char* comparison_path, const char* bands_path, const char* scenario_names, int K, int n_age, int T,
                                  const double* times, const double* probs, int n_probs, const double* quantiles, const double* metric_summary,
                                  const double* diff_quantiles) {
-    try {
+    return guarded([&] {
         SIRScenarioResult r;
         r.scenario_names = split_lines(scenario_names);
         if (static_cast<int>(r.scenario_names.size()) != K) throw InvalidParameterException("host_sir_write_scenario_csvs", "one name per scenario expected");
@@ -1528,11 +1412,7 @@ int host_sir_write_scenario_csvs(const char* comparison_path, const char* bands_
         if (diff_quantiles) r.diff_quantiles.assign(diff_quantiles, diff_quantiles + static_cast<size_t>(K) * W * n_probs);
         if (comparison_path) HipSIRScenarioAnalysis::writeScenarioComparison(comparison_path, r);
         if (bands_path) HipSIRScenarioAnalysis::writePosteriorBands(bands_path, r);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // HipSIRScenarioAnalysis::run on the handle's objective and both files.  Scenario k has counts[k] entries taken in sequence
@@ -1543,7 +1423,7 @@ int host_sir_scenario_comparison(void* hv, const double* samples, int n_samples,
                                  int n_probs, const char* comparison_path, const char* bands_path, double* quantiles, double* metrics,
                                  double* metric_summary, double* diff_quantiles, int32_t* status, int32_t* n_valid) {
     auto* h = static_cast<SirHandle*>(hv);
-    try {
+    return guarded([&] {
         if (!h->obj) throw ModelException("host_sir_scenario_comparison", "the handle has no objective");
         const std::vector<double>& times = h->times;
         const HipSIRScenarioAnalysis analysis(*h->obj, times, h->model->getNumAgeClasses());
@@ -1558,11 +1438,7 @@ int host_sir_scenario_comparison(void* hv, const double* samples, int n_samples,
         if (diff_quantiles) std::copy(r.diff_quantiles.begin(), r.diff_quantiles.end(), diff_quantiles);
         if (status) std::copy(r.status.begin(), r.status.end(), status);
         if (n_valid) std::copy(r.n_valid.begin(), r.n_valid.end(), n_valid);
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // ---- posterior predictive draws (HipPosteriorPredictive) ----
@@ -1587,13 +1463,9 @@ int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const doub
                     int R, uint64_t seed, const double* probs, int n_probs, double* pred, double* pit, double* observed, double* means,
                     double* draws, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
-        const int n = pb->n_age;
-        const size_t P = h->pm->getParameterCount();
-        HipPosteriorPredictive pp(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
-                                  strategy_for(pb->solver), pb->abs_err, pb->rel_err, device, pb->arith == SEPAIHRD_ARITH_FMA);
-        std::vector<Eigen::VectorXd> ps;
-        for (int s = 0; s < n_samples; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+    return guarded([&] {
+        HipPosteriorPredictive pp = posterior_over<HipPosteriorPredictive>(*h, pb, device);
+        const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
         const PosteriorPredictiveDraws d = pp.draw(ps, num_for_ppc, ppc_seed, R, seed, std::vector<double>(probs, probs + n_probs), means != nullptr,
                                                    draws != nullptr);
         std::copy(d.pred_quantiles.begin(), d.pred_quantiles.end(), pred);
@@ -1608,11 +1480,7 @@ int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const doub
         *n_selected = static_cast<int32_t>(d.selected.size());
         if (status) std::copy(d.status.begin(), d.status.end(), status);
         *samples_used = d.samples_used;
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // ---- stochastic chain-binomial SEPAIHRD ensembles (HipStochasticSEPAIHRD) ----
@@ -1637,13 +1505,10 @@ int host_stochastic(void* hv, const sepaihrd_problem* pb, int device, int initia
                     uint32_t select_seed, int R, int steps_per_interval, uint64_t seed, const double* probs, int n_probs, double* quantiles,
                     double* extinct, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
     auto* h = static_cast<HostHandle*>(hv);
-    try {
-        const int n = pb->n_age;
-        const size_t P = h->pm->getParameterCount();
-        HipStochasticSEPAIHRD model(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * n),
+    return guarded([&] {
+        HipStochasticSEPAIHRD model(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * pb->n_age),
                                     strategy_for(pb->solver), device, initial_state_mode);
-        std::vector<Eigen::VectorXd> ps;
-        for (int s = 0; s < n_samples; ++s) ps.push_back(vec(samples + static_cast<size_t>(s) * P, static_cast<int>(P)));
+        const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
         const StochasticSEPAIHRDResult d = model.run(ps, num_samples, select_seed, R, steps_per_interval, seed, std::vector<double>(probs, probs + n_probs));
         std::copy(d.quantiles.begin(), d.quantiles.end(), quantiles);
         if (extinct) std::copy(d.extinct.begin(), d.extinct.end(), extinct);
@@ -1651,22 +1516,18 @@ int host_stochastic(void* hv, const sepaihrd_problem* pb, int device, int initia
         *n_selected = static_cast<int32_t>(d.selected.size());
         if (status) std::copy(d.status.begin(), d.status.end(), status);
         *samples_used = d.samples_used;
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 // The parameter part of a model_values row (everything before the initial counts) as the handle's parameter manager writes it:
 // updateModelParameters(theta) in the given constraint mode, then the model parameters in the row's order.  0 ok, 1 = exception.
 int host_stochastic_manager_values(void* hv, int mode, const double* theta, double* out) {
     auto* h = static_cast<HostHandle*>(hv);
-    const ConstraintMode keep = h->pm->getConstraintMode();
-    try {
-        h->pm->setConstraintMode(mode == 1 ? ConstraintMode::MCMC_REFLECT : ConstraintMode::OPTIMIZATION_CLAMP);
-        h->pm->updateModelParameters(vec(theta, static_cast<int>(h->pm->getParameterCount())));
-        h->pm->setConstraintMode(keep);
+    return guarded([&] {
+        {
+            const ConstraintModeScope in_mode(*h->pm, mode);
+            h->pm->updateModelParameters(vec(theta, static_cast<int>(h->pm->getParameterCount())));
+        }
         const SEPAIHRDParameters& mp = h->pm->modelParameters();
         size_t at = 0;
         for (double v : {mp.theta, mp.sigma, mp.gamma_p, mp.gamma_A, mp.gamma_I, mp.gamma_H, mp.gamma_ICU, mp.beta}) out[at++] = v;
@@ -1674,12 +1535,7 @@ int host_stochastic_manager_values(void* hv, int mode, const double* theta, doub
         for (double v : mp.kappa_values) out[at++] = v;
         for (const Eigen::VectorXd* f : {&mp.a, &mp.h_infec, &mp.p, &mp.h, &mp.icu, &mp.d_H, &mp.d_ICU, &mp.d_community})
             for (Eigen::Index i = 0; i < f->size(); ++i) out[at++] = (*f)[i];
-        return 0;
-    } catch (const std::exception& e) {
-        h->pm->setConstraintMode(keep);
-        g_error = e.what();
-        return 1;
-    }
+    });
 }
 
 }  // extern "C"

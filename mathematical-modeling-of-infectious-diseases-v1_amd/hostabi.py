@@ -34,18 +34,34 @@ def load_library() -> C.CDLL:
     lib.host_objective_create.restype = vp
     lib.host_objective_create.argtypes = [C.POINTER(hipabi.sepaihrd_problem), C.c_char_p, C.c_char_p, vp, C.c_int,
                                           C.c_int, C.c_int]
+    lib.host_objective_destroy.restype = None
     lib.host_objective_destroy.argtypes = [vp]
     lib.host_model_holders.argtypes = [vp, vp, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int),
                                        C.c_char_p, C.c_int]
     lib.host_reference_constructors.argtypes = [C.POINTER(hipabi.sepaihrd_problem), C.c_char_p, C.c_char_p, vp, vp, C.c_int, vp, vp]
     lib.host_objective_calculate.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.host_objective_calculate_batch.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.host_cache_stats.restype = None
     lib.host_cache_stats.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
     lib.host_apply_constraints.argtypes = [vp, C.c_int, vp, vp]
     lib.host_current_parameters.argtypes = [vp, vp]
     lib.host_mh_run.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                 C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int]
     lib.host_mh_run_groups.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.host_mh_groups_summaries.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint32] + [C.c_int] * 5 + [vp] * 6
+    lib.host_mh_run_reported.argtypes = [vp, C.c_int, vp, C.c_uint32] + [C.c_int] * 8 + \
+        [C.c_char_p, C.c_char_p, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    lib.host_mh_run_analytic.argtypes = [C.c_int, vp, vp, C.c_double, C.c_int, vp, C.c_uint32] + [C.c_int] * 4 + [vp] * 9
+    lib.host_summary_quantiles.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.host_libm_selfcheck.restype = None
+    lib.host_libm_selfcheck.argtypes = [C.POINTER(C.c_int)] * 3
+    lib.host_libm_selfcheck_args.restype = None
+    lib.host_libm_selfcheck_args.argtypes = [vp, vp]
+    lib.host_default_arith.restype = C.c_int
+    lib.host_default_arith.argtypes = []
+    for f in (lib.host_glibc_log, lib.host_glibc_exp):
+        f.restype = None
+        f.argtypes = [vp, C.c_int, vp]
     lib.host_gradient.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_double, vp, vp]
     lib.host_calibrate.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -80,6 +96,7 @@ def load_library() -> C.CDLL:
     lib.host_sir_update_model.argtypes = [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp]
     lib.host_sir_calculate.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.host_sir_calculate_batch.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.host_sir_cache_stats.restype = None
     lib.host_sir_cache_stats.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]
     lib.host_sir_hc_run.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)]
     lib.host_sir_mh_run.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
@@ -123,6 +140,76 @@ def load_library() -> C.CDLL:
     return lib
 
 
+def _check(rc, prefix: str = "") -> None:
+    """RuntimeError with the library's last message (host_last_error) behind ``prefix`` for a non-zero return code"""
+    if rc:
+        raise RuntimeError(prefix + load_library().host_last_error().decode())
+
+
+_MH_ARRAYS = ("accepted", "best_value", "best", "final_scale", "accept_trace", "samples", "sample_values", "final_cov")
+
+
+def _mh_arrays(Cn: int, P: int, iterations: int, thinning: int = 1, want_trace: bool = True, keys=_MH_ARRAYS) -> dict:
+    """The named result arrays of a Metropolis-Hastings run, leading axis = chain (accept_trace None unless wanted).  The C
+    side stores t = 0 and every thinning-th iteration after it: n_s samples per chain."""
+    n_s = 1 + (max(iterations, 1) - 1) // max(1, thinning)
+    spec = {"accepted": ((Cn,), np.int32), "best_value": ((Cn,), np.float64), "best": ((Cn, P), np.float64),
+            "final_scale": ((Cn,), np.float64), "accept_trace": ((Cn, max(iterations - 1, 1)), np.uint8),
+            "samples": ((Cn, n_s, P), np.float64), "sample_values": ((Cn, n_s), np.float64), "final_cov": ((Cn, P, P), np.float64)}
+    return {k: np.zeros(*spec[k]) if k != "accept_trace" or want_trace else None for k in keys}
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _mh_result(a: dict, iterations: int, n_samples=None, **more) -> dict:
+    """The result dictionary of a Metropolis-Hastings wrapper from its _mh_arrays: the accept trace cut to its
+    iterations - 1 columns, the sample count the C side reported checked against the arrays, ``more`` behind them."""
+    if n_samples is not None:
+        assert n_samples == a["samples"].shape[1]
+    out = dict(a)
+    if out.get("accept_trace") is not None:
+        out["accept_trace"] = out["accept_trace"][:, :iterations - 1]
+    out.update(more)
+    return out
+
+
+def mh_analytic(mean, precision, initial, seed: int, iterations: int, burn_in: int, adaptation_period: int = 100, thinning: int = 1,
+                sigma: float = 1.0, want_trace: bool = True) -> dict:
+    """Test hook without a GPU (host_mh_run_analytic): MultiChainMetropolisHastings' scalar path, chain c through optimize()
+    with seed + c, over the log-density of a Gaussian with the given mean and precision matrix -- through the settings
+    builder and the output record of every MH entry point.  The arrays of HostObjective.metropolis_hastings."""
+    lib = load_library()
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    prec = np.ascontiguousarray(precision, dtype=np.float64)
+    x0 = np.ascontiguousarray(np.atleast_2d(initial), dtype=np.float64)
+    Cn, D = x0.shape
+    if mean.shape != (D,) or prec.shape != (D, D):
+        raise ValueError("mean [D], precision [D][D], initial [C][D]")
+    a = _mh_arrays(Cn, D, iterations, thinning, want_trace)
+    ns = C.c_int32()
+    ptrs = [_ptr(a[k]) for k in _MH_ARRAYS]
+    _check(lib.host_mh_run_analytic(D, mean.ctypes.data, prec.ctypes.data, sigma, Cn, x0.ctypes.data, seed, iterations, burn_in,
+                                    adaptation_period, thinning, *ptrs[:5], C.byref(ns), *ptrs[5:]), "host_mh_run_analytic: ")
+    return _mh_result(a, iterations, ns.value)
+
+
+def _calibration(entry, head, prefix: str, P: int, chains: int, mh_iterations: int, thinning: int) -> dict:
+    """One of the two-phase calibration entry points: its own arguments ``head``, then the ten outputs they share.  Per-chain
+    arrays are chain-major with cap samples per chain: t = 0 and every thinning-th iteration after it."""
+    cap = 1 + (mh_iterations - 1) // max(1, thinning)
+    out = {"best": np.empty(P), "phase2_cov": np.empty((P, P)), "accept_trace": np.empty((chains, mh_iterations - 1), dtype=np.uint8),
+           "samples": np.empty((chains, cap, P)), "sample_values": np.empty((chains, cap)), "mcmc_objective_values": np.empty((chains, cap))}
+    bv, iv, p1, ns = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    _check(entry(*head, out["best"].ctypes.data, C.byref(bv), C.byref(iv), C.byref(p1),
+                 *[out[k].ctypes.data for k in ("phase2_cov", "accept_trace", "samples", "sample_values", "mcmc_objective_values")], C.byref(ns)),
+           prefix)
+    assert ns.value == cap, (ns.value, cap)
+    out.update(best_value=bv.value, initial_value=iv.value, phase1_best_value=p1.value, n_samples=ns.value)
+    return out
+
+
 def _nuts_chains_outputs(Cn: int, iterations: int, P: int):
     """Arrays of a lock-step NUTS run, leading axis = chain, and their pointers in the order of the C entry points."""
     out = {"samples": np.empty((Cn, iterations, P)), "sample_values": np.empty((Cn, iterations)),
@@ -150,11 +237,9 @@ def nuts_chains_analytic(mean, precision, theta0, seed0: int, iterations: int, a
         raise ValueError("mean [D], precision [D][D], theta0 [C][D]")
     fc = None if fail_centre is None else np.ascontiguousarray(fail_centre, dtype=np.float64)
     out, stats, ptrs = _nuts_chains_outputs(th.shape[0], iterations, D)
-    rc = lib.host_nuts_chains_analytic(D, mean.ctypes.data, prec.ctypes.data, sigma, None if fc is None else fc.ctypes.data,
-                                       fail_radius, int(lock_step), iterations, adaptation_window, delta_target, max_tree_depth,
-                                       th.shape[0], th.ctypes.data, seed0, *ptrs)
-    if rc != 0:
-        raise RuntimeError("host_nuts_chains_analytic: " + lib.host_last_error().decode())
+    _check(lib.host_nuts_chains_analytic(D, mean.ctypes.data, prec.ctypes.data, sigma, None if fc is None else fc.ctypes.data,
+                                         fail_radius, int(lock_step), iterations, adaptation_window, delta_target, max_tree_depth,
+                                         th.shape[0], th.ctypes.data, seed0, *ptrs), "host_nuts_chains_analytic: ")
     out.update(ticks=int(stats[0]), rows_total=int(stats[1]),
                mean_rows_per_tick=stats[1] / stats[0] if stats[0] > 0 else 0.0)
     return out
@@ -172,8 +257,7 @@ class HostObjective:
         self.h = self.lib.host_objective_create(C.byref(st), "\n".join(pb.param_names).encode(),
                                                 "\n".join(pb.npi_names).encode(), sig.ctypes.data, device,
                                                 cache_capacity, int(with_objective))
-        if not self.h:
-            raise RuntimeError("host_objective_create failed: " + self.lib.host_last_error().decode())
+        _check(not self.h, "host_objective_create failed: ")
         self.P = pb.n_params
 
     def __del__(self):
@@ -193,11 +277,9 @@ class HostObjective:
         trace = np.empty(iterations)
         bv = C.c_double(0.0)
         ne, nl = C.c_long(0), C.c_long(0)
-        rc = self.lib.host_hc_run(self.h, x0.ctypes.data, seed, threads, iterations, cloud_size_multiplier,
-                                  int(use_scalar_interface), best.ctypes.data, C.byref(bv), cov.ctypes.data,
-                                  trace.ctypes.data, C.byref(ne), C.byref(nl))
-        if rc != 0:
-            raise RuntimeError("host_hc_run: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_hc_run(self.h, x0.ctypes.data, seed, threads, iterations, cloud_size_multiplier,
+                                    int(use_scalar_interface), best.ctypes.data, C.byref(bv), cov.ctypes.data,
+                                    trace.ctypes.data, C.byref(ne), C.byref(nl)), "host_hc_run: ")
         return {"best": best, "best_value": bv.value, "final_cov": cov, "trace": trace,
                 "evaluations": ne.value, "launches": nl.value}
 
@@ -216,10 +298,8 @@ class HostObjective:
         trace = np.empty(iters)
         bv = C.c_double(0.0)
         ne, nl = C.c_long(0), C.c_long(0)
-        rc = self.lib.host_pso_run(self.h, x0p, keys, vals.ctypes.data, len(settings), best.ctypes.data, C.byref(bv),
-                                   cov.ctypes.data, trace.ctypes.data, C.byref(ne), C.byref(nl))
-        if rc != 0:
-            raise RuntimeError("host_pso_run: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_pso_run(self.h, x0p, keys, vals.ctypes.data, len(settings), best.ctypes.data, C.byref(bv),
+                                     cov.ctypes.data, trace.ctypes.data, C.byref(ne), C.byref(nl)), "host_pso_run: ")
         return {"best": best, "best_value": bv.value, "final_cov": cov, "trace": trace,
                 "evaluations": ne.value, "launches": nl.value}
 
@@ -230,9 +310,7 @@ class HostObjective:
         st = hipabi.build_problem_struct(self.pb, keep)
         g = np.empty(self.P)
         v = C.c_double(0.0)
-        rc = self.lib.host_gradient(self.h, C.byref(st), device, th.ctypes.data, epsilon, C.byref(v), g.ctypes.data)
-        if rc != 0:
-            raise RuntimeError("host_gradient: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_gradient(self.h, C.byref(st), device, th.ctypes.data, epsilon, C.byref(v), g.ctypes.data), "host_gradient: ")
         return v.value, g
 
     def nuts(self, theta0, seed: int, iterations: int, adaptation_window: int, max_tree_depth: int = 10,
@@ -251,8 +329,7 @@ class HostObjective:
                                     max_tree_depth, fd_epsilon, constraint_mode, th.ctypes.data, seed,
                                     samples.ctypes.data, values.ctypes.data, eps.ctypes.data, depth.ctypes.data,
                                     best.ctypes.data, C.byref(bv), C.byref(nc), C.byref(nl))
-        if ns < 0:
-            raise RuntimeError("host_nuts_run: " + self.lib.host_last_error().decode())
+        _check(ns < 0, "host_nuts_run: ")
         return {"samples": samples[:ns], "sample_values": values[:ns], "epsilon_trace": eps[:ns], "depth_trace": depth[:ns],
                 "best": best, "best_value": bv.value, "gradient_calls": nc.value, "gradient_launches": nl.value}
 
@@ -271,11 +348,9 @@ class HostObjective:
         keep: list = []
         st = hipabi.build_problem_struct(self.pb, keep)
         out, stats, ptrs = _nuts_chains_outputs(th.shape[0], iterations, self.P)
-        rc = self.lib.host_nuts_chains_run(self.h, C.byref(st), device, iterations, adaptation_window, delta_target,
-                                           max_tree_depth, fd_epsilon, constraint_mode, th.shape[0], th.ctypes.data, seed0,
-                                           int(kernel_timing), *ptrs)
-        if rc != 0:
-            raise RuntimeError("host_nuts_chains_run: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_nuts_chains_run(self.h, C.byref(st), device, iterations, adaptation_window, delta_target,
+                                             max_tree_depth, fd_epsilon, constraint_mode, th.shape[0], th.ctypes.data, seed0,
+                                             int(kernel_timing), *ptrs), "host_nuts_chains_run: ")
         out.update(ticks=int(stats[0]), rows_total=int(stats[1]), mean_rows_per_tick=stats[1] / stats[0] if stats[0] > 0 else 0.0,
                    seconds=stats[2], evaluation_seconds=stats[3], centre_kernel_ms=stats[4], perturbed_kernel_ms=stats[5])
         return out
@@ -284,49 +359,18 @@ class HostObjective:
                   cloud_size_multiplier: int = 8, threads: int = 16, adaptation_period: int = 100, thinning: int = 1,
                   chains: int = 1) -> dict:
         """HipModelCalibrator: HC (clamp) -> covariance conditioning -> `chains` MH chains (reflect)."""
-        cap = 1 + (mh_iterations - 1) // max(1, thinning)  # t = 0 and every thinning-th iteration after it
-        out = {"best": np.empty(self.P), "phase2_cov": np.empty((self.P, self.P)),
-               "accept_trace": np.empty((chains, mh_iterations - 1), dtype=np.uint8),
-               "samples": np.empty((chains, cap, self.P)), "sample_values": np.empty((chains, cap)),
-               "mcmc_objective_values": np.empty((chains, cap))}
-        bv, iv, p1 = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        ns = C.c_int32(0)
-        rc = self.lib.host_calibrate(self.h, hc_iterations, cloud_size_multiplier, threads, hc_seed, mh_iterations,
-                                     burn_in, adaptation_period, thinning, mh_seed, chains, out["best"].ctypes.data,
-                                     C.byref(bv), C.byref(iv), C.byref(p1), out["phase2_cov"].ctypes.data,
-                                     out["accept_trace"].ctypes.data, out["samples"].ctypes.data,
-                                     out["sample_values"].ctypes.data, out["mcmc_objective_values"].ctypes.data,
-                                     C.byref(ns))
-        if rc != 0:
-            raise RuntimeError("host_calibrate: " + self.lib.host_last_error().decode())
-        n = ns.value
-        assert n == cap, (n, cap)
-        out.update(best_value=bv.value, initial_value=iv.value, phase1_best_value=p1.value, n_samples=n)
-        return out
+        return _calibration(self.lib.host_calibrate, (self.h, hc_iterations, cloud_size_multiplier, threads, hc_seed, mh_iterations, burn_in,
+                                                      adaptation_period, thinning, mh_seed, chains),
+                            "host_calibrate: ", self.P, chains, mh_iterations, thinning)
 
     def calibrate_pso(self, pso_settings: dict, mh_seed: int, mh_iterations: int, burn_in: int,
                       adaptation_period: int = 100, thinning: int = 1, chains: int = 1) -> dict:
         """HipModelCalibrator with the particle swarm as phase 1 (SEPAIHRDModelCalibration::runPSOMCMC)."""
-        cap = 1 + (mh_iterations - 1) // max(1, thinning)
-        out = {"best": np.empty(self.P), "phase2_cov": np.empty((self.P, self.P)),
-               "accept_trace": np.empty((chains, mh_iterations - 1), dtype=np.uint8),
-               "samples": np.empty((chains, cap, self.P)), "sample_values": np.empty((chains, cap)),
-               "mcmc_objective_values": np.empty((chains, cap))}
         keys = (C.c_char_p * len(pso_settings))(*[k.encode() for k in pso_settings])
         vals = np.array([float(v) for v in pso_settings.values()])
-        bv, iv, p1 = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        ns = C.c_int32(0)
-        rc = self.lib.host_calibrate_pso(self.h, keys, vals.ctypes.data, len(pso_settings), mh_iterations, burn_in,
-                                         adaptation_period, thinning, mh_seed, chains, out["best"].ctypes.data,
-                                         C.byref(bv), C.byref(iv), C.byref(p1), out["phase2_cov"].ctypes.data,
-                                         out["accept_trace"].ctypes.data, out["samples"].ctypes.data,
-                                         out["sample_values"].ctypes.data, out["mcmc_objective_values"].ctypes.data,
-                                         C.byref(ns))
-        if rc != 0:
-            raise RuntimeError("host_calibrate_pso: " + self.lib.host_last_error().decode())
-        assert ns.value == cap, (ns.value, cap)
-        out.update(best_value=bv.value, initial_value=iv.value, phase1_best_value=p1.value, n_samples=ns.value)
-        return out
+        return _calibration(self.lib.host_calibrate_pso, (self.h, keys, vals.ctypes.data, len(pso_settings), mh_iterations, burn_in,
+                                                          adaptation_period, thinning, mh_seed, chains),
+                            "host_calibrate_pso: ", self.P, chains, mh_iterations, thinning)
 
     def posterior_ensemble(self, samples, num_for_ppc: int, seed: int, burn_in: int = 0, thinning: int = 1,
                            want_sero: bool = True, want_rt: bool = False, device: int = -1) -> dict:
@@ -342,11 +386,9 @@ class HostObjective:
         nsel, used = C.c_int32(0), C.c_int32(0)
         sero = np.empty((5, T)) if want_sero else None
         rt = np.empty((5, T)) if want_rt else None
-        rc = self.lib.host_ensemble(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, seed,
-                                    ppc.ctypes.data, sel.ctypes.data, C.byref(nsel), C.byref(used), burn_in, thinning,
-                                    sero.ctypes.data if want_sero else None, rt.ctypes.data if want_rt else None)
-        if rc != 0:
-            raise RuntimeError("host_ensemble: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_ensemble(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, seed,
+                                      ppc.ctypes.data, sel.ctypes.data, C.byref(nsel), C.byref(used), burn_in, thinning,
+                                      sero.ctypes.data if want_sero else None, rt.ctypes.data if want_rt else None), "host_ensemble: ")
         return {"ppc": ppc, "selected": sel[:nsel.value].copy(), "samples_used": used.value, "sero": sero, "rt": rt}
 
     def posterior_predictive(self, samples, num_for_ppc: int, ppc_seed: int, R: int, seed: int,
@@ -368,13 +410,11 @@ class HostObjective:
         draws = np.empty((S, max(int(R), 0), 3, Tp, n)) if want_draws else None
         sel, status = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
         nsel, used = C.c_int32(0), C.c_int32(0)
-        rc = self.lib.host_predictive(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
-                                      int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data, pit.ctypes.data,
-                                      obs.ctypes.data, means.ctypes.data if want_means else None,
-                                      draws.ctypes.data if want_draws else None, sel.ctypes.data, C.byref(nsel), status.ctypes.data,
-                                      C.byref(used))
-        if rc != 0:
-            raise RuntimeError("host_predictive: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_predictive(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data, pit.ctypes.data,
+                                        obs.ctypes.data, means.ctypes.data if want_means else None,
+                                        draws.ctypes.data if want_draws else None, sel.ctypes.data, C.byref(nsel), status.ctypes.data,
+                                        C.byref(used)), "host_predictive: ")
         out = {"pred": pred, "pit": pit, "observed": obs, "selected": sel[:nsel.value].copy(), "status": status[:nsel.value].copy(),
                "samples_used": used.value}
         if want_means:
@@ -397,11 +437,10 @@ class HostObjective:
         q = np.empty((6, pr.size, Tp, self.pb.n))
         extinct, sel, status = np.empty(cap), np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
         nsel, used = C.c_int32(0), C.c_int32(0)
-        rc = self.lib.host_stochastic(self.h, C.byref(st), device, int(initial_state_mode), ps.ctypes.data, ps.shape[0], num_samples,
-                                      select_seed, int(R), int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size,
-                                      q.ctypes.data, extinct.ctypes.data, sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used))
-        if rc != 0:
-            raise RuntimeError("host_stochastic: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_stochastic(self.h, C.byref(st), device, int(initial_state_mode), ps.ctypes.data, ps.shape[0], num_samples,
+                                        select_seed, int(R), int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size,
+                                        q.ctypes.data, extinct.ctypes.data, sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used)),
+               "host_stochastic: ")
         k = nsel.value
         return {"quantiles": q, "extinct": extinct[:k].copy(), "selected": sel[:k].copy(), "status": status[:k].copy(),
                 "samples_used": used.value}
@@ -412,8 +451,7 @@ class HostObjective:
         th = np.ascontiguousarray(theta, dtype=np.float64)
         W = stochastic_values_width(self.pb.n, len(self.pb.beta_end_times), len(self.pb.kappa_end_times)) - 11 * self.pb.n
         out = np.empty(W)
-        if self.lib.host_stochastic_manager_values(self.h, int(mode), th.ctypes.data, out.ctypes.data) != 0:
-            raise RuntimeError("host_stochastic_manager_values: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_stochastic_manager_values(self.h, int(mode), th.ctypes.data, out.ctypes.data), "host_stochastic_manager_values: ")
         return out
 
     def scenario_comparison(self, samples, burn_in: int = 0, thinning: int = 1, path: str | None = None, device: int = -1) -> dict:
@@ -426,10 +464,9 @@ class HostObjective:
         met = np.empty((3, 12 + 4 * self.pb.n))
         kap = np.empty((3, len(self.pb.kappa_values)))
         rows = C.c_int32(0)
-        rc = self.lib.host_scenario_comparison(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning,
-                                               path.encode() if path else None, met.ctypes.data, kap.ctypes.data, C.byref(rows))
-        if rc != 0:
-            raise RuntimeError("host_scenario_comparison: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_scenario_comparison(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning,
+                                                 path.encode() if path else None, met.ctypes.data, kap.ctypes.data, C.byref(rows)),
+               "host_scenario_comparison: ")
         names = ["baseline", "stricter_lockdown", "weaker_lockdown"][:rows.value]
         return {"names": names, "metrics": met[:rows.value].copy(), "kappa": kap[:rows.value].copy()}
 
@@ -438,8 +475,8 @@ class HostObjective:
         ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
         keep: list = []
         st = hipabi.build_problem_struct(self.pb, keep)
-        if self.lib.host_ene_covid_validation(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning, path.encode()):
-            raise RuntimeError("host_ene_covid_validation: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_ene_covid_validation(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], burn_in, thinning, path.encode()),
+               "host_ene_covid_validation: ")
 
     def set_mh_diagnostics(self, on: bool) -> None:
         """Convergence diagnostics for the following metropolis_hastings(device_state=True) / calibrate / calibrate_pso runs
@@ -465,16 +502,14 @@ class HostObjective:
         rows = P + (0 if v is None else 1)
         out = np.empty((rows, len(hipabi.DIAG_COLUMNS)))
         lag = np.empty((rows, 4), dtype=np.int32)
-        if self.lib.host_chain_diagnostics(self.h, s.ctypes.data, None if v is None else v.ctypes.data, Cn, N, P,
-                                           out.ctypes.data, lag.ctypes.data):
-            raise RuntimeError("host_chain_diagnostics: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_chain_diagnostics(self.h, s.ctypes.data, None if v is None else v.ctypes.data, Cn, N, P,
+                                               out.ctypes.data, lag.ctypes.data), "host_chain_diagnostics: ")
         return {"table": out, "columns": list(hipabi.DIAG_COLUMNS), "max_lag": lag}
 
     def calculate(self, theta) -> float:
         th = np.ascontiguousarray(theta, dtype=np.float64)
         v = C.c_double()
-        if self.lib.host_objective_calculate(self.h, th.ctypes.data, C.byref(v)):
-            raise RuntimeError(self.lib.host_last_error().decode())
+        _check(self.lib.host_objective_calculate(self.h, th.ctypes.data, C.byref(v)))
         return v.value
 
     def calculate_batch(self, thetas):
@@ -482,8 +517,7 @@ class HostObjective:
         B = th.shape[0]
         out = np.empty(B)
         status = np.empty(B, dtype=np.int32)
-        if self.lib.host_objective_calculate_batch(self.h, th.ctypes.data, B, out.ctypes.data, status.ctypes.data):
-            raise RuntimeError(self.lib.host_last_error().decode())
+        _check(self.lib.host_objective_calculate_batch(self.h, th.ctypes.data, B, out.ctypes.data, status.ctypes.data))
         return out, status
 
     def cache_stats(self):
@@ -510,20 +544,14 @@ class HostObjective:
         399-411,440-469): lines into log_path, posterior_trace_checkpoint.csv / _final.csv / posterior_trace.csv into out_dir."""
         x0 = np.ascontiguousarray(np.atleast_2d(initial), dtype=np.float64)
         Cn, P = x0.shape
-        n_s = 1 + (max(iterations, 1) - 1) // max(1, thinning)
-        samples, values = np.zeros((Cn, n_s, P)), np.zeros((Cn, n_s))
+        a = _mh_arrays(Cn, P, iterations, thinning, keys=("samples", "sample_values"))
         ns, fb = C.c_int32(), C.c_int()
         failures = (C.c_long * 3)()
-        self.lib.host_mh_run_reported.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32] + [C.c_int] * 8 + \
-            [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_long)]
-        rc = self.lib.host_mh_run_reported(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning,
-                                           report_interval, checkpoint_chains, int(device_state), int(device_streams),
-                                           out_dir.encode(), log_path.encode(), samples.ctypes.data, values.ctypes.data,
-                                           C.byref(ns), C.byref(fb), failures)
-        if rc:
-            raise RuntimeError(self.lib.host_last_error().decode())
-        assert ns.value == n_s
-        return {"samples": samples, "sample_values": values, "fell_back": bool(fb.value), "failures": list(failures)}
+        _check(self.lib.host_mh_run_reported(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning,
+                                             report_interval, checkpoint_chains, int(device_state), int(device_streams),
+                                             out_dir.encode(), log_path.encode(), _ptr(a["samples"]), _ptr(a["sample_values"]),
+                                             C.byref(ns), C.byref(fb), failures))
+        return _mh_result(a, iterations, ns.value, fell_back=bool(fb.value), failures=list(failures))
 
     def metropolis_hastings(self, initial, seed: int, iterations: int, burn_in: int, adaptation_period: int = 100,
                             thinning: int = 1, reg_eps: float = 1e-6, target_acc: float = 0.234,
@@ -536,30 +564,14 @@ class HostObjective:
         only): the chains' mt19937 streams drawn on the device (default) or on the host."""
         x0 = np.ascontiguousarray(np.atleast_2d(initial), dtype=np.float64)
         Cn, P = x0.shape
-        accepted = np.zeros(Cn, dtype=np.int32)
-        best_value, final_scale = np.zeros(Cn), np.zeros(Cn)
-        best = np.zeros((Cn, P))
-        trace = np.zeros((Cn, max(iterations - 1, 1)), dtype=np.uint8) if want_trace else None
+        a = _mh_arrays(Cn, P, iterations, thinning, want_trace)
         ns = C.c_int32()
-        # the C side packs with its own n_samples: t = 0 plus every thinning-th t
-        n_s = 1 + (max(iterations, 1) - 1) // max(1, thinning)
-        samples = np.zeros((Cn, n_s, P))
-        values = np.zeros((Cn, n_s))
-        cov = np.zeros((Cn, P, P))
-        rc = self.lib.host_mh_run(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning,
-                                  reg_eps, target_acc, int(adapt_scale), 2 if device_state else int(scalar_interface),
-                                  accepted.ctypes.data,
-                                  best_value.ctypes.data, best.ctypes.data, final_scale.ctypes.data,
-                                  trace.ctypes.data if want_trace else None, C.byref(ns), samples.ctypes.data,
-                                  values.ctypes.data, int(two_pass_covariance), cov.ctypes.data, int(adaptation_window),
-                                  int(device_streams))
-        if rc:
-            raise RuntimeError(self.lib.host_last_error().decode())
-        assert ns.value == n_s
-        return {"accepted": accepted, "best_value": best_value, "best": best, "final_scale": final_scale,
-                "accept_trace": trace[:, :iterations - 1] if want_trace else None, "samples": samples,
-                "sample_values": values, "final_cov": cov,
-                "loop_seconds": float(self.lib.host_last_mh_loop_seconds())}
+        ptrs = [_ptr(a[k]) for k in _MH_ARRAYS]
+        _check(self.lib.host_mh_run(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning,
+                                    reg_eps, target_acc, int(adapt_scale), 2 if device_state else int(scalar_interface),
+                                    *ptrs[:5], C.byref(ns), *ptrs[5:7], int(two_pass_covariance), ptrs[7], int(adaptation_window),
+                                    int(device_streams)))
+        return _mh_result(a, iterations, ns.value, loop_seconds=float(self.lib.host_last_mh_loop_seconds()))
 
 
 def libm_selfcheck() -> dict:
@@ -567,12 +579,8 @@ def libm_selfcheck() -> dict:
     against this process's std::log / std::exp on the self-check arguments; also returns the arguments."""
     lib = load_library()
     n, dl, de = C.c_int(), C.c_int(), C.c_int()
-    lib.host_libm_selfcheck.argtypes = [C.POINTER(C.c_int)] * 3
-    lib.host_libm_selfcheck.restype = None
     lib.host_libm_selfcheck(C.byref(n), C.byref(dl), C.byref(de))
     la, ea = np.empty(n.value), np.empty(n.value)
-    lib.host_libm_selfcheck_args.argtypes = [C.c_void_p, C.c_void_p]
-    lib.host_libm_selfcheck_args.restype = None
     lib.host_libm_selfcheck_args(la.ctypes.data, ea.ctypes.data)
     return {"n": n.value, "log_diff": dl.value, "exp_diff": de.value, "log_args": la, "exp_args": ea}
 
@@ -586,16 +594,10 @@ def metropolis_hastings_groups(objectives, initial, seed: int, iterations: int, 
     Cn, P = x0.shape
     G = len(objectives)
     handles = (C.c_void_p * G)(*[o.h for o in objectives])
-    accepted = np.zeros(Cn, dtype=np.int32)
-    best_value = np.zeros(Cn)
-    best = np.zeros((Cn, P))
-    trace = np.zeros((Cn, max(iterations - 1, 1)), dtype=np.uint8)
-    rc = lib.host_mh_run_groups(handles, G, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning,
-                                accepted.ctypes.data, best_value.ctypes.data, best.ctypes.data, trace.ctypes.data)
-    if rc:
-        raise RuntimeError(lib.host_last_error().decode())
-    return {"accepted": accepted, "best_value": best_value, "best": best, "accept_trace": trace[:, :iterations - 1],
-            "loop_seconds": float(lib.host_last_mh_loop_seconds())}
+    a = _mh_arrays(Cn, P, iterations, keys=("accepted", "best_value", "best", "accept_trace"))
+    _check(lib.host_mh_run_groups(handles, G, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning,
+                                  *[_ptr(v) for v in a.values()]))
+    return _mh_result(a, iterations, loop_seconds=float(lib.host_last_mh_loop_seconds()))
 
 
 def reference_constructors(pb, thetas) -> dict:
@@ -611,9 +613,9 @@ def reference_constructors(pb, thetas) -> dict:
     B, P = th.shape
     values = np.empty((2, 2, B))
     back = np.empty(P)
-    if lib.host_reference_constructors(C.byref(st), "\n".join(pb.param_names).encode(), "\n".join(pb.npi_names).encode(),
-                                       sig.ctypes.data, th.ctypes.data, B, values.ctypes.data, back.ctypes.data):
-        raise RuntimeError("host_reference_constructors: " + lib.host_last_error().decode())
+    _check(lib.host_reference_constructors(C.byref(st), "\n".join(pb.param_names).encode(), "\n".join(pb.npi_names).encode(),
+                                           sig.ctypes.data, th.ctypes.data, B, values.ctypes.data, back.ctypes.data),
+           "host_reference_constructors: ")
     return {"values": values, "model_back": back}
 
 
@@ -629,8 +631,7 @@ def model_holders(ends_after, values_after, baseline, baseline_end, t) -> dict:
     buf = C.create_string_buffer(128)
     rc = lib.host_model_holders(ea.ctypes.data, va.ctypes.data, len(ea), baseline, baseline_end, tt.ctypes.data, len(tt),
                                 kap.ctypes.data, se.ctypes.data, sv.ctypes.data, C.byref(size), buf, len(buf))
-    if rc:
-        raise RuntimeError("host_model_holders: rc %d %s" % (rc, lib.host_last_error().decode()))
+    _check(rc, "host_model_holders: rc %d " % rc)
     return {"kappa": kap, "schedule_ends": se, "schedule_values": sv, "state_size": size.value, "names": buf.value.decode()}
 
 
@@ -640,9 +641,7 @@ def summary_quantiles(table, probs) -> np.ndarray:
     t = np.ascontiguousarray(table, dtype=np.float64)
     q = np.ascontiguousarray(probs, dtype=np.float64)
     out = np.empty((len(q), t.shape[1]))
-    lib.host_summary_quantiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    if lib.host_summary_quantiles(t.ctypes.data, t.shape[0], t.shape[1], q.ctypes.data, len(q), out.ctypes.data):
-        raise RuntimeError(lib.host_last_error().decode())
+    _check(lib.host_summary_quantiles(t.ctypes.data, t.shape[0], t.shape[1], q.ctypes.data, len(q), out.ctypes.data))
     return out
 
 
@@ -655,27 +654,19 @@ def metropolis_hastings_group_summaries(objectives, initial, seed: int, iteratio
     Cn, P = x0.shape
     G = len(objectives)
     W = 2 * P + 2
-    n_s = 1 + (max(iterations, 1) - 1) // max(1, thinning)
     handles = (C.c_void_p * G)(*[o.h for o in objectives])
-    records, gathered = np.zeros((Cn, W)), np.zeros((G, Cn, W))
-    samples, best_value, accepted = np.zeros((Cn, n_s, P)), np.zeros(Cn), np.zeros(Cn, dtype=np.int32)
+    out = {"records": np.zeros((Cn, W)), "gathered": np.zeros((G, Cn, W))}
+    out.update(_mh_arrays(Cn, P, iterations, thinning, keys=("samples", "best_value", "accepted")))
     used = C.c_int32(-1)
-    lib.host_mh_groups_summaries.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    rc = lib.host_mh_groups_summaries(handles, G, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning, backend,
-                                      records.ctypes.data, gathered.ctypes.data, samples.ctypes.data, best_value.ctypes.data,
-                                      accepted.ctypes.data, C.byref(used))
-    if rc:
-        raise RuntimeError(lib.host_last_error().decode())
-    return {"records": records, "gathered": gathered, "samples": samples, "best_value": best_value, "accepted": accepted,
-            "backend_used": int(used.value)}
+    _check(lib.host_mh_groups_summaries(handles, G, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning, backend,
+                                        *[_ptr(v) for v in out.values()], C.byref(used)))
+    return _mh_result(out, iterations, backend_used=int(used.value))
 
 
 def default_arith() -> int:
     """ARITH_* the reference-shaped constructors of the C++ adapters select (environment SEPAIHRD_ARITH; fma unless
     "strict").  No device needed."""
     lib = load_library()
-    lib.host_default_arith.restype = C.c_int
     return int(lib.host_default_arith())
 
 
@@ -684,8 +675,6 @@ def glibc_log(x) -> np.ndarray:
     lib = load_library()
     a = np.ascontiguousarray(x, dtype=np.float64)
     out = np.empty_like(a)
-    lib.host_glibc_log.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.host_glibc_log.restype = None
     lib.host_glibc_log(a.ctypes.data, a.size, out.ctypes.data)
     return out
 
@@ -695,8 +684,6 @@ def glibc_exp(x) -> np.ndarray:
     lib = load_library()
     a = np.ascontiguousarray(x, dtype=np.float64)
     out = np.empty_like(a)
-    lib.host_glibc_exp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.host_glibc_exp.restype = None
     lib.host_glibc_exp(a.ctypes.data, a.size, out.ctypes.data)
     return out
 
@@ -706,8 +693,8 @@ def sir_rhs(N, Cm, gamma, q, scale_C, state) -> np.ndarray:
     N, Cm, gamma, state = (np.ascontiguousarray(a, dtype=np.float64) for a in (N, Cm, gamma, state))
     out = np.empty_like(state)
     lib = load_library()
-    if lib.host_sir_rhs(len(N), N.ctypes.data, Cm.ctypes.data, gamma.ctypes.data, q, scale_C, state.ctypes.data, out.ctypes.data) != 0:
-        raise RuntimeError("host_sir_rhs: " + lib.host_last_error().decode())
+    _check(lib.host_sir_rhs(len(N), N.ctypes.data, Cm.ctypes.data, gamma.ctypes.data, q, scale_C, state.ctypes.data, out.ctypes.data),
+           "host_sir_rhs: ")
     return out
 
 
@@ -727,8 +714,7 @@ def sir_scenario_events(times, entries) -> list:
                                       params.ctypes.data, ti.ctypes.data, kind.ctypes.data, val.ctypes.data, C.byref(n))
     if rc == 1:
         raise ValueError(lib.host_last_error().decode())
-    if rc != 0:
-        raise RuntimeError(lib.host_last_error().decode())
+    _check(rc)
     return [(int(ti[e]), int(kind[e]), float(val[e])) for e in range(n.value)]
 
 
@@ -738,12 +724,10 @@ def write_sir_scenario_csvs(comparison_path, bands_path, scenario_names, times, 
     lib = load_library()
     t, pr = np.ascontiguousarray(times, dtype=np.float64), np.ascontiguousarray(probs, dtype=np.float64)
     arr = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (quantiles, metric_summary, diff_quantiles)]
-    rc = lib.host_sir_write_scenario_csvs(None if comparison_path is None else str(comparison_path).encode(),
-                                          None if bands_path is None else str(bands_path).encode(), "\n".join(scenario_names).encode(),
-                                          len(scenario_names), int(n_age), t.size, t.ctypes.data, pr.ctypes.data, pr.size,
-                                          *[None if a is None else a.ctypes.data for a in arr])
-    if rc != 0:
-        raise RuntimeError("host_sir_write_scenario_csvs: " + lib.host_last_error().decode())
+    _check(lib.host_sir_write_scenario_csvs(None if comparison_path is None else str(comparison_path).encode(),
+                                            None if bands_path is None else str(bands_path).encode(), "\n".join(scenario_names).encode(),
+                                            len(scenario_names), int(n_age), t.size, t.ctypes.data, pr.ctypes.data, pr.size,
+                                            *[None if a is None else a.ctypes.data for a in arr]), "host_sir_write_scenario_csvs: ")
 
 
 class HostSIRObjective:
@@ -762,8 +746,7 @@ class HostSIRObjective:
         sv = np.array(list(sg.values()) + [0.0])
         self.h = self.lib.host_sir_create(C.byref(st), "\n".join(names).encode(), "\n".join(sg.keys()).encode(), sv.ctypes.data,
                                           device, cache_capacity, int(with_objective))
-        if not self.h:
-            raise RuntimeError("host_sir_create failed: " + self.lib.host_last_error().decode())
+        _check(not self.h, "host_sir_create failed: ")
         self.P, self.n = len(names), pb.n
 
     def __del__(self):
@@ -776,8 +759,7 @@ class HostSIRObjective:
 
     def manager_info(self) -> dict:
         out = [np.empty(self.P) for _ in range(4)]
-        if self.lib.host_sir_manager_info(self.h, *[a.ctypes.data for a in out]) != 0:
-            raise RuntimeError("host_sir_manager_info: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_manager_info(self.h, *[a.ctypes.data for a in out]), "host_sir_manager_info: ")
         return dict(zip(("sigma", "lower", "upper", "current"), out))
 
     def index_for_param(self, name: str) -> int:
@@ -792,22 +774,19 @@ class HostSIRObjective:
     def update_model(self, theta) -> dict:
         th = np.ascontiguousarray(theta, dtype=np.float64)
         q, sc, g = C.c_double(0.0), C.c_double(0.0), np.empty(self.n)
-        if self.lib.host_sir_update_model(self.h, th.ctypes.data, C.byref(q), C.byref(sc), g.ctypes.data) != 0:
-            raise RuntimeError("host_sir_update_model: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_update_model(self.h, th.ctypes.data, C.byref(q), C.byref(sc), g.ctypes.data), "host_sir_update_model: ")
         return {"q": q.value, "scale_C_total": sc.value, "gamma": g}
 
     def calculate(self, theta) -> float:
         th = np.ascontiguousarray(theta, dtype=np.float64)
         v = C.c_double(0.0)
-        if self.lib.host_sir_calculate(self.h, th.ctypes.data, C.byref(v)) != 0:
-            raise RuntimeError("host_sir_calculate: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_calculate(self.h, th.ctypes.data, C.byref(v)), "host_sir_calculate: ")
         return v.value
 
     def calculate_batch(self, thetas):
         th = np.ascontiguousarray(thetas, dtype=np.float64)
         out, st = np.empty(len(th)), np.empty(len(th), dtype=np.int32)
-        if self.lib.host_sir_calculate_batch(self.h, th.ctypes.data, len(th), out.ctypes.data, st.ctypes.data) != 0:
-            raise RuntimeError("host_sir_calculate_batch: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_calculate_batch(self.h, th.ctypes.data, len(th), out.ctypes.data, st.ctypes.data), "host_sir_calculate_batch: ")
         return out, st
 
     def cache_stats(self) -> dict:
@@ -818,17 +797,16 @@ class HostSIRObjective:
     def hill_climbing(self, x0, seed: int, iterations: int, cloud_size_multiplier: int = 8, threads: int = 16) -> dict:
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         best, bv = np.empty(self.P), C.c_double(0.0)
-        if self.lib.host_sir_hc_run(self.h, x0.ctypes.data, seed, threads, iterations, cloud_size_multiplier, best.ctypes.data, C.byref(bv)) != 0:
-            raise RuntimeError("host_sir_hc_run: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_hc_run(self.h, x0.ctypes.data, seed, threads, iterations, cloud_size_multiplier, best.ctypes.data, C.byref(bv)),
+               "host_sir_hc_run: ")
         return {"best": best, "best_value": bv.value}
 
     def metropolis_hastings(self, initial, seed: int, iterations: int, burn_in: int = 0) -> dict:
         init = np.ascontiguousarray(initial, dtype=np.float64)
         chains = init.shape[0]
         bv, best, acc = np.empty(chains), np.empty((chains, self.P)), np.empty(chains, dtype=np.int32)
-        if self.lib.host_sir_mh_run(self.h, chains, init.ctypes.data, seed, iterations, burn_in, bv.ctypes.data, best.ctypes.data,
-                                    acc.ctypes.data) != 0:
-            raise RuntimeError("host_sir_mh_run: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_mh_run(self.h, chains, init.ctypes.data, seed, iterations, burn_in, bv.ctypes.data, best.ctypes.data,
+                                        acc.ctypes.data), "host_sir_mh_run: ")
         return {"best_value": bv, "best": best, "accepted": acc}
 
     def metropolis_hastings_ex(self, initial, seed: int, iterations: int, burn_in: int = 0, adaptation_period: int = 100,
@@ -844,30 +822,19 @@ class HostSIRObjective:
         kernel_form: hipabi.MH_FORM_*.  out_dir switches the reference's progress reports and trace files on."""
         x0 = np.ascontiguousarray(np.atleast_2d(initial), dtype=np.float64)
         Cn, P = x0.shape
-        accepted = np.zeros(Cn, dtype=np.int32)
-        best_value, final_scale = np.zeros(Cn), np.zeros(Cn)
-        best = np.zeros((Cn, P))
-        trace = np.zeros((Cn, max(iterations - 1, 1)), dtype=np.uint8) if want_trace else None
-        n_s = 1 + (max(iterations, 1) - 1) // max(1, thinning)
-        samples, values, cov = np.zeros((Cn, n_s, P)), np.zeros((Cn, n_s)), np.zeros((Cn, P, P))
+        a = _mh_arrays(Cn, P, iterations, thinning, want_trace)
+        ptrs = [_ptr(a[k]) for k in _MH_ARRAYS]
         ns, fb, drows = C.c_int32(), C.c_int(), C.c_int32()
         failures = (C.c_long * 3)()
         diag = np.zeros((P + 1, len(hipabi.DIAG_COLUMNS)))
-        rc = self.lib.host_sir_mh_run_ex(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning, reg_eps,
-                                         target_acc, int(adapt_scale), int(device_state), int(device_streams), int(two_pass_covariance),
-                                         int(adaptation_window), int(kernel_form), int(compute_diagnostics), int(report_interval),
-                                         int(checkpoint_chains), out_dir.encode() if out_dir else None,
-                                         log_path.encode() if log_path else None, accepted.ctypes.data, best_value.ctypes.data,
-                                         best.ctypes.data, final_scale.ctypes.data, trace.ctypes.data if want_trace else None,
-                                         C.byref(ns), samples.ctypes.data, values.ctypes.data, cov.ctypes.data, C.byref(fb), failures,
-                                         diag.ctypes.data, C.byref(drows))
-        if rc:
-            raise RuntimeError("host_sir_mh_run_ex: " + self.lib.host_last_error().decode())
-        assert ns.value == n_s
-        return {"accepted": accepted, "best_value": best_value, "best": best, "final_scale": final_scale,
-                "accept_trace": trace[:, :iterations - 1] if want_trace else None, "samples": samples, "sample_values": values,
-                "final_cov": cov, "loop_seconds": float(self.lib.host_last_mh_loop_seconds()), "fell_back": bool(fb.value),
-                "failures": list(failures), "diagnostics": diag[:drows.value] if drows.value else None}
+        _check(self.lib.host_sir_mh_run_ex(self.h, Cn, x0.ctypes.data, seed, iterations, burn_in, adaptation_period, thinning, reg_eps,
+                                           target_acc, int(adapt_scale), int(device_state), int(device_streams), int(two_pass_covariance),
+                                           int(adaptation_window), int(kernel_form), int(compute_diagnostics), int(report_interval),
+                                           int(checkpoint_chains), out_dir.encode() if out_dir else None,
+                                           log_path.encode() if log_path else None, *ptrs[:5], C.byref(ns), *ptrs[5:], C.byref(fb),
+                                           failures, diag.ctypes.data, C.byref(drows)), "host_sir_mh_run_ex: ")
+        return _mh_result(a, iterations, ns.value, loop_seconds=float(self.lib.host_last_mh_loop_seconds()), fell_back=bool(fb.value),
+                          failures=list(failures), diagnostics=diag[:drows.value] if drows.value else None)
 
     def calibrate(self, hc_seed: int, mh_seed: int, hc_iterations: int, mh_iterations: int, burn_in: int,
                   cloud_size_multiplier: int = 8, threads: int = 16, adaptation_period: int = 100, thinning: int = 1,
@@ -875,23 +842,9 @@ class HostSIRObjective:
         """HipModelCalibrator on the SIR objective: Hill-Climbing from the manager's current parameters -> covariance
         conditioning -> `chains` device-resident MH chains -> the objective value of every stored sample.  The dictionary of
         HostObjective.calibrate."""
-        cap = 1 + (mh_iterations - 1) // max(1, thinning)
-        out = {"best": np.empty(self.P), "phase2_cov": np.empty((self.P, self.P)),
-               "accept_trace": np.empty((chains, mh_iterations - 1), dtype=np.uint8),
-               "samples": np.empty((chains, cap, self.P)), "sample_values": np.empty((chains, cap)),
-               "mcmc_objective_values": np.empty((chains, cap))}
-        bv, iv, p1 = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        ns = C.c_int32(0)
-        rc = self.lib.host_sir_calibrate(self.h, hc_iterations, cloud_size_multiplier, threads, hc_seed, mh_iterations, burn_in,
-                                         adaptation_period, thinning, mh_seed, chains, int(kernel_form), int(device_streams),
-                                         out["best"].ctypes.data, C.byref(bv), C.byref(iv), C.byref(p1),
-                                         out["phase2_cov"].ctypes.data, out["accept_trace"].ctypes.data, out["samples"].ctypes.data,
-                                         out["sample_values"].ctypes.data, out["mcmc_objective_values"].ctypes.data, C.byref(ns))
-        if rc != 0:
-            raise RuntimeError("host_sir_calibrate: " + self.lib.host_last_error().decode())
-        assert ns.value == cap, (ns.value, cap)
-        out.update(best_value=bv.value, initial_value=iv.value, phase1_best_value=p1.value, n_samples=ns.value)
-        return out
+        return _calibration(self.lib.host_sir_calibrate, (self.h, hc_iterations, cloud_size_multiplier, threads, hc_seed, mh_iterations, burn_in,
+                                                          adaptation_period, thinning, mh_seed, chains, int(kernel_form), int(device_streams)),
+                            "host_sir_calibrate: ", self.P, chains, mh_iterations, thinning)
 
     def scenario_comparison(self, samples, scenarios, probs=(0.025, 0.05, 0.5, 0.95, 0.975), burn_in: int = 0, thinning: int = 1,
                             comparison_path: str | None = None, bands_path: str | None = None) -> dict:
@@ -911,13 +864,12 @@ class HostSIRObjective:
         ev_v = np.array([float(e[2]) for e in flat] + [0.0])
         out = {"quantiles": np.empty((K, 3, pr.size, T, n + 1)), "metrics": np.empty((K, S, W)), "metric_summary": np.empty((K, W, 2 + pr.size)),
                "diff_quantiles": np.empty((K, W, pr.size)), "status": np.empty((K, S), dtype=np.int32), "n_valid": np.empty(K, dtype=np.int32)}
-        rc = self.lib.host_sir_scenario_comparison(self.h, ps.ctypes.data, ps.shape[0], burn_in, thinning, "\n".join(names).encode(), K,
-                                                   counts.ctypes.data, ev_t.ctypes.data, "\n".join(e[1] for e in flat).encode(), ev_v.ctypes.data,
-                                                   pr.ctypes.data, pr.size, None if comparison_path is None else str(comparison_path).encode(),
-                                                   None if bands_path is None else str(bands_path).encode(),
-                                                   *[out[k].ctypes.data for k in ("quantiles", "metrics", "metric_summary", "diff_quantiles", "status", "n_valid")])
-        if rc != 0:
-            raise RuntimeError("host_sir_scenario_comparison: " + self.lib.host_last_error().decode())
+        _check(self.lib.host_sir_scenario_comparison(self.h, ps.ctypes.data, ps.shape[0], burn_in, thinning, "\n".join(names).encode(), K,
+                                                     counts.ctypes.data, ev_t.ctypes.data, "\n".join(e[1] for e in flat).encode(), ev_v.ctypes.data,
+                                                     pr.ctypes.data, pr.size, None if comparison_path is None else str(comparison_path).encode(),
+                                                     None if bands_path is None else str(bands_path).encode(),
+                                                     *[a.ctypes.data for a in out.values()]),
+               "host_sir_scenario_comparison: ")
         out["scenario_names"], out["metric_names"] = names, hipabi.sir_metric_names(n)
         return out
 
