@@ -39,7 +39,9 @@ struct sepaihrd_ctx {
     int arith = 0;
     int precision = 0;  // SEPAIHRD_PRECISION_F64 / _F32
     DevProblem dp{};
-    std::vector<void*> allocs;
+    // Everything below that owns a HIP resource releases it in its destructor; members go in reverse order of declaration, so
+    // own_stream, declared last, is drained and destroyed before any buffer it may touch is freed (sepaihrd_destroy).
+    DeviceAllocs allocs;  // the problem's tables
     // host copies needed by sepaihrd_apply_constraints
     std::vector<double> lower, upper;
     std::vector<uint8_t> has_bounds;
@@ -48,11 +50,10 @@ struct sepaihrd_ctx {
     // buffers of sepaihrd_ensemble_quantiles and sepaihrd_scenario_ensemble, kept between calls
     GrowSlots<SLOT_COUNT> ens;
     std::string last_error;
-    // staging buffers for the host-pointer entry point (grown on demand)
-    size_t cap_B = 0;
-    hipStream_t own_stream = nullptr;  // sepaihrd_eval_batch_begin / _end
+    // staging buffers for the host-pointer entry point (grown on demand), and the views ensure_staging lays into them
+    DeviceBuf theta_buf, results_buf, traj_buf;
+    PinnedBuf results_host;
     int pending_B = 0;
-    bool cap_traj = false;
     double* d_theta = nullptr;
     double* d_loglik = nullptr;
     int32_t* d_status = nullptr;
@@ -61,11 +62,9 @@ struct sepaihrd_ctx {
     double* d_parts = nullptr;
     // d_loglik .. d_parts are views into ONE allocation (results slab: [loglik B][parts 3B][status B][accepted B][rejected B]),
     // fetched with one copy into a page-locked mirror of the same layout
-    void* d_results = nullptr;
-    void* h_results = nullptr;
     double* d_traj = nullptr;
-    size_t cap_traj_elems = 0;
-    // likelihood-pass workspace (device), sized for ws_chains chains
+    // likelihood-pass workspace (device), sized for ws_chains chains: three buffers, one capacity
+    DeviceBuf ws_buf[3];
     size_t ws_chains = 0;
     double* ws_cum = nullptr;
     double* ws_rows = nullptr;
@@ -73,7 +72,7 @@ struct sepaihrd_ctx {
     size_t ws_budget_bytes = (size_t)24 << 30;  // larger batches are evaluated in chunks of chains
     // ONE evaluation in flight per context (they share the workspace above): the last launch sequence leaves an
     // event, and a launch on a different stream waits for it first (free when the stream is the same)
-    hipEvent_t busy_event = nullptr;
+    Event busy_event;
     hipStream_t busy_stream = nullptr;
     bool busy_valid = false;
     // a stream the LIBRARY owns (a sampler's) on which launches after the first record nothing: every marker between two
@@ -87,40 +86,23 @@ struct sepaihrd_ctx {
     bool timing = false;
     int timing_period = 1;     // events around every timing_period-th launch sequence only
     long timing_seen = 0;
-    std::vector<hipEvent_t> ev;  // triples: before integrator, after integrator, after likelihood pass
+    std::vector<Event> ev;  // triples: before integrator, after integrator, after likelihood pass
     size_t ev_used = 0;
     // per-chain summary records: the table of the chains this context ran, and the gathered table of all
-    double* rec_buf[2] = {nullptr, nullptr};
-    size_t rec_cap[2] = {0, 0};
+    DeviceBuf rec_buf[2];
     // sepaihrd_fd_gradient_batch (held by the context of the perturbed evaluations, grow-only): the perturbed matrix, steps
     // and perturbed values, then the staging of the call's inputs and results with a page-locked mirror of the results
-    void* fd_dev = nullptr;
-    void* fd_host = nullptr;
-    size_t fd_dev_bytes = 0, fd_host_bytes = 0;
-    hipEvent_t fd_ev_uploaded = nullptr, fd_ev_centre = nullptr;
+    DeviceBuf fd_dev;
+    PinnedBuf fd_host;
+    Event fd_ev_uploaded, fd_ev_centre;
     // the last sepaihrd_ensemble_predictive call: integrator, draws and mid-PIT counts, sorts and quantiles (ms)
     double pred_ms[3] = {0.0, 0.0, 0.0};
     // the last sepaihrd_ensemble_stochastic call: step kernel, sorts and quantiles (ms)
     double stoch_ms[2] = {0.0, 0.0};
+    Stream own_stream;  // sepaihrd_eval_batch_begin / _end; last: see above
 };
 
 namespace {
-
-template <class T>
-const T* upload(sepaihrd_ctx* ctx, const std::vector<T>& v, bool& ok) {
-    if (v.empty()) {
-        // keep a valid (1-element) allocation so kernels may form the pointer
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
-        ctx->allocs.push_back(p);
-        return static_cast<const T*>(p);
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, v.size() * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
-    ctx->allocs.push_back(p);
-    if (hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    return static_cast<const T*>(p);
-}
 
 // SEPAIHRDParameterManager.cpp:302-313
 double reflect_bound_host(double value, double minb, double maxb) {
@@ -130,15 +112,6 @@ double reflect_bound_host(double value, double minb, double maxb) {
     if (y < 0) y += 2.0 * width;
     if (y <= width) return minb + y;
     return maxb - (y - width);
-}
-
-void free_workspace(sepaihrd_ctx* c) {
-    if (c->ws_cum) (void)hipFree(c->ws_cum);
-    if (c->ws_rows) (void)hipFree(c->ws_rows);
-    if (c->ws_status) (void)hipFree(c->ws_status);
-    c->ws_cum = c->ws_rows = nullptr;
-    c->ws_status = nullptr;
-    c->ws_chains = 0;
 }
 
 // chains per launch so that the cumulative-compartment workspace stays within the budget
@@ -152,11 +125,13 @@ size_t chunk_chains(const sepaihrd_ctx* c, size_t B) {
 
 int ensure_workspace(sepaihrd_ctx* c, size_t chains) {
     if (chains <= c->ws_chains) return SEPAIHRD_OK;
-    free_workspace(c);
-    if (hipMalloc((void**)&c->ws_cum, workspace_cum_doubles(c->dp, chains) * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&c->ws_rows, workspace_rows_doubles(c->dp, chains) * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&c->ws_status, chains * sizeof(int32_t)) != hipSuccess) {
-        free_workspace(c);
+    c->ws_chains = 0;
+    for (DeviceBuf& b : c->ws_buf) b.release();  // all three before the first grows: the workspace may be most of the device
+    if (!c->ws_buf[0].get(&c->ws_cum, workspace_cum_doubles(c->dp, chains)) ||
+        !c->ws_buf[1].get(&c->ws_rows, workspace_rows_doubles(c->dp, chains)) || !c->ws_buf[2].get(&c->ws_status, chains)) {
+        for (DeviceBuf& b : c->ws_buf) b.release();
+        c->ws_cum = c->ws_rows = nullptr;
+        c->ws_status = nullptr;
         c->last_error = "likelihood workspace allocation failed";
         return SEPAIHRD_E_HIP;
     }
@@ -193,43 +168,19 @@ int fence_before(sepaihrd_ctx* c, hipStream_t st) {
 void fence_after(sepaihrd_ctx* c, hipStream_t st) {
     if (c->busy_valid && c->busy_stream == st && st == c->lazy_stream) return;  // recorded lazily (fence_before)
     if (stream_is_capturing(st)) return;
-    if (!c->busy_event && hipEventCreateWithFlags(&c->busy_event, hipEventDisableTiming) != hipSuccess) {
-        c->busy_event = nullptr;
-        return;
-    }
+    if (!c->busy_event && c->busy_event.create(hipEventDisableTiming) != hipSuccess) return;
     if (hipEventRecord(c->busy_event, st) == hipSuccess) { c->busy_stream = st; c->busy_valid = true; }
-}
-
-void free_staging(sepaihrd_ctx* c) {
-    void* ptrs[] = {c->d_theta, c->d_results, c->d_traj};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (c->h_results) (void)hipHostFree(c->h_results);
-    c->d_theta = c->d_loglik = c->d_parts = c->d_traj = nullptr;
-    c->d_status = c->d_nacc = c->d_nrej = nullptr;
-    c->d_results = c->h_results = nullptr;
-    c->cap_B = 0;
-    c->cap_traj_elems = 0;
 }
 
 constexpr size_t RESULT_BYTES_PER_CHAIN = 4 * sizeof(double) + 3 * sizeof(int32_t);
 
-// Staging of the host-pointer entry points for B chains (keeps a trajectory buffer that is already there).  The result
+// Staging of the host-pointer entry points for B chains (the trajectory buffer is sepaihrd_eval_batch's and stays).  The result
 // views are laid out for THIS batch at the front of the slab, so that one copy fetches them whatever the capacity.
 int ensure_staging(sepaihrd_ctx* ctx, size_t B) {
-    if (B > ctx->cap_B) {
-        const size_t keep_traj = ctx->cap_traj_elems;
-        double* keep = ctx->d_traj;
-        ctx->d_traj = nullptr;
-        free_staging(ctx);
-        ctx->d_traj = keep;
-        ctx->cap_traj_elems = keep_traj;
-        HIP_TRY(hipMalloc((void**)&ctx->d_theta, B * ctx->P * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
-        HIP_TRY(hipMalloc(&ctx->d_results, B * RESULT_BYTES_PER_CHAIN), ctx, return SEPAIHRD_E_HIP);
-        HIP_TRY(hipHostMalloc(&ctx->h_results, B * RESULT_BYTES_PER_CHAIN, hipHostMallocDefault), ctx, return SEPAIHRD_E_HIP);
-        ctx->cap_B = B;
-    }
-    ctx->d_loglik = static_cast<double*>(ctx->d_results);
+    ALLOC_TRY(ctx->theta_buf.get(&ctx->d_theta, B * ctx->P), ctx, return SEPAIHRD_E_HIP);
+    ALLOC_TRY(ctx->results_buf.reserve(B * RESULT_BYTES_PER_CHAIN), ctx, return SEPAIHRD_E_HIP);
+    ALLOC_TRY(ctx->results_host.reserve(B * RESULT_BYTES_PER_CHAIN), ctx, return SEPAIHRD_E_HIP);
+    ctx->d_loglik = ctx->results_buf.as<double>();
     ctx->d_parts = ctx->d_loglik + B;
     ctx->d_status = reinterpret_cast<int32_t*>(ctx->d_parts + 3 * B);
     ctx->d_nacc = ctx->d_status + B;
@@ -242,7 +193,7 @@ int ensure_staging(sepaihrd_ctx* ctx, size_t B) {
 int fetch_results(sepaihrd_ctx* ctx, hipStream_t st, int B, double* loglik, int32_t* status, int32_t* n_accept, int32_t* n_reject,
                   double* ll_parts) {
     const size_t n = (size_t)B;
-    char* const h = static_cast<char*>(ctx->h_results);
+    char* const h = ctx->results_host.as<char>();
     const size_t off_parts = n * sizeof(double), off_status = 4 * n * sizeof(double);
     const size_t off_nacc = off_status + n * sizeof(int32_t), off_nrej = off_nacc + n * sizeof(int32_t);
     size_t hi = n * sizeof(double);  // the log-likelihoods, always
@@ -250,7 +201,7 @@ int fetch_results(sepaihrd_ctx* ctx, hipStream_t st, int B, double* loglik, int3
     if (status) hi = off_nacc;
     if (n_accept) hi = off_nrej;
     if (n_reject) hi = off_nrej + n * sizeof(int32_t);
-    HIP_TRY(hipMemcpyAsync(h, ctx->d_results, hi, hipMemcpyDeviceToHost, st), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpyAsync(h, ctx->results_buf.p, hi, hipMemcpyDeviceToHost, st), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(st), ctx, return SEPAIHRD_E_HIP);
     if (loglik) std::memcpy(loglik, h, n * sizeof(double));
     if (ll_parts) std::memcpy(ll_parts, h + off_parts, n * 3 * sizeof(double));
@@ -509,25 +460,25 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
     d.abs_tol = pb->abs_err; d.rel_tol = pb->rel_err; d.dt_hint = pb->dt_hint; d.max_gap = max_gap;
 
     bool ok = true;
-    d.times = upload(ctx, std::vector<double>(pb->times, pb->times + T), ok);
-    d.grid = upload(ctx, grid, ok);
-    d.lower = upload(ctx, ctx->lower, ok);
-    d.upper = upload(ctx, ctx->upper, ok);
-    d.has_bounds = upload(ctx, hb, ok);
-    d.src_scalar = upload(ctx, src_scalar, ok);
-    d.base_scalar = upload(ctx, base_scalar, ok);
-    d.src_vec = upload(ctx, src_vec, ok);
-    d.base_vec = upload(ctx, base_vec, ok);
-    d.N = upload(ctx, Npad, ok);
-    d.age_fraction = upload(ctx, fracpad, ok);
-    d.Mrow = upload(ctx, Mrow, ok);
-    d.init_state = upload(ctx, init, ok);
-    d.beta_ends = upload(ctx, std::vector<double>(pb->beta_end_times, pb->beta_end_times + nb), ok);
-    d.kappa_ends = upload(ctx, std::vector<double>(pb->kappa_end_times, pb->kappa_end_times + nk), ok);
+    d.times = upload(ctx->allocs, std::vector<double>(pb->times, pb->times + T), ok);
+    d.grid = upload(ctx->allocs, grid, ok);
+    d.lower = upload(ctx->allocs, ctx->lower, ok);
+    d.upper = upload(ctx->allocs, ctx->upper, ok);
+    d.has_bounds = upload(ctx->allocs, hb, ok);
+    d.src_scalar = upload(ctx->allocs, src_scalar, ok);
+    d.base_scalar = upload(ctx->allocs, base_scalar, ok);
+    d.src_vec = upload(ctx->allocs, src_vec, ok);
+    d.base_vec = upload(ctx->allocs, base_vec, ok);
+    d.N = upload(ctx->allocs, Npad, ok);
+    d.age_fraction = upload(ctx->allocs, fracpad, ok);
+    d.Mrow = upload(ctx->allocs, Mrow, ok);
+    d.init_state = upload(ctx->allocs, init, ok);
+    d.beta_ends = upload(ctx->allocs, std::vector<double>(pb->beta_end_times, pb->beta_end_times + nb), ok);
+    d.kappa_ends = upload(ctx->allocs, std::vector<double>(pb->kappa_end_times, pb->kappa_end_times + nk), ok);
     d.nm = nm; d.nm_pad = (int)mends.size();
-    d.mends = upload(ctx, mends, ok);
-    d.seg_ib = upload(ctx, seg_ib, ok);
-    d.seg_ik = upload(ctx, seg_ik, ok);
+    d.mends = upload(ctx->allocs, mends, ok);
+    d.seg_ib = upload(ctx->allocs, seg_ib, ok);
+    d.seg_ik = upload(ctx->allocs, seg_ik, ok);
     if (!ok) {
         set_err(err, errlen, "device allocation / upload failed");
         sepaihrd_destroy(ctx);
@@ -543,19 +494,7 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
 
 void sepaihrd_destroy(sepaihrd_ctx* ctx) {
     if (!ctx) return;
-    for (double* b : ctx->rec_buf) if (b) { (void)hipSetDevice(ctx->device); (void)hipFree(b); }
     (void)hipSetDevice(ctx->device);
-    if (ctx->own_stream) { (void)hipStreamSynchronize(ctx->own_stream); (void)hipStreamDestroy(ctx->own_stream); }
-    free_staging(ctx);
-    free_workspace(ctx);
-    ctx->ens.release();
-    for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
-    if (ctx->busy_event) (void)hipEventDestroy(ctx->busy_event);
-    if (ctx->fd_dev) (void)hipFree(ctx->fd_dev);
-    if (ctx->fd_host) (void)hipHostFree(ctx->fd_host);
-    for (hipEvent_t e : {ctx->fd_ev_uploaded, ctx->fd_ev_centre})
-        if (e) (void)hipEventDestroy(e);
-    for (void* p : ctx->allocs) (void)hipFree(p);
     delete ctx;
 }
 
@@ -624,9 +563,9 @@ int sepaihrd_eval_batch_device(sepaihrd_ctx* ctx, const double* d_theta, int B, 
         hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
         if (ctx->timing && (ctx->timing_seen++ % ctx->timing_period) == 0) {
             while (ctx->ev.size() < ctx->ev_used + 3) {
-                hipEvent_t e;
+                Event e;
                 HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
-                ctx->ev.push_back(e);
+                ctx->ev.push_back(std::move(e));
             }
             e0 = ctx->ev[ctx->ev_used]; e1 = ctx->ev[ctx->ev_used + 1]; e2 = ctx->ev[ctx->ev_used + 2];
             ctx->ev_used += 3;
@@ -699,13 +638,7 @@ int sepaihrd_eval_batch(sepaihrd_ctx* ctx, const double* theta, int B, double* l
         const int rc = ensure_staging(ctx, (size_t)B);
         if (rc != SEPAIHRD_OK) return rc;
     }
-    if (traj_elems > ctx->cap_traj_elems) {
-        if (ctx->d_traj) (void)hipFree(ctx->d_traj);
-        ctx->d_traj = nullptr;
-        ctx->cap_traj_elems = 0;
-        HIP_TRY(hipMalloc((void**)&ctx->d_traj, traj_elems * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
-        ctx->cap_traj_elems = traj_elems;
-    }
+    ALLOC_TRY(ctx->traj_buf.get(&ctx->d_traj, traj_elems), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(ctx->d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx,
             return SEPAIHRD_E_HIP);
     const int rc = sepaihrd_eval_batch_device(ctx, ctx->d_theta, B, ctx->d_loglik, ctx->d_status, ctx->d_nacc,
@@ -787,23 +720,13 @@ int sepaihrd_fd_gradient_batch(sepaihrd_ctx* cc, sepaihrd_ctx* pc, const double*
     const size_t i32 = nC /* status */ + nC * P /* plus_status */ + nC /* centre_status */ + nC /* rows */;
     const size_t need = dbl * sizeof(double) + i32 * sizeof(int32_t);
     const size_t result_bytes = (nC + GP) * sizeof(double) + nC * sizeof(int32_t);
-    if (need > pc->fd_dev_bytes) {  // not stream-ordered: before anything is queued
-        if (pc->fd_dev) (void)hipFree(pc->fd_dev);
-        pc->fd_dev = nullptr; pc->fd_dev_bytes = 0;
-        HIP_TRY(hipMalloc(&pc->fd_dev, need), pc, return SEPAIHRD_E_HIP);
-        pc->fd_dev_bytes = need;
-    }
+    ALLOC_TRY(pc->fd_dev.reserve(need), pc, return SEPAIHRD_E_HIP);  // not stream-ordered: before anything is queued
     const size_t host_need = (nC + nC * P) * sizeof(double) + nC * sizeof(int32_t);
-    if (host_need > pc->fd_host_bytes) {
-        if (pc->fd_host) (void)hipHostFree(pc->fd_host);
-        pc->fd_host = nullptr; pc->fd_host_bytes = 0;
-        HIP_TRY(hipHostMalloc(&pc->fd_host, host_need, hipHostMallocDefault), pc, return SEPAIHRD_E_HIP);
-        pc->fd_host_bytes = host_need;
-    }
+    ALLOC_TRY(pc->fd_host.reserve(host_need), pc, return SEPAIHRD_E_HIP);
     if (sepaihrd_reserve(cc, C) != SEPAIHRD_OK) return bad(cc->last_error.c_str(), SEPAIHRD_E_HIP);
     if (G > 0 && sepaihrd_reserve(pc, (int)GP) != SEPAIHRD_OK) return SEPAIHRD_E_HIP;
     // carve; the results [value C][grad G P][status C] are contiguous: one copy home
-    double* d_plus = static_cast<double*>(pc->fd_dev);
+    double* d_plus = pc->fd_dev.as<double>();
     double* d_eps = d_plus + nC * P * P;
     double* d_fplus = d_eps + nC * P;
     double* d_theta = d_fplus + nC * P;
@@ -839,9 +762,9 @@ int sepaihrd_fd_gradient_batch(sepaihrd_ctx* cc, sepaihrd_ctx* pc, const double*
     qa.value = d_value; qa.centre_status = d_cstatus; qa.init_state = pc->dp.init_state; qa.N = pc->dp.N;
     qa.grad = d_grad; qa.status = d_status;
     if (launch_fd_quotient(qa, sp) != 0) return bad("quotient launch failed", SEPAIHRD_E_HIP);
-    HIP_TRY(hipMemcpyAsync(pc->fd_host, d_value, result_bytes, hipMemcpyDeviceToHost, sp), pc, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpyAsync(pc->fd_host.p, d_value, result_bytes, hipMemcpyDeviceToHost, sp), pc, return SEPAIHRD_E_HIP);
     HIP_TRY(hipStreamSynchronize(sp), pc, return SEPAIHRD_E_HIP);
-    const char* h = static_cast<const char*>(pc->fd_host);
+    const char* h = pc->fd_host.as<char>();
     std::memcpy(value, h, nC * sizeof(double));
     const double* hg = reinterpret_cast<const double*>(h) + nC;
     for (size_t g = 0; g < G; ++g) std::memcpy(grad + (size_t)rows[g] * P, hg + g * P, P * sizeof(double));
@@ -1000,7 +923,7 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
         !sc.alloc(&d_scratch, n_scratch) || !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_pit, cells) ||
         !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
-    for (hipEvent_t& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     // uploads
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
@@ -1100,7 +1023,7 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
         !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_traj, n_traj) ||
         !sc.alloc(&d_final, n_final) || !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)S) || !sc.alloc(&d_extinct, (size_t)S))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
-    for (hipEvent_t& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     // uploads
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
@@ -1357,23 +1280,22 @@ struct sepaihrd_mh {
     bool packed = false;                     // ... resolved: the per-iteration kernels run in the packed form
     SamplerState st{};
     int rows = 0;  // history rows written so far
-    hipStream_t stream = nullptr;  // own non-blocking stream: several samplers (one per host thread) overlap
+    // Owners release in reverse order of declaration: the three streams, declared last, are drained and destroyed before the
+    // events, and those before the buffers.  st's pointers, and the d_ / h_ pointers below, are views of these two:
+    DeviceAllocs allocs;  // what the sampler allocates once (sepaihrd_mh_create, sepaihrd_mh_keep_scale_on_device)
+    PinnedAllocs pinned;
     double* d_z = nullptr;
     double* d_scale = nullptr;
     double* d_loglik = nullptr;
     int32_t* d_status = nullptr;
     uint8_t* d_accept = nullptr;
     uint8_t* d_draw_todo = nullptr;  // [C] chains the windowed draw of the packed form left to the block-per-chain kernel
-    int32_t* d_rows = nullptr;
-    double* d_gather = nullptr;
-    size_t gather_cap = 0;
     // sepaihrd_mh_stage_normals / sepaihrd_mh_step: a second normals buffer filled by a copy stream while the
     // evaluation runs, and ONE packed upload per iteration (accept flags, scales, re-drawn rows) from pinned memory
     double* d_z_stage = nullptr;
     double* d_lz = nullptr;          // [2][C][P] L z of both continuations, formed beside the evaluation (sampler_lz)
     bool lz_ready = false;           // d_lz holds the products of the normals staged for the coming test
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_staged = nullptr;
+    Event ev_staged;
     bool staged = false;
     double* h_stage[2] = {nullptr, nullptr};  // pinned [C][P] each: the caller fills one while the other's copy may still run
     int stage_turn = 0;
@@ -1389,7 +1311,7 @@ struct sepaihrd_mh {
     double* d_scale_sel = nullptr;
     void* d_test_out = nullptr;
     void* h_test_out = nullptr;
-    hipEvent_t ev_test_up = nullptr, ev_tested = nullptr, ev_fetched = nullptr, ev_proposed = nullptr;
+    Event ev_test_up, ev_tested, ev_fetched, ev_proposed;
     hipEvent_t ev_last_proposed = nullptr;  // whichever of the two marks the end of the last proposal
     bool values_set = false, test_pending = false, proposed_once = false;
     uint8_t* d_pack = nullptr;
@@ -1398,32 +1320,35 @@ struct sepaihrd_mh {
     // gamma, in the order they were asked for.  Uploaded as [rows n int32 | gammas n doubles] from a page-locked buffer.
     std::vector<int32_t> pending_row;
     std::vector<double> pending_gamma;
-    void* d_r1 = nullptr;
-    void* h_r1 = nullptr;
-    size_t r1_cap = 0;
-    hipEvent_t ev_r1 = nullptr;  // the last upload out of h_r1 has been copied
+    DeviceBuf d_r1;
+    PinnedBuf h_r1;
+    size_t r1_cap = 0;  // entries: both are laid out [gammas r1_cap | rows r1_cap]
+    Event ev_r1;  // the last upload out of h_r1 has been copied
     bool r1_in_flight = false;
     // states [mom_rows, rows) have not entered the running sums yet (see mh_moments_catchup_kernel)
     int mom_rows = 0;
     bool device_rng = false;  // the chains' mt19937 streams live on the device (sepaihrd_mh_seed_streams)
     // a self-contained sampler lets its caller queue iterations ahead: at most ~128 of them (an event every 32 steps, four kept)
-    hipEvent_t ev_ahead[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev_ahead[4];
     bool ev_ahead_used[4] = {false, false, false, false};
     long auto_steps = 0;
     int covariance_mode = SEPAIHRD_MH_COV_RUNNING;
     int iterations = 0;
     double* d_summary = nullptr;
     // sepaihrd_mh_snapshot_begin / _end: a gather on the sampler's stream, the copy home on a stream of its own
-    hipStream_t snap_stream = nullptr;
-    hipEvent_t ev_snap_gathered = nullptr, ev_snap_done = nullptr;
-    double* d_snap = nullptr;
-    double* h_snap = nullptr;   // page-locked
+    Event ev_snap_gathered, ev_snap_done;
+    DeviceBuf snap_dev, snap_chains_dev;
+    PinnedBuf snap_host;
+    double* d_snap = nullptr;   // views of the three, which grow with what is asked for; snap_dev and snap_host share snap_cap
+    double* h_snap = nullptr;
     int32_t* d_snap_chains = nullptr;
     size_t snap_cap = 0, snap_chain_cap = 0;
     int snap_n = 0, snap_count = 0;
     bool snap_pending = false;
     std::vector<int32_t> snap_chain_list;  // what d_snap_chains holds
-    std::vector<void*> allocs;
+    Stream snap_stream;
+    Stream copy_stream;
+    Stream stream;  // own non-blocking stream: several samplers (one per host thread) overlap
 };
 
 namespace {
@@ -1445,22 +1370,18 @@ int mh_flush_rank1(sepaihrd_mh* mh) {
     }
     if (n > mh->r1_cap) {
         const size_t cap = std::max<size_t>(2 * n, 256);
-        if (mh->d_r1) (void)hipFree(mh->d_r1);
-        if (mh->h_r1) (void)hipHostFree(mh->h_r1);
-        mh->d_r1 = mh->h_r1 = nullptr;
         mh->r1_cap = 0;
-        if (hipMalloc(&mh->d_r1, cap * (sizeof(double) + sizeof(int32_t))) != hipSuccess) return -3;
-        if (hipHostMalloc(&mh->h_r1, cap * (sizeof(double) + sizeof(int32_t)), hipHostMallocDefault) != hipSuccess) return -3;
+        if (!mh->d_r1.reserve(cap * (sizeof(double) + sizeof(int32_t))) || !mh->h_r1.reserve(cap * (sizeof(double) + sizeof(int32_t)))) return -3;
         mh->r1_cap = cap;
     }
     // [gammas cap doubles | rows cap int32]: both aligned whatever n
-    std::memcpy(mh->h_r1, mh->pending_gamma.data(), n * sizeof(double));
-    std::memcpy(static_cast<char*>(mh->h_r1) + mh->r1_cap * sizeof(double), mh->pending_row.data(), n * sizeof(int32_t));
-    if (hipMemcpyAsync(mh->d_r1, mh->h_r1, mh->r1_cap * sizeof(double) + n * sizeof(int32_t), hipMemcpyHostToDevice, mh->stream) != hipSuccess) return -3;
+    std::memcpy(mh->h_r1.p, mh->pending_gamma.data(), n * sizeof(double));
+    std::memcpy(mh->h_r1.as<char>() + mh->r1_cap * sizeof(double), mh->pending_row.data(), n * sizeof(int32_t));
+    if (hipMemcpyAsync(mh->d_r1.p, mh->h_r1.p, mh->r1_cap * sizeof(double) + n * sizeof(int32_t), hipMemcpyHostToDevice, mh->stream) != hipSuccess) return -3;
     if (hipEventRecord(mh->ev_r1, mh->stream) != hipSuccess) return -3;
     mh->r1_in_flight = true;
-    const int rc = sampler_rank1_catchup(mh->st, reinterpret_cast<const int32_t*>(static_cast<char*>(mh->d_r1) + mh->r1_cap * sizeof(double)),
-                                         static_cast<const double*>(mh->d_r1), (int)n, mh->stream);
+    const int rc = sampler_rank1_catchup(mh->st, reinterpret_cast<const int32_t*>(mh->d_r1.as<char>() + mh->r1_cap * sizeof(double)),
+                                         mh->d_r1.as<double>(), (int)n, mh->stream);
     mh->pending_gamma.clear();
     mh->pending_row.clear();
     return rc;
@@ -1605,11 +1526,7 @@ sepaihrd_mh* sepaihrd::mh_create_on(const MhBackend& be, const sepaihrd_mh_confi
     mh->covariance_mode = cfg->covariance_mode;
     mh->iterations = cfg->iterations;
     bool ok = true;
-    auto dalloc = [&](void** p, size_t bytes) {
-        if (!ok) return;
-        if (hipMalloc(p, bytes) != hipSuccess) { ok = false; return; }
-        mh->allocs.push_back(*p);
-    };
+    auto dalloc = [&](void** p, size_t bytes) { ok = ok && mh->allocs.bytes(p, bytes); };
     dalloc((void**)&st.x, CP * sizeof(double));
     dalloc((void**)&st.prop, CP * sizeof(double));
     dalloc((void**)&st.cov, CPP * sizeof(double));
@@ -1647,12 +1564,9 @@ sepaihrd_mh* sepaihrd::mh_create_on(const MhBackend& be, const sepaihrd_mh_confi
         mh->off_rows = up8(mh->off_chain + (size_t)C * sizeof(int32_t));
         mh->pack_bytes = mh->off_rows + CP * sizeof(double);
         dalloc((void**)&mh->d_pack, mh->pack_bytes);
-        if (ok && hipHostMalloc((void**)&mh->h_pack, mh->pack_bytes, hipHostMallocDefault) != hipSuccess) { mh->h_pack = nullptr; ok = false; }
-        if (ok && hipHostMalloc(&mh->h_fetch, (size_t)C * (sizeof(double) + sizeof(int32_t)), hipHostMallocDefault) != hipSuccess) { mh->h_fetch = nullptr; ok = false; }
-        if (ok && hipHostMalloc((void**)&mh->h_test, (3 * (size_t)C + CP) * sizeof(double), hipHostMallocDefault) != hipSuccess) { mh->h_test = nullptr; ok = false; }
-        if (ok && hipHostMalloc(&mh->h_test_out, (size_t)C * (sizeof(double) + 1), hipHostMallocDefault) != hipSuccess) { mh->h_test_out = nullptr; ok = false; }
-        for (int b = 0; b < 2; ++b)
-            if (ok && hipHostMalloc((void**)&mh->h_stage[b], CP * sizeof(double), hipHostMallocDefault) != hipSuccess) { mh->h_stage[b] = nullptr; ok = false; }
+        ok = ok && mh->pinned.alloc(&mh->h_pack, mh->pack_bytes) && mh->pinned.bytes(&mh->h_fetch, (size_t)C * (sizeof(double) + sizeof(int32_t))) &&
+             mh->pinned.alloc(&mh->h_test, 3 * (size_t)C + CP) && mh->pinned.bytes(&mh->h_test_out, (size_t)C * (sizeof(double) + 1)) &&
+             mh->pinned.alloc(&mh->h_stage[0], CP) && mh->pinned.alloc(&mh->h_stage[1], CP);
     }
     if (ok && (ctx->sep ? sepaihrd_reserve(ctx->sep, C) : sepaihrd_sir_reserve(ctx->sir, C)) != SEPAIHRD_OK) ok = false;
     if (ok && hipStreamCreateWithFlags(&mh->stream, hipStreamNonBlocking) != hipSuccess) ok = false;
@@ -1679,16 +1593,6 @@ sepaihrd_mh* sepaihrd::mh_create_on(const MhBackend& be, const sepaihrd_mh_confi
                  hipStreamSynchronize(mh->stream) == hipSuccess;
     if (!ok) {
         ctx->last_error = "mh_create: device allocation or initialisation failed";
-        for (void* p : mh->allocs) (void)hipFree(p);
-        if (mh->h_pack) (void)hipHostFree(mh->h_pack);
-        if (mh->h_fetch) (void)hipHostFree(mh->h_fetch);
-        if (mh->h_test) (void)hipHostFree(mh->h_test);
-        if (mh->h_test_out) (void)hipHostFree(mh->h_test_out);
-        for (double* b : mh->h_stage) if (b) (void)hipHostFree(b);
-        if (mh->ev_staged) (void)hipEventDestroy(mh->ev_staged);
-        for (hipEvent_t e : {mh->ev_test_up, mh->ev_tested, mh->ev_fetched, mh->ev_proposed, mh->ev_r1}) if (e) (void)hipEventDestroy(e);
-        if (mh->copy_stream) (void)hipStreamDestroy(mh->copy_stream);
-        if (mh->stream) (void)hipStreamDestroy(mh->stream);
         delete mh;
         return nullptr;
     }
@@ -1726,33 +1630,14 @@ int sepaihrd_mh_get_kernel_form(const sepaihrd_mh* mh) {
 void sepaihrd_mh_destroy(sepaihrd_mh* mh) {
     if (!mh) return;
     (void)hipSetDevice(mh->ctx->device);
-    if (mh->copy_stream) { (void)hipStreamSynchronize(mh->copy_stream); (void)hipStreamDestroy(mh->copy_stream); }
+    if (mh->copy_stream) (void)hipStreamSynchronize(mh->copy_stream);
     if (mh->stream) {
         (void)hipStreamSynchronize(mh->stream);
-        if (sepaihrd_ctx* ctx = mh->ctx->sep) {
+        if (sepaihrd_ctx* ctx = mh->ctx->sep) {  // the context forgets the stream before it is destroyed
             if (ctx->lazy_stream == mh->stream) ctx->lazy_stream = nullptr;
             if (ctx->busy_stream == mh->stream) { ctx->busy_valid = false; ctx->busy_stream = nullptr; }  // all of it is done
         }
-        (void)hipStreamDestroy(mh->stream);
     }
-    if (mh->ev_staged) (void)hipEventDestroy(mh->ev_staged);
-    for (hipEvent_t e : {mh->ev_test_up, mh->ev_tested, mh->ev_fetched, mh->ev_proposed, mh->ev_r1}) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : mh->ev_ahead) if (e) (void)hipEventDestroy(e);
-    if (mh->h_pack) (void)hipHostFree(mh->h_pack);
-    if (mh->h_fetch) (void)hipHostFree(mh->h_fetch);
-    if (mh->h_test) (void)hipHostFree(mh->h_test);
-    if (mh->h_test_out) (void)hipHostFree(mh->h_test_out);
-    for (double* b : mh->h_stage) if (b) (void)hipHostFree(b);
-    for (void* p : mh->allocs) (void)hipFree(p);
-    if (mh->snap_stream) { (void)hipStreamSynchronize(mh->snap_stream); (void)hipStreamDestroy(mh->snap_stream); }
-    for (hipEvent_t e : {mh->ev_snap_gathered, mh->ev_snap_done}) if (e) (void)hipEventDestroy(e);
-    if (mh->d_snap) (void)hipFree(mh->d_snap);
-    if (mh->h_snap) (void)hipHostFree(mh->h_snap);
-    if (mh->d_snap_chains) (void)hipFree(mh->d_snap_chains);
-    if (mh->d_rows) (void)hipFree(mh->d_rows);
-    if (mh->d_gather) (void)hipFree(mh->d_gather);
-    if (mh->d_r1) (void)hipFree(mh->d_r1);
-    if (mh->h_r1) (void)hipHostFree(mh->h_r1);
     delete mh;
 }
 
@@ -1874,12 +1759,12 @@ int sepaihrd::device_libm_check(int device, std::string& last_error, int& log_di
     if (ctx->libm_log_diff < 0) {
         HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
         const int N = sampler_libm_check_count();
+        DeviceBuf buf;
         double* d_out = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_out, 4 * (size_t)N * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
+        ALLOC_TRY(buf.get(&d_out, 4 * (size_t)N), ctx, return SEPAIHRD_E_HIP);
         std::vector<double> h(4 * (size_t)N);
         const bool ok = sampler_libm_check_values(d_out, nullptr) == 0 &&
                         hipMemcpy(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(d_out);
         if (!ok) { ctx->last_error = "device_libm_check: launch or copy failed"; return SEPAIHRD_E_HIP; }
         int dl = 0, de = 0;
         for (int i = 0; i < N; ++i) {
@@ -1922,12 +1807,12 @@ int sepaihrd_device_log_values(sepaihrd_ctx* ctx, const double* x, int32_t n, do
     if (!ctx || n < 0 || (n > 0 && (!x || !out))) return SEPAIHRD_E_INVALID_ARG;
     if (n == 0) return SEPAIHRD_OK;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    DeviceBuf buf;
     double* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, 2 * (size_t)n * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
+    ALLOC_TRY(buf.get(&d, 2 * (size_t)n), ctx, return SEPAIHRD_E_HIP);
     const bool ok = hipMemcpy(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
                     poisson_log_values(d, n, d + n, nullptr) == 0 &&
                     hipMemcpy(out, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d);
     if (!ok) { ctx->last_error = "device_log_values: launch or copy failed"; return SEPAIHRD_E_HIP; }
     return SEPAIHRD_OK;
 }
@@ -1987,10 +1872,7 @@ int sepaihrd_mh_keep_scale_on_device(sepaihrd_mh* mh, int adapt_scale, double ta
         }
     }
     auto dalloc = [&](void** p, size_t bytes) -> bool {
-        if (*p) return true;
-        if (hipMalloc(p, bytes) != hipSuccess) return false;
-        mh->allocs.push_back(*p);
-        return true;
+        return *p != nullptr || mh->allocs.bytes(p, bytes);  // each array once, never again
     };
     bool ok = dalloc((void**)&st.log_scale, C * sizeof(double)) && dalloc((void**)&st.scale, C * sizeof(double)) &&
               dalloc((void**)&st.recent, C * 1000) && dalloc((void**)&st.recent_meta, C * 4 * sizeof(int32_t));
@@ -2053,20 +1935,15 @@ int sepaihrd_mh_snapshot_begin(sepaihrd_mh* mh, const int32_t* chains, int n, in
     }
     const size_t width = 4 + (size_t)count * ((size_t)P + 1), need = (size_t)n * width;
     if (need > mh->snap_cap) {  // the previous snapshot has been collected: nothing reads the old buffers any more
-        if (mh->d_snap) (void)hipFree(mh->d_snap);
-        if (mh->h_snap) (void)hipHostFree(mh->h_snap);
-        mh->d_snap = mh->h_snap = nullptr;
         mh->snap_cap = 0;
-        HIP_TRY(hipMalloc((void**)&mh->d_snap, need * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
-        HIP_TRY(hipHostMalloc((void**)&mh->h_snap, need * sizeof(double), hipHostMallocDefault), ctx, return SEPAIHRD_E_HIP);
+        ALLOC_TRY(mh->snap_dev.get(&mh->d_snap, need), ctx, return SEPAIHRD_E_HIP);
+        ALLOC_TRY(mh->snap_host.get(&mh->h_snap, need), ctx, return SEPAIHRD_E_HIP);
         mh->snap_cap = need;
     }
     if ((size_t)n > mh->snap_chain_cap) {
-        if (mh->d_snap_chains) (void)hipFree(mh->d_snap_chains);
-        mh->d_snap_chains = nullptr;
         mh->snap_chain_cap = 0;
         mh->snap_chain_list.clear();
-        HIP_TRY(hipMalloc((void**)&mh->d_snap_chains, (size_t)n * sizeof(int32_t)), ctx, return SEPAIHRD_E_HIP);
+        ALLOC_TRY(mh->snap_chains_dev.get(&mh->d_snap_chains, (size_t)n), ctx, return SEPAIHRD_E_HIP);
         mh->snap_chain_cap = (size_t)n;
     }
     // the chain list is uploaded when it changes (every report of a run names the same chains): a blocking copy once, none after
@@ -2430,9 +2307,9 @@ int sepaihrd_chain_diagnostics(sepaihrd_ctx* ctx, const double* samples, const d
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     if (!ctx->own_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking), ctx, return SEPAIHRD_E_HIP);
     const size_t CN = (size_t)C * N;
+    DeviceBuf buf;
     double* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, CN * ((size_t)P + (values ? 1 : 0)) * sizeof(double)), ctx, return SEPAIHRD_E_HIP);
-    struct Free { double* p; ~Free() { (void)hipFree(p); } } guard{d};
+    ALLOC_TRY(buf.get(&d, CN * ((size_t)P + (values ? 1 : 0))), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpyAsync(d, samples, CN * P * sizeof(double), hipMemcpyHostToDevice, ctx->own_stream), ctx, return SEPAIHRD_E_HIP);
     if (values)
         HIP_TRY(hipMemcpyAsync(d + CN * P, values, CN * sizeof(double), hipMemcpyHostToDevice, ctx->own_stream), ctx, return SEPAIHRD_E_HIP);
@@ -2544,24 +2421,18 @@ int sepaihrd_mh_read_covariance(sepaihrd_mh* mh, double* cov) {
 // records are staged through the host.
 double* sepaihrd_records_buffer(sepaihrd_ctx* ctx, int which, size_t doubles) {
     if (!ctx || which < 0 || which > 1) return nullptr;
-    if (doubles > ctx->rec_cap[which]) {
+    DeviceBuf& buf = ctx->rec_buf[which];
+    if (doubles * sizeof(double) > buf.cap) {
         if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
-        if (ctx->rec_buf[which]) (void)hipFree(ctx->rec_buf[which]);
-        ctx->rec_buf[which] = nullptr;
-        ctx->rec_cap[which] = 0;
-        if (hipMalloc((void**)&ctx->rec_buf[which], doubles * sizeof(double)) != hipSuccess) {
-            ctx->last_error = "records_buffer: device allocation failed";
-            return nullptr;
-        }
-        ctx->rec_cap[which] = doubles;
+        if (!buf.reserve(doubles * sizeof(double))) ctx->last_error = "records_buffer: device allocation failed";
     }
-    return ctx->rec_buf[which];
+    return buf.as<double>();
 }
 
 int sepaihrd_read_records(sepaihrd_ctx* ctx, int which, double* out, size_t doubles) {
-    if (!ctx || which < 0 || which > 1 || !out || doubles > ctx->rec_cap[which]) return SEPAIHRD_E_INVALID_ARG;
+    if (!ctx || which < 0 || which > 1 || !out || doubles * sizeof(double) > ctx->rec_buf[which].cap) return SEPAIHRD_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
-    HIP_TRY(hipMemcpy(out, ctx->rec_buf[which], doubles * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(out, ctx->rec_buf[which].p, doubles * sizeof(double), hipMemcpyDeviceToHost), ctx, return SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 
@@ -2569,7 +2440,7 @@ int sepaihrd_write_records(sepaihrd_ctx* ctx, int which, const double* in, size_
     if (!ctx || which < 0 || which > 1 || !in) return SEPAIHRD_E_INVALID_ARG;
     if (!sepaihrd_records_buffer(ctx, which, doubles)) return SEPAIHRD_E_HIP;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
-    HIP_TRY(hipMemcpy(ctx->rec_buf[which], in, doubles * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(ctx->rec_buf[which].p, in, doubles * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 
@@ -2618,7 +2489,7 @@ int sepaihrd_allgather_records(sepaihrd_ctx* const* ctxs, int n, const int32_t* 
     int max_rows = 0;
     for (int k = 0; k < n; ++k) { total += (size_t)rows[k]; max_rows = std::max(max_rows, (int)rows[k]); }
     for (int k = 0; k < n; ++k)
-        if ((size_t)rows[k] * width > ctxs[k]->rec_cap[0]) { c0->last_error = "allgather_records: a context's local table (records_buffer 0) is smaller than rows * width"; return SEPAIHRD_E_INVALID_ARG; }
+        if ((size_t)rows[k] * width * sizeof(double) > ctxs[k]->rec_buf[0].cap) { c0->last_error = "allgather_records: a context's local table (records_buffer 0) is smaller than rows * width"; return SEPAIHRD_E_INVALID_ARG; }
     bool distinct = true;
     for (int a = 0; a < n; ++a)
         for (int b = a + 1; b < n; ++b) distinct = distinct && ctxs[a]->device != ctxs[b]->device;
@@ -2637,12 +2508,12 @@ int sepaihrd_allgather_records(sepaihrd_ctx* const* ctxs, int n, const int32_t* 
         size_t off = 0;
         for (int k = 0; k < n; ++k) {
             HIP_TRY(hipSetDevice(ctxs[k]->device), c0, return SEPAIHRD_E_HIP);
-            HIP_TRY(hipMemcpy(table.data() + off, ctxs[k]->rec_buf[0], (size_t)rows[k] * width * sizeof(double), hipMemcpyDeviceToHost), c0, return SEPAIHRD_E_HIP);
+            HIP_TRY(hipMemcpy(table.data() + off, ctxs[k]->rec_buf[0].p, (size_t)rows[k] * width * sizeof(double), hipMemcpyDeviceToHost), c0, return SEPAIHRD_E_HIP);
             off += (size_t)rows[k] * width;
         }
         for (int k = 0; k < n; ++k) {
             HIP_TRY(hipSetDevice(ctxs[k]->device), c0, return SEPAIHRD_E_HIP);
-            HIP_TRY(hipMemcpy(ctxs[k]->rec_buf[1], table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice), c0, return SEPAIHRD_E_HIP);
+            HIP_TRY(hipMemcpy(ctxs[k]->rec_buf[1].p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice), c0, return SEPAIHRD_E_HIP);
         }
         return SEPAIHRD_OK;
     }
@@ -2671,7 +2542,7 @@ int sepaihrd_allgather_records(sepaihrd_ctx* const* ctxs, int n, const int32_t* 
         if (hipSetDevice(devs[k]) != hipSuccess || hipStreamCreateWithFlags(&streams[k], hipStreamNonBlocking) != hipSuccess ||
             hipMalloc((void**)&send[k], block * sizeof(double)) != hipSuccess || hipMalloc((void**)&recv[k], block * n * sizeof(double)) != hipSuccess ||
             hipMemsetAsync(send[k], 0, block * sizeof(double), streams[k]) != hipSuccess ||
-            hipMemcpyAsync(send[k], ctxs[k]->rec_buf[0], (size_t)rows[k] * width * sizeof(double), hipMemcpyDeviceToDevice, streams[k]) != hipSuccess)
+            hipMemcpyAsync(send[k], ctxs[k]->rec_buf[0].p, (size_t)rows[k] * width * sizeof(double), hipMemcpyDeviceToDevice, streams[k]) != hipSuccess)
             return fail("staging buffers");
     }
     if ((rc_code = rc.CommInitAll(comms.data(), n, devs.data())) != 0) return fail("ncclCommInitAll");
@@ -2686,7 +2557,7 @@ int sepaihrd_allgather_records(sepaihrd_ctx* const* ctxs, int n, const int32_t* 
         (void)hipSetDevice(devs[k]);
         size_t off = 0;
         for (int r = 0; r < n; ++r) {
-            if (rows[r] > 0 && hipMemcpyAsync(ctxs[k]->rec_buf[1] + off, recv[k] + (size_t)r * block, (size_t)rows[r] * width * sizeof(double),
+            if (rows[r] > 0 && hipMemcpyAsync(ctxs[k]->rec_buf[1].as<double>() + off, recv[k] + (size_t)r * block, (size_t)rows[r] * width * sizeof(double),
                                               hipMemcpyDeviceToDevice, streams[k]) != hipSuccess)
                 return fail("compaction");
             off += (size_t)rows[r] * width;

@@ -35,6 +35,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_host_util.h"
 
 namespace sepaihrd {
 namespace {
@@ -437,18 +438,6 @@ __global__ void diag_finalize_kernel(const DiagArgs a) {
 
 inline unsigned blocks_for(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-};
-
 }  // namespace
 
 int chain_diagnostics(const DiagInput& in, double* out, int32_t* max_lag, void* stream) {
@@ -472,33 +461,22 @@ int chain_diagnostics(const DiagInput& in, double* out, int32_t* max_lag, void* 
     G = (int)std::min<size_t>((size_t)G, (((size_t)1 << 31) - 1) / CN);
     if (G < 1) return -4;
 
-    Scratch sc;
+    CallScratch sc;
     DiagArgs a{};
     a.C = C; a.N = N; a.M = M; a.S = S; a.CN = CN; a.npart = npart; a.chains_per_part = chains_per_part;
     a.nb = nb; a.M_pad = M_pad;
-    a.xs = sc.get<double>((size_t)G * S);
-    a.mid = sc.get<double>((size_t)G * C);
-    a.zs = sc.get<double>((size_t)G * S);
-    a.zf = sc.get<double>((size_t)G * S);
-    a.info = sc.get<double>((size_t)G * INFO_W);
-    a.part = sc.get<double>((size_t)G * nb * 4);
-    a.cmean = sc.get<double>((size_t)G * N_KINDS * 2 * C);
-    a.cvar = sc.get<double>((size_t)G * N_KINDS * 2 * C);
-    a.kstat = sc.get<double>((size_t)G * N_KINDS * 3);
-    a.acm = sc.get<double>((size_t)G * N_ESS * M_pad);
-    a.apart = sc.get<double>((size_t)G * N_ESS * npart * LAG_BLOCK);
-    a.tstate = sc.get<int32_t>((size_t)G * N_ESS);
-    a.live = sc.get<int32_t>((size_t)G * N_ESS);
-    a.ess = sc.get<double>((size_t)G * N_ESS);
-    a.maxlag = sc.get<int32_t>((size_t)G * N_ESS);
-    a.live_count = sc.get<int32_t>(1);
-    a.out = sc.get<double>((size_t)G * 7);
-    double* keys_in = sc.get<double>((size_t)G * CN);
-    double* keys_out = sc.get<double>((size_t)G * CN);
-    int32_t* vals_in = sc.get<int32_t>((size_t)G * S);
-    int32_t* vals_out = sc.get<int32_t>((size_t)G * S);
-    if (!a.xs || !a.mid || !a.zs || !a.zf || !a.info || !a.part || !a.cmean || !a.cvar || !a.kstat || !a.acm || !a.apart ||
-        !a.tstate || !a.live || !a.ess || !a.maxlag || !a.live_count || !a.out || !keys_in || !keys_out || !vals_in || !vals_out)
+    double *keys_in = nullptr, *keys_out = nullptr;
+    int32_t *vals_in = nullptr, *vals_out = nullptr;
+    if (!(sc.alloc(&a.xs, (size_t)G * S) && sc.alloc(&a.mid, (size_t)G * C) && sc.alloc(&a.zs, (size_t)G * S) &&
+          sc.alloc(&a.zf, (size_t)G * S) && sc.alloc(&a.info, (size_t)G * INFO_W) &&
+          sc.alloc(&a.part, (size_t)G * nb * 4) && sc.alloc(&a.cmean, (size_t)G * N_KINDS * 2 * C) &&
+          sc.alloc(&a.cvar, (size_t)G * N_KINDS * 2 * C) && sc.alloc(&a.kstat, (size_t)G * N_KINDS * 3) &&
+          sc.alloc(&a.acm, (size_t)G * N_ESS * M_pad) && sc.alloc(&a.apart, (size_t)G * N_ESS * npart * LAG_BLOCK) &&
+          sc.alloc(&a.tstate, (size_t)G * N_ESS) && sc.alloc(&a.live, (size_t)G * N_ESS) &&
+          sc.alloc(&a.ess, (size_t)G * N_ESS) && sc.alloc(&a.maxlag, (size_t)G * N_ESS) &&
+          sc.alloc(&a.live_count, 1) && sc.alloc(&a.out, (size_t)G * 7) && sc.alloc(&keys_in, (size_t)G * CN) &&
+          sc.alloc(&keys_out, (size_t)G * CN) && sc.alloc(&vals_in, (size_t)G * S) &&
+          sc.alloc(&vals_out, (size_t)G * S)))
         return -3;
     // rocPRIM's device-wide radix sort, one column at a time: a column's S or C N draws fill the whole device (the
     // segmented form gives each segment one workgroup, which is what a column of millions of draws cannot afford)
@@ -506,8 +484,8 @@ int chain_diagnostics(const DiagInput& in, double* out, int32_t* max_lag, void* 
     if (rocprim::radix_sort_pairs(nullptr, need_pairs, keys_in, keys_out, vals_in, vals_out, S, 0, 64, st) != hipSuccess) return -3;
     if (!even && rocprim::radix_sort_keys(nullptr, need_keys, keys_in, keys_out, CN, 0, 64, st) != hipSuccess) return -3;
     size_t tmp_bytes = std::max(need_pairs, need_keys);
-    void* tmp = sc.get<char>(tmp_bytes);
-    if (!tmp) return -3;
+    char* tmp = nullptr;
+    if (!sc.alloc(&tmp, tmp_bytes)) return -3;
     auto sort_pairs = [&](int ng) {
         for (int g = 0; g < ng; ++g) {
             const size_t o = (size_t)g * S;

@@ -35,6 +35,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_host_util.h"
 #include "sepaihrd_predictive_device.h"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_sir_device.h"
@@ -521,12 +522,11 @@ int sort_segments_global(const double* vals, int segments, int S_pad, double* sc
     if (group < 1 || (size_t)group * S_pad >= (size_t)1 << 31) return -4;
     std::vector<unsigned> offs((size_t)group + 1);
     for (int g = 0; g <= group; ++g) offs[(size_t)g] = (unsigned)((size_t)g * S_pad);
+    DeviceBuf offs_buf, tmp;  // freed on return, after the stream has been synchronised
     unsigned* d_offs = nullptr;
-    if (hipMalloc((void**)&d_offs, offs.size() * sizeof(unsigned)) != hipSuccess) return -3;
+    if (!offs_buf.get(&d_offs, offs.size())) return -3;
     int rc = 0;
     if (hipMemcpyAsync(d_offs, offs.data(), offs.size() * sizeof(unsigned), hipMemcpyHostToDevice, st) != hipSuccess) rc = -3;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
     for (int first = 0; first < segments && rc == 0; first += group) {
         const int ng = (segments - first < group) ? segments - first : group;
         const double* in = vals + (size_t)first * S_pad;
@@ -534,19 +534,13 @@ int sort_segments_global(const double* vals, int segments, int S_pad, double* sc
         size_t need = 0;
         if (rocprim::segmented_radix_sort_keys(nullptr, need, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
                                                st) != hipSuccess) { rc = -3; break; }
-        if (need > tmp_bytes) {
-            if (tmp) (void)hipFree(tmp);
-            tmp = nullptr;
-            if (hipMalloc(&tmp, need) != hipSuccess) { rc = -3; break; }
-            tmp_bytes = need;
-        }
-        if (rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
+        if (!tmp.reserve(need)) { rc = -3; break; }
+        size_t tmp_bytes = tmp.cap;
+        if (rocprim::segmented_radix_sort_keys(tmp.p, tmp_bytes, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
                                                st) != hipSuccess) { rc = -3; break; }
         pick(first, ng);
     }
     (void)hipStreamSynchronize(st);
-    if (tmp) (void)hipFree(tmp);
-    (void)hipFree(d_offs);
     return (rc == 0 && hipGetLastError() == hipSuccess) ? 0 : -3;
 }
 

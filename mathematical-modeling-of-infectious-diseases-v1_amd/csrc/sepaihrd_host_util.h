@@ -32,58 +32,135 @@ inline bool probabilities_valid(const double* probs, int n_probs) {
         }                                                                                    \
     } while (0)
 
-// Device buffers, events and (where the call runs on a stream of its own) the stream of ONE call, released however the
-// call ends.  The events are created by the caller (n_events null handles to fill), as is the stream.
-struct CallScratch {
-    std::vector<void*> bufs;
-    std::vector<hipEvent_t> ev;
-    hipStream_t stream = nullptr;
-    explicit CallScratch(size_t n_events = 0) : ev(n_events, nullptr) {}
-    CallScratch(const CallScratch&) = delete;
-    CallScratch& operator=(const CallScratch&) = delete;
-    ~CallScratch() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        for (void* b : bufs) if (b) (void)hipFree(b);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+// an allocation that a HIP_TRY would have named: the same "<expression>: <what went wrong>" text for an owner's get / reserve
+#define ALLOC_TRY(expr, ctx, fail)                                                           \
+    do {                                                                                     \
+        if (!(expr)) {                                                                       \
+            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(hipErrorOutOfMemory); \
+            fail;                                                                            \
+        }                                                                                    \
+    } while (0)
+
+// ---- owners: every device buffer, page-locked buffer, event and stream is released by the destructor of exactly one of
+// these.  The two memory kinds as (allocate, free) pairs, true for success; a failed allocation leaves HIP's error state clear.
+inline bool device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess || ((void)hipGetLastError(), false); }
+inline void device_free(void* p) { (void)hipFree(p); }
+inline bool pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess || ((void)hipGetLastError(), false); }
+inline void pinned_free(void* p) { (void)hipHostFree(p); }
+
+// ONE grow-only buffer: get() hands it out, grown to `count` elements (at least 8 bytes) if it is smaller; false when the
+// allocation fails (the buffer is then empty: nullptr, capacity 0).  Allocating tens of GB per call costs more than the
+// kernels at large ensembles, hence grow-only.
+template <bool (*Alloc)(void**, size_t), void (*Free)(void*)>
+struct GrowBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf&) = delete;
+    GrowBuf& operator=(const GrowBuf&) = delete;
+    ~GrowBuf() { release(); }
+    bool reserve(size_t bytes) {
+        bytes = std::max<size_t>(bytes, 8);
+        if (cap >= bytes) return true;
+        release();
+        if (!Alloc(&p, bytes)) { p = nullptr; return false; }
+        cap = bytes;
+        return true;
     }
-    // a valid pointer even for count == 0, so that kernels may form it
+    template <class T>
+    bool get(T** out, size_t count) {
+        const bool ok = reserve(count * sizeof(T));
+        *out = static_cast<T*>(p);
+        return ok;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+    void release() {
+        if (p) Free(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+using DeviceBuf = GrowBuf<device_alloc, device_free>;
+using PinnedBuf = GrowBuf<pinned_alloc, pinned_free>;
+
+// N buffers a context keeps between calls, one per role: get() is the slot's.
+template <int N, class Buf = DeviceBuf>
+struct GrowSlots {
+    Buf slot[N];
+    template <class T>
+    bool get(int k, T** p, size_t count) { return slot[k].get(p, count); }
+    void release() { for (Buf& b : slot) b.release(); }
+};
+
+// The allocations an object makes once and keeps for its lifetime.  alloc() yields a valid pointer even for count == 0, so
+// that kernels may form it.
+template <bool (*Alloc)(void**, size_t), void (*Free)(void*)>
+struct FixedAllocs {
+    std::vector<void*> bufs;
+    FixedAllocs() = default;
+    FixedAllocs(const FixedAllocs&) = delete;
+    FixedAllocs& operator=(const FixedAllocs&) = delete;
+    ~FixedAllocs() { for (void* b : bufs) Free(b); }
+    bool bytes(void** p, size_t n) {
+        if (!Alloc(p, n ? n : 1)) { *p = nullptr; return false; }
+        bufs.push_back(*p);
+        return true;
+    }
     template <class T>
     bool alloc(T** p, size_t count) {
         void* q = nullptr;
-        if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        bufs.push_back(q);
+        const bool ok = bytes(&q, (count ? count : 1) * sizeof(T));
         *p = static_cast<T*>(q);
-        return true;
+        return ok;
     }
 };
+using DeviceAllocs = FixedAllocs<device_alloc, device_free>;
+using PinnedAllocs = FixedAllocs<pinned_alloc, pinned_free>;
 
-// N device buffers a context keeps between calls, one per role, grow-only: allocating tens of GB per call costs more than
-// the kernels at large ensembles.  get() hands out the slot's buffer, grown to `count` elements (at least 8 bytes) if it is
-// smaller; false when the allocation fails (the slot is then empty and the error state cleared).
-template <int N>
-struct GrowSlots {
-    void* buf[N] = {};
-    size_t cap[N] = {};
+// a vector on the device for as long as `a` lives (one element when it is empty); a failure clears `ok`
+template <class T>
+const T* upload(DeviceAllocs& a, const std::vector<T>& v, bool& ok) {
+    T* p = nullptr;
+    if (!a.alloc(&p, v.size())) { ok = false; return nullptr; }
+    if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    return p;
+}
+
+// An event / a stream: a null handle until created, used wherever the raw handle is (the conversion).  &x is the address of
+// the handle, so that a creation call inside a HIP_TRY reads -- and reports -- as it would with a raw handle.  A stream is
+// drained before it is destroyed.
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (h) (void)hipEventDestroy(h); }
+    hipError_t create(unsigned flags) { const hipError_t e = hipEventCreateWithFlags(&h, flags); if (e != hipSuccess) h = nullptr; return e; }
+    operator hipEvent_t() const { return h; }
+    hipEvent_t* operator&() { return &h; }
+};
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (h) { (void)hipStreamSynchronize(h); (void)hipStreamDestroy(h); } }
+    hipError_t create(unsigned flags) { const hipError_t e = hipStreamCreateWithFlags(&h, flags); if (e != hipSuccess) h = nullptr; return e; }
+    operator hipStream_t() const { return h; }
+    hipStream_t* operator&() { return &h; }
+};
+
+// Device buffers, events and (where the call runs on a stream of its own) the stream of ONE call, released however the
+// call ends.  The events are created by the caller (n_events null handles to fill), as is the stream.
+// Release order (reverse of declaration): stream, events, buffers.
+struct CallScratch {
+    DeviceAllocs bufs;
+    std::vector<Event> ev;
+    Stream stream;
+    explicit CallScratch(size_t n_events = 0) : ev(n_events) {}
     template <class T>
-    bool get(int slot, T** p, size_t count) {
-        const size_t bytes = std::max<size_t>(count * sizeof(T), 8);
-        if (cap[slot] < bytes) {
-            if (buf[slot]) (void)hipFree(buf[slot]);
-            buf[slot] = nullptr;
-            cap[slot] = 0;
-            if (hipMalloc(&buf[slot], bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-            cap[slot] = bytes;
-        }
-        *p = static_cast<T*>(buf[slot]);
-        return true;
-    }
-    void release() {
-        for (int k = 0; k < N; ++k) {
-            if (buf[k]) (void)hipFree(buf[k]);
-            buf[k] = nullptr;
-            cap[k] = 0;
-        }
-    }
+    bool alloc(T** p, size_t count) { return bufs.alloc(p, count); }
 };
 
 // the results of a call copied back: only those the caller asked for, nothing more after the first failure

@@ -11,6 +11,7 @@
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_hip.h"
+#include "sepaihrd_host_util.h"
 #include "sepaihrd_poisson.inc"
 #include "sepaihrd_predictive_device.h"
 
@@ -113,10 +114,6 @@ __global__ __launch_bounds__(DRAW_BLOCK) void poisson_probe_kernel(uint64_t seed
     out[i] = sepaihrd_poisson::poisson(seed, (uint32_t)i, 0u, 0u, lambda[i]);
 }
 
-void set_err(char* err, int errlen, const std::string& msg) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
-}
-
 }  // namespace
 
 int launch_predictive_draws(const PredictiveArgs& a, void* stream) {
@@ -161,10 +158,13 @@ extern "C" int sepaihrd_poisson_device(int device, uint64_t seed, const double* 
     if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return SEPAIHRD_E_HIP; }
     if (device >= ndev) { set_err(err, errlen, "device index out of range"); return SEPAIHRD_E_INVALID_ARG; }
     if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return SEPAIHRD_E_HIP; }
+    CallScratch sc;
     double *d_lambda = nullptr, *d_out = nullptr;
-    bool ok = hipMalloc((void**)&d_lambda, (size_t)count * sizeof(double)) == hipSuccess &&
-              hipMalloc((void**)&d_out, (size_t)count * sizeof(double)) == hipSuccess &&
-              hipMemcpy(d_lambda, lambda, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (!sc.alloc(&d_lambda, (size_t)count) || !sc.alloc(&d_out, (size_t)count)) {
+        set_err(err, errlen, std::string("poisson_device: ") + hipGetErrorString(hipErrorOutOfMemory));
+        return SEPAIHRD_E_HIP;
+    }
+    bool ok = hipMemcpy(d_lambda, lambda, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(poisson_probe_kernel, dim3((unsigned)((count + DRAW_BLOCK - 1) / DRAW_BLOCK)), dim3(DRAW_BLOCK), 0, nullptr, seed,
                            d_lambda, count, d_out);
@@ -172,7 +172,5 @@ extern "C" int sepaihrd_poisson_device(int device, uint64_t seed, const double* 
              hipMemcpy(out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
     }
     if (!ok) set_err(err, errlen, std::string("poisson_device: ") + hipGetErrorString(hipGetLastError()));
-    if (d_lambda) (void)hipFree(d_lambda);
-    if (d_out) (void)hipFree(d_out);
     return ok ? SEPAIHRD_OK : SEPAIHRD_E_HIP;
 }

@@ -30,14 +30,15 @@ struct sepaihrd_sir_ctx {
     int device = 0, solver = 0, arith = 0;
     int n = 0, T = 0, P = 0;
     SirDevProblem dp{};
-    std::vector<void*> allocs;
+    // the owners below release in reverse order of declaration: events, then buffers (the context has no stream of its own)
+    DeviceAllocs allocs;  // the problem's tables
     std::vector<int32_t> field;  // host copy for sepaihrd_sir_apply_constraints
     std::string last_error;
-    // staging of the host-pointer entry point (grow-only)
-    size_t cap_B = 0, cap_traj = 0;
+    // staging of the host-pointer entry point (grow-only) and the views ensure_staging hands out
+    DeviceBuf theta_buf, loglik_buf, ints_buf, traj_buf;
     double* d_theta = nullptr;
     double* d_loglik = nullptr;
-    int32_t* d_ints = nullptr;  // [3][cap_B] status, accepted, rejected
+    int32_t* d_ints = nullptr;  // [3][B] status, accepted, rejected of the batch at hand
     double* d_traj = nullptr;
     // what a device-resident sampler on this context reads (sepaihrd_sir_mh_create, csrc/sepaihrd_mh_backend.h):
     // SIRParameterManager::applyConstraints as the clamp mode of the propose kernels' constrain() (the table of
@@ -49,7 +50,7 @@ struct sepaihrd_sir_ctx {
     // scratch of sepaihrd_sir_scenario_ensemble by role (grow-only, reused across calls), its phase events, the device time
     // of the last call and the number of calls that reached the device
     GrowSlots<SLOT_COUNT> slots;
-    hipEvent_t ens_ev[4] = {};
+    Event ens_ev[4];
     double ens_ms[3] = {0.0, 0.0, 0.0};
     int64_t ens_calls = 0;
 };
@@ -59,45 +60,11 @@ static_assert(sizeof(sepaihrd_sir_event) == sizeof(SirEvent) && SEPAIHRD_SIR_MAX
 
 namespace {
 
-template <class T>
-const T* upload(sepaihrd_sir_ctx* ctx, const std::vector<T>& v, bool& ok) {
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);  // a valid allocation even when empty
-    if (hipMalloc(&p, bytes) != hipSuccess) { ok = false; return nullptr; }
-    ctx->allocs.push_back(p);
-    if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    return static_cast<const T*>(p);
-}
-
-void free_staging(sepaihrd_sir_ctx* c) {
-    void* ptrs[] = {c->d_theta, c->d_loglik, c->d_ints, c->d_traj};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    c->d_theta = c->d_loglik = c->d_traj = nullptr;
-    c->d_ints = nullptr;
-    c->cap_B = c->cap_traj = 0;
-}
-
 int ensure_staging(sepaihrd_sir_ctx* c, size_t B, size_t traj_elems) {
-    if (B > c->cap_B) {
-        void* ptrs[] = {c->d_theta, c->d_loglik, c->d_ints};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        c->d_theta = c->d_loglik = nullptr;
-        c->d_ints = nullptr;
-        c->cap_B = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_theta, B * c->P * sizeof(double)), c, return SEPAIHRD_E_HIP);
-        HIP_TRY(hipMalloc((void**)&c->d_loglik, B * sizeof(double)), c, return SEPAIHRD_E_HIP);
-        HIP_TRY(hipMalloc((void**)&c->d_ints, 3 * B * sizeof(int32_t)), c, return SEPAIHRD_E_HIP);
-        c->cap_B = B;
-    }
-    if (traj_elems > c->cap_traj) {
-        if (c->d_traj) (void)hipFree(c->d_traj);
-        c->d_traj = nullptr;
-        c->cap_traj = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_traj, traj_elems * sizeof(double)), c, return SEPAIHRD_E_HIP);
-        c->cap_traj = traj_elems;
-    }
+    ALLOC_TRY(c->theta_buf.get(&c->d_theta, B * c->P), c, return SEPAIHRD_E_HIP);
+    ALLOC_TRY(c->loglik_buf.get(&c->d_loglik, B), c, return SEPAIHRD_E_HIP);
+    ALLOC_TRY(c->ints_buf.get(&c->d_ints, 3 * B), c, return SEPAIHRD_E_HIP);
+    if (traj_elems) ALLOC_TRY(c->traj_buf.get(&c->d_traj, traj_elems), c, return SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
 
@@ -187,14 +154,14 @@ sepaihrd_sir_ctx* sepaihrd_sir_create(const sepaihrd_sir_problem* pb, int device
     d.abs_tol = pb->abs_err; d.rel_tol = pb->rel_err; d.dt_hint = pb->dt_hint; d.max_gap = max_gap;
     d.q = pb->q; d.scale = pb->scale_C_total;
     bool ok = true;
-    d.times = upload(ctx, std::vector<double>(pb->times, pb->times + T), ok);
-    d.N = upload(ctx, Npad, ok);
-    d.C = upload(ctx, Cpad, ok);
-    d.gamma = upload(ctx, gpad, ok);
-    d.init_state = upload(ctx, init, ok);
-    d.obs = upload(ctx, obs, ok);
-    d.param_field = upload(ctx, ctx->field, ok);
-    d.param_index = upload(ctx, std::vector<int32_t>(pb->param_index, pb->param_index + P), ok);
+    d.times = upload(ctx->allocs, std::vector<double>(pb->times, pb->times + T), ok);
+    d.N = upload(ctx->allocs, Npad, ok);
+    d.C = upload(ctx->allocs, Cpad, ok);
+    d.gamma = upload(ctx->allocs, gpad, ok);
+    d.init_state = upload(ctx->allocs, init, ok);
+    d.obs = upload(ctx->allocs, obs, ok);
+    d.param_field = upload(ctx->allocs, ctx->field, ok);
+    d.param_index = upload(ctx->allocs, std::vector<int32_t>(pb->param_index, pb->param_index + P), ok);
     if (!ok) {
         set_err(err, errlen, "device allocation / upload failed");
         sepaihrd_sir_destroy(ctx);
@@ -206,11 +173,6 @@ sepaihrd_sir_ctx* sepaihrd_sir_create(const sepaihrd_sir_problem* pb, int device
 void sepaihrd_sir_destroy(sepaihrd_sir_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    free_staging(ctx);
-    ctx->slots.release();
-    for (hipEvent_t e : ctx->ens_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (void* p : ctx->allocs) (void)hipFree(p);
     delete ctx;
 }
 
@@ -262,8 +224,8 @@ int sepaihrd_sir_eval_batch(sepaihrd_sir_ctx* ctx, const double* theta, int B, d
         if (rc != SEPAIHRD_OK) return rc;
     }
     int32_t* d_status = ctx->d_ints;
-    int32_t* d_nacc = ctx->d_ints + ctx->cap_B;
-    int32_t* d_nrej = ctx->d_ints + 2 * ctx->cap_B;
+    int32_t* d_nacc = ctx->d_ints + nB;
+    int32_t* d_nrej = ctx->d_ints + 2 * nB;
     HIP_TRY(hipMemcpy(ctx->d_theta, theta, nB * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     const int rc = sepaihrd_sir_eval_batch_device(ctx, ctx->d_theta, B, ctx->d_loglik, d_status, d_nacc, d_nrej,
                                                   traj ? ctx->d_traj : nullptr, nullptr);
@@ -394,7 +356,7 @@ int sepaihrd_sir_scenario_ensemble(sepaihrd_sir_ctx* ctx, const double* theta, i
         !slots.get(SLOT_INTS, &d_ints, 3 * B) || !slots.get(SLOT_COUNTS, &d_counts, (size_t)3 * K) ||
         !slots.get(SLOT_N_EVENTS, &d_nev, (size_t)K) || !slots.get(SLOT_EVENTS, &d_events, (size_t)K * SEPAIHRD_SIR_MAX_EVENTS))
         return refuse("device allocation failed", SEPAIHRD_E_HIP);
-    for (hipEvent_t& e : ctx->ens_ev)
+    for (Event& e : ctx->ens_ev)
         if (!e) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     // uploads.  Every scenario integrates the same samples: theta replicated K times, chain c = scenario c / S, sample c % S
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
@@ -486,9 +448,9 @@ sepaihrd_mh* sepaihrd_sir_mh_create(sepaihrd_sir_ctx* ctx, const sepaihrd_mh_con
         DevProblem& d = ctx->mh_dp;
         d.n = ctx->n; d.lpc = ctx->dp.lpc; d.T = ctx->T; d.P = ctx->P;
         d.constraint_mode = 0;  // clamp: this manager has no reflect mode
-        d.lower = upload(ctx, lower, ok);
-        d.upper = upload(ctx, upper, ok);
-        d.has_bounds = upload(ctx, bounded, ok);
+        d.lower = upload(ctx->allocs, lower, ok);
+        d.upper = upload(ctx->allocs, upper, ok);
+        d.has_bounds = upload(ctx->allocs, bounded, ok);
         if (!ok) { ctx->last_error = "sir_mh_create: upload of the constraint table failed"; return nullptr; }
         ctx->mh_dp_ready = true;
     }

@@ -171,7 +171,7 @@ int sepaihrd_stoch_sir_run(int device, const sepaihrd_stoch_sir_config* cfg, con
         return SEPAIHRD_E_HIP;
     };
     if (hipStreamCreate(&sc.stream) != hipSuccess) return hip_fail("hipStreamCreate");
-    for (hipEvent_t& e : sc.ev) if (hipEventCreate(&e) != hipSuccess) return hip_fail("hipEventCreate");
+    for (Event& e : sc.ev) if (hipEventCreate(&e) != hipSuccess) return hip_fail("hipEventCreate");
     hipStream_t st = sc.stream;
 
     Group* d_groups = nullptr;
