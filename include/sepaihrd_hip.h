@@ -904,6 +904,57 @@ int sepaihrd_stochastic_values_width(int n_age, int n_beta, int n_kappa);
  * quantiles. */
 int sepaihrd_stochastic_timing(const sepaihrd_ctx *ctx, double *ms);
 
+/* ---- bootstrap particle filter of the stochastic SEPAIHRD model (additive; SEPAIHRD_ABI_VERSION stays) ----------------------
+ * sepaihrd_ensemble_stochastic simulates the chain-binomial model forward; this call says how probable the observed
+ * hospitalisations, ICU admissions and deaths are under it: an unbiased estimate of the marginal likelihood p(y | theta) under
+ * process noise, by a bootstrap particle filter with systematic resampling (Gordon, Salmond & Smith 1993; Kitagawa 1996).  The
+ * reference has no such filter; this one is this build's own.  csrc/sepaihrd_particle.inc states it (one text for the kernel and
+ * the host twin):
+ *   - particles: for theta[b], slot j (0 <= j < J) starts from the rounded initial counts of b's model_values row and advances
+ *     with the model step of sepaihrd_ensemble_stochastic at stream coordinates (seed, s = b, r = j): until the first resampling,
+ *     and so through the whole run-up, slot j IS replicate j of that call.  A slot keeps drawing at its own index after an
+ *     ancestor has overwritten it;
+ *   - log-weight at output row k, t = k - runup_offset >= 0: per age the increments of CumH, CumICU and D since the previous
+ *     output row (0 at the run's first row), sim = max(0, inc) + 1e-10, term = obs log(sim) - sim where the observation is usable
+ *     (finite and >= 0, the likelihood's rule) and 0 elsewhere; lw_j = sum over ages, ascending, of (term_H + term_ICU) + term_D;
+ *   - a row without any usable cell is skipped: no weighting, no resampling, increment 0, ESS NaN;
+ *   - M = max_j lw_j, w_j = exp(lw_j - M), C and Q the inclusive prefix sums of w and w^2 in the Kogge-Stone order;
+ *     increment = M + log(C[J-1] / J), ESS = C[J-1]^2 / Q[J-1], loglik[b] = the sum of the increments in time order;
+ *   - systematic resampling at EVERY weighted row from one uniform per (b, k) (Philox counter (b, 0xFFFFFFFF, (64 k) 16 + 13, 0),
+ *     which no particle uses): the ancestor of slot i is the smallest j with C[j] > ((u + i) / J) C[J-1], clamped to J - 1; the
+ *     slot takes the ancestor's counts and its previous-row CumH, CumICU, D.  Weights are equal after every resampling: none are
+ *     carried, and there is no adaptive (ESS-threshold) rule.
+ * One workgroup holds all particles of one theta in LDS: J <= sepaihrd_particle_max_particles(n_age) (464, 258, 136, 70, 35 for
+ * up to 1, 2, 4, 8, 16 age classes).  The result for theta[b] is a function of (seed, b, J, steps_per_interval) and its model
+ * values alone: it does not depend on B, on the outputs asked for or on which other vectors are invalid.  The arithmetic mode of
+ * the context does not change the result.
+ *   loglik        [B]; -DBL_MAX for an invalid theta (status SEPAIHRD_STATUS_INVALID), the objective's lowest()
+ *   increments    [B][T_pos] or NULL: the increment of every output time >= 0 (0 for a skipped row; NaN for an invalid theta)
+ *   ess           [B][T_pos] or NULL: NaN for a skipped row and for an invalid theta
+ *   final_state   [B][J][11][n_age] or NULL: the particles after the last row's resampling; NaN for an invalid theta
+ *   model_values  [B][W] or NULL: the layout of sepaihrd_ensemble_stochastic
+ *   status [B] or NULL; n_valid: count of status 0, or NULL
+ * The host twin (host/: hostParticleLoglik) reproduces loglik, increments, ess and final_state bit for bit from model_values,
+ * status, the problem's fixed data and the observations.
+ * SEPAIHRD_E_INVALID_ARG, before the device is touched and with the outputs untouched: B < 1, J < 1 or above
+ * sepaihrd_particle_max_particles, steps_per_interval < 1, n_times steps_per_interval >= 2^22, a pending
+ * sepaihrd_eval_batch_begin, or buffers beyond the device's memory.  SEPAIHRD_E_UNSUPPORTED in F32 precision or beyond 16 age
+ * classes. */
+int sepaihrd_particle_loglik(sepaihrd_ctx *ctx, const double *theta, int B, int J, int steps_per_interval, uint64_t seed,
+                             double *loglik, double *increments, double *ess, double *final_state, double *model_values,
+                             int32_t *status, int32_t *n_valid);
+/* Host only: the argument rules above that need no context, with a message in err (NULL: not wanted). */
+int sepaihrd_particle_validate(int B, int J, int steps_per_interval, int n_times, int T_pos, int n_age, char *err, int errlen);
+/* Host only: the largest J the filter kernel takes for n_age classes; SEPAIHRD_E_INVALID_ARG outside 1..16. */
+int sepaihrd_particle_max_particles(int n_age);
+/* Device time of the context's last sepaihrd_particle_loglik call in milliseconds, ms[2]: decode; filter kernel. */
+int sepaihrd_particle_timing(const sepaihrd_ctx *ctx, double *ms);
+/* Probe of the device's normalisation, scans and ancestor search: one weighted row with log-weights logw [J] (finite, J in
+ * 1..512) at the resampling coordinates of (seed, b, row), through the device functions the filter kernel uses.  ancestors [J],
+ * increment and ess: host memory. */
+int sepaihrd_particle_resample_device(int device, uint64_t seed, uint32_t b, uint32_t row, const double *logw, int J,
+                                      int32_t *ancestors, double *increment, double *ess, char *err, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 #include "sepaihrd_mh_backend.h"
 #include "sepaihrd_predictive_device.h"
 #include "sepaihrd_segments.h"
+#include "sepaihrd_particle_device.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
 using namespace sepaihrd;
@@ -99,6 +100,8 @@ struct sepaihrd_ctx {
     double pred_ms[3] = {0.0, 0.0, 0.0};
     // the last sepaihrd_ensemble_stochastic call: step kernel, sorts and quantiles (ms)
     double stoch_ms[2] = {0.0, 0.0};
+    // the last sepaihrd_particle_loglik call: decode, filter kernel (ms)
+    double particle_ms[2] = {0.0, 0.0};
     Stream own_stream;  // sepaihrd_eval_batch_begin / _end; last: see above
 };
 
@@ -1076,6 +1079,83 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
 int sepaihrd_stochastic_timing(const sepaihrd_ctx* ctx, double* ms) {
     if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
     for (int i = 0; i < 2; ++i) ms[i] = ctx->stoch_ms[i];
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, double* loglik,
+                             double* increments, double* ess, double* final_state, double* model_values, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    const char* const who = "particle_loglik";
+    if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
+    int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
+    if (rc != SEPAIHRD_OK) return rc;
+    const DevProblem& dp = ctx->dp;
+    const int Tp = dp.T - dp.runup_offset;
+    if (dp.n > 16 || dp.lpc > 16) return refuse(ctx, who, "built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
+    {
+        char msg[256] = "";
+        if (sepaihrd_particle_validate(B, J, steps_per_interval, dp.T, Tp, dp.n, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            ctx->last_error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    if (ctx->precision != SEPAIHRD_PRECISION_F64)
+        return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    // sizes
+    const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
+    const size_t n_values = (size_t)B * W, n_rows = (size_t)B * Tp;
+    const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
+    const size_t need_bytes = sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final) + sizeof(int32_t) * ((size_t)B + 2);
+    rc = require_device_memory(ctx, need_bytes, "particle_loglik: the model values of B = " + std::to_string(B) + " parameter vectors and the outputs asked for need",
+                               "split the parameter vectors over several calls");
+    if (rc != SEPAIHRD_OK) return rc;
+    // buffers and events of this call alone
+    CallScratch sc(3);
+    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr;
+    int32_t *d_counts = nullptr, *d_status = nullptr;
+    if (!sc.alloc(&d_theta, (size_t)B * ctx->P) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_ll, (size_t)B) ||
+        !sc.alloc(&d_inc, increments ? n_rows : 0) || !sc.alloc(&d_ess, ess ? n_rows : 0) || !sc.alloc(&d_final, n_final) ||
+        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
+    for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
+    StochEpiArgs da{};
+    da.S = B; da.R = J; da.W = W;
+    da.theta = d_theta; da.values = d_values; da.status = d_status; da.counts = d_counts;
+    (void)hipEventRecord(sc.ev[0], nullptr);
+    if (launch_stoch_epi_decode(dp, da, nullptr) != 0) return refuse(ctx, who, "decode kernel launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[1], nullptr);
+    ParticleArgs a{};
+    a.B = B; a.J = J; a.m = steps_per_interval; a.W = W;
+    a.seed = seed;
+    a.values = d_values; a.status = d_status; a.loglik = d_ll;
+    a.increments = increments ? d_inc : nullptr; a.ess = ess ? d_ess : nullptr; a.final_state = final_state ? d_final : nullptr;
+    if (launch_particle_filter(dp, a, nullptr) != 0) return refuse(ctx, who, "filter kernel launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[2], nullptr);
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    for (int i = 0; i < 2; ++i) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
+        ctx->particle_ms[i] = ms;
+    }
+    // fetches
+    ResultFetch res;
+    res.fetch(loglik, d_ll, (size_t)B * sizeof(double));
+    res.fetch(increments, d_inc, n_rows * sizeof(double));
+    res.fetch(ess, d_ess, n_rows * sizeof(double));
+    res.fetch(final_state, d_final, n_final * sizeof(double));
+    res.fetch(model_values, d_values, n_values * sizeof(double));
+    res.fetch(status, d_status, (size_t)B * sizeof(int32_t));
+    res.fetch(n_valid, d_counts, sizeof(int32_t));
+    if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_particle_timing(const sepaihrd_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
+    for (int i = 0; i < 2; ++i) ms[i] = ctx->particle_ms[i];
     return SEPAIHRD_OK;
 }
 

@@ -218,6 +218,8 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_stoch_sir_num_steps", "sepaihrd_stoch_sir_validate", "sepaihrd_stoch_sir_run", "sepaihrd_stoch_sir_binomial_device",
     "sepaihrd_ensemble_predictive", "sepaihrd_predictive_validate", "sepaihrd_predictive_timing", "sepaihrd_poisson_device",
     "sepaihrd_ensemble_stochastic", "sepaihrd_stochastic_validate", "sepaihrd_stochastic_values_width", "sepaihrd_stochastic_timing",
+    "sepaihrd_particle_loglik", "sepaihrd_particle_validate", "sepaihrd_particle_max_particles", "sepaihrd_particle_timing",
+    "sepaihrd_particle_resample_device",
 )
 
 _lib = None
@@ -352,6 +354,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_stochastic_values_width.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.sepaihrd_stochastic_timing.argtypes = [vp, vp]
     lib.sepaihrd_poisson_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_loglik.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64] + [vp] * 7
+    lib.sepaihrd_particle_validate.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_max_particles.argtypes = [C.c_int]
+    lib.sepaihrd_particle_timing.argtypes = [vp, vp]
+    lib.sepaihrd_particle_resample_device.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), C.c_char_p, C.c_int]
     if path is None:
         _lib = lib
     return lib
@@ -636,6 +644,56 @@ class HipObjective:
             if arr is not None:
                 out[key] = arr
         return out
+
+    def particle_max_particles(self) -> int:
+        """sepaihrd_particle_max_particles for this problem's age classes: the largest J particle_loglik takes"""
+        return int(self.lib.sepaihrd_particle_max_particles(self.pb.n))
+
+    def particle_loglik(self, theta, J: int, steps_per_interval: int, seed: int, want_increments: bool = True, want_ess: bool = True,
+                        want_final: bool = False, want_values: bool = False) -> dict:
+        """The bootstrap particle filter of the stochastic SEPAIHRD model (sepaihrd_particle_loglik): J particles per row of theta,
+        steps_per_interval binomial steps per output interval, systematic resampling at every observed row.  loglik [B] (the
+        estimate of log p(y | theta); -DBL_MAX for an invalid theta), increments [B][T_pos], ess [B][T_pos], final_state
+        [B][J][11][n], model_values [B][W], status [B], n_valid."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        B, n, J = th.shape[0], self.pb.n, int(J)
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        W = self.lib.sepaihrd_stochastic_values_width(n, len(self.pb.beta_end_times), len(self.pb.kappa_end_times))
+        loglik = np.empty(B)
+        inc = np.empty((B, Tp)) if want_increments else None
+        ess = np.empty((B, Tp)) if want_ess else None
+        final = np.empty((B, max(J, 0), 11, n)) if want_final else None
+        values = np.empty((B, W)) if want_values else None
+        status = np.empty(B, dtype=np.int32)
+        nv = C.c_int32(0)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.sepaihrd_particle_loglik(
+            self.ctx, th.ctypes.data, B, J, int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, loglik.ctypes.data, ptr(inc), ptr(ess),
+            ptr(final), ptr(values), status.ctypes.data, C.byref(nv)), "particle_loglik")
+        out = {"loglik": loglik, "status": status, "n_valid": nv.value}
+        for key, arr in (("increments", inc), ("ess", ess), ("final_state", final), ("model_values", values)):
+            if arr is not None:
+                out[key] = arr
+        return out
+
+    def particle_timing(self) -> np.ndarray:
+        """Device time of the last particle_loglik call in ms: decode; filter kernel (sepaihrd_particle_timing)"""
+        ms = np.zeros(2)
+        self._check(self.lib.sepaihrd_particle_timing(self.ctx, ms.ctypes.data), "particle_timing")
+        return ms
+
+    def particle_resample_device(self, logw, seed: int, b: int = 0, row: int = 0) -> dict:
+        """Probe of the device's normalisation, scans and ancestor search (sepaihrd_particle_resample_device): one weighted row
+        with log-weights logw [J] at the resampling coordinates (seed, b, row).  ancestors [J], increment, ess."""
+        lw = np.ascontiguousarray(logw, dtype=np.float64).ravel()
+        anc = np.empty(lw.size, dtype=np.int32)
+        inc, ess = C.c_double(0.0), C.c_double(0.0)
+        err = C.create_string_buffer(512)
+        rc = self.lib.sepaihrd_particle_resample_device(getattr(self, "_device", -1), int(seed) & 0xFFFFFFFFFFFFFFFF, int(b), int(row),
+                                                        lw.ctypes.data, lw.size, anc.ctypes.data, C.byref(inc), C.byref(ess), err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_particle_resample_device failed ({rc}): " + err.value.decode())
+        return {"ancestors": anc, "increment": inc.value, "ess": ess.value}
 
     def poisson(self, lam, seed: int) -> np.ndarray:
         """Probe of the device's Poisson sampler (sepaihrd_poisson_device): out[i] at (seed, c0 = i, c1 = c2 = 0)."""

@@ -1,0 +1,67 @@
+// host/include/epidemic_hip/HipParticleFilter.hpp
+//
+// The bootstrap particle filter of the stochastic chain-binomial SEPAIHRD model, above sepaihrd_particle_loglik: an unbiased
+// estimate of the marginal likelihood p(y | theta) under process noise.  The reference has no such filter: this one is this
+// build's own (csrc/sepaihrd_particle.inc states it; include/sepaihrd_hip.h describes the call).  The CPU twin of the device's
+// filter kernel (the same text, OpenMP over theta) is hostParticleLoglik.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "epidemic_hip/HipStochasticSEPAIHRD.hpp"
+#include "sepaihrd_hip.h"
+
+namespace epidemic {
+
+// the observed daily counts of the output times >= 0, in time order: row r belongs to output row runup_offset + r; output rows
+// beyond n_obs have no observation
+struct ParticleObservations {
+    int n_obs = 0;
+    const double* obs_H = nullptr;    // [n_obs][n_age]
+    const double* obs_ICU = nullptr;  // [n_obs][n_age]
+    const double* obs_D = nullptr;    // [n_obs][n_age]
+};
+
+// From model_values [B][W] and status [B] as sepaihrd_particle_loglik returns them: the same loglik [B], increments
+// [B][T_pos] (nullable), ess [B][T_pos] (nullable) and final_state [B][J][11][n_age] (nullable), bit for bit.  Returns
+// SEPAIHRD_OK or SEPAIHRD_E_INVALID_ARG with sepaihrd_particle_validate's message.
+int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                       const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
+                       double* ess, double* final_state, std::string* error = nullptr);
+
+// the twin of sepaihrd_particle_resample_device: one weighted row with log-weights logw [J] at the coordinates (seed, b, row)
+void hostParticleResample(std::uint64_t seed, std::uint32_t b, std::uint32_t row, const double* logw, int J, int32_t* ancestors,
+                          double* increment, double* ess);
+
+// The filter as an objective: calculateBatch evaluates B parameter vectors in one device call with seed = seed0 + (calls so
+// far), so that successive proposals of a sampler see fresh noise.  The samplers of this library (and the reference's
+// MetropolisHastingsSampler) keep the value of the current point and do not evaluate it again: run over this objective, the
+// existing Adaptive-Metropolis loop is therefore particle-marginal Metropolis-Hastings (Andrieu, Doucet & Holenstein 2010) and
+// targets the exact posterior of the stochastic model.  Nothing in the samplers changes.  An invalid theta gives lowest(), as
+// the ODE objective does.
+class HipParticleLikelihood : public virtual IObjectiveFunction, public IBatchObjectiveFunction {
+public:
+    HipParticleLikelihood(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
+                          const std::vector<double>& time_points, const Eigen::VectorXd& initial_state,
+                          std::shared_ptr<IOdeSolverStrategy> solver_strategy, int particles, int steps_per_interval, std::uint64_t seed0,
+                          int device = -1, int initial_state_mode = SEPAIHRD_INIT_FROM_THETA);
+
+    double calculate(const Eigen::VectorXd& parameters) const override;
+    const std::vector<std::string>& getParameterNames() const override { return pm_.getParameterNames(); }
+    void calculateBatch(const double* thetas, int B, double* out, int* status = nullptr) const override;
+    std::uint64_t calls() const { return calls_; }
+
+private:
+    HipSEPAIHRDParameterManager& pm_;
+    const CalibrationData& data_;
+    std::vector<double> time_points_;
+    SimulationCache cache_;
+    std::unique_ptr<HipSEPAIHRDObjectiveFunction> objective_;
+    int particles_, steps_per_interval_;
+    std::uint64_t seed0_;
+    mutable std::uint64_t calls_ = 0;
+};
+
+}  // namespace epidemic

@@ -15,6 +15,7 @@
 #include "epidemic_hip/MultiChainNUTSSampler.hpp"
 #include "epidemic_hip/HipPosteriorEnsemble.hpp"
 #include "epidemic_hip/HipPosteriorPredictive.hpp"
+#include "epidemic_hip/HipParticleFilter.hpp"
 #include "epidemic_hip/HipStochasticSEPAIHRD.hpp"
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipSIR.hpp"
@@ -1535,6 +1536,45 @@ int host_stochastic_manager_values(void* hv, int mode, const double* theta, doub
         for (double v : mp.kappa_values) out[at++] = v;
         for (const Eigen::VectorXd* f : {&mp.a, &mp.h_infec, &mp.p, &mp.h, &mp.icu, &mp.d_H, &mp.d_ICU, &mp.d_community})
             for (Eigen::Index i = 0; i < f->size(); ++i) out[at++] = (*f)[i];
+    });
+}
+
+// ---- bootstrap particle filter of the stochastic SEPAIHRD model (HipParticleFilter) ----
+// hostParticleLoglik (no device): shapes as sepaihrd_particle_loglik; obs_* [n_obs][n_age], the rows of the output times >= 0
+int host_particle_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                              const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
+                              const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                              uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
+    StochasticSEPAIHRDFixedData fd;
+    fd.n_age = n_age; fd.n_times = n_times; fd.n_beta = n_beta; fd.n_kappa = n_kappa;
+    fd.times = times; fd.N = N; fd.M = M; fd.beta_end_times = beta_end_times; fd.kappa_end_times = kappa_end_times;
+    ParticleObservations ob;
+    ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
+    std::string error;
+    const int rc = hostParticleLoglik(fd, ob, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
+// the twin of sepaihrd_particle_resample_device (no device)
+void host_particle_resample(uint64_t seed, uint32_t b, uint32_t row, const double* logw, int J, int32_t* ancestors, double* increment, double* ess) {
+    hostParticleResample(seed, b, row, logw, J, ancestors, increment, ess);
+}
+
+// HipParticleLikelihood over the handle's parameter manager / data: n_calls successive calculateBatch calls on the same B
+// parameter vectors (thetas B x P); values [n_calls][B], status [n_calls][B] (nullable).  0 ok, 1 = exception.
+int host_particle_likelihood(void* hv, const sepaihrd_problem* pb, int device, int initial_state_mode, int J, int steps_per_interval, uint64_t seed0,
+                             const double* thetas, int B, int n_calls, double* values, int32_t* status) {
+    auto* h = static_cast<HostHandle*>(hv);
+    return guarded([&] {
+        HipParticleLikelihood lik(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * pb->n_age),
+                                  strategy_for(pb->solver), J, steps_per_interval, seed0, device, initial_state_mode);
+        const IBatchObjectiveFunction& batch = lik;
+        std::vector<int> st(static_cast<size_t>(B));
+        for (int c = 0; c < n_calls; ++c) {
+            batch.calculateBatch(thetas, B, values + static_cast<size_t>(c) * B, st.data());
+            if (status) std::copy(st.begin(), st.end(), status + static_cast<size_t>(c) * B);
+        }
     });
 }
 

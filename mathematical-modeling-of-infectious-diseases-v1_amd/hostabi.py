@@ -136,6 +136,12 @@ def load_library() -> C.CDLL:
     lib.host_stochastic_manager_values.argtypes = [vp, C.c_int, vp, vp]
     lib.host_stochastic.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int,
                                     C.c_uint64, vp, C.c_int] + [vp] * 6
+    lib.host_particle_from_values.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_uint64] + \
+        [vp] * 4 + [C.c_char_p, C.c_int]
+    lib.host_particle_resample.restype = None
+    lib.host_particle_resample.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.host_particle_likelihood.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int,
+                                             C.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -444,6 +450,20 @@ class HostObjective:
         k = nsel.value
         return {"quantiles": q, "extinct": extinct[:k].copy(), "selected": sel[:k].copy(), "status": status[:k].copy(),
                 "samples_used": used.value}
+
+    def particle_likelihood(self, thetas, J: int, steps_per_interval: int, seed0: int, n_calls: int = 1, initial_state_mode: int = 0,
+                            device: int = -1) -> dict:
+        """HipParticleLikelihood over this handle's parameter manager and data: n_calls successive calculateBatch calls on the same
+        rows of thetas; call c runs at seed0 + c.  values [n_calls][B], status [n_calls][B]."""
+        th = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        B = th.shape[0]
+        values, status = np.empty((n_calls, B)), np.empty((n_calls, B), dtype=np.int32)
+        _check(self.lib.host_particle_likelihood(self.h, C.byref(st), device, int(initial_state_mode), int(J), int(steps_per_interval),
+                                                 int(seed0) & 0xFFFFFFFFFFFFFFFF, th.ctypes.data, B, int(n_calls), values.ctypes.data,
+                                                 status.ctypes.data), "host_particle_likelihood: ")
+        return {"values": values, "status": status}
 
     def stochastic_manager_values(self, theta, mode: int) -> np.ndarray:
         """The parameter part of a model_values row of sepaihrd_ensemble_stochastic (all but the 11 n initial counts) as this
@@ -1097,6 +1117,69 @@ def stochastic_from_values(model_values, status, times, N, M, kappa_end_times, R
     out = {"quantiles": q, "extinct": extinct, "n_valid": int(np.sum(st == 0))}
     if traj is not None:
         out["traj"] = traj
+    if final is not None:
+        out["final_state"] = final
+    return out
+
+
+# ---- bootstrap particle filter of the stochastic SEPAIHRD model: the CPU twin of sepaihrd_particle_loglik ----
+def particle_max_particles(n_age: int) -> int:
+    """sepaihrd_particle_max_particles (host only): the largest J the filter takes for n_age classes; -1 outside 1..16"""
+    return int(hipabi.load_library().sepaihrd_particle_max_particles(int(n_age)))
+
+
+def particle_validate(B: int, J: int, steps_per_interval: int, n_times: int, T_pos: int, n_age: int) -> None:
+    """sepaihrd_particle_validate (host only): ValueError with its message for arguments the filter refuses"""
+    err = C.create_string_buffer(512)
+    if hipabi.load_library().sepaihrd_particle_validate(int(B), int(J), int(steps_per_interval), int(n_times), int(T_pos), int(n_age), err,
+                                                        len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def particle_resample(logw, seed: int, b: int = 0, row: int = 0) -> dict:
+    """The twin of HipObjective.particle_resample_device: ancestors [J], increment and ess of one weighted row with log-weights logw"""
+    lw = np.ascontiguousarray(logw, dtype=np.float64).ravel()
+    if lw.size < 1:
+        raise ValueError("logw must hold at least one log-weight")
+    anc = np.empty(lw.size, dtype=np.int32)
+    inc, ess = C.c_double(0.0), C.c_double(0.0)
+    load_library().host_particle_resample(int(seed) & 0xFFFFFFFFFFFFFFFF, int(b), int(row), lw.ctypes.data, lw.size, anc.ctypes.data,
+                                          C.byref(inc), C.byref(ess))
+    return {"ancestors": anc, "increment": inc.value, "ess": ess.value}
+
+
+def particle_from_values(model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J: int, steps_per_interval: int, seed: int,
+                         beta_end_times=(), want_final: bool = True) -> dict:
+    """The twin of HipObjective.particle_loglik after the decoding: from model_values [B][W] and status [B], the problem's fixed data
+    (times, N [n], M [n][n] with M[i, j] = M(i, j), the schedule end times) and the observations obs_* [n_obs][n] of the output times
+    >= 0 the same loglik [B], increments [B][T_pos], ess [B][T_pos] and final_state [B][J][11][n], bit for bit."""
+    mv = np.ascontiguousarray(np.atleast_2d(model_values), dtype=np.float64)
+    st = np.ascontiguousarray(status, dtype=np.int32).ravel()
+    tm = np.ascontiguousarray(times, dtype=np.float64).ravel()
+    Nv = np.ascontiguousarray(N, dtype=np.float64).ravel()
+    n = Nv.size
+    Mm = np.ascontiguousarray(M, dtype=np.float64)
+    be = np.ascontiguousarray(beta_end_times, dtype=np.float64).ravel()
+    ke = np.ascontiguousarray(kappa_end_times, dtype=np.float64).ravel()
+    ob = [np.ascontiguousarray(np.asarray(o, dtype=np.float64).reshape(-1, n)) for o in (obs_H, obs_ICU, obs_D)]
+    B, T, J = mv.shape[0], tm.size, int(J)
+    Tp = int(np.sum(tm >= 0.0))
+    if Mm.shape != (n, n) or st.shape != (B,) or mv.shape[1] != stochastic_values_width(n, be.size, ke.size):
+        raise ValueError("model_values [B][W], status [B], N [n], M [n][n]")
+    if not (ob[0].shape == ob[1].shape == ob[2].shape):
+        raise ValueError("obs_H, obs_ICU and obs_D must have the same shape [n_obs][n]")
+    particle_validate(B, J, steps_per_interval, T, Tp, n)
+    loglik, inc, ess = np.empty(B), np.empty((B, Tp)), np.empty((B, Tp))
+    final = np.empty((B, J, 11, n)) if want_final else None
+    err = C.create_string_buffer(512)
+    rc = load_library().host_particle_from_values(n, T, be.size, ke.size, tm.ctypes.data, Nv.ctypes.data, Mm.ctypes.data,
+                                                  be.ctypes.data if be.size else None, ke.ctypes.data, ob[0].shape[0], ob[0].ctypes.data,
+                                                  ob[1].ctypes.data, ob[2].ctypes.data, mv.ctypes.data, st.ctypes.data, B, J,
+                                                  int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, loglik.ctypes.data, inc.ctypes.data,
+                                                  ess.ctypes.data, None if final is None else final.ctypes.data, err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    out = {"loglik": loglik, "increments": inc, "ess": ess, "n_valid": int(np.sum(st == 0))}
     if final is not None:
         out["final_state"] = final
     return out
