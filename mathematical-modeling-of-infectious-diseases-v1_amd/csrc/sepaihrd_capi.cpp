@@ -107,15 +107,7 @@ struct sepaihrd_ctx {
 
 namespace {
 
-// SEPAIHRDParameterManager.cpp:302-313
-double reflect_bound_host(double value, double minb, double maxb) {
-    if (minb >= maxb) return minb;
-    const double width = maxb - minb;
-    double y = std::fmod(value - minb, 2.0 * width);
-    if (y < 0) y += 2.0 * width;
-    if (y <= width) return minb + y;
-    return maxb - (y - width);
-}
+#include "sepaihrd_constrain.inc"  // constrain: the text the kernels compile
 
 // chains per launch so that the cumulative-compartment workspace stays within the budget
 size_t chunk_chains(const sepaihrd_ctx* c, size_t B) {
@@ -307,21 +299,7 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
             set_err(err, errlen, "beta end times must be strictly increasing"); return nullptr;
         }
 
-    int ndev = 0;
-    {
-        const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) {
-            set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): "
-                                             "hipGetDeviceCount -> ") + hipGetErrorString(e) + ", count " +
-                                     std::to_string(ndev));
-            return nullptr;
-        }
-    }
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return nullptr; }
-    }
-    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return nullptr; }
+    if (select_device(device, err, errlen) != SEPAIHRD_OK) return nullptr;
 
     auto* ctx = new sepaihrd_ctx();
     ctx->device = device;
@@ -1303,18 +1281,9 @@ int sepaihrd_apply_constraints(const sepaihrd_ctx* ctx, int mode, const double* 
     if (!ctx || !in || !out || B < 0) return SEPAIHRD_E_INVALID_ARG;
     const int P = ctx->P;
     for (int b = 0; b < B; ++b)
-        for (int p = 0; p < P; ++p) {
-            const double v = in[(size_t)b * P + p];
-            double r;
-            if (ctx->has_bounds[p]) {
-                double lo = ctx->lower[p], hi = ctx->upper[p];
-                if (lo > hi) std::swap(lo, hi);
-                r = mode == SEPAIHRD_CONSTRAINT_CLAMP ? std::min(std::max(v, lo), hi) : reflect_bound_host(v, lo, hi);
-            } else {
-                r = mode == SEPAIHRD_CONSTRAINT_CLAMP ? std::max(0.0, v) : std::abs(v);
-            }
-            out[(size_t)b * P + p] = r;
-        }
+        for (int p = 0; p < P; ++p)
+            out[(size_t)b * P + p] = constrain(in[(size_t)b * P + p], ctx->lower[p], ctx->upper[p], ctx->has_bounds[p],
+                                               mode == SEPAIHRD_CONSTRAINT_CLAMP ? 0 : 1);
     return SEPAIHRD_OK;
 }
 

@@ -211,27 +211,7 @@ constexpr double b6 = 34.0 / 105, b7 = 9.0 / 35, b8 = 9.0 / 35, b9 = 9.0 / 280, 
 constexpr double db1 = -41.0 / 840, db11 = -41.0 / 840, db12 = 41.0 / 840, db13 = 41.0 / 840;
 }  // namespace f78
 
-// SEPAIHRDParameterManager.cpp:302-313 / :326-343
-__device__ __forceinline__ double reflect_bound(double value, double minb, double maxb) {
-    if (minb >= maxb) return minb;
-    const double width = maxb - minb;
-    double y = fmod(value - minb, 2.0 * width);
-    if (y < 0) y += 2.0 * width;
-    if (y <= width) return minb + y;
-    return maxb - (y - width);
-}
-__device__ __forceinline__ double constrain(double v, double lo, double hi, int has_bounds, int mode) {
-    if (has_bounds) {
-        if (lo > hi) { const double t = lo; lo = hi; hi = t; }
-        if (mode == 0) {
-            const double m = (v < lo) ? lo : v;  // std::max(v, lo)
-            return (hi < m) ? hi : m;            // std::min(m, hi)
-        }
-        return reflect_bound(v, lo, hi);
-    }
-    if (mode == 0) return (0.0 < v) ? v : 0.0;  // std::max(0.0, v)
-    return fabs(v);
-}
+#include "sepaihrd_constrain.inc"  // reflect_bound, constrain: the one text of the constraint rule
 
 // Merged beta*kappa schedule of one chain.  Segment j = (mends[j-1], mends[j]], value index = #(mends < t).
 struct Schedule {

@@ -1,6 +1,7 @@
 // csrc/sepaihrd_device.h -- structures shared by the C-ABI host code (sepaihrd_capi.cpp)
 // and the HIP kernels (sepaihrd_kernels.hip).  Internal: not part of the C ABI.
 #pragma once
+#define SEPAIHRD_HAVE_DEV_PROBLEM 1  // csrc/sepaihrd_constrain.inc adds its DevProblem part where this is set
 #include <stdint.h>
 
 namespace sepaihrd {

@@ -113,37 +113,7 @@ __global__ __launch_bounds__(WAVE) void ensemble_series_kernel(const EnsembleArg
     }
 }
 
-// SEPAIHRDParameterManager.cpp:302-313 / :326-343 (same code as the evaluation kernel's)
-__device__ __forceinline__ double ens_reflect_bound(double value, double minb, double maxb) {
-    if (minb >= maxb) return minb;
-    const double width = maxb - minb;
-    double y = fmod(value - minb, 2.0 * width);
-    if (y < 0) y += 2.0 * width;
-    if (y <= width) return minb + y;
-    return maxb - (y - width);
-}
-__device__ __forceinline__ double ens_constrain(const DevProblem& pb, const double* th, int p) {
-    const double v = th[p];
-    double lo = pb.lower[p], hi = pb.upper[p];
-    if (pb.has_bounds[p]) {
-        if (lo > hi) { const double t = lo; lo = hi; hi = t; }
-        if (pb.constraint_mode == 0) {
-            const double m = (v < lo) ? lo : v;
-            return (hi < m) ? hi : m;
-        }
-        return ens_reflect_bound(v, lo, hi);
-    }
-    if (pb.constraint_mode == 0) return (0.0 < v) ? v : 0.0;
-    return fabs(v);
-}
-__device__ __forceinline__ double ens_scalar(const DevProblem& pb, const double* th, int slot) {
-    const int src = pb.src_scalar[slot];
-    return src >= 0 ? ens_constrain(pb, th, src) : pb.base_scalar[slot];
-}
-__device__ __forceinline__ double ens_vec(const DevProblem& pb, const double* th, int field, int age) {
-    const int src = pb.src_vec[field * pb.lpc + age];
-    return src >= 0 ? ens_constrain(pb, th, src) : pb.base_vec[field * pb.lpc + age];
-}
+#include "sepaihrd_constrain.inc"  // slot_scalar, slot_vec: theta decoded under the text the evaluation kernels compile
 
 // Effective reproduction number of sample s at output time k
 // (ReproductionNumberCalculator::calculateRt, src/model/ReproductionNumberCalculator.cpp:55-92,95-171):
@@ -168,19 +138,19 @@ __global__ __launch_bounds__(WAVE) void ensemble_rt_kernel(const EnsembleArgs a,
     const double t = pb.times[k];
     int seg = 0;
     for (int j = 0; j < pb.nm; ++j) seg += (pb.mends[j] < t) ? 1 : 0;
-    const double beta = (pb.nb > 0) ? ens_scalar(pb, th, SS_SCHEDULE0 + pb.seg_ib[seg]) : ens_scalar(pb, th, SS_BETA);
-    const double kappa = ens_scalar(pb, th, SS_SCHEDULE0 + pb.nb + pb.seg_ik[seg]);
-    const double theta_i = ens_scalar(pb, th, SS_THETA);
-    const double gamma_p = ens_scalar(pb, th, SS_GAMMA_P), gamma_A = ens_scalar(pb, th, SS_GAMMA_A),
-                 gamma_I = ens_scalar(pb, th, SS_GAMMA_I);
+    const double beta = (pb.nb > 0) ? slot_scalar(pb, th, SS_SCHEDULE0 + pb.seg_ib[seg]) : slot_scalar(pb, th, SS_BETA);
+    const double kappa = slot_scalar(pb, th, SS_SCHEDULE0 + pb.nb + pb.seg_ik[seg]);
+    const double theta_i = slot_scalar(pb, th, SS_THETA);
+    const double gamma_p = slot_scalar(pb, th, SS_GAMMA_P), gamma_A = slot_scalar(pb, th, SS_GAMMA_A),
+                 gamma_I = slot_scalar(pb, th, SS_GAMMA_I);
     const double* row = a.traj + ((size_t)s * a.T + k) * (NUM_COMP * n);  // S block first
     double ci[RT_MAX_AGE], gj[RT_MAX_AGE], v[RT_MAX_AGE], w[RT_MAX_AGE];
     for (int i = 0; i < n; ++i) {
-        ci[i] = beta * kappa * ens_vec(pb, th, VF_A, i) * row[i];  // beta kappa a_i S_i
+        ci[i] = beta * kappa * slot_vec(pb, th, VF_A, i) * row[i];  // beta kappa a_i S_i
         const double Nj = pb.N[i];
-        const double pj = ens_vec(pb, th, VF_P, i), hj = ens_vec(pb, th, VF_H, i);
+        const double pj = slot_vec(pb, th, VF_P, i), hj = slot_vec(pb, th, VF_H, i);
         const double dwell = 1.0 / gamma_p + pj / gamma_A + theta_i * (1.0 - pj) / (gamma_I + hj);
-        gj[i] = (Nj < 1e-9) ? 0.0 : ens_vec(pb, th, VF_H_INFEC, i) / Nj * dwell;
+        gj[i] = (Nj < 1e-9) ? 0.0 : slot_vec(pb, th, VF_H_INFEC, i) / Nj * dwell;
         v[i] = 1.0;
     }
     double lambda = 0.0;
@@ -225,9 +195,9 @@ __global__ __launch_bounds__(WAVE) void ensemble_metrics_kernel(const EnsembleAr
         return;
     }
     const double* th = theta + (size_t)s * pb.P;
-    const double beta_c = ens_scalar(pb, th, SS_BETA), theta_i = ens_scalar(pb, th, SS_THETA);
-    const double gamma_p = ens_scalar(pb, th, SS_GAMMA_P), gamma_A = ens_scalar(pb, th, SS_GAMMA_A),
-                 gamma_I = ens_scalar(pb, th, SS_GAMMA_I);
+    const double beta_c = slot_scalar(pb, th, SS_BETA), theta_i = slot_scalar(pb, th, SS_THETA);
+    const double gamma_p = slot_scalar(pb, th, SS_GAMMA_P), gamma_A = slot_scalar(pb, th, SS_GAMMA_A),
+                 gamma_I = slot_scalar(pb, th, SS_GAMMA_I);
     const double* traj = a.traj + (size_t)s * a.T * (NUM_COMP * n);
     const double* rt = a.vals + (size_t)a.rt_segment0 * a.S_pad + s;  // Rt(s, k) at stride S_pad
     double total_pop = 0.0;
@@ -238,14 +208,14 @@ __global__ __launch_bounds__(WAVE) void ensemble_metrics_kernel(const EnsembleAr
     {
         int seg = 0;
         for (int j = 0; j < pb.nm; ++j) seg += (pb.mends[j] < 0.0) ? 1 : 0;
-        const double beta0 = (pb.nb > 0) ? ens_scalar(pb, th, SS_SCHEDULE0 + pb.seg_ib[seg]) : beta_c;
-        const double kappa0 = ens_scalar(pb, th, SS_SCHEDULE0 + pb.nb + pb.seg_ik[seg]);
+        const double beta0 = (pb.nb > 0) ? slot_scalar(pb, th, SS_SCHEDULE0 + pb.seg_ib[seg]) : beta_c;
+        const double kappa0 = slot_scalar(pb, th, SS_SCHEDULE0 + pb.nb + pb.seg_ik[seg]);
         double ci[RT_MAX_AGE], gj[RT_MAX_AGE], v[RT_MAX_AGE], w[RT_MAX_AGE];
         for (int i = 0; i < n; ++i) {
-            ci[i] = beta0 * kappa0 * ens_vec(pb, th, VF_A, i) * pb.N[i];
-            const double pj = ens_vec(pb, th, VF_P, i), hj = ens_vec(pb, th, VF_H, i);
+            ci[i] = beta0 * kappa0 * slot_vec(pb, th, VF_A, i) * pb.N[i];
+            const double pj = slot_vec(pb, th, VF_P, i), hj = slot_vec(pb, th, VF_H, i);
             const double dwell = 1.0 / gamma_p + pj / gamma_A + theta_i * (1.0 - pj) / (gamma_I + hj);
-            gj[i] = (pb.N[i] < 1e-9) ? 0.0 : ens_vec(pb, th, VF_H_INFEC, i) / pb.N[i] * dwell;
+            gj[i] = (pb.N[i] < 1e-9) ? 0.0 : slot_vec(pb, th, VF_H_INFEC, i) / pb.N[i] * dwell;
             v[i] = 1.0;
         }
         for (int it = 0; it < 2000; ++it) {
@@ -294,7 +264,7 @@ __global__ __launch_bounds__(WAVE) void ensemble_metrics_kernel(const EnsembleAr
         if (tot_icu > peak_icu) { peak_icu = tot_icu; t_peak_icu = t; }
         int seg = 0;
         for (int j = 0; j < pb.nm; ++j) seg += (pb.mends[j] < t) ? 1 : 0;
-        const double kappa = ens_scalar(pb, th, SS_SCHEDULE0 + pb.nb + pb.seg_ik[seg]);
+        const double kappa = slot_scalar(pb, th, SS_SCHEDULE0 + pb.nb + pb.seg_ik[seg]);
         for (int i = 0; i < n; ++i) {
             double acc = 0.0;
             for (int j = 0; j < n; ++j) {

@@ -1,5 +1,5 @@
 // csrc/sepaihrd_host_util.h -- what the host side of the C ABI does the same way in every entry point: the error text, the
-// buffers of one call, the buffers a context keeps between calls, the copies of the results.  Host code only.
+// choice of the device, the buffers of one call, the buffers a context keeps between calls, the copies of the results.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,22 @@ namespace sepaihrd {
 
 inline void set_err(char* err, int errlen, const std::string& msg) {
     if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
+}
+
+// Pick and open the device of a context or of a one-off call: `device` < 0 stands for the current one and is replaced by its
+// index.  SEPAIHRD_OK, or the code of the refusal with its text in err.
+inline int select_device(int& device, char* err, int errlen) {
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): hipGetDeviceCount -> ") +
+                                 hipGetErrorString(e) + ", count " + std::to_string(ndev));
+        return SEPAIHRD_E_NO_DEVICE;
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return SEPAIHRD_E_HIP; }
+    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return SEPAIHRD_E_INVALID_ARG; }
+    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return SEPAIHRD_E_HIP; }
+    return SEPAIHRD_OK;
 }
 
 inline bool probabilities_valid(const double* probs, int n_probs) {

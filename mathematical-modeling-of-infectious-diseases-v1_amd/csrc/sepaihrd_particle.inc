@@ -40,7 +40,7 @@ using sepaihrd_stoch::exp_nonpositive;
 
 constexpr double SIM_FLOOR = 1e-10;
 constexpr uint32_t RESAMPLE_STEP = 0xFFFFFFFFu, RESAMPLE_TRANSITION = 13u;
-constexpr int NUM_PREV = 3;  // the previous-row values a particle carries: CumH, CumICU, D
+using sepaihrd_stoch_epi::NUM_PREV;  // the previous-row values a particle carries: CumH, CumICU, D (take_increments)
 
 // finite and >= 0 (a NaN fails the first comparison, +inf the second)
 SEP_RNG_FN bool usable(double obs) { return obs >= 0.0 && obs <= 1.7976931348623157e308; }

@@ -148,16 +148,7 @@ extern "C" int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, 
 
 extern "C" int sepaihrd_poisson_device(int device, uint64_t seed, const double* lambda, int count, double* out, char* err, int errlen) {
     if (!lambda || !out || count < 1) { set_err(err, errlen, "poisson_device: need lambda, out and count >= 1"); return SEPAIHRD_E_INVALID_ARG; }
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): hipGetDeviceCount -> ") +
-                                 hipGetErrorString(e) + ", count " + std::to_string(ndev));
-        return SEPAIHRD_E_NO_DEVICE;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return SEPAIHRD_E_HIP; }
-    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return SEPAIHRD_E_INVALID_ARG; }
-    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return SEPAIHRD_E_HIP; }
+    if (const int drc = select_device(device, err, errlen)) return drc;
     CallScratch sc;
     double *d_lambda = nullptr, *d_out = nullptr;
     if (!sc.alloc(&d_lambda, (size_t)count) || !sc.alloc(&d_out, (size_t)count)) {

@@ -35,27 +35,7 @@
 namespace sepaihrd {
 namespace {
 
-// SEPAIHRDParameterManager.cpp:302-313 / :326-343 (same code as the evaluation kernel's)
-__device__ __forceinline__ double reflect_bound(double value, double minb, double maxb) {
-    if (minb >= maxb) return minb;
-    const double width = maxb - minb;
-    double y = fmod(value - minb, 2.0 * width);
-    if (y < 0) y += 2.0 * width;
-    if (y <= width) return minb + y;
-    return maxb - (y - width);
-}
-__device__ __forceinline__ double constrain(double v, double lo, double hi, int has_bounds, int mode) {
-    if (has_bounds) {
-        if (lo > hi) { const double t = lo; lo = hi; hi = t; }
-        if (mode == 0) {
-            const double m = (v < lo) ? lo : v;
-            return (hi < m) ? hi : m;
-        }
-        return reflect_bound(v, lo, hi);
-    }
-    if (mode == 0) return (0.0 < v) ? v : 0.0;
-    return fabs(v);
-}
+#include "sepaihrd_constrain.inc"  // reflect_bound, constrain: the text the evaluation kernels compile
 
 // where state `row` of chain c lives: its ring slot, and its place in the sample store (nullptr: not a stored state)
 __device__ __forceinline__ double* ring_row(const SamplerState& s, const int c, const int row) {

@@ -110,18 +110,7 @@ sepaihrd_sir_ctx* sepaihrd_sir_create(const sepaihrd_sir_problem* pb, int device
         }
     }
 
-    int ndev = 0;
-    {
-        const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0) {
-            set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): hipGetDeviceCount -> ") +
-                                     hipGetErrorString(e) + ", count " + std::to_string(ndev));
-            return nullptr;
-        }
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return nullptr; }
-    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return nullptr; }
+    if (select_device(device, err, errlen) != SEPAIHRD_OK) return nullptr;
 
     auto* ctx = new sepaihrd_sir_ctx();
     ctx->device = device; ctx->solver = pb->solver; ctx->arith = pb->arith;

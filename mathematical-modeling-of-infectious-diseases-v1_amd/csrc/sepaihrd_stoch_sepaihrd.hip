@@ -1,16 +1,17 @@
 // csrc/sepaihrd_stoch_sepaihrd.hip -- stochastic chain-binomial SEPAIHRD ensembles over posterior samples on gfx950
 // (sepaihrd_ensemble_stochastic): the decode kernel (theta -> model values, rounded initial state, status)
-// and the step kernel.  The model and its stream coordinates are csrc/sepaihrd_stoch_sepaihrd.inc, the text the host twin
-// compiles too; the segment sorts and the quantiles are csrc/sepaihrd_ensemble.hip's.  Compiled with -ffp-contract=off.
+// and the step kernel.  The model, its stream coordinates and the walk through one output interval (lane_interval) are
+// csrc/sepaihrd_stoch_sepaihrd.inc, the text the host twin compiles too; the constraint rule of the decode is
+// csrc/sepaihrd_constrain.inc, the text of every other kernel and of the host; the segment sorts and the quantiles are csrc/sepaihrd_ensemble.hip's.  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include <cstdio>
 #include <string>
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_hip.h"
+#include "sepaihrd_host_util.h"
 #include "sepaihrd_stoch_sepaihrd.inc"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
@@ -21,27 +22,7 @@ namespace epi = sepaihrd_stoch_epi;
 
 constexpr int STEP_BLOCK = 256;
 
-// SEPAIHRDParameterManager.cpp:302-313 / :326-343, as csrc/sepaihrd_dev_common.inc states them for the integrators
-__device__ double reflect_bound(double value, double minb, double maxb) {
-    if (minb >= maxb) return minb;
-    const double width = maxb - minb;
-    double y = fmod(value - minb, 2.0 * width);
-    if (y < 0) y += 2.0 * width;
-    if (y <= width) return minb + y;
-    return maxb - (y - width);
-}
-__device__ double constrain(double v, double lo, double hi, int has_bounds, int mode) {
-    if (has_bounds) {
-        if (lo > hi) { const double t = lo; lo = hi; hi = t; }
-        if (mode == 0) {
-            const double m = (v < lo) ? lo : v;
-            return (hi < m) ? hi : m;
-        }
-        return reflect_bound(v, lo, hi);
-    }
-    if (mode == 0) return (0.0 < v) ? v : 0.0;
-    return fabs(v);
-}
+#include "sepaihrd_constrain.inc"  // slot_scalar, slot_vec: theta decoded under the text the evaluation kernels compile
 
 // One thread per sample: the row of model values after the constraints of the context's mode, the initial state by the
 // context's initial-state rule (csrc/sepaihrd_kernels.hip, section 3 of its prologue) rounded entry by entry, and the status.
@@ -50,15 +31,7 @@ __global__ __launch_bounds__(256) void stoch_epi_decode_kernel(const DevProblem 
     if (s >= a.S) return;
     const double* th = a.theta + (size_t)s * pb.P;
     const int n = pb.n, lpc = pb.lpc;
-    auto from_theta = [&](int src) { return constrain(th[src], pb.lower[src], pb.upper[src], pb.has_bounds[src], pb.constraint_mode); };
-    auto scalar_slot = [&](int slot) -> double {
-        const int src = pb.src_scalar[slot];
-        return src >= 0 ? from_theta(src) : pb.base_scalar[slot];
-    };
-    auto vec_slot = [&](int field, int age) -> double {
-        const int src = pb.src_vec[field * lpc + age];
-        return src >= 0 ? from_theta(src) : pb.base_vec[field * lpc + age];
-    };
+    auto scalar_slot = [&](int slot) { return slot_scalar(pb, th, slot); };
     const epi::RowLayout L{n, pb.nb, pb.nk};
     double* row = a.values + (size_t)s * a.W;
     row[epi::R_THETA] = scalar_slot(SS_THETA);
@@ -72,7 +45,7 @@ __global__ __launch_bounds__(256) void stoch_epi_decode_kernel(const DevProblem 
     for (int k = 0; k < pb.nb; ++k) row[L.beta_values() + k] = scalar_slot(SS_SCHEDULE0 + k);
     for (int k = 0; k < pb.nk; ++k) row[L.kappa_values() + k] = scalar_slot(SS_SCHEDULE0 + pb.nb + k);
     for (int f = 0; f < VF_COUNT; ++f)
-        for (int i = 0; i < n; ++i) row[L.vec(f, i)] = vec_slot(f, i);
+        for (int i = 0; i < n; ++i) row[L.vec(f, i)] = slot_vec(pb, th, f, i);
 
     int status = 0;
     if (pb.kappa_calibrated)
@@ -145,16 +118,14 @@ __global__ __launch_bounds__(STEP_BLOCK) void stoch_epi_step_kernel(const DevPro
     int32_t x[epi::NUM_COMP];
 #pragma unroll
     for (int c = 0; c < epi::NUM_COMP; ++c) x[c] = ok ? (int32_t)row[L.initial(c, row_age)] : 0;
-    const double theta = row[epi::R_THETA], h_infec = row[L.vec(epi::V_H_INFEC, row_age)], a_i = row[L.vec(epi::V_A, row_age)];
-    const double Ni = pb.N[age];
-    const double* Mrow = pb.Mrow + (size_t)age * lpc;
+    const epi::LaneConstants lc = epi::lane_constants(row, L, pb.N, pb.Mrow, lpc, age);  // after the counts: before them, one SGPR spill more
     const double qnan = __builtin_nan("");
     const double pinf = __builtin_inf();
     const size_t seg_stride = (size_t)a.N_pad, cum_block = (size_t)3 * Tp * n;
     const bool want_traj = a.traj != nullptr && in_range && real_age && r < (uint32_t)a.keep;
     double* traj = want_traj ? a.traj + ((s * (size_t)a.keep + r) * T) * (size_t)(epi::NUM_COMP * n) + age : nullptr;
 
-    int32_t prevH = x[epi::C_CUM_H], prevICU = x[epi::C_CUM_ICU], prevD = x[epi::C_D];
+    int32_t prev[epi::NUM_PREV] = {x[epi::C_CUM_H], x[epi::C_CUM_ICU], x[epi::C_D]};
     double run[3] = {0.0, 0.0, 0.0};
     auto write_row = [&](int k) {
         if (want_traj) {
@@ -162,8 +133,9 @@ __global__ __launch_bounds__(STEP_BLOCK) void stoch_epi_step_kernel(const DevPro
 #pragma unroll
             for (int c = 0; c < epi::NUM_COMP; ++c) dst[(size_t)c * n] = ok ? (double)x[c] : qnan;
         }
-        const double inc[3] = {(double)(x[epi::C_CUM_H] - prevH), (double)(x[epi::C_CUM_ICU] - prevICU), (double)(x[epi::C_D] - prevD)};
-        prevH = x[epi::C_CUM_H]; prevICU = x[epi::C_CUM_ICU]; prevD = x[epi::C_D];
+        int32_t since[epi::NUM_PREV];
+        epi::take_increments(x, prev, since);
+        const double inc[3] = {(double)since[0], (double)since[1], (double)since[2]};
         const int t = k - pb.runup_offset;
         if (t < 0 || !real_age) return;
 #pragma unroll
@@ -179,15 +151,8 @@ __global__ __launch_bounds__(STEP_BLOCK) void stoch_epi_step_kernel(const DevPro
         const double t0 = pb.times[k];
         const double h = (pb.times[k + 1] - t0) / (double)a.m;
         const epi::AgeProbs q = epi::age_probs(row, L, row_age, h);
-        for (int j = 0; j < a.m; ++j) {
-            const double t_mid = t0 + ((double)j + 0.5) * h;
-            const double bk = epi::beta_kappa(row, L, pb.beta_ends, pb.kappa_ends, t_mid);
-            const double inf = epi::infectious_pressure(x, theta, h_infec, Ni);
-            double sum = 0.0;
-            for (int jj = 0; jj < n; ++jj) sum += Mrow[jj] * __shfl(inf, jj, lpc);
-            const double lambda = epi::force_of_infection(sum, bk, a_i);
-            epi::age_step(x, lambda, h, q, a.seed, (uint32_t)s, r, (uint32_t)(k * a.m + j), (uint32_t)age);
-        }
+        epi::lane_interval(x, row, L, lc, pb.beta_ends, pb.kappa_ends, t0, h, q, a.m, a.seed, (uint32_t)s, r, (uint32_t)(k * a.m), (uint32_t)age,
+                           [lpc](double inf, int jj) { return __shfl(inf, jj, lpc); });
         write_row(k + 1);
     }
     if (a.final_state != nullptr && in_range && real_age) {
@@ -198,10 +163,6 @@ __global__ __launch_bounds__(STEP_BLOCK) void stoch_epi_step_kernel(const DevPro
     const bool infected = (x[epi::C_E] | x[epi::C_P] | x[epi::C_A] | x[epi::C_I]) != 0;  // counts are >= 0
     const bool any_infected = (__ballot(infected) & group_mask) != 0ull;
     if (ok && age == 0 && !any_infected) atomicAdd(a.extinct_count + s, 1);
-}
-
-void set_err(char* err, int errlen, const std::string& msg) {
-    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", msg.c_str());
 }
 
 }  // namespace
@@ -228,6 +189,15 @@ int launch_stoch_epi_steps(const DevProblem& pb, const StochEpiArgs& a, void* st
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+const char* stoch_epi_grid_refusal(int steps_per_interval, int n_times, int T_pos, int n_age) {
+    if (steps_per_interval < 1) return "steps_per_interval must be >= 1";
+    if (n_times < 1 || T_pos < 1 || T_pos > n_times) return "need n_times >= T_pos >= 1 (an output time >= 0)";
+    if (n_age < 1) return "n_age must be >= 1";
+    if ((uint64_t)n_times * (uint64_t)steps_per_interval >= ((uint64_t)1 << 22))
+        return "n_times x steps_per_interval must stay below 2^22 (the third stream coordinate)";
+    return nullptr;
+}
+
 }  // namespace sepaihrd
 
 using namespace sepaihrd;
@@ -242,15 +212,11 @@ extern "C" int sepaihrd_stochastic_validate(int S, int R, int steps_per_interval
     auto refuse = [&](const std::string& msg) { set_err(err, errlen, "ensemble_stochastic: " + msg); return SEPAIHRD_E_INVALID_ARG; };
     if (S < 1) return refuse("S must be >= 1 (samples)");
     if (R < 1) return refuse("R must be >= 1 (replicates per sample)");
-    if (steps_per_interval < 1) return refuse("steps_per_interval must be >= 1");
     if (keep < 0 || keep > R) return refuse("keep must lie in [0, R]");
     const uint64_t N = (uint64_t)S * (uint64_t)R;
     if (N >= ((uint64_t)1 << 31) || (N + WAVE - 1) / WAVE * WAVE >= ((uint64_t)1 << 31))
         return refuse("S x R rounded up to whole wavefronts must stay below 2^31 (replicates per segment)");
-    if (n_times < 1 || T_pos < 1 || T_pos > n_times) return refuse("need n_times >= T_pos >= 1 (an output time >= 0)");
-    if (n_age < 1) return refuse("n_age must be >= 1");
-    if ((uint64_t)n_times * (uint64_t)steps_per_interval >= ((uint64_t)1 << 22))
-        return refuse("n_times x steps_per_interval must stay below 2^22 (the third stream coordinate)");
+    if (const char* grid = stoch_epi_grid_refusal(steps_per_interval, n_times, T_pos, n_age)) return refuse(grid);
     if (!probs || n_probs < 1 || n_probs > 1024) return refuse("need probs (1..1024)");
     for (int p = 0; p < n_probs; ++p)
         if (!(probs[p] >= 0.0 && probs[p] <= 1.0)) return refuse("probabilities must lie in [0, 1]");

@@ -24,7 +24,8 @@
 // sample's position, r the replicate -- the Coord of csrc/sepaihrd_stoch.inc with replicate = s, step = r and
 // 2 group + transition carrying the packed third word.  T m < 2^22 keeps that word below 2^32.
 // Only correctly rounded IEEE operations and glibc_log / glibc_exp: both sides compile with contraction off.
-// Included by csrc/sepaihrd_stoch_sepaihrd.hip and by the host library (host/src/HipStochasticSEPAIHRD.cpp).
+// Included by csrc/sepaihrd_stoch_sepaihrd.hip, csrc/sepaihrd_particle.hip (through csrc/sepaihrd_particle.inc) and by the host
+// library (host/src/StochasticSEPAIHRDTwin.hpp: HipStochasticSEPAIHRD.cpp, HipParticleFilter.cpp).
 #pragma once
 #include "sepaihrd_stoch.inc"
 
@@ -175,6 +176,78 @@ SEP_RNG_FN void age_step(int32_t* x, double lambda, double h, const AgeProbs& q,
     add(C_D, d7 + d10 + d12, 0u);
     add(C_CUM_H, d6, 0u);
     add(C_CUM_ICU, d9, 0u);
+}
+
+// ---- One output interval (t0, t0 + m h]: m steps from the counts at its start; step j takes beta kappa at its midpoint
+// t0 + (j + 0.5) h, sums the contacts over jj = 0 .. n - 1 ascending and draws at the step coordinate first_step + j (first_step =
+// k m for the interval that begins at times[k]).  q holds age_probs(row, L, age, h) of the interval.  Two forms of ONE walk:
+// what the "device equals twin" and the "a particle is a replicate" tests compare bit for bit is that the two agree.
+
+// What a lane of lane_interval keeps of its age class for the whole run.  Lanes of padded ages (age >= n) read age 0's entries
+// of the row and use none of them; N and M are padded to lpc (N [lpc], M [lpc][lpc] row-major).
+struct LaneConstants {
+    double theta, h_infec, a_i, Ni;
+    const double* Mrow;  // M(age, .)
+    int row_age;
+};
+SEP_RNG_FN LaneConstants lane_constants(const double* row, const RowLayout& L, const double* N, const double* M, int lpc, int age) {
+    LaneConstants c;
+    c.row_age = age < L.n ? age : 0;
+    c.theta = row[R_THETA];
+    c.h_infec = row[L.vec(V_H_INFEC, c.row_age)];
+    c.a_i = row[L.vec(V_A, c.row_age)];
+    c.Ni = N[age];
+    c.Mrow = M + (size_t)age * lpc;
+    return c;
+}
+
+// Lane form: the caller is age class `age` of replicate r of sample s and holds its 11 counts x; exchange(inf, jj) returns the
+// infectious pressure of age class jj of the same replicate (stoch_epi_step_kernel: __shfl(inf, jj, lpc); particle_filter_kernel writes the same walk out, see csrc/sepaihrd_particle.hip).  all_ages_interval below is
+// the same walk with every age class in one caller.
+template <class Exchange>
+SEP_RNG_FN void lane_interval(int32_t* x, const double* row, const RowLayout& L, const LaneConstants& c, const double* beta_ends,
+                              const double* kappa_ends, double t0, double h, const AgeProbs& q, int m, uint64_t seed, uint32_t s, uint32_t r,
+                              uint32_t first_step, uint32_t age, Exchange exchange) {
+    for (int j = 0; j < m; ++j) {
+        const double t_mid = t0 + ((double)j + 0.5) * h;
+        const double bk = beta_kappa(row, L, beta_ends, kappa_ends, t_mid);
+        const double inf = infectious_pressure(x, c.theta, c.h_infec, c.Ni);
+        double sum = 0.0;
+        for (int jj = 0; jj < L.n; ++jj) sum += c.Mrow[jj] * exchange(inf, jj);
+        const double lambda = force_of_infection(sum, bk, c.a_i);
+        age_step(x, lambda, h, q, seed, s, r, first_step + (uint32_t)j, age);
+    }
+}
+
+// All-ages form: the counts of age class i are x + i * stride, its probabilities q[i]; N [n], M [n][n] row-major.  Per step the
+// pressures of all ages, then the lambdas of all ages, then the steps: lane_interval above with the exchange done in memory.
+SEP_RNG_FN void all_ages_interval(int32_t* x, int stride, const double* row, const RowLayout& L, const double* N, const double* M,
+                                  const double* beta_ends, const double* kappa_ends, double t0, double h, const AgeProbs* q, int m,
+                                  uint64_t seed, uint32_t s, uint32_t r, uint32_t first_step) {
+    const int n = L.n;
+    double lambda[MAX_AGES], pressure[MAX_AGES];
+    for (int j = 0; j < m; ++j) {
+        const double t_mid = t0 + ((double)j + 0.5) * h;
+        const double bk = beta_kappa(row, L, beta_ends, kappa_ends, t_mid);
+        for (int i = 0; i < n; ++i) pressure[i] = infectious_pressure(x + i * stride, row[R_THETA], row[L.vec(V_H_INFEC, i)], N[i]);
+        for (int i = 0; i < n; ++i) {
+            double sum = 0.0;
+            for (int jj = 0; jj < n; ++jj) sum += M[(size_t)i * n + jj] * pressure[jj];
+            lambda[i] = force_of_infection(sum, bk, row[L.vec(V_A, i)]);
+        }
+        for (int i = 0; i < n; ++i) age_step(x + i * stride, lambda[i], h, q[i], seed, s, r, first_step + (uint32_t)j, (uint32_t)i);
+    }
+}
+
+// The observed series of an age class are the increments of CumH, CumICU and D between output rows (in that order): inc = the
+// counts now less prev, and prev takes the counts now.
+constexpr int NUM_PREV = 3;
+SEP_RNG_FN void take_increments(const int32_t* x, int32_t* prev, int32_t* inc) {
+    const int32_t now[NUM_PREV] = {x[C_CUM_H], x[C_CUM_ICU], x[C_D]};
+    for (int ser = 0; ser < NUM_PREV; ++ser) {
+        inc[ser] = now[ser] - prev[ser];
+        prev[ser] = now[ser];
+    }
 }
 
 // a rounded initial count is usable when it lies in [0, 2^31 - 1] (a NaN is not)

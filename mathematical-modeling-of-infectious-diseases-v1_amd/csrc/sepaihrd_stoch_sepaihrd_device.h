@@ -26,5 +26,8 @@ struct StochEpiArgs {
 int launch_stoch_epi_decode(const DevProblem& pb, const StochEpiArgs& a, void* stream);
 // the step kernel: one lane per (replicate, age class)
 int launch_stoch_epi_steps(const DevProblem& pb, const StochEpiArgs& a, void* stream);
+// What sepaihrd_stochastic_validate and sepaihrd_particle_validate check alike -- the steps per interval, the output times, the
+// age classes and the 2^22 bound of the step coordinate: the first refusal's text (without the caller's prefix), or nullptr.
+const char* stoch_epi_grid_refusal(int steps_per_interval, int n_times, int T_pos, int n_age);
 
 }  // namespace sepaihrd

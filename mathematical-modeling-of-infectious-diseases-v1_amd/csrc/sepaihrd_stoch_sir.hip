@@ -86,20 +86,6 @@ __global__ __launch_bounds__(STEP_BLOCK) void stoch_binomial_probe_kernel(uint64
     out[i] = sepaihrd_stoch::binomial(c, n[i], p[i]);
 }
 
-int select_device(int device, char* err, int errlen) {
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        set_err(err, errlen, std::string("no HIP device available (this library has no CPU fallback): hipGetDeviceCount -> ") +
-                                 hipGetErrorString(e) + ", count " + std::to_string(ndev));
-        return SEPAIHRD_E_NO_DEVICE;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { set_err(err, errlen, "hipGetDevice failed"); return SEPAIHRD_E_HIP; }
-    if (device >= ndev) { set_err(err, errlen, "device index out of range"); return SEPAIHRD_E_INVALID_ARG; }
-    if (hipSetDevice(device) != hipSuccess) { set_err(err, errlen, "hipSetDevice failed"); return SEPAIHRD_E_HIP; }
-    return SEPAIHRD_OK;
-}
-
 }  // namespace
 }  // namespace sepaihrd
 

@@ -1,12 +1,13 @@
 // host/src/HipParticleFilter.cpp -- HipParticleLikelihood and the CPU twin of sepaihrd_particle_loglik's filter kernel.  The
-// filter's rules are csrc/sepaihrd_particle.inc, the model, the stream and the sampler csrc/sepaihrd_stoch_sepaihrd.inc and
-// csrc/sepaihrd_stoch.inc: the text the kernel compiles; this library is built with -ffp-contract=off like the kernel.
+// filter's rules are csrc/sepaihrd_particle.inc, the model, its interval walk (all_ages_interval), the stream and the sampler
+// csrc/sepaihrd_stoch_sepaihrd.inc and csrc/sepaihrd_stoch.inc: the text the kernel compiles; what this twin shares with
+// hostStochasticSEPAIHRD is host/src/StochasticSEPAIHRDTwin.hpp; this library is built with -ffp-contract=off like the kernel.
 #include "epidemic_hip/HipParticleFilter.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <limits>
 
+#include "StochasticSEPAIHRDTwin.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_particle.inc"
 
@@ -19,29 +20,18 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                        const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
                        double* ess, double* final_state, std::string* error) {
     char msg[256] = "";
-    int T_pos = 0;
-    for (int k = 0; k < pb.n_times && pb.times; ++k) T_pos += pb.times[k] >= 0.0;
-    int vrc = sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, T_pos, pb.n_age, msg, (int)sizeof(msg));
-    auto refuse = [&](const char* what) {
-        std::snprintf(msg, sizeof(msg), "particle_loglik: %s", what);
-        vrc = SEPAIHRD_E_INVALID_ARG;
-    };
-    if (vrc == SEPAIHRD_OK && (!model_values || !status || !loglik)) refuse("model_values, status and loglik must not be NULL");
-    if (vrc == SEPAIHRD_OK && (!pb.N || !pb.M || !pb.kappa_end_times || pb.n_kappa < 1 || pb.n_beta < 0 || (pb.n_beta > 0 && !pb.beta_end_times)))
-        refuse("the fixed data need N, M and the schedule end times (n_kappa >= 1)");
-    if (vrc == SEPAIHRD_OK && (obs.n_obs < 0 || (obs.n_obs > 0 && (!obs.obs_H || !obs.obs_ICU || !obs.obs_D))))
-        refuse("the observations need obs_H, obs_ICU and obs_D");
-    if (vrc != SEPAIHRD_OK) {
-        if (error) *error = msg;
-        return vrc;
-    }
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    const int vrc = stoch_twin::verdict(
+        "particle_loglik", sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg,
+        {{!model_values || !status || !loglik, "model_values, status and loglik must not be NULL"},
+         {stoch_twin::fixed_data_missing(pb), stoch_twin::FIXED_DATA_TEXT},
+         {obs.n_obs < 0 || (obs.n_obs > 0 && (!obs.obs_H || !obs.obs_ICU || !obs.obs_D)), "the observations need obs_H, obs_ICU and obs_D"}},
+        error);
+    if (vrc != SEPAIHRD_OK) return vrc;
     const double qnan = std::numeric_limits<double>::quiet_NaN();
-    const int n = pb.n_age, T = pb.n_times, m = steps_per_interval;
-    const size_t Tp = (size_t)T_pos, nn = (size_t)n;
-    const int runup_offset = T - T_pos;  // the times increase: the output times >= 0 are the last T_pos
-    const epi::RowLayout L{n, pb.n_beta, pb.n_kappa};
-    const size_t W = (size_t)L.width();
-    const size_t row_doubles = (size_t)epi::NUM_COMP * nn;
+    const int n = pb.n_age, T = pb.n_times, m = steps_per_interval, runup_offset = plan.runup_offset;
+    const size_t Tp = (size_t)plan.T_pos, nn = (size_t)n, W = plan.W, row_doubles = plan.row_doubles;
+    const epi::RowLayout L = plan.L;
     // the observation of (series, output row t, age), NaN where there is none
     auto observed = [&](const double* series, int t, int i) { return t < obs.n_obs ? series[(size_t)t * nn + (size_t)i] : qnan; };
 #pragma omp parallel for schedule(dynamic, 1)
@@ -51,9 +41,9 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
         double* my_final = final_state ? final_state + (size_t)b * J * row_doubles : nullptr;
         if (status[b] != 0) {
             loglik[b] = std::numeric_limits<double>::lowest();
-            if (my_inc) std::fill(my_inc, my_inc + Tp, qnan);
-            if (my_ess) std::fill(my_ess, my_ess + Tp, qnan);
-            if (my_final) std::fill(my_final, my_final + (size_t)J * row_doubles, qnan);
+            stoch_twin::nan_fill(my_inc, 0, Tp);
+            stoch_twin::nan_fill(my_ess, 0, Tp);
+            stoch_twin::nan_fill(my_final, 0, (size_t)J * row_doubles);
             continue;
         }
         const double* row = model_values + (size_t)b * W;
@@ -66,9 +56,9 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
             for (int i = 0; i < n; ++i) {
                 int32_t* x = x_of(state, j, i);
                 for (int c = 0; c < epi::NUM_COMP; ++c) x[c] = (int32_t)row[L.initial(c, i)];
-                x[epi::NUM_COMP + 0] = x[epi::C_CUM_H]; x[epi::NUM_COMP + 1] = x[epi::C_CUM_ICU]; x[epi::NUM_COMP + 2] = x[epi::C_D];
+                int32_t none[epi::NUM_PREV];
+                epi::take_increments(x, x + epi::NUM_COMP, none);  // previous row := the initial counts (`state` starts as zeros)
             }
-        double lambda[epi::MAX_AGES], pressure[epi::MAX_AGES];
         epi::AgeProbs q[epi::MAX_AGES];
         double total = 0.0;
         for (int k = 0; k < T; ++k) {
@@ -83,26 +73,15 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                 for (int i = 0; i < n; ++i) q[i] = epi::age_probs(row, L, i, h);
             }
             for (int j = 0; j < J; ++j) {
-                for (int s = 0; k > 0 && s < m; ++s) {
-                    const double t_mid = t0 + ((double)s + 0.5) * h;
-                    const double bk = epi::beta_kappa(row, L, pb.beta_end_times, pb.kappa_end_times, t_mid);
-                    for (int i = 0; i < n; ++i)
-                        pressure[i] = epi::infectious_pressure(x_of(state, j, i), row[epi::R_THETA], row[L.vec(epi::V_H_INFEC, i)], pb.N[i]);
-                    for (int i = 0; i < n; ++i) {
-                        double sum = 0.0;
-                        for (int jj = 0; jj < n; ++jj) sum += pb.M[(size_t)i * nn + jj] * pressure[jj];
-                        lambda[i] = epi::force_of_infection(sum, bk, row[L.vec(epi::V_A, i)]);
-                    }
-                    for (int i = 0; i < n; ++i)
-                        epi::age_step(x_of(state, j, i), lambda[i], h, q[i], seed, (uint32_t)b, (uint32_t)j, (uint32_t)((k - 1) * m + s), (uint32_t)i);
-                }
+                if (k > 0)
+                    epi::all_ages_interval(x_of(state, j, 0), epi::NUM_COMP + pf::NUM_PREV, row, L, pb.N, pb.M, pb.beta_end_times, pb.kappa_end_times, t0,
+                                           h, q, m, seed, (uint32_t)b, (uint32_t)j, (uint32_t)((k - 1) * m));
                 double sum = 0.0;
                 for (int i = 0; i < n; ++i) {
                     int32_t* x = x_of(state, j, i);
-                    const int32_t incH = x[epi::C_CUM_H] - x[epi::NUM_COMP + 0], incICU = x[epi::C_CUM_ICU] - x[epi::NUM_COMP + 1],
-                                  incD = x[epi::C_D] - x[epi::NUM_COMP + 2];
-                    x[epi::NUM_COMP + 0] = x[epi::C_CUM_H]; x[epi::NUM_COMP + 1] = x[epi::C_CUM_ICU]; x[epi::NUM_COMP + 2] = x[epi::C_D];
-                    if (weighted) sum += pf::age_term(observed(obs.obs_H, t, i), observed(obs.obs_ICU, t, i), observed(obs.obs_D, t, i), incH, incICU, incD);
+                    int32_t inc[epi::NUM_PREV];
+                    epi::take_increments(x, x + epi::NUM_COMP, inc);
+                    if (weighted) sum += pf::age_term(observed(obs.obs_H, t, i), observed(obs.obs_ICU, t, i), observed(obs.obs_D, t, i), inc[0], inc[1], inc[2]);
                 }
                 lw[(size_t)j] = sum;
             }
@@ -140,10 +119,8 @@ HipParticleLikelihood::HipParticleLikelihood(HipSEPAIHRDParameterManager& parame
                                              std::uint64_t seed0, int device, int initial_state_mode)
     : pm_(parameterManager), data_(observed_data), time_points_(time_points), cache_(1), particles_(particles),
       steps_per_interval_(steps_per_interval), seed0_(seed0) {
-    objective_ = std::make_unique<HipSEPAIHRDObjectiveFunction>(pm_, cache_, data_, time_points_, initial_state, std::move(solver_strategy),
-                                                                1.0e-6, 1.0e-6, device, false);
-    if (sepaihrd_set_initial_state_mode(objective_->deviceContext(), initial_state_mode) != SEPAIHRD_OK)
-        throw ModelException("HipParticleLikelihood", "sepaihrd_set_initial_state_mode failed");
+    objective_ = stoch_twin::make_objective("HipParticleLikelihood", pm_, cache_, data_, time_points_, initial_state, std::move(solver_strategy), device,
+                                            initial_state_mode);
 }
 
 void HipParticleLikelihood::calculateBatch(const double* thetas, int B, double* out, int* status) const {

@@ -22,15 +22,7 @@ size_t parse_index(const std::string& name, size_t prefix_len, const char* where
     }
 }
 
-// SEPAIHRDParameterManager.cpp:302-313
-double reflectBound(double value, double minb, double maxb) {
-    if (minb >= maxb) return minb;
-    const double width = maxb - minb;
-    double y = std::fmod(value - minb, 2.0 * width);
-    if (y < 0) y += 2.0 * width;
-    if (y <= width) return minb + y;
-    return maxb - (y - width);
-}
+#include "sepaihrd_constrain.inc"  // constrain: the text the kernels compile (csrc/)
 
 // MurmurHash3 finaliser used by SimulationCache.cpp:12-19
 inline uint64_t mix_hash(uint64_t k) {
@@ -280,14 +272,7 @@ Eigen::VectorXd HipSEPAIHRDParameterManager::applyConstraints(const Eigen::Vecto
     Eigen::VectorXd c = parameters;
     for (size_t i = 0; i < names_.size(); ++i) {
         const Eigen::Index k = static_cast<Eigen::Index>(i);
-        if (has_bounds_[i]) {
-            double minb = lower_[i], maxb = upper_[i];
-            if (minb > maxb) std::swap(minb, maxb);
-            c[k] = mode_ == ConstraintMode::OPTIMIZATION_CLAMP ? std::min(std::max(parameters[k], minb), maxb)
-                                                               : reflectBound(parameters[k], minb, maxb);
-        } else {
-            c[k] = mode_ == ConstraintMode::OPTIMIZATION_CLAMP ? std::max(0.0, parameters[k]) : std::abs(parameters[k]);
-        }
+        c[k] = constrain(parameters[k], lower_[i], upper_[i], has_bounds_[i], mode_ == ConstraintMode::OPTIMIZATION_CLAMP ? 0 : 1);
     }
     return c;
 }

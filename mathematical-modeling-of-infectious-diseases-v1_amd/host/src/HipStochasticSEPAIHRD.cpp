@@ -1,16 +1,16 @@
 // host/src/HipStochasticSEPAIHRD.cpp -- HipStochasticSEPAIHRD and the CPU twin of sepaihrd_ensemble_stochastic's step, sort and
-// quantile passes.  The model, the stream and the sampler are csrc/sepaihrd_stoch_sepaihrd.inc and csrc/sepaihrd_stoch.inc, the
-// text the kernel compiles; this library is built with -ffp-contract=off like the kernel.
+// quantile passes.  The model, its interval walk (all_ages_interval), the stream and the sampler are
+// csrc/sepaihrd_stoch_sepaihrd.inc and csrc/sepaihrd_stoch.inc, the text the kernel compiles; what this twin shares with the
+// particle filter's is host/src/StochasticSEPAIHRDTwin.hpp; this library is built with -ffp-contract=off like the kernel.
 #include "epidemic_hip/HipStochasticSEPAIHRD.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <limits>
 
+#include "StochasticSEPAIHRDTwin.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_poisson.inc"  // sorted_quantile: the quantile rule of the predictive twin
-#include "sepaihrd_stoch_sepaihrd.inc"
 
 namespace epidemic {
 
@@ -20,37 +20,28 @@ int hostStochasticSEPAIHRD(const StochasticSEPAIHRDFixedData& pb, const double* 
                            int steps_per_interval, std::uint64_t seed, const double* probs, int n_probs, int keep, double* quantiles,
                            double* extinct, double* traj, double* final_state, std::string* error) {
     char msg[256] = "";
-    int T_pos = 0;
-    for (int k = 0; k < pb.n_times && pb.times; ++k) T_pos += pb.times[k] >= 0.0;
-    int vrc = sepaihrd_stochastic_validate(S, R, steps_per_interval, keep, pb.n_times, T_pos, pb.n_age, probs, n_probs, msg, (int)sizeof(msg));
-    auto refuse = [&](const char* what) {
-        std::snprintf(msg, sizeof(msg), "ensemble_stochastic: %s", what);
-        vrc = SEPAIHRD_E_INVALID_ARG;
-    };
-    if (vrc == SEPAIHRD_OK && (!model_values || !status || !quantiles)) refuse("model_values, status and quantiles must not be NULL");
-    if (vrc == SEPAIHRD_OK && (!pb.N || !pb.M || !pb.kappa_end_times || pb.n_kappa < 1 || pb.n_beta < 0 || (pb.n_beta > 0 && !pb.beta_end_times)))
-        refuse("the fixed data need N, M and the schedule end times (n_kappa >= 1)");
-    if (vrc == SEPAIHRD_OK && pb.n_age > epi::MAX_AGES) refuse("built for at most 16 age classes");
-    if (vrc == SEPAIHRD_OK && keep > 0 && !traj) refuse("keep > 0 needs traj");
-    if (vrc != SEPAIHRD_OK) {
-        if (error) *error = msg;
-        return vrc;
-    }
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    const int vrc = stoch_twin::verdict(
+        "ensemble_stochastic",
+        sepaihrd_stochastic_validate(S, R, steps_per_interval, keep, pb.n_times, plan.T_pos, pb.n_age, probs, n_probs, msg, (int)sizeof(msg)), msg,
+        {{!model_values || !status || !quantiles, "model_values, status and quantiles must not be NULL"},
+         {stoch_twin::fixed_data_missing(pb), stoch_twin::FIXED_DATA_TEXT},
+         {pb.n_age > epi::MAX_AGES, "built for at most 16 age classes"},
+         {keep > 0 && !traj, "keep > 0 needs traj"}},
+        error);
+    if (vrc != SEPAIHRD_OK) return vrc;
     const double qnan = std::numeric_limits<double>::quiet_NaN();
-    const int n = pb.n_age, T = pb.n_times, m = steps_per_interval;
-    const size_t Tp = (size_t)T_pos, nn = (size_t)n;
-    const int runup_offset = T - T_pos;  // the times increase: the output times >= 0 are the last T_pos
-    const epi::RowLayout L{n, pb.n_beta, pb.n_kappa};
-    const size_t W = (size_t)L.width();
+    const int n = pb.n_age, T = pb.n_times, m = steps_per_interval, runup_offset = plan.runup_offset;
+    const size_t Tp = (size_t)plan.T_pos, nn = (size_t)n, W = plan.W, row_doubles = plan.row_doubles;
+    const epi::RowLayout L = plan.L;
     std::vector<int> valid;  // positions of the valid samples
     for (int s = 0; s < S; ++s)
         if (status[s] == 0) valid.push_back(s);
     const size_t nd = valid.size() * (size_t)R;  // values per segment
-    const size_t row_doubles = (size_t)epi::NUM_COMP * nn;
     for (int s = 0; s < S; ++s)
         if (status[s] != 0) {
-            if (traj && keep > 0) std::fill(traj + (size_t)s * keep * T * row_doubles, traj + (size_t)(s + 1) * keep * T * row_doubles, qnan);
-            if (final_state) std::fill(final_state + (size_t)s * R * row_doubles, final_state + (size_t)(s + 1) * R * row_doubles, qnan);
+            stoch_twin::nan_fill(traj, (size_t)s * keep * T * row_doubles, (size_t)keep * T * row_doubles);
+            stoch_twin::nan_fill(final_state, (size_t)s * R * row_doubles, (size_t)R * row_doubles);
         }
     // the daily increments of every replicate: inc[d][series][t][age], exact in int32
     std::vector<int32_t> inc(nd * 3 * Tp * nn);
@@ -61,8 +52,7 @@ int hostStochasticSEPAIHRD(const StochasticSEPAIHRDFixedData& pb, const double* 
         const uint32_t r = (uint32_t)((size_t)d % (size_t)R);
         const double* row = model_values + s * W;
         int32_t x[epi::MAX_AGES][epi::NUM_COMP];
-        int32_t prev[epi::MAX_AGES][3];
-        double lambda[epi::MAX_AGES], pressure[epi::MAX_AGES];
+        int32_t prev[epi::MAX_AGES][epi::NUM_PREV];
         epi::AgeProbs q[epi::MAX_AGES];
         for (int i = 0; i < n; ++i) {
             for (int c = 0; c < epi::NUM_COMP; ++c) x[i][c] = (int32_t)row[L.initial(c, i)];
@@ -74,11 +64,9 @@ int hostStochasticSEPAIHRD(const StochasticSEPAIHRDFixedData& pb, const double* 
             for (int i = 0; i < n; ++i) {
                 if (tr)
                     for (int c = 0; c < epi::NUM_COMP; ++c) tr[(size_t)k * row_doubles + (size_t)c * nn + i] = (double)x[i][c];
-                const int32_t now[3] = {x[i][epi::C_CUM_H], x[i][epi::C_CUM_ICU], x[i][epi::C_D]};
-                for (int ser = 0; ser < 3; ++ser) {
-                    if (k >= runup_offset) my_inc[((size_t)ser * Tp + (size_t)(k - runup_offset)) * nn + i] = now[ser] - prev[i][ser];
-                    prev[i][ser] = now[ser];
-                }
+                int32_t since[epi::NUM_PREV];
+                epi::take_increments(x[i], prev[i], since);
+                for (int ser = 0; ser < 3 && k >= runup_offset; ++ser) my_inc[((size_t)ser * Tp + (size_t)(k - runup_offset)) * nn + i] = since[ser];
             }
         };
         write_row(0);
@@ -86,17 +74,8 @@ int hostStochasticSEPAIHRD(const StochasticSEPAIHRDFixedData& pb, const double* 
             const double t0 = pb.times[k];
             const double h = (pb.times[k + 1] - t0) / (double)m;
             for (int i = 0; i < n; ++i) q[i] = epi::age_probs(row, L, i, h);
-            for (int j = 0; j < m; ++j) {
-                const double t_mid = t0 + ((double)j + 0.5) * h;
-                const double bk = epi::beta_kappa(row, L, pb.beta_end_times, pb.kappa_end_times, t_mid);
-                for (int i = 0; i < n; ++i) pressure[i] = epi::infectious_pressure(x[i], row[epi::R_THETA], row[L.vec(epi::V_H_INFEC, i)], pb.N[i]);
-                for (int i = 0; i < n; ++i) {
-                    double sum = 0.0;
-                    for (int jj = 0; jj < n; ++jj) sum += pb.M[(size_t)i * nn + jj] * pressure[jj];
-                    lambda[i] = epi::force_of_infection(sum, bk, row[L.vec(epi::V_A, i)]);
-                }
-                for (int i = 0; i < n; ++i) epi::age_step(x[i], lambda[i], h, q[i], seed, (uint32_t)s, r, (uint32_t)(k * m + j), (uint32_t)i);
-            }
+            epi::all_ages_interval(x[0], epi::NUM_COMP, row, L, pb.N, pb.M, pb.beta_end_times, pb.kappa_end_times, t0, h, q, m, seed, (uint32_t)s, r,
+                                   (uint32_t)(k * m));
             write_row(k + 1);
         }
         bool infected = false;
@@ -147,10 +126,8 @@ HipStochasticSEPAIHRD::HipStochasticSEPAIHRD(HipSEPAIHRDParameterManager& parame
                                              const std::vector<double>& time_points, const Eigen::VectorXd& initial_state,
                                              std::shared_ptr<IOdeSolverStrategy> solver_strategy, int device, int initial_state_mode)
     : pm_(parameterManager), data_(observed_data), time_points_(time_points), cache_(1) {
-    objective_ = std::make_unique<HipSEPAIHRDObjectiveFunction>(pm_, cache_, data_, time_points_, initial_state, std::move(solver_strategy),
-                                                                1.0e-6, 1.0e-6, device, false);
-    if (sepaihrd_set_initial_state_mode(objective_->deviceContext(), initial_state_mode) != SEPAIHRD_OK)
-        throw ModelException("HipStochasticSEPAIHRD", "sepaihrd_set_initial_state_mode failed");
+    objective_ = stoch_twin::make_objective("HipStochasticSEPAIHRD", pm_, cache_, data_, time_points_, initial_state, std::move(solver_strategy),
+                                            device, initial_state_mode);
     n_ = static_cast<int>(pm_.modelParameters().N.size());
     for (double t : time_points_) t_pos_ += (t >= 0.0);
 }

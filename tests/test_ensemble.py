@@ -243,3 +243,39 @@ def test_hip_ensemble_larger_than_the_lds_sort(mm, oracle_py, ref_fixture):
     np.testing.assert_allclose(got["ppc"], ref["ppc"], rtol=1e-9, atol=1e-9)
     np.testing.assert_allclose(got["sero"], ref["sero"], rtol=1e-9, atol=1e-12)
     assert np.all(np.diff(got["rt"], axis=0) >= 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [0, 1])
+def test_hip_rt_and_metrics_constrain_theta_outside_its_bounds(mm, oracle_py, ref_fixture, mode):
+    """ensemble_rt_kernel and ensemble_metrics_kernel decode theta through the constraint rule themselves (the integrator's
+    copy in LDS is gone by then).  Samples with one entry below its lower bound and one beyond upper + width, clamp and reflect:
+    Rt and the metric rows against the numpy restatements on the host side's constrained parameters."""
+    import rt_numpy
+    pb = ref_fixture.with_(arith=mm.ARITH_STRICT, constraint_mode=mode)
+    S = 3
+    theta = _draws(oracle_py, pb, S)
+    lo, hi, _ = pb.bounds_arrays()
+    below, beyond = pb.param_names.index("beta"), pb.param_names.index("theta")
+    theta[:, below] = lo[below] - (hi[below] - lo[below]) * np.array([0.25, 0.5, 0.125])
+    theta[:, beyond] = hi[beyond] + (hi[beyond] - lo[beyond]) * np.array([1.25, 1.5, 1.75])
+    orc = oracle_py.Oracle(pb)
+    con = orc.apply_constraints(theta, mode)
+    assert (con[:, [below, beyond]] != theta[:, [below, beyond]]).all() and ((con >= lo) & (con <= hi)).all()
+    if mode == 0:
+        assert (con[:, below] == lo[below]).all() and (con[:, beyond] == hi[beyond]).all()
+    else:  # folded back into the interior
+        assert ((con[:, [below, beyond]] > lo[[below, beyond]]) & (con[:, [below, beyond]] < hi[[below, beyond]])).all()
+    rts, q = _rt_reference(oracle_py, pb, theta)
+    sim = orc.simulate_samples(theta)
+    ref = np.array([rt_numpy.essential_metrics(sim["traj"][s], orc.model_parameters(theta[s]), pb) for s in range(S)])
+    for s in range(S):  # the host side ran with the constrained values
+        mp = orc.model_parameters(theta[s])
+        assert mp["beta"] == con[s, below] and mp["theta"] == con[s, beyond]
+    hip = mm.HipObjective(pb)
+    hip.set_initial_state_mode(1)
+    got = hip.ensemble_quantiles(theta, PROBS, want_sero=True, want_rt=True, want_metrics=True)
+    assert got["n_valid"] == S
+    np.testing.assert_allclose(got["rt"], q, rtol=1e-9)
+    assert np.array_equal(got["metrics"][:, 5:7], ref[:, 5:7])
+    np.testing.assert_allclose(got["metrics"], ref, rtol=1e-9, atol=1e-12)
