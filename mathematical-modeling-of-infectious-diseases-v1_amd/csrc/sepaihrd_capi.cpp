@@ -2083,6 +2083,32 @@ int sepaihrd_mh_draw_first(sepaihrd_mh* mh) {
     return SEPAIHRD_OK;
 }
 
+// The outcome of the test just queued on the main stream goes home on the copy stream as soon as the test has run (ev_tested);
+// the main stream does not wait for it.  It is for the caller's bookkeeping (sepaihrd_mh_fetch_test): a self-contained sampler
+// keeps its own and reads it at the end.
+static int mh_send_outcome_home(sepaihrd_mh* mh, bool self_contained) {
+    MhBackend* ctx = mh->ctx;
+    hipStream_t st = mh->stream, cs = mh->copy_stream;
+    const int C = mh->st.C;
+    HIP_TRY(hipEventRecord(mh->ev_tested, st), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipStreamWaitEvent(cs, mh->ev_tested, 0), ctx, return SEPAIHRD_E_HIP);
+    if (self_contained) return SEPAIHRD_OK;
+    HIP_TRY(hipMemcpyAsync(mh->h_test_out, mh->d_test_out, (size_t)C * (sizeof(double) + 1), hipMemcpyDeviceToHost, cs), ctx,
+            return SEPAIHRD_E_HIP);
+    HIP_TRY(hipEventRecord(mh->ev_fetched, cs), ctx, return SEPAIHRD_E_HIP);
+    mh->test_pending = true;
+    return SEPAIHRD_OK;
+}
+
+// a launch (or a chain of them) of sepaihrd_mh_step_tested that did not go out
+#define MH_LAUNCH_TRY(expr, what)                                             \
+    do {                                                                      \
+        if ((expr) != 0) {                                                    \
+            ctx->last_error = "mh_step_tested: " what;                        \
+            return SEPAIHRD_E_HIP;                                            \
+        }                                                                     \
+    } while (0)
+
 int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) {
     if (!mh || adapt < 0 || adapt > 3) return SEPAIHRD_E_INVALID_ARG;
     MhBackend* ctx = mh->ctx;
@@ -2123,18 +2149,13 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
         // one round, 32 768 chains, still gains from the overlap -- 1.95 against 2.00 -- as the draws fill the round's tail;
         // a low-priority copy stream changed nothing).  SEPAIHRD_MH_DRAW=overlap|serial overrides (A/B runs).
         const bool serial_draw = mh_draws_behind_the_evaluation(ctx, C);
-        if (mh_launch_draw(mh, prev_flags, 0, mh->d_test, mh->d_z_stage, mh->d_test + 3 * (size_t)C, last ? 0 : 1, serial_draw ? st : cs) != 0) {
-            ctx->last_error = "mh_step_tested: draw launch failed";
-            return SEPAIHRD_E_HIP;
-        }
+        MH_LAUNCH_TRY(mh_launch_draw(mh, prev_flags, 0, mh->d_test, mh->d_z_stage, mh->d_test + 3 * (size_t)C, last ? 0 : 1, serial_draw ? st : cs),
+                      "draw launch failed");
         mh->staged = true;
         // ... and, when the draws run beside the evaluation and no covariance refresh separates this test from its proposal,
         // L z of both continuations too: the launch between two evaluations then reads no factor (SEPAIHRD_MH_LZ=fused: A/B)
         if (!serial_draw && !last && adapt <= 1 && mh->st.P <= 200 && mh_lz_ahead_wanted()) {
-            if (mh_launch_lz(mh, mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->d_lz, mh->d_lz + CP, cs) != 0) {
-                ctx->last_error = "mh_step_tested: L z launch failed";
-                return SEPAIHRD_E_HIP;
-            }
+            MH_LAUNCH_TRY(mh_launch_lz(mh, mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->d_lz, mh->d_lz + CP, cs), "L z launch failed");
             mh->lz_ready = true;
         }
     } else
@@ -2144,30 +2165,21 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
     HIP_TRY(hipStreamWaitEvent(st, mh->ev_test_up, 0), ctx, return SEPAIHRD_E_HIP);
     double* const d_values = static_cast<double*>(mh->d_test_out);
     uint8_t* const d_flags = reinterpret_cast<uint8_t*>(d_values + C);
-    if (mh_before_commit(mh) != 0) { ctx->last_error = "mh_step_tested: catch-up of the queued updates failed"; return SEPAIHRD_E_HIP; }
+    MH_LAUNCH_TRY(mh_before_commit(mh), "catch-up of the queued updates failed");
     if (!last && adapt <= 1) {
         // no covariance refresh between commit and proposal: test, commit and proposal in one launch
         // (the staged normals landed before the test's inputs: same copy stream, staged first -- ev_test_up covers them)
         const double* const lz_u = mh->lz_ready ? mh->d_lz : nullptr;
         const double* const lz_p = mh->lz_ready ? mh->d_lz + CP : nullptr;
-        if ((mh->packed ? sampler_test_commit_propose_packed(mh->st, mh_bounds_of(ctx->dp), mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C,
+        MH_LAUNCH_TRY(mh->packed ? sampler_test_commit_propose_packed(mh->st, mh_bounds_of(ctx->dp), mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C,
                                                              mh->d_test + 2 * (size_t)C, mh->d_lp, mh->d_best_lp, mh->d_scale_sel, d_flags, d_values,
                                                              mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->rows, st, lz_u, lz_p)
                         : sampler_test_commit_propose(mh->st, ctx->dp, mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C,
                                                       mh->d_test + 2 * (size_t)C, mh->d_lp, mh->d_best_lp, mh->d_scale_sel, d_flags, d_values,
-                                                      mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->rows, st, lz_u, lz_p)) != 0) {
-            ctx->last_error = "mh_step_tested: launch failed";
-            return SEPAIHRD_E_HIP;
-        }
-        HIP_TRY(hipEventRecord(mh->ev_tested, st), ctx, return SEPAIHRD_E_HIP);  // one marker: tested AND proposed
-        mh->ev_last_proposed = mh->ev_tested;
-        HIP_TRY(hipStreamWaitEvent(cs, mh->ev_tested, 0), ctx, return SEPAIHRD_E_HIP);
-        if (!self_contained) {  // the outcome for the caller's bookkeeping (a self-contained sampler keeps its own: read at the end)
-            HIP_TRY(hipMemcpyAsync(mh->h_test_out, mh->d_test_out, (size_t)C * (sizeof(double) + 1), hipMemcpyDeviceToHost, cs), ctx,
-                    return SEPAIHRD_E_HIP);
-            HIP_TRY(hipEventRecord(mh->ev_fetched, cs), ctx, return SEPAIHRD_E_HIP);
-            mh->test_pending = true;
-        }
+                                                      mh->d_z_stage, mh->d_test + 3 * (size_t)C, mh->rows, st, lz_u, lz_p),
+                      "launch failed");
+        if (mh_send_outcome_home(mh, self_contained) != SEPAIHRD_OK) return SEPAIHRD_E_HIP;
+        mh->ev_last_proposed = mh->ev_tested;  // one marker: tested AND proposed
         mh->proposed_once = true;
         mh->rows++;
         if (adapt == 1) mh_queue_rank1(mh, gamma);  // as mh_adapt_step: the queued update names history row rows - 1
@@ -2175,27 +2187,16 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
         mh->staged = false;
         return mh_eval_device(mh, mh->st.prop);
     }
-    int rc = sampler_accept_test(mh->st, mh->rows, mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C, mh->d_test + 2 * (size_t)C, mh->d_lp,
-                                 mh->d_best_lp, mh->d_scale_sel, d_flags, d_values, st);
-    if (rc != 0) { ctx->last_error = "mh_step_tested: launch failed"; return SEPAIHRD_E_HIP; }
-    HIP_TRY(hipEventRecord(mh->ev_tested, st), ctx, return SEPAIHRD_E_HIP);
-    // the outcome goes back on the copy stream as soon as the test has run; the main stream does not wait for it
-    HIP_TRY(hipStreamWaitEvent(cs, mh->ev_tested, 0), ctx, return SEPAIHRD_E_HIP);
-    if (!self_contained) {
-        HIP_TRY(hipMemcpyAsync(mh->h_test_out, mh->d_test_out, (size_t)C * (sizeof(double) + 1), hipMemcpyDeviceToHost, cs), ctx,
-                return SEPAIHRD_E_HIP);
-        HIP_TRY(hipEventRecord(mh->ev_fetched, cs), ctx, return SEPAIHRD_E_HIP);
-        mh->test_pending = true;
-    }
-    rc = sampler_commit_counted(mh->st, d_flags, mh->rows, 1, st);
-    if (rc != 0) { ctx->last_error = "mh_step_tested: launch failed"; return SEPAIHRD_E_HIP; }
+    MH_LAUNCH_TRY(sampler_accept_test(mh->st, mh->rows, mh->d_loglik, mh->d_status, mh->d_test, mh->d_test + C, mh->d_test + 2 * (size_t)C, mh->d_lp,
+                                      mh->d_best_lp, mh->d_scale_sel, d_flags, d_values, st),
+                  "launch failed");
+    if (mh_send_outcome_home(mh, self_contained) != SEPAIHRD_OK) return SEPAIHRD_E_HIP;
+    MH_LAUNCH_TRY(sampler_commit_counted(mh->st, d_flags, mh->rows, 1, st), "launch failed");
     mh->rows++;
     if (last) return SEPAIHRD_OK;
-    rc = mh_adapt_step(mh, gamma, adapt);
-    if (rc != 0) { ctx->last_error = "mh_step_tested: launch failed"; return SEPAIHRD_E_HIP; }
+    MH_LAUNCH_TRY(mh_adapt_step(mh, gamma, adapt), "launch failed");
     HIP_TRY(hipStreamWaitEvent(st, mh->ev_staged, 0), ctx, return SEPAIHRD_E_HIP);  // the staged normals have landed
-    rc = mh_launch_propose_select(mh, mh->d_z_stage, mh->d_test + 3 * (size_t)C, d_flags, mh->d_scale_sel, st);
-    if (rc != 0) { ctx->last_error = "mh_step_tested: launch failed"; return SEPAIHRD_E_HIP; }
+    MH_LAUNCH_TRY(mh_launch_propose_select(mh, mh->d_z_stage, mh->d_test + 3 * (size_t)C, d_flags, mh->d_scale_sel, st), "launch failed");
     HIP_TRY(hipEventRecord(mh->ev_proposed, st), ctx, return SEPAIHRD_E_HIP);
     mh->ev_last_proposed = mh->ev_proposed;
     mh->proposed_once = true;
@@ -2203,6 +2204,7 @@ int sepaihrd_mh_step_tested(sepaihrd_mh* mh, double gamma, int adapt, int last) 
     mh->staged = false;
     return mh_eval_device(mh, mh->st.prop);
 }
+#undef MH_LAUNCH_TRY
 
 int sepaihrd_mh_fetch_test(sepaihrd_mh* mh, double* values, uint8_t* flags) {
     if (!mh || !values || !flags) return SEPAIHRD_E_INVALID_ARG;

@@ -36,6 +36,7 @@ namespace sepaihrd {
 namespace {
 
 #include "sepaihrd_constrain.inc"  // reflect_bound, constrain: the text the evaluation kernels compile
+#include "sepaihrd_adapt_scale.inc"  // window_push, next_log_scale: the text the host loops compile
 
 // where state `row` of chain c lives: its ring slot, and its place in the sample store (nullptr: not a stored state)
 __device__ __forceinline__ double* ring_row(const SamplerState& s, const int c, const int row) {
@@ -107,36 +108,19 @@ __global__ void mh_propose_kernel(const SamplerState s, const DevProblem pb, con
     }
 }
 
-// adaptGlobalScale(accepted, step) of one chain (:104-152), the window of the last 1000 flags as a ring with its running sum;
-// returns global_scale_ = exp(log_scale_) (glibc's exp, csrc/sepaihrd_rng.inc).  One thread per chain.
+// adaptGlobalScale(accepted, step) of one chain (:104-152): the rule is csrc/sepaihrd_adapt_scale.inc's, the window of the last
+// 1000 flags is a ring with its running sum in SamplerState; returns global_scale_ = exp(log_scale_) (glibc's exp,
+// csrc/sepaihrd_rng.inc).  One thread per chain.
 __device__ __forceinline__ double adapt_global_scale(const SamplerState& s, const int c, const bool accepted, const int step) {
     if (!s.adapt_scale) return s.scale[c];
-    int32_t* meta = s.recent_meta + 4 * (size_t)c;
-    uint8_t* ring = s.recent + 1000 * (size_t)c;
+    int32_t* meta = s.recent_meta + 4 * (size_t)c;   // position, length, sum, emergency count
     int pos = meta[0], len = meta[1], sum = meta[2];
-    if (len == 1000) sum -= ring[pos]; else ++len;   // push_back, pop_front beyond 1000 (:107-110)
-    ring[pos] = accepted ? 1 : 0;
-    sum += accepted ? 1 : 0;
-    pos = (pos + 1) % 1000;
+    window_push(s.recent + SEP_ADAPT_WINDOW * (size_t)c, pos, len, sum, accepted);
     meta[0] = pos; meta[1] = len; meta[2] = sum;
-    const double rate = (double)sum / (double)len;
-    double ls = s.log_scale[c];
-    const double target = s.target_rate;
-    if (len >= 1000 && rate < 0.001) {
-        ls -= 0.7;
-        meta[3] += 1;
-    } else if (rate < 0.02 && len >= 500) {
-        double g = 5.0 / sqrt((double)step + 1.0);
-        g = (0.3 < g) ? 0.3 : g;                     // std::min(gamma_fast, 0.3)
-        ls += g * (0.0 - target);
-    } else {
-        double g = 1.0 / sqrt((double)step + 1.0);
-        g = (0.1 < g) ? 0.1 : g;
-        ls += g * ((accepted ? 1.0 : 0.0) - target);
-    }
-    if (s.scale[c] <= 0.011 && rate > 0.15 && rate < 0.30) ls += 0.01;   // the scale BEFORE this update (:146-148)
-    ls = (2.3 < ls) ? 2.3 : ls;                      // std::max(std::min(log_scale_, 2.3), -6.9)
-    ls = (ls < -6.9) ? -6.9 : ls;
+    bool emergency;
+    double ls = log_scale_step(s.log_scale[c], sum, len, accepted, step, s.target_rate, &emergency);
+    if (emergency) meta[3] += 1;
+    ls = log_scale_recover_and_clamp(ls, s.scale[c], sum, len);
     const double sc = sepaihrd_rng::glibc_exp(ls);
     s.log_scale[c] = ls;
     s.scale[c] = sc;

@@ -358,7 +358,16 @@ private:
         std::function<const char*()> last_error;
         std::function<double*(size_t)> records_buffer;  // where the summary records stay on the device; empty: in the sampler
     };
+    // a device-resident run and its parts (MultiChainMetropolisHastings.cpp): set-up, one of the two loops, read-back
+    struct DeviceRun;
     std::vector<OptimizationResult> runOnDevice(const std::vector<double>& initial, int C, IParameterManager& pm, const DeviceSampler& dev);
+    void setUpDeviceRun(DeviceRun& run, const std::vector<double>& initial, IParameterManager& pm);
+    void selfContainedLoop(DeviceRun& run);
+    void hostDrivenLoop(DeviceRun& run);
+    std::vector<OptimizationResult> readBackDeviceRun(DeviceRun& run);
+    int teamSize(int C) const;
+    std::vector<double> initialProposalCovariance(IParameterManager& pm, int P) const;
+    void finishResult(OptimizationResult& r, const double* cov, int P, int accepted, double scale) const;
     int sampler_kernel_form_ = 0;
     using BatchEval = std::function<void(const double*, int, double*)>;
     std::vector<OptimizationResult> run(const std::vector<double>& initial, int C, const BatchEval& eval,

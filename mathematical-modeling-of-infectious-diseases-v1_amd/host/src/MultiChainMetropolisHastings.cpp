@@ -6,6 +6,12 @@
 // Per-chain state is what the reference keeps as sampler members: current_covariance_,
 // proposal_cholesky_, running_mean_, log_scale_/global_scale_, recent_accepts_, chain_history_
 // and its own std::mt19937.  Host work per iteration is O(C P^2) and runs under OpenMP.
+//
+// adaptGlobalScale (:104-152) is csrc/sepaihrd_adapt_scale.inc, the text the device's test kernel compiles too; GlobalScale
+// below is a chain's side of it (log-scale, scale, the window of the last 1000 accept flags) for run() and for the
+// device-resident run alike.  That run (runOnDevice) is four parts over one DeviceRun: setUpDeviceRun, then selfContainedLoop
+// (streams and scale on the device, reports through a writer thread) or hostDrivenLoop (streams on the host, look-ahead
+// queue, bookkeeping one evaluation behind), then readBackDeviceRun.
 #include "epidemic_hip/HipSEPAIHRD.hpp"
 #include "epidemic_hip/HipChainDiagnostics.hpp"
 #include "epidemic_hip/HipSIR.hpp"
@@ -26,6 +32,7 @@
 #include <iomanip>
 #include <iostream>
 #include <limits>
+#include <memory>
 #include <sstream>
 #ifdef _OPENMP
 #include <omp.h>
@@ -33,12 +40,39 @@
 
 namespace epidemic {
 
+namespace {
+#include "sepaihrd_adapt_scale.inc"  // window_after_push, window_push, next_log_scale: the text the device's test kernel compiles
+
+// log_scale_ / global_scale_ / recent_accepts_ of one chain (:104-152).  The rule leaves exp() to its caller: advance() returns
+// with `scale` still the one BEFORE the update, and whoever called sets it from the new log-scale.
+struct GlobalScale {
+    double log_scale = 0.0, scale = 1.0;
+    std::vector<unsigned char> ring = std::vector<unsigned char>(SEP_ADAPT_WINDOW, 0);  // the last 1000 accept flags (:107-110)
+    int pos = 0, len = 0, sum = 0;
+    int emergency = 0;
+    // the log-scale after iteration t if its test ends in `accepted`; nothing changes
+    double candidate(bool accepted, int t, double target) const {
+        int l = len, s = sum;
+        bool e;
+        window_after_push(ring.data(), pos, accepted, l, s);
+        return next_log_scale(log_scale, scale, s, l, accepted, t, target, &e);
+    }
+    // iteration t's test ended in `accepted`: the window and the log-scale move
+    void advance(bool accepted, int t, double target) {
+        bool e;
+        window_push(ring.data(), pos, len, sum, accepted);
+        log_scale = next_log_scale(log_scale, scale, sum, len, accepted, t, target, &e);
+        if (e) emergency++;
+    }
+};
+}  // namespace
+
 struct MultiChainMetropolisHastings::Chain {
     std::mt19937 gen;
     std::vector<double> x, prop, cov, chol, mean;
-    double lp = 0.0, log_scale = 0.0, scale = 1.0;
-    std::deque<int> recent;
-    int emergency = 0, accepted = 0;
+    double lp = 0.0;
+    GlobalScale gs;
+    int accepted = 0;
     std::vector<double> history;  // chain_history_: every state ((t+1) x P) for the two-pass refresh, else the newest only
     size_t history_len = 0;
     // recomputeFullCovariance from running sums (oracle::RunningMoments states the recurrence; the device kernels
@@ -371,27 +405,18 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::run(const std::vec
     if (static_cast<int>(initial.size()) != C * P) throw InvalidParameterException("MetropolisHastingsSampler", "initial size != C*P");
     const double scaling_factor = (2.38 * 2.38) / static_cast<double>(P);
     const size_t PP = static_cast<size_t>(P) * P;
-    const int nthreads = std::min(host_threads_ > 0 ? std::min(host_threads_, host_thread_share()) : host_thread_share(), std::max(1, C));
+    const int nthreads = teamSize(C);
     (void)nthreads;
 
     std::vector<Chain> chains(static_cast<size_t>(C));
     std::vector<double> batch(static_cast<size_t>(C) * P), values(static_cast<size_t>(C));
+    const std::vector<double> cov0 = initialProposalCovariance(pm, P);
     for (int c = 0; c < C; ++c) {
         Chain& ch = chains[static_cast<size_t>(c)];
         ch.gen.seed(seed_ + static_cast<uint32_t>(c));
         ch.x.assign(initial.begin() + static_cast<size_t>(c) * P, initial.begin() + static_cast<size_t>(c + 1) * P);
         ch.prop.resize(static_cast<size_t>(P));
-        if (initial_cov_.size() == PP) {  // warm start from phase 1 (:219-223): no 2.38^2/P scaling
-            ch.cov = initial_cov_;
-        } else {
-            ch.cov.assign(PP, 0.0);
-            for (int i = 0; i < P; ++i) {  // :226-237
-                const double s = pm.getSigmaForParamIndex(i);
-                ch.cov[static_cast<size_t>(i) * P + i] = (s > 0 ? s * s : 1e-6);
-            }
-            for (double& v : ch.cov) v *= scaling_factor;
-        }
-        for (int i = 0; i < P; ++i) ch.cov[static_cast<size_t>(i) * P + i] += regularization_epsilon_;
+        ch.cov = cov0;
         if (!cholesky(ch.cov, P, ch.chol)) {  // :240-246
             ch.chol.assign(PP, 0.0);
             for (int i = 0; i < P; ++i) ch.chol[static_cast<size_t>(i) * P + i] = 0.1;
@@ -448,35 +473,34 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::run(const std::vec
                                 gamma * (diff[static_cast<size_t>(i)] * diff[static_cast<size_t>(j)]);
                 }
                 if (t % adaptation_period_ == 0) {
-                    if (ch.history_len >= static_cast<size_t>(P) + 10 && !two_pass_covariance_) {  // recomputeFullCovariance :168-199
-                        const double len = static_cast<double>(ch.history_len), denom = static_cast<double>(ch.history_len - 1);
-                        for (int i = 0; i < P; ++i) ch.mean[static_cast<size_t>(i)] = ch.sum[static_cast<size_t>(i)] / len;
-                        for (int i = 0; i < P; ++i)
-                            for (int j = 0; j < P; ++j) {
-                                const double m = i >= j ? ch.m2[static_cast<size_t>(i) * P + j] : ch.m2[static_cast<size_t>(j) * P + i];
-                                ch.cov[static_cast<size_t>(i) * P + j] = scaling_factor * (m / denom) + (i == j ? regularization_epsilon_ : 0.0);
-                            }
-                        cholesky(ch.cov, P, ch.chol);  // kept only on success
-                    } else if (ch.history_len >= static_cast<size_t>(P) + 10) {
-                        std::vector<double> mean(static_cast<size_t>(P), 0.0), acc(PP, 0.0);
-                        for (size_t s = 0; s < ch.history_len; ++s)
-                            for (int i = 0; i < P; ++i) mean[static_cast<size_t>(i)] += ch.history[s * P + i];
-                        for (int i = 0; i < P; ++i) mean[static_cast<size_t>(i)] /= static_cast<double>(ch.history_len);
-                        ch.mean = mean;
-                        for (size_t s = 0; s < ch.history_len; ++s) {
-                            const double* row = &ch.history[s * P];
-                            for (int i = 0; i < P; ++i) {
-                                const double di = row[i] - mean[static_cast<size_t>(i)];
+                    if (ch.history_len >= static_cast<size_t>(P) + 10) {  // recomputeFullCovariance :168-199
+                        std::vector<double> acc(PP, 0.0);  // the centred second moment
+                        if (!two_pass_covariance_) {
+                            const double len = static_cast<double>(ch.history_len);
+                            for (int i = 0; i < P; ++i) ch.mean[static_cast<size_t>(i)] = ch.sum[static_cast<size_t>(i)] / len;
+                            for (int i = 0; i < P; ++i)
                                 for (int j = 0; j < P; ++j)
-                                    acc[static_cast<size_t>(i) * P + j] += di * (row[j] - mean[static_cast<size_t>(j)]);
+                                    acc[static_cast<size_t>(i) * P + j] = i >= j ? ch.m2[static_cast<size_t>(i) * P + j] : ch.m2[static_cast<size_t>(j) * P + i];
+                        } else {
+                            std::vector<double> mean(static_cast<size_t>(P), 0.0);
+                            for (size_t s = 0; s < ch.history_len; ++s)
+                                for (int i = 0; i < P; ++i) mean[static_cast<size_t>(i)] += ch.history[s * P + i];
+                            for (int i = 0; i < P; ++i) mean[static_cast<size_t>(i)] /= static_cast<double>(ch.history_len);
+                            ch.mean = mean;
+                            for (size_t s = 0; s < ch.history_len; ++s) {
+                                const double* row = &ch.history[s * P];
+                                for (int i = 0; i < P; ++i) {
+                                    const double di = row[i] - mean[static_cast<size_t>(i)];
+                                    for (int j = 0; j < P; ++j)
+                                        acc[static_cast<size_t>(i) * P + j] += di * (row[j] - mean[static_cast<size_t>(j)]);
+                                }
                             }
                         }
-                        const double denom = double(ch.history_len - 1);
+                        const double denom = static_cast<double>(ch.history_len - 1);
                         for (int i = 0; i < P; ++i)
                             for (int j = 0; j < P; ++j)
                                 ch.cov[static_cast<size_t>(i) * P + j] =
-                                    scaling_factor * (acc[static_cast<size_t>(i) * P + j] / denom) +
-                                    (i == j ? regularization_epsilon_ : 0.0);
+                                    scaling_factor * (acc[static_cast<size_t>(i) * P + j] / denom) + (i == j ? regularization_epsilon_ : 0.0);
                         cholesky(ch.cov, P, ch.chol);  // kept only on success
                     }
                     std::vector<double> stable = ch.cov;  // :295-300: epsilon once more before the kept LLT
@@ -494,7 +518,7 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::run(const std::vec
             for (int i = 0; i < P; ++i) {
                 double s = 0.0;
                 for (int j = 0; j <= i; ++j) s += ch.chol[static_cast<size_t>(i) * P + j] * z[static_cast<size_t>(j)];
-                raw[i] = ch.x[static_cast<size_t>(i)] + ch.scale * s;
+                raw[i] = ch.x[static_cast<size_t>(i)] + ch.gs.scale * s;
             }
             const Eigen::VectorXd cons = pm.applyConstraints(raw);  // :309 (const, thread-safe)
             for (int i = 0; i < P; ++i) {
@@ -525,27 +549,8 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::run(const std::vec
             }
             if (keep_traces_) traces_[static_cast<size_t>(c)].push_back(accept ? 1 : 0);
             if (adapt_scale_) {  // adaptGlobalScale :104-152
-                ch.recent.push_back(accept ? 1 : 0);
-                if (ch.recent.size() > 1000) ch.recent.pop_front();
-                double rate = 0.0;
-                if (!ch.recent.empty()) {
-                    int sum = 0;
-                    for (int a : ch.recent) sum += a;
-                    rate = static_cast<double>(sum) / ch.recent.size();
-                }
-                if (ch.recent.size() >= 1000 && rate < 0.001) { ch.log_scale -= 0.7; ch.emergency++; }
-                else if (rate < 0.02 && ch.recent.size() >= 500) {
-                    double g = 5.0 / std::sqrt(static_cast<double>(t) + 1.0);
-                    g = std::min(g, 0.3);
-                    ch.log_scale += g * (0.0 - target_acceptance_rate_);
-                } else {
-                    double g = 1.0 / std::sqrt(static_cast<double>(t) + 1.0);
-                    g = std::min(g, 0.1);
-                    ch.log_scale += g * ((accept ? 1.0 : 0.0) - target_acceptance_rate_);
-                }
-                if (ch.scale <= 0.011 && rate > 0.15 && rate < 0.30) ch.log_scale += 0.01;
-                ch.log_scale = std::max(std::min(ch.log_scale, 2.3), -6.9);
-                ch.scale = std::exp(ch.log_scale);
+                ch.gs.advance(accept, t, target_acceptance_rate_);
+                ch.gs.scale = std::exp(ch.gs.log_scale);
             }
             if (two_pass_covariance_) ch.history.insert(ch.history.end(), ch.x.begin(), ch.x.end());
             else std::copy(ch.x.begin(), ch.x.end(), ch.history.begin());  // the newest state is all the rank-one update reads
@@ -560,25 +565,54 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::run(const std::vec
         for (int c = 0; c < reporter.k; ++c) {
             const Chain& ch = chains[static_cast<size_t>(c)];
             if (store_samples_ && (t % thinning_ == 0)) reporter.append(c, ch.x.data(), &ch.lp, 1);
-            if (reporter.due(t)) reporter.line(c, t, ch.lp, results[static_cast<size_t>(c)].bestObjectiveValue, ch.accepted, ch.scale);
+            if (reporter.due(t)) reporter.line(c, t, ch.lp, results[static_cast<size_t>(c)].bestObjectiveValue, ch.accepted, ch.gs.scale);
         }
         if (reporter.due(t)) reporter.checkpoint();
     }
 
     for (int c = 0; c < C; ++c) {
-        Chain& ch = chains[static_cast<size_t>(c)];
-        OptimizationResult& r = results[static_cast<size_t>(c)];
-        r.finalCovariance = Eigen::MatrixXd(P, P);
-        for (int i = 0; i < P; ++i)
-            for (int j = 0; j < P; ++j) r.finalCovariance(i, j) = ch.cov[static_cast<size_t>(i) * P + j];
-        r.additionalStats["acceptance_rate"] = static_cast<double>(ch.accepted) / iterations_;  // :387
-        r.additionalStats["accepted_count"] = ch.accepted;
-        r.additionalStats["final_scale"] = ch.scale;
-        r.additionalStats["burn_in"] = static_cast<double>(burn_in_);
-        r.additionalStats["total_iterations"] = static_cast<double>(iterations_);
+        const Chain& ch = chains[static_cast<size_t>(c)];
+        finishResult(results[static_cast<size_t>(c)], ch.cov.data(), P, ch.accepted, ch.gs.scale);
     }
     reporter.finish();
     return results;
+}
+
+// OpenMP team of a run's per-chain loops: the CPU share, under the caller's cap (setHostThreads), at most a thread per chain
+int MultiChainMetropolisHastings::teamSize(int C) const {
+    const int share = host_thread_share();
+    return std::min(host_threads_ > 0 ? std::min(host_threads_, share) : share, std::max(1, C));
+}
+
+// proposal covariance every chain starts from (:219-237), row-major P x P
+std::vector<double> MultiChainMetropolisHastings::initialProposalCovariance(IParameterManager& pm, int P) const {
+    const size_t PP = static_cast<size_t>(P) * P;
+    std::vector<double> cov;
+    if (initial_cov_.size() == PP) {  // warm start from phase 1 (:219-223): no 2.38^2/P scaling
+        cov = initial_cov_;
+    } else {
+        const double scaling_factor = (2.38 * 2.38) / static_cast<double>(P);
+        cov.assign(PP, 0.0);
+        for (int i = 0; i < P; ++i) {  // :226-237
+            const double s = pm.getSigmaForParamIndex(i);
+            cov[static_cast<size_t>(i) * P + i] = (s > 0 ? s * s : 1e-6);
+        }
+        for (double& v : cov) v *= scaling_factor;
+    }
+    for (int i = 0; i < P; ++i) cov[static_cast<size_t>(i) * P + i] += regularization_epsilon_;
+    return cov;
+}
+
+// the tail of a chain's result (:385-393): its final covariance (row-major P x P) and the run's statistics
+void MultiChainMetropolisHastings::finishResult(OptimizationResult& r, const double* cov, int P, int accepted, double scale) const {
+    r.finalCovariance = Eigen::MatrixXd(P, P);
+    for (int i = 0; i < P; ++i)
+        for (int j = 0; j < P; ++j) r.finalCovariance(i, j) = cov[static_cast<size_t>(i) * P + j];
+    r.additionalStats["acceptance_rate"] = static_cast<double>(accepted) / iterations_;  // :387
+    r.additionalStats["accepted_count"] = accepted;
+    r.additionalStats["final_scale"] = scale;
+    r.additionalStats["burn_in"] = static_cast<double>(burn_in_);
+    r.additionalStats["total_iterations"] = static_cast<double>(iterations_);
 }
 
 // ------------------------------------------------------------------ device-resident state
@@ -607,44 +641,92 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainsOnDe
     return runOnDevice(initial, C, pm, dev);
 }
 
-// the loop of both: everything below goes through the sepaihrd_mh handle, whichever context made it
+// ------------------------------------------------------------------ the device-resident run in its parts
+namespace {
+// What the host keeps per chain of a device-resident run.  The random stream is consumed in the reference's order: the normals
+// of a proposal, then ONE uniform only if log_ratio < 0 (:327), then the next proposal's normals.  While the device evaluates
+// proposal t the host draws BOTH continuations of proposal t + 1 from the chain's queue (with and without the uniform in
+// front) and hands them to the device, which runs the accept test itself; the host's own state (stream position, accept
+// window, scale) catches up one evaluation later.  A self-contained run fills lp .. sample_values from the device at its end.
+struct Light {
+    CanonicalQueue rng;   // the chain's stream, with look-ahead
+    size_t used_likely = 0, used_alt = 0;  // queue elements the two continuations of the pending accept test take
+    double log_u = 0.0;   // log of the uniform of the branch that draws it
+    double lp = 0.0, best = 0.0;
+    GlobalScale gs;
+    int accepted = 0;
+    double cand_log_scale[2] = {0.0, 0.0}, cand_scale[2] = {1.0, 1.0};  // adaptGlobalScale for reject / accept, prepared ahead
+    std::vector<double> best_x;
+    std::vector<double> sample_values;
+};
+using Clock = std::chrono::steady_clock;
+inline double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+}  // namespace
+
+// One device-resident run: the sampler handle (destroyed with it), the reporter, and what the parts hand to one another
+struct MultiChainMetropolisHastings::DeviceRun {
+    const MultiChainMetropolisHastings& mh_;
+    const DeviceSampler& dev;
+    const int C, P, nthreads;
+    Reporter reporter;
+    bool device_streams = false;  // streams and scale adaptation on the device: the self-contained loop
+    std::unique_ptr<sepaihrd_mh, decltype(&sepaihrd_mh_destroy)> mh{nullptr, sepaihrd_mh_destroy};
+    std::vector<Light> chains = std::vector<Light>(static_cast<size_t>(C));
+    std::vector<double> values = std::vector<double>(static_cast<size_t>(C));  // what the last test compared
+    std::vector<int32_t> rep_chains{};  // the reported chains: the first reporter.k
+    int rep_fetched = 0;                // samples of the reported chains already handed to the reporter
+    void check(int rc, const char* what) const {
+        if (rc != SEPAIHRD_OK) throw ModelException("MetropolisHastingsSampler", std::string(what) + ": " + dev.last_error());
+    }
+    // adaptation step that precedes proposal t (:279-301; the history then holds t rows, states 0 .. t-1)
+    int adapt_mode(int t) const {
+        if (t <= mh_.burn_in_) return 0;
+        if (t % mh_.adaptation_period_ != 0) return 1;
+        return static_cast<size_t>(t) >= static_cast<size_t>(P) + 10 ? 3 : 2;
+    }
+    // proposal 1 from the normals already on the device, and its evaluation: nothing to test yet
+    void first_step() const {
+        std::vector<double> scale(static_cast<size_t>(C));
+        for (int c = 0; c < C; ++c) scale[static_cast<size_t>(c)] = chains[static_cast<size_t>(c)].gs.scale;
+        check(sepaihrd_mh_step(mh.get(), nullptr, scale.data(), nullptr, nullptr, 0, 10.0 / (1 + 100.0), adapt_mode(1)), "mh_step");
+    }
+    // test t -> commit -> adapt -> proposal t + 1 -> evaluation t + 1: queued behind evaluation t
+    void step_tested(int t) const {
+        check(sepaihrd_mh_step_tested(mh.get(), 10.0 / ((t + 1) + 100.0), adapt_mode(t + 1), t + 1 < mh_.iterations_ ? 0 : 1), "mh_step_tested");
+    }
+};
+
+// the loop of both objectives: everything below goes through the sepaihrd_mh handle, whichever context made it
 std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const std::vector<double>& initial, int C, IParameterManager& pm,
                                                                            const DeviceSampler& dev) {
-    const int P = static_cast<int>(pm.getParameterCount());
-    if (static_cast<int>(initial.size()) != C * P) throw InvalidParameterException("MetropolisHastingsSampler", "initial size != C*P");
-    const double scaling_factor = (2.38 * 2.38) / static_cast<double>(P);
-    const size_t PP = static_cast<size_t>(P) * P;
-    const int nthreads = std::min(host_threads_ > 0 ? std::min(host_threads_, host_thread_share()) : host_thread_share(), std::max(1, C));
-    (void)nthreads;
+    if (static_cast<int>(initial.size()) != C * static_cast<int>(pm.getParameterCount()))
+        throw InvalidParameterException("MetropolisHastingsSampler", "initial size != C*P");
+    DeviceRun run{*this, dev, C, static_cast<int>(pm.getParameterCount()), teamSize(C), Reporter(*this, pm, C)};
+    setUpDeviceRun(run, initial, pm);
+    if (run.device_streams) selfContainedLoop(run);
+    else hostDrivenLoop(run);
+    return readBackDeviceRun(run);
+}
 
-    // initial covariance of every chain (:219-237)
-    std::vector<double> cov0;
-    if (initial_cov_.size() == PP) {
-        cov0 = initial_cov_;
-    } else {
-        cov0.assign(PP, 0.0);
-        for (int i = 0; i < P; ++i) {
-            const double s = pm.getSigmaForParamIndex(i);
-            cov0[static_cast<size_t>(i) * P + i] = (s > 0 ? s * s : 1e-6);
-        }
-        for (double& v : cov0) v *= scaling_factor;
-    }
-    for (int i = 0; i < P; ++i) cov0[static_cast<size_t>(i) * P + i] += regularization_epsilon_;
-
-    Reporter reporter(*this, pm, C);
+// The sampler on the device with every chain at its initial state and value, and the host's side of every chain.  The accept
+// test itself runs on the device (sepaihrd_mh_step_tested) in either loop; with the streams on the device the scale adaptation
+// goes there too (adaptGlobalScale in the test kernel).
+void MultiChainMetropolisHastings::setUpDeviceRun(DeviceRun& run, const std::vector<double>& initial, IParameterManager& pm) {
+    const int C = run.C, P = run.P;
+    const std::vector<double> cov0 = initialProposalCovariance(pm, P);
     // the device may draw the streams only if its log / exp ARE this host's libm (sepaihrd_device_libm_check)
-    bool device_streams = this->device_streams_;
+    run.device_streams = device_streams_;
     device_streams_fell_back_ = false;
-    if (device_streams) {
+    if (run.device_streams) {
         int32_t n_log = 0, n_exp = 0;
-        if (dev.libm_check(&n_log, &n_exp) != SEPAIHRD_OK)
-            throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_device_libm_check: ") + dev.last_error());
+        if (run.dev.libm_check(&n_log, &n_exp) != SEPAIHRD_OK)
+            throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_device_libm_check: ") + run.dev.last_error());
         if (n_log != 0 || n_exp != 0) {
-            device_streams = false;
+            run.device_streams = false;
             device_streams_fell_back_ = true;
-            reporter.say("WARNING", "the device's log / exp differ from this host's libm on " + std::to_string(n_log) + " (log) and " +
-                                        std::to_string(n_exp) + " (exp) of 4096 self-check arguments (csrc/sepaihrd_rng.inc restates glibc 2.35's "
-                                        "x86-64 FMA variants): random streams and scale adaptation stay on the host for this run");
+            run.reporter.say("WARNING", "the device's log / exp differ from this host's libm on " + std::to_string(n_log) + " (log) and " +
+                                            std::to_string(n_exp) + " (exp) of 4096 self-check arguments (csrc/sepaihrd_rng.inc restates glibc 2.35's "
+                                            "x86-64 FMA variants): random streams and scale adaptation stay on the host for this run");
         }
     }
     sepaihrd_mh_config mcfg{};
@@ -655,120 +737,166 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const 
     mcfg.adaptation_window = adaptation_window_ > 0 ? adaptation_window_ : std::max(adaptation_period_ + 1, 128);
     mcfg.covariance_mode = two_pass_covariance_ ? SEPAIHRD_MH_COV_TWO_PASS : SEPAIHRD_MH_COV_RUNNING;
     mcfg.reg_eps = regularization_epsilon_;
-    mcfg.scaling_factor = scaling_factor;
-    sepaihrd_mh* mh = dev.create(&mcfg, initial.data(), cov0.data());
-    if (!mh) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_mh_create: ") + dev.last_error());
-    struct Guard { sepaihrd_mh* p; ~Guard() { sepaihrd_mh_destroy(p); } } guard{mh};
-    auto check = [&](int rc, const char* what) {
-        if (rc != SEPAIHRD_OK) throw ModelException("MetropolisHastingsSampler", std::string(what) + ": " + dev.last_error());
-    };
-    check(sepaihrd_mh_set_kernel_form(mh, sampler_kernel_form_), "mh_set_kernel_form");
+    mcfg.scaling_factor = (2.38 * 2.38) / static_cast<double>(P);
+    run.mh.reset(run.dev.create(&mcfg, initial.data(), cov0.data()));
+    if (!run.mh) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_mh_create: ") + run.dev.last_error());
+    run.check(sepaihrd_mh_set_kernel_form(run.mh.get(), sampler_kernel_form_), "mh_set_kernel_form");
 
-    // What the host keeps per chain.  The random stream is consumed in the reference's order: the normals of a
-    // proposal, then ONE uniform only if log_ratio < 0 (:327), then the next proposal's normals.  While the device
-    // evaluates proposal t the host draws BOTH continuations of proposal t + 1 from the chain's queue (with and without
-    // the uniform in front) and hands them to the device, which runs the accept test itself; the host's own state
-    // (stream position, accept window, scale) catches up one evaluation later.
-    struct Light {
-        CanonicalQueue rng;   // the chain's stream, with look-ahead
-        size_t used_likely = 0, used_alt = 0;  // queue elements the two continuations of the pending accept test take
-        double log_u = 0.0;   // log of the uniform of the branch that draws it
-        double lp = 0.0, log_scale = 0.0, scale = 1.0, best = 0.0;
-        std::vector<unsigned char> recent;  // ring of the last 1000 accept flags (:107-110) + their sum
-        size_t recent_pos = 0, recent_len = 0;
-        int recent_sum = 0;
-        int emergency = 0, accepted = 0;
-        double cand_log_scale[2] = {0.0, 0.0}, cand_scale[2] = {1.0, 1.0};  // adaptGlobalScale for reject / accept, prepared ahead
-        std::vector<double> best_x;
-        std::vector<double> sample_values;
-    };
-    std::vector<Light> chains(static_cast<size_t>(C));
-    const size_t CP = static_cast<size_t>(C) * P;
-    std::vector<double> values(static_cast<size_t>(C)), scale(static_cast<size_t>(C));
-    double* z_next = sepaihrd_mh_staging_buffer(mh);  // page-locked; re-fetched after every staging (two alternate)
+    double* const z_first = sepaihrd_mh_staging_buffer(run.mh.get());  // page-locked: the normals of proposal 1 when the host draws
     std::vector<int32_t> status(static_cast<size_t>(C));
-    auto sanitize_all = [&]() {
-        for (int c = 0; c < C; ++c)
-            values[static_cast<size_t>(c)] = status[static_cast<size_t>(c)] >= 2 ? -1e18 : sanitize(values[static_cast<size_t>(c)]);
-    };
-    check(sepaihrd_mh_evaluate_current(mh, values.data(), status.data()), "mh_evaluate_current");  // :257
-    sanitize_all();
+    run.check(sepaihrd_mh_evaluate_current(run.mh.get(), run.values.data(), status.data()), "mh_evaluate_current");  // :257
+    for (int c = 0; c < C; ++c)
+        run.values[static_cast<size_t>(c)] = status[static_cast<size_t>(c)] >= 2 ? -1e18 : sanitize(run.values[static_cast<size_t>(c)]);
     traces_.assign(static_cast<size_t>(C), {});
-    // generateProposal :91-102 over the chain's queue from element `from` on; returns the elements used
-    auto draw_normals = [P](CanonicalQueue& q, size_t from, double* dst) { return standard_normals_from_queue(q, from, dst, P); };
-    // adaptGlobalScale (:104-152) as a function of the accept flag: the new log-scale, without touching the chain.
-    // Evaluated twice per chain AHEAD of the accept test (while the device works) so that the exp() of the branch
-    // taken is ready, and once more in the test itself for the ring bookkeeping -- same arithmetic both times.
-    const double target = target_acceptance_rate_;
-    auto next_log_scale = [target](const Light& ch, bool acc, int t, bool* emergency_hit) -> double {
-        size_t len = ch.recent_len;
-        int sum = ch.recent_sum;
-        if (len == 1000) sum -= ch.recent[ch.recent_pos]; else ++len;
-        sum += acc ? 1 : 0;
-        const double rate = static_cast<double>(sum) / static_cast<double>(len);
-        double ls = ch.log_scale;
-        *emergency_hit = false;
-        if (len >= 1000 && rate < 0.001) { ls -= 0.7; *emergency_hit = true; }
-        else if (rate < 0.02 && len >= 500) {
-            double g = 5.0 / std::sqrt(static_cast<double>(t) + 1.0);
-            g = std::min(g, 0.3);
-            ls += g * (0.0 - target);
-        } else {
-            double g = 1.0 / std::sqrt(static_cast<double>(t) + 1.0);
-            g = std::min(g, 0.1);
-            ls += g * ((acc ? 1.0 : 0.0) - target);
-        }
-        if (ch.scale <= 0.011 && rate > 0.15 && rate < 0.30) ls += 0.01;
-        return std::max(std::min(ls, 2.3), -6.9);
-    };
-#pragma omp parallel for schedule(static) num_threads(nthreads)
+#pragma omp parallel for schedule(static) num_threads(run.nthreads)
     for (int c = 0; c < C; ++c) {
-        Light& ch = chains[static_cast<size_t>(c)];
+        Light& ch = run.chains[static_cast<size_t>(c)];
         ch.rng.gen.seed(seed_ + static_cast<uint32_t>(c));
-        ch.lp = ch.best = values[static_cast<size_t>(c)];
+        ch.lp = ch.best = run.values[static_cast<size_t>(c)];
         ch.best_x.assign(initial.begin() + static_cast<size_t>(c) * P, initial.begin() + static_cast<size_t>(c + 1) * P);
-        ch.recent.assign(1000, 0);
         if (store_samples_) ch.sample_values.push_back(ch.lp);
         if (keep_traces_) traces_[static_cast<size_t>(c)].reserve(static_cast<size_t>(std::max(iterations_ - 1, 0)));
-        if (!device_streams) ch.rng.consume(draw_normals(ch.rng, 0, &z_next[static_cast<size_t>(c) * P]));  // proposal 1
-        scale[static_cast<size_t>(c)] = ch.scale;
+        if (!run.device_streams)  // proposal 1
+            ch.rng.consume(standard_normals_from_queue(ch.rng, 0, &z_first[static_cast<size_t>(c) * P], P));
     }
+    run.rep_chains.resize(static_cast<size_t>(run.reporter.k));
+    for (int c = 0; c < run.reporter.k; ++c) run.rep_chains[static_cast<size_t>(c)] = c;
+    if (run.device_streams)
+        run.check(sepaihrd_mh_keep_scale_on_device(run.mh.get(), adapt_scale_ ? 1 : 0, target_acceptance_rate_, keep_traces_ ? 1 : 0), "mh_keep_scale_on_device");
+    run.check(sepaihrd_mh_set_values(run.mh.get(), run.values.data()), "mh_set_values");
+}
 
-    const bool profile = std::getenv("SEPAIHRD_MH_PROFILE") != nullptr;
-    double t_launch = 0, t_prepare = 0, t_wait = 0, t_book = 0;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double>(b - a).count();
+// Streams and scale on the device: the sampler is self-contained, this loop only queues iterations, and what the host keeps per
+// chain is read back at the end.  The run is queued ahead of the device; a report must not wait for it.  Behind the iteration it
+// belongs to, a gather of the reported chains' values and new samples is queued and copied home on a stream of its own
+// (sepaihrd_mh_snapshot_begin); a writer thread waits for THAT, formats the line and rewrites the checkpoint file.
+void MultiChainMetropolisHastings::selfContainedLoop(DeviceRun& run) {
+    const int C = run.C, P = run.P;
+    sepaihrd_mh* const mh = run.mh.get();
+    Reporter& reporter = run.reporter;
+    const auto loop_begin = Clock::now();
+    run.check(sepaihrd_mh_seed_streams(mh, seed_), "mh_seed_streams");  // chain c: mt19937(seed + c), as the host's
+    if (iterations_ > 1) {
+        run.check(sepaihrd_mh_draw_first(mh), "mh_draw_first");
+        run.first_step();
+    }
+    std::thread writer;
+    std::string writer_error;
+    auto queue_report = [&](int t) {
+        if (writer.joinable()) writer.join();  // one snapshot in flight; reports are report_interval iterations apart
+        if (!writer_error.empty()) throw ModelException("MetropolisHastingsSampler", writer_error);
+        const int ns_now = store_samples_ ? sepaihrd_mh_sample_count(mh) : 0;
+        const int first = run.rep_fetched, count = std::max(ns_now - run.rep_fetched, 0);
+        run.check(sepaihrd_mh_snapshot_begin(mh, run.rep_chains.data(), reporter.k, first, count), "mh_snapshot_begin");
+        run.rep_fetched = ns_now;
+        writer = std::thread([&, t, count]() {
+            const size_t k = static_cast<size_t>(reporter.k), n = static_cast<size_t>(count);
+            std::vector<double> state(4 * k), smp(k * n * P), vals(k * n);
+            if (sepaihrd_mh_snapshot_end(mh, 1, state.data(), n ? smp.data() : nullptr, n ? vals.data() : nullptr) != SEPAIHRD_OK) {
+                writer_error = "sepaihrd_mh_snapshot_end failed";
+                return;
+            }
+            for (size_t c = 0; c < k; ++c) {
+                if (n) reporter.append(static_cast<int>(c), &smp[c * n * P], &vals[c * n], n);
+                reporter.line(static_cast<int>(c), t, state[4 * c], state[4 * c + 1], static_cast<long>(state[4 * c + 3]), state[4 * c + 2]);
+            }
+            reporter.checkpoint();
+        });
     };
-    // adaptation step that precedes proposal t (:279-301; the history then holds t rows, states 0 .. t-1)
-    auto adapt_mode = [&](int t) -> int {
-        if (t <= burn_in_) return 0;
-        if (t % adaptation_period_ != 0) return 1;
-        return static_cast<size_t>(t) >= static_cast<size_t>(P) + 10 ? 3 : 2;
-    };
-    // The accept test itself runs on the device (sepaihrd_mh_step_tested): the host hands it log(u), both outcomes of
-    // the scale adaptation and the normals of both continuations BEFORE the evaluation is over, so the device goes from
-    // one evaluation to the next without waiting for the host; the host learns the outcome (flags, the values compared)
-    // at the start of the next evaluation and does its bookkeeping for iteration t while evaluation t + 1 runs.
-    // With the streams on the device the scale adaptation goes there too (adaptGlobalScale in the test kernel): the sampler is
-    // self-contained, this loop only queues iterations, and what the host kept per chain is read back at the end
-    if (device_streams) check(sepaihrd_mh_keep_scale_on_device(mh, adapt_scale_ ? 1 : 0, target_acceptance_rate_, keep_traces_ ? 1 : 0), "mh_keep_scale_on_device");
-    check(sepaihrd_mh_set_values(mh, values.data()), "mh_set_values");
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{writer};
+    for (int t = 1; t < iterations_; ++t) {
+        run.step_tested(t);
+        if (reporter.due(t)) queue_report(t);
+    }
+    if (writer.joinable()) writer.join();
+    if (!writer_error.empty()) throw ModelException("MetropolisHastingsSampler", writer_error);
+    std::vector<double> lp_all(static_cast<size_t>(C)), best_all(static_cast<size_t>(C)), scale_all(static_cast<size_t>(C));
+    std::vector<int32_t> acc_all(static_cast<size_t>(C)), emergency_all(static_cast<size_t>(C));
+    run.check(sepaihrd_mh_read_run_state(mh, lp_all.data(), best_all.data(), scale_all.data(), acc_all.data(), emergency_all.data()), "mh_read_run_state");  // waits
+    last_loop_seconds_ = secs(loop_begin, Clock::now());
+    const int ns_dev = store_samples_ ? sepaihrd_mh_sample_count(mh) : 0;
+    std::vector<double> sv;
+    if (ns_dev > 0) {
+        sv.resize(static_cast<size_t>(C) * ns_dev);
+        run.check(sepaihrd_mh_read_sample_values(mh, 0, ns_dev, sv.data()), "mh_read_sample_values");
+    }
+    std::vector<uint8_t> tr;
+    if (keep_traces_ && iterations_ > 1) {
+        tr.resize(static_cast<size_t>(C) * (iterations_ - 1));
+        run.check(sepaihrd_mh_read_accept_trace(mh, tr.data()), "mh_read_accept_trace");
+    }
+#pragma omp parallel for schedule(static) num_threads(run.nthreads)
+    for (int c = 0; c < C; ++c) {
+        Light& ch = run.chains[static_cast<size_t>(c)];
+        ch.lp = lp_all[static_cast<size_t>(c)];
+        ch.best = best_all[static_cast<size_t>(c)];
+        ch.gs.scale = scale_all[static_cast<size_t>(c)];
+        ch.accepted = acc_all[static_cast<size_t>(c)];
+        ch.gs.emergency = emergency_all[static_cast<size_t>(c)];
+        if (ns_dev > 0) ch.sample_values.assign(sv.begin() + static_cast<size_t>(c) * ns_dev, sv.begin() + static_cast<size_t>(c + 1) * ns_dev);
+        if (!tr.empty()) {
+            auto& out = traces_[static_cast<size_t>(c)];
+            out.resize(static_cast<size_t>(iterations_ - 1));
+            for (int t = 0; t + 1 < iterations_; ++t) out[static_cast<size_t>(t)] = tr[static_cast<size_t>(t) * C + c];
+        }
+    }
+}
+
+// Streams on the host.  The host hands the device log(u), both outcomes of the scale adaptation and the normals of both
+// continuations BEFORE the evaluation is over, so the device goes from one evaluation to the next without waiting for the host;
+// the host learns the outcome (flags, the values compared) at the start of the next evaluation and does its bookkeeping for
+// iteration t while evaluation t + 1 runs.  SEPAIHRD_MH_PROFILE prints where this loop's time went.
+void MultiChainMetropolisHastings::hostDrivenLoop(DeviceRun& run) {
+    const int C = run.C, P = run.P;
+    sepaihrd_mh* const mh = run.mh.get();
+    Reporter& reporter = run.reporter;
+    std::vector<Light>& chains = run.chains;
+    std::vector<double>& values = run.values;
+    const double target = target_acceptance_rate_;
+    double* z_next = sepaihrd_mh_staging_buffer(mh);   // page-locked; re-fetched after every staging (two alternate)
     double* const test = sepaihrd_mh_test_buffer(mh);  // [log_u C][scale if rejected C][scale if accepted C][z_plain C*P]
     double* const t_log_u = test;
     double* const t_scale_reject = test + C;
     double* const t_scale_accept = test + 2 * static_cast<size_t>(C);
     double* const z_plain = test + 3 * static_cast<size_t>(C);
     std::vector<uint8_t> flags(static_cast<size_t>(C));
+    auto stage = [&] {
+        run.check(sepaihrd_mh_stage_normals(mh, z_next), "mh_stage_normals");
+        z_next = sepaihrd_mh_staging_buffer(mh);
+    };
+    // the inputs of test t and, unless it is the last, both continuations of proposal t + 1 (generateProposal :91-102 over the
+    // chain's queue).  adaptGlobalScale is evaluated for both outcomes AHEAD of the test so that the exp() of the branch taken
+    // is ready; book() evaluates it once more for the window -- same text, same arithmetic.
+    auto prepare = [&](int t, bool more) {
+#pragma omp parallel for schedule(static) num_threads(run.nthreads)
+        for (int c = 0; c < C; ++c) {
+            Light& ch = chains[static_cast<size_t>(c)];
+            // uniform_real_distribution<double>(0, 1) returns the canonical itself (c * (1 - 0) + 0)
+            ch.log_u = std::log(ch.rng.at(0));                                     // :327
+            t_log_u[c] = ch.log_u;
+            ch.used_likely = 1 + (more ? standard_normals_from_queue(ch.rng, 1, &z_next[static_cast<size_t>(c) * P], P) : 0);
+            if (more) ch.used_alt = standard_normals_from_queue(ch.rng, 0, &z_plain[static_cast<size_t>(c) * P], P);
+            if (adapt_scale_) {
+                for (int a = 0; a < 2; ++a) {
+                    ch.cand_log_scale[a] = ch.gs.candidate(a == 1, t, target);
+                    ch.cand_scale[a] = std::exp(ch.cand_log_scale[a]);
+                }
+                t_scale_reject[c] = ch.cand_scale[0];
+                t_scale_accept[c] = ch.cand_scale[1];
+            } else {
+                t_scale_reject[c] = t_scale_accept[c] = ch.gs.scale;
+            }
+        }
+    };
     // what the host keeps of iteration t once the test's outcome is known (:327-371 and adaptGlobalScale :104-152)
     auto book = [&](int t, bool drew_next) {
-#pragma omp parallel for schedule(static) num_threads(nthreads)
+#pragma omp parallel for schedule(static) num_threads(run.nthreads)
         for (int c = 0; c < C; ++c) {
             Light& ch = chains[static_cast<size_t>(c)];
             const uint8_t f = flags[static_cast<size_t>(c)];
             const bool acc = (f & 1) != 0;
             // the stream moves by what the continuation taken drew: no uniform (bit 2) -> the plain normals only
-            if (!device_streams) ch.rng.consume((f & 4) ? (drew_next ? ch.used_alt : 0) : ch.used_likely);
+            ch.rng.consume((f & 4) ? (drew_next ? ch.used_alt : 0) : ch.used_likely);
             if (acc) {
                 ch.lp = values[static_cast<size_t>(c)];
                 ch.accepted++;
@@ -776,179 +904,82 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const 
             }
             if (keep_traces_) traces_[static_cast<size_t>(c)].push_back(acc ? 1 : 0);
             if (adapt_scale_) {
-                bool emergency_hit;
-                const double ls = next_log_scale(ch, acc, t, &emergency_hit);
-                if (ch.recent_len == 1000) ch.recent_sum -= ch.recent[ch.recent_pos]; else ch.recent_len++;
-                ch.recent[ch.recent_pos] = acc ? 1 : 0;
-                ch.recent_sum += acc ? 1 : 0;
-                ch.recent_pos = (ch.recent_pos + 1) % 1000;
-                if (emergency_hit) ch.emergency++;
-                ch.log_scale = ls;
-                ch.scale = (ls == ch.cand_log_scale[acc ? 1 : 0]) ? ch.cand_scale[acc ? 1 : 0] : std::exp(ls);
+                ch.gs.advance(acc, t, target);
+                const double ls = ch.gs.log_scale;
+                ch.gs.scale = (ls == ch.cand_log_scale[acc ? 1 : 0]) ? ch.cand_scale[acc ? 1 : 0] : std::exp(ls);
             }
             if (store_samples_ && (t % thinning_ == 0)) ch.sample_values.push_back(ch.lp);
         }
     };
-    // reports and checkpoints of the first reporter.k chains
-    std::vector<int32_t> rep_chains(static_cast<size_t>(reporter.k));
-    for (int c = 0; c < reporter.k; ++c) rep_chains[static_cast<size_t>(c)] = c;
-    int rep_fetched = 0;  // samples of the reported chains already handed to the reporter
-    // host-side streams: the host has the chains' values, counts and scales of iteration t; the new samples of the reported
-    // chains come through the same snapshot, waited for at once (this loop waits for the device every iteration anyway)
-    auto report_from_host = [&](int t) {
+    // the host has the chains' values, counts and scales of iteration t; the new samples of the reported chains come through a
+    // snapshot, waited for at once (this loop waits for the device every iteration anyway)
+    auto report = [&](int t) {
         const int ns_now = store_samples_ ? std::min(sepaihrd_mh_sample_count(mh), t / thinning_ + 1) : 0;
-        const int count = std::max(ns_now - rep_fetched, 0);
+        const int count = std::max(ns_now - run.rep_fetched, 0);
         const size_t k = static_cast<size_t>(reporter.k), n = static_cast<size_t>(count);
         std::vector<double> smp(k * n * P);
         if (n) {
-            check(sepaihrd_mh_snapshot_begin(mh, rep_chains.data(), reporter.k, rep_fetched, count), "mh_snapshot_begin");
-            check(sepaihrd_mh_snapshot_end(mh, 1, nullptr, smp.data(), nullptr), "mh_snapshot_end");
+            run.check(sepaihrd_mh_snapshot_begin(mh, run.rep_chains.data(), reporter.k, run.rep_fetched, count), "mh_snapshot_begin");
+            run.check(sepaihrd_mh_snapshot_end(mh, 1, nullptr, smp.data(), nullptr), "mh_snapshot_end");
         }
         for (size_t c = 0; c < k; ++c) {
             const Light& ch = chains[c];
-            if (n) reporter.append(static_cast<int>(c), &smp[c * n * P], &ch.sample_values[static_cast<size_t>(rep_fetched)], n);
-            reporter.line(static_cast<int>(c), t, ch.lp, ch.best, ch.accepted, ch.scale);
+            if (n) reporter.append(static_cast<int>(c), &smp[c * n * P], &ch.sample_values[static_cast<size_t>(run.rep_fetched)], n);
+            reporter.line(static_cast<int>(c), t, ch.lp, ch.best, ch.accepted, ch.gs.scale);
         }
-        rep_fetched = ns_now;
+        run.rep_fetched = ns_now;
         reporter.checkpoint();
     };
-    const auto loop_begin = now();
-    if (device_streams) check(sepaihrd_mh_seed_streams(mh, seed_), "mh_seed_streams");  // chain c: mt19937(seed + c), as the host's
-    if (iterations_ > 1) {  // proposal 1: nothing to test yet
-        if (device_streams) {
-            check(sepaihrd_mh_draw_first(mh), "mh_draw_first");
-        } else {
-            check(sepaihrd_mh_stage_normals(mh, z_next), "mh_stage_normals");
-            z_next = sepaihrd_mh_staging_buffer(mh);
-        }
-        check(sepaihrd_mh_step(mh, nullptr, scale.data(), nullptr, nullptr, 0, 10.0 / (1 + 100.0), adapt_mode(1)), "mh_step");
-    }
-    if (device_streams) {
-        // The run is queued ahead of the device; a report must not wait for it.  Behind the iteration it belongs to, a gather of
-        // the reported chains' values and new samples is queued and copied home on a stream of its own
-        // (sepaihrd_mh_snapshot_begin); a writer thread waits for THAT, formats the line and rewrites the checkpoint file.
-        std::thread writer;
-        std::string writer_error;
-        auto queue_report = [&](int t) {
-            if (writer.joinable()) writer.join();  // one snapshot in flight; reports are report_interval iterations apart
-            if (!writer_error.empty()) throw ModelException("MetropolisHastingsSampler", writer_error);
-            const int ns_now = store_samples_ ? sepaihrd_mh_sample_count(mh) : 0;
-            const int first = rep_fetched, count = std::max(ns_now - rep_fetched, 0);
-            check(sepaihrd_mh_snapshot_begin(mh, rep_chains.data(), reporter.k, first, count), "mh_snapshot_begin");
-            rep_fetched = ns_now;
-            writer = std::thread([&, t, count]() {
-                const size_t k = static_cast<size_t>(reporter.k), n = static_cast<size_t>(count);
-                std::vector<double> state(4 * k), smp(k * n * P), vals(k * n);
-                if (sepaihrd_mh_snapshot_end(mh, 1, state.data(), n ? smp.data() : nullptr, n ? vals.data() : nullptr) != SEPAIHRD_OK) {
-                    writer_error = "sepaihrd_mh_snapshot_end failed";
-                    return;
-                }
-                for (size_t c = 0; c < k; ++c) {
-                    if (n) reporter.append(static_cast<int>(c), &smp[c * n * P], &vals[c * n], n);
-                    reporter.line(static_cast<int>(c), t, state[4 * c], state[4 * c + 1], static_cast<long>(state[4 * c + 3]), state[4 * c + 2]);
-                }
-                reporter.checkpoint();
-            });
-        };
-        struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{writer};
-        for (int t = 1; t < iterations_; ++t) {
-            check(sepaihrd_mh_step_tested(mh, 10.0 / ((t + 1) + 100.0), adapt_mode(t + 1), t + 1 < iterations_ ? 0 : 1), "mh_step_tested");
-            if (reporter.due(t)) queue_report(t);
-        }
-        if (writer.joinable()) writer.join();
-        if (!writer_error.empty()) throw ModelException("MetropolisHastingsSampler", writer_error);
-        std::vector<double> lp_all(static_cast<size_t>(C)), best_all(static_cast<size_t>(C)), scale_all(static_cast<size_t>(C));
-        std::vector<int32_t> acc_all(static_cast<size_t>(C)), emergency_all(static_cast<size_t>(C));
-        check(sepaihrd_mh_read_run_state(mh, lp_all.data(), best_all.data(), scale_all.data(), acc_all.data(), emergency_all.data()), "mh_read_run_state");  // waits
-        last_loop_seconds_ = secs(loop_begin, now());
-        const int ns_dev = store_samples_ ? sepaihrd_mh_sample_count(mh) : 0;
-        std::vector<double> sv;
-        if (ns_dev > 0) {
-            sv.resize(static_cast<size_t>(C) * ns_dev);
-            check(sepaihrd_mh_read_sample_values(mh, 0, ns_dev, sv.data()), "mh_read_sample_values");
-        }
-        std::vector<uint8_t> tr;
-        if (keep_traces_ && iterations_ > 1) {
-            tr.resize(static_cast<size_t>(C) * (iterations_ - 1));
-            check(sepaihrd_mh_read_accept_trace(mh, tr.data()), "mh_read_accept_trace");
-        }
-#pragma omp parallel for schedule(static) num_threads(nthreads)
-        for (int c = 0; c < C; ++c) {
-            Light& ch = chains[static_cast<size_t>(c)];
-            ch.lp = lp_all[static_cast<size_t>(c)];
-            ch.best = best_all[static_cast<size_t>(c)];
-            ch.scale = scale_all[static_cast<size_t>(c)];
-            ch.accepted = acc_all[static_cast<size_t>(c)];
-            ch.emergency = emergency_all[static_cast<size_t>(c)];
-            if (ns_dev > 0) ch.sample_values.assign(sv.begin() + static_cast<size_t>(c) * ns_dev, sv.begin() + static_cast<size_t>(c + 1) * ns_dev);
-            if (!tr.empty()) {
-                auto& out = traces_[static_cast<size_t>(c)];
-                out.resize(static_cast<size_t>(iterations_ - 1));
-                for (int t = 0; t + 1 < iterations_; ++t) out[static_cast<size_t>(t)] = tr[static_cast<size_t>(t) * C + c];
-            }
-        }
-    } else {
-    for (int t = 1; t < iterations_; ++t) {
-        const auto p0 = now();
-        const bool more = t + 1 < iterations_;
-        if (t > 1) {  // the outcome of test t - 1 (the device ran it when evaluation t - 1 ended)
-            check(sepaihrd_mh_fetch_test(mh, values.data(), flags.data()), "mh_fetch_test");
-            const auto p0b = now();
-            t_wait += secs(p0, p0b);
-            book(t - 1, true);
-            if (reporter.due(t - 1)) report_from_host(t - 1);
-            t_book += secs(p0b, now());
-        }
-        const auto p1 = now();
-        // ---- while the device evaluates proposal t: the inputs of test t and both continuations of proposal t + 1
-#pragma omp parallel for schedule(static) num_threads(nthreads)
-        for (int c = 0; c < C; ++c) {
-            Light& ch = chains[static_cast<size_t>(c)];
-            if (!device_streams) {
-                // uniform_real_distribution<double>(0, 1) returns the canonical itself (c * (1 - 0) + 0)
-                ch.log_u = std::log(ch.rng.at(0));                                     // :327
-                t_log_u[c] = ch.log_u;
-                ch.used_likely = 1 + (more ? draw_normals(ch.rng, 1, &z_next[static_cast<size_t>(c) * P]) : 0);
-                if (more) ch.used_alt = draw_normals(ch.rng, 0, &z_plain[static_cast<size_t>(c) * P]);
-            }
-            if (adapt_scale_) {
-                bool e;
-                for (int a = 0; a < 2; ++a) {
-                    ch.cand_log_scale[a] = next_log_scale(ch, a == 1, t, &e);
-                    ch.cand_scale[a] = std::exp(ch.cand_log_scale[a]);
-                }
-                t_scale_reject[c] = ch.cand_scale[0];
-                t_scale_accept[c] = ch.cand_scale[1];
-            } else {
-                t_scale_reject[c] = t_scale_accept[c] = ch.scale;
-            }
-        }
-        if (more && !device_streams) {
-            check(sepaihrd_mh_stage_normals(mh, z_next), "mh_stage_normals");
-            z_next = sepaihrd_mh_staging_buffer(mh);
-        }
-        const auto p2 = now();
-        // test t -> commit -> adapt -> proposal t + 1 -> evaluation t + 1: queued behind evaluation t
-        check(sepaihrd_mh_step_tested(mh, 10.0 / ((t + 1) + 100.0), adapt_mode(t + 1), more ? 0 : 1), "mh_step_tested");
-        const auto p3 = now();
-        t_prepare += secs(p1, p2); t_launch += secs(p2, p3);
-    }
+    // the outcome of test t (the device ran it when evaluation t ended)
+    auto fetch_and_book = [&](int t, bool drew_next) {
+        run.check(sepaihrd_mh_fetch_test(mh, values.data(), flags.data()), "mh_fetch_test");
+        const auto fetched = Clock::now();
+        book(t, drew_next);
+        if (reporter.due(t)) report(t);
+        return fetched;
+    };
+
+    double t_launch = 0, t_prepare = 0, t_wait = 0, t_book = 0;
+    const auto loop_begin = Clock::now();
     if (iterations_ > 1) {
-        check(sepaihrd_mh_fetch_test(mh, values.data(), flags.data()), "mh_fetch_test");
-        book(iterations_ - 1, false);
-        if (reporter.due(iterations_ - 1)) report_from_host(iterations_ - 1);
+        stage();  // the normals of proposal 1 (setUpDeviceRun drew them)
+        run.first_step();
     }
-    last_loop_seconds_ = secs(loop_begin, now());
-    }  // host-side streams
-    {   // the best states were kept on the device
-        std::vector<double> best_all(CP);
-        check(sepaihrd_mh_read_best(mh, best_all.data()), "mh_read_best");
-        for (int c = 0; c < C; ++c)
-            chains[static_cast<size_t>(c)].best_x.assign(best_all.begin() + static_cast<size_t>(c) * P, best_all.begin() + static_cast<size_t>(c + 1) * P);
+    for (int t = 1; t < iterations_; ++t) {
+        const auto p0 = Clock::now();
+        const bool more = t + 1 < iterations_;
+        if (t > 1) {
+            const auto p0b = fetch_and_book(t - 1, true);
+            t_wait += secs(p0, p0b);
+            t_book += secs(p0b, Clock::now());
+        }
+        const auto p1 = Clock::now();
+        prepare(t, more);  // while the device evaluates proposal t
+        if (more) stage();
+        const auto p2 = Clock::now();
+        run.step_tested(t);
+        const auto p3 = Clock::now();
+        t_prepare += secs(p1, p2);
+        t_launch += secs(p2, p3);
     }
-    if (profile)
+    if (iterations_ > 1) fetch_and_book(iterations_ - 1, false);
+    last_loop_seconds_ = secs(loop_begin, Clock::now());
+    if (std::getenv("SEPAIHRD_MH_PROFILE") != nullptr)
         std::fprintf(stderr, "[mh profile] per iteration ms: wait for the previous test %.3f  bookkeeping %.3f  prepare test and both continuations %.3f  upload + launches %.3f\n",
                      1e3 * t_wait / iterations_, 1e3 * t_book / iterations_, 1e3 * t_prepare / iterations_, 1e3 * t_launch / iterations_);
+}
+
+// What the run leaves: best states, samples and their values, covariances, summary records, diagnostics, failure counts, and
+// the reporter's trace files
+std::vector<OptimizationResult> MultiChainMetropolisHastings::readBackDeviceRun(DeviceRun& run) {
+    const int C = run.C, P = run.P;
+    const size_t PP = static_cast<size_t>(P) * P;
+    sepaihrd_mh* const mh = run.mh.get();
+    Reporter& reporter = run.reporter;
+    std::vector<double> best_all(static_cast<size_t>(C) * P);  // the best states were kept on the device
+    run.check(sepaihrd_mh_read_best(mh, best_all.data()), "mh_read_best");
+    for (int c = 0; c < C; ++c)
+        run.chains[static_cast<size_t>(c)].best_x.assign(best_all.begin() + static_cast<size_t>(c) * P, best_all.begin() + static_cast<size_t>(c + 1) * P);
 
     std::vector<double> rows, covs(static_cast<size_t>(C) * PP);
     const int ns = store_samples_ ? sepaihrd_mh_sample_count(mh) : 0;  // state 0 and every thinning-th one (:266-268,357-360)
@@ -962,22 +993,22 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const 
         int first = burn_in_ / thinning_ + 1;
         if (first >= ns) first = 0;
         double* d_rec = nullptr;  // null: the records stay in the sampler's own buffer
-        if (dev.records_buffer) {
-            d_rec = dev.records_buffer(static_cast<size_t>(C) * summary_width_);
-            if (!d_rec) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_records_buffer: ") + dev.last_error());
+        if (run.dev.records_buffer) {
+            d_rec = run.dev.records_buffer(static_cast<size_t>(C) * summary_width_);
+            if (!d_rec) throw ModelException("MetropolisHastingsSampler", std::string("sepaihrd_records_buffer: ") + run.dev.last_error());
         }
         summary_records_.resize(static_cast<size_t>(C) * summary_width_);
-        check(sepaihrd_mh_summary_records(mh, first, summary_records_.data(), d_rec), "mh_summary_records");
+        run.check(sepaihrd_mh_summary_records(mh, first, summary_records_.data(), d_rec), "mh_summary_records");
         if (compute_diagnostics_) {
             // convergence diagnostics over the same samples, from the resident store (and the values the device kept)
             if (ns - first >= 4) {
                 ChainDiagnosticsTable t;
-                t.rows = P + (device_streams ? 1 : 0);
+                t.rows = P + (run.device_streams ? 1 : 0);
                 t.values.resize(static_cast<size_t>(t.rows) * SEPAIHRD_DIAG_COLUMNS);
                 t.max_lag.resize(static_cast<size_t>(t.rows) * 4);
-                const auto d0 = now();
-                check(sepaihrd_mh_diagnostics(mh, first, 0, device_streams ? 1 : 0, t.values.data(), t.max_lag.data()), "mh_diagnostics");
-                diagnostics_seconds_ = secs(d0, now());
+                const auto d0 = Clock::now();
+                run.check(sepaihrd_mh_diagnostics(mh, first, 0, run.device_streams ? 1 : 0, t.values.data(), t.max_lag.data()), "mh_diagnostics");
+                diagnostics_seconds_ = secs(d0, Clock::now());
                 diagnostics_ = std::move(t);
             } else {
                 reporter.say("WARNING", "fewer than 4 stored samples after burn-in: no convergence diagnostics");
@@ -986,12 +1017,12 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const 
     }
     if (ns > 0) {
         rows.resize(static_cast<size_t>(C) * ns * P);
-        check(sepaihrd_mh_read_samples(mh, 0, ns, rows.data()), "mh_read_samples");
+        run.check(sepaihrd_mh_read_samples(mh, 0, ns, rows.data()), "mh_read_samples");
     }
-    check(sepaihrd_mh_read_covariance(mh, covs.data()), "mh_read_covariance");
+    run.check(sepaihrd_mh_read_covariance(mh, covs.data()), "mh_read_covariance");
     std::vector<OptimizationResult> results(static_cast<size_t>(C));
     for (int c = 0; c < C; ++c) {
-        Light& ch = chains[static_cast<size_t>(c)];
+        const Light& ch = run.chains[static_cast<size_t>(c)];
         OptimizationResult& r = results[static_cast<size_t>(c)];
         r.bestParameters = Eigen::VectorXd(P);
         for (int i = 0; i < P; ++i) r.bestParameters[i] = ch.best_x[static_cast<size_t>(i)];
@@ -1002,18 +1033,11 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const 
             r.samples.push_back(v);
         }
         r.sampleObjectiveValues = ch.sample_values;
-        r.finalCovariance = Eigen::MatrixXd(P, P);
-        for (int i = 0; i < P; ++i)
-            for (int j = 0; j < P; ++j) r.finalCovariance(i, j) = covs[static_cast<size_t>(c) * PP + static_cast<size_t>(i) * P + j];
-        r.additionalStats["acceptance_rate"] = static_cast<double>(ch.accepted) / iterations_;
-        r.additionalStats["accepted_count"] = ch.accepted;
-        r.additionalStats["final_scale"] = ch.scale;
-        r.additionalStats["burn_in"] = static_cast<double>(burn_in_);
-        r.additionalStats["total_iterations"] = static_cast<double>(iterations_);
+        finishResult(r, &covs[static_cast<size_t>(c) * PP], P, ch.accepted, ch.gs.scale);
     }
     {   // evaluations the accept tests saw FAIL (they counted as -1e18, like an objective that throws)
         int64_t fc[3] = {0, 0, 0};
-        check(sepaihrd_mh_read_failure_counts(mh, fc), "mh_read_failure_counts");
+        run.check(sepaihrd_mh_read_failure_counts(mh, fc), "mh_read_failure_counts");
         failure_counts_.assign({static_cast<long>(fc[0]), static_cast<long>(fc[1]), static_cast<long>(fc[2])});
         for (OptimizationResult& r : results) r.additionalStats["failed_evaluations_all_chains"] = static_cast<double>(fc[0] + fc[1] + fc[2]);
         if (fc[0] + fc[1] > 0)
@@ -1026,7 +1050,7 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::runOnDevice(const 
     // the trace files of the reported chains, from everything the run stored (:399-411)
     for (int c = 0; c < reporter.k && ns > 0; ++c) {
         reporter.samples[static_cast<size_t>(c)].assign(rows.begin() + static_cast<size_t>(c) * ns * P, rows.begin() + static_cast<size_t>(c + 1) * ns * P);
-        reporter.values[static_cast<size_t>(c)] = chains[static_cast<size_t>(c)].sample_values;
+        reporter.values[static_cast<size_t>(c)] = run.chains[static_cast<size_t>(c)].sample_values;
     }
     reporter.finish();
     return results;
@@ -1062,7 +1086,7 @@ std::vector<OptimizationResult> MultiChainMetropolisHastings::optimizeChainGroup
     if (auto* spm = dynamic_cast<HipSEPAIHRDParameterManager*>(&pm)) spm->setConstraintMode(ConstraintMode::MCMC_REFLECT);
     std::vector<int> first(static_cast<size_t>(G) + 1, 0);
     for (int g = 0; g < G; ++g) first[static_cast<size_t>(g) + 1] = first[static_cast<size_t>(g)] + C / G + (g < C % G ? 1 : 0);
-    const int share = host_threads_ > 0 ? std::min(host_threads_, host_thread_share()) : host_thread_share();
+    const int share = teamSize(std::numeric_limits<int>::max());  // not capped by the chains: divided among the groups below
     std::vector<std::vector<OptimizationResult>> parts(static_cast<size_t>(G));
     std::vector<std::vector<std::vector<unsigned char>>> part_traces(static_cast<size_t>(G));
     std::vector<std::string> errors(static_cast<size_t>(G));
