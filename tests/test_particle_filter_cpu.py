@@ -200,7 +200,8 @@ def test_resampling_rule(mm):
 def test_the_estimate_is_unbiased_across_particle_counts(mm):
     """n = 1, 6 output rows (one of them run-up).  exp(loglik) estimates p(y | theta) without bias for every J, so the means of
     exp(loglik - c) at J = 2 and at J = 64 agree within their standard errors: K = 150 seeds x 4 positions = 600 estimates each,
-    difference below 5 combined standard errors.  Deterministic: the seeds are fixed."""
+    difference below 5 combined standard errors.  Deterministic: the seeds are fixed.
+    An error that biases both arms alike passes here; tests/test_particle_filter_exact_cpu.py compares with the exact likelihood."""
     case = Case(mm, n=1, T=6, runup=1, m=2)
     rows = np.stack([case.row] * 4)
     K = 150

@@ -99,6 +99,37 @@ def chi_square_against_binomial(draws, n, p):
     return pval, z
 
 
+def chi_square_against_pmf(draws, pmf):
+    """chi_square_against_binomial for a given pmf over 0 .. len(pmf) - 1 (finite support: nothing to cut): the same pooling,
+    left to right until the expected count is at least 10, the remainder into the last pooled bin; (p-value, z of the sample
+    mean).  A draw outside the support, or where the pmf is exactly 0, is an assertion error: no bin could hold it."""
+    from scipy import stats
+    draws = np.asarray(draws).astype(np.int64).ravel()
+    prob = np.asarray(pmf, dtype=np.float64)
+    assert abs(prob.sum() - 1.0) < 1e-9 and draws.min() >= 0 and draws.max() < len(prob)
+    obs = np.bincount(draws, minlength=len(prob)).astype(np.float64)
+    assert not obs[prob == 0.0].any(), "draws where the pmf is exactly 0"
+    exp = prob * len(draws)
+    O, E, o, e = [], [], 0.0, 0.0
+    for oi, ei in zip(obs, exp):
+        o, e = o + oi, e + ei
+        if e >= 10.0:
+            O.append(o); E.append(e)
+            o = e = 0.0
+    if e > 0.0 or o > 0.0:  # what is left joins the last pooled bin
+        if O:
+            O[-1] += o; E[-1] += e
+        else:
+            O.append(o); E.append(e)
+    O, E = np.array(O), np.array(E)
+    pval = 1.0 if len(O) < 2 else float(stats.chi2.sf(np.sum((O - E) ** 2 / E), len(O) - 1))
+    k = np.arange(len(prob))
+    mean = float(np.sum(k * prob))
+    sd = math.sqrt(max(0.0, float(np.sum(k * k * prob)) - mean * mean) / len(draws))
+    z = 0.0 if sd == 0.0 else (float(np.mean(draws, dtype=np.float64)) - mean) / sd
+    return pval, z
+
+
 @pytest.mark.parametrize("n", BINOM_N)
 def test_binomial_sampler_distribution(mm, n):
     """56 cases, 200 000 draws each at a fixed seed: chi-square p-value >= 1e-6 and |z| of the sample mean <= 6 in every one
