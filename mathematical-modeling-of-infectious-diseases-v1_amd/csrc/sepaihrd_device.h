@@ -1,4 +1,4 @@
-// csrc/sepaihrd_device.h -- structures shared by the C-ABI host code (sepaihrd_capi.cpp)
+// csrc/sepaihrd_device.h -- structures shared by the C-ABI host code (sepaihrd_capi.cpp, sepaihrd_mh_capi.cpp)
 // and the HIP kernels (sepaihrd_kernels.hip).  Internal: not part of the C ABI.
 #pragma once
 #define SEPAIHRD_HAVE_DEV_PROBLEM 1  // csrc/sepaihrd_constrain.inc adds its DevProblem part where this is set
@@ -276,18 +276,29 @@ int sampler_propose(const SamplerState& s, const DevProblem& pb, const double* d
 int sampler_commit(const SamplerState& s, const uint8_t* d_accept, int row, void* stream);
 int sampler_commit_counted(const SamplerState& s, const uint8_t* d_accept, int row, int accepted_known, void* stream);
 // the accept test on the device (flags: bit 0 accepted, bit 1 best so far, bit 2 no uniform drawn) and the proposal that
-// follows it with the normals of the continuation taken
-// row: the state the test's outcome becomes (= the iteration t of the test); used by the device-kept scale adaptation,
-// the value store and the accept trace
-int sampler_accept_test(const SamplerState& s, const int row, const double* d_loglik, const int32_t* d_status, const double* d_log_u, const double* d_scale_reject,
-                        const double* d_scale_accept, double* d_lp, double* d_best_lp, double* d_scale_sel, uint8_t* d_flags,
-                        double* d_values, void* stream);
+// follows it with the normals of the continuation taken.  What the test reads and writes, all [C] but the normals ([C][P]):
+struct SamplerTestArgs {
+    const double* loglik;        // the evaluation's values and statuses
+    const int32_t* status;
+    const double* log_u;         // the test's inputs: log of the uniform, the next scale after a rejection / an acceptance
+    const double* scale_reject;
+    const double* scale_accept;
+    double* lp;                  // the chains' current and best values
+    double* best_lp;
+    double* scale_sel;           // the scale the test selected
+    uint8_t* flags;              // its outcome
+    double* values;
+    const double* z_uniform;     // the proposal's normals for both continuations (the fused launches only) ...
+    const double* z_plain;
+    const double* lz_uniform;    // ... and L z of them where sampler_lz formed it ahead, else null: the launch reads the factor
+    const double* lz_plain;
+    // the state the test's outcome becomes (= the iteration t of the test); used by the device-kept scale adaptation, the value
+    // store and the accept trace
+    int row;
+};
+int sampler_accept_test(const SamplerState& s, const SamplerTestArgs& a, void* stream);
 // the three in one launch (block = chain), for iterations without a covariance refresh between commit and proposal
-int sampler_test_commit_propose(const SamplerState& s, const DevProblem& pb, const double* d_loglik, const int32_t* d_status,
-                                const double* d_log_u, const double* d_scale_reject, const double* d_scale_accept, double* d_lp,
-                                double* d_best_lp, double* d_scale_sel, uint8_t* d_flags, double* d_values, const double* d_z_uniform,
-                                const double* d_z_plain, int row, void* stream, const double* d_lz_uniform = nullptr,
-                                const double* d_lz_plain = nullptr);
+int sampler_test_commit_propose(const SamplerState& s, const DevProblem& pb, const SamplerTestArgs& a, void* stream);
 // L z of both continuations' normals ahead of the test (d_lz_*: [C][P]); the fused launch above then takes them instead of
 // reading the factor itself
 int sampler_lz(const SamplerState& s, const double* d_z_uniform, const double* d_z_plain, double* d_lz_uniform, double* d_lz_plain, void* stream);

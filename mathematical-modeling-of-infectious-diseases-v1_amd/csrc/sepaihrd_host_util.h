@@ -1,5 +1,6 @@
 // csrc/sepaihrd_host_util.h -- what the host side of the C ABI does the same way in every entry point: the error text, the
-// choice of the device, the buffers of one call, the buffers a context keeps between calls, the copies of the results.  Host code only.
+// choice of the device, the buffers of one call, the buffers a context keeps between calls, the copies of the results, the
+// convergence diagnostics' checks.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "sepaihrd_device.h"
 #include "sepaihrd_hip.h"
 
 namespace sepaihrd {
@@ -198,6 +200,37 @@ int require_device_memory(Ctx* ctx, size_t need_bytes, const std::string& what, 
     ctx->last_error = what + " " + std::to_string(need_bytes >> 20) + " MiB of device memory, the device has " +
                       std::to_string(device_bytes >> 20) + " MiB: " + advice;
     return SEPAIHRD_E_INVALID_ARG;
+}
+
+// The convergence diagnostics of a context's own samples (sepaihrd_chain_diagnostics) and of a sampler's (sepaihrd_mh_diagnostics):
+// the shape both accept, and the run with its failures as the C ABI's codes.  Ctx: anything with last_error and pending_B.
+// (static: an instantiation stays in the translation unit that asked for it)
+template <class Ctx>
+static int diag_check_shape(Ctx* ctx, const char* who, int C, int N, int P) {
+    if (C < 1 || P < 1 || N < 4) {
+        ctx->last_error = std::string(who) + ": need C >= 1 chains, P >= 1 columns and N >= 4 draws per chain";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if ((int64_t)C * N >= ((int64_t)1 << 31)) {
+        ctx->last_error = std::string(who) + ": C N must stay below 2^31 draws per column";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (ctx->pending_B > 0) {
+        ctx->last_error = std::string(who) + ": a sepaihrd_eval_batch_begin is pending on this context";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    return SEPAIHRD_OK;
+}
+template <class Ctx>
+static int diag_run(Ctx* ctx, const char* who, const DiagInput& in, double* out, int32_t* max_lag, hipStream_t st) {
+    const int rc = chain_diagnostics(in, out, max_lag, st);
+    if (rc == -4) { ctx->last_error = std::string(who) + ": invalid shape"; return SEPAIHRD_E_INVALID_ARG; }
+    if (rc != 0) {
+        const hipError_t e = hipGetLastError();
+        ctx->last_error = std::string(who) + ": device failure (" + hipGetErrorString(e) + ")";
+        return SEPAIHRD_E_HIP;
+    }
+    return SEPAIHRD_OK;
 }
 
 }  // namespace sepaihrd

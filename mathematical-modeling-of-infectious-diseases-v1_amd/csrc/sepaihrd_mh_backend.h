@@ -1,4 +1,4 @@
-// csrc/sepaihrd_mh_backend.h -- what the device-resident sampler (sepaihrd_mh, csrc/sepaihrd_capi.cpp) needs of the context
+// csrc/sepaihrd_mh_backend.h -- what the device-resident sampler (sepaihrd_mh, csrc/sepaihrd_mh_capi.cpp) needs of the context
 // it samples on, and the packed small-P form of its per-iteration kernels (csrc/sepaihrd_sampler.hip).  Internal: not part of
 // the C ABI.  Two contexts make samplers: sepaihrd_ctx (sepaihrd_mh_create) and sepaihrd_sir_ctx (sepaihrd_sir_mh_create).
 #pragma once
@@ -33,10 +33,21 @@ struct MhBackend {
     sepaihrd_sir_ctx* sir;
 };
 
-// sepaihrd_mh_create's body over either context (csrc/sepaihrd_capi.cpp)
+// sepaihrd_mh_create's body over either context (csrc/sepaihrd_mh_capi.cpp)
 sepaihrd_mh* mh_create_on(const MhBackend& be, const sepaihrd_mh_config* cfg, const double* x0, const double* cov0);
 // sepaihrd_device_libm_check's body: runs the self-check once per context (diffs < 0: not run yet)
 int device_libm_check(int device, std::string& last_error, int& log_diff, int& exp_diff, int32_t* n_log_diff, int32_t* n_exp_diff);
+
+// What a sampler needs of a SEPAIHRD context beyond the record, defined beside the context (csrc/sepaihrd_capi.cpp): the record
+// itself, and the context's bookkeeping of the streams it has launched on (fence_before / fence_after there).  Between the
+// library's own translation units only: not among its dynamic symbols.
+#pragma GCC visibility push(hidden)
+MhBackend mh_backend_of(sepaihrd_ctx* ctx);
+// a sampler's stream is now the context's lazy stream: launches after the first on it record no event
+void ctx_adopt_lazy_stream(sepaihrd_ctx* ctx, void* stream);
+// the context forgets this (drained) stream before it is destroyed
+void ctx_forget_stream(sepaihrd_ctx* ctx, void* stream);
+#pragma GCC visibility pop
 
 // ---- packed form: a chain is a group of G = pow2(P) adjacent lanes, 64 / G chains per wavefront (P <= 64) ----
 constexpr int MH_PACKED_MAX_P = 64;
@@ -64,9 +75,6 @@ int sampler_draw_packed(const SamplerState& s, const uint8_t* d_flags, int first
                         int want_normals, uint8_t* d_todo, void* stream);
 int sampler_lz_packed(const SamplerState& s, const double* d_z_uniform, const double* d_z_plain, double* d_lz_uniform, double* d_lz_plain,
                       void* stream);
-int sampler_test_commit_propose_packed(const SamplerState& s, const MhBounds& b, const double* d_loglik, const int32_t* d_status,
-                                       const double* d_log_u, const double* d_scale_reject, const double* d_scale_accept, double* d_lp,
-                                       double* d_best_lp, double* d_scale_sel, uint8_t* d_flags, double* d_values, const double* d_z_uniform,
-                                       const double* d_z_plain, int row, void* stream, const double* d_lz_uniform, const double* d_lz_plain);
+int sampler_test_commit_propose_packed(const SamplerState& s, const MhBounds& b, const SamplerTestArgs& a, void* stream);
 
 }  // namespace sepaihrd

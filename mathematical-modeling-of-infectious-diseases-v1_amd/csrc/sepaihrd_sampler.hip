@@ -1010,11 +1010,9 @@ int sampler_patch_normals(double* d_z, const int32_t* d_chain, const double* d_r
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int sampler_accept_test(const SamplerState& s, const int row, const double* d_loglik, const int32_t* d_status, const double* d_log_u, const double* d_scale_reject,
-                        const double* d_scale_accept, double* d_lp, double* d_best_lp, double* d_scale_sel, uint8_t* d_flags,
-                        double* d_values, void* stream) {
-    hipLaunchKernelGGL(mh_accept_kernel, dim3(blocks_for((size_t)s.C, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), s, row, d_loglik,
-                       d_status, d_log_u, d_scale_reject, d_scale_accept, d_lp, d_best_lp, d_scale_sel, d_flags, d_values);
+int sampler_accept_test(const SamplerState& s, const SamplerTestArgs& a, void* stream) {
+    hipLaunchKernelGGL(mh_accept_kernel, dim3(blocks_for((size_t)s.C, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), s, a.row, a.loglik,
+                       a.status, a.log_u, a.scale_reject, a.scale_accept, a.lp, a.best_lp, a.scale_sel, a.flags, a.values);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 int sampler_propose_select(const SamplerState& s, const DevProblem& pb, const double* d_z_uniform, const double* d_z_plain,
@@ -1024,14 +1022,11 @@ int sampler_propose_select(const SamplerState& s, const DevProblem& pb, const do
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int sampler_test_commit_propose(const SamplerState& s, const DevProblem& pb, const double* d_loglik, const int32_t* d_status,
-                                const double* d_log_u, const double* d_scale_reject, const double* d_scale_accept, double* d_lp,
-                                double* d_best_lp, double* d_scale_sel, uint8_t* d_flags, double* d_values, const double* d_z_uniform,
-                                const double* d_z_plain, int row, void* stream, const double* d_lz_uniform, const double* d_lz_plain) {
+int sampler_test_commit_propose(const SamplerState& s, const DevProblem& pb, const SamplerTestArgs& a, void* stream) {
     if (s.P > 200) return -3;
-    hipLaunchKernelGGL(mh_test_commit_propose_kernel, dim3(s.C), dim3(2 * WAVE), 0, static_cast<hipStream_t>(stream), s, pb, d_loglik, d_status,
-                       d_log_u, d_scale_reject, d_scale_accept, d_lp, d_best_lp, d_scale_sel, d_flags, d_values, d_z_uniform, d_z_plain, row,
-                       d_lz_uniform, d_lz_plain);
+    hipLaunchKernelGGL(mh_test_commit_propose_kernel, dim3(s.C), dim3(2 * WAVE), 0, static_cast<hipStream_t>(stream), s, pb, a.loglik, a.status,
+                       a.log_u, a.scale_reject, a.scale_accept, a.lp, a.best_lp, a.scale_sel, a.flags, a.values, a.z_uniform, a.z_plain, a.row,
+                       a.lz_uniform, a.lz_plain);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 int sampler_lz(const SamplerState& s, const double* d_z_uniform, const double* d_z_plain, double* d_lz_uniform, double* d_lz_plain, void* stream) {
@@ -1070,12 +1065,9 @@ int sampler_lz_packed(const SamplerState& s, const double* d_z_uniform, const do
                       void* stream) {
     SEPAIHRD_PACKED_DISPATCH(mh_lz_packed_kernel, s, d_z_uniform, d_z_plain, d_lz_uniform, d_lz_plain);
 }
-int sampler_test_commit_propose_packed(const SamplerState& s, const MhBounds& b, const double* d_loglik, const int32_t* d_status,
-                                       const double* d_log_u, const double* d_scale_reject, const double* d_scale_accept, double* d_lp,
-                                       double* d_best_lp, double* d_scale_sel, uint8_t* d_flags, double* d_values, const double* d_z_uniform,
-                                       const double* d_z_plain, int row, void* stream, const double* d_lz_uniform, const double* d_lz_plain) {
-    SEPAIHRD_PACKED_DISPATCH(mh_test_commit_propose_packed_kernel, s, b, d_loglik, d_status, d_log_u, d_scale_reject, d_scale_accept, d_lp,
-                             d_best_lp, d_scale_sel, d_flags, d_values, d_z_uniform, d_z_plain, row, d_lz_uniform, d_lz_plain);
+int sampler_test_commit_propose_packed(const SamplerState& s, const MhBounds& b, const SamplerTestArgs& a, void* stream) {
+    SEPAIHRD_PACKED_DISPATCH(mh_test_commit_propose_packed_kernel, s, b, a.loglik, a.status, a.log_u, a.scale_reject, a.scale_accept, a.lp,
+                             a.best_lp, a.scale_sel, a.flags, a.values, a.z_uniform, a.z_plain, a.row, a.lz_uniform, a.lz_plain);
 }
 #undef SEPAIHRD_PACKED_DISPATCH
 

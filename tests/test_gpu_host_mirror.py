@@ -972,7 +972,7 @@ def test_checkpoints_and_progress_lines_while_the_device_resident_sampler_runs(m
 
 def test_draws_queued_behind_the_evaluation_give_the_overlapped_result(mm, shipped, monkeypatch):
     """The draws of the next accept test run beside the evaluation on the copy stream, except for batches that fill the chip
-    with two integrator waves per SIMD, where they queue behind it on the main stream (csrc/sepaihrd_capi.cpp
+    with two integrator waves per SIMD, where they queue behind it on the main stream (csrc/sepaihrd_mh_capi.cpp
     mh_draws_behind_the_evaluation); beside the evaluation they are followed by L z of both continuations (mh_lz_kernel), which
     the fused test + commit + proposal launch then takes instead of reading the factor itself.  Where the kernels are
     launched changes nothing they compute: the same run with either placement forced, and with the look-ahead product on or
