@@ -955,6 +955,39 @@ int sepaihrd_particle_timing(const sepaihrd_ctx *ctx, double *ms);
 int sepaihrd_particle_resample_device(int device, uint64_t seed, uint32_t b, uint32_t row, const double *logw, int J,
                                       int32_t *ancestors, double *increment, double *ess, char *err, int errlen);
 
+/* ---- the wide form of that filter: thousands of particles per theta (additive; SEPAIHRD_ABI_VERSION stays) -------------------
+ * The same filter -- the particle coordinates, the log-weight, M, w, the Kogge-Stone order of the two prefix sums, the increment,
+ * the ESS, the resampling uniform, the binary-search ancestor, resampling at every weighted row, skipped rows and invalid theta
+ * are those of csrc/sepaihrd_particle.inc, unchanged -- with the particles in device memory and the work of every output row
+ * spread over the whole device: J up to sepaihrd_particle_wide_max_particles() = 65536.  For J within
+ * sepaihrd_particle_max_particles(n_age) the outputs are the bits of sepaihrd_particle_loglik; for every J they are the bits of the
+ * host twin (host/: hostParticleLoglikWide).  Outputs, statuses and the rules for an invalid theta are word for word those of
+ * sepaihrd_particle_loglik, and so is what the result for theta[b] depends on: (seed, b, J, steps_per_interval) and its model
+ * values alone -- not B, not the outputs asked for, not the arithmetic mode, not theta_chunk.
+ * The call runs as plain launches on one stream: per segment of output rows (the rows after a weighted row up to and including
+ * the next, a row being weighted when its time is >= 0 and one of its cells is usable) one propagate-and-weight launch, per
+ * weighted row one normalise-and-resample launch with one workgroup per theta.
+ *   theta_chunk   the B vectors pass through the scratch theta_chunk at a time, chunk after chunk; b in the stream coordinates is
+ *                 the position in the call.  0: as many as keep the scratch at or under 1 GiB (at least one).  The scratch is
+ *                 theta_chunk J (88 lpc + 44) bytes, lpc = n_age rounded up to a power of two.
+ * SEPAIHRD_E_INVALID_ARG, before the device is touched and with the outputs untouched: B < 1, J outside [1, 65536],
+ * theta_chunk < 0, steps_per_interval < 1, n_times steps_per_interval >= 2^22, B J >= 2^31, a pending sepaihrd_eval_batch_begin,
+ * or scratch and buffers beyond the device's memory.  SEPAIHRD_E_UNSUPPORTED in F32 precision or beyond 16 age classes. */
+int sepaihrd_particle_loglik_wide(sepaihrd_ctx *ctx, const double *theta, int B, int J, int steps_per_interval, uint64_t seed,
+                                  int theta_chunk, double *loglik, double *increments, double *ess, double *final_state,
+                                  double *model_values, int32_t *status, int32_t *n_valid);
+/* Host only: the argument rules above that need no context, with a message in err (NULL: not wanted). */
+int sepaihrd_particle_wide_validate(int B, int J, int steps_per_interval, int theta_chunk, int n_times, int T_pos, int n_age,
+                                    char *err, int errlen);
+/* Host only: the largest J the wide form takes, 65536 for every n_age. */
+int sepaihrd_particle_wide_max_particles(void);
+/* Device time of the context's last sepaihrd_particle_loglik_wide call in milliseconds, ms[2]: decode; all filter launches. */
+int sepaihrd_particle_wide_timing(const sepaihrd_ctx *ctx, double *ms);
+/* Probe of the wide form's normalise-and-resample kernel: one weighted row with log-weights logw [J] (finite, J in 1..65536) at
+ * the resampling coordinates of (seed, b, row).  ancestors [J], increment and ess: host memory. */
+int sepaihrd_particle_wide_resample_device(int device, uint64_t seed, uint32_t b, uint32_t row, const double *logw, int J,
+                                           int32_t *ancestors, double *increment, double *ess, char *err, int errlen);
+
 #ifdef __cplusplus
 }
 #endif

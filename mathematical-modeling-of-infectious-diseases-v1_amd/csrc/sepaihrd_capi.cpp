@@ -23,6 +23,7 @@
 #include "sepaihrd_predictive_device.h"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_particle_device.h"
+#include "sepaihrd_particle_wide_device.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
 using namespace sepaihrd;
@@ -102,6 +103,10 @@ struct sepaihrd_ctx {
     double stoch_ms[2] = {0.0, 0.0};
     // the last sepaihrd_particle_loglik call: decode, filter kernel (ms)
     double particle_ms[2] = {0.0, 0.0};
+    // the last sepaihrd_particle_loglik_wide call: decode, all filter launches (ms); and the host's copy of dp.grid, from which
+    // that call plans its launches (which output rows have a usable observation)
+    double particle_wide_ms[2] = {0.0, 0.0};
+    std::vector<double> host_grid;
     Stream own_stream;  // sepaihrd_eval_batch_begin / _end; last: see above
 };
 
@@ -486,6 +491,7 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
     bool ok = true;
     d.times = upload(ctx->allocs, std::vector<double>(pb->times, pb->times + T), ok);
     d.grid = upload(ctx->allocs, grid, ok);
+    ctx->host_grid = grid;
     d.lower = upload(ctx->allocs, ctx->lower, ok);
     d.upper = upload(ctx->allocs, ctx->upper, ok);
     d.has_bounds = upload(ctx->allocs, hb, ok);
@@ -1177,6 +1183,93 @@ int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int 
 int sepaihrd_particle_timing(const sepaihrd_ctx* ctx, double* ms) {
     if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
     for (int i = 0; i < 2; ++i) ms[i] = ctx->particle_ms[i];
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, int theta_chunk,
+                                  double* loglik, double* increments, double* ess, double* final_state, double* model_values, int32_t* status,
+                                  int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    const char* const who = "particle_loglik_wide";
+    if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
+    int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
+    if (rc != SEPAIHRD_OK) return rc;
+    const DevProblem& dp = ctx->dp;
+    const int Tp = dp.T - dp.runup_offset;
+    if (dp.n > 16 || dp.lpc > 16) return refuse(ctx, who, "built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
+    {
+        char msg[256] = "";
+        if (sepaihrd_particle_wide_validate(B, J, steps_per_interval, theta_chunk, dp.T, Tp, dp.n, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            ctx->last_error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    if (ctx->precision != SEPAIHRD_PRECISION_F64)
+        return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
+    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
+    // sizes
+    const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
+    const size_t n_values = (size_t)B * W, n_rows = (size_t)B * Tp;
+    const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
+    const size_t chunk = particle_wide_chunk(dp.lpc, J, B, theta_chunk);
+    const size_t scratch_bytes = particle_wide_scratch_bytes(dp.lpc, J, chunk);
+    const size_t need_bytes = scratch_bytes + sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final) +
+                              sizeof(int32_t) * ((size_t)B + 2);
+    rc = require_device_memory(ctx, need_bytes,
+                               "particle_loglik_wide: the particles of " + std::to_string(chunk) + " parameter vectors at a time, the model values of B = " +
+                                   std::to_string(B) + " and the outputs asked for need",
+                               "lower theta_chunk or split the parameter vectors over several calls");
+    if (rc != SEPAIHRD_OK) return rc;
+    // buffers and events of this call alone
+    CallScratch sc(3);
+    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_scratch = nullptr;
+    int32_t *d_counts = nullptr, *d_status = nullptr;
+    if (!sc.alloc(&d_theta, (size_t)B * ctx->P) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_ll, (size_t)B) ||
+        !sc.alloc(&d_inc, increments ? n_rows : 0) || !sc.alloc(&d_ess, ess ? n_rows : 0) || !sc.alloc(&d_final, n_final) ||
+        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) || !sc.alloc(&d_scratch, (scratch_bytes + sizeof(double) - 1) / sizeof(double)))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
+    for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    // launches
+    StochEpiArgs da{};
+    da.S = B; da.R = J; da.W = W;
+    da.theta = d_theta; da.values = d_values; da.status = d_status; da.counts = d_counts;
+    (void)hipEventRecord(sc.ev[0], nullptr);
+    if (launch_stoch_epi_decode(dp, da, nullptr) != 0) return refuse(ctx, who, "decode kernel launch failed", SEPAIHRD_E_HIP);
+    (void)hipEventRecord(sc.ev[1], nullptr);
+    ParticleWideArgs a{};
+    a.B = B; a.J = J; a.m = steps_per_interval; a.W = W;
+    a.chunk = chunk;
+    a.seed = seed;
+    a.values = d_values; a.status = d_status; a.loglik = d_ll;
+    a.increments = increments ? d_inc : nullptr; a.ess = ess ? d_ess : nullptr; a.final_state = final_state ? d_final : nullptr;
+    a.scratch = d_scratch;
+    a.host_grid = ctx->host_grid.data();
+    const int lrc = launch_particle_filter_wide(dp, a, nullptr);
+    (void)hipEventRecord(sc.ev[2], nullptr);
+    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
+    if (lrc != 0) return refuse(ctx, who, "filter launch failed", SEPAIHRD_E_HIP);
+    for (int i = 0; i < 2; ++i) {
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
+        ctx->particle_wide_ms[i] = ms;
+    }
+    // fetches
+    ResultFetch res;
+    res.fetch(loglik, d_ll, (size_t)B * sizeof(double));
+    res.fetch(increments, d_inc, n_rows * sizeof(double));
+    res.fetch(ess, d_ess, n_rows * sizeof(double));
+    res.fetch(final_state, d_final, n_final * sizeof(double));
+    res.fetch(model_values, d_values, n_values * sizeof(double));
+    res.fetch(status, d_status, (size_t)B * sizeof(int32_t));
+    res.fetch(n_valid, d_counts, sizeof(int32_t));
+    if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_particle_wide_timing(const sepaihrd_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
+    for (int i = 0; i < 2; ++i) ms[i] = ctx->particle_wide_ms[i];
     return SEPAIHRD_OK;
 }
 

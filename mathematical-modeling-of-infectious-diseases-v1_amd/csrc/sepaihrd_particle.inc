@@ -28,7 +28,8 @@
 // from row to row and there is no adaptive (ESS-threshold) rule.
 //
 // Only correctly rounded IEEE operations and glibc_log / glibc_exp: both sides compile with contraction off.
-// Included by csrc/sepaihrd_particle.hip and by the host library (host/src/HipParticleFilter.cpp).
+// Included by csrc/sepaihrd_particle.hip, csrc/sepaihrd_particle_wide.hip (the wide form, DESIGN.md section 6l) and by the host
+// library (host/src/HipParticleFilter.cpp).
 #pragma once
 #include "sepaihrd_stoch_sepaihrd.inc"
 

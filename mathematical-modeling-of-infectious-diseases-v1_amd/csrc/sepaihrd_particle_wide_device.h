@@ -1,0 +1,51 @@
+// csrc/sepaihrd_particle_wide_device.h -- what csrc/sepaihrd_capi.cpp (sepaihrd_particle_loglik_wide) and
+// csrc/sepaihrd_particle_wide.hip (the wide form of the bootstrap particle filter: its kernels, its launch plan and the probe of
+// one row's normalisation and resampling) share.  DESIGN.md section 6l.  The rules are csrc/sepaihrd_particle.inc, the decode
+// from theta to model values is launch_stoch_epi_decode (csrc/sepaihrd_stoch_sepaihrd_device.h), both unchanged.
+//
+// The particles of a chunk of thetas live in device memory, in scratch the caller owns.  Per theta of the chunk and particle
+// (lpc = n_age rounded up to a power of two):
+//     2 x 11 counts x 4 bytes x lpc      the two copies of the state, int32 [copy][b][11][J][lpc]
+//     8                                  lw, double [b][J]
+//     4 x 8                              the prefix sums C and Q, each twice (the scans ping-pong), double [b][J]
+//     4                                  the ancestor, int32 [b][J]
+// so particle_wide_scratch_bytes(lpc, J, chunk) = chunk J (88 lpc + 44).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "sepaihrd_device.h"
+
+namespace sepaihrd {
+
+constexpr int PARTICLE_WIDE_MAX_J = 65536;
+constexpr size_t PARTICLE_WIDE_AUTO_SCRATCH = (size_t)1 << 30;  // theta_chunk = 0: as many thetas as keep the scratch within this
+constexpr size_t particle_wide_scratch_bytes(int lpc, int J, size_t chunk) {
+    return chunk * (size_t)J * ((size_t)2 * NUM_COMP * 4 * (size_t)lpc + 8 + 4 * 8 + 4);
+}
+// the thetas per chunk: theta_chunk where it is positive, else the automatic choice; never more than B, never fewer than one
+constexpr size_t particle_wide_chunk(int lpc, int J, int B, int theta_chunk) {
+    size_t c = theta_chunk > 0 ? (size_t)theta_chunk : PARTICLE_WIDE_AUTO_SCRATCH / particle_wide_scratch_bytes(lpc, J, 1);
+    c = c < 1 ? 1 : c;
+    return c < (size_t)B ? c : (size_t)B;
+}
+
+struct ParticleWideArgs {
+    int B, J, m, W;           // thetas, particles per theta, steps per output interval, width of a model-values row
+    size_t chunk;             // thetas per chunk (particle_wide_chunk)
+    uint64_t seed;
+    const double* values;     // [B][W] device: launch_stoch_epi_decode's rows
+    const int32_t* status;    // [B] device: 0, or SEPAIHRD_STATUS_INVALID
+    double* loglik;           // [B] device
+    double* increments;       // [B][Tp] device or null
+    double* ess;              // [B][Tp] device or null
+    double* final_state;      // [B][J][11][n] device or null
+    void* scratch;            // device, particle_wide_scratch_bytes(lpc, J, chunk) bytes, 8-byte aligned
+    const double* host_grid;  // [T][lpc][4] HOST copy of DevProblem::grid: which rows are weighted is planned from it
+};
+// The whole filter as plain launches on the stream, chunk after chunk: a fill of the outputs, then per segment one
+// propagate-and-weight launch and, where the segment ends in a weighted row, one normalise-and-resample launch; the final state
+// last.  No synchronisation inside.  0, -3 (a launch failed) or -4 (arguments).
+int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a, void* stream);
+
+}  // namespace sepaihrd

@@ -24,7 +24,8 @@
 // sample's position, r the replicate -- the Coord of csrc/sepaihrd_stoch.inc with replicate = s, step = r and
 // 2 group + transition carrying the packed third word.  T m < 2^22 keeps that word below 2^32.
 // Only correctly rounded IEEE operations and glibc_log / glibc_exp: both sides compile with contraction off.
-// Included by csrc/sepaihrd_stoch_sepaihrd.hip, csrc/sepaihrd_particle.hip (through csrc/sepaihrd_particle.inc) and by the host
+// Included by csrc/sepaihrd_stoch_sepaihrd.hip, csrc/sepaihrd_particle.hip and csrc/sepaihrd_particle_wide.hip (through
+// csrc/sepaihrd_particle.inc) and by the host
 // library (host/src/StochasticSEPAIHRDTwin.hpp: HipStochasticSEPAIHRD.cpp, HipParticleFilter.cpp).
 #pragma once
 #include "sepaihrd_stoch.inc"

@@ -220,6 +220,8 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_ensemble_stochastic", "sepaihrd_stochastic_validate", "sepaihrd_stochastic_values_width", "sepaihrd_stochastic_timing",
     "sepaihrd_particle_loglik", "sepaihrd_particle_validate", "sepaihrd_particle_max_particles", "sepaihrd_particle_timing",
     "sepaihrd_particle_resample_device",
+    "sepaihrd_particle_loglik_wide", "sepaihrd_particle_wide_validate", "sepaihrd_particle_wide_max_particles", "sepaihrd_particle_wide_timing",
+    "sepaihrd_particle_wide_resample_device",
 )
 
 _lib = None
@@ -360,6 +362,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_particle_timing.argtypes = [vp, vp]
     lib.sepaihrd_particle_resample_device.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(C.c_double),
                                                       C.POINTER(C.c_double), C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_loglik_wide.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int] + [vp] * 7
+    lib.sepaihrd_particle_wide_validate.argtypes = [C.c_int] * 7 + [C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_wide_max_particles.argtypes = []
+    lib.sepaihrd_particle_wide_timing.argtypes = [vp, vp]
+    lib.sepaihrd_particle_wide_resample_device.argtypes = lib.sepaihrd_particle_resample_device.argtypes
     if path is None:
         _lib = lib
     return lib
@@ -655,6 +662,17 @@ class HipObjective:
         steps_per_interval binomial steps per output interval, systematic resampling at every observed row.  loglik [B] (the
         estimate of log p(y | theta); -DBL_MAX for an invalid theta), increments [B][T_pos], ess [B][T_pos], final_state
         [B][J][11][n], model_values [B][W], status [B], n_valid."""
+        return self._particle_call("particle_loglik", self.lib.sepaihrd_particle_loglik, (), theta, J, steps_per_interval, seed, want_increments,
+                                   want_ess, want_final, want_values)
+
+    def particle_loglik_wide(self, theta, J: int, steps_per_interval: int, seed: int, theta_chunk: int = 0, want_increments: bool = True,
+                             want_ess: bool = True, want_final: bool = False, want_values: bool = False) -> dict:
+        """The wide form of particle_loglik (sepaihrd_particle_loglik_wide): the particles in device memory, J up to 65 536, the
+        thetas theta_chunk at a time (0: chosen by the call).  The same outputs, bit for bit where particle_loglik takes J."""
+        return self._particle_call("particle_loglik_wide", self.lib.sepaihrd_particle_loglik_wide, (int(theta_chunk),), theta, J, steps_per_interval,
+                                   seed, want_increments, want_ess, want_final, want_values)
+
+    def _particle_call(self, who, fn, extra, theta, J, steps_per_interval, seed, want_increments, want_ess, want_final, want_values) -> dict:
         th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
         B, n, J = th.shape[0], self.pb.n, int(J)
         Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
@@ -667,9 +685,8 @@ class HipObjective:
         status = np.empty(B, dtype=np.int32)
         nv = C.c_int32(0)
         ptr = lambda a: None if a is None else a.ctypes.data
-        self._check(self.lib.sepaihrd_particle_loglik(
-            self.ctx, th.ctypes.data, B, J, int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, loglik.ctypes.data, ptr(inc), ptr(ess),
-            ptr(final), ptr(values), status.ctypes.data, C.byref(nv)), "particle_loglik")
+        self._check(fn(self.ctx, th.ctypes.data, B, J, int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, *extra, loglik.ctypes.data, ptr(inc),
+                       ptr(ess), ptr(final), ptr(values), status.ctypes.data, C.byref(nv)), who)
         out = {"loglik": loglik, "status": status, "n_valid": nv.value}
         for key, arr in (("increments", inc), ("ess", ess), ("final_state", final), ("model_values", values)):
             if arr is not None:
@@ -682,17 +699,31 @@ class HipObjective:
         self._check(self.lib.sepaihrd_particle_timing(self.ctx, ms.ctypes.data), "particle_timing")
         return ms
 
+    def particle_wide_timing(self) -> np.ndarray:
+        """Device time of the last particle_loglik_wide call in ms: decode; all filter launches (sepaihrd_particle_wide_timing)"""
+        ms = np.zeros(2)
+        self._check(self.lib.sepaihrd_particle_wide_timing(self.ctx, ms.ctypes.data), "particle_wide_timing")
+        return ms
+
     def particle_resample_device(self, logw, seed: int, b: int = 0, row: int = 0) -> dict:
         """Probe of the device's normalisation, scans and ancestor search (sepaihrd_particle_resample_device): one weighted row
         with log-weights logw [J] at the resampling coordinates (seed, b, row).  ancestors [J], increment, ess."""
+        return self._resample_probe("sepaihrd_particle_resample_device", logw, seed, b, row)
+
+    def particle_wide_resample_device(self, logw, seed: int, b: int = 0, row: int = 0) -> dict:
+        """The same probe through the wide form's normalise-and-resample kernel (sepaihrd_particle_wide_resample_device): J up to
+        65 536."""
+        return self._resample_probe("sepaihrd_particle_wide_resample_device", logw, seed, b, row)
+
+    def _resample_probe(self, name, logw, seed, b, row) -> dict:
         lw = np.ascontiguousarray(logw, dtype=np.float64).ravel()
         anc = np.empty(lw.size, dtype=np.int32)
         inc, ess = C.c_double(0.0), C.c_double(0.0)
         err = C.create_string_buffer(512)
-        rc = self.lib.sepaihrd_particle_resample_device(getattr(self, "_device", -1), int(seed) & 0xFFFFFFFFFFFFFFFF, int(b), int(row),
-                                                        lw.ctypes.data, lw.size, anc.ctypes.data, C.byref(inc), C.byref(ess), err, len(err))
+        rc = getattr(self.lib, name)(getattr(self, "_device", -1), int(seed) & 0xFFFFFFFFFFFFFFFF, int(b), int(row), lw.ctypes.data, lw.size,
+                                     anc.ctypes.data, C.byref(inc), C.byref(ess), err, len(err))
         if rc != 0:
-            raise RuntimeError(f"sepaihrd_particle_resample_device failed ({rc}): " + err.value.decode())
+            raise RuntimeError(f"{name} failed ({rc}): " + err.value.decode())
         return {"ancestors": anc, "increment": inc.value, "ess": ess.value}
 
     def poisson(self, lam, seed: int) -> np.ndarray:

@@ -31,7 +31,13 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                        const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
                        double* ess, double* final_state, std::string* error = nullptr);
 
-// the twin of sepaihrd_particle_resample_device: one weighted row with log-weights logw [J] at the coordinates (seed, b, row)
+// The twin of sepaihrd_particle_loglik_wide: the same walk behind sepaihrd_particle_wide_validate's rules (J up to 65 536; the
+// twin has no chunks, theta_chunk does not change a result).
+int hostParticleLoglikWide(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                           const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
+                           double* ess, double* final_state, std::string* error = nullptr);
+
+// the twin of sepaihrd_particle_resample_device and of sepaihrd_particle_wide_resample_device (any J): one weighted row with log-weights logw [J] at the coordinates (seed, b, row)
 void hostParticleResample(std::uint64_t seed, std::uint32_t b, std::uint32_t row, const double* logw, int J, int32_t* ancestors,
                           double* increment, double* ess);
 
@@ -40,7 +46,8 @@ void hostParticleResample(std::uint64_t seed, std::uint32_t b, std::uint32_t row
 // MetropolisHastingsSampler) keep the value of the current point and do not evaluate it again: run over this objective, the
 // existing Adaptive-Metropolis loop is therefore particle-marginal Metropolis-Hastings (Andrieu, Doucet & Holenstein 2010) and
 // targets the exact posterior of the stochastic model.  Nothing in the samplers changes.  An invalid theta gives lowest(), as
-// the ODE objective does.
+// the ODE objective does.  With `particles` at or below sepaihrd_particle_max_particles(n_age) the call is
+// sepaihrd_particle_loglik; above it, sepaihrd_particle_loglik_wide with theta_chunk = 0 (up to 65 536 particles).
 class HipParticleLikelihood : public virtual IObjectiveFunction, public IBatchObjectiveFunction {
 public:
     HipParticleLikelihood(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
@@ -59,7 +66,7 @@ private:
     std::vector<double> time_points_;
     SimulationCache cache_;
     std::unique_ptr<HipSEPAIHRDObjectiveFunction> objective_;
-    int particles_, steps_per_interval_;
+    int particles_, steps_per_interval_, n_age_;
     std::uint64_t seed0_;
     mutable std::uint64_t calls_ = 0;
 };

@@ -16,18 +16,13 @@ namespace epidemic {
 namespace epi = sepaihrd_stoch_epi;
 namespace pf = sepaihrd_particle;
 
-int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
-                       const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
-                       double* ess, double* final_state, std::string* error) {
-    char msg[256] = "";
-    const stoch_twin::Plan plan = stoch_twin::plan(pb);
-    const int vrc = stoch_twin::verdict(
-        "particle_loglik", sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg,
-        {{!model_values || !status || !loglik, "model_values, status and loglik must not be NULL"},
-         {stoch_twin::fixed_data_missing(pb), stoch_twin::FIXED_DATA_TEXT},
-         {obs.n_obs < 0 || (obs.n_obs > 0 && (!obs.obs_H || !obs.obs_ICU || !obs.obs_D)), "the observations need obs_H, obs_ICU and obs_D"}},
-        error);
-    if (vrc != SEPAIHRD_OK) return vrc;
+namespace {
+
+// The filter's walk over B parameter vectors, after the arguments have been accepted: what hostParticleLoglik and
+// hostParticleLoglikWide both are.  Nothing in it depends on how large J is.
+void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan, const ParticleObservations& obs, const double* model_values,
+                   const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments, double* ess,
+                   double* final_state) {
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     const int n = pb.n_age, T = pb.n_times, m = steps_per_interval, runup_offset = plan.runup_offset;
     const size_t Tp = (size_t)plan.T_pos, nn = (size_t)n, W = plan.W, row_doubles = plan.row_doubles;
@@ -104,6 +99,44 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                 for (int i = 0; i < n; ++i)
                     for (int c = 0; c < epi::NUM_COMP; ++c) my_final[(size_t)j * row_doubles + (size_t)c * nn + (size_t)i] = (double)x_of(state, j, i)[c];
     }
+}
+
+// the arguments of either form: the validator's verdict (vrc, msg), then what the walk itself needs
+int particle_verdict(const char* who, int vrc, char (&msg)[256], const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs,
+                     const double* model_values, const int32_t* status, const double* loglik, std::string* error) {
+    return stoch_twin::verdict(
+        who, vrc, msg,
+        {{!model_values || !status || !loglik, "model_values, status and loglik must not be NULL"},
+         {stoch_twin::fixed_data_missing(pb), stoch_twin::FIXED_DATA_TEXT},
+         {obs.n_obs < 0 || (obs.n_obs > 0 && (!obs.obs_H || !obs.obs_ICU || !obs.obs_D)), "the observations need obs_H, obs_ICU and obs_D"}},
+        error);
+}
+
+}  // namespace
+
+int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                       const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
+                       double* ess, double* final_state, std::string* error) {
+    char msg[256] = "";
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    const int vrc = particle_verdict("particle_loglik",
+                                     sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg,
+                                     pb, obs, model_values, status, loglik, error);
+    if (vrc != SEPAIHRD_OK) return vrc;
+    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state);
+    return SEPAIHRD_OK;
+}
+
+int hostParticleLoglikWide(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                           const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
+                           double* ess, double* final_state, std::string* error) {
+    char msg[256] = "";
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    const int vrc = particle_verdict("particle_loglik_wide",
+                                     sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
+                                     msg, pb, obs, model_values, status, loglik, error);
+    if (vrc != SEPAIHRD_OK) return vrc;
+    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state);
     return SEPAIHRD_OK;
 }
 
@@ -118,7 +151,7 @@ HipParticleLikelihood::HipParticleLikelihood(HipSEPAIHRDParameterManager& parame
                                              std::shared_ptr<IOdeSolverStrategy> solver_strategy, int particles, int steps_per_interval,
                                              std::uint64_t seed0, int device, int initial_state_mode)
     : pm_(parameterManager), data_(observed_data), time_points_(time_points), cache_(1), particles_(particles),
-      steps_per_interval_(steps_per_interval), seed0_(seed0) {
+      steps_per_interval_(steps_per_interval), n_age_((int)(initial_state.size() / epi::NUM_COMP)), seed0_(seed0) {
     objective_ = stoch_twin::make_objective("HipParticleLikelihood", pm_, cache_, data_, time_points_, initial_state, std::move(solver_strategy), device,
                                             initial_state_mode);
 }
@@ -128,9 +161,16 @@ void HipParticleLikelihood::calculateBatch(const double* thetas, int B, double* 
     objective_->syncDeviceConstraintMode();
     std::vector<int32_t> st((size_t)std::max(B, 1), 0);
     const std::uint64_t seed = seed0_ + calls_;
-    const int rc = sepaihrd_particle_loglik(ctx, thetas, B, particles_, steps_per_interval_, seed, out, nullptr, nullptr, nullptr, nullptr, st.data(),
-                                            nullptr);
-    if (rc != SEPAIHRD_OK) throw ModelException("HipParticleLikelihood", std::string("sepaihrd_particle_loglik: ") + sepaihrd_last_error(ctx));
+    // up to the LDS kernel's limit that kernel, beyond it the wide form with the chunking left to the call: the same bits where
+    // both take J, so the choice is one of speed alone
+    const bool wide = particles_ > sepaihrd_particle_max_particles(n_age_);
+    const int rc = wide ? sepaihrd_particle_loglik_wide(ctx, thetas, B, particles_, steps_per_interval_, seed, 0, out, nullptr, nullptr, nullptr, nullptr,
+                                                        st.data(), nullptr)
+                        : sepaihrd_particle_loglik(ctx, thetas, B, particles_, steps_per_interval_, seed, out, nullptr, nullptr, nullptr, nullptr,
+                                                   st.data(), nullptr);
+    if (rc != SEPAIHRD_OK)
+        throw ModelException("HipParticleLikelihood",
+                             std::string(wide ? "sepaihrd_particle_loglik_wide: " : "sepaihrd_particle_loglik: ") + sepaihrd_last_error(ctx));
     ++calls_;
     if (status) std::copy(st.begin(), st.begin() + B, status);
 }

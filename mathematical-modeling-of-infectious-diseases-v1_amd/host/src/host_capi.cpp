@@ -1541,7 +1541,10 @@ int host_stochastic_manager_values(void* hv, int mode, const double* theta, doub
 
 // ---- bootstrap particle filter of the stochastic SEPAIHRD model (HipParticleFilter) ----
 // hostParticleLoglik (no device): shapes as sepaihrd_particle_loglik; obs_* [n_obs][n_age], the rows of the output times >= 0
-int host_particle_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+namespace {
+using ParticleTwin = int (*)(const StochasticSEPAIHRDFixedData&, const ParticleObservations&, const double*, const int32_t*, int, int, int, std::uint64_t,
+                             double*, double*, double*, double*, std::string*);
+int particle_twin_from_values(ParticleTwin twin, int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
                               const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
                               const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
                               uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
@@ -1551,9 +1554,29 @@ int host_particle_from_values(int n_age, int n_times, int n_beta, int n_kappa, c
     ParticleObservations ob;
     ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
     std::string error;
-    const int rc = hostParticleLoglik(fd, ob, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state, &error);
+    const int rc = twin(fd, ob, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state, &error);
     if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
     return rc;
+}
+}  // namespace
+
+int host_particle_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                              const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
+                              const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                              uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
+    return particle_twin_from_values(hostParticleLoglik, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H,
+                                     obs_ICU, obs_D, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state, err,
+                                     errlen);
+}
+
+// hostParticleLoglikWide (no device): the same shapes, J up to 65 536
+int host_particle_wide_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                                   const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
+                                   const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                                   uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
+    return particle_twin_from_values(hostParticleLoglikWide, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs,
+                                     obs_H, obs_ICU, obs_D, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
+                                     err, errlen);
 }
 
 // the twin of sepaihrd_particle_resample_device (no device)

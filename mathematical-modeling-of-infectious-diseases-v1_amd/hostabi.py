@@ -138,6 +138,7 @@ def load_library() -> C.CDLL:
                                     C.c_uint64, vp, C.c_int] + [vp] * 6
     lib.host_particle_from_values.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_uint64] + \
         [vp] * 4 + [C.c_char_p, C.c_int]
+    lib.host_particle_wide_from_values.argtypes = lib.host_particle_from_values.argtypes
     lib.host_particle_resample.restype = None
     lib.host_particle_resample.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.host_particle_likelihood.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int,
@@ -1148,11 +1149,37 @@ def particle_resample(logw, seed: int, b: int = 0, row: int = 0) -> dict:
     return {"ancestors": anc, "increment": inc.value, "ess": ess.value}
 
 
+def particle_wide_max_particles() -> int:
+    """sepaihrd_particle_wide_max_particles (host only): the largest J the wide form of the filter takes, 65 536"""
+    return int(hipabi.load_library().sepaihrd_particle_wide_max_particles())
+
+
+def particle_wide_validate(B: int, J: int, steps_per_interval: int, theta_chunk: int, n_times: int, T_pos: int, n_age: int) -> None:
+    """sepaihrd_particle_wide_validate (host only): ValueError with its message for arguments the wide form refuses"""
+    err = C.create_string_buffer(512)
+    if hipabi.load_library().sepaihrd_particle_wide_validate(int(B), int(J), int(steps_per_interval), int(theta_chunk), int(n_times), int(T_pos),
+                                                             int(n_age), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
 def particle_from_values(model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J: int, steps_per_interval: int, seed: int,
                          beta_end_times=(), want_final: bool = True) -> dict:
     """The twin of HipObjective.particle_loglik after the decoding: from model_values [B][W] and status [B], the problem's fixed data
     (times, N [n], M [n][n] with M[i, j] = M(i, j), the schedule end times) and the observations obs_* [n_obs][n] of the output times
     >= 0 the same loglik [B], increments [B][T_pos], ess [B][T_pos] and final_state [B][J][11][n], bit for bit."""
+    return _particle_from_values(False, model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J, steps_per_interval, seed,
+                                 beta_end_times, want_final)
+
+
+def particle_wide_from_values(model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J: int, steps_per_interval: int,
+                              seed: int, beta_end_times=(), want_final: bool = True) -> dict:
+    """The twin of HipObjective.particle_loglik_wide: particle_from_values' walk behind the wide form's argument rules (J up to 65 536)"""
+    return _particle_from_values(True, model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J, steps_per_interval, seed,
+                                 beta_end_times, want_final)
+
+
+def _particle_from_values(wide, model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J, steps_per_interval, seed, beta_end_times,
+                          want_final) -> dict:
     mv = np.ascontiguousarray(np.atleast_2d(model_values), dtype=np.float64)
     st = np.ascontiguousarray(status, dtype=np.int32).ravel()
     tm = np.ascontiguousarray(times, dtype=np.float64).ravel()
@@ -1168,15 +1195,18 @@ def particle_from_values(model_values, status, times, N, M, kappa_end_times, obs
         raise ValueError("model_values [B][W], status [B], N [n], M [n][n]")
     if not (ob[0].shape == ob[1].shape == ob[2].shape):
         raise ValueError("obs_H, obs_ICU and obs_D must have the same shape [n_obs][n]")
-    particle_validate(B, J, steps_per_interval, T, Tp, n)
+    if wide:
+        particle_wide_validate(B, J, steps_per_interval, 0, T, Tp, n)
+    else:
+        particle_validate(B, J, steps_per_interval, T, Tp, n)
     loglik, inc, ess = np.empty(B), np.empty((B, Tp)), np.empty((B, Tp))
     final = np.empty((B, J, 11, n)) if want_final else None
     err = C.create_string_buffer(512)
-    rc = load_library().host_particle_from_values(n, T, be.size, ke.size, tm.ctypes.data, Nv.ctypes.data, Mm.ctypes.data,
-                                                  be.ctypes.data if be.size else None, ke.ctypes.data, ob[0].shape[0], ob[0].ctypes.data,
-                                                  ob[1].ctypes.data, ob[2].ctypes.data, mv.ctypes.data, st.ctypes.data, B, J,
-                                                  int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, loglik.ctypes.data, inc.ctypes.data,
-                                                  ess.ctypes.data, None if final is None else final.ctypes.data, err, len(err))
+    call = load_library().host_particle_wide_from_values if wide else load_library().host_particle_from_values
+    rc = call(n, T, be.size, ke.size, tm.ctypes.data, Nv.ctypes.data, Mm.ctypes.data, be.ctypes.data if be.size else None, ke.ctypes.data,
+              ob[0].shape[0], ob[0].ctypes.data, ob[1].ctypes.data, ob[2].ctypes.data, mv.ctypes.data, st.ctypes.data, B, J, int(steps_per_interval),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, loglik.ctypes.data, inc.ctypes.data, ess.ctypes.data, None if final is None else final.ctypes.data,
+              err, len(err))
     if rc != 0:
         raise ValueError(err.value.decode())
     out = {"loglik": loglik, "increments": inc, "ess": ess, "n_valid": int(np.sum(st == 0))}
