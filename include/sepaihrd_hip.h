@@ -947,7 +947,8 @@ int sepaihrd_particle_loglik(sepaihrd_ctx *ctx, const double *theta, int B, int 
 int sepaihrd_particle_validate(int B, int J, int steps_per_interval, int n_times, int T_pos, int n_age, char *err, int errlen);
 /* Host only: the largest J the filter kernel takes for n_age classes; SEPAIHRD_E_INVALID_ARG outside 1..16. */
 int sepaihrd_particle_max_particles(int n_age);
-/* Device time of the context's last sepaihrd_particle_loglik call in milliseconds, ms[2]: decode; filter kernel. */
+/* Device time of the context's last sepaihrd_particle_loglik or sepaihrd_particle_loglik_nb call (whichever came last) in
+ * milliseconds, ms[2]: decode; filter kernel. */
 int sepaihrd_particle_timing(const sepaihrd_ctx *ctx, double *ms);
 /* Probe of the device's normalisation, scans and ancestor search: one weighted row with log-weights logw [J] (finite, J in
  * 1..512) at the resampling coordinates of (seed, b, row), through the device functions the filter kernel uses.  ancestors [J],
@@ -981,12 +982,48 @@ int sepaihrd_particle_wide_validate(int B, int J, int steps_per_interval, int th
                                     char *err, int errlen);
 /* Host only: the largest J the wide form takes, 65536 for every n_age. */
 int sepaihrd_particle_wide_max_particles(void);
-/* Device time of the context's last sepaihrd_particle_loglik_wide call in milliseconds, ms[2]: decode; all filter launches. */
+/* Device time of the context's last sepaihrd_particle_loglik_wide or sepaihrd_particle_loglik_wide_nb call (whichever came last) in
+ * milliseconds, ms[2]: decode; all filter launches. */
 int sepaihrd_particle_wide_timing(const sepaihrd_ctx *ctx, double *ms);
 /* Probe of the wide form's normalise-and-resample kernel: one weighted row with log-weights logw [J] (finite, J in 1..65536) at
  * the resampling coordinates of (seed, b, row).  ancestors [J], increment and ess: host memory. */
 int sepaihrd_particle_wide_resample_device(int device, uint64_t seed, uint32_t b, uint32_t row, const double *logw, int J,
                                            int32_t *ancestors, double *increment, double *ess, char *err, int errlen);
+
+/* ---- a negative-binomial observation model for both filters (additive; SEPAIHRD_ABI_VERSION stays) ---------------------------
+ * The two calls above weigh a particle as if the observed counts were Poisson around the simulated increments.  These two give
+ * each observed series a dispersion k: dispersion[3] = {k_H, k_ICU, k_D}, every entry +inf or finite in [1e-3, 1e6].  +inf keeps
+ * the Poisson term of that series, untouched.  A finite k makes the series negative binomial with mean sim and size k (variance
+ * sim + sim^2 / k; csrc/sepaihrd_particle.inc states the rule, one text for both kernels and the host twin):
+ *   - the term of a usable cell is  obs log(sim) - (obs + k) log(1 + sim / k),  sim = max(0, inc) + 1e-10 as before, 0 where the
+ *     cell is not usable; the sum over a class keeps its association (term_H + term_ICU) + term_D;
+ *   - what is left of the log-pmf, g(obs, k) = lgamma(obs + k) - lgamma(k) - obs log(k), is shared by every particle of a row and
+ *     never enters the weights: its sum G over the row's usable cells with a finite k (ascending age; H, ICU, D within an age;
+ *     from 0.0; glibc's lgamma and log on the host) is added to the row's increment, increment = (M + log(C[J-1] / J)) + G;
+ *   - the -lgamma(obs + 1) of the pmf is left out, as the Poisson term leaves it out.  With that convention term + g tends to the
+ *     Poisson term as k grows: the difference is ((sim - obs)^2 - obs) / (2 k) + O(k^-2).  Above 1e6 the cancellation in these
+ *     formulas costs more than 1e-8, hence the upper bound.
+ * M, w, the scans, the ESS, the resampling uniform, the ancestors, skipped rows, invalid theta, the limits on J and every other
+ * argument rule are those of the Poisson calls.  With all three entries +inf no table is formed and the Poisson kernels run: the
+ * outputs are the bits of sepaihrd_particle_loglik and sepaihrd_particle_loglik_wide.  The host twins are hostParticleLoglikNB and
+ * hostParticleLoglikWideNB (host/), bit for bit.
+ * SEPAIHRD_E_INVALID_ARG, before the device is touched and with the outputs untouched: what the Poisson call refuses, and a
+ * dispersion sepaihrd_particle_nb_validate refuses. */
+int sepaihrd_particle_loglik_nb(sepaihrd_ctx *ctx, const double *theta, int B, int J, int steps_per_interval, uint64_t seed,
+                                const double dispersion[3], double *loglik, double *increments, double *ess, double *final_state,
+                                double *model_values, int32_t *status, int32_t *n_valid);
+int sepaihrd_particle_loglik_wide_nb(sepaihrd_ctx *ctx, const double *theta, int B, int J, int steps_per_interval, uint64_t seed,
+                                     const double dispersion[3], int theta_chunk, double *loglik, double *increments, double *ess,
+                                     double *final_state, double *model_values, int32_t *status, int32_t *n_valid);
+/* Host only: SEPAIHRD_E_INVALID_ARG with a message in err (NULL: not wanted) that names the entry for a NULL pointer, a NaN, -inf,
+ * a value <= 0, a finite value below 1e-3 or a finite value above 1e6. */
+int sepaihrd_particle_nb_validate(const double dispersion[3], char *err, int errlen);
+/* Host only: G [T_pos], the row constants a call with this dispersion uploads (all 0 where every entry is +inf). */
+int sepaihrd_particle_nb_row_constants(const sepaihrd_ctx *ctx, const double dispersion[3], double *G);
+/* Probe of the device's negative-binomial term: out[i] = the term of obs[i] (double) and inc[i] (int32) under a finite k in
+ * [1e-3, 1e6], count cells; host memory. */
+int sepaihrd_particle_nb_term_device(int device, const double *obs, const int32_t *inc, int count, double k, double *out,
+                                     char *err, int errlen);
 
 #ifdef __cplusplus
 }

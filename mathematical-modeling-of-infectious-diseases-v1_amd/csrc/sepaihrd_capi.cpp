@@ -23,6 +23,7 @@
 #include "sepaihrd_predictive_device.h"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_particle_device.h"
+#include "sepaihrd_particle_nb_host.h"
 #include "sepaihrd_particle_wide_device.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
@@ -1109,10 +1110,45 @@ int sepaihrd_stochastic_timing(const sepaihrd_ctx* ctx, double* ms) {
     return SEPAIHRD_OK;
 }
 
-int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, double* loglik,
-                             double* increments, double* ess, double* final_state, double* model_values, int32_t* status, int32_t* n_valid) {
+}  // extern "C"
+
+namespace {
+
+// The dispersion of a sepaihrd_particle_loglik_nb / _wide_nb call after sepaihrd_particle_nb_validate: whether some series is
+// dispersed, and then the row constants G [T_pos] from the context's copy of the observation grid.
+struct NbPlan {
+    bool some = false;
+    sepaihrd_particle::Dispersion d{};
+    std::vector<double> G;
+};
+void nb_row_constants_of(const sepaihrd_ctx* ctx, const sepaihrd_particle::Dispersion& d, double* G) {
+    const DevProblem& dp = ctx->dp;
+    const double* grid = ctx->host_grid.data();  // [T][lpc][4]: {obs_H, obs_ICU, obs_D, times[k + 1]}
+    sepaihrd_particle::nb_row_constants(d, dp.n, dp.T - dp.runup_offset,
+                                        [&](int series, int t, int age) { return grid[((size_t)(dp.runup_offset + t) * dp.lpc + age) * 4 + series]; }, G);
+}
+// SEPAIHRD_OK, or the validator's refusal as the context's last error
+int nb_plan(sepaihrd_ctx* ctx, const double* dispersion, NbPlan& plan) {
+    char msg[256] = "";
+    if (sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+        ctx->last_error = msg;
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    plan.d = sepaihrd_particle::Dispersion{dispersion[0], dispersion[1], dispersion[2]};
+    plan.some = sepaihrd_particle::any_dispersed(plan.d);
+    if (plan.some) {
+        plan.G.resize((size_t)(ctx->dp.T - ctx->dp.runup_offset));
+        nb_row_constants_of(ctx, plan.d, plan.G.data());
+    }
+    return SEPAIHRD_OK;
+}
+
+// sepaihrd_particle_loglik (dispersion NULL) and sepaihrd_particle_loglik_nb: one body.  With no dispersed series no table is
+// formed and the Poisson kernel runs, launch for launch.
+int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, const double* dispersion, const double* theta, int B, int J, int steps_per_interval,
+                         uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, double* model_values, int32_t* status,
+                         int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    const char* const who = "particle_loglik";
     if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
     int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
     if (rc != SEPAIHRD_OK) return rc;
@@ -1126,6 +1162,11 @@ int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int 
             return SEPAIHRD_E_INVALID_ARG;
         }
     }
+    NbPlan nb;
+    if (dispersion != nullptr) {
+        rc = nb_plan(ctx, dispersion, nb);
+        if (rc != SEPAIHRD_OK) return rc;
+    }
     if (ctx->precision != SEPAIHRD_PRECISION_F64)
         return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
@@ -1133,20 +1174,22 @@ int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int 
     const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
     const size_t n_values = (size_t)B * W, n_rows = (size_t)B * Tp;
     const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
-    const size_t need_bytes = sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final) + sizeof(int32_t) * ((size_t)B + 2);
+    const size_t need_bytes =
+        sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size()) + sizeof(int32_t) * ((size_t)B + 2);
     rc = require_device_memory(ctx, need_bytes, "particle_loglik: the model values of B = " + std::to_string(B) + " parameter vectors and the outputs asked for need",
                                "split the parameter vectors over several calls");
     if (rc != SEPAIHRD_OK) return rc;
     // buffers and events of this call alone
     CallScratch sc(3);
-    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr;
+    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_G = nullptr;
     int32_t *d_counts = nullptr, *d_status = nullptr;
     if (!sc.alloc(&d_theta, (size_t)B * ctx->P) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_ll, (size_t)B) ||
         !sc.alloc(&d_inc, increments ? n_rows : 0) || !sc.alloc(&d_ess, ess ? n_rows : 0) || !sc.alloc(&d_final, n_final) ||
-        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B))
+        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) || !sc.alloc(&d_G, nb.G.size()))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    if (nb.some) HIP_TRY(hipMemcpy(d_G, nb.G.data(), nb.G.size() * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     // launches
     StochEpiArgs da{};
     da.S = B; da.R = J; da.W = W;
@@ -1154,12 +1197,15 @@ int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int 
     (void)hipEventRecord(sc.ev[0], nullptr);
     if (launch_stoch_epi_decode(dp, da, nullptr) != 0) return refuse(ctx, who, "decode kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[1], nullptr);
-    ParticleArgs a{};
+    ParticleArgsNB a{};
     a.B = B; a.J = J; a.m = steps_per_interval; a.W = W;
     a.seed = seed;
     a.values = d_values; a.status = d_status; a.loglik = d_ll;
     a.increments = increments ? d_inc : nullptr; a.ess = ess ? d_ess : nullptr; a.final_state = final_state ? d_final : nullptr;
-    if (launch_particle_filter(dp, a, nullptr) != 0) return refuse(ctx, who, "filter kernel launch failed", SEPAIHRD_E_HIP);
+    a.k_H = nb.d.k_H; a.k_ICU = nb.d.k_ICU; a.k_D = nb.d.k_D;
+    a.row_const = d_G;
+    if ((nb.some ? launch_particle_filter_nb(dp, a, nullptr) : launch_particle_filter(dp, a, nullptr)) != 0)
+        return refuse(ctx, who, "filter kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
     for (int i = 0; i < 2; ++i) {
@@ -1180,17 +1226,46 @@ int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int 
     return SEPAIHRD_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, double* loglik,
+                             double* increments, double* ess, double* final_state, double* model_values, int32_t* status, int32_t* n_valid) {
+    return particle_loglik_call(ctx, "particle_loglik", nullptr, theta, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
+                                model_values, status, n_valid);
+}
+
+int sepaihrd_particle_loglik_nb(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed,
+                                const double dispersion[3], double* loglik, double* increments, double* ess, double* final_state,
+                                double* model_values, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (!dispersion) return refuse(ctx, "particle_loglik_nb", "need dispersion (three entries: k_H, k_ICU, k_D)", SEPAIHRD_E_INVALID_ARG);
+    return particle_loglik_call(ctx, "particle_loglik_nb", dispersion, theta, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
+                                model_values, status, n_valid);
+}
+
+int sepaihrd_particle_nb_row_constants(const sepaihrd_ctx* ctx, const double dispersion[3], double* G) {
+    if (!ctx || !G || sepaihrd_particle_nb_validate(dispersion, nullptr, 0) != SEPAIHRD_OK || ctx->host_grid.empty()) return SEPAIHRD_E_INVALID_ARG;
+    nb_row_constants_of(ctx, sepaihrd_particle::Dispersion{dispersion[0], dispersion[1], dispersion[2]}, G);
+    return SEPAIHRD_OK;
+}
+
 int sepaihrd_particle_timing(const sepaihrd_ctx* ctx, double* ms) {
     if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
     for (int i = 0; i < 2; ++i) ms[i] = ctx->particle_ms[i];
     return SEPAIHRD_OK;
 }
 
-int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, int theta_chunk,
-                                  double* loglik, double* increments, double* ess, double* final_state, double* model_values, int32_t* status,
-                                  int32_t* n_valid) {
+}  // extern "C"
+
+namespace {
+
+// sepaihrd_particle_loglik_wide (dispersion NULL) and sepaihrd_particle_loglik_wide_nb: one body, as particle_loglik_call
+int particle_loglik_wide_call(sepaihrd_ctx* ctx, const char* who, const double* dispersion, const double* theta, int B, int J, int steps_per_interval,
+                              uint64_t seed, int theta_chunk, double* loglik, double* increments, double* ess, double* final_state,
+                              double* model_values, int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    const char* const who = "particle_loglik_wide";
     if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
     int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
     if (rc != SEPAIHRD_OK) return rc;
@@ -1204,6 +1279,11 @@ int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B,
             return SEPAIHRD_E_INVALID_ARG;
         }
     }
+    NbPlan nb;
+    if (dispersion != nullptr) {
+        rc = nb_plan(ctx, dispersion, nb);
+        if (rc != SEPAIHRD_OK) return rc;
+    }
     if (ctx->precision != SEPAIHRD_PRECISION_F64)
         return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
@@ -1213,7 +1293,7 @@ int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B,
     const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
     const size_t chunk = particle_wide_chunk(dp.lpc, J, B, theta_chunk);
     const size_t scratch_bytes = particle_wide_scratch_bytes(dp.lpc, J, chunk);
-    const size_t need_bytes = scratch_bytes + sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final) +
+    const size_t need_bytes = scratch_bytes + sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size()) +
                               sizeof(int32_t) * ((size_t)B + 2);
     rc = require_device_memory(ctx, need_bytes,
                                "particle_loglik_wide: the particles of " + std::to_string(chunk) + " parameter vectors at a time, the model values of B = " +
@@ -1222,14 +1302,17 @@ int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B,
     if (rc != SEPAIHRD_OK) return rc;
     // buffers and events of this call alone
     CallScratch sc(3);
-    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_scratch = nullptr;
+    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_scratch = nullptr,
+           *d_G = nullptr;
     int32_t *d_counts = nullptr, *d_status = nullptr;
     if (!sc.alloc(&d_theta, (size_t)B * ctx->P) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_ll, (size_t)B) ||
         !sc.alloc(&d_inc, increments ? n_rows : 0) || !sc.alloc(&d_ess, ess ? n_rows : 0) || !sc.alloc(&d_final, n_final) ||
-        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) || !sc.alloc(&d_scratch, (scratch_bytes + sizeof(double) - 1) / sizeof(double)))
+        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) || !sc.alloc(&d_scratch, (scratch_bytes + sizeof(double) - 1) / sizeof(double)) ||
+        !sc.alloc(&d_G, nb.G.size()))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    if (nb.some) HIP_TRY(hipMemcpy(d_G, nb.G.data(), nb.G.size() * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     // launches
     StochEpiArgs da{};
     da.S = B; da.R = J; da.W = W;
@@ -1245,6 +1328,10 @@ int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B,
     a.increments = increments ? d_inc : nullptr; a.ess = ess ? d_ess : nullptr; a.final_state = final_state ? d_final : nullptr;
     a.scratch = d_scratch;
     a.host_grid = ctx->host_grid.data();
+    if (nb.some) {
+        a.row_const = d_G;
+        a.k_H = nb.d.k_H; a.k_ICU = nb.d.k_ICU; a.k_D = nb.d.k_D;
+    }
     const int lrc = launch_particle_filter_wide(dp, a, nullptr);
     (void)hipEventRecord(sc.ev[2], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
@@ -1265,6 +1352,26 @@ int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B,
     res.fetch(n_valid, d_counts, sizeof(int32_t));
     if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, int theta_chunk,
+                                  double* loglik, double* increments, double* ess, double* final_state, double* model_values, int32_t* status,
+                                  int32_t* n_valid) {
+    return particle_loglik_wide_call(ctx, "particle_loglik_wide", nullptr, theta, B, J, steps_per_interval, seed, theta_chunk, loglik, increments, ess,
+                                     final_state, model_values, status, n_valid);
+}
+
+int sepaihrd_particle_loglik_wide_nb(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed,
+                                     const double dispersion[3], int theta_chunk, double* loglik, double* increments, double* ess,
+                                     double* final_state, double* model_values, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (!dispersion) return refuse(ctx, "particle_loglik_wide_nb", "need dispersion (three entries: k_H, k_ICU, k_D)", SEPAIHRD_E_INVALID_ARG);
+    return particle_loglik_wide_call(ctx, "particle_loglik_wide_nb", dispersion, theta, B, J, steps_per_interval, seed, theta_chunk, loglik,
+                                     increments, ess, final_state, model_values, status, n_valid);
 }
 
 int sepaihrd_particle_wide_timing(const sepaihrd_ctx* ctx, double* ms) {

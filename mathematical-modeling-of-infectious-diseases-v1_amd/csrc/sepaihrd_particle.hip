@@ -9,13 +9,16 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_host_util.h"
 #include "sepaihrd_particle.inc"
 #include "sepaihrd_particle_device.h"
+#include "sepaihrd_particle_nb_host.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
 namespace sepaihrd {
@@ -94,7 +97,12 @@ __device__ void block_normalise_and_resample(const BlockLds& l, int J, double u,
 // Barriers: one at the top of every row (it also carries the block-uniform "this row has a usable observation"), so that no
 // lane writes a copy others still read; then those of the weighting.  Lanes of padded ages and of the slots beyond J in the
 // last pass carry zero counts and draw nothing; they reach every barrier.  An invalid theta ends its whole block at once.
-__global__ __launch_bounds__(PARTICLE_BLOCK) void particle_filter_kernel(const DevProblem pb, const ParticleArgs a) {
+//
+// NB = "some series is dispersed" (DESIGN.md section 6m).  The false instantiation is the Poisson kernel, argument for argument;
+// the true one takes the three k and the row constants in its argument struct, weighs each series by a kernel-uniform test on
+// its k (pf::series_term) and has lane 0 add the row's constant where the increment is formed.  No per-particle state is added.
+template <bool NB>
+__global__ __launch_bounds__(PARTICLE_BLOCK) void particle_filter_kernel(const DevProblem pb, const std::conditional_t<NB, ParticleArgsNB, ParticleArgs> a) {
     extern __shared__ double particle_lds[];
     const int n = pb.n, lpc = pb.lpc, T = pb.T, Tp = pb.T - pb.runup_offset, J = a.J;
     const uint32_t b = blockIdx.x;
@@ -179,7 +187,12 @@ __global__ __launch_bounds__(PARTICLE_BLOCK) void particle_filter_kernel(const D
                 *slot(cur ^ 1, p, epi::NUM_COMP + 2) = x[epi::C_D];
             }
             if (weighted) {
-                const double term = pf::age_term(oH, oICU, oD, x[epi::C_CUM_H] - prevH, x[epi::C_CUM_ICU] - prevICU, x[epi::C_D] - prevD);
+                double term;
+                if constexpr (NB)
+                    term = pf::age_term(oH, oICU, oD, x[epi::C_CUM_H] - prevH, x[epi::C_CUM_ICU] - prevICU, x[epi::C_D] - prevD,
+                                        pf::Dispersion{a.k_H, a.k_ICU, a.k_D});
+                else
+                    term = pf::age_term(oH, oICU, oD, x[epi::C_CUM_H] - prevH, x[epi::C_CUM_ICU] - prevICU, x[epi::C_D] - prevD);
                 double lw = 0.0;
                 for (int aa = 0; aa < n; ++aa) lw += __shfl(term, aa, lpc);
                 if (in_range && age == 0) l.lw[p] = lw;
@@ -193,6 +206,7 @@ __global__ __launch_bounds__(PARTICLE_BLOCK) void particle_filter_kernel(const D
             block_normalise_and_resample(l, J, pf::resample_uniform(a.seed, b, (uint32_t)k), inc, ess);
             resampled = true;
             if (tid == 0) {
+                if constexpr (NB) inc = pf::increment_with_constant(inc, a.row_const[t]);
                 loglik += inc;
                 if (a.increments != nullptr) a.increments[(size_t)b * Tp + t] = inc;
                 if (a.ess != nullptr) a.ess[(size_t)b * Tp + t] = ess;
@@ -229,9 +243,13 @@ __global__ __launch_bounds__(PARTICLE_BLOCK) void particle_resample_probe_kernel
     if (j == 0) { out2[0] = inc; out2[1] = ess; }
 }
 
-}  // namespace
+// cells of the probe of pf::nb_term: one lane per cell, grid-stride
+__global__ __launch_bounds__(256) void particle_nb_term_probe_kernel(const double* obs, const int32_t* inc, int count, double k, double* out) {
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < count; i += (int)(gridDim.x * blockDim.x)) out[i] = pf::nb_term(obs[i], inc[i], k);
+}
 
-int launch_particle_filter(const DevProblem& pb, const ParticleArgs& a, void* stream) {
+template <bool NB, class Args>
+int launch_filter(const DevProblem& pb, const Args& a, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int Tp = pb.T - pb.runup_offset;
     if (a.B <= 0 || a.m < 1 || pb.n < 1 || pb.n > epi::MAX_AGES || pb.lpc < pb.n || pb.lpc > epi::MAX_AGES || (pb.lpc & (pb.lpc - 1)) != 0 ||
@@ -240,8 +258,17 @@ int launch_particle_filter(const DevProblem& pb, const ParticleArgs& a, void* st
         return -4;
     const size_t lds = particle_lds_bytes(pb.lpc, a.J);
     if (lds > PARTICLE_LDS_LIMIT) return -4;
-    hipLaunchKernelGGL(particle_filter_kernel, dim3((unsigned)a.B), dim3(PARTICLE_BLOCK), lds, st, pb, a);
+    hipLaunchKernelGGL(particle_filter_kernel<NB>, dim3((unsigned)a.B), dim3(PARTICLE_BLOCK), lds, st, pb, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace
+
+int launch_particle_filter(const DevProblem& pb, const ParticleArgs& a, void* stream) { return launch_filter<false>(pb, a, stream); }
+
+int launch_particle_filter_nb(const DevProblem& pb, const ParticleArgsNB& a, void* stream) {
+    if (!a.row_const || !pf::any_dispersed(pf::Dispersion{a.k_H, a.k_ICU, a.k_D})) return -4;
+    return launch_filter<true>(pb, a, stream);
 }
 
 }  // namespace sepaihrd
@@ -293,5 +320,41 @@ extern "C" int sepaihrd_particle_resample_device(int device, uint64_t seed, uint
     }
     *increment = out2[0];
     *ess = out2[1];
+    return SEPAIHRD_OK;
+}
+
+extern "C" int sepaihrd_particle_nb_validate(const double* dispersion, char* err, int errlen) {
+    const std::string refusal = pf::nb_refusal(dispersion);
+    if (refusal.empty()) return SEPAIHRD_OK;
+    set_err(err, errlen, "particle_nb: " + refusal);
+    return SEPAIHRD_E_INVALID_ARG;
+}
+
+extern "C" int sepaihrd_particle_nb_term_device(int device, const double* obs, const int32_t* inc, int count, double k, double* out, char* err,
+                                                int errlen) {
+    if (!obs || !inc || !out || count < 1 || !(k >= pf::NB_K_MIN && k <= pf::NB_K_MAX)) {
+        set_err(err, errlen, "particle_nb_term_device: need obs, inc, out, count >= 1 and a finite k in [1e-3, 1e6]");
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    if (const int drc = select_device(device, err, errlen)) return drc;
+    CallScratch sc;
+    double *d_obs = nullptr, *d_out = nullptr;
+    int32_t* d_inc = nullptr;
+    if (!sc.alloc(&d_obs, (size_t)count) || !sc.alloc(&d_out, (size_t)count) || !sc.alloc(&d_inc, (size_t)count)) {
+        set_err(err, errlen, std::string("particle_nb_term_device: ") + hipGetErrorString(hipErrorOutOfMemory));
+        return SEPAIHRD_E_HIP;
+    }
+    bool ok = hipMemcpy(d_obs, obs, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_inc, inc, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        const unsigned blocks = (unsigned)std::min<size_t>(((size_t)count + 255) / 256, 1024);
+        hipLaunchKernelGGL(particle_nb_term_probe_kernel, dim3(blocks), dim3(256), 0, nullptr, d_obs, d_inc, count, k, d_out);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) {
+        set_err(err, errlen, std::string("particle_nb_term_device: ") + hipGetErrorString(hipGetLastError()));
+        return SEPAIHRD_E_HIP;
+    }
     return SEPAIHRD_OK;
 }

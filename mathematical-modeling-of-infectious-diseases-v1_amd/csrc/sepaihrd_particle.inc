@@ -13,6 +13,8 @@
 // observation is usable (finite and >= 0, the likelihood's rule) and 0 elsewhere;
 //     t_a = (term_H + term_ICU) + term_D,     lw_j = sum_a t_a from 0.0 in ascending a.
 // A row without a usable (series, age) cell is skipped: no weighting, no resampling, increment 0, ESS NaN.
+// With a dispersion (DESIGN.md section 6m; stated below, above nb_term) a series' term is negative binomial instead and the row's
+// increment gains a constant; with none every line here holds as it stands.
 //
 // Normalisation.  M = max_j lw_j, w_j = exp_nonpositive(lw_j - M); C = the inclusive prefix sums of w in the Kogge-Stone order,
 // which is a function of J alone: for d = 1, 2, 4, ... < J, c[j] += c[j - d] for all j >= d at once (on the host the same loop
@@ -54,6 +56,35 @@ SEP_RNG_FN double poisson_term(double obs, int32_t inc) {
 SEP_RNG_FN double age_term(double obs_H, double obs_ICU, double obs_D, int32_t inc_H, int32_t inc_ICU, int32_t inc_D) {
     return (poisson_term(obs_H, inc_H) + poisson_term(obs_ICU, inc_ICU)) + poisson_term(obs_D, inc_D);
 }
+
+// ---- the negative-binomial observation model (DESIGN.md section 6m): one dispersion k per observed series, +inf or finite in
+// [NB_K_MIN, NB_K_MAX].  +inf keeps that series' poisson_term.  For a finite k the series is negative binomial with mean sim and
+// size k (variance sim + sim^2 / k); the part of its log-pmf that depends on the particle is
+//     nb_term = obs glibc_log(sim) - (obs + k) glibc_log(1.0 + sim / k).
+// The rest, g(obs, k) = lgamma(obs + k) - lgamma(k) - obs log(k), is the same for every particle of a row: it never enters the
+// weights and is added to the row's increment as the row constant G (csrc/sepaihrd_particle_nb_host.h forms it on the host).
+// The -lgamma(obs + 1) of the pmf is left out, as poisson_term leaves it out; with that convention nb_term + g tends to
+// poisson_term as k grows, the difference being ((sim - obs)^2 - obs) / (2 k) + O(k^-2).  Above NB_K_MAX the cancellation in
+// these formulas costs more than 1e-8.
+constexpr double NB_K_MIN = 1e-3, NB_K_MAX = 1e6;
+struct Dispersion {
+    double k_H, k_ICU, k_D;
+};
+// a validated k is +inf or finite: a finite one selects nb_term
+SEP_RNG_FN bool dispersed(double k) { return k <= 1.7976931348623157e308; }
+SEP_RNG_FN bool any_dispersed(const Dispersion& d) { return dispersed(d.k_H) || dispersed(d.k_ICU) || dispersed(d.k_D); }
+
+SEP_RNG_FN double nb_term(double obs, int32_t inc, double k) {
+    const double sim = (double)(inc > 0 ? inc : 0) + SIM_FLOOR;
+    return usable(obs) ? obs * glibc_log(sim) - (obs + k) * glibc_log(1.0 + sim / k) : 0.0;
+}
+SEP_RNG_FN double series_term(double obs, int32_t inc, double k) { return dispersed(k) ? nb_term(obs, inc, k) : poisson_term(obs, inc); }
+// t_a of one age class under the dispersion d: age_term's association, each series by its own k
+SEP_RNG_FN double age_term(double obs_H, double obs_ICU, double obs_D, int32_t inc_H, int32_t inc_ICU, int32_t inc_D, const Dispersion& d) {
+    return (series_term(obs_H, inc_H, d.k_H) + series_term(obs_ICU, inc_ICU, d.k_ICU)) + series_term(obs_D, inc_D, d.k_D);
+}
+// the increment of a weighted row whose constant is G
+SEP_RNG_FN double increment_with_constant(double inc, double G) { return inc + G; }
 
 SEP_RNG_FN double weight(double lw, double M) { return exp_nonpositive(lw - M); }
 SEP_RNG_FN double increment(double M, double total, int J) { return M + glibc_log(total / (double)J); }

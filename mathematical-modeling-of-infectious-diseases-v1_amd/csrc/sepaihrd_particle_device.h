@@ -41,4 +41,12 @@ struct ParticleArgs {
 // one workgroup per theta: propagate, weight, scan and resample without leaving the device between output rows
 int launch_particle_filter(const DevProblem& pb, const ParticleArgs& a, void* stream);
 
+// The negative-binomial observation model: the arguments above and, for the kernel's dispersed
+// instantiation alone, the three k (+inf: that series stays Poisson; at least one finite) and the row constants.
+struct ParticleArgsNB : ParticleArgs {
+    double k_H, k_ICU, k_D;
+    const double* row_const;  // [Tp] device: G of every output time >= 0, added by lane 0 to the row's increment
+};
+int launch_particle_filter_nb(const DevProblem& pb, const ParticleArgsNB& a, void* stream);
+
 }  // namespace sepaihrd

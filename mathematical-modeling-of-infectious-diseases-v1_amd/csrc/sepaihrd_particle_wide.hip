@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sepaihrd_device.h"
@@ -93,6 +94,11 @@ struct WideSegment {
     double* lw;
 };
 
+// the dispersed instantiation's arguments: the segment and the three k, +inf where a series stays Poisson
+struct WideSegmentNB : WideSegment {
+    double k_H, k_ICU, k_D;
+};
+
 __device__ size_t state_index(int Bc, int J, int lpc, int copy, int bl, int c, int p, int age) {
     return ((((size_t)copy * Bc + bl) * epi::NUM_COMP + c) * (size_t)J + p) * lpc + age;
 }
@@ -103,7 +109,11 @@ __device__ size_t state_index(int Bc, int J, int lpc, int copy, int bl, int c, i
 // are the counts at the start of the segment's last interval (every row, weighted or not, takes the increments: the host twin's
 // walk) and are never stored.  Lanes of padded ages, of invalid thetas and of the slots past the chunk's last carry zeros, take
 // part in the exchanges, draw nothing (binomial(0, .) returns at once) and store nothing.
-__global__ __launch_bounds__(WIDE_STEP_BLOCK) void wide_propagate_kernel(const DevProblem pb, const WideSegment s) {
+//
+// NB = "some series is dispersed": the false instantiation is the Poisson kernel, argument for argument; the true one takes the
+// three k in its argument struct and weighs each series by a kernel-uniform test on its k (pf::series_term).
+template <bool NB>
+__global__ __launch_bounds__(WIDE_STEP_BLOCK) void wide_propagate_kernel(const DevProblem pb, const std::conditional_t<NB, WideSegmentNB, WideSegment> s) {
     const int n = pb.n, lpc = pb.lpc, J = s.J;
     const size_t gl = (size_t)blockIdx.x * WIDE_STEP_BLOCK + threadIdx.x;
     const size_t idx = gl / (size_t)lpc;
@@ -148,7 +158,12 @@ __global__ __launch_bounds__(WIDE_STEP_BLOCK) void wide_propagate_kernel(const D
             const double* rec = pb.grid + ((size_t)s.k_last * lpc + age) * 4;  // {obs_H, obs_ICU, obs_D, times[k + 1]}
             oH = rec[0]; oICU = rec[1]; oD = rec[2];
         }
-        const double term = pf::age_term(oH, oICU, oD, x[epi::C_CUM_H] - prevH, x[epi::C_CUM_ICU] - prevICU, x[epi::C_D] - prevD);
+        double term;
+        if constexpr (NB)
+            term = pf::age_term(oH, oICU, oD, x[epi::C_CUM_H] - prevH, x[epi::C_CUM_ICU] - prevICU, x[epi::C_D] - prevD,
+                                pf::Dispersion{s.k_H, s.k_ICU, s.k_D});
+        else
+            term = pf::age_term(oH, oICU, oD, x[epi::C_CUM_H] - prevH, x[epi::C_CUM_ICU] - prevICU, x[epi::C_D] - prevD);
         double lw = 0.0;
         for (int aa = 0; aa < n; ++aa) lw += __shfl(term, aa, lpc);
         if (ok && age == 0) s.lw[(size_t)bl * J + p] = lw;
@@ -167,6 +182,7 @@ struct WideRow {
     double* loglik;          // [Bc]: the running sum, in time order
     double* increments;      // [Bc][Tp] or null
     double* ess;             // [Bc][Tp] or null
+    const double* row_const; // [Tp], the same for every theta: the row constants G of a dispersed call; null on the Poisson path
 };
 
 // One workgroup per theta of the chunk; lane i owns the elements i, i + 1024, ... of the row.  The maximum; w and w^2; the two
@@ -222,7 +238,8 @@ __global__ __launch_bounds__(WIDE_SCAN_BLOCK) void wide_resample_kernel(const Wi
         sw = q_old; q_old = q_new; q_new = sw;
     }
     if (tid == 0) {
-        const double inc = pf::increment(M, c_old[J - 1], J);
+        double inc = pf::increment(M, c_old[J - 1], J);
+        if (r.row_const != nullptr) inc = pf::increment_with_constant(inc, r.row_const[r.t]);
         r.loglik[bl] += inc;
         if (r.increments != nullptr) r.increments[(size_t)bl * r.Tp + r.t] = inc;
         if (r.ess != nullptr) r.ess[(size_t)bl * r.Tp + r.t] = pf::effective_sample_size(c_old[J - 1], q_old[J - 1]);
@@ -275,13 +292,16 @@ int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a,
             if (pf::usable(rec[0]) || pf::usable(rec[1]) || pf::usable(rec[2])) weighted[(size_t)k] = 1;
         }
     const size_t final_doubles = (size_t)J * epi::NUM_COMP * pb.n;
+    const bool nb = a.row_const != nullptr;
+    if (nb && !pf::any_dispersed(pf::Dispersion{a.k_H, a.k_ICU, a.k_D})) return -4;
     WideFill f{J, Tp, pb.n, a.status, a.loglik, a.increments, a.ess, a.final_state};
     hipLaunchKernelGGL(wide_fill_kernel, dim3((unsigned)a.B, WIDE_FILL_SLICES), dim3(WIDE_FILL_BLOCK), 0, st, f);
     for (size_t b0 = 0; b0 < (size_t)a.B; b0 += a.chunk) {
         const int Bc = (int)std::min(a.chunk, (size_t)a.B - b0);
         const ChunkScratch sc = carve(a.scratch, (size_t)Bc, J);
         const size_t slots = (size_t)Bc * (size_t)J;
-        WideSegment s{};
+        WideSegmentNB s{};
+        s.k_H = a.k_H; s.k_ICU = a.k_ICU; s.k_D = a.k_D;
         s.Bc = Bc; s.J = J; s.m = a.m; s.W = a.W;
         s.seed = a.seed;
         s.b0 = (uint32_t)b0;
@@ -297,13 +317,18 @@ int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a,
         r.loglik = a.loglik + b0;
         r.increments = a.increments ? a.increments + b0 * (size_t)Tp : nullptr;
         r.ess = a.ess ? a.ess + b0 * (size_t)Tp : nullptr;
+        r.row_const = a.row_const;
         int cur = 0, gather = 0;
         for (int k = 0; k < T;) {
             int k_last = k;
             while (!weighted[(size_t)k_last] && k_last + 1 < T) ++k_last;
             s.k_first = k; s.k_last = k_last;
             s.cur = cur; s.gather = gather; s.weighted = weighted[(size_t)k_last];
-            hipLaunchKernelGGL(wide_propagate_kernel, dim3(lane_blocks(slots, lpc)), dim3(WIDE_STEP_BLOCK), 0, st, pb, s);
+            if (nb)
+                hipLaunchKernelGGL(wide_propagate_kernel<true>, dim3(lane_blocks(slots, lpc)), dim3(WIDE_STEP_BLOCK), 0, st, pb, s);
+            else
+                hipLaunchKernelGGL(wide_propagate_kernel<false>, dim3(lane_blocks(slots, lpc)), dim3(WIDE_STEP_BLOCK), 0, st, pb,
+                                   static_cast<const WideSegment&>(s));
             cur ^= 1;
             gather = 0;
             if (s.weighted) {

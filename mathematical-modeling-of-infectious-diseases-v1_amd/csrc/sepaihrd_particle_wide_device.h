@@ -42,6 +42,9 @@ struct ParticleWideArgs {
     double* final_state;      // [B][J][11][n] device or null
     void* scratch;            // device, particle_wide_scratch_bytes(lpc, J, chunk) bytes, 8-byte aligned
     const double* host_grid;  // [T][lpc][4] HOST copy of DevProblem::grid: which rows are weighted is planned from it
+    // the negative-binomial observation model.  row_const null: the Poisson path, the k are not read
+    const double* row_const = nullptr;  // [Tp] device: G of every output time >= 0
+    double k_H = 0.0, k_ICU = 0.0, k_D = 0.0;  // +inf: that series stays Poisson; at least one finite
 };
 // The whole filter as plain launches on the stream, chunk after chunk: a fill of the outputs, then per segment one
 // propagate-and-weight launch and, where the segment ends in a weighted row, one normalise-and-resample launch; the final state

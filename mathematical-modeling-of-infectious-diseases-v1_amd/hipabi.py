@@ -222,6 +222,8 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_particle_resample_device",
     "sepaihrd_particle_loglik_wide", "sepaihrd_particle_wide_validate", "sepaihrd_particle_wide_max_particles", "sepaihrd_particle_wide_timing",
     "sepaihrd_particle_wide_resample_device",
+    "sepaihrd_particle_loglik_nb", "sepaihrd_particle_loglik_wide_nb", "sepaihrd_particle_nb_validate", "sepaihrd_particle_nb_row_constants",
+    "sepaihrd_particle_nb_term_device",
 )
 
 _lib = None
@@ -367,6 +369,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_particle_wide_max_particles.argtypes = []
     lib.sepaihrd_particle_wide_timing.argtypes = [vp, vp]
     lib.sepaihrd_particle_wide_resample_device.argtypes = lib.sepaihrd_particle_resample_device.argtypes
+    lib.sepaihrd_particle_loglik_nb.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp] + [vp] * 7
+    lib.sepaihrd_particle_loglik_wide_nb.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int] + [vp] * 7
+    lib.sepaihrd_particle_nb_validate.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_nb_row_constants.argtypes = [vp, vp, vp]
+    lib.sepaihrd_particle_nb_term_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_double, vp, C.c_char_p, C.c_int]
     if path is None:
         _lib = lib
     return lib
@@ -657,22 +664,31 @@ class HipObjective:
         return int(self.lib.sepaihrd_particle_max_particles(self.pb.n))
 
     def particle_loglik(self, theta, J: int, steps_per_interval: int, seed: int, want_increments: bool = True, want_ess: bool = True,
-                        want_final: bool = False, want_values: bool = False) -> dict:
+                        want_final: bool = False, want_values: bool = False, dispersion=None) -> dict:
         """The bootstrap particle filter of the stochastic SEPAIHRD model (sepaihrd_particle_loglik): J particles per row of theta,
         steps_per_interval binomial steps per output interval, systematic resampling at every observed row.  loglik [B] (the
         estimate of log p(y | theta); -DBL_MAX for an invalid theta), increments [B][T_pos], ess [B][T_pos], final_state
-        [B][J][11][n], model_values [B][W], status [B], n_valid."""
+        [B][J][11][n], model_values [B][W], status [B], n_valid.  dispersion = (k_H, k_ICU, k_D), each +inf or finite in
+        [1e-3, 1e6]: the negative-binomial observation model through sepaihrd_particle_loglik_nb (None: the Poisson call)."""
+        if dispersion is not None:
+            return self._particle_call("particle_loglik_nb", self.lib.sepaihrd_particle_loglik_nb, (), theta, J, steps_per_interval, seed,
+                                       want_increments, want_ess, want_final, want_values, dispersion)
         return self._particle_call("particle_loglik", self.lib.sepaihrd_particle_loglik, (), theta, J, steps_per_interval, seed, want_increments,
                                    want_ess, want_final, want_values)
 
     def particle_loglik_wide(self, theta, J: int, steps_per_interval: int, seed: int, theta_chunk: int = 0, want_increments: bool = True,
-                             want_ess: bool = True, want_final: bool = False, want_values: bool = False) -> dict:
+                             want_ess: bool = True, want_final: bool = False, want_values: bool = False, dispersion=None) -> dict:
         """The wide form of particle_loglik (sepaihrd_particle_loglik_wide): the particles in device memory, J up to 65 536, the
-        thetas theta_chunk at a time (0: chosen by the call).  The same outputs, bit for bit where particle_loglik takes J."""
+        thetas theta_chunk at a time (0: chosen by the call).  The same outputs, bit for bit where particle_loglik takes J.
+        dispersion as in particle_loglik, through sepaihrd_particle_loglik_wide_nb."""
+        if dispersion is not None:
+            return self._particle_call("particle_loglik_wide_nb", self.lib.sepaihrd_particle_loglik_wide_nb, (int(theta_chunk),), theta, J,
+                                       steps_per_interval, seed, want_increments, want_ess, want_final, want_values, dispersion)
         return self._particle_call("particle_loglik_wide", self.lib.sepaihrd_particle_loglik_wide, (int(theta_chunk),), theta, J, steps_per_interval,
                                    seed, want_increments, want_ess, want_final, want_values)
 
-    def _particle_call(self, who, fn, extra, theta, J, steps_per_interval, seed, want_increments, want_ess, want_final, want_values) -> dict:
+    def _particle_call(self, who, fn, extra, theta, J, steps_per_interval, seed, want_increments, want_ess, want_final, want_values,
+                       dispersion=None) -> dict:
         th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
         B, n, J = th.shape[0], self.pb.n, int(J)
         Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
@@ -685,6 +701,11 @@ class HipObjective:
         status = np.empty(B, dtype=np.int32)
         nv = C.c_int32(0)
         ptr = lambda a: None if a is None else a.ctypes.data
+        if dispersion is not None:  # the _nb calls take it after the seed
+            disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+            if disp.size != 3:
+                raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+            extra = (disp.ctypes.data,) + tuple(extra)
         self._check(fn(self.ctx, th.ctypes.data, B, J, int(steps_per_interval), int(seed) & 0xFFFFFFFFFFFFFFFF, *extra, loglik.ctypes.data, ptr(inc),
                        ptr(ess), ptr(final), ptr(values), status.ctypes.data, C.byref(nv)), who)
         out = {"loglik": loglik, "status": status, "n_valid": nv.value}
@@ -693,14 +714,41 @@ class HipObjective:
                 out[key] = arr
         return out
 
+    def particle_nb_row_constants(self, dispersion) -> np.ndarray:
+        """sepaihrd_particle_nb_row_constants (host only): G [T_pos], the row constants a call with this dispersion uploads"""
+        disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+        if disp.size != 3:
+            raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+        G = np.empty(int(np.sum(np.asarray(self.pb.times) >= 0.0)))
+        if self.lib.sepaihrd_particle_nb_row_constants(self.ctx, disp.ctypes.data, G.ctypes.data) != 0:
+            raise ValueError("sepaihrd_particle_nb_row_constants refused the dispersion")
+        return G
+
+    def particle_nb_term_device(self, obs, inc, k: float) -> np.ndarray:
+        """Probe of the device's negative-binomial term (sepaihrd_particle_nb_term_device): out[i] for the observation obs[i] and
+        the increment inc[i] (int32) under the dispersion k"""
+        ob = np.ascontiguousarray(obs, dtype=np.float64).ravel()
+        ic = np.ascontiguousarray(inc, dtype=np.int32).ravel()
+        if ob.size != ic.size:
+            raise ValueError("obs and inc must have the same number of cells")
+        out = np.empty(ob.size)
+        err = C.create_string_buffer(512)
+        rc = self.lib.sepaihrd_particle_nb_term_device(getattr(self, "_device", -1), ob.ctypes.data, ic.ctypes.data, ob.size, float(k),
+                                                       out.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_particle_nb_term_device failed ({rc}): " + err.value.decode())
+        return out
+
     def particle_timing(self) -> np.ndarray:
-        """Device time of the last particle_loglik call in ms: decode; filter kernel (sepaihrd_particle_timing)"""
+        """Device time of the last particle_loglik call (with or without a dispersion) in ms: decode; filter kernel
+        (sepaihrd_particle_timing)"""
         ms = np.zeros(2)
         self._check(self.lib.sepaihrd_particle_timing(self.ctx, ms.ctypes.data), "particle_timing")
         return ms
 
     def particle_wide_timing(self) -> np.ndarray:
-        """Device time of the last particle_loglik_wide call in ms: decode; all filter launches (sepaihrd_particle_wide_timing)"""
+        """Device time of the last particle_loglik_wide call (with or without a dispersion) in ms: decode; all filter launches
+        (sepaihrd_particle_wide_timing)"""
         ms = np.zeros(2)
         self._check(self.lib.sepaihrd_particle_wide_timing(self.ctx, ms.ctypes.data), "particle_wide_timing")
         return ms

@@ -6,6 +6,7 @@
 // filter kernel (the same text, OpenMP over theta) is hostParticleLoglik.
 #pragma once
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -37,6 +38,21 @@ int hostParticleLoglikWide(const StochasticSEPAIHRDFixedData& pb, const Particle
                            const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments,
                            double* ess, double* final_state, std::string* error = nullptr);
 
+// The twins of sepaihrd_particle_loglik_nb and sepaihrd_particle_loglik_wide_nb: the same walk with the dispersion dispersion[3] =
+// {k_H, k_ICU, k_D} of the observed series (csrc/sepaihrd_particle.inc; +inf keeps a series Poisson) and the row constants, formed
+// by the text the device call forms them with (csrc/sepaihrd_particle_nb_host.h).  SEPAIHRD_E_INVALID_ARG with
+// sepaihrd_particle_nb_validate's message for a dispersion that call refuses.
+int hostParticleLoglikNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                         const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, double* loglik,
+                         double* increments, double* ess, double* final_state, std::string* error = nullptr);
+int hostParticleLoglikWideNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                             const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, double* loglik,
+                             double* increments, double* ess, double* final_state, std::string* error = nullptr);
+// the row constants G [T_pos] such a call adds (the twin of sepaihrd_particle_nb_row_constants) and the twin of
+// sepaihrd_particle_nb_term_device: out[i] = nb_term(obs[i], inc[i], k)
+int hostParticleNBRowConstants(const ParticleObservations& obs, int n_age, int T_pos, const double* dispersion, double* G, std::string* error = nullptr);
+void hostParticleNBTerm(const double* obs, const int32_t* inc, int count, double k, double* out);
+
 // the twin of sepaihrd_particle_resample_device and of sepaihrd_particle_wide_resample_device (any J): one weighted row with log-weights logw [J] at the coordinates (seed, b, row)
 void hostParticleResample(std::uint64_t seed, std::uint32_t b, std::uint32_t row, const double* logw, int J, int32_t* ancestors,
                           double* increment, double* ess);
@@ -47,7 +63,8 @@ void hostParticleResample(std::uint64_t seed, std::uint32_t b, std::uint32_t row
 // existing Adaptive-Metropolis loop is therefore particle-marginal Metropolis-Hastings (Andrieu, Doucet & Holenstein 2010) and
 // targets the exact posterior of the stochastic model.  Nothing in the samplers changes.  An invalid theta gives lowest(), as
 // the ODE objective does.  With `particles` at or below sepaihrd_particle_max_particles(n_age) the call is
-// sepaihrd_particle_loglik; above it, sepaihrd_particle_loglik_wide with theta_chunk = 0 (up to 65 536 particles).
+// sepaihrd_particle_loglik; above it, sepaihrd_particle_loglik_wide with theta_chunk = 0 (up to 65 536 particles).  After
+// setDispersion with a finite entry the call is the _nb call of the same form (the negative-binomial observation model).
 class HipParticleLikelihood : public virtual IObjectiveFunction, public IBatchObjectiveFunction {
 public:
     HipParticleLikelihood(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
@@ -59,6 +76,9 @@ public:
     const std::vector<std::string>& getParameterNames() const override { return pm_.getParameterNames(); }
     void calculateBatch(const double* thetas, int B, double* out, int* status = nullptr) const override;
     std::uint64_t calls() const { return calls_; }
+    // the dispersion of the observed series, each +inf (Poisson, the default) or finite in [1e-3, 1e6]; throws
+    // InvalidParameterException with sepaihrd_particle_nb_validate's message for anything else
+    void setDispersion(double k_H, double k_ICU, double k_D);
 
 private:
     HipSEPAIHRDParameterManager& pm_;
@@ -69,6 +89,8 @@ private:
     int particles_, steps_per_interval_, n_age_;
     std::uint64_t seed0_;
     mutable std::uint64_t calls_ = 0;
+    double dispersion_[3] = {std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(),
+                             std::numeric_limits<double>::infinity()};
 };
 
 }  // namespace epidemic

@@ -10,6 +10,7 @@
 #include "StochasticSEPAIHRDTwin.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_particle.inc"
+#include "sepaihrd_particle_nb_host.h"
 
 namespace epidemic {
 
@@ -19,10 +20,14 @@ namespace pf = sepaihrd_particle;
 namespace {
 
 // The filter's walk over B parameter vectors, after the arguments have been accepted: what hostParticleLoglik and
-// hostParticleLoglikWide both are.  Nothing in it depends on how large J is.
+// hostParticleLoglikWide both are, and their negative-binomial forms.  Nothing in it depends on how large J is.  disp is the
+// dispersion of the observed series (NO_DISPERSION: every series Poisson); row_const the row constants G [T_pos] of a call with
+// a dispersed series, null where there is none.
+constexpr pf::Dispersion NO_DISPERSION{std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(),
+                                       std::numeric_limits<double>::infinity()};
 void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan, const ParticleObservations& obs, const double* model_values,
-                   const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, double* loglik, double* increments, double* ess,
-                   double* final_state) {
+                   const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const pf::Dispersion& disp, const double* row_const,
+                   double* loglik, double* increments, double* ess, double* final_state) {
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     const int n = pb.n_age, T = pb.n_times, m = steps_per_interval, runup_offset = plan.runup_offset;
     const size_t Tp = (size_t)plan.T_pos, nn = (size_t)n, W = plan.W, row_doubles = plan.row_doubles;
@@ -76,7 +81,7 @@ void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan
                     int32_t* x = x_of(state, j, i);
                     int32_t inc[epi::NUM_PREV];
                     epi::take_increments(x, x + epi::NUM_COMP, inc);
-                    if (weighted) sum += pf::age_term(observed(obs.obs_H, t, i), observed(obs.obs_ICU, t, i), observed(obs.obs_D, t, i), inc[0], inc[1], inc[2]);
+                    if (weighted) sum += pf::age_term(observed(obs.obs_H, t, i), observed(obs.obs_ICU, t, i), observed(obs.obs_D, t, i), inc[0], inc[1], inc[2], disp);
                 }
                 lw[(size_t)j] = sum;
             }
@@ -85,6 +90,7 @@ void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan
                 pf::normalise_and_resample(lw.data(), J, pf::resample_uniform(seed, (uint32_t)b, (uint32_t)k), C.data(), Q.data(), anc.data(), inc, e);
                 for (int j = 0; j < J; ++j) std::copy_n(state.data() + (size_t)anc[(size_t)j] * per, per, next.data() + (size_t)j * per);
                 state.swap(next);
+                if (row_const) inc = pf::increment_with_constant(inc, row_const[t]);
                 total += inc;
                 if (my_inc) my_inc[t] = inc;
                 if (my_ess) my_ess[t] = e;
@@ -123,7 +129,7 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                                      sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg,
                                      pb, obs, model_values, status, loglik, error);
     if (vrc != SEPAIHRD_OK) return vrc;
-    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state);
+    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, NO_DISPERSION, nullptr, loglik, increments, ess, final_state);
     return SEPAIHRD_OK;
 }
 
@@ -136,8 +142,73 @@ int hostParticleLoglikWide(const StochasticSEPAIHRDFixedData& pb, const Particle
                                      sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
                                      msg, pb, obs, model_values, status, loglik, error);
     if (vrc != SEPAIHRD_OK) return vrc;
-    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state);
+    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, NO_DISPERSION, nullptr, loglik, increments, ess, final_state);
     return SEPAIHRD_OK;
+}
+
+namespace {
+
+// the observation of (series, output row t >= 0, age), NaN where there is none: the cells of the row constants
+double observed_cell(const ParticleObservations& obs, int n_age, int series, int t, int age) {
+    const double* table = series == 0 ? obs.obs_H : series == 1 ? obs.obs_ICU : obs.obs_D;
+    return t < obs.n_obs ? table[(size_t)t * (size_t)n_age + (size_t)age] : std::numeric_limits<double>::quiet_NaN();
+}
+
+// either negative-binomial twin: the dispersion's verdict beside the form's own, the row constants, the walk
+int particle_nb(const char* who, int vrc, char (&msg)[256], const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan,
+                const ParticleObservations& obs, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                std::uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state, std::string* error) {
+    vrc = particle_verdict(who, vrc, msg, pb, obs, model_values, status, loglik, error);
+    if (vrc != SEPAIHRD_OK) return vrc;
+    if (sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+        if (error) *error = msg;
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    const pf::Dispersion d{dispersion[0], dispersion[1], dispersion[2]};
+    std::vector<double> G;
+    if (pf::any_dispersed(d)) {
+        G.resize((size_t)plan.T_pos);
+        pf::nb_row_constants(d, pb.n_age, plan.T_pos, [&](int series, int t, int age) { return observed_cell(obs, pb.n_age, series, t, age); }, G.data());
+    }
+    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, d, G.empty() ? nullptr : G.data(), loglik, increments, ess,
+                  final_state);
+    return SEPAIHRD_OK;
+}
+
+}  // namespace
+
+int hostParticleLoglikNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                         const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, double* loglik,
+                         double* increments, double* ess, double* final_state, std::string* error) {
+    char msg[256] = "";
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    return particle_nb("particle_loglik_nb", sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
+                       msg, pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state, error);
+}
+
+int hostParticleLoglikWideNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
+                             const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, double* loglik,
+                             double* increments, double* ess, double* final_state, std::string* error) {
+    char msg[256] = "";
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    return particle_nb("particle_loglik_wide_nb",
+                       sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg, pb,
+                       plan, obs, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state, error);
+}
+
+int hostParticleNBRowConstants(const ParticleObservations& obs, int n_age, int T_pos, const double* dispersion, double* G, std::string* error) {
+    char msg[256] = "";
+    if (sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+        if (error) *error = msg;
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    pf::nb_row_constants(pf::Dispersion{dispersion[0], dispersion[1], dispersion[2]}, n_age, T_pos,
+                         [&](int series, int t, int age) { return observed_cell(obs, n_age, series, t, age); }, G);
+    return SEPAIHRD_OK;
+}
+
+void hostParticleNBTerm(const double* obs, const int32_t* inc, int count, double k, double* out) {
+    for (int i = 0; i < count; ++i) out[i] = pf::nb_term(obs[i], inc[i], k);
 }
 
 void hostParticleResample(std::uint64_t seed, std::uint32_t b, std::uint32_t row, const double* logw, int J, int32_t* ancestors,
@@ -156,6 +227,13 @@ HipParticleLikelihood::HipParticleLikelihood(HipSEPAIHRDParameterManager& parame
                                             initial_state_mode);
 }
 
+void HipParticleLikelihood::setDispersion(double k_H, double k_ICU, double k_D) {
+    const double d[3] = {k_H, k_ICU, k_D};
+    char msg[256] = "";
+    if (sepaihrd_particle_nb_validate(d, msg, (int)sizeof(msg)) != SEPAIHRD_OK) throw InvalidParameterException("HipParticleLikelihood", msg);
+    std::copy_n(d, 3, dispersion_);
+}
+
 void HipParticleLikelihood::calculateBatch(const double* thetas, int B, double* out, int* status) const {
     sepaihrd_ctx* ctx = objective_->deviceContext();
     objective_->syncDeviceConstraintMode();
@@ -164,13 +242,22 @@ void HipParticleLikelihood::calculateBatch(const double* thetas, int B, double* 
     // up to the LDS kernel's limit that kernel, beyond it the wide form with the chunking left to the call: the same bits where
     // both take J, so the choice is one of speed alone
     const bool wide = particles_ > sepaihrd_particle_max_particles(n_age_);
-    const int rc = wide ? sepaihrd_particle_loglik_wide(ctx, thetas, B, particles_, steps_per_interval_, seed, 0, out, nullptr, nullptr, nullptr, nullptr,
-                                                        st.data(), nullptr)
-                        : sepaihrd_particle_loglik(ctx, thetas, B, particles_, steps_per_interval_, seed, out, nullptr, nullptr, nullptr, nullptr,
-                                                   st.data(), nullptr);
+    // the _nb call of that form once setDispersion has made some series dispersed
+    const bool nb = pf::any_dispersed(pf::Dispersion{dispersion_[0], dispersion_[1], dispersion_[2]});
+    int rc;
+    if (nb)
+        rc = wide ? sepaihrd_particle_loglik_wide_nb(ctx, thetas, B, particles_, steps_per_interval_, seed, dispersion_, 0, out, nullptr, nullptr, nullptr,
+                                                     nullptr, st.data(), nullptr)
+                  : sepaihrd_particle_loglik_nb(ctx, thetas, B, particles_, steps_per_interval_, seed, dispersion_, out, nullptr, nullptr, nullptr,
+                                                nullptr, st.data(), nullptr);
+    else
+        rc = wide ? sepaihrd_particle_loglik_wide(ctx, thetas, B, particles_, steps_per_interval_, seed, 0, out, nullptr, nullptr, nullptr, nullptr,
+                                                  st.data(), nullptr)
+                  : sepaihrd_particle_loglik(ctx, thetas, B, particles_, steps_per_interval_, seed, out, nullptr, nullptr, nullptr, nullptr, st.data(),
+                                             nullptr);
     if (rc != SEPAIHRD_OK)
-        throw ModelException("HipParticleLikelihood",
-                             std::string(wide ? "sepaihrd_particle_loglik_wide: " : "sepaihrd_particle_loglik: ") + sepaihrd_last_error(ctx));
+        throw ModelException("HipParticleLikelihood", std::string(wide ? "sepaihrd_particle_loglik_wide" : "sepaihrd_particle_loglik") +
+                                                          (nb ? "_nb: " : ": ") + sepaihrd_last_error(ctx));
     ++calls_;
     if (status) std::copy(st.begin(), st.begin() + B, status);
 }

@@ -1579,6 +1579,60 @@ int host_particle_wide_from_values(int n_age, int n_times, int n_beta, int n_kap
                                      err, errlen);
 }
 
+// hostParticleLoglikNB / hostParticleLoglikWideNB (no device): the same shapes with dispersion [3] = {k_H, k_ICU, k_D}
+namespace {
+int particle_nb_twin_from_values(bool wide, int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                                 const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
+                                 const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                                 uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
+                                 char* err, int errlen) {
+    StochasticSEPAIHRDFixedData fd;
+    fd.n_age = n_age; fd.n_times = n_times; fd.n_beta = n_beta; fd.n_kappa = n_kappa;
+    fd.times = times; fd.N = N; fd.M = M; fd.beta_end_times = beta_end_times; fd.kappa_end_times = kappa_end_times;
+    ParticleObservations ob;
+    ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
+    std::string error;
+    const int rc = (wide ? hostParticleLoglikWideNB : hostParticleLoglikNB)(fd, ob, model_values, status, B, J, steps_per_interval, seed, dispersion,
+                                                                           loglik, increments, ess, final_state, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+}  // namespace
+
+int host_particle_nb_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                                 const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
+                                 const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                                 uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
+                                 char* err, int errlen) {
+    return particle_nb_twin_from_values(false, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
+                                        obs_D, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state,
+                                        err, errlen);
+}
+
+int host_particle_wide_nb_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                                      const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H,
+                                      const double* obs_ICU, const double* obs_D, const double* model_values, const int32_t* status, int B, int J,
+                                      int steps_per_interval, uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess,
+                                      double* final_state, char* err, int errlen) {
+    return particle_nb_twin_from_values(true, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
+                                        obs_D, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state,
+                                        err, errlen);
+}
+
+// the twin of sepaihrd_particle_nb_term_device (no device): out[i] = nb_term(obs[i], inc[i], k)
+void host_particle_nb_term(const double* obs, const int32_t* inc, int count, double k, double* out) { hostParticleNBTerm(obs, inc, count, k, out); }
+
+// the twin of sepaihrd_particle_nb_row_constants (no device): G [T_pos] from obs_* [n_obs][n_age]
+int host_particle_nb_row_constants(int n_age, int T_pos, int n_obs, const double* obs_H, const double* obs_ICU, const double* obs_D,
+                                   const double* dispersion, double* G, char* err, int errlen) {
+    ParticleObservations ob;
+    ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
+    std::string error;
+    const int rc = hostParticleNBRowConstants(ob, n_age, T_pos, dispersion, G, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
 // the twin of sepaihrd_particle_resample_device (no device)
 void host_particle_resample(uint64_t seed, uint32_t b, uint32_t row, const double* logw, int J, int32_t* ancestors, double* increment, double* ess) {
     hostParticleResample(seed, b, row, logw, J, ancestors, increment, ess);
@@ -1586,12 +1640,21 @@ void host_particle_resample(uint64_t seed, uint32_t b, uint32_t row, const doubl
 
 // HipParticleLikelihood over the handle's parameter manager / data: n_calls successive calculateBatch calls on the same B
 // parameter vectors (thetas B x P); values [n_calls][B], status [n_calls][B] (nullable).  0 ok, 1 = exception.
+int host_particle_likelihood_nb(void* hv, const sepaihrd_problem* pb, int device, int initial_state_mode, int J, int steps_per_interval, uint64_t seed0,
+                                const double* dispersion, const double* thetas, int B, int n_calls, double* values, int32_t* status);
 int host_particle_likelihood(void* hv, const sepaihrd_problem* pb, int device, int initial_state_mode, int J, int steps_per_interval, uint64_t seed0,
                              const double* thetas, int B, int n_calls, double* values, int32_t* status) {
+    return host_particle_likelihood_nb(hv, pb, device, initial_state_mode, J, steps_per_interval, seed0, nullptr, thetas, B, n_calls, values, status);
+}
+
+// the same after setDispersion(dispersion[0], dispersion[1], dispersion[2]); dispersion NULL: the adapter's default
+int host_particle_likelihood_nb(void* hv, const sepaihrd_problem* pb, int device, int initial_state_mode, int J, int steps_per_interval, uint64_t seed0,
+                                const double* dispersion, const double* thetas, int B, int n_calls, double* values, int32_t* status) {
     auto* h = static_cast<HostHandle*>(hv);
     return guarded([&] {
         HipParticleLikelihood lik(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * pb->n_age),
                                   strategy_for(pb->solver), J, steps_per_interval, seed0, device, initial_state_mode);
+        if (dispersion) lik.setDispersion(dispersion[0], dispersion[1], dispersion[2]);
         const IBatchObjectiveFunction& batch = lik;
         std::vector<int> st(static_cast<size_t>(B));
         for (int c = 0; c < n_calls; ++c) {

@@ -139,6 +139,14 @@ def load_library() -> C.CDLL:
     lib.host_particle_from_values.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_uint64] + \
         [vp] * 4 + [C.c_char_p, C.c_int]
     lib.host_particle_wide_from_values.argtypes = lib.host_particle_from_values.argtypes
+    lib.host_particle_nb_from_values.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_uint64, vp] + \
+        [vp] * 4 + [C.c_char_p, C.c_int]
+    lib.host_particle_wide_nb_from_values.argtypes = lib.host_particle_nb_from_values.argtypes
+    lib.host_particle_nb_term.restype = None
+    lib.host_particle_nb_term.argtypes = [vp, vp, C.c_int, C.c_double, vp]
+    lib.host_particle_nb_row_constants.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.host_particle_likelihood_nb.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp,
+                                                C.c_int, C.c_int, vp, vp]
     lib.host_particle_resample.restype = None
     lib.host_particle_resample.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.host_particle_likelihood.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int,
@@ -453,14 +461,21 @@ class HostObjective:
                 "samples_used": used.value}
 
     def particle_likelihood(self, thetas, J: int, steps_per_interval: int, seed0: int, n_calls: int = 1, initial_state_mode: int = 0,
-                            device: int = -1) -> dict:
+                            device: int = -1, dispersion=None) -> dict:
         """HipParticleLikelihood over this handle's parameter manager and data: n_calls successive calculateBatch calls on the same
-        rows of thetas; call c runs at seed0 + c.  values [n_calls][B], status [n_calls][B]."""
+        rows of thetas; call c runs at seed0 + c.  values [n_calls][B], status [n_calls][B].  dispersion = (k_H, k_ICU, k_D): the
+        calls run after setDispersion (None: the adapter's default, every series Poisson)."""
         th = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
         keep: list = []
         st = hipabi.build_problem_struct(self.pb, keep)
         B = th.shape[0]
         values, status = np.empty((n_calls, B)), np.empty((n_calls, B), dtype=np.int32)
+        if dispersion is not None:
+            disp = _dispersion(dispersion)
+            _check(self.lib.host_particle_likelihood_nb(self.h, C.byref(st), device, int(initial_state_mode), int(J), int(steps_per_interval),
+                                                        int(seed0) & 0xFFFFFFFFFFFFFFFF, disp.ctypes.data, th.ctypes.data, B, int(n_calls),
+                                                        values.ctypes.data, status.ctypes.data), "host_particle_likelihood_nb: ")
+            return {"values": values, "status": status}
         _check(self.lib.host_particle_likelihood(self.h, C.byref(st), device, int(initial_state_mode), int(J), int(steps_per_interval),
                                                  int(seed0) & 0xFFFFFFFFFFFFFFFF, th.ctypes.data, B, int(n_calls), values.ctypes.data,
                                                  status.ctypes.data), "host_particle_likelihood: ")
@@ -1162,24 +1177,69 @@ def particle_wide_validate(B: int, J: int, steps_per_interval: int, theta_chunk:
         raise ValueError(err.value.decode())
 
 
+def _dispersion(dispersion) -> np.ndarray:
+    """(k_H, k_ICU, k_D) as three contiguous doubles"""
+    disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+    if disp.size != 3:
+        raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+    return disp
+
+
+def particle_nb_validate(dispersion) -> None:
+    """sepaihrd_particle_nb_validate (host only): ValueError with its message for a dispersion the filters refuse (None: NULL)"""
+    err = C.create_string_buffer(512)
+    disp = None if dispersion is None else _dispersion(dispersion)
+    if hipabi.load_library().sepaihrd_particle_nb_validate(None if disp is None else disp.ctypes.data, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def particle_nb_term(obs, inc, k: float) -> np.ndarray:
+    """The twin of HipObjective.particle_nb_term_device: the negative-binomial term of csrc/sepaihrd_particle.inc for the observations
+    obs, the increments inc (int32) and the dispersion k, cell by cell"""
+    ob = np.ascontiguousarray(obs, dtype=np.float64).ravel()
+    ic = np.ascontiguousarray(inc, dtype=np.int32).ravel()
+    if ob.size != ic.size:
+        raise ValueError("obs and inc must have the same number of cells")
+    out = np.empty(ob.size)
+    load_library().host_particle_nb_term(ob.ctypes.data, ic.ctypes.data, ob.size, float(k), out.ctypes.data)
+    return out
+
+
+def particle_nb_row_constants(obs_H, obs_ICU, obs_D, n_age: int, T_pos: int, dispersion) -> np.ndarray:
+    """The twin of sepaihrd_particle_nb_row_constants: G [T_pos], the row constants of the observations obs_* [n_obs][n_age] under
+    the dispersion (k_H, k_ICU, k_D); output rows beyond n_obs have no observation"""
+    n = int(n_age)
+    ob = [np.ascontiguousarray(np.asarray(o, dtype=np.float64).reshape(-1, n)) for o in (obs_H, obs_ICU, obs_D)]
+    if not (ob[0].shape == ob[1].shape == ob[2].shape):
+        raise ValueError("obs_H, obs_ICU and obs_D must have the same shape [n_obs][n]")
+    disp = _dispersion(dispersion)
+    G = np.empty(int(T_pos))
+    err = C.create_string_buffer(512)
+    if load_library().host_particle_nb_row_constants(n, int(T_pos), ob[0].shape[0], ob[0].ctypes.data, ob[1].ctypes.data, ob[2].ctypes.data,
+                                                     disp.ctypes.data, G.ctypes.data, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+    return G
+
+
 def particle_from_values(model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J: int, steps_per_interval: int, seed: int,
-                         beta_end_times=(), want_final: bool = True) -> dict:
+                         beta_end_times=(), want_final: bool = True, dispersion=None) -> dict:
     """The twin of HipObjective.particle_loglik after the decoding: from model_values [B][W] and status [B], the problem's fixed data
     (times, N [n], M [n][n] with M[i, j] = M(i, j), the schedule end times) and the observations obs_* [n_obs][n] of the output times
     >= 0 the same loglik [B], increments [B][T_pos], ess [B][T_pos] and final_state [B][J][11][n], bit for bit."""
     return _particle_from_values(False, model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J, steps_per_interval, seed,
-                                 beta_end_times, want_final)
+                                 beta_end_times, want_final, dispersion)
 
 
 def particle_wide_from_values(model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J: int, steps_per_interval: int,
-                              seed: int, beta_end_times=(), want_final: bool = True) -> dict:
+                              seed: int, beta_end_times=(), want_final: bool = True, dispersion=None) -> dict:
     """The twin of HipObjective.particle_loglik_wide: particle_from_values' walk behind the wide form's argument rules (J up to 65 536)"""
     return _particle_from_values(True, model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J, steps_per_interval, seed,
-                                 beta_end_times, want_final)
+                                 beta_end_times, want_final, dispersion)
 
 
 def _particle_from_values(wide, model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J, steps_per_interval, seed, beta_end_times,
-                          want_final) -> dict:
+                          want_final, dispersion=None) -> dict:
+    # dispersion = (k_H, k_ICU, k_D): the negative-binomial twins (hostParticleLoglikNB, hostParticleLoglikWideNB); None: the Poisson twins
     mv = np.ascontiguousarray(np.atleast_2d(model_values), dtype=np.float64)
     st = np.ascontiguousarray(status, dtype=np.int32).ravel()
     tm = np.ascontiguousarray(times, dtype=np.float64).ravel()
@@ -1202,10 +1262,18 @@ def _particle_from_values(wide, model_values, status, times, N, M, kappa_end_tim
     loglik, inc, ess = np.empty(B), np.empty((B, Tp)), np.empty((B, Tp))
     final = np.empty((B, J, 11, n)) if want_final else None
     err = C.create_string_buffer(512)
-    call = load_library().host_particle_wide_from_values if wide else load_library().host_particle_from_values
+    lib = load_library()
+    extra = ()
+    if dispersion is None:
+        call = lib.host_particle_wide_from_values if wide else lib.host_particle_from_values
+    else:
+        particle_nb_validate(dispersion)
+        disp = _dispersion(dispersion)
+        extra = (disp.ctypes.data,)
+        call = lib.host_particle_wide_nb_from_values if wide else lib.host_particle_nb_from_values
     rc = call(n, T, be.size, ke.size, tm.ctypes.data, Nv.ctypes.data, Mm.ctypes.data, be.ctypes.data if be.size else None, ke.ctypes.data,
               ob[0].shape[0], ob[0].ctypes.data, ob[1].ctypes.data, ob[2].ctypes.data, mv.ctypes.data, st.ctypes.data, B, J, int(steps_per_interval),
-              int(seed) & 0xFFFFFFFFFFFFFFFF, loglik.ctypes.data, inc.ctypes.data, ess.ctypes.data, None if final is None else final.ctypes.data,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, *extra, loglik.ctypes.data, inc.ctypes.data, ess.ctypes.data, None if final is None else final.ctypes.data,
               err, len(err))
     if rc != 0:
         raise ValueError(err.value.decode())
