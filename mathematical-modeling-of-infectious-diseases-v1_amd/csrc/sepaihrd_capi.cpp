@@ -217,6 +217,22 @@ int refuse(sepaihrd_ctx* ctx, const char* who, const std::string& msg, int rc) {
     return rc;
 }
 
+// a validator's verdict (vrc, with its text in msg) as the call's: a refusal becomes the context's last error
+int validated(sepaihrd_ctx* ctx, int vrc, const char* msg) {
+    if (vrc == SEPAIHRD_OK) return SEPAIHRD_OK;
+    ctx->last_error = msg;
+    return SEPAIHRD_E_INVALID_ARG;
+}
+
+// ms[i]: the time from ev[i] to ev[i + 1] of a call that has been synchronised
+void elapsed_ms(const std::vector<Event>& ev, double* ms, int n) {
+    for (int i = 0; i < n; ++i) {
+        float t = 0.0f;
+        (void)hipEventElapsedTime(&t, ev[i], ev[i + 1]);
+        ms[i] = t;
+    }
+}
+
 // The opening checks the ensemble entry points share.  Always: the arguments every call needs (have_args, with the text
 // `need` that names them) and n_probs in 1..1024.  Then those of `checks`, in this order; an entry point that has checks of
 // its own in between asks in several steps (need == nullptr: the arguments were checked before).
@@ -915,13 +931,9 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     if (rc != SEPAIHRD_OK) return rc;
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
-    {
-        char msg[256] = "";
-        if (sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-            ctx->last_error = msg;
-            return SEPAIHRD_E_INVALID_ARG;
-        }
-    }
+    char msg[256] = "";
+    rc = validated(ctx, sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)), msg);
+    if (rc != SEPAIHRD_OK) return rc;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     // sizes
     const size_t N = (size_t)S * (size_t)R;
@@ -980,11 +992,7 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     if (launch_predictive_quantiles(a, nullptr) != 0) return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[3], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
-    for (int i = 0; i < 3; ++i) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
-        ctx->pred_ms[i] = ms;
-    }
+    elapsed_ms(sc.ev, ctx->pred_ms, 3);
     // fetches
     ResultFetch res;
     res.fetch(pred_quantiles, d_q, n_q * sizeof(double));
@@ -1013,13 +1021,9 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
     if (rc != SEPAIHRD_OK) return rc;
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
-    {
-        char msg[256] = "";
-        if (sepaihrd_stochastic_validate(S, R, steps_per_interval, keep, dp.T, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-            ctx->last_error = msg;
-            return SEPAIHRD_E_INVALID_ARG;
-        }
-    }
+    char msg[256] = "";
+    rc = validated(ctx, sepaihrd_stochastic_validate(S, R, steps_per_interval, keep, dp.T, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)), msg);
+    if (rc != SEPAIHRD_OK) return rc;
     if (keep > 0 && !traj) return refuse(ctx, who, "keep > 0 needs traj", SEPAIHRD_E_INVALID_ARG);
     if (ctx->precision != SEPAIHRD_PRECISION_F64)
         return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
@@ -1081,11 +1085,7 @@ int sepaihrd_ensemble_stochastic(sepaihrd_ctx* ctx, const double* theta, int S, 
     if (launch_predictive_quantiles(pa, nullptr) != 0) return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
-    for (int i = 0; i < 2; ++i) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
-        ctx->stoch_ms[i] = ms;
-    }
+    elapsed_ms(sc.ev, ctx->stoch_ms, 2);
     // fetches
     ResultFetch res;
     std::vector<int32_t> h_status((size_t)S), h_extinct((size_t)S);
@@ -1130,10 +1130,8 @@ void nb_row_constants_of(const sepaihrd_ctx* ctx, const sepaihrd_particle::Dispe
 // SEPAIHRD_OK, or the validator's refusal as the context's last error
 int nb_plan(sepaihrd_ctx* ctx, const double* dispersion, NbPlan& plan) {
     char msg[256] = "";
-    if (sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-        ctx->last_error = msg;
-        return SEPAIHRD_E_INVALID_ARG;
-    }
+    const int rc = validated(ctx, sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)), msg);
+    if (rc != SEPAIHRD_OK) return rc;
     plan.d = sepaihrd_particle::Dispersion{dispersion[0], dispersion[1], dispersion[2]};
     plan.some = sepaihrd_particle::any_dispersed(plan.d);
     if (plan.some) {
@@ -1143,11 +1141,13 @@ int nb_plan(sepaihrd_ctx* ctx, const double* dispersion, NbPlan& plan) {
     return SEPAIHRD_OK;
 }
 
-// sepaihrd_particle_loglik (dispersion NULL) and sepaihrd_particle_loglik_nb: one body.  With no dispersed series no table is
-// formed and the Poisson kernel runs, launch for launch.
-int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, const double* dispersion, const double* theta, int B, int J, int steps_per_interval,
-                         uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, double* model_values, int32_t* status,
-                         int32_t* n_valid) {
+// The four forms of the particle-filter call, one body: the LDS kernel (sepaihrd_particle_loglik, _nb) or, with `wide`, the
+// launches over particles in device memory (sepaihrd_particle_loglik_wide, _wide_nb; theta_chunk is theirs alone); dispersion
+// NULL for the Poisson forms.  With no dispersed series no table is formed and the Poisson kernels run, launch for launch.
+// Each form keeps its own validator, memory rule and timing slot.
+int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, bool wide, int theta_chunk, const double* dispersion, const double* theta, int B, int J,
+                         int steps_per_interval, uint64_t seed, double* loglik, double* increments, double* ess, double* final_state,
+                         double* model_values, int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
     if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
     int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
@@ -1155,13 +1155,12 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, const double* dispe
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
     if (dp.n > 16 || dp.lpc > 16) return refuse(ctx, who, "built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
-    {
-        char msg[256] = "";
-        if (sepaihrd_particle_validate(B, J, steps_per_interval, dp.T, Tp, dp.n, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-            ctx->last_error = msg;
-            return SEPAIHRD_E_INVALID_ARG;
-        }
-    }
+    char msg[256] = "";
+    rc = validated(ctx,
+                   wide ? sepaihrd_particle_wide_validate(B, J, steps_per_interval, theta_chunk, dp.T, Tp, dp.n, msg, (int)sizeof(msg))
+                        : sepaihrd_particle_validate(B, J, steps_per_interval, dp.T, Tp, dp.n, msg, (int)sizeof(msg)),
+                   msg);
+    if (rc != SEPAIHRD_OK) return rc;
     NbPlan nb;
     if (dispersion != nullptr) {
         rc = nb_plan(ctx, dispersion, nb);
@@ -1174,18 +1173,26 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, const double* dispe
     const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
     const size_t n_values = (size_t)B * W, n_rows = (size_t)B * Tp;
     const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
-    const size_t need_bytes =
-        sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size()) + sizeof(int32_t) * ((size_t)B + 2);
-    rc = require_device_memory(ctx, need_bytes, "particle_loglik: the model values of B = " + std::to_string(B) + " parameter vectors and the outputs asked for need",
-                               "split the parameter vectors over several calls");
+    const size_t chunk = wide ? particle_wide_chunk(dp.lpc, J, B, theta_chunk) : 0;
+    const size_t scratch_bytes = wide ? particle_wide_scratch_bytes(dp.lpc, J, chunk) : 0;  // the particles: the LDS form keeps them on chip
+    const size_t need_bytes = scratch_bytes + sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size()) +
+                              sizeof(int32_t) * ((size_t)B + 2);
+    const std::string what =
+        wide ? "particle_loglik_wide: the particles of " + std::to_string(chunk) + " parameter vectors at a time, the model values of B = " +
+                   std::to_string(B) + " and the outputs asked for need"
+             : "particle_loglik: the model values of B = " + std::to_string(B) + " parameter vectors and the outputs asked for need";
+    rc = require_device_memory(ctx, need_bytes, what,
+                               wide ? "lower theta_chunk or split the parameter vectors over several calls" : "split the parameter vectors over several calls");
     if (rc != SEPAIHRD_OK) return rc;
     // buffers and events of this call alone
     CallScratch sc(3);
-    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_G = nullptr;
+    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_scratch = nullptr,
+           *d_G = nullptr;
     int32_t *d_counts = nullptr, *d_status = nullptr;
     if (!sc.alloc(&d_theta, (size_t)B * ctx->P) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_ll, (size_t)B) ||
         !sc.alloc(&d_inc, increments ? n_rows : 0) || !sc.alloc(&d_ess, ess ? n_rows : 0) || !sc.alloc(&d_final, n_final) ||
-        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) || !sc.alloc(&d_G, nb.G.size()))
+        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) ||
+        (wide && !sc.alloc(&d_scratch, (scratch_bytes + sizeof(double) - 1) / sizeof(double))) || !sc.alloc(&d_G, nb.G.size()))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
@@ -1197,22 +1204,23 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, const double* dispe
     (void)hipEventRecord(sc.ev[0], nullptr);
     if (launch_stoch_epi_decode(dp, da, nullptr) != 0) return refuse(ctx, who, "decode kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[1], nullptr);
-    ParticleArgsNB a{};
+    ParticleWideArgs a{};
     a.B = B; a.J = J; a.m = steps_per_interval; a.W = W;
     a.seed = seed;
     a.values = d_values; a.status = d_status; a.loglik = d_ll;
     a.increments = increments ? d_inc : nullptr; a.ess = ess ? d_ess : nullptr; a.final_state = final_state ? d_final : nullptr;
-    a.k_H = nb.d.k_H; a.k_ICU = nb.d.k_ICU; a.k_D = nb.d.k_D;
-    a.row_const = d_G;
-    if ((nb.some ? launch_particle_filter_nb(dp, a, nullptr) : launch_particle_filter(dp, a, nullptr)) != 0)
-        return refuse(ctx, who, "filter kernel launch failed", SEPAIHRD_E_HIP);
+    if (nb.some) {
+        a.k_H = nb.d.k_H; a.k_ICU = nb.d.k_ICU; a.k_D = nb.d.k_D;
+        a.row_const = d_G;
+    }
+    a.chunk = chunk; a.scratch = d_scratch; a.host_grid = ctx->host_grid.data();  // read by the wide launch alone
+    const int lrc = wide      ? launch_particle_filter_wide(dp, a, nullptr)
+                    : nb.some ? launch_particle_filter_nb(dp, a, nullptr)
+                              : launch_particle_filter(dp, a, nullptr);
     (void)hipEventRecord(sc.ev[2], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
-    for (int i = 0; i < 2; ++i) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
-        ctx->particle_ms[i] = ms;
-    }
+    if (lrc != 0) return refuse(ctx, who, wide ? "filter launch failed" : "filter kernel launch failed", SEPAIHRD_E_HIP);
+    elapsed_ms(sc.ev, wide ? ctx->particle_wide_ms : ctx->particle_ms, 2);
     // fetches
     ResultFetch res;
     res.fetch(loglik, d_ll, (size_t)B * sizeof(double));
@@ -1232,7 +1240,7 @@ extern "C" {
 
 int sepaihrd_particle_loglik(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, double* loglik,
                              double* increments, double* ess, double* final_state, double* model_values, int32_t* status, int32_t* n_valid) {
-    return particle_loglik_call(ctx, "particle_loglik", nullptr, theta, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
+    return particle_loglik_call(ctx, "particle_loglik", false, 0, nullptr, theta, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
                                 model_values, status, n_valid);
 }
 
@@ -1241,8 +1249,8 @@ int sepaihrd_particle_loglik_nb(sepaihrd_ctx* ctx, const double* theta, int B, i
                                 double* model_values, int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
     if (!dispersion) return refuse(ctx, "particle_loglik_nb", "need dispersion (three entries: k_H, k_ICU, k_D)", SEPAIHRD_E_INVALID_ARG);
-    return particle_loglik_call(ctx, "particle_loglik_nb", dispersion, theta, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
-                                model_values, status, n_valid);
+    return particle_loglik_call(ctx, "particle_loglik_nb", false, 0, dispersion, theta, B, J, steps_per_interval, seed, loglik, increments, ess,
+                                final_state, model_values, status, n_valid);
 }
 
 int sepaihrd_particle_nb_row_constants(const sepaihrd_ctx* ctx, const double dispersion[3], double* G) {
@@ -1257,112 +1265,11 @@ int sepaihrd_particle_timing(const sepaihrd_ctx* ctx, double* ms) {
     return SEPAIHRD_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// sepaihrd_particle_loglik_wide (dispersion NULL) and sepaihrd_particle_loglik_wide_nb: one body, as particle_loglik_call
-int particle_loglik_wide_call(sepaihrd_ctx* ctx, const char* who, const double* dispersion, const double* theta, int B, int J, int steps_per_interval,
-                              uint64_t seed, int theta_chunk, double* loglik, double* increments, double* ess, double* final_state,
-                              double* model_values, int32_t* status, int32_t* n_valid) {
-    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
-    if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
-    int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
-    if (rc != SEPAIHRD_OK) return rc;
-    const DevProblem& dp = ctx->dp;
-    const int Tp = dp.T - dp.runup_offset;
-    if (dp.n > 16 || dp.lpc > 16) return refuse(ctx, who, "built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
-    {
-        char msg[256] = "";
-        if (sepaihrd_particle_wide_validate(B, J, steps_per_interval, theta_chunk, dp.T, Tp, dp.n, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-            ctx->last_error = msg;
-            return SEPAIHRD_E_INVALID_ARG;
-        }
-    }
-    NbPlan nb;
-    if (dispersion != nullptr) {
-        rc = nb_plan(ctx, dispersion, nb);
-        if (rc != SEPAIHRD_OK) return rc;
-    }
-    if (ctx->precision != SEPAIHRD_PRECISION_F64)
-        return refuse(ctx, who, "the stochastic model is built for fp64 contexts (set precision F64)", SEPAIHRD_E_UNSUPPORTED);
-    HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
-    // sizes
-    const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
-    const size_t n_values = (size_t)B * W, n_rows = (size_t)B * Tp;
-    const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
-    const size_t chunk = particle_wide_chunk(dp.lpc, J, B, theta_chunk);
-    const size_t scratch_bytes = particle_wide_scratch_bytes(dp.lpc, J, chunk);
-    const size_t need_bytes = scratch_bytes + sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size()) +
-                              sizeof(int32_t) * ((size_t)B + 2);
-    rc = require_device_memory(ctx, need_bytes,
-                               "particle_loglik_wide: the particles of " + std::to_string(chunk) + " parameter vectors at a time, the model values of B = " +
-                                   std::to_string(B) + " and the outputs asked for need",
-                               "lower theta_chunk or split the parameter vectors over several calls");
-    if (rc != SEPAIHRD_OK) return rc;
-    // buffers and events of this call alone
-    CallScratch sc(3);
-    double *d_theta = nullptr, *d_values = nullptr, *d_ll = nullptr, *d_inc = nullptr, *d_ess = nullptr, *d_final = nullptr, *d_scratch = nullptr,
-           *d_G = nullptr;
-    int32_t *d_counts = nullptr, *d_status = nullptr;
-    if (!sc.alloc(&d_theta, (size_t)B * ctx->P) || !sc.alloc(&d_values, n_values) || !sc.alloc(&d_ll, (size_t)B) ||
-        !sc.alloc(&d_inc, increments ? n_rows : 0) || !sc.alloc(&d_ess, ess ? n_rows : 0) || !sc.alloc(&d_final, n_final) ||
-        !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) || !sc.alloc(&d_scratch, (scratch_bytes + sizeof(double) - 1) / sizeof(double)) ||
-        !sc.alloc(&d_G, nb.G.size()))
-        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
-    for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
-    HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
-    if (nb.some) HIP_TRY(hipMemcpy(d_G, nb.G.data(), nb.G.size() * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
-    // launches
-    StochEpiArgs da{};
-    da.S = B; da.R = J; da.W = W;
-    da.theta = d_theta; da.values = d_values; da.status = d_status; da.counts = d_counts;
-    (void)hipEventRecord(sc.ev[0], nullptr);
-    if (launch_stoch_epi_decode(dp, da, nullptr) != 0) return refuse(ctx, who, "decode kernel launch failed", SEPAIHRD_E_HIP);
-    (void)hipEventRecord(sc.ev[1], nullptr);
-    ParticleWideArgs a{};
-    a.B = B; a.J = J; a.m = steps_per_interval; a.W = W;
-    a.chunk = chunk;
-    a.seed = seed;
-    a.values = d_values; a.status = d_status; a.loglik = d_ll;
-    a.increments = increments ? d_inc : nullptr; a.ess = ess ? d_ess : nullptr; a.final_state = final_state ? d_final : nullptr;
-    a.scratch = d_scratch;
-    a.host_grid = ctx->host_grid.data();
-    if (nb.some) {
-        a.row_const = d_G;
-        a.k_H = nb.d.k_H; a.k_ICU = nb.d.k_ICU; a.k_D = nb.d.k_D;
-    }
-    const int lrc = launch_particle_filter_wide(dp, a, nullptr);
-    (void)hipEventRecord(sc.ev[2], nullptr);
-    HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
-    if (lrc != 0) return refuse(ctx, who, "filter launch failed", SEPAIHRD_E_HIP);
-    for (int i = 0; i < 2; ++i) {
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, sc.ev[i], sc.ev[i + 1]);
-        ctx->particle_wide_ms[i] = ms;
-    }
-    // fetches
-    ResultFetch res;
-    res.fetch(loglik, d_ll, (size_t)B * sizeof(double));
-    res.fetch(increments, d_inc, n_rows * sizeof(double));
-    res.fetch(ess, d_ess, n_rows * sizeof(double));
-    res.fetch(final_state, d_final, n_final * sizeof(double));
-    res.fetch(model_values, d_values, n_values * sizeof(double));
-    res.fetch(status, d_status, (size_t)B * sizeof(int32_t));
-    res.fetch(n_valid, d_counts, sizeof(int32_t));
-    if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
-    return SEPAIHRD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int sepaihrd_particle_loglik_wide(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, int theta_chunk,
                                   double* loglik, double* increments, double* ess, double* final_state, double* model_values, int32_t* status,
                                   int32_t* n_valid) {
-    return particle_loglik_wide_call(ctx, "particle_loglik_wide", nullptr, theta, B, J, steps_per_interval, seed, theta_chunk, loglik, increments, ess,
-                                     final_state, model_values, status, n_valid);
+    return particle_loglik_call(ctx, "particle_loglik_wide", true, theta_chunk, nullptr, theta, B, J, steps_per_interval, seed, loglik, increments, ess,
+                                final_state, model_values, status, n_valid);
 }
 
 int sepaihrd_particle_loglik_wide_nb(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed,
@@ -1370,8 +1277,8 @@ int sepaihrd_particle_loglik_wide_nb(sepaihrd_ctx* ctx, const double* theta, int
                                      double* final_state, double* model_values, int32_t* status, int32_t* n_valid) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
     if (!dispersion) return refuse(ctx, "particle_loglik_wide_nb", "need dispersion (three entries: k_H, k_ICU, k_D)", SEPAIHRD_E_INVALID_ARG);
-    return particle_loglik_wide_call(ctx, "particle_loglik_wide_nb", dispersion, theta, B, J, steps_per_interval, seed, theta_chunk, loglik,
-                                     increments, ess, final_state, model_values, status, n_valid);
+    return particle_loglik_call(ctx, "particle_loglik_wide_nb", true, theta_chunk, dispersion, theta, B, J, steps_per_interval, seed, loglik,
+                                increments, ess, final_state, model_values, status, n_valid);
 }
 
 int sepaihrd_particle_wide_timing(const sepaihrd_ctx* ctx, double* ms) {

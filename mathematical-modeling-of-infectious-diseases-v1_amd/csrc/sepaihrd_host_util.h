@@ -190,6 +190,39 @@ struct ResultFetch {
     bool ok() const { return good; }
 };
 
+// The device side of a probe (a one-off call that runs a few values through one kernel): in() allocates a buffer and uploads
+// `count` values, out() allocates one.  When ready() the caller launches, then names what to copy back: the first fetch() asks
+// for the launch's error and waits for the kernel.  status() is SEPAIHRD_OK, or SEPAIHRD_E_HIP with "<who>: <HIP's text>" in err
+// (a failed allocation: hipErrorOutOfMemory's).
+struct Probe {
+    CallScratch sc;
+    bool oom = false, good = true, launched = false;
+    template <class T>
+    T* out(size_t count) {
+        T* p = nullptr;
+        if (!oom && good && !sc.alloc(&p, count)) oom = true;
+        return p;
+    }
+    template <class T>
+    T* in(const T* host, size_t count) {
+        T* p = out<T>(count);
+        if (p && hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) good = false;
+        return p;
+    }
+    bool ready() const { return !oom && good; }
+    template <class T>
+    void fetch(T* host, const T* dev, size_t count) {
+        if (!launched) good = good && hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        launched = true;
+        good = good && hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    int status(const char* who, char* err, int errlen) const {
+        if (ready()) return SEPAIHRD_OK;
+        set_err(err, errlen, std::string(who) + ": " + hipGetErrorString(oom ? hipErrorOutOfMemory : hipGetLastError()));
+        return SEPAIHRD_E_HIP;
+    }
+};
+
 // The buffers of a call must fit the device's memory; a larger request is refused before anything is allocated, with
 // "<what> <need> MiB of device memory, the device has <total> MiB: <advice>" as the context's last error.
 template <class Ctx>

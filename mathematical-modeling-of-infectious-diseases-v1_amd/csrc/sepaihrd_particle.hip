@@ -298,26 +298,18 @@ extern "C" int sepaihrd_particle_resample_device(int device, uint64_t seed, uint
         return SEPAIHRD_E_INVALID_ARG;
     }
     if (const int drc = select_device(device, err, errlen)) return drc;
-    CallScratch sc;
-    double *d_logw = nullptr, *d_out2 = nullptr;
-    int32_t* d_anc = nullptr;
-    if (!sc.alloc(&d_logw, (size_t)J) || !sc.alloc(&d_out2, 2) || !sc.alloc(&d_anc, (size_t)J)) {
-        set_err(err, errlen, std::string("particle_resample_device: ") + hipGetErrorString(hipErrorOutOfMemory));
-        return SEPAIHRD_E_HIP;
-    }
+    Probe pr;
+    const double* d_logw = pr.in(logw, (size_t)J);
+    double* d_out2 = pr.out<double>(2);
+    int32_t* d_anc = pr.out<int32_t>((size_t)J);
     double out2[2] = {0.0, 0.0};
-    bool ok = hipMemcpy(d_logw, logw, (size_t)J * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
+    if (pr.ready()) {
         hipLaunchKernelGGL(particle_resample_probe_kernel, dim3(1), dim3(PARTICLE_BLOCK), particle_lds_bytes(0, J), nullptr, seed, b, row, d_logw, J,
                            d_anc, d_out2);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-             hipMemcpy(ancestors, d_anc, (size_t)J * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(out2, d_out2, sizeof(out2), hipMemcpyDeviceToHost) == hipSuccess;
+        pr.fetch(ancestors, d_anc, (size_t)J);
+        pr.fetch(out2, d_out2, 2);
     }
-    if (!ok) {
-        set_err(err, errlen, std::string("particle_resample_device: ") + hipGetErrorString(hipGetLastError()));
-        return SEPAIHRD_E_HIP;
-    }
+    if (const int prc = pr.status("particle_resample_device", err, errlen)) return prc;
     *increment = out2[0];
     *ess = out2[1];
     return SEPAIHRD_OK;
@@ -337,24 +329,14 @@ extern "C" int sepaihrd_particle_nb_term_device(int device, const double* obs, c
         return SEPAIHRD_E_INVALID_ARG;
     }
     if (const int drc = select_device(device, err, errlen)) return drc;
-    CallScratch sc;
-    double *d_obs = nullptr, *d_out = nullptr;
-    int32_t* d_inc = nullptr;
-    if (!sc.alloc(&d_obs, (size_t)count) || !sc.alloc(&d_out, (size_t)count) || !sc.alloc(&d_inc, (size_t)count)) {
-        set_err(err, errlen, std::string("particle_nb_term_device: ") + hipGetErrorString(hipErrorOutOfMemory));
-        return SEPAIHRD_E_HIP;
-    }
-    bool ok = hipMemcpy(d_obs, obs, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_inc, inc, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
+    Probe pr;
+    const double* d_obs = pr.in(obs, (size_t)count);
+    const int32_t* d_inc = pr.in(inc, (size_t)count);
+    double* d_out = pr.out<double>((size_t)count);
+    if (pr.ready()) {
         const unsigned blocks = (unsigned)std::min<size_t>(((size_t)count + 255) / 256, 1024);
         hipLaunchKernelGGL(particle_nb_term_probe_kernel, dim3(blocks), dim3(256), 0, nullptr, d_obs, d_inc, count, k, d_out);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-             hipMemcpy(out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        pr.fetch(out, d_out, (size_t)count);
     }
-    if (!ok) {
-        set_err(err, errlen, std::string("particle_nb_term_device: ") + hipGetErrorString(hipGetLastError()));
-        return SEPAIHRD_E_HIP;
-    }
-    return SEPAIHRD_OK;
+    return pr.status("particle_nb_term_device", err, errlen);
 }

@@ -373,18 +373,14 @@ extern "C" int sepaihrd_particle_wide_resample_device(int device, uint64_t seed,
         return SEPAIHRD_E_INVALID_ARG;
     }
     if (const int drc = select_device(device, err, errlen)) return drc;
-    CallScratch sc;
-    double *d_logw = nullptr, *d_scan = nullptr, *d_out3 = nullptr;  // out3 = {the running sum, increment, ESS}
-    int32_t *d_anc = nullptr, *d_status = nullptr;
-    if (!sc.alloc(&d_logw, (size_t)J) || !sc.alloc(&d_scan, (size_t)4 * J) || !sc.alloc(&d_out3, 3) || !sc.alloc(&d_anc, (size_t)J) ||
-        !sc.alloc(&d_status, 1)) {
-        set_err(err, errlen, std::string("particle_wide_resample_device: ") + hipGetErrorString(hipErrorOutOfMemory));
-        return SEPAIHRD_E_HIP;
-    }
-    double out3[3] = {0.0, 0.0, 0.0};
-    bool ok = hipMemcpy(d_logw, logw, (size_t)J * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemset(d_out3, 0, sizeof(out3)) == hipSuccess && hipMemset(d_status, 0, sizeof(int32_t)) == hipSuccess;
-    if (ok) {
+    Probe pr;
+    double out3[3] = {0.0, 0.0, 0.0};  // {the running sum, increment, ESS}
+    const int32_t valid = 0;
+    const double* d_logw = pr.in(logw, (size_t)J);
+    double *d_scan = pr.out<double>((size_t)4 * J), *d_out3 = pr.in(out3, 3);
+    int32_t* d_anc = pr.out<int32_t>((size_t)J);
+    const int32_t* d_status = pr.in(&valid, 1);
+    if (pr.ready()) {
         WideRow r{};
         r.J = J; r.Tp = 1; r.t = 0;
         r.seed = seed;
@@ -394,14 +390,10 @@ extern "C" int sepaihrd_particle_wide_resample_device(int device, uint64_t seed,
         r.anc = d_anc;
         r.loglik = d_out3; r.increments = d_out3 + 1; r.ess = d_out3 + 2;
         launch_row(r, 1, nullptr);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-             hipMemcpy(ancestors, d_anc, (size_t)J * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(out3, d_out3, sizeof(out3), hipMemcpyDeviceToHost) == hipSuccess;
+        pr.fetch(ancestors, d_anc, (size_t)J);
+        pr.fetch(out3, d_out3, 3);
     }
-    if (!ok) {
-        set_err(err, errlen, std::string("particle_wide_resample_device: ") + hipGetErrorString(hipGetLastError()));
-        return SEPAIHRD_E_HIP;
-    }
+    if (const int prc = pr.status("particle_wide_resample_device", err, errlen)) return prc;
     *increment = out3[1];
     *ess = out3[2];
     return SEPAIHRD_OK;

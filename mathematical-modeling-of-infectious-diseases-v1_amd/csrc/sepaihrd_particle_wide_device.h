@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "sepaihrd_device.h"
+#include "sepaihrd_particle_device.h"
 
 namespace sepaihrd {
 
@@ -30,21 +31,12 @@ constexpr size_t particle_wide_chunk(int lpc, int J, int B, int theta_chunk) {
     return c < (size_t)B ? c : (size_t)B;
 }
 
-struct ParticleWideArgs {
-    int B, J, m, W;           // thetas, particles per theta, steps per output interval, width of a model-values row
+// the arguments of the LDS filter's negative-binomial launch and what the wide form needs beside them.  Host only: the kernels take
+// their own records.  row_const null: the Poisson path, the k are not read.
+struct ParticleWideArgs : ParticleArgsNB {
     size_t chunk;             // thetas per chunk (particle_wide_chunk)
-    uint64_t seed;
-    const double* values;     // [B][W] device: launch_stoch_epi_decode's rows
-    const int32_t* status;    // [B] device: 0, or SEPAIHRD_STATUS_INVALID
-    double* loglik;           // [B] device
-    double* increments;       // [B][Tp] device or null
-    double* ess;              // [B][Tp] device or null
-    double* final_state;      // [B][J][11][n] device or null
     void* scratch;            // device, particle_wide_scratch_bytes(lpc, J, chunk) bytes, 8-byte aligned
     const double* host_grid;  // [T][lpc][4] HOST copy of DevProblem::grid: which rows are weighted is planned from it
-    // the negative-binomial observation model.  row_const null: the Poisson path, the k are not read
-    const double* row_const = nullptr;  // [Tp] device: G of every output time >= 0
-    double k_H = 0.0, k_ICU = 0.0, k_D = 0.0;  // +inf: that series stays Poisson; at least one finite
 };
 // The whole filter as plain launches on the stream, chunk after chunk: a fill of the outputs, then per segment one
 // propagate-and-weight launch and, where the segment ends in a weighted row, one normalise-and-resample launch; the final state

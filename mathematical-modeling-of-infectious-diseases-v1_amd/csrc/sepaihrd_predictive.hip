@@ -149,19 +149,13 @@ extern "C" int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, 
 extern "C" int sepaihrd_poisson_device(int device, uint64_t seed, const double* lambda, int count, double* out, char* err, int errlen) {
     if (!lambda || !out || count < 1) { set_err(err, errlen, "poisson_device: need lambda, out and count >= 1"); return SEPAIHRD_E_INVALID_ARG; }
     if (const int drc = select_device(device, err, errlen)) return drc;
-    CallScratch sc;
-    double *d_lambda = nullptr, *d_out = nullptr;
-    if (!sc.alloc(&d_lambda, (size_t)count) || !sc.alloc(&d_out, (size_t)count)) {
-        set_err(err, errlen, std::string("poisson_device: ") + hipGetErrorString(hipErrorOutOfMemory));
-        return SEPAIHRD_E_HIP;
-    }
-    bool ok = hipMemcpy(d_lambda, lambda, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
+    Probe pr;
+    const double* d_lambda = pr.in(lambda, (size_t)count);
+    double* d_out = pr.out<double>((size_t)count);
+    if (pr.ready()) {
         hipLaunchKernelGGL(poisson_probe_kernel, dim3((unsigned)((count + DRAW_BLOCK - 1) / DRAW_BLOCK)), dim3(DRAW_BLOCK), 0, nullptr, seed,
                            d_lambda, count, d_out);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-             hipMemcpy(out, d_out, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+        pr.fetch(out, d_out, (size_t)count);
     }
-    if (!ok) set_err(err, errlen, std::string("poisson_device: ") + hipGetErrorString(hipGetLastError()));
-    return ok ? SEPAIHRD_OK : SEPAIHRD_E_HIP;
+    return pr.status("poisson_device", err, errlen);
 }

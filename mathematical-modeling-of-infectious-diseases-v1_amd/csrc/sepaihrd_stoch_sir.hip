@@ -242,23 +242,16 @@ int sepaihrd_stoch_sir_binomial_device(int device, uint64_t seed, const int32_t*
         if (n[i] < 0 || std::isnan(p[i])) { set_err(err, errlen, "stoch_sir_binomial_device: n must be >= 0 and p a number"); return SEPAIHRD_E_INVALID_ARG; }
     const int drc = select_device(device, err, errlen);
     if (drc != SEPAIHRD_OK) return drc;
-    CallScratch sc;
-    int32_t *d_n = nullptr, *d_out = nullptr;
-    double* d_p = nullptr;
-    if (!sc.alloc(&d_n, (size_t)count) || !sc.alloc(&d_out, (size_t)count) || !sc.alloc(&d_p, (size_t)count)) {
-        set_err(err, errlen, "stoch_sir_binomial_device: device allocation failed");
-        return SEPAIHRD_E_HIP;
-    }
-    bool ok = hipMemcpy(d_n, n, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_p, p, (size_t)count * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
+    Probe pr;
+    const int32_t* d_n = pr.in(n, (size_t)count);
+    const double* d_p = pr.in(p, (size_t)count);
+    int32_t* d_out = pr.out<int32_t>((size_t)count);
+    if (pr.ready()) {
         hipLaunchKernelGGL(stoch_binomial_probe_kernel, dim3((unsigned)((count + STEP_BLOCK - 1) / STEP_BLOCK)), dim3(STEP_BLOCK), 0, nullptr, seed,
                            d_n, d_p, count, d_out);
-        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-             hipMemcpy(out, d_out, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+        pr.fetch(out, d_out, (size_t)count);
     }
-    if (!ok) { set_err(err, errlen, std::string("stoch_sir_binomial_device: ") + hipGetErrorString(hipGetLastError())); return SEPAIHRD_E_HIP; }
-    return SEPAIHRD_OK;
+    return pr.status("stoch_sir_binomial_device", err, errlen);
 }
 
 }  // extern "C"

@@ -107,15 +107,41 @@ void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan
     }
 }
 
-// the arguments of either form: the validator's verdict (vrc, msg), then what the walk itself needs
-int particle_verdict(const char* who, int vrc, char (&msg)[256], const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs,
-                     const double* model_values, const int32_t* status, const double* loglik, std::string* error) {
-    return stoch_twin::verdict(
+// the observation of (series, output row t >= 0, age), NaN where there is none: the cells of the row constants
+double observed_cell(const ParticleObservations& obs, int n_age, int series, int t, int age) {
+    const double* table = series == 0 ? obs.obs_H : series == 1 ? obs.obs_ICU : obs.obs_D;
+    return t < obs.n_obs ? table[(size_t)t * (size_t)n_age + (size_t)age] : std::numeric_limits<double>::quiet_NaN();
+}
+
+// Every twin after its form's validator (vrc, msg): what the walk itself needs, then the dispersion of a negative-binomial form
+// (nb) with its row constants, then the walk.  A Poisson form passes no dispersion and never meets sepaihrd_particle_nb_validate.
+int particle_twin(const char* who, int vrc, char (&msg)[256], const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan,
+                  const ParticleObservations& obs, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
+                  std::uint64_t seed, bool nb, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
+                  std::string* error) {
+    vrc = stoch_twin::verdict(
         who, vrc, msg,
         {{!model_values || !status || !loglik, "model_values, status and loglik must not be NULL"},
          {stoch_twin::fixed_data_missing(pb), stoch_twin::FIXED_DATA_TEXT},
          {obs.n_obs < 0 || (obs.n_obs > 0 && (!obs.obs_H || !obs.obs_ICU || !obs.obs_D)), "the observations need obs_H, obs_ICU and obs_D"}},
         error);
+    if (vrc != SEPAIHRD_OK) return vrc;
+    pf::Dispersion d = NO_DISPERSION;
+    std::vector<double> G;
+    if (nb) {
+        if (sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            if (error) *error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+        d = pf::Dispersion{dispersion[0], dispersion[1], dispersion[2]};
+        if (pf::any_dispersed(d)) {
+            G.resize((size_t)plan.T_pos);
+            pf::nb_row_constants(d, pb.n_age, plan.T_pos, [&](int series, int t, int age) { return observed_cell(obs, pb.n_age, series, t, age); }, G.data());
+        }
+    }
+    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, d, G.empty() ? nullptr : G.data(), loglik, increments, ess,
+                  final_state);
+    return SEPAIHRD_OK;
 }
 
 }  // namespace
@@ -125,12 +151,9 @@ int hostParticleLoglik(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                        double* ess, double* final_state, std::string* error) {
     char msg[256] = "";
     const stoch_twin::Plan plan = stoch_twin::plan(pb);
-    const int vrc = particle_verdict("particle_loglik",
-                                     sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg,
-                                     pb, obs, model_values, status, loglik, error);
-    if (vrc != SEPAIHRD_OK) return vrc;
-    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, NO_DISPERSION, nullptr, loglik, increments, ess, final_state);
-    return SEPAIHRD_OK;
+    return particle_twin("particle_loglik", sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
+                         msg, pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, false, nullptr, loglik, increments, ess, final_state,
+                         error);
 }
 
 int hostParticleLoglikWide(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
@@ -138,52 +161,19 @@ int hostParticleLoglikWide(const StochasticSEPAIHRDFixedData& pb, const Particle
                            double* ess, double* final_state, std::string* error) {
     char msg[256] = "";
     const stoch_twin::Plan plan = stoch_twin::plan(pb);
-    const int vrc = particle_verdict("particle_loglik_wide",
-                                     sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
-                                     msg, pb, obs, model_values, status, loglik, error);
-    if (vrc != SEPAIHRD_OK) return vrc;
-    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, NO_DISPERSION, nullptr, loglik, increments, ess, final_state);
-    return SEPAIHRD_OK;
+    return particle_twin("particle_loglik_wide",
+                         sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg, pb,
+                         plan, obs, model_values, status, B, J, steps_per_interval, seed, false, nullptr, loglik, increments, ess, final_state, error);
 }
-
-namespace {
-
-// the observation of (series, output row t >= 0, age), NaN where there is none: the cells of the row constants
-double observed_cell(const ParticleObservations& obs, int n_age, int series, int t, int age) {
-    const double* table = series == 0 ? obs.obs_H : series == 1 ? obs.obs_ICU : obs.obs_D;
-    return t < obs.n_obs ? table[(size_t)t * (size_t)n_age + (size_t)age] : std::numeric_limits<double>::quiet_NaN();
-}
-
-// either negative-binomial twin: the dispersion's verdict beside the form's own, the row constants, the walk
-int particle_nb(const char* who, int vrc, char (&msg)[256], const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan,
-                const ParticleObservations& obs, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
-                std::uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state, std::string* error) {
-    vrc = particle_verdict(who, vrc, msg, pb, obs, model_values, status, loglik, error);
-    if (vrc != SEPAIHRD_OK) return vrc;
-    if (sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
-        if (error) *error = msg;
-        return SEPAIHRD_E_INVALID_ARG;
-    }
-    const pf::Dispersion d{dispersion[0], dispersion[1], dispersion[2]};
-    std::vector<double> G;
-    if (pf::any_dispersed(d)) {
-        G.resize((size_t)plan.T_pos);
-        pf::nb_row_constants(d, pb.n_age, plan.T_pos, [&](int series, int t, int age) { return observed_cell(obs, pb.n_age, series, t, age); }, G.data());
-    }
-    particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, d, G.empty() ? nullptr : G.data(), loglik, increments, ess,
-                  final_state);
-    return SEPAIHRD_OK;
-}
-
-}  // namespace
 
 int hostParticleLoglikNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
                          const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, double* loglik,
                          double* increments, double* ess, double* final_state, std::string* error) {
     char msg[256] = "";
     const stoch_twin::Plan plan = stoch_twin::plan(pb);
-    return particle_nb("particle_loglik_nb", sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
-                       msg, pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state, error);
+    return particle_twin("particle_loglik_nb", sepaihrd_particle_validate(B, J, steps_per_interval, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)),
+                         msg, pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, true, dispersion, loglik, increments, ess, final_state,
+                         error);
 }
 
 int hostParticleLoglikWideNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
@@ -191,9 +181,9 @@ int hostParticleLoglikWideNB(const StochasticSEPAIHRDFixedData& pb, const Partic
                              double* increments, double* ess, double* final_state, std::string* error) {
     char msg[256] = "";
     const stoch_twin::Plan plan = stoch_twin::plan(pb);
-    return particle_nb("particle_loglik_wide_nb",
-                       sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg, pb,
-                       plan, obs, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state, error);
+    return particle_twin("particle_loglik_wide_nb",
+                         sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg, pb,
+                         plan, obs, model_values, status, B, J, steps_per_interval, seed, true, dispersion, loglik, increments, ess, final_state, error);
 }
 
 int hostParticleNBRowConstants(const ParticleObservations& obs, int n_age, int T_pos, const double* dispersion, double* G, std::string* error) {

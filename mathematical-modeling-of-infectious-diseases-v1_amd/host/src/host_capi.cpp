@@ -1542,19 +1542,22 @@ int host_stochastic_manager_values(void* hv, int mode, const double* theta, doub
 // ---- bootstrap particle filter of the stochastic SEPAIHRD model (HipParticleFilter) ----
 // hostParticleLoglik (no device): shapes as sepaihrd_particle_loglik; obs_* [n_obs][n_age], the rows of the output times >= 0
 namespace {
-using ParticleTwin = int (*)(const StochasticSEPAIHRDFixedData&, const ParticleObservations&, const double*, const int32_t*, int, int, int, std::uint64_t,
-                             double*, double*, double*, double*, std::string*);
-int particle_twin_from_values(ParticleTwin twin, int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+// the twin of one form: wide or not, negative-binomial (nb, with dispersion [3] = {k_H, k_ICU, k_D}) or Poisson
+int particle_twin_from_values(bool wide, bool nb, int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
                               const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
                               const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
-                              uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
+                              uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
+                              char* err, int errlen) {
     StochasticSEPAIHRDFixedData fd;
     fd.n_age = n_age; fd.n_times = n_times; fd.n_beta = n_beta; fd.n_kappa = n_kappa;
     fd.times = times; fd.N = N; fd.M = M; fd.beta_end_times = beta_end_times; fd.kappa_end_times = kappa_end_times;
     ParticleObservations ob;
     ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
     std::string error;
-    const int rc = twin(fd, ob, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state, &error);
+    const int rc = nb ? (wide ? hostParticleLoglikWideNB : hostParticleLoglikNB)(fd, ob, model_values, status, B, J, steps_per_interval, seed, dispersion,
+                                                                                loglik, increments, ess, final_state, &error)
+                      : (wide ? hostParticleLoglikWide : hostParticleLoglik)(fd, ob, model_values, status, B, J, steps_per_interval, seed, loglik,
+                                                                            increments, ess, final_state, &error);
     if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
     return rc;
 }
@@ -1564,8 +1567,8 @@ int host_particle_from_values(int n_age, int n_times, int n_beta, int n_kappa, c
                               const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
                               const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
                               uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
-    return particle_twin_from_values(hostParticleLoglik, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H,
-                                     obs_ICU, obs_D, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state, err,
+    return particle_twin_from_values(false, false, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
+                                     obs_D, model_values, status, B, J, steps_per_interval, seed, nullptr, loglik, increments, ess, final_state, err,
                                      errlen);
 }
 
@@ -1574,39 +1577,20 @@ int host_particle_wide_from_values(int n_age, int n_times, int n_beta, int n_kap
                                    const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
                                    const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
                                    uint64_t seed, double* loglik, double* increments, double* ess, double* final_state, char* err, int errlen) {
-    return particle_twin_from_values(hostParticleLoglikWide, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs,
-                                     obs_H, obs_ICU, obs_D, model_values, status, B, J, steps_per_interval, seed, loglik, increments, ess, final_state,
-                                     err, errlen);
+    return particle_twin_from_values(true, false, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
+                                     obs_D, model_values, status, B, J, steps_per_interval, seed, nullptr, loglik, increments, ess, final_state, err,
+                                     errlen);
 }
 
 // hostParticleLoglikNB / hostParticleLoglikWideNB (no device): the same shapes with dispersion [3] = {k_H, k_ICU, k_D}
-namespace {
-int particle_nb_twin_from_values(bool wide, int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
-                                 const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
-                                 const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
-                                 uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
-                                 char* err, int errlen) {
-    StochasticSEPAIHRDFixedData fd;
-    fd.n_age = n_age; fd.n_times = n_times; fd.n_beta = n_beta; fd.n_kappa = n_kappa;
-    fd.times = times; fd.N = N; fd.M = M; fd.beta_end_times = beta_end_times; fd.kappa_end_times = kappa_end_times;
-    ParticleObservations ob;
-    ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
-    std::string error;
-    const int rc = (wide ? hostParticleLoglikWideNB : hostParticleLoglikNB)(fd, ob, model_values, status, B, J, steps_per_interval, seed, dispersion,
-                                                                           loglik, increments, ess, final_state, &error);
-    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
-    return rc;
-}
-}  // namespace
-
 int host_particle_nb_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
                                  const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H, const double* obs_ICU,
                                  const double* obs_D, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
                                  uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
                                  char* err, int errlen) {
-    return particle_nb_twin_from_values(false, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
-                                        obs_D, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state,
-                                        err, errlen);
+    return particle_twin_from_values(false, true, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
+                                     obs_D, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state,
+                                     err, errlen);
 }
 
 int host_particle_wide_nb_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
@@ -1614,9 +1598,9 @@ int host_particle_wide_nb_from_values(int n_age, int n_times, int n_beta, int n_
                                       const double* obs_ICU, const double* obs_D, const double* model_values, const int32_t* status, int B, int J,
                                       int steps_per_interval, uint64_t seed, const double* dispersion, double* loglik, double* increments, double* ess,
                                       double* final_state, char* err, int errlen) {
-    return particle_nb_twin_from_values(true, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
-                                        obs_D, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state,
-                                        err, errlen);
+    return particle_twin_from_values(true, true, n_age, n_times, n_beta, n_kappa, times, N, M, beta_end_times, kappa_end_times, n_obs, obs_H, obs_ICU,
+                                     obs_D, model_values, status, B, J, steps_per_interval, seed, dispersion, loglik, increments, ess, final_state,
+                                     err, errlen);
 }
 
 // the twin of sepaihrd_particle_nb_term_device (no device): out[i] = nb_term(obs[i], inc[i], k)

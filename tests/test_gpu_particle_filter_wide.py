@@ -240,6 +240,35 @@ def test_argument_errors_leave_the_outputs_untouched(mm, ref_fixture):
         hip.particle_loglik(theta, max_particles(mm, n) + 1, 2, SEED)
 
 
+def test_each_form_keeps_its_own_timing(mm, ref_fixture):
+    """the LDS and the wide calls share one body: a call of one form, Poisson or dispersed, writes that form's pair of times and
+    leaves the other form's exactly as it was"""
+    from test_gpu_particle_nb import twin_of  # (that module imports this one)
+    n, m, J = 3, 2, 17
+    pb = problem(mm, ref_fixture, n, m)
+    hip = objective(mm, pb)
+    theta = three_thetas(mm, pb)
+    assert not hip.particle_timing().any() and not hip.particle_wide_timing().any()
+    for disp in (None, (1.0, np.inf, 5.0)):
+        before = hip.particle_timing(), hip.particle_wide_timing()
+        narrow = hip.particle_loglik(theta, J, m, SEED, want_final=True, want_values=True, dispersion=disp)
+        after_narrow = hip.particle_timing(), hip.particle_wide_timing()
+        wide = hip.particle_loglik_wide(theta, J, m, SEED, want_final=True, want_values=True, dispersion=disp)
+        after_wide = hip.particle_timing(), hip.particle_wide_timing()
+        print(f"dispersion {disp}: before {before}, after the LDS call {after_narrow}, after the wide call {after_wide}")
+        assert np.array_equal(after_narrow[1], before[1]), disp
+        if disp is None:
+            assert list(after_narrow[1]) == [0.0, 0.0]
+        assert np.array_equal(after_wide[0], after_narrow[0]), disp
+        assert np.isfinite(after_narrow[0]).all() and (after_narrow[0] > 0).all(), disp
+        assert np.isfinite(after_wide[1]).all() and (after_wide[1] > 0).all(), disp
+        if disp is not None:
+            for got, is_wide in ((narrow, False), (wide, True)):
+                twin = twin_of(mm, pb, got, J, m, disp, is_wide)
+                for key in KEYS:
+                    assert np.array_equal(got[key], twin[key], equal_nan=True), (is_wide, key)
+
+
 def test_cpp_adapter_goes_wide_above_the_limit(mm, ref_fixture):
     """HipParticleLikelihood::calculateBatch with more particles than the LDS kernel takes is sepaihrd_particle_loglik_wide at
     seed0 + (calls so far)"""
