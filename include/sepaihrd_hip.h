@@ -1025,6 +1025,40 @@ int sepaihrd_particle_nb_row_constants(const sepaihrd_ctx *ctx, const double dis
 int sepaihrd_particle_nb_term_device(int device, const double *obs, const int32_t *inc, int count, double k, double *out,
                                      char *err, int errlen);
 
+/* ---- filtered state means and quantile bands of every output row (additive; SEPAIHRD_ABI_VERSION stays) ------------------------
+ * The wide form of the filter with the other product of a particle filter: the filtering distribution of the latent state at
+ * every output row k in 0 .. n_times - 1, run-up rows included, summarised over the J particles the next interval starts from
+ * (after a weighted row slot i holds the state of its ancestor, so the set is equally weighted; after an unweighted row the
+ * particles as propagated; row n_times - 1 is the set sepaihrd_particle_loglik_wide's final_state holds).  For each of the 11
+ * counts there are n_age + 1 series: one per age class and, at index n_age, the particle's sum over its age classes.
+ *   state_mean      [B][n_times][11][n_age + 1]            (double)(the sum of the J counts in 64-bit integers) / (double)J
+ *   state_quantiles [B][n_times][11][n_age + 1][n_probs]   the ensemble's rule over the J values sorted ascending: pos = p (J - 1),
+ *                   idx = (size_t)pos, frac = pos - idx, v[idx] (1 - frac) + v[idx + 1] frac where idx + 1 < J, else v[idx];
+ *                   NULL: not wanted
+ * csrc/sepaihrd_particle_states.inc states the rule, one text for the device and the host twin (hostParticleStates, bit for bit).
+ * The filter is untouched: loglik, increments, ess, model_values, status and n_valid are those of sepaihrd_particle_loglik_wide
+ * (dispersion NULL) or sepaihrd_particle_loglik_wide_nb (dispersion [3]), bit for bit; J is 1 to 65 536 for every n_age.  An
+ * invalid theta has NaN in every row of both tables.  theta_chunk as in the wide form; the scratch of a chunk is the wide form's
+ * plus a row table of 88 (n_age + 1) pad bytes per theta, pad = the power of two >= max(J, 64).
+ * SEPAIHRD_E_INVALID_ARG, before the device is touched and with the outputs untouched: what sepaihrd_particle_states_validate
+ * refuses, a dispersion sepaihrd_particle_nb_validate refuses, a NULL theta, loglik or state_mean, state_quantiles with
+ * n_probs == 0. */
+int sepaihrd_particle_filter_states(sepaihrd_ctx *ctx, const double *theta, int B, int J, int steps_per_interval, uint64_t seed,
+                                    int theta_chunk, const double *dispersion /* [3] or NULL: Poisson */,
+                                    const double *probs, int n_probs,
+                                    double *loglik, double *increments, double *ess,
+                                    double *state_mean      /* [B][T][11][n_age+1] */,
+                                    double *state_quantiles /* [B][T][11][n_age+1][n_probs] or NULL */,
+                                    double *model_values, int32_t *status, int32_t *n_valid);
+/* Host only: the rules of sepaihrd_particle_wide_validate and, with a message that names this entry, n_probs outside [0, 64],
+ * n_probs > 0 with NULL probs, a probability that is NaN or outside [0, 1]. */
+int sepaihrd_particle_states_validate(int B, int J, int steps_per_interval, int theta_chunk, int n_times, int T_pos, int n_age,
+                                      const double *probs, int n_probs, char *err, int errlen);
+/* Device time of the context's last sepaihrd_particle_filter_states call in milliseconds, ms[3]: decode; all launches of the
+ * filter and the summaries; of these the summaries' launches of the first chunk of parameter vectors -- the whole share of the
+ * summaries where the call has one chunk (NaN on a grid of more than 1024 output rows). */
+int sepaihrd_particle_states_timing(const sepaihrd_ctx *ctx, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

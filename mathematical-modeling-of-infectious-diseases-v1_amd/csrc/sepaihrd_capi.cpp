@@ -24,6 +24,7 @@
 #include "sepaihrd_segments.h"
 #include "sepaihrd_particle_device.h"
 #include "sepaihrd_particle_nb_host.h"
+#include "sepaihrd_particle_states_device.h"
 #include "sepaihrd_particle_wide_device.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
@@ -108,6 +109,8 @@ struct sepaihrd_ctx {
     // that call plans its launches (which output rows have a usable observation)
     double particle_wide_ms[2] = {0.0, 0.0};
     std::vector<double> host_grid;
+    // the last sepaihrd_particle_filter_states call: decode, all launches, of these the summaries of the first chunk (ms)
+    double particle_states_ms[3] = {0.0, 0.0, 0.0};
     Stream own_stream;  // sepaihrd_eval_batch_begin / _end; last: see above
 };
 
@@ -1144,11 +1147,19 @@ int nb_plan(sepaihrd_ctx* ctx, const double* dispersion, NbPlan& plan) {
 // The four forms of the particle-filter call, one body: the LDS kernel (sepaihrd_particle_loglik, _nb) or, with `wide`, the
 // launches over particles in device memory (sepaihrd_particle_loglik_wide, _wide_nb; theta_chunk is theirs alone); dispersion
 // NULL for the Poisson forms.  With no dispersed series no table is formed and the Poisson kernels run, launch for launch.
-// Each form keeps its own validator, memory rule and timing slot.
+// Each form keeps its own validator, memory rule and timing slot.  A further form, sepaihrd_particle_filter_states (`states`
+// given; wide): the wide launches with every output row a segment and the row summaries of DESIGN.md section 6n between them.
+struct StatesOutputs {
+    const double* probs;
+    int n_probs;
+    double *state_mean, *state_quantiles;
+};
 int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, bool wide, int theta_chunk, const double* dispersion, const double* theta, int B, int J,
                          int steps_per_interval, uint64_t seed, double* loglik, double* increments, double* ess, double* final_state,
-                         double* model_values, int32_t* status, int32_t* n_valid) {
+                         double* model_values, int32_t* status, int32_t* n_valid, const StatesOutputs* states = nullptr) {
     if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    if (states != nullptr && (!theta || !loglik || !states->state_mean))
+        return refuse(ctx, who, "need theta, loglik and state_mean", SEPAIHRD_E_INVALID_ARG);
     if (!theta || !loglik) return refuse(ctx, who, "need theta and loglik", SEPAIHRD_E_INVALID_ARG);
     int rc = ensemble_preflight(ctx, who, true, nullptr, CHECK_PENDING);
     if (rc != SEPAIHRD_OK) return rc;
@@ -1157,10 +1168,14 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, bool wide, int thet
     if (dp.n > 16 || dp.lpc > 16) return refuse(ctx, who, "built for at most 16 age classes", SEPAIHRD_E_UNSUPPORTED);
     char msg[256] = "";
     rc = validated(ctx,
-                   wide ? sepaihrd_particle_wide_validate(B, J, steps_per_interval, theta_chunk, dp.T, Tp, dp.n, msg, (int)sizeof(msg))
-                        : sepaihrd_particle_validate(B, J, steps_per_interval, dp.T, Tp, dp.n, msg, (int)sizeof(msg)),
+                   states ? sepaihrd_particle_states_validate(B, J, steps_per_interval, theta_chunk, dp.T, Tp, dp.n, states->probs, states->n_probs, msg,
+                                                              (int)sizeof(msg))
+                   : wide ? sepaihrd_particle_wide_validate(B, J, steps_per_interval, theta_chunk, dp.T, Tp, dp.n, msg, (int)sizeof(msg))
+                          : sepaihrd_particle_validate(B, J, steps_per_interval, dp.T, Tp, dp.n, msg, (int)sizeof(msg)),
                    msg);
     if (rc != SEPAIHRD_OK) return rc;
+    if (states != nullptr && states->state_quantiles != nullptr && states->n_probs == 0)
+        return refuse(ctx, who, "state_quantiles needs n_probs > 0", SEPAIHRD_E_INVALID_ARG);
     NbPlan nb;
     if (dispersion != nullptr) {
         rc = nb_plan(ctx, dispersion, nb);
@@ -1173,14 +1188,23 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, bool wide, int thet
     const int W = sepaihrd_stochastic_values_width(dp.n, dp.nb, dp.nk);
     const size_t n_values = (size_t)B * W, n_rows = (size_t)B * Tp;
     const size_t n_final = final_state ? (size_t)B * J * NUM_COMP * dp.n : 0;
-    const size_t chunk = wide ? particle_wide_chunk(dp.lpc, J, B, theta_chunk) : 0;
+    const size_t chunk = states ? particle_states_chunk(dp.lpc, dp.n, J, B, theta_chunk) : wide ? particle_wide_chunk(dp.lpc, J, B, theta_chunk) : 0;
     const size_t scratch_bytes = wide ? particle_wide_scratch_bytes(dp.lpc, J, chunk) : 0;  // the particles: the LDS form keeps them on chip
-    const size_t need_bytes = scratch_bytes + sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size()) +
+    // the summaries: the row table of a chunk, the probabilities and the two outputs
+    const size_t n_table = states ? particle_states_table_doubles(dp.n, J, chunk) : 0;
+    const size_t n_mean = states ? (size_t)B * dp.T * NUM_COMP * (dp.n + 1) : 0;
+    const size_t n_quant = states && states->state_quantiles ? n_mean * (size_t)states->n_probs : 0;
+    const size_t n_probs = states ? (size_t)states->n_probs : 0;
+    const size_t need_bytes = scratch_bytes +
+                              sizeof(double) * ((size_t)B * ctx->P + n_values + (size_t)B + 2 * n_rows + n_final + nb.G.size() + n_table + n_mean + n_quant +
+                                                n_probs) +
                               sizeof(int32_t) * ((size_t)B + 2);
     const std::string what =
-        wide ? "particle_loglik_wide: the particles of " + std::to_string(chunk) + " parameter vectors at a time, the model values of B = " +
-                   std::to_string(B) + " and the outputs asked for need"
-             : "particle_loglik: the model values of B = " + std::to_string(B) + " parameter vectors and the outputs asked for need";
+        states ? "particle_filter_states: the particles and the row table of " + std::to_string(chunk) +
+                     " parameter vectors at a time, the model values of B = " + std::to_string(B) + " and the outputs asked for need"
+        : wide ? "particle_loglik_wide: the particles of " + std::to_string(chunk) + " parameter vectors at a time, the model values of B = " +
+                     std::to_string(B) + " and the outputs asked for need"
+               : "particle_loglik: the model values of B = " + std::to_string(B) + " parameter vectors and the outputs asked for need";
     rc = require_device_memory(ctx, need_bytes, what,
                                wide ? "lower theta_chunk or split the parameter vectors over several calls" : "split the parameter vectors over several calls");
     if (rc != SEPAIHRD_OK) return rc;
@@ -1194,8 +1218,18 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, bool wide, int thet
         !sc.alloc(&d_counts, 2) || !sc.alloc(&d_status, (size_t)B) ||
         (wide && !sc.alloc(&d_scratch, (scratch_bytes + sizeof(double) - 1) / sizeof(double))) || !sc.alloc(&d_G, nb.G.size()))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
+    double *d_table = nullptr, *d_mean = nullptr, *d_quant = nullptr, *d_probs = nullptr;
+    if (!sc.alloc(&d_table, n_table) || !sc.alloc(&d_mean, n_mean) || !sc.alloc(&d_quant, n_quant) || !sc.alloc(&d_probs, n_probs))
+        return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
+    // a pair of events around every row's summary of the first chunk, where the grid has few enough rows: the third entry of the
+    // timing
+    const size_t n_summaries = states ? (size_t)dp.T : 0;
+    if (n_summaries > 0 && n_summaries <= 1024) sc.ev.resize(3 + 2 * n_summaries);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
+    std::vector<void*> summary_ev;
+    for (size_t i = 3; i < sc.ev.size(); ++i) summary_ev.push_back(static_cast<hipEvent_t>(sc.ev[i]));
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)B * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    if (n_probs) HIP_TRY(hipMemcpy(d_probs, states->probs, n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     if (nb.some) HIP_TRY(hipMemcpy(d_G, nb.G.data(), nb.G.size() * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     // launches
     StochEpiArgs da{};
@@ -1214,15 +1248,35 @@ int particle_loglik_call(sepaihrd_ctx* ctx, const char* who, bool wide, int thet
         a.row_const = d_G;
     }
     a.chunk = chunk; a.scratch = d_scratch; a.host_grid = ctx->host_grid.data();  // read by the wide launch alone
+    ParticleStatesArgs sa{};
+    if (states != nullptr) {
+        sa.n_probs = states->n_probs; sa.probs = d_probs; sa.table = d_table;
+        sa.state_mean = d_mean; sa.state_quantiles = states->state_quantiles ? d_quant : nullptr;
+        sa.ev = summary_ev.empty() ? nullptr : summary_ev.data(); sa.n_ev = summary_ev.size();
+        a.states = &sa;
+    }
     const int lrc = wide      ? launch_particle_filter_wide(dp, a, nullptr)
                     : nb.some ? launch_particle_filter_nb(dp, a, nullptr)
                               : launch_particle_filter(dp, a, nullptr);
     (void)hipEventRecord(sc.ev[2], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
     if (lrc != 0) return refuse(ctx, who, wide ? "filter launch failed" : "filter kernel launch failed", SEPAIHRD_E_HIP);
-    elapsed_ms(sc.ev, wide ? ctx->particle_wide_ms : ctx->particle_ms, 2);
+    elapsed_ms(sc.ev, states ? ctx->particle_states_ms : wide ? ctx->particle_wide_ms : ctx->particle_ms, 2);
+    if (states != nullptr) {  // the summaries' share of the first chunk's launches; NaN where the grid has too many rows for the events
+        double summary = sa.used_ev == 2 * n_summaries && n_summaries > 0 ? 0.0 : std::numeric_limits<double>::quiet_NaN();
+        for (size_t i = 0; i + 1 < sa.used_ev; i += 2) {
+            float t = 0.0f;
+            (void)hipEventElapsedTime(&t, static_cast<hipEvent_t>(summary_ev[i]), static_cast<hipEvent_t>(summary_ev[i + 1]));
+            summary += t;
+        }
+        ctx->particle_states_ms[2] = summary;
+    }
     // fetches
     ResultFetch res;
+    if (states != nullptr) {
+        res.fetch(states->state_mean, d_mean, n_mean * sizeof(double));
+        res.fetch(states->state_quantiles, d_quant, n_quant * sizeof(double));
+    }
     res.fetch(loglik, d_ll, (size_t)B * sizeof(double));
     res.fetch(increments, d_inc, n_rows * sizeof(double));
     res.fetch(ess, d_ess, n_rows * sizeof(double));
@@ -1284,6 +1338,20 @@ int sepaihrd_particle_loglik_wide_nb(sepaihrd_ctx* ctx, const double* theta, int
 int sepaihrd_particle_wide_timing(const sepaihrd_ctx* ctx, double* ms) {
     if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
     for (int i = 0; i < 2; ++i) ms[i] = ctx->particle_wide_ms[i];
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_particle_filter_states(sepaihrd_ctx* ctx, const double* theta, int B, int J, int steps_per_interval, uint64_t seed, int theta_chunk,
+                                    const double* dispersion, const double* probs, int n_probs, double* loglik, double* increments, double* ess,
+                                    double* state_mean, double* state_quantiles, double* model_values, int32_t* status, int32_t* n_valid) {
+    const StatesOutputs states{probs, n_probs, state_mean, state_quantiles};
+    return particle_loglik_call(ctx, "particle_filter_states", true, theta_chunk, dispersion, theta, B, J, steps_per_interval, seed, loglik, increments,
+                                ess, nullptr, model_values, status, n_valid, &states);
+}
+
+int sepaihrd_particle_states_timing(const sepaihrd_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return SEPAIHRD_E_INVALID_ARG;
+    for (int i = 0; i < 3; ++i) ms[i] = ctx->particle_states_ms[i];
     return SEPAIHRD_OK;
 }
 

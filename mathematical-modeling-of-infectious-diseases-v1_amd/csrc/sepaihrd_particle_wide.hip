@@ -18,6 +18,7 @@
 #include "sepaihrd_hip.h"
 #include "sepaihrd_host_util.h"
 #include "sepaihrd_particle.inc"
+#include "sepaihrd_particle_states_device.h"
 #include "sepaihrd_particle_wide_device.h"
 #include "sepaihrd_stoch_sepaihrd_device.h"
 
@@ -100,7 +101,7 @@ struct WideSegmentNB : WideSegment {
 };
 
 __device__ size_t state_index(int Bc, int J, int lpc, int copy, int bl, int c, int p, int age) {
-    return ((((size_t)copy * Bc + bl) * epi::NUM_COMP + c) * (size_t)J + p) * lpc + age;
+    return particle_wide_state_index(Bc, J, lpc, copy, bl, c, p, age);
 }
 
 // One lane per (theta of the chunk, particle, age class), slots along bl J + p, the lpc lanes of a particle adjacent: in every
@@ -294,6 +295,7 @@ int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a,
     const size_t final_doubles = (size_t)J * epi::NUM_COMP * pb.n;
     const bool nb = a.row_const != nullptr;
     if (nb && !pf::any_dispersed(pf::Dispersion{a.k_H, a.k_ICU, a.k_D})) return -4;
+    if (a.states != nullptr && prepare_particle_states(J) != 0) return -3;
     WideFill f{J, Tp, pb.n, a.status, a.loglik, a.increments, a.ess, a.final_state};
     hipLaunchKernelGGL(wide_fill_kernel, dim3((unsigned)a.B, WIDE_FILL_SLICES), dim3(WIDE_FILL_BLOCK), 0, st, f);
     for (size_t b0 = 0; b0 < (size_t)a.B; b0 += a.chunk) {
@@ -321,7 +323,7 @@ int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a,
         int cur = 0, gather = 0;
         for (int k = 0; k < T;) {
             int k_last = k;
-            while (!weighted[(size_t)k_last] && k_last + 1 < T) ++k_last;
+            while (a.states == nullptr && !weighted[(size_t)k_last] && k_last + 1 < T) ++k_last;
             s.k_first = k; s.k_last = k_last;
             s.cur = cur; s.gather = gather; s.weighted = weighted[(size_t)k_last];
             if (nb)
@@ -337,6 +339,10 @@ int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a,
                 gather = 1;
             }
             if (hipGetLastError() != hipSuccess) return -3;
+            if (a.states != nullptr) {  // k_last == k: the row's cloud is copy cur, through anc where the row was resampled
+                const int src = launch_particle_states_row(pb, *a.states, Bc, b0, J, k, cur, gather, sc.state, sc.anc, s.status, st);
+                if (src != 0) return src;
+            }
             k = k_last + 1;
         }
         if (a.final_state != nullptr) {

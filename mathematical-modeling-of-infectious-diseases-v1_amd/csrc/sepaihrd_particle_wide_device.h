@@ -31,16 +31,26 @@ constexpr size_t particle_wide_chunk(int lpc, int J, int B, int theta_chunk) {
     return c < (size_t)B ? c : (size_t)B;
 }
 
+// where count c of (theta bl of a chunk of Bc, particle p, age) lies in copy `copy` of the state: int32 [copy][b][11][J][lpc]
+constexpr size_t particle_wide_state_index(int Bc, int J, int lpc, int copy, int bl, int c, int p, int age) {
+    return ((((size_t)copy * Bc + bl) * NUM_COMP + c) * (size_t)J + p) * lpc + age;
+}
+
+struct ParticleStatesArgs;  // csrc/sepaihrd_particle_states_device.h
+
 // the arguments of the LDS filter's negative-binomial launch and what the wide form needs beside them.  Host only: the kernels take
 // their own records.  row_const null: the Poisson path, the k are not read.
 struct ParticleWideArgs : ParticleArgsNB {
     size_t chunk;             // thetas per chunk (particle_wide_chunk)
     void* scratch;            // device, particle_wide_scratch_bytes(lpc, J, chunk) bytes, 8-byte aligned
     const double* host_grid;  // [T][lpc][4] HOST copy of DevProblem::grid: which rows are weighted is planned from it
+    // sepaihrd_particle_filter_states alone, null in every other call: every output row ends a segment and
+    // launch_particle_states_row summarises the row's cloud
+    ParticleStatesArgs* states;
 };
 // The whole filter as plain launches on the stream, chunk after chunk: a fill of the outputs, then per segment one
 // propagate-and-weight launch and, where the segment ends in a weighted row, one normalise-and-resample launch; the final state
-// last.  No synchronisation inside.  0, -3 (a launch failed) or -4 (arguments).
+// last.  With ParticleWideArgs::states a segment is one row and the row's summary follows its launches.  No synchronisation inside.  0, -3 (a launch failed) or -4 (arguments).
 int launch_particle_filter_wide(const DevProblem& pb, const ParticleWideArgs& a, void* stream);
 
 }  // namespace sepaihrd

@@ -224,6 +224,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_particle_wide_resample_device",
     "sepaihrd_particle_loglik_nb", "sepaihrd_particle_loglik_wide_nb", "sepaihrd_particle_nb_validate", "sepaihrd_particle_nb_row_constants",
     "sepaihrd_particle_nb_term_device",
+    "sepaihrd_particle_filter_states", "sepaihrd_particle_states_validate", "sepaihrd_particle_states_timing",
 )
 
 _lib = None
@@ -374,6 +375,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_particle_nb_validate.argtypes = [vp, C.c_char_p, C.c_int]
     lib.sepaihrd_particle_nb_row_constants.argtypes = [vp, vp, vp]
     lib.sepaihrd_particle_nb_term_device.argtypes = [C.c_int, vp, vp, C.c_int, C.c_double, vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_filter_states.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, vp, vp, C.c_int] + [vp] * 8
+    lib.sepaihrd_particle_states_validate.argtypes = [C.c_int] * 7 + [vp, C.c_int, C.c_char_p, C.c_int]
+    lib.sepaihrd_particle_states_timing.argtypes = [vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -713,6 +717,51 @@ class HipObjective:
             if arr is not None:
                 out[key] = arr
         return out
+
+    def particle_filter_states(self, theta, J: int, steps_per_interval: int, seed: int, probs=(), dispersion=None, theta_chunk: int = 0,
+                               want_increments: bool = True, want_ess: bool = True, want_quantiles: bool = True,
+                               want_values: bool = False) -> dict:
+        """The filtered state means and quantile bands of every output row (sepaihrd_particle_filter_states): the wide form of
+        the filter, J up to 65 536, summarised after every row over the J particles the next interval starts from.  state_mean
+        [B][T][11][n + 1] (index n: the age total), state_quantiles [B][T][11][n + 1][len(probs)] (where probs is not empty and
+        want_quantiles), and loglik, increments, ess, status, n_valid, model_values as particle_loglik_wide gives them, bit for
+        bit.  dispersion as in particle_loglik."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        B, n, T = th.shape[0], self.pb.n, len(self.pb.times)
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        W = self.lib.sepaihrd_stochastic_values_width(n, len(self.pb.beta_end_times), len(self.pb.kappa_end_times))
+        disp = None
+        if dispersion is not None:
+            disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+            if disp.size != 3:
+                raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+        loglik = np.empty(B)
+        inc = np.empty((B, Tp)) if want_increments else None
+        ess = np.empty((B, Tp)) if want_ess else None
+        mean = np.empty((B, T, 11, n + 1))
+        quant = np.empty((B, T, 11, n + 1, pr.size)) if (want_quantiles and pr.size) else None
+        values = np.empty((B, W)) if want_values else None
+        status = np.empty(B, dtype=np.int32)
+        nv = C.c_int32(0)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.sepaihrd_particle_filter_states(self.ctx, th.ctypes.data, B, int(J), int(steps_per_interval),
+                                                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(theta_chunk), ptr(disp),
+                                                             pr.ctypes.data if pr.size else None, pr.size, loglik.ctypes.data, ptr(inc), ptr(ess),
+                                                             mean.ctypes.data, ptr(quant), ptr(values), status.ctypes.data, C.byref(nv)),
+                    "particle_filter_states")
+        out = {"loglik": loglik, "status": status, "n_valid": nv.value, "state_mean": mean}
+        for key, arr in (("increments", inc), ("ess", ess), ("state_quantiles", quant), ("model_values", values)):
+            if arr is not None:
+                out[key] = arr
+        return out
+
+    def particle_states_timing(self) -> np.ndarray:
+        """Device time of the last particle_filter_states call in ms: decode; all launches; of these the summaries of the first
+        chunk of thetas, the whole share where the call has one chunk (sepaihrd_particle_states_timing)"""
+        ms = np.zeros(3)
+        self._check(self.lib.sepaihrd_particle_states_timing(self.ctx, ms.ctypes.data), "particle_states_timing")
+        return ms
 
     def particle_nb_row_constants(self, dispersion) -> np.ndarray:
         """sepaihrd_particle_nb_row_constants (host only): G [T_pos], the row constants a call with this dispersion uploads"""

@@ -48,6 +48,14 @@ int hostParticleLoglikNB(const StochasticSEPAIHRDFixedData& pb, const ParticleOb
 int hostParticleLoglikWideNB(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values,
                              const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, double* loglik,
                              double* increments, double* ess, double* final_state, std::string* error = nullptr);
+// The twin of sepaihrd_particle_filter_states: the same walk (dispersion NULL: Poisson) with the per-row summaries of
+// csrc/sepaihrd_particle_states.inc taken from every row's cloud by std::sort and the ensemble's quantile expression.
+// state_mean [B][n_times][11][n_age + 1], state_quantiles [B][n_times][11][n_age + 1][n_probs] (nullable), bit for bit; loglik,
+// increments and ess are hostParticleLoglikWide's / hostParticleLoglikWideNB's.  SEPAIHRD_E_INVALID_ARG with
+// sepaihrd_particle_states_validate's or sepaihrd_particle_nb_validate's message.
+int hostParticleStates(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values, const int32_t* status,
+                       int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, const double* probs, int n_probs,
+                       double* loglik, double* increments, double* ess, double* state_mean, double* state_quantiles, std::string* error = nullptr);
 // the row constants G [T_pos] such a call adds (the twin of sepaihrd_particle_nb_row_constants) and the twin of
 // sepaihrd_particle_nb_term_device: out[i] = nb_term(obs[i], inc[i], k)
 int hostParticleNBRowConstants(const ParticleObservations& obs, int n_age, int T_pos, const double* dispersion, double* G, std::string* error = nullptr);
@@ -76,6 +84,12 @@ public:
     const std::vector<std::string>& getParameterNames() const override { return pm_.getParameterNames(); }
     void calculateBatch(const double* thetas, int B, double* out, int* status = nullptr) const override;
     std::uint64_t calls() const { return calls_; }
+    // The filtered state means [B][n_times][11][n_age + 1] and quantile bands [B][n_times][11][n_age + 1][probs.size()] of
+    // sepaihrd_particle_filter_states for B parameter vectors, at the seed the next calculateBatch would use and under the
+    // dispersion set; the call count does not advance, so that next call is what it would have been.  loglik (optional): the
+    // estimates of that call; status (optional) as in calculateBatch.
+    void filterStates(const double* thetas, int B, const std::vector<double>& probs, std::vector<double>& state_mean,
+                      std::vector<double>& state_quantiles, std::vector<double>* loglik = nullptr, int* status = nullptr) const;
     // the dispersion of the observed series, each +inf (Poisson, the default) or finite in [1e-3, 1e6]; throws
     // InvalidParameterException with sepaihrd_particle_nb_validate's message for anything else
     void setDispersion(double k_H, double k_ICU, double k_D);

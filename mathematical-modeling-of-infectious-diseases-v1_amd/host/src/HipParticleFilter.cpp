@@ -5,29 +5,36 @@
 #include "epidemic_hip/HipParticleFilter.hpp"
 
 #include <algorithm>
+#include <cstdio>
+#include <functional>
 #include <limits>
 
 #include "StochasticSEPAIHRDTwin.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_particle.inc"
 #include "sepaihrd_particle_nb_host.h"
+#include "sepaihrd_particle_states.inc"
 
 namespace epidemic {
 
 namespace epi = sepaihrd_stoch_epi;
 namespace pf = sepaihrd_particle;
+namespace ps = sepaihrd_particle_states;
 
 namespace {
 
 // The filter's walk over B parameter vectors, after the arguments have been accepted: what hostParticleLoglik and
 // hostParticleLoglikWide both are, and their negative-binomial forms.  Nothing in it depends on how large J is.  disp is the
 // dispersion of the observed series (NO_DISPERSION: every series Poisson); row_const the row constants G [T_pos] of a call with
-// a dispersed series, null where there is none.
+// a dispersed series, null where there is none.  row_sink (optional): called once per output row k of every valid theta b with
+// the cloud of csrc/sepaihrd_particle_states.inc -- the J particles the next interval starts from, after the resampling's copy
+// where the row is weighted; count c of (particle j, age i) at cloud[j per + i stride + c].
+using RowSink = std::function<void(int b, int k, const int32_t* cloud, size_t per, size_t stride)>;
 constexpr pf::Dispersion NO_DISPERSION{std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(),
                                        std::numeric_limits<double>::infinity()};
 void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan, const ParticleObservations& obs, const double* model_values,
                    const int32_t* status, int B, int J, int steps_per_interval, std::uint64_t seed, const pf::Dispersion& disp, const double* row_const,
-                   double* loglik, double* increments, double* ess, double* final_state) {
+                   double* loglik, double* increments, double* ess, double* final_state, const RowSink& row_sink = nullptr) {
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     const int n = pb.n_age, T = pb.n_times, m = steps_per_interval, runup_offset = plan.runup_offset;
     const size_t Tp = (size_t)plan.T_pos, nn = (size_t)n, W = plan.W, row_doubles = plan.row_doubles;
@@ -98,6 +105,7 @@ void particle_walk(const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan
                 if (my_inc) my_inc[t] = 0.0;
                 if (my_ess) my_ess[t] = qnan;
             }
+            if (row_sink) row_sink(b, k, state.data(), per, epi::NUM_COMP + pf::NUM_PREV);
         }
         loglik[b] = total;
         if (my_final)
@@ -118,7 +126,7 @@ double observed_cell(const ParticleObservations& obs, int n_age, int series, int
 int particle_twin(const char* who, int vrc, char (&msg)[256], const StochasticSEPAIHRDFixedData& pb, const stoch_twin::Plan& plan,
                   const ParticleObservations& obs, const double* model_values, const int32_t* status, int B, int J, int steps_per_interval,
                   std::uint64_t seed, bool nb, const double* dispersion, double* loglik, double* increments, double* ess, double* final_state,
-                  std::string* error) {
+                  std::string* error, const RowSink& row_sink = nullptr) {
     vrc = stoch_twin::verdict(
         who, vrc, msg,
         {{!model_values || !status || !loglik, "model_values, status and loglik must not be NULL"},
@@ -140,7 +148,7 @@ int particle_twin(const char* who, int vrc, char (&msg)[256], const StochasticSE
         }
     }
     particle_walk(pb, plan, obs, model_values, status, B, J, steps_per_interval, seed, d, G.empty() ? nullptr : G.data(), loglik, increments, ess,
-                  final_state);
+                  final_state, row_sink);
     return SEPAIHRD_OK;
 }
 
@@ -184,6 +192,52 @@ int hostParticleLoglikWideNB(const StochasticSEPAIHRDFixedData& pb, const Partic
     return particle_twin("particle_loglik_wide_nb",
                          sepaihrd_particle_wide_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, msg, (int)sizeof(msg)), msg, pb,
                          plan, obs, model_values, status, B, J, steps_per_interval, seed, true, dispersion, loglik, increments, ess, final_state, error);
+}
+
+int hostParticleStates(const StochasticSEPAIHRDFixedData& pb, const ParticleObservations& obs, const double* model_values, const int32_t* status,
+                       int B, int J, int steps_per_interval, std::uint64_t seed, const double* dispersion, const double* probs, int n_probs,
+                       double* loglik, double* increments, double* ess, double* state_mean, double* state_quantiles, std::string* error) {
+    char msg[256] = "";
+    const stoch_twin::Plan plan = stoch_twin::plan(pb);
+    int vrc = sepaihrd_particle_states_validate(B, J, steps_per_interval, 0, pb.n_times, plan.T_pos, pb.n_age, probs, n_probs, msg, (int)sizeof(msg));
+    if (vrc == SEPAIHRD_OK && (!state_mean || (state_quantiles && n_probs == 0))) {
+        std::snprintf(msg, sizeof(msg), "particle_filter_states: %s", !state_mean ? "need theta, loglik and state_mean" : "state_quantiles needs n_probs > 0");
+        vrc = SEPAIHRD_E_INVALID_ARG;
+    }
+    const size_t series = (size_t)pb.n_age + 1, cells = (size_t)epi::NUM_COMP * series, row_cells = (size_t)std::max(pb.n_times, 0) * cells;
+    // the summary of one row: per (count, series) the J values, their sum in 64-bit integers, std::sort, the quantile expression
+    const RowSink sink = [&](int b, int k, const int32_t* cloud, size_t per, size_t stride) {
+        std::vector<double> v((size_t)J);
+        for (int c = 0; c < epi::NUM_COMP; ++c)
+            for (size_t a = 0; a < series; ++a) {
+                int64_t sum = 0;
+                for (int j = 0; j < J; ++j) {
+                    const int32_t* x = cloud + (size_t)j * per;
+                    int64_t value = 0;
+                    if (a < (size_t)pb.n_age)
+                        value = x[a * stride + (size_t)c];
+                    else
+                        for (int i = 0; i < pb.n_age; ++i) value += x[(size_t)i * stride + (size_t)c];
+                    v[(size_t)j] = (double)value;
+                    sum += value;
+                }
+                const size_t cell = ((size_t)b * (size_t)pb.n_times + (size_t)k) * cells + (size_t)c * series + a;
+                state_mean[cell] = ps::mean_of(sum, J);
+                if (state_quantiles) {
+                    std::sort(v.begin(), v.end());
+                    for (int p = 0; p < n_probs; ++p) state_quantiles[cell * (size_t)n_probs + (size_t)p] = ps::quantile_of(v.data(), J, probs[p]);
+                }
+            }
+    };
+    const int rc = particle_twin("particle_filter_states", vrc, msg, pb, plan, obs, model_values, status, B, J, steps_per_interval, seed,
+                                 dispersion != nullptr, dispersion, loglik, increments, ess, nullptr, error, sink);
+    if (rc != SEPAIHRD_OK) return rc;
+    for (int b = 0; b < B; ++b)
+        if (status[b] != 0) {
+            stoch_twin::nan_fill(state_mean + (size_t)b * row_cells, 0, row_cells);
+            if (state_quantiles) stoch_twin::nan_fill(state_quantiles + (size_t)b * row_cells * (size_t)n_probs, 0, row_cells * (size_t)n_probs);
+        }
+    return SEPAIHRD_OK;
 }
 
 int hostParticleNBRowConstants(const ParticleObservations& obs, int n_age, int T_pos, const double* dispersion, double* G, std::string* error) {
@@ -249,6 +303,25 @@ void HipParticleLikelihood::calculateBatch(const double* thetas, int B, double* 
         throw ModelException("HipParticleLikelihood", std::string(wide ? "sepaihrd_particle_loglik_wide" : "sepaihrd_particle_loglik") +
                                                           (nb ? "_nb: " : ": ") + sepaihrd_last_error(ctx));
     ++calls_;
+    if (status) std::copy(st.begin(), st.begin() + B, status);
+}
+
+void HipParticleLikelihood::filterStates(const double* thetas, int B, const std::vector<double>& probs, std::vector<double>& state_mean,
+                                         std::vector<double>& state_quantiles, std::vector<double>* loglik, int* status) const {
+    sepaihrd_ctx* ctx = objective_->deviceContext();
+    objective_->syncDeviceConstraintMode();
+    const size_t cells = (size_t)std::max(B, 0) * time_points_.size() * epi::NUM_COMP * ((size_t)n_age_ + 1);
+    state_mean.assign(cells, 0.0);
+    state_quantiles.assign(cells * probs.size(), 0.0);
+    std::vector<double> ll((size_t)std::max(B, 1));
+    std::vector<int32_t> st((size_t)std::max(B, 1), 0);
+    const bool nb = pf::any_dispersed(pf::Dispersion{dispersion_[0], dispersion_[1], dispersion_[2]});
+    // the seed of the next calculateBatch; the call count stays
+    const int rc = sepaihrd_particle_filter_states(ctx, thetas, B, particles_, steps_per_interval_, seed0_ + calls_, 0, nb ? dispersion_ : nullptr,
+                                                   probs.empty() ? nullptr : probs.data(), (int)probs.size(), ll.data(), nullptr, nullptr,
+                                                   state_mean.data(), probs.empty() ? nullptr : state_quantiles.data(), nullptr, st.data(), nullptr);
+    if (rc != SEPAIHRD_OK) throw ModelException("HipParticleLikelihood", std::string("sepaihrd_particle_filter_states: ") + sepaihrd_last_error(ctx));
+    if (loglik) loglik->assign(ll.begin(), ll.begin() + B);
     if (status) std::copy(st.begin(), st.begin() + B, status);
 }
 

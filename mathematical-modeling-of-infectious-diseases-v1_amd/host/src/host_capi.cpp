@@ -1603,6 +1603,26 @@ int host_particle_wide_nb_from_values(int n_age, int n_times, int n_beta, int n_
                                      err, errlen);
 }
 
+// hostParticleStates (no device): the shapes of host_particle_wide_nb_from_values (dispersion NULL: Poisson) with probs [n_probs] and
+// state_mean [B][n_times][11][n_age + 1], state_quantiles [B][n_times][11][n_age + 1][n_probs] (nullable) for final_state
+int host_particle_states_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,
+                                     const double* beta_end_times, const double* kappa_end_times, int n_obs, const double* obs_H,
+                                     const double* obs_ICU, const double* obs_D, const double* model_values, const int32_t* status, int B, int J,
+                                     int steps_per_interval, uint64_t seed, const double* dispersion, const double* probs, int n_probs,
+                                     double* loglik, double* increments, double* ess, double* state_mean, double* state_quantiles, char* err,
+                                     int errlen) {
+    StochasticSEPAIHRDFixedData fd;
+    fd.n_age = n_age; fd.n_times = n_times; fd.n_beta = n_beta; fd.n_kappa = n_kappa;
+    fd.times = times; fd.N = N; fd.M = M; fd.beta_end_times = beta_end_times; fd.kappa_end_times = kappa_end_times;
+    ParticleObservations ob;
+    ob.n_obs = n_obs; ob.obs_H = obs_H; ob.obs_ICU = obs_ICU; ob.obs_D = obs_D;
+    std::string error;
+    const int rc = hostParticleStates(fd, ob, model_values, status, B, J, steps_per_interval, seed, dispersion, probs, n_probs, loglik, increments, ess,
+                                      state_mean, state_quantiles, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
 // the twin of sepaihrd_particle_nb_term_device (no device): out[i] = nb_term(obs[i], inc[i], k)
 void host_particle_nb_term(const double* obs, const int32_t* inc, int count, double k, double* out) { hostParticleNBTerm(obs, inc, count, k, out); }
 
@@ -1645,6 +1665,30 @@ int host_particle_likelihood_nb(void* hv, const sepaihrd_problem* pb, int device
             batch.calculateBatch(thetas, B, values + static_cast<size_t>(c) * B, st.data());
             if (status) std::copy(st.begin(), st.end(), status + static_cast<size_t>(c) * B);
         }
+    });
+}
+
+// HipParticleLikelihood::filterStates after n_calls_before calculateBatch calls on the same B parameter vectors, then one more
+// calculateBatch: state_mean [B][n_times][11][n_age + 1], state_quantiles [B][n_times][11][n_age + 1][n_probs], loglik [B] (that
+// of the filterStates call), next_values [B] (the calculateBatch after it), calls [2] (the call count before and after
+// filterStates).  0 ok, 1 = exception.
+int host_particle_filter_states(void* hv, const sepaihrd_problem* pb, int device, int initial_state_mode, int J, int steps_per_interval, uint64_t seed0,
+                                const double* dispersion, const double* thetas, int B, int n_calls_before, const double* probs, int n_probs,
+                                double* state_mean, double* state_quantiles, double* loglik, double* next_values, uint64_t* calls) {
+    auto* h = static_cast<HostHandle*>(hv);
+    return guarded([&] {
+        HipParticleLikelihood lik(*h->pm, *h->data, std::vector<double>(pb->times, pb->times + pb->n_times), vec(pb->initial_state, 11 * pb->n_age),
+                                  strategy_for(pb->solver), J, steps_per_interval, seed0, device, initial_state_mode);
+        if (dispersion) lik.setDispersion(dispersion[0], dispersion[1], dispersion[2]);
+        std::vector<double> scratch(static_cast<size_t>(B)), mean, quant, ll;
+        for (int c = 0; c < n_calls_before; ++c) lik.calculateBatch(thetas, B, scratch.data(), nullptr);
+        calls[0] = lik.calls();
+        lik.filterStates(thetas, B, std::vector<double>(probs, probs + n_probs), mean, quant, &ll, nullptr);
+        calls[1] = lik.calls();
+        std::copy(mean.begin(), mean.end(), state_mean);
+        std::copy(quant.begin(), quant.end(), state_quantiles);
+        std::copy(ll.begin(), ll.end(), loglik);
+        lik.calculateBatch(thetas, B, next_values, nullptr);
     });
 }
 

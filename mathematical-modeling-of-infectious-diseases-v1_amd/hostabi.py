@@ -142,6 +142,10 @@ def load_library() -> C.CDLL:
     lib.host_particle_nb_from_values.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_uint64, vp] + \
         [vp] * 4 + [C.c_char_p, C.c_int]
     lib.host_particle_wide_nb_from_values.argtypes = lib.host_particle_nb_from_values.argtypes
+    lib.host_particle_states_from_values.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 5 + [C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp,
+                                                     C.c_int] + [vp] * 5 + [C.c_char_p, C.c_int]
+    lib.host_particle_filter_states.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp,
+                                                C.c_int, C.c_int, vp, C.c_int] + [vp] * 5
     lib.host_particle_nb_term.restype = None
     lib.host_particle_nb_term.argtypes = [vp, vp, C.c_int, C.c_double, vp]
     lib.host_particle_nb_row_constants.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
@@ -459,6 +463,25 @@ class HostObjective:
         k = nsel.value
         return {"quantiles": q, "extinct": extinct[:k].copy(), "selected": sel[:k].copy(), "status": status[:k].copy(),
                 "samples_used": used.value}
+
+    def particle_filter_states(self, thetas, J: int, steps_per_interval: int, seed0: int, probs, n_calls_before: int = 0,
+                               initial_state_mode: int = 0, device: int = -1, dispersion=None) -> dict:
+        """HipParticleLikelihood::filterStates after n_calls_before calculateBatch calls, then one more calculateBatch: state_mean
+        [B][T][11][n + 1], state_quantiles [B][T][11][n + 1][len(probs)], loglik [B] of the filterStates call, next_values [B] of
+        the calculateBatch after it, calls (the adapter's call count before and after filterStates)."""
+        th = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        B, n, T = th.shape[0], self.pb.n, len(self.pb.times)
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        mean, quant = np.empty((B, T, 11, n + 1)), np.empty((B, T, 11, n + 1, pr.size))
+        loglik, nxt, calls = np.empty(B), np.empty(B), np.zeros(2, dtype=np.uint64)
+        disp = None if dispersion is None else _dispersion(dispersion)
+        _check(self.lib.host_particle_filter_states(self.h, C.byref(st), device, int(initial_state_mode), int(J), int(steps_per_interval),
+                                                    int(seed0) & 0xFFFFFFFFFFFFFFFF, None if disp is None else disp.ctypes.data, th.ctypes.data, B,
+                                                    int(n_calls_before), pr.ctypes.data, pr.size, mean.ctypes.data, quant.ctypes.data,
+                                                    loglik.ctypes.data, nxt.ctypes.data, calls.ctypes.data), "host_particle_filter_states: ")
+        return {"state_mean": mean, "state_quantiles": quant, "loglik": loglik, "next_values": nxt, "calls": calls}
 
     def particle_likelihood(self, thetas, J: int, steps_per_interval: int, seed0: int, n_calls: int = 1, initial_state_mode: int = 0,
                             device: int = -1, dispersion=None) -> dict:
@@ -1280,4 +1303,60 @@ def _particle_from_values(wide, model_values, status, times, N, M, kappa_end_tim
     out = {"loglik": loglik, "increments": inc, "ess": ess, "n_valid": int(np.sum(st == 0))}
     if final is not None:
         out["final_state"] = final
+    return out
+
+
+def particle_states_validate(B: int, J: int, steps_per_interval: int, theta_chunk: int, n_times: int, T_pos: int, n_age: int, probs=()) -> None:
+    """sepaihrd_particle_states_validate (host only): ValueError with its message for arguments particle_filter_states refuses
+    (probs None: a NULL pointer with n_probs = 1)"""
+    err = C.create_string_buffer(512)
+    pr = None if probs is None else np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    n_probs = 1 if pr is None else pr.size
+    if hipabi.load_library().sepaihrd_particle_states_validate(int(B), int(J), int(steps_per_interval), int(theta_chunk), int(n_times), int(T_pos),
+                                                               int(n_age), pr.ctypes.data if n_probs and pr is not None else None, n_probs, err,
+                                                               len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def particle_states_from_values(model_values, status, times, N, M, kappa_end_times, obs_H, obs_ICU, obs_D, J: int, steps_per_interval: int,
+                                seed: int, probs=(), beta_end_times=(), want_quantiles: bool = True, dispersion=None) -> dict:
+    """The twin of HipObjective.particle_filter_states after the decoding: particle_wide_from_values' walk with the per-row summaries
+    of csrc/sepaihrd_particle_states.inc.  loglik [B], increments [B][T_pos], ess [B][T_pos] (those of particle_wide_from_values),
+    state_mean [B][T][11][n + 1] and, where probs is not empty and want_quantiles, state_quantiles [B][T][11][n + 1][len(probs)],
+    bit for bit."""
+    mv = np.ascontiguousarray(np.atleast_2d(model_values), dtype=np.float64)
+    st = np.ascontiguousarray(status, dtype=np.int32).ravel()
+    tm = np.ascontiguousarray(times, dtype=np.float64).ravel()
+    Nv = np.ascontiguousarray(N, dtype=np.float64).ravel()
+    n = Nv.size
+    Mm = np.ascontiguousarray(M, dtype=np.float64)
+    be = np.ascontiguousarray(beta_end_times, dtype=np.float64).ravel()
+    ke = np.ascontiguousarray(kappa_end_times, dtype=np.float64).ravel()
+    ob = [np.ascontiguousarray(np.asarray(o, dtype=np.float64).reshape(-1, n)) for o in (obs_H, obs_ICU, obs_D)]
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    B, T, J = mv.shape[0], tm.size, int(J)
+    Tp = int(np.sum(tm >= 0.0))
+    if Mm.shape != (n, n) or st.shape != (B,) or mv.shape[1] != stochastic_values_width(n, be.size, ke.size):
+        raise ValueError("model_values [B][W], status [B], N [n], M [n][n]")
+    if not (ob[0].shape == ob[1].shape == ob[2].shape):
+        raise ValueError("obs_H, obs_ICU and obs_D must have the same shape [n_obs][n]")
+    particle_states_validate(B, J, steps_per_interval, 0, T, Tp, n, pr)
+    disp = None
+    if dispersion is not None:
+        particle_nb_validate(dispersion)
+        disp = _dispersion(dispersion)
+    loglik, inc, ess = np.empty(B), np.empty((B, Tp)), np.empty((B, Tp))
+    mean = np.empty((B, T, 11, n + 1))
+    quant = np.empty((B, T, 11, n + 1, pr.size)) if (want_quantiles and pr.size) else None
+    err = C.create_string_buffer(512)
+    rc = load_library().host_particle_states_from_values(
+        n, T, be.size, ke.size, tm.ctypes.data, Nv.ctypes.data, Mm.ctypes.data, be.ctypes.data if be.size else None, ke.ctypes.data, ob[0].shape[0],
+        ob[0].ctypes.data, ob[1].ctypes.data, ob[2].ctypes.data, mv.ctypes.data, st.ctypes.data, B, J, int(steps_per_interval),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, None if disp is None else disp.ctypes.data, pr.ctypes.data if pr.size else None, pr.size, loglik.ctypes.data,
+        inc.ctypes.data, ess.ctypes.data, mean.ctypes.data, None if quant is None else quant.ctypes.data, err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    out = {"loglik": loglik, "increments": inc, "ess": ess, "n_valid": int(np.sum(st == 0)), "state_mean": mean}
+    if quant is not None:
+        out["state_quantiles"] = quant
     return out
