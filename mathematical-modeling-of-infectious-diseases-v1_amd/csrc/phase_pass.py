@@ -9,6 +9,9 @@ inside a stage.  This pass walks the big straight-line blocks of the chosen kern
 8-byte encodings that would start off phase, re-encodes the nearest preceding 4-byte VOP1 / VOP2 / VOPC instruction of the same
 block as its 8-byte VOP3 form (`_e32` -> `_e64`: the same instruction, no issue slot, four more bytes), or -- if there is none
 close enough -- inserts one `s_nop 0` when the run is long enough to pay for it.
+For the 16-lane kernels (--exact-kernels) which instructions to re-encode and where to pad is chosen exactly per block
+(best_choices: two states, the fewest off-phase encodings); the other kernels, and with `--greedy` all of them, keep the
+front-to-back walk, which the strict build's placement and the 16-age kernel's were measured with.
 
 usage: phase_pass.py <in.s> <out.s> [--kernels substr,substr] [--min-run N] [--llvm DIR] [--mcpu ARCH]
 Needs the assembler of the image: addresses come from assembling the input once, and the OUTPUT is assembled again at the end --
@@ -95,6 +98,62 @@ def is_instruction(line):
     return bool(t) and not t.startswith((";", ".", "//", "#")) and not re.match(r"^[\w.$]+:", t)
 
 
+def best_choices(blk, ins, shift, can_widen, can_pad, min_run, nop_run):
+    """The re-encodings and pads of one straight-line block that leave the fewest 8-byte encodings off phase, found exactly: walking
+    the block, all that the instructions still to come see of the choices made so far is whether an odd number of them lies
+    behind -- two states.  The costs are WEIGHTS that order the choices, not measured cycles (measured, tools/ubench/phase.hip: 0.9
+    cycles per off-phase encoding inside a run, 4.3 for a pad): an off-phase 8-byte encoding inside a run of >= min_run weighs 11,
+    outside a run 5, a re-encoded instruction that lands off phase 11 like the encoding in a run it becomes, every re-encoding
+    0.01 more (fewer edits among equals), a pad 43 and only in front of a run of >= nop_run.  11 against 43 makes a pad win over
+    an unreachable off-phase run from four encodings on: the length from which tools/check_code_phase.py counts a run, and the
+    build check wants none off phase in those; at the measured 9 a run of four would stay.  Returns (indices into blk to
+    re-encode, indices to pad in front of)."""
+    n = len(blk)
+    wide = [ins[a][1] == 8 for a in blk]
+    run_len = [0] * n    # at the first instruction of a run: its length
+    in_run = [False] * n
+    j = 0
+    while j < n:
+        if not wide[j]:
+            j += 1
+            continue
+        r = j
+        while r < n and wide[r]:
+            r += 1
+        run_len[j] = r - j
+        if r - j >= min_run:
+            for x in range(j, r):
+                in_run[x] = True
+        j = r
+    INF = float("inf")
+    cost = [[INF, INF] for _ in range(n + 1)]   # cost[i][t]: best cost of instructions i.. when t changes lie in front of i
+    pick = [[None, None] for _ in range(n + 1)]
+    cost[n] = [0, 0]
+    for i in range(n - 1, -1, -1):
+        off0 = (ins[blk[i]][0] + shift) % 8 == 4
+        for t in (0, 1):
+            options = []
+            for pad in ((0, 1) if wide[i] and run_len[i] >= nop_run and can_pad[i] else (0,)):
+                tt = t ^ pad
+                off = off0 ^ bool(tt)
+                if wide[i]:
+                    options.append((43 * pad + (0 if not off else 11 if in_run[i] else 5) + cost[i + 1][tt], (pad, 0)))
+                else:
+                    options.append((cost[i + 1][tt], (0, 0)))
+                    if can_widen[i]:
+                        options.append(((11 if off else 0) + 0.01 + cost[i + 1][tt ^ 1], (0, 1)))
+            cost[i][t], pick[i][t] = min(options)
+    widen, pads, t = [], [], 0
+    for i in range(n):
+        pad, w = pick[i][t]
+        if pad:
+            pads.append(i)
+        if w:
+            widen.append(i)
+        t ^= pad ^ w
+    return widen, pads
+
+
 def main():
     global LLVM, MCPU
     ap = argparse.ArgumentParser()
@@ -102,8 +161,17 @@ def main():
     ap.add_argument("--kernels", default="sepaihrd_eval_quad_kernel,sepaihrd_eval_kernelILi16E")
     ap.add_argument("--min-run", type=int, default=3)
     ap.add_argument("--min-block", type=int, default=200)
-    ap.add_argument("--nop-run", type=int, default=7, help="insert s_nop 0 in front of an off-phase run at least this long when nothing can be re-encoded")
+    ap.add_argument("--nop-run", type=int, default=0,
+                    help="insert s_nop 0 in front of an off-phase run at least this long when nothing can be re-encoded (0: 7 for the walk, 4 for the exact choice)")
     ap.add_argument("--look-back", type=int, default=12)
+    ap.add_argument("--greedy", action="store_true",
+                    help="the round-3 walk (nearest re-encodable instruction within --look-back in front of each off-phase run) for EVERY "
+                         "kernel: what the strict build was placed and measured with")
+    ap.add_argument("--exact-kernels", default="sepaihrd_eval_quad_kernel",
+                    help="without --greedy: the kernels (substrings) whose blocks get the exact choice (best_choices); the other --kernels "
+                         "keep the walk -- the 16-age kernel's code is what it was before the exact choice existed")
+    ap.add_argument("--common-body", choices=["walk", "exact"], default="walk",
+                    help="how the common RK body of an --exact-kernels kernel (the shortest of its big FP64 blocks) is treated")
     ap.add_argument("--body-residue", type=int, default=-1,
                     help="0, 8, .., 56: pad the ENTRY of every sepaihrd_eval_quad_kernel (s_nop pairs, executed once per wave) so that its "
                          "largest straight-line block -- the common RK body -- starts at this offset within a 64-byte line.  The 8-byte phase "
@@ -113,6 +181,7 @@ def main():
     ap.add_argument("--mcpu", default=MCPU)
     args = ap.parse_args()
     LLVM, MCPU = args.llvm, args.mcpu
+    exact_names = [] if args.greedy else [w for w in args.exact_kernels.split(",") if w]
     wanted = args.kernels.split(",")
     sizes = assemble_sizes(args.src)
     lines = open(args.src).read().split("\n")
@@ -138,6 +207,20 @@ def main():
             print(f"skip {name[:70]}: {len(ins)} disassembled vs {len(idxs)} listed instructions", file=sys.stderr)
             continue
         guarded = protected_spans(lines, idxs)
+        exact = any(w in name for w in exact_names)
+        nop_run = args.nop_run if args.nop_run > 0 else 7
+        # the common RK body of a 16-lane kernel: the SHORTEST of its big FP64 / DPP blocks (see --body-residue below); it runs on
+        # every attempt, the other copy only for a step that straddles a breakpoint
+        common_start = -1
+        if exact:
+            bodies, b0 = [], 0
+            for k in range(len(ins) + 1):
+                if k == len(ins) or ins[k][2].startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc")):
+                    b = range(b0, min(k + 1, len(ins))); b0 = k + 1
+                    if len(b) >= args.min_block and sum(1 for x in b if "f64" in ins[x][2] or "dpp" in ins[x][2]) * 2 > len(b):
+                        bodies.append(b)
+            if bodies:
+                common_start = min(bodies, key=len)[0]
         # straight-line blocks
         start = 0
         shift = 0  # bytes added in this function so far: every edit moves everything behind it
@@ -148,6 +231,20 @@ def main():
             blk = list(range(start, min(k + 1, len(ins))))
             start = k + 1
             if len(blk) < args.min_block:
+                continue
+            is_common = exact and blk[0] == common_start
+            if exact and not (is_common and args.common_body == "walk"):
+                # a pad in the common body is an issue slot of every attempt: there only a run of >= 7 gets one, as in the walk
+                # (measured: three pads in a body of 277 instructions cost the headline 1.1 %); elsewhere from 4 on
+                pad_run = args.nop_run if args.nop_run > 0 else (7 if is_common else 4)
+                can_widen = [ins[x][1] == 4 and x not in guarded and bool(E64_OK.match(lines[idxs[x]])) and "0x" not in lines[idxs[x]]
+                             and "dpp" not in lines[idxs[x]] and "sdwa" not in lines[idxs[x]] for x in blk]
+                widen, pads = best_choices(blk, ins, shift, can_widen, [x not in guarded for x in blk], args.min_run, pad_run)
+                for i in widen:
+                    edits[idxs[blk[i]]] = lines[idxs[blk[i]]].replace("_e32", "_e64", 1)
+                for i in pads:
+                    inserts[idxs[blk[i]]] = "\ts_nop 0"
+                shift += 4 * (len(widen) + len(pads)); n_re += len(widen); n_nop += len(pads)
                 continue
             j = 0
             last_touch = -1
@@ -175,7 +272,7 @@ def main():
                                 edits[li] = lines[li].replace("_e32", "_e64", 1)
                                 shift += 4; n_re += 1; fixed = True; last_touch = b
                                 break
-                        if not fixed and run_len >= args.nop_run and a not in guarded:
+                        if not fixed and run_len >= nop_run and a not in guarded:
                             inserts[idxs[a]] = "\ts_nop 0"
                             shift += 4; n_nop += 1; fixed = True; last_touch = j
                         n_fixed += fixed
@@ -210,8 +307,12 @@ def main():
             if not bodies:
                 continue
             body = min(bodies, key=len)
-            delta = (args.body_residue - body[0][0]) % 64
-            delta -= delta % 8                      # pairs of 4-byte pads only: the 8-byte phase of everything stays
+            # pairs of 4-byte pads only: the 8-byte phase of everything stays, so a body that starts on the other phase goes to
+            # the reachable offset just behind the wanted one
+            delta = (args.body_residue + (body[0][0] - args.body_residue) % 8 - body[0][0]) % 64
+            if args.greedy:                         # as the strict build was placed: such a body stays 4 bytes short
+                delta = (args.body_residue - body[0][0]) % 64
+                delta -= delta % 8
             if delta:
                 inserts_at[name] = delta // 4
         if inserts_at:
@@ -230,8 +331,9 @@ def main():
             print(f"body residue {args.body_residue}: entry pads {sorted(set(inserts_at.values()))} s_nop in {len(inserts_at)} kernels")
     runs_before, off_before = off_phase_runs(sizes, wanted, args.min_run, args.min_block)
     runs_after, off_after = off_phase_runs(after, wanted, args.min_run, args.min_block)
-    print(f"runs of >= {args.min_run} wide encodings: {n_runs}; off phase and fixed: {n_fixed} ({n_re} re-encoded, {n_nop} s_nop); "
-          f"off-phase runs by the assembled addresses: {off_before} of {runs_before} before, {off_after} of {runs_after} after")
+    head = (f"runs of >= {args.min_run} wide encodings: {n_runs}; off phase and fixed: {n_fixed} ({n_re} re-encoded, {n_nop} s_nop); " if not exact_names else
+            f"walk: {n_fixed} of {n_runs} runs fixed; exact choice per block (with the walk's): {n_re} re-encoded, {n_nop} s_nop; ")
+    print(head + f"off-phase runs by the assembled addresses: {off_before} of {runs_before} before, {off_after} of {runs_after} after")
     if off_after > off_before:
         print("phase_pass: the rewritten assembly has MORE off-phase runs than its input", file=sys.stderr)
         sys.exit(1)

@@ -232,20 +232,25 @@ __device__ __forceinline__ void rhs(const LaneModel<LPC>& q, const double (&x)[N
 // constants: 26 v_mul_f64 per attempt, each constant a 64-bit literal that has to sit in (or be re-materialised into)
 // an SGPR pair.  A chain is a 16-lane DPP row here, so lane l of the row computes cur * coefficient[l] ONCE (two
 // multiplications fill two 16-entry vectors) and every term of a stage sum after the first takes its factor from there
-// as the row_newbcast source of the v_fmac_f64_dpp that adds the term: the broadcast costs nothing.  The first term of a
-// sum (x + f1 k1: a three-operand fma) and the two leading products of the error estimate keep their own per-lane
-// factor.  Same products, same fmas, same order as written out term by term (and as the 4-lane kernel): same bits.
+// as the row_newbcast source of the v_fmac_f64_dpp that adds the term: the broadcast costs nothing.  In rk_stages_row_coef
+// below (the 16-age kernel, the one-wavefront-per-chain kernel) the first term of a sum (x + f1 k1: a three-operand fma) and
+// the two leading products of the error estimate keep their own per-lane factor from a literal; the 16-lane form
+// (rk_stages_quad, sepaihrd_lane_split.inc) takes those from the second vector too.  Same products, same fmas, same order as
+// written out term by term (and as the 4-lane kernel): same bits.
 enum QuadCoefDopri5 { QD_B32 = 0, QD_B42, QD_B43, QD_B52, QD_B53, QD_B54, QD_B62, QD_B63, QD_B64, QD_B65, QD_C3, QD_C4, QD_C5,
                       QD_C6, QD_DC4, QD_DC5, QD_DC6 /* vector B lane 0 */, QD_DC7 /* vector B lane 1 */ };
 enum QuadCoefCashKarp { QK_A32 = 0, QK_A42, QK_A43, QK_A52, QK_A53, QK_A54, QK_A62, QK_A63, QK_A64, QK_A65, QK_B3, QK_B4, QK_B6,
                         QK_DB4, QK_DB5, QK_DB6 };
+// vector B from lane 2 on, both tableaus alike: the factor of the FIRST term of every sum and the two leading ones of the error
+// estimate.  Only the 16-lane form reads them (rk_stages_quad, sepaihrd_lane_split.inc); the forms below keep their literals.
+enum QuadLeadCoef { QL_STAGE2 = 2, QL_STAGE3, QL_STAGE4, QL_STAGE5, QL_STAGE6, QL_NEW, QL_ERR1, QL_ERR3 };
 __device__ const double QUAD_COEF[2][2][16] = {
     {{dp::b32, dp::b42, dp::b43, dp::b52, dp::b53, dp::b54, dp::b62, dp::b63, dp::b64, dp::b65, dp::c3, dp::c4, dp::c5, dp::c6,
       dp::dc4, dp::dc5},
-     {dp::dc6, dp::dc7, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+     {dp::dc6, dp::dc7, dp::b21, dp::b31, dp::b41, dp::b51, dp::b61, dp::c1, dp::dc1, dp::dc3, 0, 0, 0, 0, 0, 0}},
     {{ck::a32, ck::a42, ck::a43, ck::a52, ck::a53, ck::a54, ck::a62, ck::a63, ck::a64, ck::a65, ck::b3, ck::b4, ck::b6, ck::db4,
       ck::db5, ck::db6},
-     {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}}};
+     {0, 0, ck::a21, ck::a31, ck::a41, ck::a51, ck::a61, ck::b1, ck::db1, ck::db3, 0, 0, 0, 0, 0, 0}}};
 // acc += (cur * coefficient IDX of the chain's row) * k
 template <int IDX>
 __device__ __forceinline__ void stage_term(double& acc, double vecA, double vecB, double k) {
@@ -255,7 +260,9 @@ __device__ __forceinline__ void stage_term(double& acc, double vecA, double vecB
 
 
 // The RK stages of one attempt with the row-coefficient vectors: k2..k7 (k1 for Cash-Karp), the new state and the
-// error estimate.  rhs_call(x_in, k_out, beta_kappa) evaluates the right-hand side.  N = values per lane.
+// error estimate.  rhs_call(x_in, k_out, beta_kappa) evaluates the right-hand side.  N = values per lane: 11 (16 ages) or 1.
+// The 16-lane form (three values per lane) has the SAME stages written for its lane layout in rk_stages_quad
+// (sepaihrd_lane_split.inc): a change to a tableau's stage structure here has to be made there too.
 // Phase pads of the 16-age RK body of the tolerance build (N = 11 values per lane, one wave per SIMD: configs[4]; DESIGN.md 4,
 // "The strict build's two speeds"): one 4-byte s_nop in front of (even bits) or behind (odd bits) the RHS of stage i / 2 when the
 // bit is set in SEPAIHRD_FMA16_STAGE_PADS, tied to a value of that point so that it stays where it is written.  The mask is chosen
@@ -263,10 +270,7 @@ __device__ __forceinline__ void stage_term(double& acc, double vecA, double vecB
 #ifndef SEPAIHRD_FMA16_STAGE_PADS
 #define SEPAIHRD_FMA16_STAGE_PADS 194  // greedy front-to-back search: 231 -> 180 of the body's 458 eight-byte encodings off phase, c5 18.40 -> 18.25 ms
 #endif
-#ifndef SEPAIHRD_FMA3_STAGE_PADS   // the same pad points in the 16-lane form's body (N = 3 values per lane)
-#define SEPAIHRD_FMA3_STAGE_PADS 0
-#endif
-#define SEP_ROW_STAGE_PAD(i, v) do { if ((((N == NUM_COMP) ? SEPAIHRD_FMA16_STAGE_PADS : (N == 3) ? SEPAIHRD_FMA3_STAGE_PADS : 0) >> (i)) & 1) asm volatile("s_nop 0" : "+v"(v)); } while (0)
+#define SEP_ROW_STAGE_PAD(i, v) do { if ((((N == NUM_COMP) ? SEPAIHRD_FMA16_STAGE_PADS : 0) >> (i)) & 1) asm volatile("s_nop 0" : "+v"(v)); } while (0)
 
 template <int SOLVER, int N, class RHS>
 __device__ __forceinline__ void rk_stages_row_coef(const double cur, const double vecA, const double vecB, const double (&x)[N],

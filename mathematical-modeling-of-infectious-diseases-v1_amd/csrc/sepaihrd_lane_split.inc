@@ -93,19 +93,54 @@ struct QuadModel {
     double a1, a2, a3, a4, a5;        // slot 2: CumICU, CumH, R, D
 };
 
-__device__ __forceinline__ void rhs_quad(const QuadModel& q, const double (&x)[QUAD_SLOTS], double (&dx)[QUAD_SLOTS],
-                                         double beta_eff) {
+// The contact sum of one right-hand-side call as ONE fixed instruction sequence: the pressure (cg-2 lanes: P + A + theta I;
+// meaningless, finite and unused in the other lanes; h_infec / N rides in q.m), then lambda_i = sum_j m_ij pressure_j, j ascending,
+// one v_fmac_f64_dpp per term; fma(m_0, p_0, +0.0) = round(m_0 p_0) is the 4-lane kernel's first term.  The first DPP read of the
+// pressure needs two wait states behind its VALU write.  They hold instructions the call needs anyway -- the accumulator's zero
+// and the first half of the rotation Nx1 of slot 1 that only dx[2] reads (its second half goes between the first two terms, where
+// the compiler put it too) -- instead of an s_nop (an issue slot of a lone wave like any other); a call whose dx[2] nobody
+// reads (WANT2 = false: the second stage's) puts the zero and an fma of the caller's there: fill = fma(fa, fb, fc), any
+// product-sum the caller needs next that does not depend on this call (the first term of the next stage's sum).
+// x[1] itself was written at least three instructions earlier: Lx1's two moves and the addition separate it from this block.
+template <bool WANT2>
+__device__ __forceinline__ void contact_sum(const QuadModel& q, const double x1, const double lx1_plus_x0, double& lambda, double& Nx1,
+                                            double& fill, const double fa, const double fb, const double fc) {
+    double pressure = lx1_plus_x0;  // v_fmac: fma(theta, x1, Lx1 + x0)
+    if constexpr (WANT2) {
+        int lo, hi;
+        asm("v_fmac_f64_e32 %0, %4, %5\n\t"
+            "v_mov_b64_e32 %1, 0\n\t"
+            "v_mov_b32_dpp %2, %6 quad_perm:[1,2,3,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+            "v_fmac_f64_dpp %1, %0, %8 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
+            "v_mov_b32_dpp %3, %7 quad_perm:[1,2,3,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+            "v_fmac_f64_dpp %1, %0, %9 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %1, %0, %10 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %1, %0, %11 row_newbcast:14 row_mask:0xf bank_mask:0xf"
+            : "+v"(pressure), "=&v"(lambda), "=&v"(lo), "=&v"(hi)
+            : "v"(q.theta_inf), "v"(x1), "v"(__double2loint(x1)), "v"(__double2hiint(x1)), "v"(q.m[0]), "v"(q.m[1]), "v"(q.m[2]), "v"(q.m[3]));
+        Nx1 = __hiloint2double(hi, lo);
+    } else {
+        asm("v_fmac_f64_e32 %0, %3, %4\n\t"
+            "v_mov_b64_e32 %1, 0\n\t"
+            "v_fma_f64 %2, %9, %10, %11\n\t"
+            "v_fmac_f64_dpp %1, %0, %5 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %1, %0, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %1, %0, %7 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
+            "v_fmac_f64_dpp %1, %0, %8 row_newbcast:14 row_mask:0xf bank_mask:0xf"
+            : "+v"(pressure), "=&v"(lambda), "=&v"(fill)
+            : "v"(q.theta_inf), "v"(x1), "v"(q.m[0]), "v"(q.m[1]), "v"(q.m[2]), "v"(q.m[3]), "v"(fa), "v"(fb), "v"(fc));
+        Nx1 = 0.0;
+    }
+}
+
+// The body of both forms below.  WANT2 = false: dx[2] comes back as 0 and fill = fma(fa, fb, fc) is formed on the way.
+template <bool WANT2>
+__device__ __forceinline__ void rhs_quad_body(const QuadModel& q, const double (&x)[QUAD_SLOTS], double (&dx)[QUAD_SLOTS],
+                                              double beta_eff, double& fill, const double fa, const double fb, const double fc) {
     const double Lx1 = quad_rot<QROT_LEFT>(x[1]);
-    const double Nx1 = quad_rot<QROT_NEXT>(x[1]), Nx0 = quad_rot<QROT_NEXT>(x[0]);
-    // cg-2 lanes: P + A + theta I (meaningless, finite and unused in the other lanes); h_infec / N rides in q.m
-    const double pressure = fma(q.theta_inf, x[1], Lx1 + x[0]);
-    // lambda_i = sum_j m_ij pressure_j, j ascending, one v_fmac_f64_dpp per term (fmac_row_bcast);
-    // fma(m_0, p_0, +0.0) = round(m_0 p_0) is the 4-lane kernel's first term
-    double lambda = 0.0;
-    fmac_row_bcast<2, 0xf, true>(lambda, pressure, q.m[0]);
-    fmac_row_bcast<6, 0xf, false>(lambda, pressure, q.m[1]);
-    fmac_row_bcast<10, 0xf, false>(lambda, pressure, q.m[2]);
-    fmac_row_bcast<14, 0xf, false>(lambda, pressure, q.m[3]);
+    const double Nx0 = quad_rot<QROT_NEXT>(x[0]);
+    double lambda, Nx1;
+    contact_sum<WANT2>(q, x[1], Lx1 + x[0], lambda, Nx1, fill, fa, fb, fc);
     lambda *= beta_eff;
     const double lambda_val = (0.0 < lambda) ? lambda : 0.0;
     const double W = lambda_val * x[0];  // lambda_i S_i in the cg-0 lanes; exactly 0 elsewhere (their contact row is zero)
@@ -114,7 +149,116 @@ __device__ __forceinline__ void rhs_quad(const QuadModel& q, const double (&x)[Q
     // dR = fma(g_ICU, ICU, fma(g_A, A, fma(g_H, H, g_I I))), dD = fma(d_ICU, ICU, fma(d_comm, I, d_H H))
     dx[1] = fma(q.cO1, x[1], fma(q.cL1, Lx1, W));
     dx[0] = fma(q.cO0, x[0], fma(q.cX0, x[1], fma(q.cL0, Lx1, -W)));
-    dx[2] = fma(q.a5, Nx0, fma(q.a4, x[0], fma(q.a3, Lx1, fma(q.a2, Nx1, q.a1 * x[1]))));
+    if constexpr (WANT2) dx[2] = fma(q.a5, Nx0, fma(q.a4, x[0], fma(q.a3, Lx1, fma(q.a2, Nx1, q.a1 * x[1]))));
+    else dx[2] = 0.0;
+}
+// the right-hand side
+__device__ __forceinline__ void rhs_quad(const QuadModel& q, const double (&x)[QUAD_SLOTS], double (&dx)[QUAD_SLOTS], double beta_eff) {
+    double unused = 0.0;
+    rhs_quad_body<true>(q, x, dx, beta_eff, unused, 0.0, 0.0, 0.0);
+}
+// the right-hand side of a call whose dx[2] the caller never reads (it comes back as 0); returns fma(fa, fb, fc), formed inside
+// the contact sum's hazard window: every argument is required, there is no form of this call without the fill
+__device__ __forceinline__ double rhs_quad_slots01_fill(const QuadModel& q, const double (&x)[QUAD_SLOTS], double (&dx)[QUAD_SLOTS],
+                                                        double beta_eff, const double fa, const double fb, const double fc) {
+    double fill;
+    rhs_quad_body<false>(q, x, dx, beta_eff, fill, fa, fb, fc);
+    return fill;
+}
+
+// acc += (cur * coefficient IDX of the chain's row) * k for the terms after the first of ONE stage sum, all slots in a single
+// fixed sequence: slot 1 first -- its quad rotation is what the right-hand side behind the sum starts with, and the other slots'
+// terms separate its last write from that DPP read -- then slot 0, then (SL = 3) slot 2.  Per slot the terms in the order
+// stage_term adds them one by one: the same fmas on the same operands.  One asm statement per sum, not one per term: the
+// compiler counts an asm statement as no wait state at all and pads between two of them that touch the same register.
+#define SEP_QLINE(t, s) "v_fmac_f64_dpp %[a" #s "], %[v" #t "], %[w" #t #s "] row_newbcast:%[n" #t "] row_mask:0xf bank_mask:0xf\n\t"
+#define SEP_QTERM2(t) SEP_QLINE(t, 1) SEP_QLINE(t, 0)
+#define SEP_QTERM3(t) SEP_QLINE(t, 1) SEP_QLINE(t, 0) SEP_QLINE(t, 2)
+#define SEP_QIN2(t, IDX, k) [v##t] "v"((IDX) < 16 ? vecA : vecB), [n##t] "n"((IDX) & 15), [w##t##1] "v"(k[1]), [w##t##0] "v"(k[0])
+#define SEP_QIN3(t, IDX, k) SEP_QIN2(t, IDX, k), [w##t##2] "v"(k[2])
+#define SEP_QACC2(acc) [a1] "+v"(acc[1]), [a0] "+v"(acc[0])
+#define SEP_QACC3(acc) SEP_QACC2(acc), [a2] "+v"(acc[2])
+
+// The RK stages of one attempt of the 16-lane form: the stages of rk_stages_row_coef (sepaihrd_kernels.hip; a change to a
+// tableau's stage structure there has to be made here too) for three values per lane, with
+// the leading factor of every sum taken from vector B (lead<>: fl(cur * c) formed in lane IDX is the product every lane used
+// to form from a 64-bit literal -- the same bits, and eight literals, two scalar registers each, leave a kernel that sits at the
+// scalar-register limit), each sum's later terms as one sequence (above), and without the stage values nobody reads: slot 2
+// of a lane holds output quadratures that no right-hand side reads, so xt[2] is never formed, and k2 has no weight in the
+// solution or the error estimate of either tableau, so k2[2] is not either.
+template <int IDX>
+__device__ __forceinline__ double lead(double vecB) { return dpp_bcast_row<IDX, 0xf, IDX, 0x0>(vecB); }
+
+template <int SOLVER>
+__device__ __forceinline__ void rk_stages_quad(const QuadModel& q, const double vecA, const double vecB, const double (&x)[QUAD_SLOTS],
+                                               double (&k1)[QUAD_SLOTS], double (&k2)[QUAD_SLOTS], double (&k3)[QUAD_SLOTS],
+                                               double (&k4)[QUAD_SLOTS], double (&k5)[QUAD_SLOTS], double (&k6)[QUAD_SLOTS],
+                                               double (&k7)[QUAD_SLOTS], double (&xnew)[QUAD_SLOTS], double (&xerr)[QUAD_SLOTS],
+                                               const double (&bks)[7]) {
+    double xt[QUAD_SLOTS];
+    xt[2] = 0.0;
+    auto first_term = [&](double (&acc)[QUAD_SLOTS], double f1, int slots) {
+        acc[0] = fma(f1, k1[0], x[0]);
+        acc[1] = fma(f1, k1[1], x[1]);
+        if (slots == 3) acc[2] = fma(f1, k1[2], x[2]);
+    };
+    if (SOLVER == 0) {
+        first_term(xt, lead<QL_STAGE2>(vecB), 2);
+        {   // the third stage's first term of slot 1 rides in the second stage's contact sum
+            const double f1 = lead<QL_STAGE3>(vecB);
+            const double xt1 = rhs_quad_slots01_fill(q, xt, k2, bks[1], f1, k1[1], x[1]);
+            xt[0] = fma(f1, k1[0], x[0]);
+            xt[1] = xt1;
+        }
+        asm(SEP_QTERM2(1) : SEP_QACC2(xt) : SEP_QIN2(1, QD_B32, k2));
+        rhs_quad(q, xt, k3, bks[2]);
+        first_term(xt, lead<QL_STAGE4>(vecB), 2);
+        asm(SEP_QTERM2(1) SEP_QTERM2(2) : SEP_QACC2(xt) : SEP_QIN2(1, QD_B42, k2), SEP_QIN2(2, QD_B43, k3));
+        rhs_quad(q, xt, k4, bks[3]);
+        first_term(xt, lead<QL_STAGE5>(vecB), 2);
+        asm(SEP_QTERM2(1) SEP_QTERM2(2) SEP_QTERM2(3) : SEP_QACC2(xt) : SEP_QIN2(1, QD_B52, k2), SEP_QIN2(2, QD_B53, k3), SEP_QIN2(3, QD_B54, k4));
+        rhs_quad(q, xt, k5, bks[4]);
+        first_term(xt, lead<QL_STAGE6>(vecB), 2);
+        asm(SEP_QTERM2(1) SEP_QTERM2(2) SEP_QTERM2(3) SEP_QTERM2(4)
+            : SEP_QACC2(xt) : SEP_QIN2(1, QD_B62, k2), SEP_QIN2(2, QD_B63, k3), SEP_QIN2(3, QD_B64, k4), SEP_QIN2(4, QD_B65, k5));
+        rhs_quad(q, xt, k6, bks[5]);
+        first_term(xnew, lead<QL_NEW>(vecB), 3);
+        asm(SEP_QTERM3(1) SEP_QTERM3(2) SEP_QTERM3(3) SEP_QTERM3(4)
+            : SEP_QACC3(xnew) : SEP_QIN3(1, QD_C3, k3), SEP_QIN3(2, QD_C4, k4), SEP_QIN3(3, QD_C5, k5), SEP_QIN3(4, QD_C6, k6));
+        rhs_quad(q, xnew, k7, bks[6]);
+        // e1 k1 + e3 k3 + ...: the second product rounded, the first fused, as in rk_stages_row_coef
+        const double e1 = lead<QL_ERR1>(vecB), e3 = lead<QL_ERR3>(vecB);
+        SEP_UNROLL for (int c = 0; c < QUAD_SLOTS; ++c) xerr[c] = fma(e1, k1[c], e3 * k3[c]);
+        asm(SEP_QTERM3(1) SEP_QTERM3(2) SEP_QTERM3(3) SEP_QTERM3(4)
+            : SEP_QACC3(xerr) : SEP_QIN3(1, QD_DC4, k4), SEP_QIN3(2, QD_DC5, k5), SEP_QIN3(3, QD_DC6, k6), SEP_QIN3(4, QD_DC7, k7));
+    } else {
+        rhs_quad(q, x, k1, bks[0]);
+        first_term(xt, lead<QL_STAGE2>(vecB), 2);
+        {   // the third stage's first term of slot 1 rides in the second stage's contact sum
+            const double f1 = lead<QL_STAGE3>(vecB);
+            const double xt1 = rhs_quad_slots01_fill(q, xt, k2, bks[1], f1, k1[1], x[1]);
+            xt[0] = fma(f1, k1[0], x[0]);
+            xt[1] = xt1;
+        }
+        asm(SEP_QTERM2(1) : SEP_QACC2(xt) : SEP_QIN2(1, QK_A32, k2));
+        rhs_quad(q, xt, k3, bks[2]);
+        first_term(xt, lead<QL_STAGE4>(vecB), 2);
+        asm(SEP_QTERM2(1) SEP_QTERM2(2) : SEP_QACC2(xt) : SEP_QIN2(1, QK_A42, k2), SEP_QIN2(2, QK_A43, k3));
+        rhs_quad(q, xt, k4, bks[3]);
+        first_term(xt, lead<QL_STAGE5>(vecB), 2);
+        asm(SEP_QTERM2(1) SEP_QTERM2(2) SEP_QTERM2(3) : SEP_QACC2(xt) : SEP_QIN2(1, QK_A52, k2), SEP_QIN2(2, QK_A53, k3), SEP_QIN2(3, QK_A54, k4));
+        rhs_quad(q, xt, k5, bks[4]);
+        first_term(xt, lead<QL_STAGE6>(vecB), 2);
+        asm(SEP_QTERM2(1) SEP_QTERM2(2) SEP_QTERM2(3) SEP_QTERM2(4)
+            : SEP_QACC2(xt) : SEP_QIN2(1, QK_A62, k2), SEP_QIN2(2, QK_A63, k3), SEP_QIN2(3, QK_A64, k4), SEP_QIN2(4, QK_A65, k5));
+        rhs_quad(q, xt, k6, bks[5]);
+        first_term(xnew, lead<QL_NEW>(vecB), 3);
+        asm(SEP_QTERM3(1) SEP_QTERM3(2) SEP_QTERM3(3) : SEP_QACC3(xnew) : SEP_QIN3(1, QK_B3, k3), SEP_QIN3(2, QK_B4, k4), SEP_QIN3(3, QK_B6, k6));
+        // here the FIRST product is rounded and the second fused, as in rk_stages_row_coef
+        const double e1 = lead<QL_ERR1>(vecB), e3 = lead<QL_ERR3>(vecB);
+        SEP_UNROLL for (int c = 0; c < QUAD_SLOTS; ++c) xerr[c] = fma(e3, k3[c], e1 * k1[c]);
+        asm(SEP_QTERM3(1) SEP_QTERM3(2) SEP_QTERM3(3) : SEP_QACC3(xerr) : SEP_QIN3(1, QK_DB4, k4), SEP_QIN3(2, QK_DB5, k5), SEP_QIN3(3, QK_DB6, k6));
+    }
 }
 
 #else
@@ -659,8 +803,7 @@ __global__ __launch_bounds__(FUSED ? 8 * WAVE : WAVE, 2) void sepaihrd_eval_quad
         double k2[NS], k3[NS], k4[NS], k5[NS], k6[NS], k7[NS];
         double xnew[NS], xerr[NS];
 #if SEPAIHRD_ARITH_FMA
-        rk_stages_row_coef<SOLVER, NS>(cur, vecA, vecB, x, k1, k2, k3, k4, k5, k6, k7, xnew, xerr, bks,
-                                       [&](const double (&xin)[NS], double (&kout)[NS], double bk) { rhs_quad(q, xin, kout, bk); });
+        rk_stages_quad<SOLVER>(q, vecA, vecB, x, k1, k2, k3, k4, k5, k6, k7, xnew, xerr, bks);
 #else
         double xt[NS];
         if (SOLVER == 0) {
@@ -829,11 +972,11 @@ __global__ __launch_bounds__(FUSED ? 8 * WAVE : WAVE, 2) void sepaihrd_eval_quad
         }
         const double cur = lane_of(act) ? cur_m : 1.0;  // a finished chain idles on a harmless step
 #if SEPAIHRD_ARITH_FMA
-        // the chain's step times sixteen (+2) tableau coefficients, one per lane of its row.  Their first DPP read is the
-        // third stage's sum, dozens of instructions later; that no DPP read of ANY inline-asm operand follows its VALU
-        // write within two wait states is checked on the listing (tools/check_dpp_hazards.py, run by the test suite)
+        // the chain's step times sixteen (+10) tableau coefficients, one per lane of its row.  Their first DPP read is the
+        // second stage's leading factor, behind the segment test below; that no DPP read of ANY inline-asm operand follows
+        // its VALU write within two wait states is checked on the listing (tools/check_dpp_hazards.py, run by the test suite)
         double vecA, vecB;
-        asm("v_mul_f64 %0, %2, %3\n\tv_mul_f64 %1, %2, %4" : "=&v"(vecA), "=&v"(vecB) : "v"(cur), "v"(coefA), "v"(coefB));
+        asm("v_mul_f64 %1, %2, %4\n\tv_mul_f64 %0, %2, %3" : "=&v"(vecA), "=&v"(vecB) : "v"(cur), "v"(coefA), "v"(coefB));  // B first: it is read first
 #else
         const double vecA = cur * coefA, vecB = cur * coefB;  // the strict build's factors: strict_coef<>() hands them out
 #endif

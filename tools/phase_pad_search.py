@@ -19,7 +19,7 @@ def evaluate(job):
     base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
             "-ffp-contract=off", "-DSEPAIHRD_ARITH_FMA=0", *flags, "--cuda-device-only", "-S", os.path.join(CSRC, "sepaihrd_kernels.hip"), "-o", dev]
     subprocess.run(base, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    subprocess.run(["python3", os.path.join(CSRC, "phase_pass.py"), dev, phased], check=True, stdout=subprocess.DEVNULL)
+    subprocess.run(["python3", os.path.join(CSRC, "phase_pass.py"), dev, phased, "--greedy"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run([cp.LLVM + "/clang", "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", phased, "-o", obj], check=True)
     dis = subprocess.run([cp.LLVM + "/llvm-objdump", "-d", obj], check=True, capture_output=True, text=True).stdout
     best = None
