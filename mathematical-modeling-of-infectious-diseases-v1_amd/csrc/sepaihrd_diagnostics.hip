@@ -36,6 +36,7 @@
 
 #include "sepaihrd_device.h"
 #include "sepaihrd_host_util.h"
+#include "sepaihrd_quantile.inc"  // the project's type-7 rule
 
 namespace sepaihrd {
 namespace {
@@ -87,14 +88,6 @@ __device__ inline double series_value(const DiagArgs& a, int g, int kind, size_t
         case 3: return a.xs[e] <= a.info[g * INFO_W + I_Q05] ? 1.0 : 0.0;
         default: return a.xs[e] <= a.info[g * INFO_W + I_Q95] ? 1.0 : 0.0;
     }
-}
-
-// type-7 quantile of n sorted values (the project's rule: v[floor pos] (1 - frac) + v[floor pos + 1] frac)
-__device__ inline double quantile_sorted(const double* v, size_t n, double q) {
-    const double pos = q * (double)(n - 1);
-    const size_t idx = (size_t)floor(pos);
-    const double frac = pos - (double)idx;
-    return (idx + 1 < n) ? v[idx] * (1.0 - frac) + v[idx + 1] * frac : v[idx];
 }
 
 // number of sorted values <= x
@@ -209,8 +202,8 @@ __global__ void diag_all_quantiles_kernel(const DiagArgs a, const double* sorted
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.G) return;
     const double* v = sorted + (size_t)g * a.CN;
-    a.info[g * INFO_W + I_Q05] = quantile_sorted(v, a.CN, 0.05);
-    a.info[g * INFO_W + I_Q95] = quantile_sorted(v, a.CN, 0.95);
+    a.info[g * INFO_W + I_Q05] = sepaihrd_quantile::sorted_quantile(v, a.CN, 0.05);
+    a.info[g * INFO_W + I_Q95] = sepaihrd_quantile::sorted_quantile(v, a.CN, 0.95);
 }
 
 // ---- average ranks -> normal scores, written back to the draw's split position
@@ -245,8 +238,8 @@ __global__ void diag_split_info_kernel(const DiagArgs a, const double* sorted, c
     double* info = a.info + g * INFO_W;
     info[I_MED] = (v[S / 2 - 1] + v[S / 2]) / 2.0;
     if (even) {
-        info[I_Q05] = quantile_sorted(v, S, 0.05);
-        info[I_Q95] = quantile_sorted(v, S, 0.95);
+        info[I_Q05] = sepaihrd_quantile::sorted_quantile(v, S, 0.05);
+        info[I_Q95] = sepaihrd_quantile::sorted_quantile(v, S, 0.95);
     }
     info[I_XS_CONST] = !(v[S - 1] - v[0] >= DBL_EPSILON) ? 1.0 : 0.0;
     info[I_Z_CONST] = (v[0] == v[S - 1]) ? 1.0 : 0.0;

@@ -10,8 +10,7 @@
 //              cumulative = running sum of the daily values in time order; X in {CumH, CumICU, D}
 //   sero       src/model/MetricsCalculator.cpp:199-226  (sum N - sum_a S_a(t)) / sum N, every time
 //   Rt         src/model/ReproductionNumberCalculator.cpp:55-171  spectral radius of F V^-1 (below)
-//   quantile   src/model/PostCalibrationAnalyser.cpp:303-340  exact sort, pos = q (n - 1),
-//              v[floor pos] (1 - frac) + v[floor pos + 1] frac
+//   quantile   src/model/PostCalibrationAnalyser.cpp:303-340  exact sort, then the rule of csrc/sepaihrd_quantile.inc
 // The reference feeds the six incidence series through Boost.Accumulators' P^2 estimator
 // (ResultAggregator.cpp:226-244, order-dependent, third-party); here every series uses the exact
 // sort rule of PostCalibrationAnalyser, as SURVEY 8f prescribes.
@@ -22,7 +21,9 @@
 // loads its segment coalesced, sorts it in LDS (bitonic, up to 16384 doubles = 128 KiB) and
 // interpolates the quantiles.  Samples whose integration failed are +inf and sort to the end; the
 // quantile positions use the count of valid samples.  How a segment is padded and when it is sorted
-// in global memory instead: csrc/sepaihrd_segments.h; the one dispatch: sort_segments_and_pick below.
+// in global memory instead: csrc/sepaihrd_segments.h; the one dispatch: sort_segments_and_pick below, under the one kernel
+// pair (segment_sort_pick_kernel, segment_pick_sorted_kernel) and the one launcher (launch_sort_pick) that every summary
+// here instantiates with its own pick: EnsemblePick, ScenarioPick, StochSirPick.
 // Compiled with -ffp-contract=off: the interpolation is the CPU build's operation sequence.
 // =============================================================================
 #include <hip/hip_runtime.h>
@@ -34,9 +35,11 @@
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
+#include "sepaihrd_bitonic.inc"
 #include "sepaihrd_device.h"
 #include "sepaihrd_host_util.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_quantile.inc"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_sir_device.h"
 #include "sepaihrd_stoch_device.h"
@@ -302,69 +305,61 @@ __global__ __launch_bounds__(WAVE) void ensemble_metrics_kernel(const EnsembleAr
     out[8] = max_rt; out[9] = min_rt; out[10] = final_rt; out[11] = sero64;
 }
 
-// quantile p of sorted segment `sid` (nv valid values first, +inf after them) into its output slot
-__device__ __forceinline__ void write_quantile(const EnsembleArgs& a, int n_series_segments, size_t sid, int p, int nv,
-                                               const double* seg) {
-    double r = NAN;
-    if (nv > 0) {
-        const double pos = a.probs[p] * (double)(size_t)(nv - 1);
-        const size_t idx = (size_t)pos;
-        const double frac = pos - (double)idx;
-        r = (idx + 1 < (size_t)nv) ? seg[idx] * (1.0 - frac) + seg[idx + 1] * frac : seg[idx];
-    }
-    if ((int)sid < n_series_segments) {
-        const int age = (int)(sid % a.n);
-        const int t = (int)((sid / a.n) % a.Tp);
-        const int ser = (int)(sid / ((size_t)a.n * a.Tp));
-        a.q_out[(((size_t)ser * a.n_probs + p) * a.Tp + t) * a.n + age] = r;
-    } else if (a.rt_out != nullptr && (int)sid >= a.rt_segment0) {
-        a.rt_out[(size_t)p * a.T + (sid - (size_t)a.rt_segment0)] = r;
-    } else {
-        const size_t k = sid - (size_t)n_series_segments;
-        a.sero_out[(size_t)p * a.T + k] = r;
-    }
-}
+// ---- sort and pick: every summary across samples sorts segments of values (+inf padding last) and picks a few numbers from
+// each.  A pick is a functor passed to the kernels by value, carrying its caller's argument struct: picks() numbers per
+// segment, operator()(sid, p, sorted segment) stores number p of segment sid, SORTED_BLOCK is the workgroup of the sorted kernel.
 
 // Np (a power of two) doubles of src sorted ascending into seg (LDS) by the whole workgroup
 __device__ __forceinline__ void lds_bitonic_sort(double* seg, const double* src, const int Np) {
     const int tid = threadIdx.x, BS = blockDim.x;
     for (int i = tid; i < Np; i += BS) seg[i] = src[i];
     __syncthreads();
-    for (int k = 2; k <= Np; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (Np >> 1); i += BS) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));  // index with bit j clear
-                const int hi = lo | j;
-                const bool up = (lo & k) == 0;
-                const double x = seg[lo], y = seg[hi];
-                if ((x > y) == up) { seg[lo] = y; seg[hi] = x; }
-            }
-            __syncthreads();
+    bitonic_sort_pow2(seg, Np);
+}
+
+// one workgroup per segment of Np doubles: bitonic sort in LDS, then thread p stores pick p
+template <class Pick>
+__global__ void segment_sort_pick_kernel(const Pick pick, const double* vals, const int Np) {
+    extern __shared__ double seg[];
+    const size_t sid = blockIdx.x;
+    lds_bitonic_sort(seg, vals + sid * (size_t)Np, Np);
+    for (int p = threadIdx.x; p < pick.picks(); p += blockDim.x) pick(sid, p, seg);
+}
+
+// Segments beyond the LDS sort: those of a group were sorted in global memory by the library's segmented radix sort; one
+// thread per (segment of the group, pick).
+template <class Pick>
+__global__ __launch_bounds__(Pick::SORTED_BLOCK) void segment_pick_sorted_kernel(const Pick pick, const double* sorted, const int Np,
+                                                                                 const int first_segment, const int n_group) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int picks = pick.picks();
+    if (idx >= (size_t)n_group * picks) return;
+    const int g = (int)(idx / picks), p = (int)(idx % picks);
+    pick((size_t)(first_segment + g), p, sorted + (size_t)g * Np);
+}
+
+// quantile p of sorted segment `sid` (*n_valid valid values first, +inf after them) into its output slot
+struct EnsemblePick {
+    static constexpr int SORTED_BLOCK = 256;
+    EnsembleArgs a;
+    int n_series_segments;
+    __host__ __device__ int picks() const { return a.n_probs; }
+    __device__ void operator()(size_t sid, int p, const double* seg) const {
+        const int nv = *a.n_valid;
+        const double r = nv > 0 ? sepaihrd_quantile::sorted_quantile(seg, (size_t)nv, a.probs[p]) : NAN;
+        if ((int)sid < n_series_segments) {
+            const int age = (int)(sid % a.n);
+            const int t = (int)((sid / a.n) % a.Tp);
+            const int ser = (int)(sid / ((size_t)a.n * a.Tp));
+            a.q_out[(((size_t)ser * a.n_probs + p) * a.Tp + t) * a.n + age] = r;
+        } else if (a.rt_out != nullptr && (int)sid >= a.rt_segment0) {
+            a.rt_out[(size_t)p * a.T + (sid - (size_t)a.rt_segment0)] = r;
+        } else {
+            const size_t k = sid - (size_t)n_series_segments;
+            a.sero_out[(size_t)p * a.T + k] = r;
         }
     }
-}
-
-// Pass 2: one workgroup per segment; bitonic sort in LDS, then the interpolated quantiles.
-__global__ void ensemble_quantile_kernel(const EnsembleArgs a, const int n_series_segments) {
-    extern __shared__ double seg[];
-    const int Np = a.S_pad;
-    const int tid = threadIdx.x, BS = blockDim.x;
-    const size_t sid = blockIdx.x;
-    const double* src = a.vals + sid * (size_t)Np;
-    lds_bitonic_sort(seg, src, Np);
-    const int nv = *a.n_valid;
-    for (int p = tid; p < a.n_probs; p += BS) write_quantile(a, n_series_segments, sid, p, nv, seg);
-}
-
-// Large ensembles (more samples than fit LDS): the segments of a group were sorted in global memory by the
-// library's segmented radix sort; one thread per (segment, probability) interpolates.
-__global__ void ensemble_quantile_sorted_kernel(const EnsembleArgs a, const int n_series_segments, const double* sorted,
-                                                const int first_segment, const int n_group) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)n_group * a.n_probs) return;
-    const int g = (int)(idx / a.n_probs), p = (int)(idx % a.n_probs);
-    write_quantile(a, n_series_segments, (size_t)(first_segment + g), p, *a.n_valid, sorted + (size_t)g * a.S_pad);
-}
+};
 
 // ---- scenario analysis (sepaihrd_scenario_ensemble): metric table [K][S][W] -> per-scenario summaries ----
 // Segment (k, col) of the metric values and of the paired differences metric[k][s] - metric[0][s]; samples that failed
@@ -449,37 +444,22 @@ __global__ __launch_bounds__(64) void scenario_moments_kernel(const ScenarioArgs
 }
 
 // quantile p of sorted segment `sid` (metric segments first, then the paired differences) into its output slot
-__device__ __forceinline__ void scenario_write_quantile(const ScenarioArgs& a, size_t sid, int p, const double* seg) {
-    const bool paired = sid >= (size_t)a.K * a.W;
-    const size_t cell = paired ? sid - (size_t)a.K * a.W : sid;
-    const int nv = a.counts[(paired ? a.K : 0) + (int)(cell / a.W)];
-    double r = NAN;
-    if (nv > 0) {
-        const double pos = a.probs[p] * (double)(size_t)(nv - 1);
-        const size_t idx = (size_t)pos;
-        const double frac = pos - (double)idx;
-        r = (idx + 1 < (size_t)nv) ? seg[idx] * (1.0 - frac) + seg[idx + 1] * frac : seg[idx];
+struct ScenarioPick {
+    static constexpr int SORTED_BLOCK = 256;
+    ScenarioArgs a;
+    __host__ __device__ int picks() const { return a.n_probs; }
+    __device__ void operator()(size_t sid, int p, const double* seg) const {
+        const bool paired = sid >= (size_t)a.K * a.W;
+        const size_t cell = paired ? sid - (size_t)a.K * a.W : sid;
+        const int nv = a.counts[(paired ? a.K : 0) + (int)(cell / a.W)];
+        const double r = nv > 0 ? sepaihrd_quantile::sorted_quantile(seg, (size_t)nv, a.probs[p]) : NAN;
+        if (paired) {
+            if (a.diff_out != nullptr) a.diff_out[cell * a.n_probs + p] = r;
+        } else if (a.summary_out != nullptr) {
+            a.summary_out[cell * (2 + a.n_probs) + 2 + p] = r;
+        }
     }
-    if (paired) {
-        if (a.diff_out != nullptr) a.diff_out[cell * a.n_probs + p] = r;
-    } else if (a.summary_out != nullptr) {
-        a.summary_out[cell * (2 + a.n_probs) + 2 + p] = r;
-    }
-}
-
-__global__ void scenario_quantile_kernel(const ScenarioArgs a) {
-    extern __shared__ double seg[];
-    const size_t sid = blockIdx.x;
-    lds_bitonic_sort(seg, a.vals + sid * (size_t)a.S_pad, a.S_pad);
-    for (int p = threadIdx.x; p < a.n_probs; p += blockDim.x) scenario_write_quantile(a, sid, p, seg);
-}
-
-__global__ void scenario_quantile_sorted_kernel(const ScenarioArgs a, const double* sorted, const int first_segment, const int n_group) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)n_group * a.n_probs) return;
-    const int g = (int)(idx / a.n_probs), p = (int)(idx % a.n_probs);
-    scenario_write_quantile(a, (size_t)(first_segment + g), p, sorted + (size_t)g * a.S_pad);
-}
+};
 
 // Segments of S_pad doubles (more than the LDS sort holds) sorted in groups by rocPRIM's segmented radix sort into
 // `scratch`; pick(first, n_group) launches the interpolation of each sorted group.  Synchronises the stream.
@@ -536,19 +516,35 @@ int sort_segments_and_pick(const SegmentPlan& plan, int segments, const double* 
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// the interpolated quantiles of `segments` segments of e.vals (e.S_pad apart, e.n_valid values each) into e's outputs
-int launch_segment_quantiles(const EnsembleArgs& e, int n_series_segments, int segments, double* scratch, size_t scratch_doubles,
-                             hipStream_t st, bool lds_limit_raised = false) {
+// events and the sum that time every sorted pick of a call (launch_stoch_sir_summaries); null: untimed
+struct PickTimer {
+    hipEvent_t ev0, ev1;
+    double* ms;
+};
+
+// The one launcher: `segments` segments of vals, `pad` doubles apart, are sorted and `pick` takes its numbers from each.
+// lds_limit_raised: the caller has raised the LDS limit of this pick's segment_sort_pick_kernel already.
+template <class Pick>
+int launch_sort_pick(const Pick& pick, const double* vals, int pad, int segments, double* scratch, size_t scratch_doubles, hipStream_t st,
+                     bool lds_limit_raised = false, const PickTimer* timer = nullptr) {
     return sort_segments_and_pick(
-        plan_of_pad((size_t)e.S_pad), segments, e.vals, scratch, scratch_doubles, st,
-        lds_limit_raised ? nullptr : reinterpret_cast<const void*>(&ensemble_quantile_kernel),
+        plan_of_pad((size_t)pad), segments, vals, scratch, scratch_doubles, st,
+        lds_limit_raised ? nullptr : reinterpret_cast<const void*>(&segment_sort_pick_kernel<Pick>),
         [&](int threads, size_t lds) {
-            hipLaunchKernelGGL(ensemble_quantile_kernel, dim3((unsigned)segments), dim3(threads), lds, st, e, n_series_segments);
+            hipLaunchKernelGGL(segment_sort_pick_kernel<Pick>, dim3((unsigned)segments), dim3(threads), lds, st, pick, vals, pad);
         },
         [&](int first, int ng) {
-            const size_t work = (size_t)ng * e.n_probs;
-            hipLaunchKernelGGL(ensemble_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, e,
-                               n_series_segments, scratch, first, ng);
+            constexpr int BLOCK = Pick::SORTED_BLOCK;
+            const size_t work = (size_t)ng * pick.picks();
+            if (timer) (void)hipEventRecord(timer->ev0, st);
+            hipLaunchKernelGGL(segment_pick_sorted_kernel<Pick>, dim3((unsigned)((work + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, pick,
+                               scratch, pad, first, ng);
+            if (timer) {
+                float ms = 0.0f;
+                (void)hipEventRecord(timer->ev1, st);
+                if (hipEventSynchronize(timer->ev1) == hipSuccess && hipEventElapsedTime(&ms, timer->ev0, timer->ev1) == hipSuccess)
+                    *timer->ms += (double)ms;
+            }
         });
 }
 
@@ -698,15 +694,7 @@ int launch_scenario_summaries(const ScenarioArgs& a, void* stream) {
     hipLaunchKernelGGL(scenario_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a);
     if (a.summary_out != nullptr)
         hipLaunchKernelGGL(scenario_moments_kernel, dim3((unsigned)((a.K * a.W + 63) / 64)), dim3(64), 0, st, a);
-    return sort_segments_and_pick(
-        plan_of_pad((size_t)a.S_pad), segments, a.vals, a.sort_scratch, a.sort_scratch_doubles, st,
-        reinterpret_cast<const void*>(&scenario_quantile_kernel),
-        [&](int threads, size_t lds) { hipLaunchKernelGGL(scenario_quantile_kernel, dim3(segments), dim3(threads), lds, st, a); },
-        [&](int first, int ng) {
-            const size_t work = (size_t)ng * a.n_probs;
-            hipLaunchKernelGGL(scenario_quantile_sorted_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a,
-                               a.sort_scratch, first, ng);
-        });
+    return launch_sort_pick(ScenarioPick{a}, a.vals, a.S_pad, segments, a.sort_scratch, a.sort_scratch_doubles, st);
 }
 
 int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
@@ -728,7 +716,7 @@ int launch_ensemble_summaries(const EnsembleArgs& a, void* stream) {
         hipLaunchKernelGGL(ensemble_metrics_kernel, dim3((unsigned)((a.S + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, a, *a.pb, a.theta);
     }
     const int segments = n_series_segments + (sero ? a.T : 0) + (rt ? a.T : 0);
-    return launch_segment_quantiles(a, n_series_segments, segments, a.sort_scratch, a.sort_scratch_doubles, st);
+    return launch_sort_pick(EnsemblePick{a, n_series_segments}, a.vals, a.S_pad, segments, a.sort_scratch, a.sort_scratch_doubles, st);
 }
 
 }  // namespace sepaihrd
@@ -753,7 +741,7 @@ int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
     // the series' quantiles: the segment sort and the interpolation of sepaihrd_ensemble_quantiles, per scenario (each has
     // its own count of valid samples), with (T, n + 1) in the place of (Tp, n) and no seroprevalence / Rt block; the LDS
     // limit is raised once for all scenarios
-    if (raise_lds_limit(plan_of_pad((size_t)a.S_pad), reinterpret_cast<const void*>(&ensemble_quantile_kernel)) != 0) return -3;
+    if (raise_lds_limit(plan_of_pad((size_t)a.S_pad), reinterpret_cast<const void*>(&segment_sort_pick_kernel<EnsemblePick>)) != 0) return -3;
     for (int k = 0; k < a.K; ++k) {
         EnsembleArgs e{};
         e.S = a.S; e.S_pad = a.S_pad; e.lpc = a.lpc; e.n = a.n + 1; e.T = a.T; e.Tp = a.T;
@@ -764,7 +752,8 @@ int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
         e.rt_segment0 = rows;
         hipLaunchKernelGGL(ensemble_count_valid_kernel, dim3(1), dim3(256), 0, st, a.status + (size_t)k * a.S, a.S, e.n_valid);
         if (a.q_out == nullptr) continue;
-        const int rc = launch_segment_quantiles(e, rows, rows, a.sort_scratch, a.sort_scratch_doubles, st, /*lds_limit_raised=*/true);
+        const int rc = launch_sort_pick(EnsemblePick{e, rows}, e.vals, e.S_pad, rows, a.sort_scratch, a.sort_scratch_doubles, st,
+                                        /*lds_limit_raised=*/true);
         if (rc != 0) return rc;  // a failed sort of scenario k ends the call at once
     }
     if (hipGetLastError() != hipSuccess) return -3;
@@ -785,30 +774,19 @@ int launch_sir_ensemble_summaries(const SirEnsSummaryArgs& a, void* stream) {
 namespace sepaihrd {
 namespace {
 
-// statistic `stat` of sorted segment `sid` of the chunk into stats[g][stat][compartment][step0 + local step]
-__device__ __forceinline__ void stoch_write_stat(const StochSummaryArgs& a, size_t sid, int stat, const double* seg) {
-    const int s = (int)(sid % (size_t)a.chunk_steps);
-    const size_t gc = sid / (size_t)a.chunk_steps;  // group 3 + compartment
-    const size_t g = gc / 3, comp = gc % 3;
-    a.stats[((g * 4 + (size_t)stat) * 3 + comp) * (size_t)a.steps + (size_t)(a.step0 + s)] = sepaihrd_stoch::sorted_stat(seg, a.R, stat);
-}
-
-// one workgroup per segment: bitonic sort in LDS, then one thread per statistic (the mean's recurrence is serial)
-__global__ void stoch_sir_summary_kernel(const StochSummaryArgs a) {
-    extern __shared__ double seg[];
-    const size_t sid = blockIdx.x;
-    lds_bitonic_sort(seg, a.vals + sid * (size_t)a.R_pad, a.R_pad);
-    if (threadIdx.x < 4) stoch_write_stat(a, sid, (int)threadIdx.x, seg);
-}
-
-// beyond the LDS sort: one thread per (segment, statistic) of a group of globally sorted segments
-__global__ __launch_bounds__(64) void stoch_sir_summary_sorted_kernel(const StochSummaryArgs a, const double* sorted, const int first_segment,
-                                                                      const int n_group) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)n_group * 4) return;
-    const int g = (int)(idx / 4), stat = (int)(idx % 4);
-    stoch_write_stat(a, (size_t)(first_segment + g), stat, sorted + (size_t)g * a.R_pad);
-}
+// statistic `stat` of sorted segment `sid` of the chunk into stats[g][stat][compartment][step0 + local step]: one thread per
+// statistic (the mean's recurrence is serial)
+struct StochSirPick {
+    static constexpr int SORTED_BLOCK = 64;
+    StochSummaryArgs a;
+    __host__ __device__ int picks() const { return 4; }
+    __device__ void operator()(size_t sid, int stat, const double* seg) const {
+        const int s = (int)(sid % (size_t)a.chunk_steps);
+        const size_t gc = sid / (size_t)a.chunk_steps;  // group 3 + compartment
+        const size_t g = gc / 3, comp = gc % 3;
+        a.stats[((g * 4 + (size_t)stat) * 3 + comp) * (size_t)a.steps + (size_t)(a.step0 + s)] = sepaihrd_stoch::sorted_stat(seg, a.R, stat);
+    }
+};
 
 }  // namespace
 
@@ -818,23 +796,11 @@ int launch_stoch_sir_summaries(const StochSummaryArgs& a, void* stream) {
     if (a.G <= 0 || a.R <= 0 || a.chunk_steps <= 0 || a.step0 < 0 || a.step0 + a.chunk_steps > a.steps || segments >= ((size_t)1 << 31) ||
         !pad_legal((size_t)a.R, a.R_pad))
         return -4;
-    return sort_segments_and_pick(
-        plan_of_pad((size_t)a.R_pad), (int)segments, a.vals, a.sort_scratch, a.sort_scratch_doubles, st,
-        reinterpret_cast<const void*>(&stoch_sir_summary_kernel),
-        [&](int threads, size_t lds) { hipLaunchKernelGGL(stoch_sir_summary_kernel, dim3((unsigned)segments), dim3(threads), lds, st, a); },
-        [&](int first, int ng) {
-            const bool timed = a.summary_ms != nullptr && a.ev[0] != nullptr && a.ev[1] != nullptr;
-            if (timed) (void)hipEventRecord(static_cast<hipEvent_t>(a.ev[0]), st);
-            hipLaunchKernelGGL(stoch_sir_summary_sorted_kernel, dim3((unsigned)(((size_t)ng * 4 + 63) / 64)), dim3(64), 0, st, a,
-                               a.sort_scratch, first, ng);
-            if (timed) {
-                float ms = 0.0f;
-                (void)hipEventRecord(static_cast<hipEvent_t>(a.ev[1]), st);
-                if (hipEventSynchronize(static_cast<hipEvent_t>(a.ev[1])) == hipSuccess &&
-                    hipEventElapsedTime(&ms, static_cast<hipEvent_t>(a.ev[0]), static_cast<hipEvent_t>(a.ev[1])) == hipSuccess)
-                    *a.summary_ms += (double)ms;
-            }
-        });
+    // summary_ms takes the sorted pick of every group (the LDS route is one launch and is not timed here)
+    const PickTimer timer{static_cast<hipEvent_t>(a.ev[0]), static_cast<hipEvent_t>(a.ev[1]), a.summary_ms};
+    const bool timed = a.summary_ms != nullptr && a.ev[0] != nullptr && a.ev[1] != nullptr;
+    return launch_sort_pick(StochSirPick{a}, a.vals, a.R_pad, (int)segments, a.sort_scratch, a.sort_scratch_doubles, st,
+                            /*lds_limit_raised=*/false, timed ? &timer : nullptr);
 }
 
 }  // namespace sepaihrd
@@ -854,7 +820,7 @@ int launch_predictive_quantiles(const PredictiveArgs& a, void* stream) {
     e.vals = a.vals; e.q_out = a.q_out;
     e.n_valid = a.counts + 1;
     e.rt_segment0 = (int)segments;
-    return launch_segment_quantiles(e, (int)segments, (int)segments, a.sort_scratch, a.sort_scratch_doubles, st);
+    return launch_sort_pick(EnsemblePick{e, (int)segments}, e.vals, e.S_pad, (int)segments, a.sort_scratch, a.sort_scratch_doubles, st);
 }
 
 }  // namespace sepaihrd

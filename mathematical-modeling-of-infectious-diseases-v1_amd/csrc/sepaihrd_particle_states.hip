@@ -10,6 +10,7 @@
 
 #include <string>
 
+#include "sepaihrd_bitonic.inc"
 #include "sepaihrd_device.h"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_host_util.h"
@@ -64,9 +65,8 @@ __global__ __launch_bounds__(STATES_GATHER_BLOCK) void states_gather_kernel(cons
 }
 
 // One workgroup per (theta of the chunk, count, series).  The J values of the segment, +inf up to the power of two Np = pad,
-// are sorted ascending by the bitonic network of csrc/sepaihrd_ensemble.hip -- in LDS where Np <= ENSEMBLE_MAX_SAMPLES, in the
-// segment itself beyond (a barrier ends every round and makes a wave's stores visible to the workgroup, as in
-// wide_resample_kernel).  The sum is taken in 64-bit integers before the sort.  Thread 0 writes the mean, thread p quantile p.
+// are sorted ascending by the bitonic network of csrc/sepaihrd_bitonic.inc -- in LDS where Np <= ENSEMBLE_MAX_SAMPLES, in the
+// segment itself beyond.  The sum is taken in 64-bit integers before the sort.  Thread 0 writes the mean, thread p quantile p.
 // An invalid theta's workgroup writes NaN.
 __global__ __launch_bounds__(STATES_SORT_BLOCK) void states_sort_pick_kernel(const StatesRow r) {
     extern __shared__ double lds_seg[];
@@ -96,25 +96,14 @@ __global__ __launch_bounds__(STATES_SORT_BLOCK) void states_sort_pick_kernel(con
     for (int off = WAVE / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, WAVE);
     if ((tid & (WAVE - 1)) == 0) part[tid / WAVE] = sum;
     __syncthreads();
-    for (int kk = 2; kk <= Np; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < (Np >> 1); i += BS) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));  // index with bit j clear
-                const int hi = lo | j;
-                const bool up = (lo & kk) == 0;
-                const double x = seg[lo], y = seg[hi];
-                if ((x > y) == up) { seg[lo] = y; seg[hi] = x; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_pow2(seg, Np);
     if (tid == 0) {
         long long total = 0;
         for (int w = 0; w < (BS + WAVE - 1) / WAVE; ++w) total += part[w];
         *mean = ps::mean_of((int64_t)total, J);
     }
     if (q != nullptr)
-        for (int p = tid; p < r.n_probs; p += BS) q[p] = ps::quantile_of(seg, J, r.probs[p]);
+        for (int p = tid; p < r.n_probs; p += BS) q[p] = sepaihrd_quantile::sorted_quantile(seg, (size_t)J, r.probs[p]);
 }
 
 // the dynamic LDS of the sort of `pad` doubles: the segment where it is sorted in LDS, nothing where it is sorted in place

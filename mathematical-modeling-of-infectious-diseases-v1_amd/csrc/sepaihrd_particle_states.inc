@@ -14,11 +14,9 @@
 // The mean.  mean[k][c][a] = (double)(sum_j count_j) / (double)J with the sum in 64-bit integers: exact and independent of the
 // order of the additions (2^31 x 65 536 x 16 < 2^53).
 //
-// The quantiles.  For each probability p of the caller's list, over the J values sorted ascending:
-//     pos = p (J - 1), idx = (size_t)pos, frac = pos - idx,
-//     v[idx] (1 - frac) + v[idx + 1] frac   where idx + 1 < J, else v[idx]
-// -- two products and one sum, not contracted: write_quantile of csrc/sepaihrd_ensemble.hip and the predictive twin's.  The values
-// are integers below 2^35; sorting them as integers and converting the two picked ones is sorting them as doubles.
+// The quantiles.  For each probability p of the caller's list, the rule of csrc/sepaihrd_quantile.inc over the J values sorted
+// ascending, as the ensemble summaries and the predictive twin apply it.  The values are integers below 2^35; sorting them as
+// integers and converting the two picked ones is sorting them as doubles.
 //
 // An invalid theta has NaN everywhere.
 // Included by csrc/sepaihrd_particle_states.hip and by the host library (host/src/HipParticleFilter.cpp), contraction off.
@@ -27,21 +25,13 @@
 #include <stdint.h>
 
 #include "sepaihrd_particle.inc"
+#include "sepaihrd_quantile.inc"
 
 namespace sepaihrd_particle_states {
 
 constexpr int MAX_PROBS = 64;  // probabilities per call
 
 SEP_RNG_FN double mean_of(int64_t sum, int J) { return (double)sum / (double)J; }
-
-// quantile p of v[0 .. J - 1], sorted ascending; V an integer or floating type
-template <class V>
-SEP_RNG_FN double quantile_of(const V* v, int J, double p) {
-    const double pos = p * (double)(size_t)(J - 1);
-    const size_t idx = (size_t)pos;
-    const double frac = pos - (double)idx;
-    return (idx + 1 < (size_t)J) ? (double)v[idx] * (1.0 - frac) + (double)v[idx + 1] * frac : (double)v[idx];
-}
 
 // a probability the call takes: in [0, 1] (a NaN fails both comparisons)
 SEP_RNG_FN bool probability_ok(double p) { return p >= 0.0 && p <= 1.0; }

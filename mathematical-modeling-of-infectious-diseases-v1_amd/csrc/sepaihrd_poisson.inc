@@ -68,15 +68,6 @@ SEP_RNG_FN double poisson(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, 
     }
 }
 
-// quantile f of n values sorted ascending: the expression of csrc/sepaihrd_ensemble.hip's write_quantile
-// (PostCalibrationAnalyser.cpp:316-326)
-SEP_RNG_FN double sorted_quantile(const double* x, size_t n, double f) {
-    const double pos = f * (double)(n - 1);
-    const size_t idx = (size_t)pos;
-    const double frac = pos - (double)idx;
-    return (idx + 1 < n) ? x[idx] * (1.0 - frac) + x[idx + 1] * frac : x[idx];
-}
-
 // mid-PIT of an observation among n_draws draws, `less` of them below and `equal` of them at the observation
 SEP_RNG_FN double mid_pit(int64_t less, int64_t equal, int64_t n_draws) {
     return n_draws > 0 ? ((double)less + 0.5 * (double)equal) / (double)n_draws : __builtin_nan("");

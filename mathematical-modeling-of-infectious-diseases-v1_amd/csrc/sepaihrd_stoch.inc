@@ -25,6 +25,7 @@
 // device kernel agree bit for bit whatever libm the host has.
 // Included by csrc/sepaihrd_stoch_sir.hip and by the host library (host/src/HipStochasticSIR.cpp).
 #pragma once
+#include "sepaihrd_quantile.inc"
 #include "sepaihrd_rng.inc"
 
 namespace sepaihrd_stoch {
@@ -205,12 +206,7 @@ SEP_RNG_FN void sir_step(double& S, double& I, double& R, const Group& g, double
 // The summaries of one segment of R values sorted ascending (SIR_stochastic.cpp:244-250; GSL's definitions of
 // gsl_stats_mean, gsl_stats_median_from_sorted_data and gsl_stats_quantile_from_sorted_data, written down from memory --
 // GSL is not available to this build): stat 0 mean by the running recurrence, 1 median, 2 the 0.05 and 3 the 0.95 quantile.
-SEP_RNG_FN double sorted_quantile(const double* x, int R, double f) {
-    const double pos = f * (double)(R - 1);
-    const int lhs = (int)pos;
-    const double delta = pos - (double)lhs;
-    return (lhs + 1 < R) ? (1.0 - delta) * x[lhs] + delta * x[lhs + 1] : x[lhs];
-}
+SEP_RNG_FN double sorted_quantile(const double* x, int R, double f) { return sepaihrd_quantile::sorted_quantile(x, (size_t)R, f); }
 SEP_RNG_FN double sorted_stat(const double* x, int R, int stat) {
     if (stat == 0) {
         double m = 0.0;

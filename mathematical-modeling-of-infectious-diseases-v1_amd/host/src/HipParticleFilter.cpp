@@ -225,7 +225,7 @@ int hostParticleStates(const StochasticSEPAIHRDFixedData& pb, const ParticleObse
                 state_mean[cell] = ps::mean_of(sum, J);
                 if (state_quantiles) {
                     std::sort(v.begin(), v.end());
-                    for (int p = 0; p < n_probs; ++p) state_quantiles[cell * (size_t)n_probs + (size_t)p] = ps::quantile_of(v.data(), J, probs[p]);
+                    for (int p = 0; p < n_probs; ++p) state_quantiles[cell * (size_t)n_probs + (size_t)p] = sepaihrd_quantile::sorted_quantile(v.data(), (size_t)J, probs[p]);
                 }
             }
     };

@@ -10,6 +10,7 @@
 #include <random>
 
 #include "sepaihrd_hip.h"
+#include "sepaihrd_quantile.inc"
 
 namespace epidemic {
 
@@ -191,12 +192,7 @@ std::map<std::string, AggregatedStats> HipPosteriorEnsemble::aggregateMetrics(co
         cols.push_back({"IICUR_age_" + std::to_string(a), [a](const EssentialMetrics& m) { return m.age_specific_IICUR[static_cast<size_t>(a)]; }});
         cols.push_back({"AttackRate_age_" + std::to_string(a), [a](const EssentialMetrics& m) { return m.age_specific_attack_rate[static_cast<size_t>(a)]; }});
     }
-    auto quantile = [](const std::vector<double>& v, double q) {  // PostCalibrationAnalyser.cpp:316-326
-        const double pos = q * (v.size() - 1);
-        const size_t idx = static_cast<size_t>(pos);
-        const double frac = pos - idx;
-        return idx + 1 < v.size() ? v[idx] * (1.0 - frac) + v[idx + 1] * frac : v[idx];
-    };
+    auto quantile = [](const std::vector<double>& v, double q) { return sepaihrd_quantile::sorted_quantile(v.data(), v.size(), q); };
     for (const auto& col : cols) {
         std::vector<double> v;
         for (const EssentialMetrics& m : rows) v.push_back(col.second(m));

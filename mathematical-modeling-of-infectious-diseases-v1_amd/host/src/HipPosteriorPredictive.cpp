@@ -9,6 +9,7 @@
 
 #include "sepaihrd_hip.h"
 #include "sepaihrd_poisson.inc"
+#include "sepaihrd_quantile.inc"
 
 namespace epidemic {
 
@@ -72,7 +73,7 @@ int hostPosteriorPredictive(const double* means, const int32_t* status, const do
             }
             std::sort(x, x + nd);
             for (int p = 0; p < n_probs; ++p)
-                pred_quantiles[((ser * (size_t)n_probs + (size_t)p) * Tp + t) * n + a] = nd > 0 ? sepaihrd_poisson::sorted_quantile(x, nd, probs[p]) : qnan;
+                pred_quantiles[((ser * (size_t)n_probs + (size_t)p) * Tp + t) * n + a] = nd > 0 ? sepaihrd_quantile::sorted_quantile(x, nd, probs[p]) : qnan;
         }
     }
     return SEPAIHRD_OK;

@@ -10,7 +10,7 @@
 
 #include "StochasticSEPAIHRDTwin.hpp"
 #include "sepaihrd_hip.h"
-#include "sepaihrd_poisson.inc"  // sorted_quantile: the quantile rule of the predictive twin
+#include "sepaihrd_quantile.inc"  // the quantile rule of the predictive twin
 
 namespace epidemic {
 
@@ -116,7 +116,7 @@ int hostStochasticSEPAIHRD(const StochasticSEPAIHRDFixedData& pb, const double* 
             double* xs = seg.data() + (size_t)sg * nd;
             std::sort(xs, xs + nd);
             for (int p = 0; p < n_probs; ++p)
-                quantiles[((ser * (size_t)n_probs + (size_t)p) * Tp + t) * nn + a] = nd > 0 ? sepaihrd_poisson::sorted_quantile(xs, nd, probs[p]) : qnan;
+                quantiles[((ser * (size_t)n_probs + (size_t)p) * Tp + t) * nn + a] = nd > 0 ? sepaihrd_quantile::sorted_quantile(xs, nd, probs[p]) : qnan;
         }
     }
     return SEPAIHRD_OK;
