@@ -136,7 +136,8 @@ enum sepaihrd_field {
     SEPAIHRD_F_ICU = 24,
     SEPAIHRD_F_D_H = 25,
     SEPAIHRD_F_D_ICU = 26,
-    SEPAIHRD_F_D_COMMUNITY = 27
+    SEPAIHRD_F_D_COMMUNITY = 27,
+    SEPAIHRD_F_DISPERSION = 28   /* index 0, 1, 2: the negative-binomial dispersion of the H, ICU, D series (sepaihrd_set_dispersion) */
 };
 
 /* Everything calculate() reads that does not depend on theta.  All pointers are HOST
@@ -1058,6 +1059,47 @@ int sepaihrd_particle_states_validate(int B, int J, int steps_per_interval, int 
  * filter and the summaries; of these the summaries' launches of the first chunk of parameter vectors -- the whole share of the
  * summaries where the call has one chunk (NaN on a grid of more than 1024 output rows). */
 int sepaihrd_particle_states_timing(const sepaihrd_ctx *ctx, double *ms);
+
+/* ---- negative-binomial observation model of the deterministic objective (additive; SEPAIHRD_ABI_VERSION stays) ----------------
+ * The reference's objective is Poisson.  Here each observed series (H, ICU, D) may have a dispersion k, +inf (the default: that
+ * series keeps the Poisson cell) or finite in [1e-3, 1e6], either fixed on the context (sepaihrd_set_dispersion) or calibrated: a
+ * theta entry with field SEPAIHRD_F_DISPERSION and param_index 0, 1, 2 for H, ICU, D, constrained like every other entry.
+ * For a usable cell (obs finite and >= 0) of a series with finite k, sim = max(0, increment) + 1e-10 as in the Poisson cell,
+ *     term = obs log(sim) - (obs + k) log(1 + sim / k)        (nb_term of the particle filters, sim real-valued)
+ *     g    = lgamma(obs + k) - lgamma(k) - obs log(k),        exactly 0 when obs == 0
+ * and the cell is term + g; the -lgamma(obs + 1) of the pmf is left out, as the Poisson cell leaves it out.  An unusable cell is 0.
+ * Sums as in the Poisson objective: the ages ascending within a day, the days ascending from 0.0 per series, total = (H + ICU) + D,
+ * a NaN or Inf total gives status 1 and lowest(); ll_parts are the three series sums, g included.  lgamma is an explicit
+ * operation sequence (csrc/sepaihrd_lgamma.inc) over the library's restatement of glibc's log: host twin and device agree in
+ * everything but log(sim), which the device takes through its table path (sepaihrd_device_log_values) and the twin from std::log.
+ * Every entry point that evaluates through the context follows: sepaihrd_eval_batch / _device / _begin / _end,
+ * sepaihrd_fd_gradient_batch (set both contexts alike), sepaihrd_mh_*.  A dispersed context integrates in a form that parks its
+ * increments (the likelihood_form SEPAIHRD_LL_SEPARATE_PASS) and runs the negative-binomial pass over them instead of the Poisson
+ * pass; sepaihrd_reserve sizes the workspace for it.  With all three series at +inf nothing changes: the kernels and the bits
+ * of the Poisson objective.  SEPAIHRD_PRECISION_F32 with a dispersed series: SEPAIHRD_E_UNSUPPORTED from the evaluation.
+ * The ensemble entry points and the particle filters do not read the context's dispersion.
+ *   create          refuses a SEPAIHRD_F_DISPERSION entry whose index is not 0, 1, 2, that has no bounds, whose bounds do not
+ *                   satisfy 1e-3 <= lower <= upper <= 1e6, or that names a series another entry already calibrates
+ *                   (sepaihrd_dispersion_validate's message in err)
+ *   set_dispersion  k[3]: the fixed values of the series theta does not calibrate (the others' entries are ignored); refuses
+ *                   what sepaihrd_particle_nb_validate refuses, with its message as the context's last error
+ *   get_dispersion  k[3]: the fixed values, NaN for a calibrated series */
+int sepaihrd_set_dispersion(sepaihrd_ctx *ctx, const double k[3]);
+int sepaihrd_get_dispersion(const sepaihrd_ctx *ctx, double k[3]);
+/* Host only: the rules sepaihrd_create applies to the SEPAIHRD_F_DISPERSION entries of a parameter map (lower / upper / has_bounds
+ * as in sepaihrd_problem; has_bounds NULL: bounded where both arrays are given).  series_param [3] (nullable): the theta index
+ * that calibrates each series, -1 for none. */
+int sepaihrd_dispersion_validate(int n_params, const int32_t *param_field, const int32_t *param_index, const double *lower,
+                                 const double *upper, const uint8_t *has_bounds, int32_t *series_param, char *err, int errlen);
+/* Host only, the twin of the pass: increments [B][T][3][n_age] (series H, ICU, D; the daily differences of CumH, CumICU, D, not yet
+ * clamped at 0), observations obs_* [T][n_age] (NaN where there is none), k [B][3] -> loglik [B], ll_parts [B][3] (nullable),
+ * status [B] (nullable; 0 or 1).  Compiled from the text the device pass compiles, with std::log for log(sim). */
+int sepaihrd_nb_objective_host(const double *increments, const double *obs_H, const double *obs_ICU, const double *obs_D,
+                               const double *k, int B, int T, int n_age, double *loglik, double *ll_parts, int32_t *status);
+/* lgamma of csrc/sepaihrd_lgamma.inc for x in [1e-3, 1e6 + the largest observation]: on the host, and a probe of the device's
+ * (n values, host memory), bit for bit the same. */
+double sepaihrd_lgamma_host(double x);
+int sepaihrd_lgamma_device(int device, const double *x, int n, double *out, char *err, int errlen);
 
 #ifdef __cplusplus
 }

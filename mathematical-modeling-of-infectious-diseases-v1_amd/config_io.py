@@ -31,6 +31,9 @@ SCALARS = (
     "ICU0_multiplier", "R0_multiplier", "D0_multiplier", "runup_days", "seed_exposed",
 )
 AGE_BANDS = ("0_30", "30_60", "60_80", "80_plus")
+# negative-binomial dispersion of the three observed series (problem.py DISPERSION_NAMES): in initial_guess.txt a fixed value,
+# in params_to_calibrate / param_bounds / proposal_sigmas a parameter like any other
+DISPERSION_NAMES = ("dispersion_H", "dispersion_ICU", "dispersion_D")
 
 
 def _config_lines(path: str):
@@ -57,6 +60,8 @@ def read_sepaihrd_parameters(path: str, num_age_classes: int) -> dict:
             kappa_map[int(name[6:])] = vals[0]
         elif name in SCALARS:
             out[name] = vals[0]
+        elif name in DISPERSION_NAMES:  # this build's own: negative-binomial dispersion of a series, +inf where not given
+            out.setdefault("dispersion", [float("inf")] * 3)[DISPERSION_NAMES.index(name)] = vals[0]
         elif name in ("beta_end_times", "kappa_end_times"):
             out[name] = np.array(vals)
         elif name in AGE_VECTORS:

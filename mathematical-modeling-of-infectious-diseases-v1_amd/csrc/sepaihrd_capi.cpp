@@ -20,6 +20,7 @@
 #include "sepaihrd_fd_device.h"
 #include "sepaihrd_host_util.h"
 #include "sepaihrd_mh_backend.h"
+#include "sepaihrd_nb_objective_device.h"
 #include "sepaihrd_predictive_device.h"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_particle_device.h"
@@ -43,6 +44,9 @@ struct sepaihrd_ctx {
     int arith = 0;
     int precision = 0;  // SEPAIHRD_PRECISION_F64 / _F32
     DevProblem dp{};
+    // the negative-binomial observation model (sepaihrd_set_dispersion): per series the theta entry that
+    // calibrates its dispersion, or the fixed value; all +inf: the Poisson objective, untouched
+    NbDispersion disp{{-1, -1, -1}, 0, {std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()}};
     // Everything below that owns a HIP resource releases it in its destructor; members go in reverse order of declaration, so
     // own_stream, declared last, is drained and destroyed before any buffer it may touch is freed (sepaihrd_destroy).
     DeviceAllocs allocs;  // the problem's tables
@@ -367,9 +371,15 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
             set_err(err, errlen, "beta end times must be strictly increasing"); return nullptr;
         }
 
+    // the SEPAIHRD_F_DISPERSION entries: index, bounds within [1e-3, 1e6], one entry per series
+    int32_t disp_src[3] = {-1, -1, -1};
+    if (sepaihrd_dispersion_validate(P, pb->param_field, pb->param_index, pb->lower, pb->upper, pb->has_bounds, disp_src, err, errlen) != SEPAIHRD_OK)
+        return nullptr;
+
     if (select_device(device, err, errlen) != SEPAIHRD_OK) return nullptr;
 
     auto* ctx = new sepaihrd_ctx();
+    for (int s = 0; s < 3; ++s) ctx->disp.src[s] = disp_src[s];
     ctx->device = device;
     ctx->solver = pb->solver;
     ctx->arith = pb->arith == SEPAIHRD_ARITH_FMA ? SEPAIHRD_ARITH_FMA : SEPAIHRD_ARITH_STRICT;
@@ -434,6 +444,8 @@ sepaihrd_ctx* sepaihrd_create(const sepaihrd_problem* pb, int device, char* err,
         } else if (f >= SEPAIHRD_F_A && f <= SEPAIHRD_F_D_COMMUNITY) {
             if (idx < 0 || idx >= n) return bad("age index out of range");
             src_vec[(size_t)(f - SEPAIHRD_F_A) * lpc + idx] = p;
+        } else if (f == SEPAIHRD_F_DISPERSION) {
+            // no model slot: the likelihood pass reads the entry (ctx->disp.src, validated above)
         } else {
             return bad("unknown field code");
         }
@@ -577,6 +589,22 @@ int sepaihrd_set_precision(sepaihrd_ctx* ctx, int precision) {
     return SEPAIHRD_OK;
 }
 
+int sepaihrd_set_dispersion(sepaihrd_ctx* ctx, const double* k) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    char msg[256] = "";
+    const int rc = validated(ctx, sepaihrd_particle_nb_validate(k, msg, (int)sizeof(msg)), msg);
+    if (rc != SEPAIHRD_OK) return rc;
+    for (int s = 0; s < 3; ++s)
+        if (ctx->disp.src[s] < 0) ctx->disp.fixed[s] = k[s];
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_get_dispersion(const sepaihrd_ctx* ctx, double* k) {
+    if (!ctx || !k) return SEPAIHRD_E_INVALID_ARG;
+    for (int s = 0; s < 3; ++s) k[s] = ctx->disp.src[s] >= 0 ? std::numeric_limits<double>::quiet_NaN() : ctx->disp.fixed[s];
+    return SEPAIHRD_OK;
+}
+
 int sepaihrd_reserve(sepaihrd_ctx* ctx, int max_B) {
     if (!ctx || max_B < 0) return SEPAIHRD_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
@@ -595,7 +623,14 @@ int sepaihrd_eval_batch_device(sepaihrd_ctx* ctx, const double* d_theta, int B, 
     // The workspace grows on the first call for a larger batch (an allocation: call sepaihrd_reserve
     // beforehand when the launch must be allocation-free, e.g. under stream capture).
     // batches that fill the chip use the inline-likelihood kernel and need no workspace / chunking
-    const int needs = needs_workspace(ctx, B, 0);
+    // a dispersed context parks its increments whatever the batch: the negative-binomial pass reads them
+    const bool dispersed = nb_any_dispersed(ctx->disp);
+    if (dispersed && ctx->precision == SEPAIHRD_PRECISION_F32) {
+        ctx->last_error = "eval_batch_device: the negative-binomial likelihood reads the fp64 integrator's parked increments (set precision F64)";
+        return SEPAIHRD_E_UNSUPPORTED;
+    }
+    const int force_split = dispersed ? FORCE_SPLIT_PARK_ONLY : 0;
+    const int needs = needs_workspace(ctx, B, force_split);
     if (needs < 0) { ctx->last_error = "unsupported lanes-per-chain"; return SEPAIHRD_E_UNSUPPORTED; }
     const bool split = needs != 0;
     const size_t chunk = split ? chunk_chains(ctx, (size_t)B) : (size_t)B;
@@ -627,11 +662,15 @@ int sepaihrd_eval_batch_device(sepaihrd_ctx* ctx, const double* d_theta, int B, 
                         d_n_reject ? d_n_reject + off : nullptr,
                         d_ll_parts ? d_ll_parts + 3 * off : nullptr,
                         d_traj ? d_traj + off * traj_per_chain : nullptr,
-                        ctx->ws_cum, ctx->ws_rows, ctx->ws_status, e1, 0};
+                        ctx->ws_cum, ctx->ws_rows, ctx->ws_status, e1, force_split};
         const double* th = d_theta + off * (size_t)ctx->P;
-        const int rc = ctx->precision == SEPAIHRD_PRECISION_F32 ? launch_eval_f32(ctx->dp, ctx->solver, th, nb, out, stream)
-                       : ctx->arith == SEPAIHRD_ARITH_FMA       ? launch_eval_fma(ctx->dp, ctx->solver, th, nb, out, stream)
-                                                                : launch_eval_strict(ctx->dp, ctx->solver, th, nb, out, stream);
+        int rc = ctx->precision == SEPAIHRD_PRECISION_F32 ? launch_eval_f32(ctx->dp, ctx->solver, th, nb, out, stream)
+                 : ctx->arith == SEPAIHRD_ARITH_FMA       ? launch_eval_fma(ctx->dp, ctx->solver, th, nb, out, stream)
+                                                          : launch_eval_strict(ctx->dp, ctx->solver, th, nb, out, stream);
+        if (rc == 0 && dispersed) {
+            ctx->disp.fused_poisson = ctx->arith == SEPAIHRD_ARITH_FMA ? 1 : 0;
+            rc = launch_nb_objective_pass(ctx->dp, th, nb, out, ctx->disp, stream);
+        }
         if (rc != 0) {
             ctx->last_error = rc == -4 ? "unsupported lanes-per-chain"
                               : rc == -5 ? "launch needs the likelihood workspace but none was sized for it"
@@ -1510,7 +1549,9 @@ int sepaihrd_get_kernel_info_for_batch(sepaihrd_ctx* ctx, int32_t batch_chains, 
     std::memset(info, 0, sizeof(*info));
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     LaunchInfo li{};
-    const int rc = ctx->precision == SEPAIHRD_PRECISION_F32 ? kernel_info_f32(ctx->dp, ctx->solver, &li)
+    // a dispersed context: the pass that takes the Poisson pass's place behind whichever integrator form parks the increments
+    const int rc = nb_any_dispersed(ctx->disp) && ctx->precision != SEPAIHRD_PRECISION_F32 ? kernel_info_nb_pass(ctx->dp, &li)
+                   : ctx->precision == SEPAIHRD_PRECISION_F32 ? kernel_info_f32(ctx->dp, ctx->solver, &li)
                    : ctx->arith == SEPAIHRD_ARITH_FMA       ? kernel_info_fma(ctx->dp, ctx->solver, batch_chains, &li)
                                                             : kernel_info_strict(ctx->dp, ctx->solver, batch_chains, &li);
     if (rc != 0) { ctx->last_error = "kernel_info failed"; return SEPAIHRD_E_HIP; }

@@ -70,8 +70,12 @@ struct EvalOutputs {
     double* rows;
     int32_t* wstatus;
     void* ev_after_integrator;  // optional hipEvent_t recorded between the integrator kernel and the likelihood pass
-    int32_t force_split;        // always park the increments in `cum` (ensemble summaries read them)
+    int32_t force_split;        // always park the increments in `cum` (ensemble summaries read them); FORCE_SPLIT_PARK_ONLY: see below
 };
+// force_split == FORCE_SPLIT_PARK_ONLY: park the increments and launch NO Poisson pass behind the integrator -- the caller runs
+// its own pass over `cum` / `wstatus` (the negative-binomial pass, csrc/sepaihrd_nb_objective.hip), which writes loglik, status
+// and ll_parts.  Read by the launch code only; no kernel reads force_split.
+constexpr int32_t FORCE_SPLIT_PARK_ONLY = 2;
 inline size_t workspace_cum_doubles(const DevProblem& pb, size_t chains) { return (size_t)pb.T * 3 * chains * pb.lpc; }
 // Layout of the parked daily increments (D, CumH, CumICU of every (chain, age) column and output day): WAVE-major,
 // cum[column / 64][T][3][64].  A wave of the integrator writes its own contiguous T x 1.5 KB, day after day -- one or two

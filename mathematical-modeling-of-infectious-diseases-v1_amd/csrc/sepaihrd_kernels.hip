@@ -1357,7 +1357,9 @@ int launch_wps(const DevProblem& pb, const double* d_theta, int blocks, int B, c
                        st, pb, d_theta, B, out, cum_chains);
     if (out.ev_after_integrator) (void)hipEventRecord(static_cast<hipEvent_t>(out.ev_after_integrator), st);
     if constexpr (!INLINE_LL) {
-        if ((B + WAVE - 1) / WAVE >= ll_serial_min_waves<LPC>() / 3) {
+        if (out.force_split == FORCE_SPLIT_PARK_ONLY) {
+            // the caller's own pass over the parked increments follows
+        } else if ((B + WAVE - 1) / WAVE >= ll_serial_min_waves<LPC>() / 3) {
             // lanes per (chain, stream): one from three waves per SIMD on; below that a pair, so that every SIMD holds the same
             // number of waves (32 768 chains: 1536 waves -> 3072)
             const int waves1 = 3 * ((B + WAVE - 1) / WAVE);

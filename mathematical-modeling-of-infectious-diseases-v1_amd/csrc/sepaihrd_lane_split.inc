@@ -1141,6 +1141,7 @@ int launch_quad(const DevProblem& pb, const double* d_theta, int B, const EvalOu
     const int cum_chains = ll_blocks * 16;
     hipLaunchKernelGGL((sepaihrd_eval_quad_kernel<SOLVER, SEPAIHRD_ARITH_FMA, false>), dim3(blocks), dim3(WAVE), lds, st, pb, d_theta, B, out, cum_chains);
     if (out.ev_after_integrator) (void)hipEventRecord(static_cast<hipEvent_t>(out.ev_after_integrator), st);
+    if (out.force_split == FORCE_SPLIT_PARK_ONLY) return hipGetLastError() == hipSuccess ? 0 : -3;  // the caller's own pass follows
     hipLaunchKernelGGL((sepaihrd_ll_terms_kernel<4>), dim3(ll_blocks, (pb.T + LL_DAYS_PER_BLOCK - 1) / LL_DAYS_PER_BLOCK),
                        dim3(WAVE * LL_DAYS_PER_BLOCK), 0, st, pb, B, out, cum_chains);
     hipLaunchKernelGGL(sepaihrd_ll_reduce_kernel, dim3((B + 15) / 16), dim3(WAVE), 0, st, pb, B, out, cum_chains, pb.T);

@@ -225,7 +225,11 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_particle_loglik_nb", "sepaihrd_particle_loglik_wide_nb", "sepaihrd_particle_nb_validate", "sepaihrd_particle_nb_row_constants",
     "sepaihrd_particle_nb_term_device",
     "sepaihrd_particle_filter_states", "sepaihrd_particle_states_validate", "sepaihrd_particle_states_timing",
+    "sepaihrd_set_dispersion", "sepaihrd_get_dispersion", "sepaihrd_dispersion_validate", "sepaihrd_nb_objective_host",
+    "sepaihrd_lgamma_host", "sepaihrd_lgamma_device",
 )
+
+F_DISPERSION = 28  # enum sepaihrd_field SEPAIHRD_F_DISPERSION: param_index 0, 1, 2 = the dispersion of the H, ICU, D series
 
 _lib = None
 
@@ -378,6 +382,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_particle_filter_states.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, vp, vp, C.c_int] + [vp] * 8
     lib.sepaihrd_particle_states_validate.argtypes = [C.c_int] * 7 + [vp, C.c_int, C.c_char_p, C.c_int]
     lib.sepaihrd_particle_states_timing.argtypes = [vp, vp]
+    lib.sepaihrd_set_dispersion.argtypes = [vp, vp]
+    lib.sepaihrd_get_dispersion.argtypes = [vp, vp]
+    lib.sepaihrd_dispersion_validate.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_nb_objective_host.argtypes = [vp] * 5 + [C.c_int] * 3 + [vp] * 3
+    lib.sepaihrd_lgamma_host.restype = C.c_double
+    lib.sepaihrd_lgamma_host.argtypes = [C.c_double]
+    lib.sepaihrd_lgamma_device.argtypes = [C.c_int, vp, C.c_int, vp, C.c_char_p, C.c_int]
     if path is None:
         _lib = lib
     return lib
@@ -440,6 +451,8 @@ class HipObjective:
         self.P, self.n, self.T = pb.n_params, pb.n, pb.n_times
         self._device = device
         self._fd_perturbed = None
+        if getattr(pb, "dispersion", None) is not None:
+            self.set_dispersion(pb.dispersion)
 
     def close(self):
         if getattr(self, "_fd_perturbed", None) is not None:
@@ -475,6 +488,34 @@ class HipObjective:
     def set_integrator_form(self, form: int):
         """FORM_AUTO (by batch size), FORM_LANE_PER_AGE or FORM_QUAD (sixteen lanes per chain): same bits either way."""
         self._check(self.lib.sepaihrd_set_integrator_form(self.ctx, int(form)), "set_integrator_form")
+
+    def set_dispersion(self, k):
+        """sepaihrd_set_dispersion: k [3] = the fixed negative-binomial dispersions of the H, ICU, D series (+inf: Poisson; a series
+        that theta calibrates, dispersion_H / _ICU / _D, ignores its entry).  ValueError with the validator's message for a k the
+        library refuses.  The finite-difference objective's perturbed context, if it exists already, follows."""
+        kk = np.ascontiguousarray(k, dtype=np.float64)
+        if kk.shape != (3,):
+            raise ValueError("dispersion must have three entries: k_H, k_ICU, k_D")
+        if self.lib.sepaihrd_set_dispersion(self.ctx, kk.ctypes.data) != 0:
+            raise ValueError(self.lib.sepaihrd_last_error(self.ctx).decode())
+        if getattr(self, "_fd_perturbed", None) is not None:
+            self._fd_perturbed.set_dispersion(kk)
+
+    def get_dispersion(self) -> np.ndarray:
+        """sepaihrd_get_dispersion: the fixed dispersions [3], NaN for a series that theta calibrates"""
+        k = np.empty(3)
+        self._check(self.lib.sepaihrd_get_dispersion(self.ctx, k.ctypes.data), "sepaihrd_get_dispersion")
+        return k
+
+    def lgamma_device(self, x) -> np.ndarray:
+        """Probe of the device's lgamma_pos (sepaihrd_lgamma_device) on the arguments x > 0"""
+        xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        out = np.empty(xs.size)
+        err = C.create_string_buffer(256)
+        rc = self.lib.sepaihrd_lgamma_device(getattr(self, "_device", -1), xs.ctypes.data, xs.size, out.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_lgamma_device failed ({rc}): " + err.value.decode())
+        return out.reshape(np.shape(x))
 
     def calculate(self, theta) -> float:
         return float(self.eval_batch(np.asarray(theta, dtype=np.float64)[None, :])["loglik"][0])
@@ -527,6 +568,7 @@ class HipObjective:
             other = HipObjective(pb.with_(bounds=bounds, constraint_mode=CONSTRAINT_CLAMP, multipliers=np.ones(8)),
                                  device=getattr(self, "_device", -1))
             other.set_initial_state_mode(2)
+            other.set_dispersion(np.where(np.isnan(self.get_dispersion()), np.inf, self.get_dispersion()))  # the same observation model
             self._fd_perturbed = other
         return self._fd_perturbed
 

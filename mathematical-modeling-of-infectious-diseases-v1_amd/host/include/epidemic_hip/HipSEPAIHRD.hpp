@@ -114,6 +114,10 @@ private:
     std::vector<uint8_t> has_bounds_;
     std::vector<int32_t> field_, index_;
     ConstraintMode mode_ = ConstraintMode::OPTIMIZATION_CLAMP;
+    // the calibrated negative-binomial dispersions (names dispersion_H, dispersion_ICU, dispersion_D -> SEPAIHRD_F_DISPERSION
+    // 0, 1, 2; this build's own, the reference has none): no entry of SEPAIHRDParameters, so the manager keeps the current
+    // values itself.  Until the first updateModelParameters: the upper bound, the end nearest the Poisson limit
+    double dispersion_[3] = {0.0, 0.0, 0.0};
 };
 
 class HipSEPAIHRDObjectiveFunction : public virtual IObjectiveFunction, public IBatchObjectiveFunction {
@@ -163,6 +167,10 @@ public:
     // build-side accessors for other device callers of the same problem (HipPosteriorEnsemble)
     sepaihrd_ctx* deviceContext() const { return ctx_; }
     void syncDeviceConstraintMode() const { syncConstraintMode(); }
+    // sepaihrd_set_dispersion on this objective's context(s): k[3] = the fixed negative-binomial dispersions of the H, ICU, D
+    // series (+inf: Poisson, the default); a series a dispersion_* parameter calibrates ignores its entry.
+    // InvalidParameterException with the library's message for a k it refuses.
+    virtual void setDispersion(const double k[3]);
 protected:
     // builds the device context for this problem; multipliers_override (8 values) replaces the model's
     // E0..D0 multipliers as the base values of the non-calibrated ones
@@ -224,6 +232,8 @@ public:
     void evaluateRows(const double* thetas, const uint8_t* want_gradient, int B, int P, double* values, double* gradients,
                       int32_t* status) override;
     sepaihrd_ctx* gradientContext() const { return grad_ctx_; }
+    // both contexts: the perturbed evaluations use the centre's observation model
+    void setDispersion(const double k[3]) override;
 private:
     void buildGradientContext(const CalibrationData& data, const std::vector<double>& time_points,
                               const std::shared_ptr<IOdeSolverStrategy>& solver_strategy, double abs_error, double rel_error,

@@ -129,7 +129,14 @@ HipSEPAIHRDParameterManager::HipSEPAIHRDParameterManager(
 
         int field = SEPAIHRD_F_NONE, index = 0;
         bool done = false;
-        if (name == "beta") { field = SEPAIHRD_F_BETA; done = true; }
+        static const char* const dispersion_names[3] = {"dispersion_H", "dispersion_ICU", "dispersion_D"};
+        for (int s = 0; s < 3; ++s)
+            if (name == dispersion_names[s]) {
+                field = SEPAIHRD_F_DISPERSION; index = s; done = true;
+                dispersion_[s] = bd->second.second;
+            }
+        if (done) { /* this build's own name: none of the reference's rules below applies */ }
+        else if (name == "beta") { field = SEPAIHRD_F_BETA; done = true; }
         else if (starts_with(name, "beta_")) {
             const size_t k = parse_index(name, 5, W);
             if (k < 1 || k > params_.beta_values.size())
@@ -225,6 +232,7 @@ double* HipSEPAIHRDParameterManager::slot(int field, int index) {
         case SEPAIHRD_F_D_H: return &p.d_H[index];
         case SEPAIHRD_F_D_ICU: return &p.d_ICU[index];
         case SEPAIHRD_F_D_COMMUNITY: return &p.d_community[index];
+        case SEPAIHRD_F_DISPERSION: return &dispersion_[index];
         default: return nullptr;
     }
 }
@@ -440,6 +448,12 @@ HipSEPAIHRDObjectiveFunction::~HipSEPAIHRDObjectiveFunction() { sepaihrd_destroy
 
 const std::vector<std::string>& HipSEPAIHRDObjectiveFunction::getParameterNames() const { return pm_.getParameterNames(); }
 
+void HipSEPAIHRDObjectiveFunction::setDispersion(const double k[3]) {
+    if (sepaihrd_set_dispersion(ctx_, k) != SEPAIHRD_OK)
+        throw InvalidParameterException("SEPAIHRDObjectiveFunction::setDispersion", sepaihrd_last_error(ctx_));
+    cache_.clear();  // the cached values are those of the previous observation model
+}
+
 void HipSEPAIHRDObjectiveFunction::syncConstraintMode() const {
     // the reference consults the SHARED parameter manager's mode_ on every evaluation
     if (foreign_pm_) {
@@ -578,6 +592,12 @@ void HipSEPAIHRDGradientObjectiveFunction::buildGradientContext(const Calibratio
 }
 
 HipSEPAIHRDGradientObjectiveFunction::~HipSEPAIHRDGradientObjectiveFunction() { sepaihrd_destroy(grad_ctx_); }
+
+void HipSEPAIHRDGradientObjectiveFunction::setDispersion(const double k[3]) {
+    HipSEPAIHRDObjectiveFunction::setDispersion(k);
+    if (sepaihrd_set_dispersion(grad_ctx_, k) != SEPAIHRD_OK)
+        throw InvalidParameterException("SEPAIHRDGradientObjectiveFunction::setDispersion", sepaihrd_last_error(grad_ctx_));
+}
 
 bool HipSEPAIHRDGradientObjectiveFunction::initialStateValid(const double* plus) const {
     const Eigen::VectorXd& N = pm_.modelParameters().N;

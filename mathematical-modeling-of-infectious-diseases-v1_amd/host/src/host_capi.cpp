@@ -22,6 +22,7 @@
 #include "epidemic_hip/HipSIRScenarioAnalysis.hpp"
 #include "sepaihrd_hip.h"
 #include "sepaihrd_rng.inc"
+#include "sepaihrd_nb_objective.inc"
 
 using namespace epidemic;
 
@@ -32,6 +33,9 @@ struct HostHandle {
     std::unique_ptr<CalibrationData> data;
     std::unique_ptr<HipSEPAIHRDObjectiveFunction> obj;
     std::string error;
+    // host_objective_set_dispersion: kept for the gradient objectives the calls below build over this handle's manager
+    bool has_dispersion = false;
+    double dispersion[3] = {0.0, 0.0, 0.0};
     bool mh_diagnostics = false;        // host_set_mh_diagnostics: compute_diagnostics for the runs below
     ChainDiagnosticsTable last_diag;    // of the last host_mh_run / host_calibrate / host_calibrate_pso
 };
@@ -522,6 +526,16 @@ int host_objective_calculate_batch(void* hv, const double* thetas, int B, double
     });
 }
 
+// HipSEPAIHRDObjectiveFunction::setDispersion on the handle's objective; 0 ok, 1 = refused (message in host_last_error)
+int host_objective_set_dispersion(void* hv, const double* k) {
+    auto* h = static_cast<HostHandle*>(hv);
+    return guarded([&] {
+        h->obj->setDispersion(k);
+        std::copy(k, k + 3, h->dispersion);
+        h->has_dispersion = true;
+    });
+}
+
 void host_cache_stats(void* hv, long* calls, long* hits, long* size) {
     auto* h = static_cast<HostHandle*>(hv);
     *calls = static_cast<long>(h->cache->getLikelihoodCalls());
@@ -749,6 +763,7 @@ int host_gradient(void* hv, const sepaihrd_problem* pb, int device, const double
                                                  vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err, device,
                                                  pb->arith == SEPAIHRD_ARITH_FMA);
         obj.epsilon_ = epsilon;
+        if (h->has_dispersion) obj.setDispersion(h->dispersion);
         Eigen::VectorXd g;
         IGradientObjectiveFunction& iface = obj;  // through the interface NUTS uses (NUTSSampler.cpp:80)
         *value = iface.evaluate_with_gradient(vec(theta, P), g);
@@ -775,6 +790,7 @@ int host_nuts_run(void* hv, const sepaihrd_problem* pb, int device, int iteratio
                                                  vec(pb->initial_state, 11 * n), solver, pb->abs_err, pb->rel_err, device,
                                                  pb->arith == SEPAIHRD_ARITH_FMA);
         obj.epsilon_ = fd_epsilon;
+        if (h->has_dispersion) obj.setDispersion(h->dispersion);
         HipNUTSSampler nuts;
         nuts.configure({{"nuts_iterations", double(iterations)}, {"nuts_adaptation_window", double(adaptation_window)},
                         {"nuts_delta_target", delta_target}, {"nuts_max_tree_depth", double(max_tree_depth)},
@@ -816,6 +832,7 @@ int host_nuts_chains_run(void* hv, const sepaihrd_problem* pb, int device, int i
                                                  vec(pb->initial_state, 11 * n), strategy_for(pb->solver), pb->abs_err, pb->rel_err,
                                                  device, pb->arith == SEPAIHRD_ARITH_FMA);
         obj.epsilon_ = fd_epsilon;
+        if (h->has_dispersion) obj.setDispersion(h->dispersion);
         TimedRows rows(obj, kernel_timing != 0);
         MultiChainNUTSSampler nuts;
         nuts.configure(nuts_settings(iterations, adaptation_window, delta_target, max_tree_depth, seed0));
@@ -1690,6 +1707,31 @@ int host_particle_filter_states(void* hv, const sepaihrd_problem* pb, int device
         std::copy(ll.begin(), ll.end(), loglik);
         lik.calculateBatch(thetas, B, next_values, nullptr);
     });
+}
+
+// ---- the negative-binomial observation model of the deterministic objective, this library's compile of
+// csrc/sepaihrd_lgamma.inc and csrc/sepaihrd_nb_objective.inc
+double host_lgamma_pos(double x) { return sepaihrd_lgamma::lgamma_pos(x); }
+
+// the twin of the device pass (sepaihrd_nb_objective_host's arguments): increments [B][T][3][n_age], obs_* [T][n_age], k [B][3]
+// -> loglik [B], ll_parts [B][3] (nullable), status [B] (nullable)
+int host_nb_objective(const double* increments, const double* obs_H, const double* obs_ICU, const double* obs_D, const double* k, int B, int T,
+                      int n_age, double* loglik, double* ll_parts, int32_t* status) {
+    if (!increments || !obs_H || !obs_ICU || !obs_D || !k || !loglik || B < 0 || T < 0 || n_age < 1) return SEPAIHRD_E_INVALID_ARG;
+    const size_t Tn = static_cast<size_t>(T) * static_cast<size_t>(n_age);
+    std::vector<double> obs(3 * Tn);
+    std::copy(obs_H, obs_H + Tn, obs.begin());
+    std::copy(obs_ICU, obs_ICU + Tn, obs.begin() + static_cast<std::ptrdiff_t>(Tn));
+    std::copy(obs_D, obs_D + Tn, obs.begin() + static_cast<std::ptrdiff_t>(2 * Tn));
+    for (int b = 0; b < B; ++b) {
+        double parts[3];
+        const int st = sepaihrd_nb_objective::chain_loglik(increments + static_cast<size_t>(b) * 3 * Tn, obs.data(), k + 3 * static_cast<size_t>(b), T,
+                                                           n_age, [](double sim) { return std::log(sim); }, loglik + b, parts);
+        if (status) status[b] = st;
+        if (ll_parts)
+            for (int s = 0; s < 3; ++s) ll_parts[3 * static_cast<size_t>(b) + s] = parts[s];
+    }
+    return SEPAIHRD_OK;
 }
 
 }  // extern "C"

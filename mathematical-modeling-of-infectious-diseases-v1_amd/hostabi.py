@@ -155,6 +155,10 @@ def load_library() -> C.CDLL:
     lib.host_particle_resample.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.host_particle_likelihood.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int,
                                              C.c_int, vp, vp]
+    lib.host_lgamma_pos.restype = C.c_double
+    lib.host_lgamma_pos.argtypes = [C.c_double]
+    lib.host_nb_objective.argtypes = [vp] * 5 + [C.c_int] * 3 + [vp] * 3
+    lib.host_objective_set_dispersion.argtypes = [vp, vp]
     _lib = lib
     return lib
 
@@ -278,6 +282,16 @@ class HostObjective:
                                                 cache_capacity, int(with_objective))
         _check(not self.h, "host_objective_create failed: ")
         self.P = pb.n_params
+        if with_objective and getattr(pb, "dispersion", None) is not None:
+            self.set_dispersion(pb.dispersion)
+
+    def set_dispersion(self, k) -> None:
+        """HipSEPAIHRDObjectiveFunction::setDispersion: the fixed negative-binomial dispersions of the H, ICU, D series (+inf:
+        Poisson) for everything that evaluates through this object's objective"""
+        kk = np.ascontiguousarray(k, dtype=np.float64)
+        if kk.shape != (3,):
+            raise ValueError("dispersion must have three entries: k_H, k_ICU, k_D")
+        _check(self.lib.host_objective_set_dispersion(self.h, kk.ctypes.data), "setDispersion: ")
 
     def __del__(self):
         try:
@@ -1214,6 +1228,37 @@ def particle_nb_validate(dispersion) -> None:
     disp = None if dispersion is None else _dispersion(dispersion)
     if hipabi.load_library().sepaihrd_particle_nb_validate(None if disp is None else disp.ctypes.data, err, len(err)) != 0:
         raise ValueError(err.value.decode())
+
+
+def lgamma_pos(x) -> np.ndarray:
+    """lgamma_pos of csrc/sepaihrd_lgamma.inc as this library compiles it, element by element (the twin of HipObjective.lgamma_device)"""
+    fn = load_library().host_lgamma_pos
+    xs = np.ascontiguousarray(x, dtype=np.float64)
+    return np.array([fn(float(v)) for v in xs.ravel()]).reshape(xs.shape)
+
+
+def nb_objective(increments, obs_H, obs_ICU, obs_D, k, lib: str = "host") -> dict:
+    """The twin of the negative-binomial likelihood pass of the deterministic objective: increments
+    [B][T][3][n] (series H, ICU, D: the daily differences of CumH, CumICU and D, not yet clamped at 0), observations obs_* [T][n]
+    (NaN where there is none), k [B][3] (+inf: that series is Poisson) -> loglik [B], ll_parts [B][3], status [B].
+    lib = "host": this library's compile (host_nb_objective); "hip": libsepaihrd_hip.so's (sepaihrd_nb_objective_host)."""
+    inc = np.ascontiguousarray(increments, dtype=np.float64)
+    if inc.ndim != 4 or inc.shape[2] != 3:
+        raise ValueError("increments must be [B][T][3][n]")
+    B, T, _, n = inc.shape
+    ob = [np.ascontiguousarray(o, dtype=np.float64) for o in (obs_H, obs_ICU, obs_D)]
+    if any(o.shape != (T, n) for o in ob):
+        raise ValueError(f"obs_H, obs_ICU and obs_D must be [{T}][{n}]")
+    kk = np.ascontiguousarray(k, dtype=np.float64)
+    if kk.shape != (B, 3):
+        raise ValueError(f"k must be [{B}][3]")
+    out = {"loglik": np.empty(B), "ll_parts": np.empty((B, 3)), "status": np.empty(B, dtype=np.int32)}
+    fn = load_library().host_nb_objective if lib == "host" else hipabi.load_library().sepaihrd_nb_objective_host
+    rc = fn(inc.ctypes.data, ob[0].ctypes.data, ob[1].ctypes.data, ob[2].ctypes.data, kk.ctypes.data, B, T, n, out["loglik"].ctypes.data,
+            out["ll_parts"].ctypes.data, out["status"].ctypes.data)
+    if rc != 0:
+        raise ValueError(f"nb_objective refused its arguments ({rc})")
+    return out
 
 
 def particle_nb_term(obs, inc, k: float) -> np.ndarray:

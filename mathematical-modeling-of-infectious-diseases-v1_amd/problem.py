@@ -37,10 +37,16 @@ F_BETA_VALUE, F_KAPPA_VALUE = 18, 19
 # prefix dispatch ORDER matters ("h_infec_" before "h_"): PM.cpp:221-228
 F_AGE_PREFIXES = (("a_", 20), ("h_infec_", 21), ("p_", 22), ("h_", 23), ("icu_", 24), ("d_H_", 25),
                   ("d_ICU_", 26), ("d_community_", 27))
+# this build's own: the negative-binomial dispersion of an observed series (SEPAIHRD_F_DISPERSION, index 0, 1, 2)
+F_DISPERSION = 28
+DISPERSION_NAMES = ("dispersion_H", "dispersion_ICU", "dispersion_D")
 
 
 def resolve_param_name(name: str, npi_names: Sequence[str], n_age: int, n_beta: int) -> Tuple[int, int]:
-    """name -> (field, index), in the reference's if/else-if order (PM.cpp:201-266)."""
+    """name -> (field, index), in the reference's if/else-if order (PM.cpp:201-266); the dispersion names, which the reference
+    does not have and none of its prefixes matches, first."""
+    if name in DISPERSION_NAMES:
+        return F_DISPERSION, DISPERSION_NAMES.index(name)
     if name == "beta":
         return F_SCALARS["beta"], 0
     if name.startswith("beta_"):
@@ -128,6 +134,9 @@ class SEPAIHRDProblem:
     max_attempts: int = 0  # build-side guard on RK step attempts per chain, 0 = default (1e6)
     # calibrated starting point (getCurrentParameters of the shipped model)
     base_theta: Optional[np.ndarray] = None
+    # negative-binomial dispersion of the H, ICU, D series, [3] with +inf for a Poisson series; None: all Poisson.  The fixed
+    # values of the series that no dispersion_* parameter calibrates (HipObjective.set_dispersion)
+    dispersion: Optional[List[float]] = None
 
     def __post_init__(self):
         self.N = _arr(self.N)
@@ -212,6 +221,10 @@ class SEPAIHRDProblem:
                 out[k] = self.kappa_values[i]
             elif c in vecs:
                 out[k] = vecs[c][i]
+            elif c == F_DISPERSION:
+                # the series' fixed value where it is finite, else the end of its bounds nearest the Poisson limit
+                fixed = float(self.dispersion[i]) if self.dispersion is not None else float("inf")
+                out[k] = fixed if np.isfinite(fixed) else self.bounds.get(self.param_names[k], (1e-3, 1e6))[1]
             else:
                 raise ValueError(f"Unknown parameter name: {self.param_names[k]}")
         return out
