@@ -847,12 +847,40 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx *ctx, const double *theta, int S, 
                                  double *pred_quantiles, double *pit, double *means, double *draws, int32_t *status, int32_t *n_valid);
 /* Host only: the argument rules above that need no context, with a message in err (NULL: not wanted). */
 int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, const double *probs, int n_probs, char *err, int errlen);
-/* Device time of the context's last sepaihrd_ensemble_predictive call in milliseconds, ms[3]: integrator; draws and mid-PIT
- * counts; segment sorts and quantiles. */
+/* Device time of the context's last sepaihrd_ensemble_predictive or sepaihrd_ensemble_predictive_nb call in milliseconds, ms[3]:
+ * integrator; draws and mid-PIT counts; segment sorts and quantiles. */
 int sepaihrd_predictive_timing(const sepaihrd_ctx *ctx, double *ms);
 /* Probe of the device's Poisson sampler: out[i] ~ Poisson(lambda[i]), the variate at (seed, c0 = i, c1 = 0, c2 = 0).
  * lambda [count], out [count], host memory; lambda <= 0 gives 0, NaN and +infinity give NaN. */
 int sepaihrd_poisson_device(int device, uint64_t seed, const double *lambda, int count, double *out, char *err, int errlen);
+
+/* ---- posterior predictive draws under the negative-binomial observation model (additive; SEPAIHRD_ABI_VERSION stays) ---------
+ * After a calibration under the negative-binomial likelihood (sepaihrd_set_dispersion, SEPAIHRD_F_DISPERSION) the replicated
+ * data must carry that model's noise: Poisson replicates give bands that are too narrow, the defect the replicated-data check
+ * exists to avoid.  sepaihrd_ensemble_predictive_nb is sepaihrd_ensemble_predictive -- same preconditions, failure codes, memory
+ * rule, outputs, stream coordinates, and what the context keeps -- with, for sample s and daily series k,
+ *   y = NegativeBinomial(mean m + 1e-10, dispersion k_used[s][k])   (variance mean + mean^2 / k)
+ * drawn as a gamma-Poisson mixture by the sampler of csrc/sepaihrd_nb_draw.inc: G ~ Gamma(k) by Cheng's algorithm GB (shape
+ * below 1: the boost Gamma(k + 1) U^(1/k)) on the counters (c0, c1, c2, 0x80000000 + attempt) and (c0, c1, c2, 0xC0000000), then
+ * Poisson(mean (G / k)) on the Poisson call's own counters.  A series with k = +inf has the Poisson call's draws, bit for bit;
+ * with all three at +inf for every sample every output is that call's.
+ *   dispersion  NULL: each sample's k is what the deterministic objective would use for that theta -- the constrained theta
+ *               entry of a calibrated series, the context's fixed value otherwise.  [3]: these values for every sample, whatever
+ *               the context holds; refused with sepaihrd_particle_nb_validate's message where that function refuses
+ *   k_used      [S][3] or NULL: the dispersions drawn with.  A sample whose k is NaN (a NaN theta entry) counts as failed:
+ *               status 1, no draws
+ * The device maps one lane to a (sample, replicate, age, series) and walks its T_pos output times; the host twin
+ * (hostPosteriorPredictive with k_used) reproduces draws, quantiles and PIT bit for bit from means, status and k_used.
+ * sepaihrd_predictive_timing reports this call when it was the last of the two. */
+int sepaihrd_ensemble_predictive_nb(sepaihrd_ctx *ctx, const double *theta, int S, int R, uint64_t seed,
+                                    const double *dispersion /* [3] or NULL: the context's */, const double *probs, int n_probs,
+                                    double *pred_quantiles, double *pit, double *means, double *draws, double *k_used /* [S][3] or NULL */,
+                                    int32_t *status, int32_t *n_valid);
+/* Probes of the device's gamma and negative-binomial samplers, host memory: out[i] ~ Gamma(shape[i], 1), and
+ * out[i] ~ NegativeBinomial(mu[i], k[i]), the variates at (seed, c0 = i, c1 = 0, c2 = 0).  shape finite in [1e-3, 1e6]; k the
+ * same or +inf (Poisson); mu <= 0 gives 0, NaN and +infinity give NaN. */
+int sepaihrd_gamma_device(int device, uint64_t seed, const double *shape, int count, double *out, char *err, int errlen);
+int sepaihrd_nb_draw_device(int device, uint64_t seed, const double *mu, const double *k, int count, double *out, char *err, int errlen);
 
 /* ---- stochastic chain-binomial SEPAIHRD ensembles over posterior samples (additive; SEPAIHRD_ABI_VERSION stays) -------------
  * Process noise for the age-structured model: the ensemble calls above give parameter uncertainty and observation noise, this
@@ -1077,7 +1105,8 @@ int sepaihrd_particle_states_timing(const sepaihrd_ctx *ctx, double *ms);
  * increments (the likelihood_form SEPAIHRD_LL_SEPARATE_PASS) and runs the negative-binomial pass over them instead of the Poisson
  * pass; sepaihrd_reserve sizes the workspace for it.  With all three series at +inf nothing changes: the kernels and the bits
  * of the Poisson objective.  SEPAIHRD_PRECISION_F32 with a dispersed series: SEPAIHRD_E_UNSUPPORTED from the evaluation.
- * The ensemble entry points and the particle filters do not read the context's dispersion.
+ * sepaihrd_ensemble_predictive_nb draws its replicates under this model.  The other ensemble entry points (sepaihrd_ensemble_predictive
+ * among them) and the particle filters do not read the context's dispersion.
  *   create          refuses a SEPAIHRD_F_DISPERSION entry whose index is not 0, 1, 2, that has no bounds, whose bounds do not
  *                   satisfy 1e-3 <= lower <= upper <= 1e6, or that names a series another entry already calibrates
  *                   (sepaihrd_dispersion_validate's message in err)

@@ -537,13 +537,15 @@ def write_posterior_predictive(out_dir: str, times_pos, ppc: np.ndarray, observe
 def write_posterior_predictive_draws(out_dir: str, times_pos, pred: np.ndarray, pit, observed: Dict[str, np.ndarray]) -> List[str]:
     """The replicated-data check beside write_posterior_predictive's files (the reference has no such output: its bands are of
     expectations), into the same directory:
-      <series>_predictive_{median,lower90,upper90,lower95,upper95}.csv   bands of y_rep ~ Poisson(mean), the format above
+      <series>_predictive_{median,lower90,upper90,lower95,upper95}.csv   bands of y_rep around the mean under the observation model
+                                                    the draws were made with -- Poisson, or negative-binomial where the call was
+                                                    HipObjective.ensemble_predictive(..., dispersion=...) -- in the format above
       pit_<daily series>.csv                        ``time,age_0,...``, the mid-PIT of every observation (17 significant digits, nan
                                                     where the observation is not usable)
       predictive_coverage.csv                       ``series,age,n_observations,coverage_90,coverage_95``: per daily series with
                                                     observations and age, the share of usable observations (finite and >= 0) inside
                                                     [lower90, upper90] and [lower95, upper95], computed here; nan without any
-    pred: [6 series][5 PPC_PROBS][T_pos][n] (HipObjective.ensemble_predictive at PPC_PROBS); pit: [3][T_pos][n] or None;
+    pred: [6 series][5 PPC_PROBS][T_pos][n] (HipObjective.ensemble_predictive at PPC_PROBS, with or without a dispersion); pit: [3][T_pos][n] or None;
     observed: series -> [T_pos][n]."""
     os.makedirs(out_dir, exist_ok=True)
     written = []
@@ -783,7 +785,7 @@ def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: n
     ppc, sero, rt, metrics; quantiles at PPC_PROBS).  scenarios (rows as write_scenario_comparison takes them):
     scenarios/scenario_comparison.csv; ene_covid: seroprevalence/ene_covid_validation.csv from the metric table;
     diagnostics (a table as write_posterior_diagnostics takes it): parameter_posteriors/posterior_diagnostics.csv;
-    predictive (a HipObjective.ensemble_predictive result at PPC_PROBS, keys pred and pit): the files of
+    predictive (a HipObjective.ensemble_predictive result at PPC_PROBS, Poisson or dispersed, keys pred and pit): the files of
     write_posterior_predictive_draws next to the bands of expectations."""
     times = np.asarray(times, dtype=np.float64)
     write_posterior_predictive(os.path.join(out_base, "posterior_predictive"), times[times >= 0], ensemble["ppc"], observed or {})

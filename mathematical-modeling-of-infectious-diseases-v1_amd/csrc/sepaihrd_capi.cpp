@@ -964,9 +964,12 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx* ctx, const double* theta, int S, c
     return SEPAIHRD_OK;
 }
 
-int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* probs, int n_probs,
-                                 double* pred_quantiles, double* pit, double* means, double* draws, int32_t* status, int32_t* n_valid) {
-    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+// The body of sepaihrd_ensemble_predictive and sepaihrd_ensemble_predictive_nb.  nb == nullptr: the Poisson call, its draw kernel
+// and nothing else.  Otherwise the dispersion every sample's draws take: the call's own three values (src = -1 throughout) or the
+// context's (the objective's rule, per sample), resolved on the device into k_used [S][3].
+static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const NbDispersion* nb, const double* probs,
+                           int n_probs, double* pred_quantiles, double* pit, double* means, double* draws, double* k_used, int32_t* status,
+                           int32_t* n_valid) {
     const char* const who = "ensemble_predictive";
     int rc = ensemble_preflight(ctx, who, S > 0 && theta && probs && pred_quantiles, "need S > 0, theta, probs (1..1024) and pred_quantiles",
                                 CHECK_PENDING | CHECK_F64 | CHECK_TP, probs, n_probs);
@@ -989,9 +992,10 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     const size_t n_vals = 2 * cells * N_pad;
     const size_t n_scratch = sort_scratch_doubles(plan, n_vals);
     const size_t n_means = means ? (size_t)S * cells : 0, n_draws = draws ? N * cells : 0;
+    const size_t n_k = nb ? (size_t)S * 3 : 0;
     // the rule of sepaihrd_scenario_ensemble: the buffers below plus the likelihood workspace must fit the device's memory
     // (the segment table dominates: 6 T_pos n_age segments of S R doubles)
-    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + (size_t)n_probs) +
+    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + n_k + (size_t)n_probs) +
                               sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) +
                               sizeof(int32_t) * (chains + 2);
     rc = require_device_memory(ctx, need_bytes, "ensemble_predictive: the segment table of S x R = " + std::to_string(N) + " draws needs",
@@ -1002,11 +1006,11 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     if (rc != SEPAIHRD_OK) return rc;
     CallScratch sc(4);
     double *d_theta = nullptr, *d_ll = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_pit = nullptr,
-           *d_means = nullptr, *d_draws = nullptr;
+           *d_means = nullptr, *d_draws = nullptr, *d_k = nullptr;
     int32_t* d_counts = nullptr;
     if (!sc.alloc(&d_theta, (size_t)S * ctx->P) || !sc.alloc(&d_ll, (size_t)S) || !sc.alloc(&d_vals, n_vals) ||
         !sc.alloc(&d_scratch, n_scratch) || !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_pit, cells) ||
-        !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2))
+        !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2) || !sc.alloc(&d_k, n_k))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     // uploads
@@ -1029,7 +1033,8 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     a.n_probs = n_probs; a.probs = d_probs; a.q_out = d_q; a.pit_out = pit ? d_pit : nullptr; a.counts = d_counts;
     a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
-    if (launch_predictive_draws(a, nullptr) != 0) return refuse(ctx, who, "draw kernel launch failed", SEPAIHRD_E_HIP);
+    const int drc = nb ? launch_predictive_draws_nb(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr) : launch_predictive_draws(a, nullptr);
+    if (drc != 0) return refuse(ctx, who, "draw kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
     if (launch_predictive_quantiles(a, nullptr) != 0) return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[3], nullptr);
@@ -1041,10 +1046,31 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, 
     res.fetch(pit, d_pit, cells * sizeof(double));
     res.fetch(means, d_means, n_means * sizeof(double));
     res.fetch(draws, d_draws, n_draws * sizeof(double));
+    res.fetch(k_used, d_k, n_k * sizeof(double));
     res.fetch(status, ctx->ws_status, (size_t)S * sizeof(int32_t));
     res.fetch(n_valid, d_counts, sizeof(int32_t));
     if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
+}
+
+int sepaihrd_ensemble_predictive(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* probs, int n_probs,
+                                 double* pred_quantiles, double* pit, double* means, double* draws, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    return predictive_call(ctx, theta, S, R, seed, nullptr, probs, n_probs, pred_quantiles, pit, means, draws, nullptr, status, n_valid);
+}
+
+int sepaihrd_ensemble_predictive_nb(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* dispersion,
+                                    const double* probs, int n_probs, double* pred_quantiles, double* pit, double* means, double* draws,
+                                    double* k_used, int32_t* status, int32_t* n_valid) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    NbDispersion nb = ctx->disp;  // NULL: what the deterministic objective would use for each theta
+    if (dispersion) {
+        char msg[256] = "";
+        const int rc = validated(ctx, sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)), msg);
+        if (rc != SEPAIHRD_OK) return rc;
+        for (int s = 0; s < 3; ++s) { nb.src[s] = -1; nb.fixed[s] = dispersion[s]; }
+    }
+    return predictive_call(ctx, theta, S, R, seed, &nb, probs, n_probs, pred_quantiles, pit, means, draws, k_used, status, n_valid);
 }
 
 int sepaihrd_predictive_timing(const sepaihrd_ctx* ctx, double* ms) {

@@ -128,6 +128,17 @@ int launch_predictive_draws(const PredictiveArgs& a, void* stream) {
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// the same two kernels around another draw kernel (csrc/sepaihrd_predictive_nb.hip)
+int launch_predictive_counts(const PredictiveArgs& a, void* stream) {
+    hipLaunchKernelGGL(predictive_count_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a.wstatus, a.S, a.R, a.counts);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+int launch_predictive_pit(const PredictiveArgs& a, void* stream) {
+    if (a.pit_out != nullptr)
+        hipLaunchKernelGGL(predictive_pit_kernel, dim3((unsigned)((size_t)3 * a.Tp * a.n)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 }  // namespace sepaihrd
 
 using namespace sepaihrd;

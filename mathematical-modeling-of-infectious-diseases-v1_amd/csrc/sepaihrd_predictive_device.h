@@ -29,6 +29,16 @@ struct PredictiveArgs {
 };
 // counts, the draws into vals / means / draws, and the mid-PIT of every usable observation (csrc/sepaihrd_predictive.hip)
 int launch_predictive_draws(const PredictiveArgs& a, void* stream);
+// The dispersed call's form of it (csrc/sepaihrd_predictive_nb.hip): the dispersion of every sample into
+// d_k_used [S][3] (sepaihrd_nb_ll_rows_kernel's rule; a sample with a NaN k becomes a failed one in d_wstatus = a.wstatus), then
+// the counts, the negative-binomial draws -- one lane per (draw, age, series) -- and the mid-PIT.  0, -3 (launch failure), -4.
+struct DevProblem;
+struct NbDispersion;
+int launch_predictive_draws_nb(const PredictiveArgs& a, const DevProblem& pb, const double* d_theta, const NbDispersion& disp, double* d_k_used,
+                               int32_t* d_wstatus, void* stream);
+// its parts that are csrc/sepaihrd_predictive.hip's own kernels: the counts before the draws, the mid-PIT (where a.pit_out) after
+int launch_predictive_counts(const PredictiveArgs& a, void* stream);
+int launch_predictive_pit(const PredictiveArgs& a, void* stream);
 // the quantiles of every segment with the ensemble's sorts and interpolation (csrc/sepaihrd_ensemble.hip)
 int launch_predictive_quantiles(const PredictiveArgs& a, void* stream);
 

@@ -217,6 +217,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_sir_validate_events", "sepaihrd_sir_scenario_ensemble", "sepaihrd_sir_ensemble_quantiles", "sepaihrd_sir_ensemble_timing",
     "sepaihrd_stoch_sir_num_steps", "sepaihrd_stoch_sir_validate", "sepaihrd_stoch_sir_run", "sepaihrd_stoch_sir_binomial_device",
     "sepaihrd_ensemble_predictive", "sepaihrd_predictive_validate", "sepaihrd_predictive_timing", "sepaihrd_poisson_device",
+    "sepaihrd_ensemble_predictive_nb", "sepaihrd_gamma_device", "sepaihrd_nb_draw_device",
     "sepaihrd_ensemble_stochastic", "sepaihrd_stochastic_validate", "sepaihrd_stochastic_values_width", "sepaihrd_stochastic_timing",
     "sepaihrd_particle_loglik", "sepaihrd_particle_validate", "sepaihrd_particle_max_particles", "sepaihrd_particle_timing",
     "sepaihrd_particle_resample_device",
@@ -363,6 +364,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_stochastic_values_width.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.sepaihrd_stochastic_timing.argtypes = [vp, vp]
     lib.sepaihrd_poisson_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_ensemble_predictive_nb.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_gamma_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
+    lib.sepaihrd_nb_draw_device.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_particle_loglik.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64] + [vp] * 7
     lib.sepaihrd_particle_validate.argtypes = [C.c_int] * 6 + [C.c_char_p, C.c_int]
     lib.sepaihrd_particle_max_particles.argtypes = [C.c_int]
@@ -643,12 +647,20 @@ class HipObjective:
             out["metrics"] = met
         return out
 
+    CONTEXT_DISPERSION = "context"  # ensemble_predictive(dispersion=...): the context's own, per sample
+
     def ensemble_predictive(self, theta, R: int, seed: int, probs, want_pit: bool = True, want_means: bool = False,
-                            want_draws: bool = False) -> dict:
+                            want_draws: bool = False, dispersion=None) -> dict:
         """Posterior predictive draws with Poisson noise (sepaihrd_ensemble_predictive): R replicates y ~ Poisson(mean) per
         sample.  pred [6][n_probs][T_pos][n] (quantiles over the draws of the valid samples), pit [3][T_pos][n] (mid-PIT of
         the usable observations, NaN elsewhere), means [S][3][T_pos][n], draws [S][R][3][T_pos][n], status [S], n_valid,
-        phase_ms (integrator; draws and PIT counts; sorts and quantiles)."""
+        phase_ms (integrator; draws and PIT counts; sorts and quantiles).
+        dispersion (None: the call above, whatever the context's dispersion): negative-binomial noise through
+        sepaihrd_ensemble_predictive_nb.  HipObjective.CONTEXT_DISPERSION ("context"): each sample's k as eval_batch would take it
+        (the constrained theta entry of a calibrated series, the fixed value of set_dispersion otherwise); (k_H, k_ICU, k_D): these
+        for every sample, each +inf or finite in [1e-3, 1e6] (ValueError otherwise).  The result gains k_used [S][3]."""
+        if dispersion is not None:
+            return self._ensemble_predictive_nb(theta, R, seed, probs, want_pit, want_means, want_draws, dispersion)
         th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
         pr = np.ascontiguousarray(probs, dtype=np.float64)
         S, npb, n, R = th.shape[0], pr.size, self.pb.n, int(R)
@@ -666,6 +678,41 @@ class HipObjective:
         ms = np.zeros(3)
         self._check(self.lib.sepaihrd_predictive_timing(self.ctx, ms.ctypes.data), "predictive_timing")
         out = {"pred": pred, "status": status, "n_valid": nv.value, "phase_ms": ms}
+        if want_pit:
+            out["pit"] = pit
+        if want_means:
+            out["means"] = means
+        if want_draws:
+            out["draws"] = draws
+        return out
+
+    def _ensemble_predictive_nb(self, theta, R, seed, probs, want_pit, want_means, want_draws, dispersion) -> dict:
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        S, npb, n, R = th.shape[0], pr.size, self.pb.n, int(R)
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        disp = None
+        if not (isinstance(dispersion, str) and dispersion == self.CONTEXT_DISPERSION):
+            disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+            if disp.size != 3:
+                raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+        pred = np.empty((6, npb, Tp, n))
+        pit = np.empty((3, Tp, n)) if want_pit else None
+        means = np.empty((S, 3, Tp, n)) if want_means else None
+        draws = np.empty((S, max(R, 0), 3, Tp, n)) if want_draws else None
+        k_used = np.empty((S, 3))
+        status = np.empty(S, dtype=np.int32)
+        nv = C.c_int32(0)
+        rc = self.lib.sepaihrd_ensemble_predictive_nb(
+            self.ctx, th.ctypes.data, S, R, int(seed) & 0xFFFFFFFFFFFFFFFF, None if disp is None else disp.ctypes.data, pr.ctypes.data, npb,
+            pred.ctypes.data, pit.ctypes.data if want_pit else None, means.ctypes.data if want_means else None,
+            draws.ctypes.data if want_draws else None, k_used.ctypes.data, status.ctypes.data, C.byref(nv))
+        if rc == -1 and disp is not None and not np.all(np.isposinf(disp) | ((disp >= 1e-3) & (disp <= 1e6))):
+            raise ValueError(self.lib.sepaihrd_last_error(self.ctx).decode())  # sepaihrd_particle_nb_validate's message
+        self._check(rc, "ensemble_predictive_nb")
+        ms = np.zeros(3)
+        self._check(self.lib.sepaihrd_predictive_timing(self.ctx, ms.ctypes.data), "predictive_timing")
+        out = {"pred": pred, "status": status, "n_valid": nv.value, "phase_ms": ms, "k_used": k_used}
         if want_pit:
             out["pit"] = pit
         if want_means:
@@ -874,6 +921,31 @@ class HipObjective:
                                               out.ctypes.data, err, len(err))
         if rc != 0:
             raise RuntimeError(f"sepaihrd_poisson_device failed ({rc}): " + err.value.decode())
+        return out
+
+    def gamma_device(self, shape, seed: int) -> np.ndarray:
+        """Probe of the device's gamma sampler (sepaihrd_gamma_device): out[i] ~ Gamma(shape[i], 1) at (seed, c0 = i, c1 = c2 = 0);
+        every shape finite in [1e-3, 1e6]."""
+        shape = np.ascontiguousarray(shape, dtype=np.float64).ravel()
+        out = np.empty(shape.size)
+        err = C.create_string_buffer(512)
+        rc = self.lib.sepaihrd_gamma_device(getattr(self, "_device", -1), int(seed) & 0xFFFFFFFFFFFFFFFF, shape.ctypes.data, shape.size,
+                                            out.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_gamma_device failed ({rc}): " + err.value.decode())
+        return out
+
+    def nb_draw_device(self, mu, k, seed: int) -> np.ndarray:
+        """Probe of the device's negative-binomial sampler (sepaihrd_nb_draw_device): out[i] ~ NB(mean mu[i], dispersion k[i]) at
+        (seed, c0 = i, c1 = c2 = 0); every k +inf (Poisson) or finite in [1e-3, 1e6]."""
+        mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.float64), mu.shape), dtype=np.float64).ravel()
+        out = np.empty(mu.size)
+        err = C.create_string_buffer(512)
+        rc = self.lib.sepaihrd_nb_draw_device(getattr(self, "_device", -1), int(seed) & 0xFFFFFFFFFFFFFFFF, mu.ctypes.data, k.ctypes.data,
+                                              mu.size, out.ctypes.data, err, len(err))
+        if rc != 0:
+            raise RuntimeError(f"sepaihrd_nb_draw_device failed ({rc}): " + err.value.decode())
         return out
 
     def scenario_ensemble(self, theta, kappa_mult, probs, want_sero: bool = False, want_rt: bool = False) -> dict:

@@ -24,6 +24,20 @@ int hostPosteriorPredictive(const double* means, const int32_t* status, const do
                             std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
                             std::string* error = nullptr);
 
+// The dispersed form, the twin of sepaihrd_ensemble_predictive_nb: k_used [S][3] as that call returns it next to means and status;
+// y ~ NegativeBinomial(m + 1e-10, k_used[s][series]) from csrc/sepaihrd_nb_draw.inc, a series at +inf the draws of the call above.
+// SEPAIHRD_E_INVALID_ARG also for a NULL k_used and for a valid sample's k that sepaihrd_particle_nb_validate refuses (its message).
+int hostPosteriorPredictiveNB(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                              int n_age, std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                              std::string* error = nullptr);
+
+// the gamma and negative-binomial samplers on the host: the variates at (seed, c0, c1, c2), and the twins of sepaihrd_gamma_device
+// and sepaihrd_nb_draw_device (c0 = i, c1 = c2 = 0)
+double hostGamma(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double shape);
+double hostNBDraw(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double mu, double k);
+void hostGammaProbe(std::uint64_t seed, const double* shape, int count, double* out);
+void hostNBDrawProbe(std::uint64_t seed, const double* mu, const double* k, int count, double* out);
+
 // the sampler on the host: the variate at (seed, c0, c1, c2), and the twin of sepaihrd_poisson_device (c0 = i, c1 = c2 = 0)
 double hostPoisson(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double lambda);
 void hostPoissonProbe(std::uint64_t seed, const double* lambda, int count, double* out);
@@ -38,6 +52,7 @@ struct PosteriorPredictiveDraws {
     std::vector<double> pit;             // [3][T_pos][n_age]
     std::vector<double> means, draws;    // [S][3][T_pos][n_age], [S][R][3][T_pos][n_age]; empty unless asked for
     std::vector<int32_t> status;         // [S]
+    std::vector<double> k_used;          // [S][3]: the dispersions drawn with; empty where the objective is not dispersed (Poisson draws)
 };
 
 class HipPosteriorPredictive {
@@ -49,12 +64,17 @@ public:
 
     // The device call over stored samples, selected by the PPC rule of HipPosteriorEnsemble::selectSamples
     // (num_samples_for_ppc draws with replacement from mt19937(random_seed) when 0 < num < size, else every sample in order).
+    // Where the objective is dispersed (setDispersion on objective(), or calibrated dispersion_* names) the call is
+    // sepaihrd_ensemble_predictive_nb with the context's dispersion: negative-binomial replicates, k_used filled.
     PosteriorPredictiveDraws draw(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc, unsigned int random_seed,
                                   int replicates, std::uint64_t seed, const std::vector<double>& probs, bool want_means = false,
                                   bool want_draws = false);
 
     // the observations as the device places them: [3][T_pos][n_age], row j of the data at output time j >= 0, NaN beyond the data
     std::vector<double> observed() const;
+
+    // the objective whose context the draws run on (setDispersion)
+    HipSEPAIHRDObjectiveFunction& objective() { return *objective_; }
 
 private:
     HipSEPAIHRDParameterManager& pm_;

@@ -1,5 +1,6 @@
 // host/src/HipPosteriorPredictive.cpp -- HipPosteriorPredictive, the CPU twin of sepaihrd_ensemble_predictive's draw, sort and
-// count passes.  The sampler is csrc/sepaihrd_poisson.inc, the text the kernel compiles; this library is built with -ffp-contract=off like the kernel.
+// count passes, and of sepaihrd_ensemble_predictive_nb's.  The samplers are csrc/sepaihrd_poisson.inc and csrc/sepaihrd_nb_draw.inc, the
+// texts the kernels compile; this library is built with -ffp-contract=off like the kernels.
 #include "epidemic_hip/HipPosteriorPredictive.hpp"
 
 #include <algorithm>
@@ -8,14 +9,17 @@
 #include <limits>
 
 #include "sepaihrd_hip.h"
+#include "sepaihrd_nb_draw.inc"
 #include "sepaihrd_poisson.inc"
 #include "sepaihrd_quantile.inc"
 
 namespace epidemic {
 
-int hostPosteriorPredictive(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
-                            std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
-                            std::string* error) {
+namespace {
+// both forms; k_used null: the Poisson call's draws
+int predictive_from_means(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                          int n_age, std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                          std::string* error) {
     char msg[256] = "";
     int vrc = sepaihrd_predictive_validate(S, R, T_pos, n_age, probs, n_probs, msg, (int)sizeof(msg));
     if (vrc == SEPAIHRD_OK && (!means || !status || !pred_quantiles)) {
@@ -46,7 +50,8 @@ int hostPosteriorPredictive(const double* means, const int32_t* status, const do
                 for (size_t k = 0; k < 3; ++k) {
                     const size_t cell = (k * Tp + t) * n + a;
                     const double m = means[((s * 3 + k) * Tp + t) * n + a];
-                    const double y = sepaihrd_poisson::poisson(seed, (uint32_t)s, (uint32_t)r, (uint32_t)cell, m + 1e-10);
+                    const double y = k_used ? sepaihrd_nb_draw::nb_variate(seed, (uint32_t)s, (uint32_t)r, (uint32_t)cell, m + 1e-10, k_used[s * 3 + k])
+                                            : sepaihrd_poisson::poisson(seed, (uint32_t)s, (uint32_t)r, (uint32_t)cell, m + 1e-10);
                     run[k] += y;
                     seg[(k * Tp + t) * nd + (size_t)d] = y;
                     seg[((k + 3) * Tp + t) * nd + (size_t)d] = run[k];
@@ -77,6 +82,50 @@ int hostPosteriorPredictive(const double* means, const int32_t* status, const do
         }
     }
     return SEPAIHRD_OK;
+}
+}  // namespace
+
+int hostPosteriorPredictive(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
+                            std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                            std::string* error) {
+    return predictive_from_means(means, status, nullptr, observed, S, R, T_pos, n_age, seed, probs, n_probs, pred_quantiles, pit, draws, error);
+}
+
+int hostPosteriorPredictiveNB(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                              int n_age, std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                              std::string* error) {
+    if (!k_used) {
+        if (error) *error = "ensemble_predictive: k_used must not be NULL";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    // a valid sample's dispersions are what the device call can have produced: each +inf or finite in [1e-3, 1e6]
+    for (int s = 0; s < S && status; ++s) {
+        if (status[s] != 0) continue;
+        char msg[256] = "";
+        if (sepaihrd_particle_nb_validate(k_used + (size_t)s * 3, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            if (error) *error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    return predictive_from_means(means, status, k_used, observed, S, R, T_pos, n_age, seed, probs, n_probs, pred_quantiles, pit, draws, error);
+}
+
+double hostGamma(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double shape) {
+    return sepaihrd_nb_draw::gamma(seed, c0, c1, c2, shape);
+}
+
+double hostNBDraw(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double mu, double k) {
+    return sepaihrd_nb_draw::nb_variate(seed, c0, c1, c2, mu, k);
+}
+
+void hostGammaProbe(std::uint64_t seed, const double* shape, int count, double* out) {
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < count; ++i) out[i] = sepaihrd_nb_draw::gamma(seed, (uint32_t)i, 0u, 0u, shape[i]);
+}
+
+void hostNBDrawProbe(std::uint64_t seed, const double* mu, const double* k, int count, double* out) {
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < count; ++i) out[i] = sepaihrd_nb_draw::nb_variate(seed, (uint32_t)i, 0u, 0u, mu[i], k[i]);
 }
 
 double hostPoisson(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double lambda) {
@@ -139,10 +188,23 @@ PosteriorPredictiveDraws HipPosteriorPredictive::draw(const std::vector<Eigen::V
     if (want_draws && replicates > 0) out.draws.assign(S * static_cast<size_t>(replicates) * cells, 0.0);
     out.status.assign(S, 0);
     int32_t nv = 0;
-    const int rc = sepaihrd_ensemble_predictive(ctx, thetas.data(), static_cast<int>(S), replicates, seed, probs.data(),
-                                                static_cast<int>(probs.size()), out.pred_quantiles.data(), out.pit.data(),
-                                                want_means ? out.means.data() : nullptr, out.draws.empty() ? nullptr : out.draws.data(),
-                                                out.status.data(), &nv);
+    // a dispersed objective (fixed values or calibrated dispersion_* names): the replicates carry its negative-binomial noise
+    double fixed_k[3];
+    bool dispersed = sepaihrd_get_dispersion(ctx, fixed_k) == SEPAIHRD_OK;
+    if (dispersed) dispersed = !(std::isinf(fixed_k[0]) && std::isinf(fixed_k[1]) && std::isinf(fixed_k[2]));  // NaN: calibrated
+    int rc;
+    if (dispersed) {
+        out.k_used.assign(S * 3, 0.0);
+        rc = sepaihrd_ensemble_predictive_nb(ctx, thetas.data(), static_cast<int>(S), replicates, seed, nullptr, probs.data(),
+                                             static_cast<int>(probs.size()), out.pred_quantiles.data(), out.pit.data(),
+                                             want_means ? out.means.data() : nullptr, out.draws.empty() ? nullptr : out.draws.data(),
+                                             out.k_used.data(), out.status.data(), &nv);
+    } else {
+        rc = sepaihrd_ensemble_predictive(ctx, thetas.data(), static_cast<int>(S), replicates, seed, probs.data(),
+                                          static_cast<int>(probs.size()), out.pred_quantiles.data(), out.pit.data(),
+                                          want_means ? out.means.data() : nullptr, out.draws.empty() ? nullptr : out.draws.data(),
+                                          out.status.data(), &nv);
+    }
     if (rc != SEPAIHRD_OK)
         throw ModelException("HipPosteriorPredictive", std::string("sepaihrd_ensemble_predictive: ") + sepaihrd_last_error(ctx));
     out.samples_used = nv;

@@ -1474,15 +1474,35 @@ int host_predictive_from_means(const double* means, const int32_t* status, const
     return rc;
 }
 
+// the dispersed form (hostPosteriorPredictiveNB): k_used [S][3] next to means and status
+int host_predictive_nb_from_means(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                                  int n_age, uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
+                                  char* err, int errlen) {
+    std::string error;
+    const int rc = hostPosteriorPredictiveNB(means, status, k_used, observed, S, R, T_pos, n_age, seed, probs, n_probs, pred_quantiles, pit, draws, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+// the gamma and negative-binomial samplers (no device): one variate, and the twins of sepaihrd_gamma_device / sepaihrd_nb_draw_device
+double host_gamma_at(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, double shape) { return hostGamma(seed, c0, c1, c2, shape); }
+double host_nb_draw_at(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, double mu, double k) { return hostNBDraw(seed, c0, c1, c2, mu, k); }
+void host_gamma_probe(uint64_t seed, const double* shape, int count, double* out) { hostGammaProbe(seed, shape, count, out); }
+void host_nb_draw_probe(uint64_t seed, const double* mu, const double* k, int count, double* out) { hostNBDrawProbe(seed, mu, k, count, out); }
+
 // HipPosteriorPredictive::draw over the handle's parameter manager / data.  samples: n_samples x P, selected by the PPC rule
 // (num_for_ppc, ppc_seed).  pred [6][n_probs][T_pos][n], pit [3][T_pos][n], observed [3][T_pos][n]; means / draws (nullable)
 // [n_selected][3][T_pos][n] / [n_selected][R][3][T_pos][n]; selected and status: capacity max(n_samples, num_for_ppc).
-int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int num_for_ppc, uint32_t ppc_seed,
-                    int R, uint64_t seed, const double* probs, int n_probs, double* pred, double* pit, double* observed, double* means,
-                    double* draws, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
+// host_predictive_dispersed: the same with k_used (nullable; capacity as status, [n_selected][3]) and *dispersed = whether the draws
+// ran through sepaihrd_ensemble_predictive_nb -- they do where the handle's objective is dispersed, through host_objective_set_dispersion
+// or calibrated dispersion_* names.
+int host_predictive_dispersed(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int num_for_ppc,
+                              uint32_t ppc_seed, int R, uint64_t seed, const double* probs, int n_probs, double* pred, double* pit, double* observed,
+                              double* means, double* draws, double* k_used, int32_t* dispersed, int32_t* selected, int32_t* n_selected,
+                              int32_t* status, int32_t* samples_used) {
     auto* h = static_cast<HostHandle*>(hv);
     return guarded([&] {
         HipPosteriorPredictive pp = posterior_over<HipPosteriorPredictive>(*h, pb, device);
+        if (h->has_dispersion) pp.objective().setDispersion(h->dispersion);
         const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
         const PosteriorPredictiveDraws d = pp.draw(ps, num_for_ppc, ppc_seed, R, seed, std::vector<double>(probs, probs + n_probs), means != nullptr,
                                                    draws != nullptr);
@@ -1494,11 +1514,20 @@ int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const doub
         }
         if (means) std::copy(d.means.begin(), d.means.end(), means);
         if (draws) std::copy(d.draws.begin(), d.draws.end(), draws);
+        if (k_used) std::copy(d.k_used.begin(), d.k_used.end(), k_used);
+        if (dispersed) *dispersed = d.k_used.empty() ? 0 : 1;
         for (size_t i = 0; i < d.selected.size(); ++i) selected[i] = d.selected[i];
         *n_selected = static_cast<int32_t>(d.selected.size());
         if (status) std::copy(d.status.begin(), d.status.end(), status);
         *samples_used = d.samples_used;
     });
+}
+
+int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int num_for_ppc, uint32_t ppc_seed,
+                    int R, uint64_t seed, const double* probs, int n_probs, double* pred, double* pit, double* observed, double* means,
+                    double* draws, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
+    return host_predictive_dispersed(hv, pb, device, samples, n_samples, num_for_ppc, ppc_seed, R, seed, probs, n_probs, pred, pit, observed, means,
+                                     draws, nullptr, nullptr, selected, n_selected, status, samples_used);
 }
 
 // ---- stochastic chain-binomial SEPAIHRD ensembles (HipStochasticSEPAIHRD) ----

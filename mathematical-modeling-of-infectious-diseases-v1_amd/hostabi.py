@@ -131,6 +131,18 @@ def load_library() -> C.CDLL:
                                                C.c_char_p, C.c_int]
     lib.host_predictive.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint64,
                                     vp, C.c_int] + [vp] * 9
+    lib.host_predictive_dispersed.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int,
+                                              C.c_uint64, vp, C.c_int] + [vp] * 11
+    lib.host_predictive_nb_from_means.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, vp, vp,
+                                                  C.c_char_p, C.c_int]
+    lib.host_gamma_at.restype = C.c_double
+    lib.host_gamma_at.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
+    lib.host_nb_draw_at.restype = C.c_double
+    lib.host_nb_draw_at.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double]
+    lib.host_gamma_probe.restype = None
+    lib.host_gamma_probe.argtypes = [C.c_uint64, vp, C.c_int, vp]
+    lib.host_nb_draw_probe.restype = None
+    lib.host_nb_draw_probe.argtypes = [C.c_uint64, vp, vp, C.c_int, vp]
     lib.host_stochastic_from_values.argtypes = [C.c_int] * 4 + [vp] * 7 + [C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, C.c_int] + \
         [vp] * 4 + [C.c_char_p, C.c_int]
     lib.host_stochastic_manager_values.argtypes = [vp, C.c_int, vp, vp]
@@ -428,8 +440,10 @@ class HostObjective:
                              probs=(0.025, 0.05, 0.5, 0.95, 0.975), want_means: bool = False, want_draws: bool = False,
                              device: int = -1) -> dict:
         """HipPosteriorPredictive::draw over this handle's parameter manager and data: the samples picked by the PPC rule of
-        posterior_ensemble, R Poisson replicates each.  pred [6][n_probs][T_pos][n], pit and observed [3][T_pos][n], selected,
-        status, samples_used; means [S][3][T_pos][n] and draws [S][R][3][T_pos][n] on request."""
+        posterior_ensemble, R replicates each -- Poisson, or negative-binomial where the objective is dispersed (set_dispersion on
+        this handle, or calibrated dispersion_* names): then `dispersed` is True and k_used [S][3] holds every sample's dispersions.
+        pred [6][n_probs][T_pos][n], pit and observed [3][T_pos][n], selected, status, samples_used; means [S][3][T_pos][n] and
+        draws [S][R][3][T_pos][n] on request."""
         ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
         pr = np.ascontiguousarray(probs, dtype=np.float64)
         keep: list = []
@@ -442,14 +456,15 @@ class HostObjective:
         means = np.empty((S, 3, Tp, n)) if want_means else None
         draws = np.empty((S, max(int(R), 0), 3, Tp, n)) if want_draws else None
         sel, status = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
-        nsel, used = C.c_int32(0), C.c_int32(0)
-        _check(self.lib.host_predictive(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data, pit.ctypes.data,
-                                        obs.ctypes.data, means.ctypes.data if want_means else None,
-                                        draws.ctypes.data if want_draws else None, sel.ctypes.data, C.byref(nsel), status.ctypes.data,
-                                        C.byref(used)), "host_predictive: ")
+        nsel, used, dispersed = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        k_used = np.full((cap, 3), np.inf)
+        _check(self.lib.host_predictive_dispersed(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data, pit.ctypes.data,
+                                                  obs.ctypes.data, means.ctypes.data if want_means else None,
+                                                  draws.ctypes.data if want_draws else None, k_used.ctypes.data, C.byref(dispersed),
+                                                  sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used)), "host_predictive: ")
         out = {"pred": pred, "pit": pit, "observed": obs, "selected": sel[:nsel.value].copy(), "status": status[:nsel.value].copy(),
-               "samples_used": used.value}
+               "samples_used": used.value, "dispersed": bool(dispersed.value), "k_used": k_used[:nsel.value].copy()}
         if want_means:
             out["means"] = means
         if want_draws:
@@ -1065,10 +1080,39 @@ def observed_table(pb) -> np.ndarray:
     return out
 
 
-def predictive_from_means(means, status, observed, R: int, seed: int, probs, want_pit: bool = True, want_draws: bool = True) -> dict:
+def gamma_at(seed: int, c0: int, c1: int, c2: int, shape: float) -> float:
+    """the Gamma(shape, 1) variate at these coordinates of the stream (csrc/sepaihrd_nb_draw.inc)"""
+    return float(load_library().host_gamma_at(int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), int(c1), int(c2), float(shape)))
+
+
+def nb_draw_at(seed: int, c0: int, c1: int, c2: int, mu: float, k: float) -> float:
+    """the negative-binomial variate (mean mu, dispersion k; k = +inf: Poisson) at these coordinates of the stream"""
+    return float(load_library().host_nb_draw_at(int(seed) & 0xFFFFFFFFFFFFFFFF, int(c0), int(c1), int(c2), float(mu), float(k)))
+
+
+def gamma_probe(shape, seed: int) -> np.ndarray:
+    """the twin of HipObjective.gamma_device: out[i] ~ Gamma(shape[i], 1) at (seed, c0 = i, c1 = c2 = 0)"""
+    shape = np.ascontiguousarray(shape, dtype=np.float64).ravel()
+    out = np.empty(shape.size)
+    load_library().host_gamma_probe(int(seed) & 0xFFFFFFFFFFFFFFFF, shape.ctypes.data, shape.size, out.ctypes.data)
+    return out
+
+
+def nb_draw_probe(mu, k, seed: int) -> np.ndarray:
+    """the twin of HipObjective.nb_draw_device: out[i] ~ NB(mu[i], k[i]) at (seed, c0 = i, c1 = c2 = 0)"""
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.float64), mu.shape), dtype=np.float64).ravel()
+    out = np.empty(mu.size)
+    load_library().host_nb_draw_probe(int(seed) & 0xFFFFFFFFFFFFFFFF, mu.ctypes.data, k.ctypes.data, mu.size, out.ctypes.data)
+    return out
+
+
+def predictive_from_means(means, status, observed, R: int, seed: int, probs, want_pit: bool = True, want_draws: bool = True,
+                          k_used=None) -> dict:
     """The twin of HipObjective.ensemble_predictive after the integration: from means [S][3][T_pos][n] and status [S] (and
     observed [3][T_pos][n], NaN where there is none) the same pred [6][n_probs][T_pos][n], pit [3][T_pos][n] and draws
-    [S][R][3][T_pos][n], bit for bit."""
+    [S][R][3][T_pos][n], bit for bit.  k_used [S][3] (None: Poisson draws): the twin of the dispersed call, negative-binomial
+    draws with every sample's own dispersions as that call returns them."""
     m = np.ascontiguousarray(means, dtype=np.float64)
     if m.ndim != 4 or m.shape[1] != 3:
         raise ValueError("means must be [S][3][T_pos][n]")
@@ -1086,10 +1130,15 @@ def predictive_from_means(means, status, observed, R: int, seed: int, probs, wan
     pit = np.empty((3, Tp, n)) if want_pit and ob is not None else None
     draws = np.empty((S, R, 3, Tp, n)) if want_draws else None
     err = C.create_string_buffer(512)
-    rc = load_library().host_predictive_from_means(m.ctypes.data, st.ctypes.data, None if ob is None else ob.ctypes.data, S, R, Tp, n,
-                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data,
-                                                   None if pit is None else pit.ctypes.data, None if draws is None else draws.ctypes.data,
-                                                   err, len(err))
+    tail = (None if ob is None else ob.ctypes.data, S, R, Tp, n, int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, pred.ctypes.data,
+            None if pit is None else pit.ctypes.data, None if draws is None else draws.ctypes.data, err, len(err))
+    if k_used is None:
+        rc = load_library().host_predictive_from_means(m.ctypes.data, st.ctypes.data, *tail)
+    else:
+        ku = np.ascontiguousarray(k_used, dtype=np.float64)
+        if ku.shape != (S, 3):
+            raise ValueError("k_used must be [S][3]")
+        rc = load_library().host_predictive_nb_from_means(m.ctypes.data, st.ctypes.data, ku.ctypes.data, *tail)
     if rc != 0:
         raise ValueError(err.value.decode())
     out = {"pred": pred, "n_valid": int(np.sum(st == 0))}

@@ -56,6 +56,10 @@ def main():
                     help="also the chains' convergence diagnostics on the device (split R-hat, bulk / tail ESS over the post-burn-in "
                          "samples): parameter_posteriors/posterior_diagnostics.csv, and max_r_hat / min_ess_bulk / min_ess_tail in "
                          "run_summary.json")
+    ap.add_argument("--predictive-replicates", type=int, default=0,
+                    help="also the replicated-data check (posterior_predictive/<series>_predictive_*.csv, pit_*.csv, "
+                         "predictive_coverage.csv): this many replicates per pooled sample, drawn under the problem's observation "
+                         "model -- negative-binomial where the problem carries a dispersion (fixed or calibrated), else Poisson")
     args = ap.parse_args()
 
     mm = mmid_amd_loader.load()
@@ -99,6 +103,12 @@ def main():
     hip.set_initial_state_mode(1)
     ens = hip.ensemble_quantiles(pooled, PROBS, want_sero=True, want_rt=True, want_metrics=True)
     t_ens = time.perf_counter() - t0
+    predictive = None
+    if args.predictive_replicates > 0:
+        # a fixed dispersion is +inf or finite, a calibrated one reads NaN: anything but three +inf is a dispersed problem
+        dispersed = not np.all(np.isposinf(hip.get_dispersion()))
+        predictive = hip.ensemble_predictive(pooled, args.predictive_replicates, args.seed + 2, PROBS,
+                                             dispersion=hip.CONTEXT_DISPERSION if dispersed else None)
     times = np.asarray(pb.times)
     pos = times[times >= 0]
     # the reference's post-calibration output tree (file names, headers and number formats of AnalysisWriter.cpp; what
@@ -132,7 +142,8 @@ def main():
         with open(os.path.join(args.out, "scenarios", "scenario_posterior.json"), "w") as fh:
             json.dump(post, fh, indent=1)
     mm.config_io.write_post_calibration_tree(args.out, times, ens, pooled, list(pb.param_names), pb.n, observed=observed,
-                                             scenarios=scenario_rows, ene_covid=args.scenarios, diagnostics=diag)
+                                             scenarios=scenario_rows, ene_covid=args.scenarios, diagnostics=diag,
+                                             predictive=predictive)
     assert len(pos) == ens["ppc"].shape[2]
 
     evals = args.chains * args.mcmc_iterations
@@ -140,7 +151,8 @@ def main():
                "best_value": cal["best_value"], "algorithm": args.algorithm, "chains": args.chains, "mcmc_iterations": args.mcmc_iterations,
                "acceptance_rate_mean": float(cal["accept_trace"].mean()), "calibration_seconds": t_cal,
                "proposals_per_s": evals / t_cal, "ensemble_samples": int(len(pooled)), "ensemble_valid": int(ens["n_valid"]),
-               "ensemble_seconds": t_ens, "median_R0": float(np.nanmedian(ens["metrics"][:, 0])), "out": args.out}
+               "ensemble_seconds": t_ens, "predictive_noise": None if predictive is None else ("negative_binomial" if "k_used" in predictive else "poisson"),
+               "median_R0": float(np.nanmedian(ens["metrics"][:, 0])), "out": args.out}
     if diag is not None:
         summary.update(max_r_hat=float(np.nanmax(diag[:, 6])), min_ess_bulk=float(np.nanmin(diag[:, 4])),
                        min_ess_tail=float(np.nanmin(diag[:, 5])))
