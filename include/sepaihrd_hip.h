@@ -847,8 +847,9 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx *ctx, const double *theta, int S, 
                                  double *pred_quantiles, double *pit, double *means, double *draws, int32_t *status, int32_t *n_valid);
 /* Host only: the argument rules above that need no context, with a message in err (NULL: not wanted). */
 int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, const double *probs, int n_probs, char *err, int errlen);
-/* Device time of the context's last sepaihrd_ensemble_predictive or sepaihrd_ensemble_predictive_nb call in milliseconds, ms[3]:
- * integrator; draws and mid-PIT counts; segment sorts and quantiles. */
+/* Device time of the context's last sepaihrd_ensemble_predictive, sepaihrd_ensemble_predictive_nb or
+ * sepaihrd_ensemble_predictive_scores call in milliseconds, ms[3]: integrator; draws and mid-PIT counts (the scored call has no PIT
+ * pass); segment sorts and quantiles (and, in the scored call, the scores). */
 int sepaihrd_predictive_timing(const sepaihrd_ctx *ctx, double *ms);
 /* Probe of the device's Poisson sampler: out[i] ~ Poisson(lambda[i]), the variate at (seed, c0 = i, c1 = 0, c2 = 0).
  * lambda [count], out [count], host memory; lambda <= 0 gives 0, NaN and +infinity give NaN. */
@@ -881,6 +882,45 @@ int sepaihrd_ensemble_predictive_nb(sepaihrd_ctx *ctx, const double *theta, int 
  * same or +inf (Poisson); mu <= 0 gives 0, NaN and +infinity give NaN. */
 int sepaihrd_gamma_device(int device, uint64_t seed, const double *shape, int count, double *out, char *err, int errlen);
 int sepaihrd_nb_draw_device(int device, uint64_t seed, const double *mu, const double *k, int count, double *out, char *err, int errlen);
+
+/* ---- scores of the posterior predictive draws against data (additive; SEPAIHRD_ABI_VERSION stays) ---------------------------
+ * Which observation model predicts the data better, and how well does a fit forecast days it never saw?  Proper scoring rules of
+ * the predictive sample against the observation, cell by cell and averaged: CRPS, the interval score of each central interval
+ * and their weighted sum (WIS), empirical coverage, the absolute error of the median.  The reference has none; this is this
+ * build's own.  sepaihrd_ensemble_predictive_scores is sepaihrd_ensemble_predictive_nb -- same preconditions, failure codes,
+ * memory rule, stream coordinates and failed-sample rule, the same draws bit for bit, and pred_quantiles, means, draws, k_used,
+ * status, n_valid that call's for the same inputs (with observed == NULL so is pit) -- and scores every (time, age) cell of the
+ * three daily series from the segment of m = n_valid R draws while it is still sorted for the quantiles: no segment is sorted
+ * twice, and the mid-PIT comes from the sorted segment's counts instead of a pass of its own.
+ *   observed     [3][T_pos][n_age] or NULL: the table every score and the PIT of this call are taken against; NULL: the context's
+ *                observations.  A cell is usable when its value is finite and >= 0 (it need not be an integer).  A fit with the
+ *                days after T0 set to NaN, scored with the full table, is a forecast check
+ *   levels       [n_levels], 0 <= n_levels <= 8 (L below): central coverage levels c, each strictly inside (0, 1)
+ *   cell_scores  [3][T_pos][n_age][5 + 4 L]: mean S1 / m; variance (S2 - S1 S1 / m) / (m - 1), NaN for m = 1; median q(0.5);
+ *                CRPS A / m - G / (m m) with A = sum |x - y| and G = sum_i (2 i - m + 1) x(i) over the sorted draws;
+ *                WIS (0.5 |y - median| + sum_l (alpha_l / 2) IS_l) / (L + 0.5), alpha_l = 1 - c_l; then per level
+ *                lo = q(0.5 - 0.5 c), hi = q(0.5 + 0.5 c), IS = (hi - lo) + (2 / alpha)(max(0, lo - y) + max(0, y - hi)),
+ *                covered (1.0 or 0.0).  q is the quantile rule of pred_quantiles.  Mean, variance, median, lo, hi for every cell
+ *                with m > 0; CRPS, WIS, IS, covered NaN where the cell is not usable; every field NaN when m = 0
+ *   summary      [3][n_age + 1][4 + 2 L], entry n_age pooling all ages: the number of usable cells, the means of CRPS, WIS and
+ *                |y - median|, per level the coverage fraction and the mean IS; sums from 0.0 over the usable cells with time
+ *                ascending (pooled: ages ascending within a time); a count of 0 gives NaN means
+ *   pit          [3][T_pos][n_age] or NULL: (n_less + 0.5 n_eq) / m against `observed`
+ *   exact        NULL or [1]: 1 when, for every daily cell, m x_max max(m, x_max) < 2^53.  The draws are integers, so every sum
+ *                above is then exact and independent of the order it is formed in, and the host twin
+ *                (hostPosteriorPredictiveScores, the text csrc/sepaihrd_predictive_score.inc) gives the same bits from means,
+ *                status and k_used; 0: the scores are right to rounding but not promised equal to the twin's
+ * SEPAIHRD_E_INVALID_ARG with a message that names the first wrong argument; sepaihrd_predictive_scores_validate is the same
+ * check without a context (host only).  sepaihrd_predictive_timing reports this call when it was the last; its third phase is
+ * sorts, quantiles and scores. */
+int sepaihrd_ensemble_predictive_scores(sepaihrd_ctx *ctx, const double *theta, int S, int R, uint64_t seed,
+                                        const double *dispersion /* [3] or NULL: the context's, as in _predictive_nb */,
+                                        const double *observed /* [3][T_pos][n_age] or NULL: the context's observations */,
+                                        const double *probs, int n_probs, const double *levels, int n_levels, double *pred_quantiles,
+                                        double *pit, double *cell_scores, double *summary, double *means, double *draws, double *k_used,
+                                        int32_t *status, int32_t *n_valid, int32_t *exact);
+int sepaihrd_predictive_scores_validate(int S, int R, int T_pos, int n_age, const double *probs, int n_probs, const double *levels,
+                                        int n_levels, char *err, int errlen);
 
 /* ---- stochastic chain-binomial SEPAIHRD ensembles over posterior samples (additive; SEPAIHRD_ABI_VERSION stays) -------------
  * Process noise for the age-structured model: the ensemble calls above give parameter uncertainty and observation noise, this

@@ -534,7 +534,8 @@ def write_posterior_predictive(out_dir: str, times_pos, ppc: np.ndarray, observe
     return written
 
 
-def write_posterior_predictive_draws(out_dir: str, times_pos, pred: np.ndarray, pit, observed: Dict[str, np.ndarray]) -> List[str]:
+def write_posterior_predictive_draws(out_dir: str, times_pos, pred: np.ndarray, pit, observed: Dict[str, np.ndarray],
+                                     scores: dict | None = None) -> List[str]:
     """The replicated-data check beside write_posterior_predictive's files (the reference has no such output: its bands are of
     expectations), into the same directory:
       <series>_predictive_{median,lower90,upper90,lower95,upper95}.csv   bands of y_rep around the mean under the observation model
@@ -545,6 +546,12 @@ def write_posterior_predictive_draws(out_dir: str, times_pos, pred: np.ndarray, 
       predictive_coverage.csv                       ``series,age,n_observations,coverage_90,coverage_95``: per daily series with
                                                     observations and age, the share of usable observations (finite and >= 0) inside
                                                     [lower90, upper90] and [lower95, upper95], computed here; nan without any
+      predictive_scores.csv                         only with `scores` (a HipObjective.ensemble_predictive_scores result: keys summary
+                                                    [3][n + 1][4 + 2 L] and levels [L]): ``series,age,n_observations,crps,wis,
+                                                    abs_err_median,coverage_<c>,interval_score_<c>...`` per daily series and age, and
+                                                    age ``all`` for the pooled entry; the means over the usable cells as the device
+                                                    formed them (17 significant digits, nan without any).  Without `scores` the files
+                                                    and their bytes are those of the list above
     pred: [6 series][5 PPC_PROBS][T_pos][n] (HipObjective.ensemble_predictive at PPC_PROBS, with or without a dispersion); pit: [3][T_pos][n] or None;
     observed: series -> [T_pos][n]."""
     os.makedirs(out_dir, exist_ok=True)
@@ -590,7 +597,26 @@ def write_posterior_predictive_draws(out_dir: str, times_pos, pred: np.ndarray, 
                 in95 = np.sum((o >= pred[si, lo95, :, a]) & (o <= pred[si, hi95, :, a]) & usable) / cnt
                 fh.write("%s,%d,%d,%.6f,%.6f\n" % (name, a, cnt, in90, in95))
     written.append(path)
+    if scores is not None:
+        written.append(write_predictive_scores(os.path.join(out_dir, "predictive_scores.csv"), scores["summary"], scores["levels"]))
     return written
+
+
+def write_predictive_scores(path: str, summary, levels) -> str:
+    """predictive_scores.csv from the summary [3][n + 1][4 + 2 L] of sepaihrd_ensemble_predictive_scores at the L central levels:
+    one row per (daily series, age) and one with age ``all`` for the pooled entry."""
+    summary = np.asarray(summary, dtype=np.float64)
+    levels = [float(c) for c in np.asarray(levels, dtype=np.float64).ravel()]
+    if summary.ndim != 3 or summary.shape[0] != 3 or summary.shape[2] != 4 + 2 * len(levels):
+        raise ValueError("summary must be [3][n + 1][4 + 2 L]")
+    n = summary.shape[1] - 1
+    with open(path, "w") as fh:
+        fh.write("series,age,n_observations,crps,wis,abs_err_median" + "".join(f",coverage_{c:g},interval_score_{c:g}" for c in levels) + "\n")
+        for si, name in enumerate(PPC_SERIES[:3]):
+            for a in range(n + 1):
+                row = summary[si, a]
+                fh.write("%s,%s,%d" % (name, a if a < n else "all", int(row[0])) + "".join(",%.17g" % v for v in row[1:]) + "\n")
+    return path
 
 
 def write_aggregated_trajectory(path: str, times, quantiles: np.ndarray) -> None:
@@ -786,7 +812,8 @@ def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: n
     scenarios/scenario_comparison.csv; ene_covid: seroprevalence/ene_covid_validation.csv from the metric table;
     diagnostics (a table as write_posterior_diagnostics takes it): parameter_posteriors/posterior_diagnostics.csv;
     predictive (a HipObjective.ensemble_predictive result at PPC_PROBS, Poisson or dispersed, keys pred and pit): the files of
-    write_posterior_predictive_draws next to the bands of expectations."""
+    write_posterior_predictive_draws next to the bands of expectations; a HipObjective.ensemble_predictive_scores result (it also
+    has summary and levels) adds predictive_scores.csv."""
     times = np.asarray(times, dtype=np.float64)
     write_posterior_predictive(os.path.join(out_base, "posterior_predictive"), times[times >= 0], ensemble["ppc"], observed or {})
     write_parameter_posteriors(os.path.join(out_base, "parameter_posteriors"), samples, names, burn_in, thinning)
@@ -806,4 +833,4 @@ def write_post_calibration_tree(out_base: str, times, ensemble: dict, samples: n
         write_posterior_diagnostics(os.path.join(out_base, "parameter_posteriors", "posterior_diagnostics.csv"), names, diagnostics)
     if predictive is not None:
         write_posterior_predictive_draws(os.path.join(out_base, "posterior_predictive"), times[times >= 0], predictive["pred"],
-                                         predictive.get("pit"), observed or {})
+                                         predictive.get("pit"), observed or {}, scores=predictive if "summary" in predictive else None)

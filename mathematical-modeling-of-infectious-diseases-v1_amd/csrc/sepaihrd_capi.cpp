@@ -103,7 +103,8 @@ struct sepaihrd_ctx {
     DeviceBuf fd_dev;
     PinnedBuf fd_host;
     Event fd_ev_uploaded, fd_ev_centre;
-    // the last sepaihrd_ensemble_predictive call: integrator, draws and mid-PIT counts, sorts and quantiles (ms)
+    // the last sepaihrd_ensemble_predictive call (or _nb, or _scores): integrator, draws and mid-PIT counts, sorts and quantiles --
+    // with the scores in the scored call, which has no PIT pass (ms)
     double pred_ms[3] = {0.0, 0.0, 0.0};
     // the last sepaihrd_ensemble_stochastic call: step kernel, sorts and quantiles (ms)
     double stoch_ms[2] = {0.0, 0.0};
@@ -967,18 +968,30 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx* ctx, const double* theta, int S, c
 // The body of sepaihrd_ensemble_predictive and sepaihrd_ensemble_predictive_nb.  nb == nullptr: the Poisson call, its draw kernel
 // and nothing else.  Otherwise the dispersion every sample's draws take: the call's own three values (src = -1 throughout) or the
 // context's (the objective's rule, per sample), resolved on the device into k_used [S][3].
+// sr (sepaihrd_ensemble_predictive_scores; null: no scores): the segments are scored where they are sorted and the mid-PIT comes
+// from the sorted segment, so the draw launch takes no PIT pass.
+struct ScoreRequest {
+    const double* observed;  // [3][T_pos][n_age] host or null: the context's observations
+    const double* levels;
+    int n_levels;
+    double *cell_scores, *summary;
+    int32_t* exact;
+};
 static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const NbDispersion* nb, const double* probs,
                            int n_probs, double* pred_quantiles, double* pit, double* means, double* draws, double* k_used, int32_t* status,
-                           int32_t* n_valid) {
-    const char* const who = "ensemble_predictive";
+                           int32_t* n_valid, const ScoreRequest* sr = nullptr) {
+    const char* const who = sr ? "ensemble_predictive_scores" : "ensemble_predictive";
     int rc = ensemble_preflight(ctx, who, S > 0 && theta && probs && pred_quantiles, "need S > 0, theta, probs (1..1024) and pred_quantiles",
                                 CHECK_PENDING | CHECK_F64 | CHECK_TP, probs, n_probs);
     if (rc != SEPAIHRD_OK) return rc;
     const DevProblem& dp = ctx->dp;
     const int Tp = dp.T - dp.runup_offset;
     char msg[256] = "";
-    rc = validated(ctx, sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)), msg);
+    rc = validated(ctx, sr ? sepaihrd_predictive_scores_validate(S, R, Tp, dp.n, probs, n_probs, sr->levels, sr->n_levels, msg, (int)sizeof(msg))
+                              : sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)), msg);
     if (rc != SEPAIHRD_OK) return rc;
+    if (sr && !sr->cell_scores) return refuse(ctx, who, "cell_scores must not be NULL", SEPAIHRD_E_INVALID_ARG);
+    if (sr && !sr->summary) return refuse(ctx, who, "summary must not be NULL", SEPAIHRD_E_INVALID_ARG);
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     // sizes
     const size_t N = (size_t)S * (size_t)R;
@@ -993,9 +1006,12 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     const size_t n_scratch = sort_scratch_doubles(plan, n_vals);
     const size_t n_means = means ? (size_t)S * cells : 0, n_draws = draws ? N * cells : 0;
     const size_t n_k = nb ? (size_t)S * 3 : 0;
+    const size_t L = sr ? (size_t)sr->n_levels : 0;
+    const size_t n_cs = sr ? cells * (size_t)(5 + 4 * L) : 0, n_sum = sr ? (size_t)3 * (dp.n + 1) * (4 + 2 * L) : 0, n_obs = sr ? cells : 0;
     // the rule of sepaihrd_scenario_ensemble: the buffers below plus the likelihood workspace must fit the device's memory
     // (the segment table dominates: 6 T_pos n_age segments of S R doubles)
-    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + n_k + (size_t)n_probs) +
+    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + n_k + (size_t)n_probs +
+                                               n_cs + n_sum + n_obs + L + 1) +
                               sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) +
                               sizeof(int32_t) * (chains + 2);
     rc = require_device_memory(ctx, need_bytes, "ensemble_predictive: the segment table of S x R = " + std::to_string(N) + " draws needs",
@@ -1006,16 +1022,23 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     if (rc != SEPAIHRD_OK) return rc;
     CallScratch sc(4);
     double *d_theta = nullptr, *d_ll = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_pit = nullptr,
-           *d_means = nullptr, *d_draws = nullptr, *d_k = nullptr;
-    int32_t* d_counts = nullptr;
+           *d_means = nullptr, *d_draws = nullptr, *d_k = nullptr, *d_cs = nullptr, *d_sum = nullptr, *d_obs = nullptr, *d_levels = nullptr;
+    int32_t *d_counts = nullptr, *d_exact = nullptr;
     if (!sc.alloc(&d_theta, (size_t)S * ctx->P) || !sc.alloc(&d_ll, (size_t)S) || !sc.alloc(&d_vals, n_vals) ||
         !sc.alloc(&d_scratch, n_scratch) || !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_pit, cells) ||
-        !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2) || !sc.alloc(&d_k, n_k))
+        !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2) || !sc.alloc(&d_k, n_k) ||
+        (sr && (!sc.alloc(&d_cs, n_cs) || !sc.alloc(&d_sum, n_sum) || !sc.alloc(&d_obs, n_obs) || !sc.alloc(&d_levels, L) || !sc.alloc(&d_exact, 1))))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     // uploads
     HIP_TRY(hipMemcpy(d_theta, theta, (size_t)S * ctx->P * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     HIP_TRY(hipMemcpy(d_probs, probs, (size_t)n_probs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    if (sr) {
+        const int32_t one = 1;
+        HIP_TRY(hipMemcpy(d_exact, &one, sizeof(one), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+        if (L > 0) HIP_TRY(hipMemcpy(d_levels, sr->levels, L * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+        if (sr->observed) HIP_TRY(hipMemcpy(d_obs, sr->observed, n_obs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    }
     // launches
     EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
     rc = fence_before(ctx, nullptr);  // an evaluation of this context may still be running on another stream
@@ -1030,13 +1053,21 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     a.seed = seed;
     a.cum = ctx->ws_cum; a.wstatus = ctx->ws_status; a.grid = dp.grid;
     a.vals = d_vals; a.means = means ? d_means : nullptr; a.draws = draws ? d_draws : nullptr;
-    a.n_probs = n_probs; a.probs = d_probs; a.q_out = d_q; a.pit_out = pit ? d_pit : nullptr; a.counts = d_counts;
+    a.n_probs = n_probs; a.probs = d_probs; a.q_out = d_q; a.pit_out = pit && !sr ? d_pit : nullptr; a.counts = d_counts;
     a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
     const int drc = nb ? launch_predictive_draws_nb(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr) : launch_predictive_draws(a, nullptr);
     if (drc != 0) return refuse(ctx, who, "draw kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
-    if (launch_predictive_quantiles(a, nullptr) != 0) return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
+    if (sr) {
+        PredictiveScoreArgs sa{};
+        sa.obs = d_obs; sa.obs_from_grid = sr->observed == nullptr;
+        sa.levels = d_levels; sa.n_levels = sr->n_levels;
+        sa.cell_scores = d_cs; sa.summary = d_sum; sa.pit_out = pit ? d_pit : nullptr; sa.exact = d_exact;
+        if (launch_predictive_scores(a, sa, nullptr) != 0) return refuse(ctx, who, "score launch failed", SEPAIHRD_E_HIP);
+    } else if (launch_predictive_quantiles(a, nullptr) != 0) {
+        return refuse(ctx, who, "quantile launch failed", SEPAIHRD_E_HIP);
+    }
     (void)hipEventRecord(sc.ev[3], nullptr);
     HIP_TRY(hipDeviceSynchronize(), ctx, return SEPAIHRD_E_HIP);
     elapsed_ms(sc.ev, ctx->pred_ms, 3);
@@ -1049,6 +1080,11 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     res.fetch(k_used, d_k, n_k * sizeof(double));
     res.fetch(status, ctx->ws_status, (size_t)S * sizeof(int32_t));
     res.fetch(n_valid, d_counts, sizeof(int32_t));
+    if (sr) {
+        res.fetch(sr->cell_scores, d_cs, n_cs * sizeof(double));
+        res.fetch(sr->summary, d_sum, n_sum * sizeof(double));
+        res.fetch(sr->exact, d_exact, sizeof(int32_t));
+    }
     if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
 }
@@ -1071,6 +1107,34 @@ int sepaihrd_ensemble_predictive_nb(sepaihrd_ctx* ctx, const double* theta, int 
         for (int s = 0; s < 3; ++s) { nb.src[s] = -1; nb.fixed[s] = dispersion[s]; }
     }
     return predictive_call(ctx, theta, S, R, seed, &nb, probs, n_probs, pred_quantiles, pit, means, draws, k_used, status, n_valid);
+}
+
+int sepaihrd_predictive_scores_validate(int S, int R, int T_pos, int n_age, const double* probs, int n_probs, const double* levels, int n_levels,
+                                        char* err, int errlen) {
+    const int rc = sepaihrd_predictive_validate(S, R, T_pos, n_age, probs, n_probs, err, errlen);
+    if (rc != SEPAIHRD_OK) return rc;
+    auto refuse = [&](const std::string& msg) { set_err(err, errlen, "ensemble_predictive_scores: " + msg); return SEPAIHRD_E_INVALID_ARG; };
+    if (n_levels < 0 || n_levels > 8) return refuse("n_levels must lie in 0..8 (central coverage levels)");
+    if (n_levels > 0 && !levels) return refuse("levels must not be NULL where n_levels > 0");
+    for (int l = 0; l < n_levels; ++l)
+        if (!(levels[l] > 0.0 && levels[l] < 1.0)) return refuse("levels must lie strictly inside (0, 1): levels[" + std::to_string(l) + "] does not");
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_ensemble_predictive_scores(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* dispersion,
+                                        const double* observed, const double* probs, int n_probs, const double* levels, int n_levels,
+                                        double* pred_quantiles, double* pit, double* cell_scores, double* summary, double* means, double* draws,
+                                        double* k_used, int32_t* status, int32_t* n_valid, int32_t* exact) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    NbDispersion nb = ctx->disp;  // NULL: the context's, as in sepaihrd_ensemble_predictive_nb
+    if (dispersion) {
+        char msg[256] = "";
+        const int rc = validated(ctx, sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)), msg);
+        if (rc != SEPAIHRD_OK) return rc;
+        for (int s = 0; s < 3; ++s) { nb.src[s] = -1; nb.fixed[s] = dispersion[s]; }
+    }
+    const ScoreRequest sr{observed, levels, n_levels, cell_scores, summary, exact};
+    return predictive_call(ctx, theta, S, R, seed, &nb, probs, n_probs, pred_quantiles, pit, means, draws, k_used, status, n_valid, &sr);
 }
 
 int sepaihrd_predictive_timing(const sepaihrd_ctx* ctx, double* ms) {

@@ -39,6 +39,7 @@
 #include "sepaihrd_device.h"
 #include "sepaihrd_host_util.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_predictive_score.inc"
 #include "sepaihrd_quantile.inc"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_sir_device.h"
@@ -497,9 +498,10 @@ int sort_segments_global(const double* vals, int segments, int S_pad, double* sc
 // what every launcher asks of the segments it is handed: `count` values each, in a pad the plan gives (sepaihrd_segments.h)
 bool pad_legal(size_t count, int pad) { return pad > 0 && segment_pad_valid(count, (size_t)pad); }
 
-// the LDS sort of plan.pad doubles needs the kernel's dynamic-LDS limit raised above 48 KiB; 0 or -3
-int raise_lds_limit(const SegmentPlan& plan, const void* lds_kernel) {
-    const size_t lds = plan.pad * sizeof(double);
+// the LDS sort of plan.pad doubles (and `extra_bytes` the kernel keeps next to them) needs the kernel's dynamic-LDS limit raised
+// above 48 KiB; 0 or -3
+int raise_lds_limit(const SegmentPlan& plan, const void* lds_kernel, size_t extra_bytes = 0) {
+    const size_t lds = plan.pad * sizeof(double) + extra_bytes;
     if (!plan.in_lds || lds <= 48 * 1024) return 0;
     return hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -3;
 }
@@ -821,6 +823,155 @@ int launch_predictive_quantiles(const PredictiveArgs& a, void* stream) {
     e.n_valid = a.counts + 1;
     e.rt_segment0 = (int)segments;
     return launch_sort_pick(EnsemblePick{e, (int)segments}, e.vals, e.S_pad, (int)segments, a.sort_scratch, a.sort_scratch_doubles, st);
+}
+
+}  // namespace sepaihrd
+
+// ---- scores of the posterior predictive draws (sepaihrd_ensemble_predictive_scores): the quantiles above
+// and, from the same sorted segment, the scoring rules of csrc/sepaihrd_predictive_score.inc for every cell of the three daily
+// series.  A segment is sorted once: in LDS the workgroup that sorted it reduces its sums before it leaves, beyond the LDS sort a
+// workgroup per daily segment reads the radix sort's scratch ----
+namespace sepaihrd {
+namespace {
+
+// what the kernels below take by value: the cells, the draw count and where the scores go
+struct ScoreCells {
+    int cells, Tp, n, L;     // 3 Tp n daily segments come first in the segment table
+    const int32_t* counts;   // PredictiveArgs::counts: [1] = draws per segment
+    const double* obs;       // [cells]
+    const double* levels;    // [L]
+    double* cell_scores;     // [cells][5 + 4 L]
+    double* pit_out;         // [cells] or null
+    int32_t* exact;
+    double* summary;         // [3][n + 1][4 + 2 L]
+};
+
+constexpr int SCORE_MAX_WAVES = 16;                       // of a 1024-lane workgroup
+constexpr int SCORE_SUMS = 6;                             // S1, S2, S_less, G, n_less, n_eq
+constexpr size_t SCORE_RED_BYTES = SCORE_MAX_WAVES * SCORE_SUMS * sizeof(double);  // 768: the cross-wave step
+
+// v of lane + off added down to lane 0 of the wave; lanes past `active` (a workgroup of 32 lanes is half a wave) add nothing
+template <class T>
+__device__ __forceinline__ T wave_sum(T v, const int lane, const int active) {
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        const T o = __shfl_down(v, off, WAVE);
+        if (lane + off < active) v += o;
+    }
+    return v;
+}
+
+// The sums of sorted segment `seg` (LDS or device memory; m valid draws first) against the cell's observation, reduced by the
+// whole workgroup -- lane-strided reads of consecutive doubles: conflict-free in LDS, coalesced in device memory -- then the cell
+// rule by one lane.  Every partial sum is a sum of integers and exact below 2^53, so the shape of the reduction does not show;
+// where sums_exact fails the cell says so in *exact.  red: SCORE_RED_BYTES of LDS.
+__device__ __forceinline__ void score_sorted_segment(const ScoreCells& sc, const size_t cell, const double* seg, double* red) {
+    const int tid = threadIdx.x, BS = blockDim.x;
+    const int m = sc.counts[1];
+    const double y = sc.obs[cell];
+    sepaihrd_score::SegmentSums s = {0, 0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < m; i += BS) sepaihrd_score::add_draw(s, seg[i], i, m, y);
+    const int lane = tid % WAVE, wave = tid / WAVE;
+    const int active = (BS - wave * WAVE < WAVE) ? BS - wave * WAVE : WAVE;
+    const double S1 = wave_sum(s.S1, lane, active), S2 = wave_sum(s.S2, lane, active), S_less = wave_sum(s.S_less, lane, active),
+                 G = wave_sum(s.G, lane, active);
+    const int n_less = wave_sum((int)s.n_less, lane, active), n_eq = wave_sum((int)s.n_eq, lane, active);
+    if (lane == 0) {
+        double* r = red + wave * SCORE_SUMS;
+        r[0] = S1; r[1] = S2; r[2] = S_less; r[3] = G; r[4] = (double)n_less; r[5] = (double)n_eq;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double t[SCORE_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int waves = (BS + WAVE - 1) / WAVE;
+    for (int w = 0; w < waves; ++w)
+#pragma unroll
+        for (int k = 0; k < SCORE_SUMS; ++k) t[k] += red[w * SCORE_SUMS + k];
+    const sepaihrd_score::SegmentSums total = {(int64_t)t[4], (int64_t)t[5], t[0], t[1], t[2], t[3]};
+    sepaihrd_score::cell_rule(seg, (size_t)m, y, total, sc.levels, sc.L, sc.cell_scores + cell * (size_t)sepaihrd_score::cell_width(sc.L));
+    if (sc.pit_out != nullptr) sc.pit_out[cell] = sepaihrd_score::pit_of(total, (size_t)m, y);
+    if (m > 0 && !sepaihrd_score::sums_exact((size_t)m, seg[m - 1])) *sc.exact = 0;
+}
+
+// the sibling of segment_sort_pick_kernel<EnsemblePick>: one workgroup per segment of Np doubles sorts it in LDS and stores the
+// quantile picks; for a daily segment it then scores the segment still in LDS.  Dynamic LDS: Np doubles, then SCORE_RED_BYTES.
+__global__ void segment_sort_score_kernel(const EnsemblePick pick, const ScoreCells sc, const double* vals, const int Np) {
+    extern __shared__ double seg[];
+    const size_t sid = blockIdx.x;
+    lds_bitonic_sort(seg, vals + sid * (size_t)Np, Np);
+    for (int p = threadIdx.x; p < pick.picks(); p += blockDim.x) pick(sid, p, seg);
+    if (sid < (size_t)sc.cells) score_sorted_segment(sc, sid, seg, seg + Np);
+}
+
+// beyond the LDS sort: one workgroup per daily segment of a group the radix sort has left in `sorted`
+constexpr int SCORE_SORTED_BLOCK = 256;
+__global__ __launch_bounds__(SCORE_SORTED_BLOCK) void segment_score_sorted_kernel(const ScoreCells sc, const double* sorted, const int Np,
+                                                                                  const int first_segment) {
+    __shared__ double red[SCORE_MAX_WAVES * SCORE_SUMS];
+    score_sorted_segment(sc, (size_t)first_segment + blockIdx.x, sorted + (size_t)blockIdx.x * Np, red);
+}
+
+// the observations of every daily cell as predictive_pit_kernel reads them from the context's grid
+__global__ __launch_bounds__(256) void score_observed_kernel(const PredictiveArgs a, double* obs) {
+    const size_t cell = (size_t)blockIdx.x * 256 + threadIdx.x;  // (series Tp + t) n + age
+    if (cell >= (size_t)3 * a.Tp * a.n) return;
+    const int age = (int)(cell % a.n);
+    const int t = (int)((cell / a.n) % a.Tp);
+    const int ser = (int)(cell / ((size_t)a.n * a.Tp));
+    obs[cell] = a.grid[((size_t)(a.runup_offset + t) * a.lpc + age) * 4 + ser];
+}
+
+// One lane per (series, age or pooled, field): the walk of csrc/sepaihrd_predictive_score.inc over the cell scores in its stated
+// order, the sum in a register.  A lane per field instead of one per entry: an entry's 4 + 2 L sums are independent chains of
+// additions, and a lane that carried them all would serve each in turn.
+__global__ __launch_bounds__(WAVE) void score_summary_kernel(const ScoreCells sc) {
+    const int SW = sepaihrd_score::summary_width(sc.L);
+    const int idx = (int)(blockIdx.x * (unsigned)WAVE + threadIdx.x);
+    if (idx >= 3 * (sc.n + 1) * SW) return;
+    const int e = idx / SW, f = idx % SW;
+    sc.summary[idx] = sepaihrd_score::summary_field(sc.cell_scores, sc.obs, (size_t)sc.counts[1], sc.Tp, sc.n, sc.L, e / (sc.n + 1), e % (sc.n + 1), f);
+}
+
+}  // namespace
+
+int launch_predictive_scores(const PredictiveArgs& a, const PredictiveScoreArgs& sa, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t segments = (size_t)6 * a.Tp * a.n;
+    if (a.S <= 0 || a.R <= 0 || segments >= ((size_t)1 << 31) || !pad_legal((size_t)a.S * a.R, a.N_pad)) return -4;
+    if (sa.n_levels < 0 || sa.n_levels > sepaihrd_score::MAX_LEVELS || !sa.obs || !sa.cell_scores || !sa.summary || !sa.exact ||
+        (sa.n_levels > 0 && !sa.levels))
+        return -4;
+    EnsembleArgs e{};
+    e.S = a.S * a.R; e.S_pad = a.N_pad; e.lpc = a.lpc; e.n = a.n; e.T = a.T; e.Tp = a.Tp;
+    e.n_probs = a.n_probs; e.probs = a.probs;
+    e.vals = a.vals; e.q_out = a.q_out;
+    e.n_valid = a.counts + 1;
+    e.rt_segment0 = (int)segments;
+    const EnsemblePick pick{e, (int)segments};
+    const int cells = 3 * a.Tp * a.n, pad = a.N_pad;
+    const ScoreCells sc{cells, a.Tp, a.n, sa.n_levels, a.counts, sa.obs, sa.levels, sa.cell_scores, sa.pit_out, sa.exact, sa.summary};
+    if (sa.obs_from_grid) hipLaunchKernelGGL(score_observed_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a, sa.obs);
+    const SegmentPlan plan = plan_of_pad((size_t)pad);
+    if (plan.in_lds && raise_lds_limit(plan, reinterpret_cast<const void*>(&segment_sort_score_kernel), SCORE_RED_BYTES) != 0) return -3;
+    const int rc = sort_segments_and_pick(
+        plan, (int)segments, a.vals, a.sort_scratch, a.sort_scratch_doubles, st, nullptr,
+        [&](int threads, size_t lds) {
+            hipLaunchKernelGGL(segment_sort_score_kernel, dim3((unsigned)segments), dim3(threads), lds + SCORE_RED_BYTES, st, pick, sc, a.vals, pad);
+        },
+        [&](int first, int ng) {
+            constexpr int BLOCK = EnsemblePick::SORTED_BLOCK;
+            const size_t work = (size_t)ng * pick.picks();
+            hipLaunchKernelGGL(segment_pick_sorted_kernel<EnsemblePick>, dim3((unsigned)((work + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, pick,
+                               a.sort_scratch, pad, first, ng);
+            const int daily = (first + ng < cells ? first + ng : cells) - first;  // the group's segments that are daily cells
+            if (daily > 0)
+                hipLaunchKernelGGL(segment_score_sorted_kernel, dim3((unsigned)daily), dim3(SCORE_SORTED_BLOCK), 0, st, sc, a.sort_scratch, pad,
+                                   first);
+        });
+    if (rc != 0) return rc;
+    const int fields = 3 * (a.n + 1) * sepaihrd_score::summary_width(sa.n_levels);
+    hipLaunchKernelGGL(score_summary_kernel, dim3((unsigned)((fields + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, sc);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace sepaihrd

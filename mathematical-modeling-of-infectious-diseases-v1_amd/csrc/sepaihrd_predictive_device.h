@@ -42,4 +42,20 @@ int launch_predictive_pit(const PredictiveArgs& a, void* stream);
 // the quantiles of every segment with the ensemble's sorts and interpolation (csrc/sepaihrd_ensemble.hip)
 int launch_predictive_quantiles(const PredictiveArgs& a, void* stream);
 
+// What sepaihrd_ensemble_predictive_scores adds to the quantiles: every daily segment, still sorted, is
+// scored against its observation by the rules of csrc/sepaihrd_predictive_score.inc.
+struct PredictiveScoreArgs {
+    double* obs;             // [3][Tp][n] device: the table the scores are taken against
+    bool obs_from_grid;      // obs is filled here with the context's observations (PredictiveArgs::grid, as the PIT kernel reads them)
+    const double* levels;    // [n_levels] device
+    int n_levels;
+    double* cell_scores;     // [3][Tp][n][5 + 4 n_levels] device
+    double* summary;         // [3][n + 1][4 + 2 n_levels] device
+    double* pit_out;         // [3][Tp][n] device or null: the mid-PIT from the sorted segment's counts
+    int32_t* exact;          // [1] device, 1 on entry: set to 0 by a cell whose sums may round
+};
+// launch_predictive_quantiles with the scores: the same sorts and picks (each segment sorted once), the cell rule on every daily
+// segment -- in LDS after the picks, or over the radix sort's scratch -- and the summary walk.  a.pit_out is not read.
+int launch_predictive_scores(const PredictiveArgs& a, const PredictiveScoreArgs& sa, void* stream);
+
 }  // namespace sepaihrd

@@ -218,6 +218,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_stoch_sir_num_steps", "sepaihrd_stoch_sir_validate", "sepaihrd_stoch_sir_run", "sepaihrd_stoch_sir_binomial_device",
     "sepaihrd_ensemble_predictive", "sepaihrd_predictive_validate", "sepaihrd_predictive_timing", "sepaihrd_poisson_device",
     "sepaihrd_ensemble_predictive_nb", "sepaihrd_gamma_device", "sepaihrd_nb_draw_device",
+    "sepaihrd_ensemble_predictive_scores", "sepaihrd_predictive_scores_validate",
     "sepaihrd_ensemble_stochastic", "sepaihrd_stochastic_validate", "sepaihrd_stochastic_values_width", "sepaihrd_stochastic_timing",
     "sepaihrd_particle_loglik", "sepaihrd_particle_validate", "sepaihrd_particle_max_particles", "sepaihrd_particle_timing",
     "sepaihrd_particle_resample_device",
@@ -229,6 +230,41 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_set_dispersion", "sepaihrd_get_dispersion", "sepaihrd_dispersion_validate", "sepaihrd_nb_objective_host",
     "sepaihrd_lgamma_host", "sepaihrd_lgamma_device",
 )
+
+SCORE_SERIES = ("hospitalizations", "icu_admissions", "deaths")
+
+
+def score_views(cell_scores, summary, observed, levels) -> dict:
+    """Named views of cell_scores [3][T_pos][n][5 + 4 L] and summary [3][n + 1][4 + 2 L] as sepaihrd_ensemble_predictive_scores
+    lays them out -- mean, variance, median, crps, wis [3][T_pos][n]; lower, upper, interval_score, covered [L][3][T_pos][n];
+    summary_count, summary_crps, summary_wis, summary_abs_err_median [3][n + 1]; summary_coverage, summary_interval_score
+    [L][3][n + 1] -- and dawid_sebastiani [3][T_pos][n]: (y - mean)^2 / variance + log(variance) against `observed`, formed here
+    from the mean and the variance (it is not part of the ABI), NaN where the variance is 0 or the cell is not usable, with
+    summary_dawid_sebastiani [3][n + 1] its mean over the cells where it is finite."""
+    cs, sm = np.asarray(cell_scores), np.asarray(summary)
+    L = np.asarray(levels).size
+    out = {name: cs[..., f] for f, name in enumerate(("mean", "variance", "median", "crps", "wis"))}
+    for f, name in enumerate(("lower", "upper", "interval_score", "covered")):
+        out[name] = np.moveaxis(cs[..., 5 + f::4], -1, 0) if L else np.empty((0,) + cs.shape[:3])
+    for f, name in enumerate(("summary_count", "summary_crps", "summary_wis", "summary_abs_err_median")):
+        out[name] = sm[..., f]
+    out["summary_coverage"] = np.moveaxis(sm[..., 4::2], -1, 0) if L else np.empty((0,) + sm.shape[:2])
+    out["summary_interval_score"] = np.moveaxis(sm[..., 5::2], -1, 0) if L else np.empty((0,) + sm.shape[:2])
+    y = np.asarray(observed, dtype=np.float64)
+    var = np.where(out["variance"] > 0.0, out["variance"], np.nan)
+    usable = np.isfinite(y) & (y >= 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ds = np.where(usable, (y - out["mean"]) ** 2 / var + np.log(var), np.nan)
+    out["dawid_sebastiani"] = ds
+    pooled = np.empty(sm.shape[:2])
+    for k in range(ds.shape[0]):
+        for a in range(ds.shape[2] + 1):
+            v = ds[k, :, a] if a < ds.shape[2] else ds[k].ravel()
+            v = v[np.isfinite(v)]
+            pooled[k, a] = v.mean() if v.size else np.nan
+    out["summary_dawid_sebastiani"] = pooled
+    return out
+
 
 F_DISPERSION = 28  # enum sepaihrd_field SEPAIHRD_F_DISPERSION: param_index 0, 1, 2 = the dispersion of the H, ICU, D series
 
@@ -365,6 +401,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_stochastic_timing.argtypes = [vp, vp]
     lib.sepaihrd_poisson_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_ensemble_predictive_nb.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_ensemble_predictive_scores.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, C.c_int, vp, C.c_int,
+                                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.sepaihrd_predictive_scores_validate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_char_p, C.c_int]
     lib.sepaihrd_gamma_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_nb_draw_device.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_particle_loglik.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64] + [vp] * 7
@@ -719,6 +758,63 @@ class HipObjective:
             out["means"] = means
         if want_draws:
             out["draws"] = draws
+        return out
+
+    def ensemble_predictive_scores(self, theta, R: int, seed: int, probs, levels, observed=None, dispersion="context",
+                                   want_means: bool = False, want_draws: bool = False) -> dict:
+        """The posterior predictive draws scored against data on the device (sepaihrd_ensemble_predictive_scores): the dict of
+        ensemble_predictive(..., dispersion=dispersion) -- pred, pit, status, n_valid, phase_ms, k_used, means and draws on
+        request, the same bits -- plus cell_scores [3][T_pos][n][5 + 4 L], summary [3][n + 1][4 + 2 L] (entry n pools the ages),
+        exact (the sums were exact: the host twin gives the same bits), levels, observed (the table scored against) and the named
+        views of score_views.  observed [3][T_pos][n] (None: the context's observations) is what the scores and the PIT are taken
+        against: a cell is usable when finite and >= 0.  levels: up to 8 central coverage levels inside (0, 1).  phase_ms: integrator;
+        draws and counts; sorts, quantiles and scores.  ValueError for an argument sepaihrd_predictive_scores_validate refuses."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+        S, npb, n, R, L = th.shape[0], pr.size, self.pb.n, int(R), lv.size
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        ob = None
+        if observed is not None:
+            ob = np.ascontiguousarray(observed, dtype=np.float64)
+            if ob.shape != (3, Tp, n):
+                raise ValueError("observed must be [3][T_pos][n]: (3, %d, %d), not %s" % (Tp, n, ob.shape))
+        disp = None
+        if not (isinstance(dispersion, str) and dispersion == self.CONTEXT_DISPERSION):
+            disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+            if disp.size != 3:
+                raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+        err = C.create_string_buffer(512)
+        if S > 0 and R > 0 and self.lib.sepaihrd_predictive_validate(S, R, Tp, n, pr.ctypes.data, npb, None, 0) == 0 and \
+                self.lib.sepaihrd_predictive_scores_validate(S, R, Tp, n, pr.ctypes.data, npb, lv.ctypes.data, L, err, len(err)) != 0:
+            raise ValueError(err.value.decode())  # the levels: the arguments of the predictive call keep its own errors
+        pred, pit = np.empty((6, npb, Tp, n)), np.empty((3, Tp, n))
+        cell_scores, summary = np.empty((3, Tp, n, 5 + 4 * L)), np.empty((3, n + 1, 4 + 2 * L))
+        means = np.empty((S, 3, Tp, n)) if want_means else None
+        draws = np.empty((S, max(R, 0), 3, Tp, n)) if want_draws else None
+        k_used = np.empty((S, 3))
+        status = np.empty(S, dtype=np.int32)
+        nv, exact = C.c_int32(0), C.c_int32(0)
+        rc = self.lib.sepaihrd_ensemble_predictive_scores(
+            self.ctx, th.ctypes.data, S, R, int(seed) & 0xFFFFFFFFFFFFFFFF, None if disp is None else disp.ctypes.data,
+            None if ob is None else ob.ctypes.data, pr.ctypes.data, npb, lv.ctypes.data, L, pred.ctypes.data, pit.ctypes.data,
+            cell_scores.ctypes.data, summary.ctypes.data, means.ctypes.data if want_means else None,
+            draws.ctypes.data if want_draws else None, k_used.ctypes.data, status.ctypes.data, C.byref(nv), C.byref(exact))
+        if rc == -1 and disp is not None and not np.all(np.isposinf(disp) | ((disp >= 1e-3) & (disp <= 1e6))):
+            raise ValueError(self.lib.sepaihrd_last_error(self.ctx).decode())  # sepaihrd_particle_nb_validate's message
+        self._check(rc, "ensemble_predictive_scores")
+        ms = np.zeros(3)
+        self._check(self.lib.sepaihrd_predictive_timing(self.ctx, ms.ctypes.data), "predictive_timing")
+        if ob is None:
+            from . import hostabi
+            ob = hostabi.observed_table(self.pb)
+        out = {"pred": pred, "pit": pit, "status": status, "n_valid": nv.value, "phase_ms": ms, "k_used": k_used,
+               "cell_scores": cell_scores, "summary": summary, "exact": bool(exact.value), "levels": lv, "observed": ob}
+        if want_means:
+            out["means"] = means
+        if want_draws:
+            out["draws"] = draws
+        out.update(score_views(cell_scores, summary, ob, lv))
         return out
 
     def ensemble_stochastic(self, theta, R: int, steps_per_interval: int, seed: int, probs, keep: int = 0, want_extinct: bool = True,

@@ -31,6 +31,21 @@ int hostPosteriorPredictiveNB(const double* means, const int32_t* status, const 
                               int n_age, std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
                               std::string* error = nullptr);
 
+// The scored form, the twin of sepaihrd_ensemble_predictive_scores (k_used NULL: Poisson draws): draws, pred_quantiles and pit as
+// above -- the pit from the sorted segment's counts -- and cell_scores [3][T_pos][n_age][5 + 4 L], summary [3][n_age + 1][4 + 2 L]
+// and *exact (nullable) by the text the kernels compile, csrc/sepaihrd_predictive_score.inc, after a std::sort of every segment:
+// bit for bit where exact is 1.  observed [3][T_pos][n_age] is required.  SEPAIHRD_E_INVALID_ARG with
+// sepaihrd_predictive_scores_validate's message.
+int hostPosteriorPredictiveScores(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                                  int n_age, std::uint64_t seed, const double* probs, int n_probs, const double* levels, int n_levels,
+                                  double* pred_quantiles, double* pit, double* cell_scores, double* summary, double* draws, int32_t* exact,
+                                  std::string* error = nullptr);
+
+// one unsorted sample x [m] against one observation y: scores [5 + 4 L] as a cell of cell_scores, its mid-PIT and whether its sums
+// are exact (both nullable)
+int hostScoreCell(const double* x, int m, double y, const double* levels, int n_levels, double* scores, double* pit, int32_t* exact,
+                  std::string* error = nullptr);
+
 // the gamma and negative-binomial samplers on the host: the variates at (seed, c0, c1, c2), and the twins of sepaihrd_gamma_device
 // and sepaihrd_nb_draw_device (c0 = i, c1 = c2 = 0)
 double hostGamma(std::uint64_t seed, std::uint32_t c0, std::uint32_t c1, std::uint32_t c2, double shape);
@@ -55,6 +70,14 @@ struct PosteriorPredictiveDraws {
     std::vector<double> k_used;          // [S][3]: the dispersions drawn with; empty where the objective is not dispersed (Poisson draws)
 };
 
+// draw()'s result with the scores of sepaihrd_ensemble_predictive_scores
+struct PosteriorPredictiveScores : PosteriorPredictiveDraws {
+    std::vector<double> levels;       // the central coverage levels, L of them
+    std::vector<double> cell_scores;  // [3][T_pos][n_age][5 + 4 L]
+    std::vector<double> summary;      // [3][n_age + 1][4 + 2 L]
+    bool exact = false;               // the sums were exact: the host twin gives the same bits
+};
+
 class HipPosteriorPredictive {
 public:
     HipPosteriorPredictive(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
@@ -70,6 +93,13 @@ public:
                                   int replicates, std::uint64_t seed, const std::vector<double>& probs, bool want_means = false,
                                   bool want_draws = false);
 
+    // The scored call (sepaihrd_ensemble_predictive_scores) over the samples draw() would select, with the context's dispersion as
+    // draw() picks it: Poisson draws where the objective is not dispersed.  k_used is always filled.  observed_table
+    // [3][T_pos][n_age] (null: the data the object was built over) is what the scores and the PIT are taken against.
+    PosteriorPredictiveScores score(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc, unsigned int random_seed,
+                                    int replicates, std::uint64_t seed, const std::vector<double>& probs, const std::vector<double>& levels,
+                                    const std::vector<double>* observed_table = nullptr, bool want_means = false, bool want_draws = false);
+
     // the observations as the device places them: [3][T_pos][n_age], row j of the data at output time j >= 0, NaN beyond the data
     std::vector<double> observed() const;
 
@@ -77,6 +107,10 @@ public:
     HipSEPAIHRDObjectiveFunction& objective() { return *objective_; }
 
 private:
+    // the header fields of `out`, its selection, and the selected samples as one S x P table (empty: nothing to simulate)
+    std::vector<double> selectedThetas(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc, unsigned int random_seed,
+                                       int replicates, const std::vector<double>& probs, PosteriorPredictiveDraws& out) const;
+
     HipSEPAIHRDParameterManager& pm_;
     const CalibrationData& data_;
     std::vector<double> time_points_;

@@ -11,17 +11,31 @@
 #include "sepaihrd_hip.h"
 #include "sepaihrd_nb_draw.inc"
 #include "sepaihrd_poisson.inc"
+#include "sepaihrd_predictive_score.inc"
 #include "sepaihrd_quantile.inc"
 
 namespace epidemic {
 
 namespace {
+// what the scored form adds: every daily segment is scored after its sort, and the PIT comes from the sorted segment's counts
+struct ScoreOut {
+    const double* levels;
+    int n_levels;
+    double *cell_scores, *summary;
+    int32_t* exact;
+};
+
 // both forms; k_used null: the Poisson call's draws
 int predictive_from_means(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
                           int n_age, std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
-                          std::string* error) {
+                          std::string* error, const ScoreOut* so = nullptr) {
     char msg[256] = "";
-    int vrc = sepaihrd_predictive_validate(S, R, T_pos, n_age, probs, n_probs, msg, (int)sizeof(msg));
+    int vrc = so ? sepaihrd_predictive_scores_validate(S, R, T_pos, n_age, probs, n_probs, so->levels, so->n_levels, msg, (int)sizeof(msg))
+                 : sepaihrd_predictive_validate(S, R, T_pos, n_age, probs, n_probs, msg, (int)sizeof(msg));
+    if (vrc == SEPAIHRD_OK && so && (!observed || !so->cell_scores || !so->summary)) {
+        std::snprintf(msg, sizeof(msg), "ensemble_predictive_scores: observed, cell_scores and summary must not be NULL");
+        vrc = SEPAIHRD_E_INVALID_ARG;
+    }
     if (vrc == SEPAIHRD_OK && (!means || !status || !pred_quantiles)) {
         std::snprintf(msg, sizeof(msg), "ensemble_predictive: means, status and pred_quantiles must not be NULL");
         vrc = SEPAIHRD_E_INVALID_ARG;
@@ -39,6 +53,7 @@ int predictive_from_means(const double* means, const int32_t* status, const doub
     if (draws)
         for (int s = 0; s < S; ++s)
             if (status[s] != 0) std::fill(draws + (size_t)s * R * 3 * Tp * n, draws + (size_t)(s + 1) * R * 3 * Tp * n, qnan);
+    int all_exact = 1;
     // one age class at a time: its 6 T_pos segments of nd draws
     std::vector<double> seg((size_t)6 * Tp * nd);
     for (size_t a = 0; a < n; ++a) {
@@ -62,7 +77,7 @@ int predictive_from_means(const double* means, const int32_t* status, const doub
         for (long long sg = 0; sg < (long long)(6 * Tp); ++sg) {
             const size_t ser = (size_t)sg / Tp, t = (size_t)sg % Tp;
             double* x = seg.data() + (size_t)sg * nd;
-            if (pit && ser < 3) {
+            if (pit && ser < 3 && !so) {
                 const size_t cell = (ser * Tp + t) * n + a;
                 const double obs = observed ? observed[cell] : qnan;
                 double v = qnan;
@@ -77,13 +92,69 @@ int predictive_from_means(const double* means, const int32_t* status, const doub
                 pit[cell] = v;
             }
             std::sort(x, x + nd);
+            if (so && ser < 3) {
+                const size_t cell = (ser * Tp + t) * n + a;
+                const double obs = observed[cell];
+                const sepaihrd_score::SegmentSums sums = sepaihrd_score::segment_sums(x, nd, obs);
+                sepaihrd_score::cell_rule(x, nd, obs, sums, so->levels, so->n_levels,
+                                          so->cell_scores + cell * (size_t)sepaihrd_score::cell_width(so->n_levels));
+                if (pit) pit[cell] = sepaihrd_score::pit_of(sums, nd, obs);
+                if (nd > 0 && !sepaihrd_score::sums_exact(nd, x[nd - 1])) {
+#pragma omp atomic write
+                    all_exact = 0;
+                }
+            }
             for (int p = 0; p < n_probs; ++p)
                 pred_quantiles[((ser * (size_t)n_probs + (size_t)p) * Tp + t) * n + a] = nd > 0 ? sepaihrd_quantile::sorted_quantile(x, nd, probs[p]) : qnan;
         }
     }
+    if (so) {
+        const size_t SW = (size_t)sepaihrd_score::summary_width(so->n_levels);
+        for (int ser = 0; ser < 3; ++ser)
+            for (int a = 0; a <= n_age; ++a)
+                sepaihrd_score::summary_walk(so->cell_scores, observed, nd, T_pos, n_age, so->n_levels, ser, a,
+                                             so->summary + ((size_t)ser * (n + 1) + (size_t)a) * SW);
+        if (so->exact) *so->exact = all_exact;
+    }
     return SEPAIHRD_OK;
 }
 }  // namespace
+
+int hostPosteriorPredictiveScores(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                                  int n_age, std::uint64_t seed, const double* probs, int n_probs, const double* levels, int n_levels,
+                                  double* pred_quantiles, double* pit, double* cell_scores, double* summary, double* draws, int32_t* exact,
+                                  std::string* error) {
+    for (int s = 0; s < S && status && k_used; ++s) {
+        if (status[s] != 0) continue;
+        char msg[256] = "";
+        if (sepaihrd_particle_nb_validate(k_used + (size_t)s * 3, msg, (int)sizeof(msg)) != SEPAIHRD_OK) {
+            if (error) *error = msg;
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    }
+    const ScoreOut so{levels, n_levels, cell_scores, summary, exact};
+    return predictive_from_means(means, status, k_used, observed, S, R, T_pos, n_age, seed, probs, n_probs, pred_quantiles, pit, draws, error, &so);
+}
+
+int hostScoreCell(const double* x, int m, double y, const double* levels, int n_levels, double* scores, double* pit, int32_t* exact,
+                  std::string* error) {
+    if (!x || m < 1 || !scores || n_levels < 0 || n_levels > sepaihrd_score::MAX_LEVELS || (n_levels > 0 && !levels)) {
+        if (error) *error = "score_cell: need x, m >= 1, scores and 0 <= n_levels <= 8 levels";
+        return SEPAIHRD_E_INVALID_ARG;
+    }
+    for (int l = 0; l < n_levels; ++l)
+        if (!(levels[l] > 0.0 && levels[l] < 1.0)) {
+            if (error) *error = "score_cell: levels must lie strictly inside (0, 1)";
+            return SEPAIHRD_E_INVALID_ARG;
+        }
+    std::vector<double> sorted(x, x + m);
+    std::sort(sorted.begin(), sorted.end());
+    const sepaihrd_score::SegmentSums sums = sepaihrd_score::segment_sums(sorted.data(), (size_t)m, y);
+    sepaihrd_score::cell_rule(sorted.data(), (size_t)m, y, sums, levels, n_levels, scores);
+    if (pit) *pit = sepaihrd_score::pit_of(sums, (size_t)m, y);
+    if (exact) *exact = sepaihrd_score::sums_exact((size_t)m, sorted[(size_t)m - 1]) ? 1 : 0;
+    return SEPAIHRD_OK;
+}
 
 int hostPosteriorPredictive(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
                             std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
@@ -161,16 +232,15 @@ std::vector<double> HipPosteriorPredictive::observed() const {
     return out;
 }
 
-PosteriorPredictiveDraws HipPosteriorPredictive::draw(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc,
-                                                      unsigned int random_seed, int replicates, std::uint64_t seed,
-                                                      const std::vector<double>& probs, bool want_means, bool want_draws) {
-    PosteriorPredictiveDraws out;
+std::vector<double> HipPosteriorPredictive::selectedThetas(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc,
+                                                           unsigned int random_seed, int replicates, const std::vector<double>& probs,
+                                                           PosteriorPredictiveDraws& out) const {
     for (double t : time_points_)
         if (t >= 0.0) out.time_points.push_back(t);
     out.n_age = n_;
     out.replicates = replicates;
     out.probs = probs;
-    if (out.time_points.empty() || param_samples.empty()) return out;
+    if (out.time_points.empty() || param_samples.empty()) return {};
     out.selected = HipPosteriorEnsemble::selectSamples(param_samples.size(), num_samples_for_ppc, random_seed);
     const size_t P = pm_.getParameterCount(), S = out.selected.size();
     std::vector<double> thetas(S * P);
@@ -179,6 +249,52 @@ PosteriorPredictiveDraws HipPosteriorPredictive::draw(const std::vector<Eigen::V
         if (static_cast<size_t>(v.size()) != P) throw InvalidParameterException("HipPosteriorPredictive", "sample size mismatch");
         for (size_t i = 0; i < P; ++i) thetas[s * P + i] = v[static_cast<Eigen::Index>(i)];
     }
+    return thetas;
+}
+
+PosteriorPredictiveScores HipPosteriorPredictive::score(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc,
+                                                        unsigned int random_seed, int replicates, std::uint64_t seed,
+                                                        const std::vector<double>& probs, const std::vector<double>& levels,
+                                                        const std::vector<double>* observed_table, bool want_means, bool want_draws) {
+    PosteriorPredictiveScores out;
+    out.levels = levels;
+    const std::vector<double> thetas = selectedThetas(param_samples, num_samples_for_ppc, random_seed, replicates, probs, out);
+    if (thetas.empty()) return out;
+    const size_t S = out.selected.size(), L = levels.size();
+    const size_t cells = static_cast<size_t>(3) * t_pos_ * n_;
+    if (observed_table && observed_table->size() != cells)
+        throw InvalidParameterException("HipPosteriorPredictive", "observed must hold 3 x T_pos x n_age values");
+    sepaihrd_ctx* ctx = objective_->deviceContext();
+    objective_->syncDeviceConstraintMode();
+    out.pred_quantiles.assign(2 * cells * probs.size(), 0.0);
+    out.pit.assign(cells, 0.0);
+    out.cell_scores.assign(cells * (5 + 4 * L), 0.0);
+    out.summary.assign(static_cast<size_t>(3) * (n_ + 1) * (4 + 2 * L), 0.0);
+    if (want_means) out.means.assign(S * cells, 0.0);
+    if (want_draws && replicates > 0) out.draws.assign(S * static_cast<size_t>(replicates) * cells, 0.0);
+    out.status.assign(S, 0);
+    out.k_used.assign(S * 3, 0.0);
+    int32_t nv = 0, exact = 0;
+    // dispersion NULL: the context's own, per sample -- Poisson draws where the objective is not dispersed, as draw() picks
+    const int rc = sepaihrd_ensemble_predictive_scores(
+        ctx, thetas.data(), static_cast<int>(S), replicates, seed, nullptr, observed_table ? observed_table->data() : nullptr, probs.data(),
+        static_cast<int>(probs.size()), levels.data(), static_cast<int>(L), out.pred_quantiles.data(), out.pit.data(), out.cell_scores.data(),
+        out.summary.data(), want_means ? out.means.data() : nullptr, out.draws.empty() ? nullptr : out.draws.data(), out.k_used.data(),
+        out.status.data(), &nv, &exact);
+    if (rc != SEPAIHRD_OK)
+        throw ModelException("HipPosteriorPredictive", std::string("sepaihrd_ensemble_predictive_scores: ") + sepaihrd_last_error(ctx));
+    out.samples_used = nv;
+    out.exact = exact != 0;
+    return out;
+}
+
+PosteriorPredictiveDraws HipPosteriorPredictive::draw(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc,
+                                                      unsigned int random_seed, int replicates, std::uint64_t seed,
+                                                      const std::vector<double>& probs, bool want_means, bool want_draws) {
+    PosteriorPredictiveDraws out;
+    const std::vector<double> thetas = selectedThetas(param_samples, num_samples_for_ppc, random_seed, replicates, probs, out);
+    if (thetas.empty()) return out;
+    const size_t S = out.selected.size();
     sepaihrd_ctx* ctx = objective_->deviceContext();
     objective_->syncDeviceConstraintMode();
     const size_t cells = static_cast<size_t>(3) * t_pos_ * n_;

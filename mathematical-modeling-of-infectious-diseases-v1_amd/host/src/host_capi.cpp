@@ -1530,6 +1530,59 @@ int host_predictive(void* hv, const sepaihrd_problem* pb, int device, const doub
                                      draws, nullptr, nullptr, selected, n_selected, status, samples_used);
 }
 
+// ---- scores of the posterior predictive draws (sepaihrd_ensemble_predictive_scores) ----
+// hostPosteriorPredictiveScores (no device): shapes as sepaihrd_ensemble_predictive_scores; k_used NULL: Poisson draws
+int host_predictive_scores_from_means(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R,
+                                      int T_pos, int n_age, uint64_t seed, const double* probs, int n_probs, const double* levels, int n_levels,
+                                      double* pred_quantiles, double* pit, double* cell_scores, double* summary, double* draws, int32_t* exact,
+                                      char* err, int errlen) {
+    std::string error;
+    const int rc = hostPosteriorPredictiveScores(means, status, k_used, observed, S, R, T_pos, n_age, seed, probs, n_probs, levels, n_levels,
+                                                 pred_quantiles, pit, cell_scores, summary, draws, exact, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
+// hostScoreCell (no device): one unsorted sample x [m] against y; scores [5 + 4 n_levels]
+int host_score_cell(const double* x, int m, double y, const double* levels, int n_levels, double* scores, double* pit, int32_t* exact, char* err,
+                    int errlen) {
+    std::string error;
+    const int rc = hostScoreCell(x, m, y, levels, n_levels, scores, pit, exact, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
+// HipPosteriorPredictive::score over the handle's parameter manager / data, as host_predictive_dispersed drives draw():
+// observed_in [3][T_pos][n] (nullable: the handle's data), cell_scores [3][T_pos][n][5 + 4 L], summary [3][n + 1][4 + 2 L]
+int host_predictive_scores(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int num_for_ppc,
+                           uint32_t ppc_seed, int R, uint64_t seed, const double* probs, int n_probs, const double* levels, int n_levels,
+                           const double* observed_in, double* pred, double* pit, double* cell_scores, double* summary, double* means, double* draws,
+                           double* k_used, int32_t* exact, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
+    auto* h = static_cast<HostHandle*>(hv);
+    return guarded([&] {
+        HipPosteriorPredictive pp = posterior_over<HipPosteriorPredictive>(*h, pb, device);
+        if (h->has_dispersion) pp.objective().setDispersion(h->dispersion);
+        const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
+        std::vector<double> obs;
+        if (observed_in) obs.assign(observed_in, observed_in + pp.observed().size());
+        const PosteriorPredictiveScores d =
+            pp.score(ps, num_for_ppc, ppc_seed, R, seed, std::vector<double>(probs, probs + n_probs), std::vector<double>(levels, levels + n_levels),
+                     observed_in ? &obs : nullptr, means != nullptr, draws != nullptr);
+        std::copy(d.pred_quantiles.begin(), d.pred_quantiles.end(), pred);
+        if (pit) std::copy(d.pit.begin(), d.pit.end(), pit);
+        std::copy(d.cell_scores.begin(), d.cell_scores.end(), cell_scores);
+        std::copy(d.summary.begin(), d.summary.end(), summary);
+        if (means) std::copy(d.means.begin(), d.means.end(), means);
+        if (draws) std::copy(d.draws.begin(), d.draws.end(), draws);
+        if (k_used) std::copy(d.k_used.begin(), d.k_used.end(), k_used);
+        if (exact) *exact = d.exact ? 1 : 0;
+        for (size_t i = 0; i < d.selected.size(); ++i) selected[i] = d.selected[i];
+        *n_selected = static_cast<int32_t>(d.selected.size());
+        if (status) std::copy(d.status.begin(), d.status.end(), status);
+        *samples_used = d.samples_used;
+    });
+}
+
 // ---- stochastic chain-binomial SEPAIHRD ensembles (HipStochasticSEPAIHRD) ----
 // hostStochasticSEPAIHRD (no device): shapes as sepaihrd_ensemble_stochastic; M row-major, M[i n_age + j] = M(i, j)
 int host_stochastic_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,

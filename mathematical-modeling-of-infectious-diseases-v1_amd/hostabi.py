@@ -135,6 +135,11 @@ def load_library() -> C.CDLL:
                                               C.c_uint64, vp, C.c_int] + [vp] * 11
     lib.host_predictive_nb_from_means.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, vp, vp,
                                                   C.c_char_p, C.c_int]
+    lib.host_predictive_scores_from_means.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_int,
+                                                      vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.host_score_cell.argtypes = [vp, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.host_predictive_scores.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int,
+                                           C.c_uint64, vp, C.c_int, vp, C.c_int] + [vp] * 13
     lib.host_gamma_at.restype = C.c_double
     lib.host_gamma_at.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double]
     lib.host_nb_draw_at.restype = C.c_double
@@ -465,6 +470,46 @@ class HostObjective:
                                                   sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used)), "host_predictive: ")
         out = {"pred": pred, "pit": pit, "observed": obs, "selected": sel[:nsel.value].copy(), "status": status[:nsel.value].copy(),
                "samples_used": used.value, "dispersed": bool(dispersed.value), "k_used": k_used[:nsel.value].copy()}
+        if want_means:
+            out["means"] = means
+        if want_draws:
+            out["draws"] = draws
+        return out
+
+    def posterior_predictive_scores(self, samples, num_for_ppc: int, ppc_seed: int, R: int, seed: int, probs, levels, observed=None,
+                                    want_means: bool = False, want_draws: bool = False, device: int = -1) -> dict:
+        """HipPosteriorPredictive::score over this handle's parameter manager and data: posterior_predictive's selection and
+        dispersion rule through sepaihrd_ensemble_predictive_scores.  pred, pit, cell_scores [3][T_pos][n][5 + 4 L], summary
+        [3][n + 1][4 + 2 L], exact, k_used, selected, status, samples_used; means and draws on request.  observed [3][T_pos][n]
+        (None: the handle's data) is the table scored against."""
+        ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        n, L = self.pb.n, lv.size
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        ob = None if observed is None else np.ascontiguousarray(observed, dtype=np.float64)
+        if ob is not None and ob.shape != (3, Tp, n):
+            raise ValueError("observed must be [3][T_pos][n]")
+        cap = max(ps.shape[0], num_for_ppc, 1)
+        S = num_for_ppc if 0 < num_for_ppc < ps.shape[0] else ps.shape[0]
+        pred, pit = np.empty((6, pr.size, Tp, n)), np.empty((3, Tp, n))
+        cell_scores, summary = np.empty((3, Tp, n, 5 + 4 * L)), np.empty((3, n + 1, 4 + 2 * L))
+        means = np.empty((S, 3, Tp, n)) if want_means else None
+        draws = np.empty((S, max(int(R), 0), 3, Tp, n)) if want_draws else None
+        sel, status = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        nsel, used, exact = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        k_used = np.full((cap, 3), np.inf)
+        _check(self.lib.host_predictive_scores(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, lv.ctypes.data, L,
+                                               None if ob is None else ob.ctypes.data, pred.ctypes.data, pit.ctypes.data,
+                                               cell_scores.ctypes.data, summary.ctypes.data, means.ctypes.data if want_means else None,
+                                               draws.ctypes.data if want_draws else None, k_used.ctypes.data, C.byref(exact),
+                                               sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used)), "host_predictive_scores: ")
+        out = {"pred": pred, "pit": pit, "cell_scores": cell_scores, "summary": summary, "exact": bool(exact.value),
+               "selected": sel[:nsel.value].copy(), "status": status[:nsel.value].copy(), "samples_used": used.value,
+               "k_used": k_used[:nsel.value].copy()}
         if want_means:
             out["means"] = means
         if want_draws:
@@ -1146,6 +1191,80 @@ def predictive_from_means(means, status, observed, R: int, seed: int, probs, wan
         out["pit"] = pit
     if draws is not None:
         out["draws"] = draws
+    return out
+
+
+# ---- scores of the posterior predictive draws: the CPU twin of sepaihrd_ensemble_predictive_scores ----
+def predictive_scores_validate(S: int, R: int, T_pos: int, n_age: int, probs, levels) -> None:
+    """sepaihrd_predictive_scores_validate (host only): ValueError with its message for arguments the scored call refuses"""
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    err = C.create_string_buffer(512)
+    if hipabi.load_library().sepaihrd_predictive_scores_validate(int(S), int(R), int(T_pos), int(n_age), pr.ctypes.data, pr.size, lv.ctypes.data,
+                                                                 lv.size, err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+
+
+def predictive_scores_from_means(means, status, observed, R: int, seed: int, probs, levels, k_used=None, want_draws: bool = True) -> dict:
+    """The twin of HipObjective.ensemble_predictive_scores after the integration: from means [S][3][T_pos][n], status [S], k_used
+    [S][3] (None: Poisson draws) and observed [3][T_pos][n] the same draws, pred, pit, cell_scores, summary and exact -- std::sort
+    and the text the kernels compile (csrc/sepaihrd_predictive_score.inc): bit for bit where exact is True.  The result carries
+    the named views of hipabi.score_views too."""
+    m = np.ascontiguousarray(means, dtype=np.float64)
+    if m.ndim != 4 or m.shape[1] != 3:
+        raise ValueError("means must be [S][3][T_pos][n]")
+    S, _, Tp, n = m.shape
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    if st.shape != (S,):
+        raise ValueError("status must have one entry per sample")
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    predictive_scores_validate(S, R, Tp, n, pr, lv)
+    R, L = int(R), lv.size
+    if observed is None:
+        raise ValueError("observed must be [3][T_pos][n]")
+    ob = np.ascontiguousarray(observed, dtype=np.float64)
+    if ob.shape != (3, Tp, n):
+        raise ValueError("observed must be [3][T_pos][n]: (3, %d, %d), not %s" % (Tp, n, ob.shape))
+    ku = None
+    if k_used is not None:
+        ku = np.ascontiguousarray(k_used, dtype=np.float64)
+        if ku.shape != (S, 3):
+            raise ValueError("k_used must be [S][3]")
+    pred, pit = np.empty((6, pr.size, Tp, n)), np.empty((3, Tp, n))
+    cell_scores, summary = np.empty((3, Tp, n, 5 + 4 * L)), np.empty((3, n + 1, 4 + 2 * L))
+    draws = np.empty((S, R, 3, Tp, n)) if want_draws else None
+    exact = C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = load_library().host_predictive_scores_from_means(
+        m.ctypes.data, st.ctypes.data, None if ku is None else ku.ctypes.data, ob.ctypes.data, S, R, Tp, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        pr.ctypes.data, pr.size, lv.ctypes.data, L, pred.ctypes.data, pit.ctypes.data, cell_scores.ctypes.data, summary.ctypes.data,
+        None if draws is None else draws.ctypes.data, C.byref(exact), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    out = {"pred": pred, "pit": pit, "cell_scores": cell_scores, "summary": summary, "exact": bool(exact.value),
+           "n_valid": int(np.sum(st == 0)), "levels": lv, "observed": ob}
+    if draws is not None:
+        out["draws"] = draws
+    out.update(hipabi.score_views(cell_scores, summary, ob, lv))
+    return out
+
+
+def score_cell(x, y: float, levels) -> dict:
+    """One unsorted sample x against one observation y by the cell rule of csrc/sepaihrd_predictive_score.inc: scores [5 + 4 L]
+    (mean, variance, median, crps, wis, then lower, upper, interval_score, covered per level) with their named entries, pit and
+    exact (every sum stayed below 2^53)."""
+    xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    scores = np.empty(5 + 4 * lv.size)
+    pit, exact = C.c_double(0.0), C.c_int32(0)
+    err = C.create_string_buffer(512)
+    if load_library().host_score_cell(xs.ctypes.data, xs.size, float(y), lv.ctypes.data, lv.size, scores.ctypes.data, C.byref(pit),
+                                      C.byref(exact), err, len(err)) != 0:
+        raise ValueError(err.value.decode())
+    out = {"scores": scores, "pit": pit.value, "exact": bool(exact.value)}
+    out.update({name: scores[f] for f, name in enumerate(("mean", "variance", "median", "crps", "wis"))})
+    out.update({name: scores[5 + f::4] for f, name in enumerate(("lower", "upper", "interval_score", "covered"))})
     return out
 
 

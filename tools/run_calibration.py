@@ -58,8 +58,12 @@ def main():
                          "run_summary.json")
     ap.add_argument("--predictive-replicates", type=int, default=0,
                     help="also the replicated-data check (posterior_predictive/<series>_predictive_*.csv, pit_*.csv, "
-                         "predictive_coverage.csv): this many replicates per pooled sample, drawn under the problem's observation "
-                         "model -- negative-binomial where the problem carries a dispersion (fixed or calibrated), else Poisson")
+                         "predictive_coverage.csv, predictive_scores.csv): this many replicates per pooled sample, drawn under the "
+                         "problem's observation model -- negative-binomial where the problem carries a dispersion (fixed or "
+                         "calibrated), else Poisson -- and scored against the observations on the device")
+    ap.add_argument("--predictive-levels", default="0.5,0.9,0.95",
+                    help="central coverage levels of predictive_scores.csv (interval score and coverage per level, and the WIS over "
+                         "them): up to 8 values inside (0, 1), comma-separated")
     args = ap.parse_args()
 
     mm = mmid_amd_loader.load()
@@ -105,10 +109,10 @@ def main():
     t_ens = time.perf_counter() - t0
     predictive = None
     if args.predictive_replicates > 0:
-        # a fixed dispersion is +inf or finite, a calibrated one reads NaN: anything but three +inf is a dispersed problem
+        # the context's dispersion, per sample: Poisson draws where the problem carries none (three +inf; a calibrated one reads NaN)
         dispersed = not np.all(np.isposinf(hip.get_dispersion()))
-        predictive = hip.ensemble_predictive(pooled, args.predictive_replicates, args.seed + 2, PROBS,
-                                             dispersion=hip.CONTEXT_DISPERSION if dispersed else None)
+        levels = [float(c) for c in args.predictive_levels.split(",") if c.strip()]
+        predictive = hip.ensemble_predictive_scores(pooled, args.predictive_replicates, args.seed + 2, PROBS, levels)
     times = np.asarray(pb.times)
     pos = times[times >= 0]
     # the reference's post-calibration output tree (file names, headers and number formats of AnalysisWriter.cpp; what
@@ -151,7 +155,7 @@ def main():
                "best_value": cal["best_value"], "algorithm": args.algorithm, "chains": args.chains, "mcmc_iterations": args.mcmc_iterations,
                "acceptance_rate_mean": float(cal["accept_trace"].mean()), "calibration_seconds": t_cal,
                "proposals_per_s": evals / t_cal, "ensemble_samples": int(len(pooled)), "ensemble_valid": int(ens["n_valid"]),
-               "ensemble_seconds": t_ens, "predictive_noise": None if predictive is None else ("negative_binomial" if "k_used" in predictive else "poisson"),
+               "ensemble_seconds": t_ens, "predictive_noise": None if predictive is None else ("negative_binomial" if dispersed else "poisson"),
                "median_R0": float(np.nanmedian(ens["metrics"][:, 0])), "out": args.out}
     if diag is not None:
         summary.update(max_r_hat=float(np.nanmax(diag[:, 6])), min_ess_bulk=float(np.nanmin(diag[:, 4])),
