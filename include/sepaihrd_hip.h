@@ -849,7 +849,8 @@ int sepaihrd_ensemble_predictive(sepaihrd_ctx *ctx, const double *theta, int S, 
 int sepaihrd_predictive_validate(int S, int R, int T_pos, int n_age, const double *probs, int n_probs, char *err, int errlen);
 /* Device time of the context's last sepaihrd_ensemble_predictive, sepaihrd_ensemble_predictive_nb or
  * sepaihrd_ensemble_predictive_scores call in milliseconds, ms[3]: integrator; draws and mid-PIT counts (the scored call has no PIT
- * pass); segment sorts and quantiles (and, in the scored call, the scores). */
+ * pass); segment sorts and quantiles (and, in the scored call, the scores).  sepaihrd_ensemble_predictive_targets reports the
+ * same three phases over its targets. */
 int sepaihrd_predictive_timing(const sepaihrd_ctx *ctx, double *ms);
 /* Probe of the device's Poisson sampler: out[i] ~ Poisson(lambda[i]), the variate at (seed, c0 = i, c1 = 0, c2 = 0).
  * lambda [count], out [count], host memory; lambda <= 0 gives 0, NaN and +infinity give NaN. */
@@ -921,6 +922,48 @@ int sepaihrd_ensemble_predictive_scores(sepaihrd_ctx *ctx, const double *theta, 
                                         int32_t *status, int32_t *n_valid, int32_t *exact);
 int sepaihrd_predictive_scores_validate(int S, int R, int T_pos, int n_age, const double *probs, int n_probs, const double *levels,
                                         int n_levels, char *err, int errlen);
+
+/* ---- the same scores on window and age-group totals (additive; SEPAIHRD_ABI_VERSION stays) -----------------------------------
+ * Forecasts of surveillance counts are judged on weekly totals, often summed over ages, and a weekday reporting artefact the model
+ * has no term for spoils every daily interval of a fit whose weekly totals are right.  The distribution of a sum is no function of
+ * the per-cell quantiles: it needs the joint draws.  sepaihrd_ensemble_predictive_targets draws the replicates of
+ * sepaihrd_ensemble_predictive_scores -- same preconditions, failure codes, stream coordinates and failed-sample rule, and means,
+ * draws (the daily table), k_used, status, n_valid that call's for the same inputs, bit for bit -- and sums them on the device into
+ * targets (the rule: csrc/sepaihrd_predictive_targets.inc): an age group x a window of output rows, plus the running sums of those
+ * window totals.  Every target segment is sorted once and gives quantiles, mid-PIT, scores and summaries for six series:
+ * k = 0, 1, 2 the window totals of H, ICU, D, k = 3, 4, 5 their running sums over the windows.
+ *   age_group        [n_age]: -1 leaves the age out, otherwise a group id; the ids in use must be exactly 0 .. G - 1, 1 <= G <= n_age
+ *   window, origin   w >= 1 and o >= 0 in output rows with t >= 0: W = (T_pos - o) / w windows (integer division; W >= 1), window v
+ *                    covers rows o + v w .. o + (v + 1) w - 1; rows before o and the incomplete tail belong to no target.  On a
+ *                    daily grid w = 7 is a week
+ *   observed         as in the scored call.  The observed target is the same sum of the table (rows ascending, ages ascending
+ *                    within a row, from 0.0; the running sum adds the window totals in order).  A window target is usable when
+ *                    every daily observation it sums is (finite and >= 0), a cumulative one when every window u <= v of its series
+ *                    and group is; an unusable observed target is NaN
+ *   target_quantiles [6][n_probs][W][G]: the quantile rule of pred_quantiles over the m = n_valid R values of the target
+ *   pit              [6][W][G] or NULL;  target_obs [6][W][G] or NULL: the observed targets
+ *   target_scores    [6][W][G][5 + 4 L], summary [6][G + 1][4 + 2 L] (entry G pools the groups): the fields of cell_scores and
+ *                    summary above, a target in the place of a cell; summary order windows ascending, groups ascending within one
+ *   target_draws     [S][R][3][W][G] or NULL: the window totals of the three daily series of every draw, NaN for failed samples
+ *   exact            NULL or [1]: the scored call's criterion, m x_max max(m, x_max) < 2^53, over every one of the 6 W G segments;
+ *                    the host twin (hostPosteriorPredictiveTargets) then gives the same bits and reports the same flag
+ * Memory: 6 W G segments of S R doubles (padded as the other calls') plus the optional outputs; the scored call's 6 T_pos n_age
+ * table is not allocated.  SEPAIHRD_E_INVALID_ARG with a message that names the first wrong argument: the scored call's refusals,
+ * then age_group NULL, an id < -1 or >= n_age, a gap in the ids, no age in any group, window < 1, origin < 0, W < 1.
+ * sepaihrd_predictive_targets_validate is the same check without a context (host only; W and G out, nullable).
+ * sepaihrd_predictive_timing reports this call when it was the last: integrator; draws and their sums into the targets; sorts,
+ * quantiles and scores. */
+int sepaihrd_ensemble_predictive_targets(sepaihrd_ctx *ctx, const double *theta, int S, int R, uint64_t seed,
+                                         const double *dispersion /* [3] or NULL */, const double *observed /* [3][T_pos][n_age] or NULL */,
+                                         const int32_t *age_group /* [n_age] */, int window, int origin, const double *probs, int n_probs,
+                                         const double *levels, int n_levels, double *target_quantiles /* [6][n_probs][W][G] */,
+                                         double *pit /* [6][W][G] or NULL */, double *target_scores /* [6][W][G][5 + 4 L] */,
+                                         double *summary /* [6][G + 1][4 + 2 L] */, double *target_obs /* [6][W][G] or NULL */,
+                                         double *target_draws /* [S][R][3][W][G] or NULL */, double *means, double *draws, double *k_used,
+                                         int32_t *status, int32_t *n_valid, int32_t *exact);
+int sepaihrd_predictive_targets_validate(int S, int R, int T_pos, int n_age, const int32_t *age_group, int window, int origin,
+                                         const double *probs, int n_probs, const double *levels, int n_levels, int *W, int *G, char *err,
+                                         int errlen);
 
 /* ---- stochastic chain-binomial SEPAIHRD ensembles over posterior samples (additive; SEPAIHRD_ABI_VERSION stays) -------------
  * Process noise for the age-structured model: the ensemble calls above give parameter uncertainty and observation noise, this

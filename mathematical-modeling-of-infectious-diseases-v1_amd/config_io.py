@@ -619,6 +619,59 @@ def write_predictive_scores(path: str, summary, levels) -> str:
     return path
 
 
+def parse_age_groups(spec: str, n_age: int) -> List[int]:
+    """age_group [n_age] of sepaihrd_ensemble_predictive_targets from ``all`` (one group of every age), ``each`` (a group per
+    age) or lists of ages, ``;`` between groups and ``,`` within one (``0,1;2,3``: two groups; an age in no list is left out)."""
+    spec = spec.strip()
+    if spec == "all":
+        return [0] * n_age
+    if spec == "each":
+        return list(range(n_age))
+    groups = [-1] * n_age
+    for g, part in enumerate(p for p in spec.split(";") if p.strip()):
+        for tok in part.split(","):
+            a = int(tok)
+            if not 0 <= a < n_age:
+                raise ValueError("age %d of group %d lies outside 0..%d" % (a, g, n_age - 1))
+            if groups[a] != -1:
+                raise ValueError("age %d is named twice" % a)
+            groups[a] = g
+    return groups
+
+
+def write_predictive_target_scores(path: str, targets: dict) -> str:
+    """predictive_target_scores.csv from a HipObjective.ensemble_predictive_targets result (keys target_scores [6][W][G][5 + 4 L],
+    target_obs [6][W][G], summary [6][G + 1][4 + 2 L], window_first_row [W], levels [L]):
+    ``series,window_first_row,group,n_observations,crps,wis,abs_err_median,coverage_<c>,interval_score_<c>...``.  Per series (the
+    six of PPC_SERIES: window totals, then their running sums) one row per window and group -- n_observations 1 where the observed
+    target is usable, else 0 and nan scores -- then the averages over the windows with window_first_row ``all``: one row per group
+    and one with group ``all`` for the pooled entry.  17 significant digits."""
+    ts, sm = np.asarray(targets["target_scores"], dtype=np.float64), np.asarray(targets["summary"], dtype=np.float64)
+    tobs = np.asarray(targets["target_obs"], dtype=np.float64)
+    levels = [float(c) for c in np.asarray(targets["levels"], dtype=np.float64).ravel()]
+    first = [int(r) for r in np.asarray(targets["window_first_row"]).ravel()]
+    L = len(levels)
+    if ts.ndim != 4 or ts.shape[0] != 6 or ts.shape[3] != 5 + 4 * L or sm.shape != (6, ts.shape[2] + 1, 4 + 2 * L) or len(first) != ts.shape[1]:
+        raise ValueError("targets must hold target_scores [6][W][G][5 + 4 L], summary [6][G + 1][4 + 2 L] and window_first_row [W]")
+    _, W, G, _ = ts.shape
+    with open(path, "w") as fh:
+        fh.write("series,window_first_row,group,n_observations,crps,wis,abs_err_median" +
+                 "".join(f",coverage_{c:g},interval_score_{c:g}" for c in levels) + "\n")
+        for k, name in enumerate(PPC_SERIES):
+            for v in range(W):
+                for g in range(G):
+                    y, cell = tobs[k, v, g], ts[k, v, g]
+                    usable = bool(np.isfinite(y) and y >= 0.0 and np.isfinite(cell[3]))
+                    vals = [cell[3], cell[4], abs(y - cell[2]) if usable else np.nan]
+                    for lv in range(L):
+                        vals += [cell[5 + 4 * lv + 3], cell[5 + 4 * lv + 2]]
+                    fh.write("%s,%d,%d,%d" % (name, first[v], g, int(usable)) + "".join(",%.17g" % x for x in vals) + "\n")
+            for g in range(G + 1):
+                row = sm[k, g]
+                fh.write("%s,all,%s,%d" % (name, g if g < G else "all", int(row[0])) + "".join(",%.17g" % x for x in row[1:]) + "\n")
+    return path
+
+
 def write_aggregated_trajectory(path: str, times, quantiles: np.ndarray) -> None:
     """rt_trajectories/Rt_aggregated_with_uncertainty.csv, seroprevalence/seroprevalence_trajectory.csv:
     ``time,median,q025,q975,q05,q95`` fixed 6 digits.  quantiles: [5 PPC_PROBS][T]."""

@@ -24,4 +24,12 @@ __device__ __forceinline__ void bitonic_sort_pow2(double* seg, const int Np) {
     }
 }
 
+// Np (a power of two) doubles of src sorted ascending into seg (LDS) by the whole workgroup
+__device__ __forceinline__ void lds_bitonic_sort(double* seg, const double* src, const int Np) {
+    const int tid = threadIdx.x, BS = blockDim.x;
+    for (int i = tid; i < Np; i += BS) seg[i] = src[i];
+    __syncthreads();
+    bitonic_sort_pow2(seg, Np);
+}
+
 }  // namespace sepaihrd

@@ -22,6 +22,8 @@
 #include "sepaihrd_mh_backend.h"
 #include "sepaihrd_nb_objective_device.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_predictive_targets.inc"
+#include "sepaihrd_predictive_targets_device.h"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_particle_device.h"
 #include "sepaihrd_particle_nb_host.h"
@@ -977,10 +979,20 @@ struct ScoreRequest {
     double *cell_scores, *summary;
     int32_t* exact;
 };
+// tr (sepaihrd_ensemble_predictive_targets; null: the daily cells): the draws are summed into the 6 W G target segments of
+// csrc/sepaihrd_predictive_targets.inc and those are sorted and scored; the 6 T_pos n_age table is not allocated.  Its score
+// request's cell_scores and summary are the target outputs, and pred_quantiles and pit of the call are the targets' too.
+struct TargetRequest {
+    ScoreRequest score;
+    const int32_t* age_group;  // [n_age] host
+    int window, origin, W, G;
+    double *target_obs, *target_draws;
+};
 static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const NbDispersion* nb, const double* probs,
                            int n_probs, double* pred_quantiles, double* pit, double* means, double* draws, double* k_used, int32_t* status,
-                           int32_t* n_valid, const ScoreRequest* sr = nullptr) {
-    const char* const who = sr ? "ensemble_predictive_scores" : "ensemble_predictive";
+                           int32_t* n_valid, const ScoreRequest* sr = nullptr, const TargetRequest* tr = nullptr) {
+    if (tr) sr = &tr->score;
+    const char* const who = tr ? "ensemble_predictive_targets" : sr ? "ensemble_predictive_scores" : "ensemble_predictive";
     int rc = ensemble_preflight(ctx, who, S > 0 && theta && probs && pred_quantiles, "need S > 0, theta, probs (1..1024) and pred_quantiles",
                                 CHECK_PENDING | CHECK_F64 | CHECK_TP, probs, n_probs);
     if (rc != SEPAIHRD_OK) return rc;
@@ -990,7 +1002,7 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     rc = validated(ctx, sr ? sepaihrd_predictive_scores_validate(S, R, Tp, dp.n, probs, n_probs, sr->levels, sr->n_levels, msg, (int)sizeof(msg))
                               : sepaihrd_predictive_validate(S, R, Tp, dp.n, probs, n_probs, msg, (int)sizeof(msg)), msg);
     if (rc != SEPAIHRD_OK) return rc;
-    if (sr && !sr->cell_scores) return refuse(ctx, who, "cell_scores must not be NULL", SEPAIHRD_E_INVALID_ARG);
+    if (sr && !sr->cell_scores) return refuse(ctx, who, tr ? "target_scores must not be NULL" : "cell_scores must not be NULL", SEPAIHRD_E_INVALID_ARG);
     if (sr && !sr->summary) return refuse(ctx, who, "summary must not be NULL", SEPAIHRD_E_INVALID_ARG);
     HIP_TRY(hipSetDevice(ctx->device), ctx, return SEPAIHRD_E_HIP);
     // sizes
@@ -1001,17 +1013,22 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     const size_t cpw = (size_t)(WAVE / dp.lpc);
     const size_t chains = ((size_t)S + cpw - 1) / cpw * cpw;
     const size_t cells = (size_t)3 * Tp * dp.n;
-    const size_t n_q = (size_t)6 * n_probs * Tp * dp.n;
-    const size_t n_vals = 2 * cells * N_pad;
+    // the sorted and scored cells: the daily ones and their running sums, or the targets (3 W G window totals and their running sums)
+    const size_t seg_cells = tr ? (size_t)3 * tr->W * tr->G : cells;
+    const size_t n_q = 2 * seg_cells * (size_t)n_probs;
+    const size_t n_vals = 2 * seg_cells * N_pad;
     const size_t n_scratch = sort_scratch_doubles(plan, n_vals);
     const size_t n_means = means ? (size_t)S * cells : 0, n_draws = draws ? N * cells : 0;
     const size_t n_k = nb ? (size_t)S * 3 : 0;
     const size_t L = sr ? (size_t)sr->n_levels : 0;
-    const size_t n_cs = sr ? cells * (size_t)(5 + 4 * L) : 0, n_sum = sr ? (size_t)3 * (dp.n + 1) * (4 + 2 * L) : 0, n_obs = sr ? cells : 0;
+    const size_t n_cs = sr ? (tr ? 2 * seg_cells : cells) * (size_t)(5 + 4 * L) : 0;
+    const size_t n_sum = tr ? (size_t)6 * (tr->G + 1) * (4 + 2 * L) : sr ? (size_t)3 * (dp.n + 1) * (4 + 2 * L) : 0, n_obs = sr ? cells : 0;
+    const size_t n_pit = tr ? 2 * seg_cells : cells, n_tobs = tr ? 2 * seg_cells : 0, n_tdraws = tr && tr->target_draws ? N * seg_cells : 0;
+    const size_t n_ages = tr ? (size_t)dp.n : 0;
     // the rule of sepaihrd_scenario_ensemble: the buffers below plus the likelihood workspace must fit the device's memory
     // (the segment table dominates: 6 T_pos n_age segments of S R doubles)
-    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + cells + n_means + n_draws + n_k + (size_t)n_probs +
-                                               n_cs + n_sum + n_obs + L + 1) +
+    const size_t need_bytes = sizeof(double) * ((size_t)S * ctx->P + (size_t)S + n_vals + n_scratch + n_q + n_pit + n_means + n_draws + n_k + (size_t)n_probs +
+                                               n_cs + n_sum + n_obs + L + 1 + n_tobs + n_tdraws + n_ages) +
                               sizeof(double) * (workspace_cum_doubles(dp, chains) + workspace_rows_doubles(dp, chains)) +
                               sizeof(int32_t) * (chains + 2);
     rc = require_device_memory(ctx, need_bytes, "ensemble_predictive: the segment table of S x R = " + std::to_string(N) + " draws needs",
@@ -1022,12 +1039,14 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     if (rc != SEPAIHRD_OK) return rc;
     CallScratch sc(4);
     double *d_theta = nullptr, *d_ll = nullptr, *d_vals = nullptr, *d_scratch = nullptr, *d_probs = nullptr, *d_q = nullptr, *d_pit = nullptr,
-           *d_means = nullptr, *d_draws = nullptr, *d_k = nullptr, *d_cs = nullptr, *d_sum = nullptr, *d_obs = nullptr, *d_levels = nullptr;
-    int32_t *d_counts = nullptr, *d_exact = nullptr;
+           *d_means = nullptr, *d_draws = nullptr, *d_k = nullptr, *d_cs = nullptr, *d_sum = nullptr, *d_obs = nullptr, *d_levels = nullptr,
+           *d_tobs = nullptr, *d_tdraws = nullptr;
+    int32_t *d_counts = nullptr, *d_exact = nullptr, *d_group = nullptr, *d_launch = nullptr;
     if (!sc.alloc(&d_theta, (size_t)S * ctx->P) || !sc.alloc(&d_ll, (size_t)S) || !sc.alloc(&d_vals, n_vals) ||
-        !sc.alloc(&d_scratch, n_scratch) || !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_pit, cells) ||
+        !sc.alloc(&d_scratch, n_scratch) || !sc.alloc(&d_probs, (size_t)n_probs) || !sc.alloc(&d_q, n_q) || !sc.alloc(&d_pit, n_pit) ||
         !sc.alloc(&d_means, n_means) || !sc.alloc(&d_draws, n_draws) || !sc.alloc(&d_counts, 2) || !sc.alloc(&d_k, n_k) ||
-        (sr && (!sc.alloc(&d_cs, n_cs) || !sc.alloc(&d_sum, n_sum) || !sc.alloc(&d_obs, n_obs) || !sc.alloc(&d_levels, L) || !sc.alloc(&d_exact, 1))))
+        (sr && (!sc.alloc(&d_cs, n_cs) || !sc.alloc(&d_sum, n_sum) || !sc.alloc(&d_obs, n_obs) || !sc.alloc(&d_levels, L) || !sc.alloc(&d_exact, 1))) ||
+        (tr && (!sc.alloc(&d_tobs, n_tobs) || !sc.alloc(&d_tdraws, n_tdraws) || !sc.alloc(&d_group, n_ages) || !sc.alloc(&d_launch, n_ages))))
         return refuse(ctx, who, "device allocation failed", SEPAIHRD_E_HIP);
     for (Event& e : sc.ev) HIP_TRY(hipEventCreate(&e), ctx, return SEPAIHRD_E_HIP);
     // uploads
@@ -1038,6 +1057,14 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
         HIP_TRY(hipMemcpy(d_exact, &one, sizeof(one), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
         if (L > 0) HIP_TRY(hipMemcpy(d_levels, sr->levels, L * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
         if (sr->observed) HIP_TRY(hipMemcpy(d_obs, sr->observed, n_obs * sizeof(double), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+    }
+    // the ages the target draw kernel launches: every age where the daily tables are wanted, else those of a group
+    std::vector<int32_t> launch_age;
+    if (tr) {
+        for (int a = 0; a < dp.n; ++a)
+            if (means || draws || tr->age_group[a] >= 0) launch_age.push_back(a);
+        HIP_TRY(hipMemcpy(d_group, tr->age_group, n_ages * sizeof(int32_t), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
+        HIP_TRY(hipMemcpy(d_launch, launch_age.data(), launch_age.size() * sizeof(int32_t), hipMemcpyHostToDevice), ctx, return SEPAIHRD_E_HIP);
     }
     // launches
     EvalOutputs out{d_ll, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->ws_cum, ctx->ws_rows, ctx->ws_status, nullptr, 1};
@@ -1056,10 +1083,26 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     a.n_probs = n_probs; a.probs = d_probs; a.q_out = d_q; a.pit_out = pit && !sr ? d_pit : nullptr; a.counts = d_counts;
     a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
-    const int drc = nb ? launch_predictive_draws_nb(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr) : launch_predictive_draws(a, nullptr);
+    PredictiveTargetArgs ta{};
+    int drc;
+    if (tr) {
+        a.vals = nullptr; a.q_out = nullptr; a.pit_out = nullptr;
+        ta.W = tr->W; ta.G = tr->G; ta.window = tr->window; ta.origin = tr->origin;
+        ta.n_launch = (int)launch_age.size(); ta.launch_age = d_launch; ta.age_group = d_group;
+        ta.tvals = d_vals; ta.q_out = d_q; ta.obs_daily = sr->observed ? d_obs : nullptr; ta.target_obs = d_tobs;
+        ta.levels = d_levels; ta.n_levels = sr->n_levels; ta.target_scores = d_cs; ta.summary = d_sum; ta.pit_out = pit ? d_pit : nullptr;
+        ta.target_draws = tr->target_draws ? d_tdraws : nullptr; ta.exact = d_exact;
+        drc = launch_predictive_nb_k(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr);
+        if (drc == 0) drc = launch_predictive_counts(a, nullptr);
+        if (drc == 0) drc = launch_predictive_target_draws(a, ta, d_k, nullptr);
+    } else {
+        drc = nb ? launch_predictive_draws_nb(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr) : launch_predictive_draws(a, nullptr);
+    }
     if (drc != 0) return refuse(ctx, who, "draw kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
-    if (sr) {
+    if (tr) {
+        if (launch_predictive_target_scores(a, ta, nullptr) != 0) return refuse(ctx, who, "score launch failed", SEPAIHRD_E_HIP);
+    } else if (sr) {
         PredictiveScoreArgs sa{};
         sa.obs = d_obs; sa.obs_from_grid = sr->observed == nullptr;
         sa.levels = d_levels; sa.n_levels = sr->n_levels;
@@ -1074,7 +1117,7 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     // fetches
     ResultFetch res;
     res.fetch(pred_quantiles, d_q, n_q * sizeof(double));
-    res.fetch(pit, d_pit, cells * sizeof(double));
+    res.fetch(pit, d_pit, n_pit * sizeof(double));
     res.fetch(means, d_means, n_means * sizeof(double));
     res.fetch(draws, d_draws, n_draws * sizeof(double));
     res.fetch(k_used, d_k, n_k * sizeof(double));
@@ -1084,6 +1127,10 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
         res.fetch(sr->cell_scores, d_cs, n_cs * sizeof(double));
         res.fetch(sr->summary, d_sum, n_sum * sizeof(double));
         res.fetch(sr->exact, d_exact, sizeof(int32_t));
+    }
+    if (tr) {
+        res.fetch(tr->target_obs, d_tobs, n_tobs * sizeof(double));
+        res.fetch(tr->target_draws, d_tdraws, n_tdraws * sizeof(double));
     }
     if (!res.ok()) return refuse(ctx, who, "copy of the results failed", SEPAIHRD_E_HIP);
     return SEPAIHRD_OK;
@@ -1135,6 +1182,58 @@ int sepaihrd_ensemble_predictive_scores(sepaihrd_ctx* ctx, const double* theta, 
     }
     const ScoreRequest sr{observed, levels, n_levels, cell_scores, summary, exact};
     return predictive_call(ctx, theta, S, R, seed, &nb, probs, n_probs, pred_quantiles, pit, means, draws, k_used, status, n_valid, &sr);
+}
+
+int sepaihrd_predictive_targets_validate(int S, int R, int T_pos, int n_age, const int32_t* age_group, int window, int origin, const double* probs,
+                                         int n_probs, const double* levels, int n_levels, int* W, int* G, char* err, int errlen) {
+    const int rc = sepaihrd_predictive_scores_validate(S, R, T_pos, n_age, probs, n_probs, levels, n_levels, err, errlen);
+    if (rc != SEPAIHRD_OK) return rc;
+    auto refuse = [&](const std::string& msg) { set_err(err, errlen, "ensemble_predictive_targets: " + msg); return SEPAIHRD_E_INVALID_ARG; };
+    if (!age_group) return refuse("age_group must not be NULL");
+    int where = 0;
+    const int groups = sepaihrd_targets::group_count(age_group, n_age, &where);
+    if (groups == -1)
+        return refuse("age_group[" + std::to_string(where) + "] = " + std::to_string(age_group[where]) + " must be -1 or a group id in 0.." +
+                      std::to_string(n_age - 1));
+    if (groups == -2) return refuse("age_group puts no age in any group");
+    if (groups == -3) return refuse("age_group leaves a gap: no age has group id " + std::to_string(where) + " though a larger id is in use");
+    if (window < 1) return refuse("window must be >= 1 output row");
+    if (origin < 0) return refuse("origin must be >= 0");
+    const int windows = sepaihrd_targets::window_count(T_pos, window, origin);
+    if (windows < 1)
+        return refuse("origin = " + std::to_string(origin) + " and window = " + std::to_string(window) + " leave no whole window in T_pos = " +
+                      std::to_string(T_pos) + " rows (W < 1)");
+    if ((uint64_t)6 * windows * groups >= ((uint64_t)1 << 31)) return refuse("6 W G target segments must stay below 2^31");
+    if (W) *W = windows;
+    if (G) *G = groups;
+    return SEPAIHRD_OK;
+}
+
+int sepaihrd_ensemble_predictive_targets(sepaihrd_ctx* ctx, const double* theta, int S, int R, uint64_t seed, const double* dispersion,
+                                         const double* observed, const int32_t* age_group, int window, int origin, const double* probs, int n_probs,
+                                         const double* levels, int n_levels, double* target_quantiles, double* pit, double* target_scores,
+                                         double* summary, double* target_obs, double* target_draws, double* means, double* draws, double* k_used,
+                                         int32_t* status, int32_t* n_valid, int32_t* exact) {
+    if (!ctx) return SEPAIHRD_E_INVALID_ARG;
+    NbDispersion nb = ctx->disp;  // NULL: the context's, as in sepaihrd_ensemble_predictive_scores
+    char msg[256] = "";
+    if (dispersion) {
+        const int rc = validated(ctx, sepaihrd_particle_nb_validate(dispersion, msg, (int)sizeof(msg)), msg);
+        if (rc != SEPAIHRD_OK) return rc;
+        for (int s = 0; s < 3; ++s) { nb.src[s] = -1; nb.fixed[s] = dispersion[s]; }
+    }
+    TargetRequest tr{{observed, levels, n_levels, target_scores, summary, exact}, age_group, window, origin, 0, 0, target_obs, target_draws};
+    // the grouping and the windows, once the scored call's own rules hold (those keep their messages in predictive_call)
+    const int Tp = ctx->dp.T - ctx->dp.runup_offset;
+    if (S > 0 && theta && probs && target_quantiles &&
+        sepaihrd_predictive_scores_validate(S, R, Tp, ctx->dp.n, probs, n_probs, levels, n_levels, nullptr, 0) == SEPAIHRD_OK) {
+        const int rc = validated(ctx, sepaihrd_predictive_targets_validate(S, R, Tp, ctx->dp.n, age_group, window, origin, probs, n_probs, levels,
+                                                                           n_levels, &tr.W, &tr.G, msg, (int)sizeof(msg)), msg);
+        if (rc != SEPAIHRD_OK) return rc;
+    } else {
+        tr.W = tr.G = 1;  // predictive_call refuses before either is read
+    }
+    return predictive_call(ctx, theta, S, R, seed, &nb, probs, n_probs, target_quantiles, pit, means, draws, k_used, status, n_valid, nullptr, &tr);
 }
 
 int sepaihrd_predictive_timing(const sepaihrd_ctx* ctx, double* ms) {

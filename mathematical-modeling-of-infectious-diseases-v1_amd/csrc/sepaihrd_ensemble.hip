@@ -40,6 +40,7 @@
 #include "sepaihrd_host_util.h"
 #include "sepaihrd_predictive_device.h"
 #include "sepaihrd_predictive_score.inc"
+#include "sepaihrd_predictive_targets_device.h"
 #include "sepaihrd_quantile.inc"
 #include "sepaihrd_segments.h"
 #include "sepaihrd_sir_device.h"
@@ -310,13 +311,7 @@ __global__ __launch_bounds__(WAVE) void ensemble_metrics_kernel(const EnsembleAr
 // each.  A pick is a functor passed to the kernels by value, carrying its caller's argument struct: picks() numbers per
 // segment, operator()(sid, p, sorted segment) stores number p of segment sid, SORTED_BLOCK is the workgroup of the sorted kernel.
 
-// Np (a power of two) doubles of src sorted ascending into seg (LDS) by the whole workgroup
-__device__ __forceinline__ void lds_bitonic_sort(double* seg, const double* src, const int Np) {
-    const int tid = threadIdx.x, BS = blockDim.x;
-    for (int i = tid; i < Np; i += BS) seg[i] = src[i];
-    __syncthreads();
-    bitonic_sort_pow2(seg, Np);
-}
+// (lds_bitonic_sort, the load into LDS and the network: csrc/sepaihrd_bitonic.inc)
 
 // one workgroup per segment of Np doubles: bitonic sort in LDS, then thread p stores pick p
 template <class Pick>
@@ -972,6 +967,17 @@ int launch_predictive_scores(const PredictiveArgs& a, const PredictiveScoreArgs&
     const int fields = 3 * (a.n + 1) * sepaihrd_score::summary_width(sa.n_levels);
     hipLaunchKernelGGL(score_summary_kernel, dim3((unsigned)((fields + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, sc);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace sepaihrd
+
+// ---- sort_segments_global for csrc/sepaihrd_predictive_targets.hip, whose sorted kernels are its own ----
+namespace sepaihrd {
+
+int sort_segments_global_for(const double* vals, int segments, int S_pad, double* scratch, size_t scratch_doubles, void* stream,
+                             const std::function<void(int, int)>& pick) {
+    return sort_segments_global(vals, segments, S_pad, scratch, scratch_doubles, static_cast<hipStream_t>(stream),
+                                [&](int first, int ng) { pick(first, ng); });
 }
 
 }  // namespace sepaihrd

@@ -15,6 +15,7 @@
 #include "sepaihrd_nb_draw.inc"
 #include "sepaihrd_nb_objective_device.h"
 #include "sepaihrd_predictive_device.h"
+#include "sepaihrd_predictive_targets_device.h"
 
 namespace sepaihrd {
 namespace {
@@ -100,6 +101,14 @@ bool probe_values_ok(const double* v, int count, bool allow_inf) {
 }
 
 }  // namespace
+
+int launch_predictive_nb_k(const PredictiveArgs& a, const DevProblem& pb, const double* d_theta, const NbDispersion& disp, double* d_k_used,
+                           int32_t* d_wstatus, void* stream) {
+    if (a.S <= 0 || d_theta == nullptr || d_k_used == nullptr || d_wstatus == nullptr || a.wstatus != d_wstatus) return -4;
+    hipLaunchKernelGGL(predictive_nb_k_kernel, dim3((unsigned)((a.S + DRAW_BLOCK - 1) / DRAW_BLOCK)), dim3(DRAW_BLOCK), 0, static_cast<hipStream_t>(stream),
+                       pb, d_theta, a.S, disp, d_k_used, d_wstatus);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int launch_predictive_draws_nb(const PredictiveArgs& a, const DevProblem& pb, const double* d_theta, const NbDispersion& disp, double* d_k_used,
                                int32_t* d_wstatus, void* stream) {

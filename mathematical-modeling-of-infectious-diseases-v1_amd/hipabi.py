@@ -219,6 +219,7 @@ EXPORTED_SYMBOLS = (
     "sepaihrd_ensemble_predictive", "sepaihrd_predictive_validate", "sepaihrd_predictive_timing", "sepaihrd_poisson_device",
     "sepaihrd_ensemble_predictive_nb", "sepaihrd_gamma_device", "sepaihrd_nb_draw_device",
     "sepaihrd_ensemble_predictive_scores", "sepaihrd_predictive_scores_validate",
+    "sepaihrd_ensemble_predictive_targets", "sepaihrd_predictive_targets_validate",
     "sepaihrd_ensemble_stochastic", "sepaihrd_stochastic_validate", "sepaihrd_stochastic_values_width", "sepaihrd_stochastic_timing",
     "sepaihrd_particle_loglik", "sepaihrd_particle_validate", "sepaihrd_particle_max_particles", "sepaihrd_particle_timing",
     "sepaihrd_particle_resample_device",
@@ -264,6 +265,33 @@ def score_views(cell_scores, summary, observed, levels) -> dict:
             pooled[k, a] = v.mean() if v.size else np.nan
     out["summary_dawid_sebastiani"] = pooled
     return out
+
+
+TARGET_SERIES = SCORE_SERIES + tuple("cumulative_" + name for name in SCORE_SERIES)
+
+
+def target_views(target_scores, summary, target_obs, levels) -> dict:
+    """score_views over the targets of sepaihrd_ensemble_predictive_targets: target_scores [6][W][G][5 + 4 L], summary
+    [6][G + 1][4 + 2 L] and target_obs [6][W][G] take the places of cell_scores, summary and observed -- mean, variance, median,
+    crps, wis [6][W][G]; lower, upper, interval_score, covered [L][6][W][G]; the summary_* entries [6][G + 1] and [L][6][G + 1];
+    series in the order of TARGET_SERIES."""
+    return score_views(target_scores, summary, target_obs, levels)
+
+
+def predictive_targets_validate(S: int, R: int, T_pos: int, n_age: int, age_group, window: int, origin: int, probs, levels) -> tuple:
+    """sepaihrd_predictive_targets_validate (host only): (W, G) of the grouping and the windows, or ValueError with its message"""
+    ag = np.ascontiguousarray(age_group, dtype=np.int32).ravel()
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    if ag.size != int(n_age):
+        raise ValueError("age_group must hold n_age = %d entries, not %d" % (int(n_age), ag.size))
+    W, G = C.c_int(0), C.c_int(0)
+    err = C.create_string_buffer(512)
+    if load_library().sepaihrd_predictive_targets_validate(int(S), int(R), int(T_pos), int(n_age), ag.ctypes.data, int(window), int(origin),
+                                                           pr.ctypes.data, pr.size, lv.ctypes.data, lv.size, C.byref(W), C.byref(G), err,
+                                                           len(err)) != 0:
+        raise ValueError(err.value.decode())
+    return W.value, G.value
 
 
 F_DISPERSION = 28  # enum sepaihrd_field SEPAIHRD_F_DISPERSION: param_index 0, 1, 2 = the dispersion of the H, ICU, D series
@@ -404,6 +432,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.sepaihrd_ensemble_predictive_scores.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, C.c_int, vp, C.c_int,
                                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sepaihrd_predictive_scores_validate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_char_p, C.c_int]
+    lib.sepaihrd_ensemble_predictive_targets.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp,
+                                                         C.c_int] + [vp] * 12
+    lib.sepaihrd_predictive_targets_validate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int,
+                                                         vp, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_gamma_device.argtypes = [C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_nb_draw_device.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_char_p, C.c_int]
     lib.sepaihrd_particle_loglik.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64] + [vp] * 7
@@ -815,6 +847,69 @@ class HipObjective:
         if want_draws:
             out["draws"] = draws
         out.update(score_views(cell_scores, summary, ob, lv))
+        return out
+
+    def ensemble_predictive_targets(self, theta, R: int, seed: int, probs, levels, age_group, window: int, origin: int = 0, observed=None,
+                                    dispersion="context", want_means: bool = False, want_draws: bool = False,
+                                    want_target_draws: bool = False) -> dict:
+        """The posterior predictive draws scored on window and age-group totals on the device
+        (sepaihrd_ensemble_predictive_targets): the draws of ensemble_predictive_scores(..., dispersion=dispersion) summed into
+        targets -- age_group [n] (-1: left out, else a group id 0 .. G - 1) x windows of `window` output rows from row `origin`,
+        W = (T_pos - origin) // window of them, and the running sums of those totals.  target_quantiles [6][n_probs][W][G], pit,
+        target_obs [6][W][G], target_scores [6][W][G][5 + 4 L], summary [6][G + 1][4 + 2 L] (entry G pools the groups), exact,
+        W, G, window_first_row [W], levels, age_group, the named views of target_views, and status, n_valid, k_used, phase_ms
+        (means, the daily draws and target_draws [S][R][3][W][G] on request) as the scored call gives them.  observed
+        [3][T_pos][n] (None: the context's observations) is the daily table the observed targets are summed from.  ValueError for
+        an argument sepaihrd_predictive_targets_validate refuses."""
+        th = np.ascontiguousarray(np.atleast_2d(theta), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+        ag = np.ascontiguousarray(age_group, dtype=np.int32).ravel()
+        S, npb, n, R, L = th.shape[0], pr.size, self.pb.n, int(R), lv.size
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        ob = None
+        if observed is not None:
+            ob = np.ascontiguousarray(observed, dtype=np.float64)
+            if ob.shape != (3, Tp, n):
+                raise ValueError("observed must be [3][T_pos][n]: (3, %d, %d), not %s" % (Tp, n, ob.shape))
+        disp = None
+        if not (isinstance(dispersion, str) and dispersion == self.CONTEXT_DISPERSION):
+            disp = np.ascontiguousarray(dispersion, dtype=np.float64).ravel()
+            if disp.size != 3:
+                raise ValueError("dispersion must hold three entries: k_H, k_ICU, k_D")
+        W, G = 1, 1  # where the scored call's own rules fail, the call below refuses with their message before either is read
+        if S > 0 and R > 0 and self.lib.sepaihrd_predictive_validate(S, R, Tp, n, pr.ctypes.data, npb, None, 0) == 0:
+            W, G = predictive_targets_validate(S, R, Tp, n, ag, window, origin, pr, lv)
+        tq, pit, tobs = np.empty((6, npb, W, G)), np.empty((6, W, G)), np.empty((6, W, G))
+        tscores, summary = np.empty((6, W, G, 5 + 4 * L)), np.empty((6, G + 1, 4 + 2 * L))
+        means = np.empty((S, 3, Tp, n)) if want_means else None
+        draws = np.empty((S, max(R, 0), 3, Tp, n)) if want_draws else None
+        tdraws = np.empty((S, max(R, 0), 3, W, G)) if want_target_draws else None
+        k_used = np.empty((S, 3))
+        status = np.empty(S, dtype=np.int32)
+        nv, exact = C.c_int32(0), C.c_int32(0)
+        rc = self.lib.sepaihrd_ensemble_predictive_targets(
+            self.ctx, th.ctypes.data, S, R, int(seed) & 0xFFFFFFFFFFFFFFFF, None if disp is None else disp.ctypes.data,
+            None if ob is None else ob.ctypes.data, ag.ctypes.data, int(window), int(origin), pr.ctypes.data, npb, lv.ctypes.data, L,
+            tq.ctypes.data, pit.ctypes.data, tscores.ctypes.data, summary.ctypes.data, tobs.ctypes.data,
+            None if tdraws is None else tdraws.ctypes.data, means.ctypes.data if want_means else None,
+            draws.ctypes.data if want_draws else None, k_used.ctypes.data, status.ctypes.data, C.byref(nv), C.byref(exact))
+        if rc == -1 and disp is not None and not np.all(np.isposinf(disp) | ((disp >= 1e-3) & (disp <= 1e6))):
+            raise ValueError(self.lib.sepaihrd_last_error(self.ctx).decode())  # sepaihrd_particle_nb_validate's message
+        self._check(rc, "ensemble_predictive_targets")
+        ms = np.zeros(3)
+        self._check(self.lib.sepaihrd_predictive_timing(self.ctx, ms.ctypes.data), "predictive_timing")
+        out = {"target_quantiles": tq, "pit": pit, "target_obs": tobs, "target_scores": tscores, "summary": summary,
+               "exact": bool(exact.value), "W": W, "G": G, "window": int(window), "origin": int(origin),
+               "window_first_row": int(origin) + int(window) * np.arange(W), "levels": lv, "age_group": ag, "status": status,
+               "n_valid": nv.value, "phase_ms": ms, "k_used": k_used}
+        if want_means:
+            out["means"] = means
+        if want_draws:
+            out["draws"] = draws
+        if want_target_draws:
+            out["target_draws"] = tdraws
+        out.update(target_views(tscores, summary, tobs, lv))
         return out
 
     def ensemble_stochastic(self, theta, R: int, steps_per_interval: int, seed: int, probs, keep: int = 0, want_extinct: bool = True,

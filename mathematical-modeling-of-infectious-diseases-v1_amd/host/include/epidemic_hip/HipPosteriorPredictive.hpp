@@ -41,6 +41,17 @@ int hostPosteriorPredictiveScores(const double* means, const int32_t* status, co
                                   double* pred_quantiles, double* pit, double* cell_scores, double* summary, double* draws, int32_t* exact,
                                   std::string* error = nullptr);
 
+// The scores on window and age-group totals, the twin of sepaihrd_ensemble_predictive_targets (k_used NULL: Poisson draws): the
+// same daily draws summed into the targets of csrc/sepaihrd_predictive_targets.inc, a std::sort of every target segment and the
+// score text; shapes as that call's.  observed [3][T_pos][n_age], target_quantiles, target_scores and summary are required; pit,
+// target_obs, target_draws, draws and exact are nullable.  Bit for bit where *exact is 1.  SEPAIHRD_E_INVALID_ARG with
+// sepaihrd_predictive_targets_validate's message.
+int hostPosteriorPredictiveTargets(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                                   int n_age, std::uint64_t seed, const int32_t* age_group, int window, int origin, const double* probs, int n_probs,
+                                   const double* levels, int n_levels, double* target_quantiles, double* pit, double* target_scores,
+                                   double* summary, double* target_obs, double* target_draws, double* draws, int32_t* exact,
+                                   std::string* error = nullptr);
+
 // one unsorted sample x [m] against one observation y: scores [5 + 4 L] as a cell of cell_scores, its mid-PIT and whether its sums
 // are exact (both nullable)
 int hostScoreCell(const double* x, int m, double y, const double* levels, int n_levels, double* scores, double* pit, int32_t* exact,
@@ -78,6 +89,18 @@ struct PosteriorPredictiveScores : PosteriorPredictiveDraws {
     bool exact = false;               // the sums were exact: the host twin gives the same bits
 };
 
+// the result of sepaihrd_ensemble_predictive_targets: pred_quantiles [6][n_probs][W][G] and pit [6][W][G] are the targets'
+struct PosteriorPredictiveTargets : PosteriorPredictiveDraws {
+    std::vector<int32_t> age_group;     // [n_age]
+    int window = 0, origin = 0, W = 0, G = 0;
+    std::vector<double> levels;
+    std::vector<double> target_scores;  // [6][W][G][5 + 4 L]
+    std::vector<double> summary;        // [6][G + 1][4 + 2 L]
+    std::vector<double> target_obs;     // [6][W][G]
+    std::vector<double> target_draws;   // [S][R][3][W][G]; empty unless asked for
+    bool exact = false;
+};
+
 class HipPosteriorPredictive {
 public:
     HipPosteriorPredictive(HipSEPAIHRDParameterManager& parameterManager, const CalibrationData& observed_data,
@@ -99,6 +122,15 @@ public:
     PosteriorPredictiveScores score(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc, unsigned int random_seed,
                                     int replicates, std::uint64_t seed, const std::vector<double>& probs, const std::vector<double>& levels,
                                     const std::vector<double>* observed_table = nullptr, bool want_means = false, bool want_draws = false);
+
+    // The scores on window and age-group totals (sepaihrd_ensemble_predictive_targets) over the samples score() would select, the
+    // dispersion picked as score() picks it.  InvalidParameterException with sepaihrd_predictive_targets_validate's message for a
+    // grouping or windows the call refuses.
+    PosteriorPredictiveTargets scoreTargets(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc, unsigned int random_seed,
+                                            int replicates, std::uint64_t seed, const std::vector<double>& probs,
+                                            const std::vector<double>& levels, const std::vector<int32_t>& age_group, int window, int origin = 0,
+                                            const std::vector<double>* observed_table = nullptr, bool want_means = false,
+                                            bool want_draws = false, bool want_target_draws = false);
 
     // the observations as the device places them: [3][T_pos][n_age], row j of the data at output time j >= 0, NaN beyond the data
     std::vector<double> observed() const;

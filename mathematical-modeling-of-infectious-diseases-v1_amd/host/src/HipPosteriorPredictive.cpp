@@ -12,6 +12,7 @@
 #include "sepaihrd_nb_draw.inc"
 #include "sepaihrd_poisson.inc"
 #include "sepaihrd_predictive_score.inc"
+#include "sepaihrd_predictive_targets.inc"
 #include "sepaihrd_quantile.inc"
 
 namespace epidemic {
@@ -156,6 +157,108 @@ int hostScoreCell(const double* x, int m, double y, const double* levels, int n_
     return SEPAIHRD_OK;
 }
 
+int hostPosteriorPredictiveTargets(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R, int T_pos,
+                                   int n_age, std::uint64_t seed, const int32_t* age_group, int window, int origin, const double* probs, int n_probs,
+                                   const double* levels, int n_levels, double* target_quantiles, double* pit, double* target_scores,
+                                   double* summary, double* target_obs, double* target_draws, double* draws, int32_t* exact, std::string* error) {
+    char msg[256] = "";
+    int W = 0, G = 0;
+    int vrc = sepaihrd_predictive_targets_validate(S, R, T_pos, n_age, age_group, window, origin, probs, n_probs, levels, n_levels, &W, &G, msg,
+                                                   (int)sizeof(msg));
+    if (vrc == SEPAIHRD_OK && (!means || !status || !observed || !target_quantiles || !target_scores || !summary)) {
+        std::snprintf(msg, sizeof(msg), "ensemble_predictive_targets: means, status, observed, target_quantiles, target_scores and summary must not be NULL");
+        vrc = SEPAIHRD_E_INVALID_ARG;
+    }
+    for (int s = 0; vrc == SEPAIHRD_OK && s < S && k_used; ++s)
+        if (status[s] == 0) vrc = sepaihrd_particle_nb_validate(k_used + (size_t)s * 3, msg, (int)sizeof(msg));
+    if (vrc != SEPAIHRD_OK) {
+        if (error) *error = msg;
+        return vrc;
+    }
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    const size_t Tp = (size_t)T_pos, n = (size_t)n_age, WG = (size_t)W * G, segments = 6 * WG;
+    std::vector<int> valid;
+    for (int s = 0; s < S; ++s)
+        if (status[s] == 0) valid.push_back(s);
+    const size_t nd = valid.size() * (size_t)R;  // draws per segment
+    const size_t per_draw = 3 * Tp * n;
+    for (int s = 0; s < S; ++s) {
+        if (status[s] == 0) continue;
+        if (draws) std::fill(draws + (size_t)s * R * per_draw, draws + (size_t)(s + 1) * R * per_draw, qnan);
+        if (target_draws) std::fill(target_draws + (size_t)s * R * 3 * WG, target_draws + (size_t)(s + 1) * R * 3 * WG, qnan);
+    }
+    // every draw's daily variates summed into its targets: the order does not show while the sums are exact
+    std::vector<double> seg(segments * nd);
+#pragma omp parallel
+    {
+        std::vector<double> tot(3 * WG);
+#pragma omp for schedule(static)
+        for (long long d = 0; d < (long long)nd; ++d) {
+            const size_t s = (size_t)valid[(size_t)d / (size_t)R], r = (size_t)d % (size_t)R;
+            std::fill(tot.begin(), tot.end(), 0.0);
+            for (size_t k = 0; k < 3; ++k)
+                for (size_t t = 0; t < Tp; ++t) {
+                    const int v = sepaihrd_targets::window_of_row((int)t, window, origin, W);
+                    for (size_t a = 0; a < n; ++a) {
+                        const int g = age_group[a];
+                        if (!draws && (v < 0 || g < 0)) continue;
+                        const size_t cell = (k * Tp + t) * n + a;
+                        const double m = means[((s * 3 + k) * Tp + t) * n + a];
+                        const double y = k_used ? sepaihrd_nb_draw::nb_variate(seed, (uint32_t)s, (uint32_t)r, (uint32_t)cell, m + 1e-10, k_used[s * 3 + k])
+                                                : sepaihrd_poisson::poisson(seed, (uint32_t)s, (uint32_t)r, (uint32_t)cell, m + 1e-10);
+                        if (draws) draws[(s * (size_t)R + r) * per_draw + cell] = y;
+                        if (v >= 0 && g >= 0) tot[(k * W + (size_t)v) * G + (size_t)g] += y;
+                    }
+                }
+            for (size_t k = 0; k < 3; ++k)
+                for (size_t g = 0; g < (size_t)G; ++g) {
+                    double run = 0.0;
+                    for (size_t v = 0; v < (size_t)W; ++v) {
+                        const double x = tot[(k * W + v) * G + g];
+                        run += x;
+                        seg[sepaihrd_targets::target_index((int)k, (int)v, (int)g, W, G) * nd + (size_t)d] = x;
+                        seg[sepaihrd_targets::target_index((int)k + 3, (int)v, (int)g, W, G) * nd + (size_t)d] = run;
+                    }
+                }
+            if (target_draws) std::copy(tot.begin(), tot.end(), target_draws + (s * (size_t)R + r) * 3 * WG);
+        }
+    }
+    std::vector<double> tobs_own;
+    if (!target_obs) {
+        tobs_own.resize(segments);
+        target_obs = tobs_own.data();
+    }
+    const auto obs_at = [&](int k, int t, int a) { return observed[((size_t)k * Tp + (size_t)t) * n + (size_t)a]; };
+    for (int k = 0; k < 3; ++k)
+        for (int g = 0; g < G; ++g) sepaihrd_targets::observed_targets(obs_at, age_group, n_age, window, origin, W, G, k, g, target_obs);
+    int all_exact = 1;
+    const size_t CW = (size_t)sepaihrd_score::cell_width(n_levels);
+#pragma omp parallel for schedule(dynamic, 4)
+    for (long long sg = 0; sg < (long long)segments; ++sg) {
+        const size_t sid = (size_t)sg, k = sid / WG, vg = sid % WG;
+        double* x = seg.data() + sid * nd;
+        std::sort(x, x + nd);
+        const double obs = target_obs[sid];
+        const sepaihrd_score::SegmentSums sums = sepaihrd_score::segment_sums(x, nd, obs);
+        sepaihrd_score::cell_rule(x, nd, obs, sums, levels, n_levels, target_scores + sid * CW);
+        if (pit) pit[sid] = sepaihrd_score::pit_of(sums, nd, obs);
+        if (nd > 0 && !sepaihrd_score::sums_exact(nd, x[nd - 1])) {
+#pragma omp atomic write
+            all_exact = 0;
+        }
+        for (int p = 0; p < n_probs; ++p)
+            target_quantiles[(k * (size_t)n_probs + (size_t)p) * WG + vg] = nd > 0 ? sepaihrd_quantile::sorted_quantile(x, nd, probs[p]) : qnan;
+    }
+    const size_t SW = (size_t)sepaihrd_score::summary_width(n_levels);
+    for (int k = 0; k < sepaihrd_targets::N_SERIES; ++k)
+        for (int g = 0; g <= G; ++g)
+            for (int f = 0; f < (int)SW; ++f)
+                summary[((size_t)k * (G + 1) + (size_t)g) * SW + (size_t)f] =
+                    sepaihrd_targets::target_summary_field(target_scores, target_obs, nd, W, G, n_levels, k, g, f);
+    if (exact) *exact = all_exact;
+    return SEPAIHRD_OK;
+}
+
 int hostPosteriorPredictive(const double* means, const int32_t* status, const double* observed, int S, int R, int T_pos, int n_age,
                             std::uint64_t seed, const double* probs, int n_probs, double* pred_quantiles, double* pit, double* draws,
                             std::string* error) {
@@ -283,6 +386,59 @@ PosteriorPredictiveScores HipPosteriorPredictive::score(const std::vector<Eigen:
         out.status.data(), &nv, &exact);
     if (rc != SEPAIHRD_OK)
         throw ModelException("HipPosteriorPredictive", std::string("sepaihrd_ensemble_predictive_scores: ") + sepaihrd_last_error(ctx));
+    out.samples_used = nv;
+    out.exact = exact != 0;
+    return out;
+}
+
+PosteriorPredictiveTargets HipPosteriorPredictive::scoreTargets(const std::vector<Eigen::VectorXd>& param_samples, int num_samples_for_ppc,
+                                                                unsigned int random_seed, int replicates, std::uint64_t seed,
+                                                                const std::vector<double>& probs, const std::vector<double>& levels,
+                                                                const std::vector<int32_t>& age_group, int window, int origin,
+                                                                const std::vector<double>* observed_table, bool want_means, bool want_draws,
+                                                                bool want_target_draws) {
+    PosteriorPredictiveTargets out;
+    out.levels = levels;
+    out.age_group = age_group;
+    out.window = window;
+    out.origin = origin;
+    const std::vector<double> thetas = selectedThetas(param_samples, num_samples_for_ppc, random_seed, replicates, probs, out);
+    if (thetas.empty()) return out;
+    const size_t S = out.selected.size(), L = levels.size();
+    const size_t cells = static_cast<size_t>(3) * t_pos_ * n_;
+    if (observed_table && observed_table->size() != cells)
+        throw InvalidParameterException("HipPosteriorPredictive", "observed must hold 3 x T_pos x n_age values");
+    if (static_cast<int>(age_group.size()) != n_) throw InvalidParameterException("HipPosteriorPredictive", "age_group must hold n_age entries");
+    char msg[256] = "";
+    if (replicates > 0 && !probs.empty() &&
+        sepaihrd_predictive_scores_validate(static_cast<int>(S), replicates, t_pos_, n_, probs.data(), static_cast<int>(probs.size()), levels.data(),
+                                            static_cast<int>(L), nullptr, 0) == SEPAIHRD_OK &&
+        sepaihrd_predictive_targets_validate(static_cast<int>(S), replicates, t_pos_, n_, age_group.data(), window, origin, probs.data(),
+                                             static_cast<int>(probs.size()), levels.data(), static_cast<int>(L), &out.W, &out.G, msg,
+                                             static_cast<int>(sizeof(msg))) != SEPAIHRD_OK)
+        throw InvalidParameterException("HipPosteriorPredictive", msg);
+    if (out.W < 1 || out.G < 1) out.W = out.G = 1;  // the call below refuses with the scored call's own message
+    sepaihrd_ctx* ctx = objective_->deviceContext();
+    objective_->syncDeviceConstraintMode();
+    const size_t targets = static_cast<size_t>(6) * out.W * out.G;
+    out.pred_quantiles.assign(targets * probs.size(), 0.0);
+    out.pit.assign(targets, 0.0);
+    out.target_obs.assign(targets, 0.0);
+    out.target_scores.assign(targets * (5 + 4 * L), 0.0);
+    out.summary.assign(static_cast<size_t>(6) * (out.G + 1) * (4 + 2 * L), 0.0);
+    if (want_means) out.means.assign(S * cells, 0.0);
+    if (want_draws && replicates > 0) out.draws.assign(S * static_cast<size_t>(replicates) * cells, 0.0);
+    if (want_target_draws && replicates > 0) out.target_draws.assign(S * static_cast<size_t>(replicates) * (targets / 2), 0.0);
+    out.status.assign(S, 0);
+    out.k_used.assign(S * 3, 0.0);
+    int32_t nv = 0, exact = 0;
+    const int rc = sepaihrd_ensemble_predictive_targets(
+        ctx, thetas.data(), static_cast<int>(S), replicates, seed, nullptr, observed_table ? observed_table->data() : nullptr, age_group.data(),
+        window, origin, probs.data(), static_cast<int>(probs.size()), levels.data(), static_cast<int>(L), out.pred_quantiles.data(), out.pit.data(),
+        out.target_scores.data(), out.summary.data(), out.target_obs.data(), out.target_draws.empty() ? nullptr : out.target_draws.data(),
+        want_means ? out.means.data() : nullptr, out.draws.empty() ? nullptr : out.draws.data(), out.k_used.data(), out.status.data(), &nv, &exact);
+    if (rc != SEPAIHRD_OK)
+        throw ModelException("HipPosteriorPredictive", std::string("sepaihrd_ensemble_predictive_targets: ") + sepaihrd_last_error(ctx));
     out.samples_used = nv;
     out.exact = exact != 0;
     return out;

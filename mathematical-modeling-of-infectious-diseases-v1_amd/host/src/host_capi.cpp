@@ -1583,6 +1583,53 @@ int host_predictive_scores(void* hv, const sepaihrd_problem* pb, int device, con
     });
 }
 
+// ---- the same scores on window and age-group totals (sepaihrd_ensemble_predictive_targets) ----
+// hostPosteriorPredictiveTargets (no device): shapes as sepaihrd_ensemble_predictive_targets; k_used NULL: Poisson draws
+int host_predictive_targets_from_means(const double* means, const int32_t* status, const double* k_used, const double* observed, int S, int R,
+                                       int T_pos, int n_age, uint64_t seed, const int32_t* age_group, int window, int origin, const double* probs,
+                                       int n_probs, const double* levels, int n_levels, double* target_quantiles, double* pit,
+                                       double* target_scores, double* summary, double* target_obs, double* target_draws, double* draws,
+                                       int32_t* exact, char* err, int errlen) {
+    std::string error;
+    const int rc = hostPosteriorPredictiveTargets(means, status, k_used, observed, S, R, T_pos, n_age, seed, age_group, window, origin, probs, n_probs,
+                                                  levels, n_levels, target_quantiles, pit, target_scores, summary, target_obs, target_draws, draws,
+                                                  exact, &error);
+    if (rc != SEPAIHRD_OK && err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", error.c_str());
+    return rc;
+}
+
+// HipPosteriorPredictive::scoreTargets over the handle's parameter manager / data, as host_predictive_scores drives score(); W and G
+// are the caller's (sepaihrd_predictive_targets_validate), the outputs sized by them
+int host_predictive_targets(void* hv, const sepaihrd_problem* pb, int device, const double* samples, int n_samples, int num_for_ppc,
+                            uint32_t ppc_seed, int R, uint64_t seed, const double* probs, int n_probs, const double* levels, int n_levels,
+                            const int32_t* age_group, int n_age, int window, int origin, const double* observed_in, double* target_quantiles,
+                            double* pit, double* target_scores, double* summary, double* target_obs, double* target_draws, double* k_used,
+                            int32_t* exact, int32_t* selected, int32_t* n_selected, int32_t* status, int32_t* samples_used) {
+    auto* h = static_cast<HostHandle*>(hv);
+    return guarded([&] {
+        HipPosteriorPredictive pp = posterior_over<HipPosteriorPredictive>(*h, pb, device);
+        if (h->has_dispersion) pp.objective().setDispersion(h->dispersion);
+        const std::vector<Eigen::VectorXd> ps = sample_vectors(samples, n_samples, h->pm->getParameterCount());
+        std::vector<double> obs;
+        if (observed_in) obs.assign(observed_in, observed_in + pp.observed().size());
+        const PosteriorPredictiveTargets d = pp.scoreTargets(
+            ps, num_for_ppc, ppc_seed, R, seed, std::vector<double>(probs, probs + n_probs), std::vector<double>(levels, levels + n_levels),
+            std::vector<int32_t>(age_group, age_group + n_age), window, origin, observed_in ? &obs : nullptr, false, false, target_draws != nullptr);
+        std::copy(d.pred_quantiles.begin(), d.pred_quantiles.end(), target_quantiles);
+        if (pit) std::copy(d.pit.begin(), d.pit.end(), pit);
+        std::copy(d.target_scores.begin(), d.target_scores.end(), target_scores);
+        std::copy(d.summary.begin(), d.summary.end(), summary);
+        if (target_obs) std::copy(d.target_obs.begin(), d.target_obs.end(), target_obs);
+        if (target_draws) std::copy(d.target_draws.begin(), d.target_draws.end(), target_draws);
+        if (k_used) std::copy(d.k_used.begin(), d.k_used.end(), k_used);
+        if (exact) *exact = d.exact ? 1 : 0;
+        for (size_t i = 0; i < d.selected.size(); ++i) selected[i] = d.selected[i];
+        *n_selected = static_cast<int32_t>(d.selected.size());
+        if (status) std::copy(d.status.begin(), d.status.end(), status);
+        *samples_used = d.samples_used;
+    });
+}
+
 // ---- stochastic chain-binomial SEPAIHRD ensembles (HipStochasticSEPAIHRD) ----
 // hostStochasticSEPAIHRD (no device): shapes as sepaihrd_ensemble_stochastic; M row-major, M[i n_age + j] = M(i, j)
 int host_stochastic_from_values(int n_age, int n_times, int n_beta, int n_kappa, const double* times, const double* N, const double* M,

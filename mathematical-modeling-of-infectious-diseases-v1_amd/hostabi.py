@@ -137,6 +137,10 @@ def load_library() -> C.CDLL:
                                                   C.c_char_p, C.c_int]
     lib.host_predictive_scores_from_means.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, vp, C.c_int,
                                                       vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_int]
+    lib.host_predictive_targets_from_means.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, C.c_int, C.c_int, vp,
+                                                       C.c_int, vp, C.c_int] + [vp] * 8 + [C.c_char_p, C.c_int]
+    lib.host_predictive_targets.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int,
+                                            C.c_uint64, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int] + [vp] * 13
     lib.host_score_cell.argtypes = [vp, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, C.c_char_p, C.c_int]
     lib.host_predictive_scores.argtypes = [vp, C.POINTER(hipabi.sepaihrd_problem), C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int,
                                            C.c_uint64, vp, C.c_int, vp, C.c_int] + [vp] * 13
@@ -514,6 +518,44 @@ class HostObjective:
             out["means"] = means
         if want_draws:
             out["draws"] = draws
+        return out
+
+    def posterior_predictive_targets(self, samples, num_for_ppc: int, ppc_seed: int, R: int, seed: int, probs, levels, age_group,
+                                     window: int, origin: int = 0, observed=None, want_target_draws: bool = False, device: int = -1) -> dict:
+        """HipPosteriorPredictive::scoreTargets over this handle's parameter manager and data: posterior_predictive_scores'
+        selection and dispersion rule through sepaihrd_ensemble_predictive_targets.  target_quantiles, pit, target_obs,
+        target_scores, summary, exact, W, G, k_used, selected, status, samples_used; target_draws on request."""
+        ps = np.ascontiguousarray(np.atleast_2d(samples), dtype=np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+        ag = np.ascontiguousarray(age_group, dtype=np.int32).ravel()
+        keep: list = []
+        st = hipabi.build_problem_struct(self.pb, keep)
+        n, L = self.pb.n, lv.size
+        Tp = int(np.sum(np.asarray(self.pb.times) >= 0.0))
+        ob = None if observed is None else np.ascontiguousarray(observed, dtype=np.float64)
+        if ob is not None and ob.shape != (3, Tp, n):
+            raise ValueError("observed must be [3][T_pos][n]")
+        cap = max(ps.shape[0], num_for_ppc, 1)
+        S = num_for_ppc if 0 < num_for_ppc < ps.shape[0] else ps.shape[0]
+        W, G = hipabi.predictive_targets_validate(S, R, Tp, n, ag, window, origin, pr, lv)
+        tq, pit, tobs = np.empty((6, pr.size, W, G)), np.empty((6, W, G)), np.empty((6, W, G))
+        tscores, summary = np.empty((6, W, G, 5 + 4 * L)), np.empty((6, G + 1, 4 + 2 * L))
+        tdraws = np.empty((S, max(int(R), 0), 3, W, G)) if want_target_draws else None
+        sel, status = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        nsel, used, exact = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        k_used = np.full((cap, 3), np.inf)
+        _check(self.lib.host_predictive_targets(self.h, C.byref(st), device, ps.ctypes.data, ps.shape[0], num_for_ppc, ppc_seed, int(R),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, pr.ctypes.data, pr.size, lv.ctypes.data, L, ag.ctypes.data,
+                                                ag.size, int(window), int(origin), None if ob is None else ob.ctypes.data, tq.ctypes.data,
+                                                pit.ctypes.data, tscores.ctypes.data, summary.ctypes.data, tobs.ctypes.data,
+                                                None if tdraws is None else tdraws.ctypes.data, k_used.ctypes.data, C.byref(exact),
+                                                sel.ctypes.data, C.byref(nsel), status.ctypes.data, C.byref(used)), "host_predictive_targets: ")
+        out = {"target_quantiles": tq, "pit": pit, "target_obs": tobs, "target_scores": tscores, "summary": summary,
+               "exact": bool(exact.value), "W": W, "G": G, "selected": sel[:nsel.value].copy(), "status": status[:nsel.value].copy(),
+               "samples_used": used.value, "k_used": k_used[:nsel.value].copy()}
+        if want_target_draws:
+            out["target_draws"] = tdraws
         return out
 
     def posterior_stochastic(self, samples, num_samples: int, select_seed: int, R: int, steps_per_interval: int, seed: int,
@@ -1247,6 +1289,64 @@ def predictive_scores_from_means(means, status, observed, R: int, seed: int, pro
     if draws is not None:
         out["draws"] = draws
     out.update(hipabi.score_views(cell_scores, summary, ob, lv))
+    return out
+
+
+def predictive_targets_validate(S: int, R: int, T_pos: int, n_age: int, age_group, window: int, origin: int, probs, levels) -> tuple:
+    """sepaihrd_predictive_targets_validate (host only): (W, G), or ValueError with its message for arguments the call refuses"""
+    return hipabi.predictive_targets_validate(S, R, T_pos, n_age, age_group, window, origin, probs, levels)
+
+
+def predictive_targets_from_means(means, status, observed, R: int, seed: int, probs, levels, age_group, window: int, origin: int = 0,
+                                  k_used=None, want_draws: bool = True, want_target_draws: bool = True) -> dict:
+    """The twin of HipObjective.ensemble_predictive_targets after the integration: from means [S][3][T_pos][n], status [S], k_used
+    [S][3] (None: Poisson draws) and observed [3][T_pos][n] the same daily draws summed into the targets of
+    csrc/sepaihrd_predictive_targets.inc, then std::sort and the score text: target_quantiles, pit, target_obs, target_scores,
+    summary, exact, W, G, window_first_row, draws and target_draws on request, and the named views of hipabi.target_views.  Bit for
+    bit where exact is True."""
+    m = np.ascontiguousarray(means, dtype=np.float64)
+    if m.ndim != 4 or m.shape[1] != 3:
+        raise ValueError("means must be [S][3][T_pos][n]")
+    S, _, Tp, n = m.shape
+    st = np.ascontiguousarray(status, dtype=np.int32)
+    if st.shape != (S,):
+        raise ValueError("status must have one entry per sample")
+    pr = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    ag = np.ascontiguousarray(age_group, dtype=np.int32).ravel()
+    W, G = hipabi.predictive_targets_validate(S, R, Tp, n, ag, window, origin, pr, lv)
+    R, L = int(R), lv.size
+    if observed is None:
+        raise ValueError("observed must be [3][T_pos][n]")
+    ob = np.ascontiguousarray(observed, dtype=np.float64)
+    if ob.shape != (3, Tp, n):
+        raise ValueError("observed must be [3][T_pos][n]: (3, %d, %d), not %s" % (Tp, n, ob.shape))
+    ku = None
+    if k_used is not None:
+        ku = np.ascontiguousarray(k_used, dtype=np.float64)
+        if ku.shape != (S, 3):
+            raise ValueError("k_used must be [S][3]")
+    tq, pit, tobs = np.empty((6, pr.size, W, G)), np.empty((6, W, G)), np.empty((6, W, G))
+    tscores, summary = np.empty((6, W, G, 5 + 4 * L)), np.empty((6, G + 1, 4 + 2 * L))
+    draws = np.empty((S, R, 3, Tp, n)) if want_draws else None
+    tdraws = np.empty((S, R, 3, W, G)) if want_target_draws else None
+    exact = C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = load_library().host_predictive_targets_from_means(
+        m.ctypes.data, st.ctypes.data, None if ku is None else ku.ctypes.data, ob.ctypes.data, S, R, Tp, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        ag.ctypes.data, int(window), int(origin), pr.ctypes.data, pr.size, lv.ctypes.data, L, tq.ctypes.data, pit.ctypes.data,
+        tscores.ctypes.data, summary.ctypes.data, tobs.ctypes.data, None if tdraws is None else tdraws.ctypes.data,
+        None if draws is None else draws.ctypes.data, C.byref(exact), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    out = {"target_quantiles": tq, "pit": pit, "target_obs": tobs, "target_scores": tscores, "summary": summary,
+           "exact": bool(exact.value), "W": W, "G": G, "window_first_row": int(origin) + int(window) * np.arange(W),
+           "n_valid": int(np.sum(st == 0)), "levels": lv, "age_group": ag}
+    if draws is not None:
+        out["draws"] = draws
+    if tdraws is not None:
+        out["target_draws"] = tdraws
+    out.update(hipabi.target_views(tscores, summary, tobs, lv))
     return out
 
 

@@ -64,6 +64,14 @@ def main():
     ap.add_argument("--predictive-levels", default="0.5,0.9,0.95",
                     help="central coverage levels of predictive_scores.csv (interval score and coverage per level, and the WIS over "
                          "them): up to 8 values inside (0, 1), comma-separated")
+    ap.add_argument("--predictive-window", type=int, default=0,
+                    help="with --predictive-replicates: also score the replicates on totals over windows of this many output rows (7 on "
+                         "a daily grid: weekly totals) and on their running sums, on the device: "
+                         "posterior_predictive/predictive_target_scores.csv")
+    ap.add_argument("--predictive-age-groups", default=None,
+                    help="the age groups those totals are summed over: all (one group, the default), each (a group per age) or lists "
+                         "of ages such as '0,1;2,3' (';' between groups; an age in no list is left out).  Alone it scores every output "
+                         "row on its own (a window of 1)")
     args = ap.parse_args()
 
     mm = mmid_amd_loader.load()
@@ -113,6 +121,14 @@ def main():
         dispersed = not np.all(np.isposinf(hip.get_dispersion()))
         levels = [float(c) for c in args.predictive_levels.split(",") if c.strip()]
         predictive = hip.ensemble_predictive_scores(pooled, args.predictive_replicates, args.seed + 2, PROBS, levels)
+        if args.predictive_window > 0 or args.predictive_age_groups is not None:
+            groups = mm.config_io.parse_age_groups(args.predictive_age_groups or "all", pb.n)
+            targets = hip.ensemble_predictive_targets(pooled, args.predictive_replicates, args.seed + 2, PROBS, levels, groups,
+                                                      args.predictive_window if args.predictive_window > 0 else 1)
+            os.makedirs(os.path.join(args.out, "posterior_predictive"), exist_ok=True)
+            mm.config_io.write_predictive_target_scores(os.path.join(args.out, "posterior_predictive", "predictive_target_scores.csv"), targets)
+    elif args.predictive_window > 0 or args.predictive_age_groups is not None:
+        raise SystemExit("--predictive-window and --predictive-age-groups need --predictive-replicates")
     times = np.asarray(pb.times)
     pos = times[times >= 0]
     # the reference's post-calibration output tree (file names, headers and number formats of AnalysisWriter.cpp; what
