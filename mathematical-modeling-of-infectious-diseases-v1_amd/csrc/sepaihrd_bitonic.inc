@@ -1,5 +1,5 @@
 // csrc/sepaihrd_bitonic.inc -- the bitonic network of the segment sorts, device only: one text for the sort-and-pick
-// kernels of csrc/sepaihrd_ensemble.hip and for states_sort_pick_kernel of csrc/sepaihrd_particle_states.hip.
+// kernels of csrc/sepaihrd_segment_sort.inc and for states_sort_pick_kernel of csrc/sepaihrd_particle_states.hip.
 #pragma once
 
 namespace sepaihrd {

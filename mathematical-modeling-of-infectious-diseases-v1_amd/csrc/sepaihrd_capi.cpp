@@ -967,8 +967,8 @@ int sepaihrd_ensemble_quantiles(sepaihrd_ctx* ctx, const double* theta, int S, c
     return SEPAIHRD_OK;
 }
 
-// The body of sepaihrd_ensemble_predictive and sepaihrd_ensemble_predictive_nb.  nb == nullptr: the Poisson call, its draw kernel
-// and nothing else.  Otherwise the dispersion every sample's draws take: the call's own three values (src = -1 throughout) or the
+// The body of sepaihrd_ensemble_predictive and sepaihrd_ensemble_predictive_nb.  nb == nullptr: the Poisson call, the draw kernel
+// with no dispersion table.  Otherwise the dispersion every sample's draws take: the call's own three values (src = -1 throughout) or the
 // context's (the objective's rule, per sample), resolved on the device into k_used [S][3].
 // sr (sepaihrd_ensemble_predictive_scores; null: no scores): the segments are scored where they are sorted and the mid-PIT comes
 // from the sorted segment, so the draw launch takes no PIT pass.
@@ -1084,7 +1084,6 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
     a.sort_scratch = plan.in_lds ? nullptr : d_scratch;
     a.sort_scratch_doubles = n_scratch;
     PredictiveTargetArgs ta{};
-    int drc;
     if (tr) {
         a.vals = nullptr; a.q_out = nullptr; a.pit_out = nullptr;
         ta.W = tr->W; ta.G = tr->G; ta.window = tr->window; ta.origin = tr->origin;
@@ -1092,12 +1091,13 @@ static int predictive_call(sepaihrd_ctx* ctx, const double* theta, int S, int R,
         ta.tvals = d_vals; ta.q_out = d_q; ta.obs_daily = sr->observed ? d_obs : nullptr; ta.target_obs = d_tobs;
         ta.levels = d_levels; ta.n_levels = sr->n_levels; ta.target_scores = d_cs; ta.summary = d_sum; ta.pit_out = pit ? d_pit : nullptr;
         ta.target_draws = tr->target_draws ? d_tdraws : nullptr; ta.exact = d_exact;
-        drc = launch_predictive_nb_k(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr);
-        if (drc == 0) drc = launch_predictive_counts(a, nullptr);
-        if (drc == 0) drc = launch_predictive_target_draws(a, ta, d_k, nullptr);
-    } else {
-        drc = nb ? launch_predictive_draws_nb(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr) : launch_predictive_draws(a, nullptr);
     }
+    // the draw phase: the dispersions (none for the Poisson call, whose null table reads k = +inf), the counts, the draws, and
+    // the mid-PIT of the unsorted daily table where a.pit_out asks for it
+    int drc = nb ? launch_predictive_nb_k(a, dp, d_theta, *nb, d_k, ctx->ws_status, nullptr) : 0;
+    if (drc == 0) drc = launch_predictive_counts(a, nullptr);
+    if (drc == 0) drc = tr ? launch_predictive_target_draws(a, ta, d_k, nullptr) : launch_predictive_draws(a, nb ? d_k : nullptr, nullptr);
+    if (drc == 0) drc = launch_predictive_pit(a, nullptr);
     if (drc != 0) return refuse(ctx, who, "draw kernel launch failed", SEPAIHRD_E_HIP);
     (void)hipEventRecord(sc.ev[2], nullptr);
     if (tr) {

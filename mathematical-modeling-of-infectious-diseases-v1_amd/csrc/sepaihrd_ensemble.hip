@@ -21,9 +21,10 @@
 // loads its segment coalesced, sorts it in LDS (bitonic, up to 16384 doubles = 128 KiB) and
 // interpolates the quantiles.  Samples whose integration failed are +inf and sort to the end; the
 // quantile positions use the count of valid samples.  How a segment is padded and when it is sorted
-// in global memory instead: csrc/sepaihrd_segments.h; the one dispatch: sort_segments_and_pick below, under the one kernel
-// pair (segment_sort_pick_kernel, segment_pick_sorted_kernel) and the one launcher (launch_sort_pick) that every summary
-// here instantiates with its own pick: EnsemblePick, ScenarioPick, StochSirPick.
+// in global memory instead: csrc/sepaihrd_segments.h; the one dispatch (sort_segments_and_pick), the one kernel pair
+// (segment_sort_pick_kernel, segment_pick_sorted_kernel) and the one launcher (launch_sort_pick), with their scored forms, are
+// the text of csrc/sepaihrd_segment_sort.inc, which every summary here instantiates with its own pick: EnsemblePick,
+// ScenarioPick, StochSirPick.
 // Compiled with -ffp-contract=off: the interpolation is the CPU build's operation sequence.
 // =============================================================================
 #include <hip/hip_runtime.h>
@@ -31,18 +32,10 @@
 #include <stdint.h>
 
 #include <cstring>
-#include <vector>
 
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
-#include "sepaihrd_bitonic.inc"
 #include "sepaihrd_device.h"
-#include "sepaihrd_host_util.h"
 #include "sepaihrd_predictive_device.h"
-#include "sepaihrd_predictive_score.inc"
-#include "sepaihrd_predictive_targets_device.h"
-#include "sepaihrd_quantile.inc"
-#include "sepaihrd_segments.h"
+#include "sepaihrd_segment_sort.inc"
 #include "sepaihrd_sir_device.h"
 #include "sepaihrd_stoch_device.h"
 #include "sepaihrd_stoch.inc"
@@ -307,32 +300,7 @@ __global__ __launch_bounds__(WAVE) void ensemble_metrics_kernel(const EnsembleAr
     out[8] = max_rt; out[9] = min_rt; out[10] = final_rt; out[11] = sero64;
 }
 
-// ---- sort and pick: every summary across samples sorts segments of values (+inf padding last) and picks a few numbers from
-// each.  A pick is a functor passed to the kernels by value, carrying its caller's argument struct: picks() numbers per
-// segment, operator()(sid, p, sorted segment) stores number p of segment sid, SORTED_BLOCK is the workgroup of the sorted kernel.
-
-// (lds_bitonic_sort, the load into LDS and the network: csrc/sepaihrd_bitonic.inc)
-
-// one workgroup per segment of Np doubles: bitonic sort in LDS, then thread p stores pick p
-template <class Pick>
-__global__ void segment_sort_pick_kernel(const Pick pick, const double* vals, const int Np) {
-    extern __shared__ double seg[];
-    const size_t sid = blockIdx.x;
-    lds_bitonic_sort(seg, vals + sid * (size_t)Np, Np);
-    for (int p = threadIdx.x; p < pick.picks(); p += blockDim.x) pick(sid, p, seg);
-}
-
-// Segments beyond the LDS sort: those of a group were sorted in global memory by the library's segmented radix sort; one
-// thread per (segment of the group, pick).
-template <class Pick>
-__global__ __launch_bounds__(Pick::SORTED_BLOCK) void segment_pick_sorted_kernel(const Pick pick, const double* sorted, const int Np,
-                                                                                 const int first_segment, const int n_group) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int picks = pick.picks();
-    if (idx >= (size_t)n_group * picks) return;
-    const int g = (int)(idx / picks), p = (int)(idx % picks);
-    pick((size_t)(first_segment + g), p, sorted + (size_t)g * Np);
-}
+// ---- the picks of the summaries here (the kernels and launchers that take them: csrc/sepaihrd_segment_sort.inc) ----
 
 // quantile p of sorted segment `sid` (*n_valid valid values first, +inf after them) into its output slot
 struct EnsemblePick {
@@ -456,94 +424,6 @@ struct ScenarioPick {
         }
     }
 };
-
-// Segments of S_pad doubles (more than the LDS sort holds) sorted in groups by rocPRIM's segmented radix sort into
-// `scratch`; pick(first, n_group) launches the interpolation of each sorted group.  Synchronises the stream.
-template <class Pick>
-int sort_segments_global(const double* vals, int segments, int S_pad, double* scratch, size_t scratch_doubles, hipStream_t st,
-                         Pick pick) {
-    // group size bounded by the scratch buffer
-    int group = (int)(scratch_doubles / (size_t)S_pad);
-    if (group > segments) group = segments;
-    if (group < 1 || (size_t)group * S_pad >= (size_t)1 << 31) return -4;
-    std::vector<unsigned> offs((size_t)group + 1);
-    for (int g = 0; g <= group; ++g) offs[(size_t)g] = (unsigned)((size_t)g * S_pad);
-    DeviceBuf offs_buf, tmp;  // freed on return, after the stream has been synchronised
-    unsigned* d_offs = nullptr;
-    if (!offs_buf.get(&d_offs, offs.size())) return -3;
-    int rc = 0;
-    if (hipMemcpyAsync(d_offs, offs.data(), offs.size() * sizeof(unsigned), hipMemcpyHostToDevice, st) != hipSuccess) rc = -3;
-    for (int first = 0; first < segments && rc == 0; first += group) {
-        const int ng = (segments - first < group) ? segments - first : group;
-        const double* in = vals + (size_t)first * S_pad;
-        const unsigned size = (unsigned)((size_t)ng * S_pad);
-        size_t need = 0;
-        if (rocprim::segmented_radix_sort_keys(nullptr, need, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
-                                               st) != hipSuccess) { rc = -3; break; }
-        if (!tmp.reserve(need)) { rc = -3; break; }
-        size_t tmp_bytes = tmp.cap;
-        if (rocprim::segmented_radix_sort_keys(tmp.p, tmp_bytes, in, scratch, size, (unsigned)ng, d_offs, d_offs + 1, 0, 64,
-                                               st) != hipSuccess) { rc = -3; break; }
-        pick(first, ng);
-    }
-    (void)hipStreamSynchronize(st);
-    return (rc == 0 && hipGetLastError() == hipSuccess) ? 0 : -3;
-}
-
-// what every launcher asks of the segments it is handed: `count` values each, in a pad the plan gives (sepaihrd_segments.h)
-bool pad_legal(size_t count, int pad) { return pad > 0 && segment_pad_valid(count, (size_t)pad); }
-
-// the LDS sort of plan.pad doubles (and `extra_bytes` the kernel keeps next to them) needs the kernel's dynamic-LDS limit raised
-// above 48 KiB; 0 or -3
-int raise_lds_limit(const SegmentPlan& plan, const void* lds_kernel, size_t extra_bytes = 0) {
-    const size_t lds = plan.pad * sizeof(double) + extra_bytes;
-    if (!plan.in_lds || lds <= 48 * 1024) return 0;
-    return hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -3;
-}
-
-// Sort every segment, then pick from it, by the plan's route.  In LDS: launch_lds(threads, lds_bytes) launches `lds_kernel`
-// with one workgroup per segment (null: the caller has raised its LDS limit already).  In global memory:
-// sort_segments_global with pick(first, n_group).  0, -3 (HIP failure) or -4 (no segment fits the scratch).
-template <class LaunchLds, class Pick>
-int sort_segments_and_pick(const SegmentPlan& plan, int segments, const double* vals, double* scratch, size_t scratch_doubles,
-                           hipStream_t st, const void* lds_kernel, LaunchLds launch_lds, Pick pick) {
-    if (!plan.in_lds) return sort_segments_global(vals, segments, (int)plan.pad, scratch, scratch_doubles, st, pick);
-    if (lds_kernel != nullptr && raise_lds_limit(plan, lds_kernel) != 0) return -3;
-    launch_lds(plan.pad / 2 < 1024 ? (int)(plan.pad / 2) : 1024, plan.pad * sizeof(double));
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// events and the sum that time every sorted pick of a call (launch_stoch_sir_summaries); null: untimed
-struct PickTimer {
-    hipEvent_t ev0, ev1;
-    double* ms;
-};
-
-// The one launcher: `segments` segments of vals, `pad` doubles apart, are sorted and `pick` takes its numbers from each.
-// lds_limit_raised: the caller has raised the LDS limit of this pick's segment_sort_pick_kernel already.
-template <class Pick>
-int launch_sort_pick(const Pick& pick, const double* vals, int pad, int segments, double* scratch, size_t scratch_doubles, hipStream_t st,
-                     bool lds_limit_raised = false, const PickTimer* timer = nullptr) {
-    return sort_segments_and_pick(
-        plan_of_pad((size_t)pad), segments, vals, scratch, scratch_doubles, st,
-        lds_limit_raised ? nullptr : reinterpret_cast<const void*>(&segment_sort_pick_kernel<Pick>),
-        [&](int threads, size_t lds) {
-            hipLaunchKernelGGL(segment_sort_pick_kernel<Pick>, dim3((unsigned)segments), dim3(threads), lds, st, pick, vals, pad);
-        },
-        [&](int first, int ng) {
-            constexpr int BLOCK = Pick::SORTED_BLOCK;
-            const size_t work = (size_t)ng * pick.picks();
-            if (timer) (void)hipEventRecord(timer->ev0, st);
-            hipLaunchKernelGGL(segment_pick_sorted_kernel<Pick>, dim3((unsigned)((work + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, pick,
-                               scratch, pad, first, ng);
-            if (timer) {
-                float ms = 0.0f;
-                (void)hipEventRecord(timer->ev1, st);
-                if (hipEventSynchronize(timer->ev1) == hipSuccess && hipEventElapsedTime(&ms, timer->ev0, timer->ev1) == hipSuccess)
-                    *timer->ms += (double)ms;
-            }
-        });
-}
 
 // ---- age-structured SIR: posterior ensemble and intervention scenarios (sepaihrd_sir_scenario_ensemble) ----
 // The ensemble build of the SIR integrator (csrc/sepaihrd_sir.hip) has stored the series of every valid chain in
@@ -804,106 +684,24 @@ int launch_stoch_sir_summaries(const StochSummaryArgs& a, void* stream) {
 
 // ---- posterior predictive draws (sepaihrd_ensemble_predictive): the quantiles of the 6 Tp n segments of S R replicated
 // counts, with the segment sorts and the interpolation of sepaihrd_ensemble_quantiles; the count of values per segment is
-// the number of valid samples times R ----
+// the number of valid samples times R.  With scores (sepaihrd_ensemble_predictive_scores) every cell of
+// the three daily series is, from the same sorted segment, scored by the rules of csrc/sepaihrd_predictive_score.inc ----
 namespace sepaihrd {
+namespace {
 
-int launch_predictive_quantiles(const PredictiveArgs& a, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t segments = (size_t)6 * a.Tp * a.n;
-    if (a.S <= 0 || a.R <= 0 || segments >= ((size_t)1 << 31) || !pad_legal((size_t)a.S * a.R, a.N_pad)) return -4;
+bool predictive_segments_ok(const PredictiveArgs& a) {
+    return a.S > 0 && a.R > 0 && (size_t)6 * a.Tp * a.n < ((size_t)1 << 31) && pad_legal((size_t)a.S * a.R, a.N_pad);
+}
+
+EnsemblePick predictive_pick(const PredictiveArgs& a) {
+    const int segments = 6 * a.Tp * a.n;
     EnsembleArgs e{};
     e.S = a.S * a.R; e.S_pad = a.N_pad; e.lpc = a.lpc; e.n = a.n; e.T = a.T; e.Tp = a.Tp;
     e.n_probs = a.n_probs; e.probs = a.probs;
     e.vals = a.vals; e.q_out = a.q_out;
     e.n_valid = a.counts + 1;
-    e.rt_segment0 = (int)segments;
-    return launch_sort_pick(EnsemblePick{e, (int)segments}, e.vals, e.S_pad, (int)segments, a.sort_scratch, a.sort_scratch_doubles, st);
-}
-
-}  // namespace sepaihrd
-
-// ---- scores of the posterior predictive draws (sepaihrd_ensemble_predictive_scores): the quantiles above
-// and, from the same sorted segment, the scoring rules of csrc/sepaihrd_predictive_score.inc for every cell of the three daily
-// series.  A segment is sorted once: in LDS the workgroup that sorted it reduces its sums before it leaves, beyond the LDS sort a
-// workgroup per daily segment reads the radix sort's scratch ----
-namespace sepaihrd {
-namespace {
-
-// what the kernels below take by value: the cells, the draw count and where the scores go
-struct ScoreCells {
-    int cells, Tp, n, L;     // 3 Tp n daily segments come first in the segment table
-    const int32_t* counts;   // PredictiveArgs::counts: [1] = draws per segment
-    const double* obs;       // [cells]
-    const double* levels;    // [L]
-    double* cell_scores;     // [cells][5 + 4 L]
-    double* pit_out;         // [cells] or null
-    int32_t* exact;
-    double* summary;         // [3][n + 1][4 + 2 L]
-};
-
-constexpr int SCORE_MAX_WAVES = 16;                       // of a 1024-lane workgroup
-constexpr int SCORE_SUMS = 6;                             // S1, S2, S_less, G, n_less, n_eq
-constexpr size_t SCORE_RED_BYTES = SCORE_MAX_WAVES * SCORE_SUMS * sizeof(double);  // 768: the cross-wave step
-
-// v of lane + off added down to lane 0 of the wave; lanes past `active` (a workgroup of 32 lanes is half a wave) add nothing
-template <class T>
-__device__ __forceinline__ T wave_sum(T v, const int lane, const int active) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) {
-        const T o = __shfl_down(v, off, WAVE);
-        if (lane + off < active) v += o;
-    }
-    return v;
-}
-
-// The sums of sorted segment `seg` (LDS or device memory; m valid draws first) against the cell's observation, reduced by the
-// whole workgroup -- lane-strided reads of consecutive doubles: conflict-free in LDS, coalesced in device memory -- then the cell
-// rule by one lane.  Every partial sum is a sum of integers and exact below 2^53, so the shape of the reduction does not show;
-// where sums_exact fails the cell says so in *exact.  red: SCORE_RED_BYTES of LDS.
-__device__ __forceinline__ void score_sorted_segment(const ScoreCells& sc, const size_t cell, const double* seg, double* red) {
-    const int tid = threadIdx.x, BS = blockDim.x;
-    const int m = sc.counts[1];
-    const double y = sc.obs[cell];
-    sepaihrd_score::SegmentSums s = {0, 0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = tid; i < m; i += BS) sepaihrd_score::add_draw(s, seg[i], i, m, y);
-    const int lane = tid % WAVE, wave = tid / WAVE;
-    const int active = (BS - wave * WAVE < WAVE) ? BS - wave * WAVE : WAVE;
-    const double S1 = wave_sum(s.S1, lane, active), S2 = wave_sum(s.S2, lane, active), S_less = wave_sum(s.S_less, lane, active),
-                 G = wave_sum(s.G, lane, active);
-    const int n_less = wave_sum((int)s.n_less, lane, active), n_eq = wave_sum((int)s.n_eq, lane, active);
-    if (lane == 0) {
-        double* r = red + wave * SCORE_SUMS;
-        r[0] = S1; r[1] = S2; r[2] = S_less; r[3] = G; r[4] = (double)n_less; r[5] = (double)n_eq;
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    double t[SCORE_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int waves = (BS + WAVE - 1) / WAVE;
-    for (int w = 0; w < waves; ++w)
-#pragma unroll
-        for (int k = 0; k < SCORE_SUMS; ++k) t[k] += red[w * SCORE_SUMS + k];
-    const sepaihrd_score::SegmentSums total = {(int64_t)t[4], (int64_t)t[5], t[0], t[1], t[2], t[3]};
-    sepaihrd_score::cell_rule(seg, (size_t)m, y, total, sc.levels, sc.L, sc.cell_scores + cell * (size_t)sepaihrd_score::cell_width(sc.L));
-    if (sc.pit_out != nullptr) sc.pit_out[cell] = sepaihrd_score::pit_of(total, (size_t)m, y);
-    if (m > 0 && !sepaihrd_score::sums_exact((size_t)m, seg[m - 1])) *sc.exact = 0;
-}
-
-// the sibling of segment_sort_pick_kernel<EnsemblePick>: one workgroup per segment of Np doubles sorts it in LDS and stores the
-// quantile picks; for a daily segment it then scores the segment still in LDS.  Dynamic LDS: Np doubles, then SCORE_RED_BYTES.
-__global__ void segment_sort_score_kernel(const EnsemblePick pick, const ScoreCells sc, const double* vals, const int Np) {
-    extern __shared__ double seg[];
-    const size_t sid = blockIdx.x;
-    lds_bitonic_sort(seg, vals + sid * (size_t)Np, Np);
-    for (int p = threadIdx.x; p < pick.picks(); p += blockDim.x) pick(sid, p, seg);
-    if (sid < (size_t)sc.cells) score_sorted_segment(sc, sid, seg, seg + Np);
-}
-
-// beyond the LDS sort: one workgroup per daily segment of a group the radix sort has left in `sorted`
-constexpr int SCORE_SORTED_BLOCK = 256;
-__global__ __launch_bounds__(SCORE_SORTED_BLOCK) void segment_score_sorted_kernel(const ScoreCells sc, const double* sorted, const int Np,
-                                                                                  const int first_segment) {
-    __shared__ double red[SCORE_MAX_WAVES * SCORE_SUMS];
-    score_sorted_segment(sc, (size_t)first_segment + blockIdx.x, sorted + (size_t)blockIdx.x * Np, red);
+    e.rt_segment0 = segments;
+    return EnsemblePick{e, segments};
 }
 
 // the observations of every daily cell as predictive_pit_kernel reads them from the context's grid
@@ -919,65 +717,36 @@ __global__ __launch_bounds__(256) void score_observed_kernel(const PredictiveArg
 // One lane per (series, age or pooled, field): the walk of csrc/sepaihrd_predictive_score.inc over the cell scores in its stated
 // order, the sum in a register.  A lane per field instead of one per entry: an entry's 4 + 2 L sums are independent chains of
 // additions, and a lane that carried them all would serve each in turn.
-__global__ __launch_bounds__(WAVE) void score_summary_kernel(const ScoreCells sc) {
+__global__ __launch_bounds__(WAVE) void score_summary_kernel(const ScoreArgs sc, const int Tp, const int n, double* summary) {
     const int SW = sepaihrd_score::summary_width(sc.L);
     const int idx = (int)(blockIdx.x * (unsigned)WAVE + threadIdx.x);
-    if (idx >= 3 * (sc.n + 1) * SW) return;
+    if (idx >= 3 * (n + 1) * SW) return;
     const int e = idx / SW, f = idx % SW;
-    sc.summary[idx] = sepaihrd_score::summary_field(sc.cell_scores, sc.obs, (size_t)sc.counts[1], sc.Tp, sc.n, sc.L, e / (sc.n + 1), e % (sc.n + 1), f);
+    summary[idx] = sepaihrd_score::summary_field(sc.scores, sc.obs, (size_t)sc.counts[1], Tp, n, sc.L, e / (n + 1), e % (n + 1), f);
 }
 
 }  // namespace
 
+int launch_predictive_quantiles(const PredictiveArgs& a, void* stream) {
+    if (!predictive_segments_ok(a)) return -4;
+    return launch_sort_pick(predictive_pick(a), a.vals, a.N_pad, 6 * a.Tp * a.n, a.sort_scratch, a.sort_scratch_doubles,
+                            static_cast<hipStream_t>(stream));
+}
+
 int launch_predictive_scores(const PredictiveArgs& a, const PredictiveScoreArgs& sa, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t segments = (size_t)6 * a.Tp * a.n;
-    if (a.S <= 0 || a.R <= 0 || segments >= ((size_t)1 << 31) || !pad_legal((size_t)a.S * a.R, a.N_pad)) return -4;
-    if (sa.n_levels < 0 || sa.n_levels > sepaihrd_score::MAX_LEVELS || !sa.obs || !sa.cell_scores || !sa.summary || !sa.exact ||
-        (sa.n_levels > 0 && !sa.levels))
+    if (!predictive_segments_ok(a) || sa.n_levels < 0 || sa.n_levels > sepaihrd_score::MAX_LEVELS || !sa.obs || !sa.cell_scores || !sa.summary ||
+        !sa.exact || (sa.n_levels > 0 && !sa.levels))
         return -4;
-    EnsembleArgs e{};
-    e.S = a.S * a.R; e.S_pad = a.N_pad; e.lpc = a.lpc; e.n = a.n; e.T = a.T; e.Tp = a.Tp;
-    e.n_probs = a.n_probs; e.probs = a.probs;
-    e.vals = a.vals; e.q_out = a.q_out;
-    e.n_valid = a.counts + 1;
-    e.rt_segment0 = (int)segments;
-    const EnsemblePick pick{e, (int)segments};
-    const int cells = 3 * a.Tp * a.n, pad = a.N_pad;
-    const ScoreCells sc{cells, a.Tp, a.n, sa.n_levels, a.counts, sa.obs, sa.levels, sa.cell_scores, sa.pit_out, sa.exact, sa.summary};
+    const int cells = 3 * a.Tp * a.n;  // the daily segments come first in the segment table
+    const ScoreArgs sc{cells, sa.n_levels, a.counts, sa.obs, sa.levels, sa.cell_scores, sa.pit_out, sa.exact};
     if (sa.obs_from_grid) hipLaunchKernelGGL(score_observed_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a, sa.obs);
-    const SegmentPlan plan = plan_of_pad((size_t)pad);
-    if (plan.in_lds && raise_lds_limit(plan, reinterpret_cast<const void*>(&segment_sort_score_kernel), SCORE_RED_BYTES) != 0) return -3;
-    const int rc = sort_segments_and_pick(
-        plan, (int)segments, a.vals, a.sort_scratch, a.sort_scratch_doubles, st, nullptr,
-        [&](int threads, size_t lds) {
-            hipLaunchKernelGGL(segment_sort_score_kernel, dim3((unsigned)segments), dim3(threads), lds + SCORE_RED_BYTES, st, pick, sc, a.vals, pad);
-        },
-        [&](int first, int ng) {
-            constexpr int BLOCK = EnsemblePick::SORTED_BLOCK;
-            const size_t work = (size_t)ng * pick.picks();
-            hipLaunchKernelGGL(segment_pick_sorted_kernel<EnsemblePick>, dim3((unsigned)((work + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, pick,
-                               a.sort_scratch, pad, first, ng);
-            const int daily = (first + ng < cells ? first + ng : cells) - first;  // the group's segments that are daily cells
-            if (daily > 0)
-                hipLaunchKernelGGL(segment_score_sorted_kernel, dim3((unsigned)daily), dim3(SCORE_SORTED_BLOCK), 0, st, sc, a.sort_scratch, pad,
-                                   first);
-        });
+    const int rc = launch_sort_pick_score(predictive_pick(a), sc, a.vals, a.N_pad, 2 * cells, a.sort_scratch, a.sort_scratch_doubles, st);
     if (rc != 0) return rc;
     const int fields = 3 * (a.n + 1) * sepaihrd_score::summary_width(sa.n_levels);
-    hipLaunchKernelGGL(score_summary_kernel, dim3((unsigned)((fields + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, sc);
+    hipLaunchKernelGGL(score_summary_kernel, dim3((unsigned)((fields + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, sc, a.Tp, a.n, sa.summary);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace sepaihrd
 
-// ---- sort_segments_global for csrc/sepaihrd_predictive_targets.hip, whose sorted kernels are its own ----
-namespace sepaihrd {
-
-int sort_segments_global_for(const double* vals, int segments, int S_pad, double* scratch, size_t scratch_doubles, void* stream,
-                             const std::function<void(int, int)>& pick) {
-    return sort_segments_global(vals, segments, S_pad, scratch, scratch_doubles, static_cast<hipStream_t>(stream),
-                                [&](int first, int ng) { pick(first, ng); });
-}
-
-}  // namespace sepaihrd

@@ -11,7 +11,7 @@
 //   * lambda >= 10: Hoermann's transformed rejection with squeeze, PTRS (PAPERS.md), everything in double.
 // Every log / exp is glibc_log / glibc_exp, every other operation a correctly rounded IEEE one, an fma only where written
 // (both sides compile with contraction off): the host twin and the device agree bit for bit.
-// Included by csrc/sepaihrd_predictive.hip and by the host library (host/src/HipPosteriorPredictive.cpp).
+// Included by csrc/sepaihrd_predictive.hip (the probe), through csrc/sepaihrd_nb_draw.inc by the draw kernels, and by the host library (host/src/HipPosteriorPredictive.cpp).
 #pragma once
 #include "sepaihrd_stoch.inc"
 

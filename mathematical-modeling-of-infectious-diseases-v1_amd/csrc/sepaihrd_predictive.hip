@@ -1,7 +1,8 @@
-// csrc/sepaihrd_predictive.hip -- posterior predictive draws with Poisson noise on gfx950 (sepaihrd_ensemble_predictive;
-// DESIGN.md section 6i): the draw kernel over the integrator's parked increments, the mid-PIT counts and the probe of the
-// Poisson sampler.  The sampler is csrc/sepaihrd_poisson.inc, the text the host twin compiles too; the segment sorts and the
-// quantiles are csrc/sepaihrd_ensemble.hip's.  Compiled with -ffp-contract=off.
+// csrc/sepaihrd_predictive.hip -- what every posterior predictive call on gfx950 runs around its draw kernel
+// (sepaihrd_ensemble_predictive and its dispersed and scored forms): the counts of valid samples and the
+// mid-PIT counts, with the argument rules and the probe of the Poisson sampler.  That sampler is csrc/sepaihrd_poisson.inc, the
+// text the host twin compiles too; the draw kernel is csrc/sepaihrd_predictive_nb.hip's (the Poisson draw is its k = +inf), the
+// segment sorts and the quantiles are csrc/sepaihrd_ensemble.hip's.  Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,46 +33,6 @@ __global__ __launch_bounds__(256) void predictive_count_kernel(const int32_t* ws
         __syncthreads();
     }
     if (threadIdx.x == 0) { counts[0] = part[0]; counts[1] = part[0] * R; }
-}
-
-// One lane per (sample s, replicate r), consecutive lanes along s R + r: the loads of a sample's increments are broadcasts,
-// the stores into a segment contiguous.  The lane walks the ages and, per age, the output times >= 0 in time order:
-// m = max(0, increment), y ~ Poisson(m + 1e-10) at stream coordinates (s, r, (series Tp + time) n + age), series 3 .. 5
-// the running sums of y (exact integers in double).
-__global__ __launch_bounds__(DRAW_BLOCK) void predictive_draw_kernel(const PredictiveArgs a) {
-    const size_t idx = (size_t)blockIdx.x * DRAW_BLOCK + threadIdx.x;
-    if (idx >= (size_t)a.N_pad) return;
-    const size_t s = idx / (size_t)a.R;
-    const uint32_t r = (uint32_t)(idx % (size_t)a.R);
-    const bool in_range = s < (size_t)a.S;
-    const bool ok = in_range && a.wstatus[s] == 0;
-    const size_t seg_stride = (size_t)a.N_pad;
-    // series order: daily H, daily ICU, daily D; cum rows are D, CumH, CumICU
-    const int comp_of[3] = {1, 2, 0};
-    for (int age = 0; age < a.n; ++age) {
-        const size_t col = s * (size_t)a.lpc + (size_t)age;
-        double run[3] = {0.0, 0.0, 0.0};
-        for (int t = 0; t < a.Tp; ++t) {
-#pragma unroll
-            for (int ser = 0; ser < 3; ++ser) {
-                const size_t cell = ((size_t)ser * a.Tp + t) * a.n + age;
-                double m = NAN, y = INFINITY, cumulative = INFINITY;
-                if (ok) {
-                    const double inc = a.cum[cum_index(a.T, col, a.runup_offset + t, comp_of[ser])];
-                    m = (0.0 < inc) ? inc : 0.0;  // std::max(0.0, cur - prev)
-                    y = sepaihrd_poisson::poisson(a.seed, (uint32_t)s, r, (uint32_t)cell, m + 1e-10);
-                    run[ser] += y;
-                    cumulative = run[ser];
-                }
-                a.vals[cell * seg_stride + idx] = y;
-                a.vals[(cell + (size_t)3 * a.Tp * a.n) * seg_stride + idx] = cumulative;
-                if (in_range) {
-                    if (a.means != nullptr && r == 0) a.means[((s * 3 + ser) * a.Tp + t) * a.n + age] = m;
-                    if (a.draws != nullptr) a.draws[((idx * 3 + ser) * a.Tp + t) * a.n + age] = ok ? y : (double)NAN;
-                }
-            }
-        }
-    }
 }
 
 // One workgroup per cell of the three daily series: the draws below and at the observation, counted before the sort (the
@@ -116,19 +77,6 @@ __global__ __launch_bounds__(DRAW_BLOCK) void poisson_probe_kernel(uint64_t seed
 
 }  // namespace
 
-int launch_predictive_draws(const PredictiveArgs& a, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a.S <= 0 || a.R <= 0 || a.n <= 0 || a.Tp <= 0 || (size_t)a.S * a.R > (size_t)a.N_pad || a.N_pad % WAVE != 0 ||
-        (uint64_t)3 * a.Tp * a.n >= ((uint64_t)1 << 32))
-        return -4;
-    hipLaunchKernelGGL(predictive_count_kernel, dim3(1), dim3(256), 0, st, a.wstatus, a.S, a.R, a.counts);
-    hipLaunchKernelGGL(predictive_draw_kernel, dim3((unsigned)((a.N_pad + DRAW_BLOCK - 1) / DRAW_BLOCK)), dim3(DRAW_BLOCK), 0, st, a);
-    if (a.pit_out != nullptr)
-        hipLaunchKernelGGL(predictive_pit_kernel, dim3((unsigned)((size_t)3 * a.Tp * a.n)), dim3(256), 0, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// the same two kernels around another draw kernel (csrc/sepaihrd_predictive_nb.hip)
 int launch_predictive_counts(const PredictiveArgs& a, void* stream) {
     hipLaunchKernelGGL(predictive_count_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a.wstatus, a.S, a.R, a.counts);
     return hipGetLastError() == hipSuccess ? 0 : -3;

@@ -1,5 +1,6 @@
-// csrc/sepaihrd_predictive_device.h -- what csrc/sepaihrd_capi.cpp (sepaihrd_ensemble_predictive), csrc/sepaihrd_predictive.hip
-// (the draw kernel, the mid-PIT counts) and csrc/sepaihrd_ensemble.hip (the segment sorts and the quantiles) share.
+// csrc/sepaihrd_predictive_device.h -- what csrc/sepaihrd_capi.cpp (sepaihrd_ensemble_predictive and its dispersed and scored
+// forms), csrc/sepaihrd_predictive.hip (the counts, the mid-PIT counts), csrc/sepaihrd_predictive_nb.hip (the dispersions, the draw
+// kernel) and csrc/sepaihrd_ensemble.hip (the segment sorts, the quantiles and the scores) share.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,17 +28,21 @@ struct PredictiveArgs {
     double* sort_scratch;      // as EnsembleArgs
     size_t sort_scratch_doubles;
 };
-// counts, the draws into vals / means / draws, and the mid-PIT of every usable observation (csrc/sepaihrd_predictive.hip)
-int launch_predictive_draws(const PredictiveArgs& a, void* stream);
-// The dispersed call's form of it (csrc/sepaihrd_predictive_nb.hip): the dispersion of every sample into
-// d_k_used [S][3] (sepaihrd_nb_ll_rows_kernel's rule; a sample with a NaN k becomes a failed one in d_wstatus = a.wstatus), then
-// the counts, the negative-binomial draws -- one lane per (draw, age, series) -- and the mid-PIT.  0, -3 (launch failure), -4.
+// The steps of a draw phase, in the order sepaihrd_capi.cpp's predictive_call issues them.  Each returns 0, -3 (launch failure)
+// or -4 (arguments).
+// 1. the dispersed calls only (csrc/sepaihrd_predictive_nb.hip): the dispersion of every sample into d_k_used
+//    [S][3] (sepaihrd_nb_ll_rows_kernel's rule; a sample with a NaN k becomes a failed one in d_wstatus = a.wstatus)
 struct DevProblem;
 struct NbDispersion;
-int launch_predictive_draws_nb(const PredictiveArgs& a, const DevProblem& pb, const double* d_theta, const NbDispersion& disp, double* d_k_used,
-                               int32_t* d_wstatus, void* stream);
-// its parts that are csrc/sepaihrd_predictive.hip's own kernels: the counts before the draws, the mid-PIT (where a.pit_out) after
+int launch_predictive_nb_k(const PredictiveArgs& a, const DevProblem& pb, const double* d_theta, const NbDispersion& disp, double* d_k_used,
+                           int32_t* d_wstatus, void* stream);
+// 2. the counts of valid samples and draws (csrc/sepaihrd_predictive.hip)
 int launch_predictive_counts(const PredictiveArgs& a, void* stream);
+// 3. the draws into vals / means / draws, one lane per (draw, age, series) (csrc/sepaihrd_predictive_nb.hip): negative-binomial
+//    with the dispersions of d_k_used, Poisson where it is null -- or launch_predictive_target_draws
+//    (sepaihrd_predictive_targets_device.h)
+int launch_predictive_draws(const PredictiveArgs& a, const double* d_k_used, void* stream);
+// 4. where a.pit_out: the mid-PIT of every usable observation from the unsorted daily table (csrc/sepaihrd_predictive.hip)
 int launch_predictive_pit(const PredictiveArgs& a, void* stream);
 // the quantiles of every segment with the ensemble's sorts and interpolation (csrc/sepaihrd_ensemble.hip)
 int launch_predictive_quantiles(const PredictiveArgs& a, void* stream);

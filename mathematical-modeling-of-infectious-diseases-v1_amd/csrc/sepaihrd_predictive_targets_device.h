@@ -1,10 +1,8 @@
 // csrc/sepaihrd_predictive_targets_device.h -- what csrc/sepaihrd_capi.cpp (sepaihrd_ensemble_predictive_targets) and
-// csrc/sepaihrd_predictive_targets.hip share, and the two launchers that unit borrows from its neighbours.
+// csrc/sepaihrd_predictive_targets.hip share.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-
-#include <functional>
 
 #include "sepaihrd_predictive_device.h"
 
@@ -31,19 +29,10 @@ struct PredictiveTargetArgs {
     double* target_draws;       // [S][R][3][W][G] device or null
     int32_t* exact;             // [1] device, 1 on entry
 };
-// the table zeroed, then the draws of sepaihrd_ensemble_predictive_scores summed into it (a.counts and k_used must be ready:
-// launch_predictive_nb_k, launch_predictive_counts), and target_draws gathered from it where wanted.  0, -3, -4.
+// Step 3 of a draw phase (sepaihrd_predictive_device.h) for the targets: the table zeroed, then the draws of
+// sepaihrd_ensemble_predictive_scores summed into it, and target_draws gathered from it where wanted.  0, -3, -4.
 int launch_predictive_target_draws(const PredictiveArgs& a, const PredictiveTargetArgs& t, const double* d_k_used, void* stream);
 // the observed targets, every segment sorted once with its quantile picks and scores, and the summary walk.  0, -3, -4.
 int launch_predictive_target_scores(const PredictiveArgs& a, const PredictiveTargetArgs& t, void* stream);
-
-// csrc/sepaihrd_predictive_nb.hip: the first step of launch_predictive_draws_nb alone, every sample's dispersion into d_k_used
-// (a sample with a NaN k becomes a failed one in d_wstatus)
-int launch_predictive_nb_k(const PredictiveArgs& a, const DevProblem& pb, const double* d_theta, const NbDispersion& disp, double* d_k_used,
-                           int32_t* d_wstatus, void* stream);
-// csrc/sepaihrd_ensemble.hip: its sort_segments_global (the segmented radix sort of segments beyond the LDS sort, in groups that fit
-// the scratch) for a caller outside that unit; pick(first, n_group) launches what reads each sorted group from `scratch`
-int sort_segments_global_for(const double* vals, int segments, int S_pad, double* scratch, size_t scratch_doubles, void* stream,
-                             const std::function<void(int, int)>& pick);
 
 }  // namespace sepaihrd

@@ -1,6 +1,6 @@
 // csrc/sepaihrd_segments.h -- how the ensemble entry points pad and sort their segments.  Host only, no HIP type: the one
 // statement of the rule for the C ABI code that sizes the buffers (sepaihrd_capi.cpp, sepaihrd_sir_capi.cpp,
-// sepaihrd_stoch_sir.hip) and for the launchers that check what they are handed (sepaihrd_ensemble.hip).
+// sepaihrd_stoch_sir.hip) and for the launchers that check what they are handed (sepaihrd_segment_sort.inc and its includers).
 //
 // A segment holds `count` values of one (series, time, age) cell, one per sample or replicate, padded with +inf to `pad`:
 //   count <= ENSEMBLE_MAX_SAMPLES   pad = the power of two >= max(count, 64); one workgroup sorts the segment in LDS

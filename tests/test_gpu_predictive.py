@@ -33,7 +33,7 @@ def _check_against_twin(mm, pb, got, R, seed=SEED, probs=PROBS):
     return twin
 
 
-@pytest.mark.parametrize("name,S,R,fma", [("ref", 1, 64, False), ("ref", 37, 3, False), ("shipped", 5, 3, False), ("shipped", 37, 1, False),
+@pytest.mark.parametrize("name,S,R,fma", [("ref", 1, 64, False), ("ref", 37, 3, False), ("ref", 37, 7, False), ("shipped", 5, 3, False), ("shipped", 37, 1, False),
                                           ("shipped", 5, 3, True), ("wide", 1, 3, False), ("wide", 5, 64, False)])
 def test_device_equals_twin(mm, shipped, ref_fixture, name, S, R, fma):
     pb, mode = _problem(mm, name, shipped, ref_fixture)
